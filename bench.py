@@ -17,6 +17,10 @@ region and the reduction of the ranks' counts run over gloo: the whole-job figur
 warm-up is flushed before the clock starts and the K timed steps are flushed before it stops, so every sample of
 the K steps — `samples` = K * spp * pixels, and all their rays — is computed inside the timed region.
 
+A plain run sets up, warms up, times the K steps, writes their outputs with --dump-outputs DIR (dump_outputs) and prints
+the line.  --full adds, after the timed steps, what the headline figure does not need: the side runs with the other walks,
+parity_check, cpu_baseline and the extras below (N = 1 only).
+
 value = (primary + secondary rays traced by all ranks in the K timed steps) / max-over-ranks wall time, Mray/s.
         A ray = one hitBVH query (PathTrace.cu:795).
 rooflines: the dominant kernel, k_trace (BVH traversal + triangle tests), against the three resources a traversal without
@@ -32,8 +36,9 @@ rooflines: the dominant kernel, k_trace (BVH traversal + triangle tests), agains
         figures belong to a build: profiles/k_trace_counters.json carries a hash of csrc/ and the fractions are null when
         the tree's differs (a kernel edit without re-profiling must not keep the old numbers).
         `algorithmic`: SURVEY.md 8d's 40 B per node record + 36 B per triangle test, per kernel (V and T are counted
-        separately for k_light and k_trace); it exceeds the HBM peak when the scene is cache-resident, which is why it is
-        reported beside the rooflines and not as one.
+        separately for k_light and k_trace; k_trace's V and T are the reference walk's side run's under --full, the timed
+        walk's own without it); it exceeds the HBM peak when the scene is cache-resident, which is why it is reported beside
+        the rooflines and not as one.
 parity_check: the frame this run rendered (every sample of warm-up + timed steps) against the oracle on a few of its
         16x16 tiles - statue, mirror floor, sky - at the full sample count: relative L2 of the radiance, largest BGR8
         difference.  Outside the timed region; part of the cpu_baseline leg (the oracle is the checker, never the product).
@@ -99,7 +104,16 @@ def parse():
                     help="jade_render_params.walk = JADE_WALK_REFERENCE in the timed region: every query walks what the reference walks "
                          "(the default, JADE_WALK_EARLY_EXIT, ends shadow / environment-visibility walks at the hit that settles them: the same frame, bit for bit)")
     ap.add_argument("--parity-rays", type=float, default=1.2e8, help="oracle rays the parity check may cost (about 7 Mray/s on 16 cores)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the side runs with the other walks, the close-up and "
+                         "glass-statue variants, the CPU baseline and the oracle parity check (--no-extras / --no-cpu-baseline / "
+                         "--no-parity-check drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/*.npy (dump_outputs: the frame and its ray counts)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(n):
@@ -295,11 +309,12 @@ def main():
     gather_ms = (time.perf_counter() - g0) * 1e3
     if world == 1 and part_world == 1:
         frame = D.gather_framebuffer(tiles, width, height)
-    frame_ok, frame_sha = True, None
+    frame_ok, frame_sha, frame_np = True, None, None
     if rank == 0 and frame is not None:
         frame_ok = bool(torch.isfinite(frame).all().item()) and tuple(frame.shape) == (height, width, 3)
         import hashlib
-        frame_sha = hashlib.sha256(frame.detach().cpu().contiguous().numpy().tobytes()).hexdigest()[:32]  # the gathered linear frame, bit for bit
+        frame_np = frame.detach().cpu().contiguous().numpy()
+        frame_sha = hashlib.sha256(frame_np.tobytes()).hexdigest()[:32]  # the gathered linear frame, bit for bit
 
     cls_keys = ("rays_primary", "rays_shadow", "rays_env", "rays_indirect", "rays_mirror", "rays_refract")
     vals = torch.tensor([float(st.rays_primary + st.rays_secondary), float(st.nodes_visited), float(st.tris_tested),
@@ -312,8 +327,14 @@ def main():
     dt = float(tmax.item())
     rays_all = float(vals[0].item())
 
+    if rank == 0 and args.dump_outputs:
+        if frame_np is None:  # --virtual-ranks: this rank's share of the frame, the other ranks' tiles left zero
+            frame_np = B.assemble_tiles(tiles.cpu().numpy(), width, height, part_rank, part_world)
+        dump_outputs(args.dump_outputs, frame_np, vals[[0, 5] + list(range(6, 6 + len(cls_keys)))].numpy())
+
+    full = args.full and rank == 0 and world == 1   # the side measurements and checks of --full (one rank, after the timed steps)
     parity_frame = None
-    if rank == 0 and world == 1 and part_world == 1 and not args.no_cpu_baseline and not args.no_parity_check:
+    if full and part_world == 1 and not args.no_cpu_baseline and not args.no_parity_check:
         parity_frame = scene.resolve()   # (rgb, bgr8) of the frame the timed region finished: host copies, outside the clock
     # The same steps with the other walks, outside the timed region and with the SAME step and warm-up counts (a side run
     # of two steps weighs its flush differently): the reference's walk - what the early exits are worth, and the V / T per ray of the
@@ -344,7 +365,7 @@ def main():
                 "what": what}
 
     ref_walk = early_walk = None
-    if rank == 0 and world == 1 and not args.no_extras:
+    if full and not args.no_extras:
         if walk != _abi.WALK_REFERENCE:
             ref_walk = side_run(_abi.WALK_REFERENCE, "this rank's share of the frame, same steps and warm-up as the timed region, jade_render_params.walk = "
                                 "JADE_WALK_REFERENCE (nodes_visited / tris_tested equal the oracle's); the flush inside its clock, outside the timed region")
@@ -425,6 +446,8 @@ def main():
             "Mray_per_s_of_this_kernel": rays_rank / trace_s / 1e6 if trace_s > 0 else None,
             "algorithmic_bytes_per_launch": alg_trace / launches,
             "algorithmic_GBps": alg_trace / trace_s / 1e9 if trace_s > 0 else None,
+            # whose V and T priced the algorithmic bytes: the reference walk's side run (--full), else this run's own walk
+            "algorithmic_walk": "reference" if ref_walk is not None else walk_name,
             "counters_build": ctr_file.get("csrc_sha"), "tree_build": tree_sha,
             "counters_stale": ("profiles/k_trace_counters.json was cut from another build of csrc/ (%s, tree %s): fractions withheld"
                                % (ctr_file.get("csrc_sha"), tree_sha)) if stale else None})
@@ -448,7 +471,7 @@ def main():
                 "bvh_nodes": hs.n_nodes, "bvh_depth": hs.bvh_depth, "parallelism": f"tiles{world}",
                 "walk": walk_name,
             },
-            # the same steps with every query walked to the end as the reference does (null with --reference-walk / --no-extras)
+            # the same steps with every query walked to the end as the reference does (null without --full, or with --reference-walk / --no-extras)
             "reference_walk": ref_walk,
             "value_reference_walk": ref_walk["value"] if ref_walk else (None if walk != _abi.WALK_REFERENCE else rays_all / dt / 1e6),
             # ... and with early exits but no occluder cache (null unless the timed region ran with the cache)
@@ -502,11 +525,11 @@ def main():
             # the resource with the largest share of its roof (null when the counter file belongs to another build)
             "binding": roof["bound"] if roof.get("frac") is not None else None,
         }
-        if world == 1 and part_world == 1 and not args.no_extras and args.config in ("C2", "C3", "C4"):
+        if full and part_world == 1 and not args.no_extras and args.config in ("C2", "C3", "C4"):
             out["statue_closeup"] = closeup(scene, hip, B, H, _abi, cfg, width, height, args.spp_per_step, walk)
-        if world == 1 and part_world == 1 and not args.no_extras and args.config in ("C3", "C4"):
+        if full and part_world == 1 and not args.no_extras and args.config in ("C3", "C4"):
             out["glass_statue"] = glass_statue(hip, J, B, _abi, width, height, args.spp_per_step, walk, check=not args.no_cpu_baseline)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(hs, cfg, width, height, args.cpu_spp)
             if parity_frame is not None:
                 out["parity_check"] = parity_check(hs, cfg, width, height, int(params.spp), parity_frame, args.parity_rays)
@@ -514,6 +537,34 @@ def main():
     scene.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 << 20   # --dump-outputs writes at most this much (under 64 MB with the .npy headers)
+DUMP_COUNTERS = ("rays", "samples", "rays_primary", "rays_shadow", "rays_env", "rays_indirect", "rays_mirror", "rays_refract")
+
+
+def dump_outputs(out_dir, frame, counters):
+    """--dump-outputs: what the timed steps computed, for comparing two builds output for output (the inputs are the same on
+    every run with the same arguments: the scene is built by the host pipeline, every sample's random stream is seeded by its
+    pixel and index, jade_rt.h).
+      radiance.npy  float32 [H, W, 3]: the linear frame after warm-up + timed steps, as gathered on rank 0.  A frame larger than
+                    the budget is written as a fixed, seeded sample of its pixels instead: radiance_sample.npy float32 [k, 3] holds
+                    pixels radiance_sample_index.npy (float64, row-major y * W + x) of the frame.
+      counters.npy  float64 [8]: DUMP_COUNTERS of the timed steps, summed over the ranks."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    frame = np.ascontiguousarray(frame, np.float32)
+    counters = np.asarray(counters, np.float64)
+    assert counters.shape == (len(DUMP_COUNTERS),)
+    if frame.nbytes + counters.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(out_dir, "radiance.npy"), frame)
+    else:
+        pixels = frame.reshape(-1, 3)
+        k = (DUMP_BYTES - counters.nbytes) // (pixels.itemsize * 3 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(pixels), size=k, replace=False))
+        np.save(os.path.join(out_dir, "radiance_sample.npy"), pixels[idx])
+        np.save(os.path.join(out_dir, "radiance_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "counters.npy"), counters)
 
 
 def closeup(scene, hip, B, H, _abi, cfg, width, height, spp, walk):

@@ -28,6 +28,28 @@ def test_counter_file_belongs_to_the_tree():
         assert e["valu_lane_ops_per_ray"] > 0 and e["l2_requests_per_ray"] > 0 and e["hbm_bytes_per_ray"] > 0 and e["fetch_size_factor"] == 1.0
 
 
+def test_dump_outputs_fit_the_budget_and_repeat(tmp_path, monkeypatch):
+    """--dump-outputs: a frame within the budget is written whole; a larger one as the same seeded sample of its pixels on every
+    call, with their row-major indices; the counters beside it.  Float32 / float64 only, under the budget in all."""
+    import numpy as np
+    frame = np.random.default_rng(1).random((40, 56, 3), dtype=np.float32)
+    ctr = np.arange(len(bench.DUMP_COUNTERS), dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), frame, ctr)
+    assert sorted(os.listdir(tmp_path / "whole")) == ["counters.npy", "radiance.npy"]
+    assert np.array_equal(np.load(tmp_path / "whole" / "radiance.npy"), frame)
+    assert np.array_equal(np.load(tmp_path / "whole" / "counters.npy"), ctr)
+    monkeypatch.setattr(bench, "DUMP_BYTES", frame.nbytes // 2)
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / str(k)), frame, ctr)
+    d0, d1 = tmp_path / "0", tmp_path / "1"
+    assert sorted(os.listdir(d0)) == ["counters.npy", "radiance_sample.npy", "radiance_sample_index.npy"]
+    px, idx = np.load(d0 / "radiance_sample.npy"), np.load(d0 / "radiance_sample_index.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and px.shape == (len(idx), 3) and len(idx) > 0
+    assert np.array_equal(px, frame.reshape(-1, 3)[idx.astype(np.int64)]) and np.all(np.diff(idx) > 0)
+    assert px.nbytes + idx.nbytes + ctr.nbytes <= bench.DUMP_BYTES
+    assert all(np.array_equal(np.load(d0 / n), np.load(d1 / n)) for n in os.listdir(d0))
+
+
 def test_issue_roof_is_the_calibrated_one():
     """bench.py's `valu_issue` roof (one wave64 instruction per SIMD per 4 clocks) is a measurement, not a reading of the guide:
     profiles/valu_calibration.json holds tools/calib/valu_calib's runs - every instruction kind but unpacked fp32 add / mul / fma and

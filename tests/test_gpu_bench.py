@@ -20,9 +20,9 @@ def test_device_tiles_feed_the_gather():
 
 
 def test_bench_json_contract():
-    """One tiny bench run: the single JSON line the driver parses, with roofline and cpu_baseline objects."""
+    """One tiny bench run with --full: the single JSON line the driver parses, with roofline and cpu_baseline objects."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "tinyjade", "--width", "96", "--height", "64",
-           "--spp-per-step", "16", "--steps", "2", "--warmup", "1", "--cpu-spp", "1"]
+           "--spp-per-step", "16", "--steps", "2", "--warmup", "1", "--cpu-spp", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -70,12 +70,32 @@ def test_bench_with_the_occluder_cache():
     """bench.py --walk cached: JADE_WALK_EARLY_EXIT_CACHED in the timed region, both other walks beside it; the frame is checked
     against the oracle like any other (parity_check)."""
     d = _bench_line(["--config", "tinyjade", "--width", "96", "--height", "64", "--spp-per-step", "16", "--steps", "2", "--warmup", "1",
-                     "--cpu-spp", "1", "--walk", "cached"])
+                     "--cpu-spp", "1", "--walk", "cached", "--full"])
     rw, ew, oc = d["reference_walk"], d["early_exit_walk"], d["occluder_cache"]
     assert d["config"]["walk"] == "cached" and rw["value"] > 0 and ew["value"] > 0 and d["value_early_exit_walk"] == ew["value"]
     assert rw["nodes_per_ray_k_trace"] >= ew["nodes_per_ray_k_trace"] and rw["tris_per_ray_k_trace"] >= ew["tris_per_ray_k_trace"]
     assert 0 <= oc["answered"] <= d["rays_by_call_site"]["shadow"] + d["rays_by_call_site"]["env"] and 0 <= oc["share_of_shadow_and_env_rays"] <= 1
     assert d["parity_check"]["ok"] is True
+
+
+def test_plain_bench_is_lean_and_dumps_what_it_computed(tmp_path):
+    """Without --full the line carries the headline and none of the side measurements; --dump-outputs writes the frame the timed
+    steps finished (the one frame_sha256 hashes) and their ray counts, the same on every run with the same arguments."""
+    import hashlib
+    import numpy as np
+    args = ["--config", "tinyjade", "--width", "96", "--height", "64", "--spp-per-step", "16", "--steps", "3", "--warmup", "1"]
+    runs = []
+    for k in range(2):
+        d = _bench_line(args + ["--dump-outputs", str(tmp_path / str(k))])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["frame_ok"] is True
+        assert d["reference_walk"] is None and "cpu_baseline" not in d and "parity_check" not in d and "statue_closeup" not in d
+        rad, ctr = np.load(tmp_path / str(k) / "radiance.npy"), np.load(tmp_path / str(k) / "counters.npy")
+        assert rad.dtype == np.float32 and rad.shape == (64, 96, 3) and np.isfinite(rad).all()
+        assert hashlib.sha256(rad.tobytes()).hexdigest()[:32] == d["frame_sha256"]
+        assert ctr.dtype == np.float64 and ctr[0] == d["rays"] and ctr[1] == d["samples"] == 3 * 16 * 96 * 64
+        assert list(ctr[2:]) == [d["rays_by_call_site"][c] for c in ("primary", "shadow", "env", "indirect", "mirror", "refract")]
+        runs.append((rad, ctr))
+    assert np.array_equal(runs[0][0].view(np.uint32), runs[1][0].view(np.uint32)) and np.array_equal(runs[0][1], runs[1][1])
 
 
 def _bench_line(args, timeout=900, env=None):

@@ -35,16 +35,16 @@ case "$what" in
     tag=$1; shift; O="$R/gpurun_out/$tag"; mkdir -p "$O"
     timeout -k 10 900 python3 -m pytest ${@:-tests/test_gpu_early_exit.py tests/test_gpu_packet.py tests/test_gpu_parity.py} -m gpu -x -q > "$O/pytest.log" 2>&1; rc=$?
     tail -4 "$O/pytest.log"; [ $rc -eq 0 ] || { tail -80 "$O/pytest.log"; exit $rc; }
-    timeout -k 10 600 python3 bench.py > "$O/bench.json" 2> "$O/bench.err" && line "$O/bench.json" C3 || { tail -20 "$O/bench.err"; exit 1; }
-    timeout -k 10 600 python3 bench.py --config C5 --steps 2 --warmup 1 --spp-per-step 64 --no-cpu-baseline > "$O/c5_bench.json" 2> "$O/c5_bench.err" && line "$O/c5_bench.json" C5 || { tail -20 "$O/c5_bench.err"; exit 1; } ;;
+    timeout -k 10 600 python3 bench.py --full > "$O/bench.json" 2> "$O/bench.err" && line "$O/bench.json" C3 || { tail -20 "$O/bench.err"; exit 1; }
+    timeout -k 10 600 python3 bench.py --full --config C5 --steps 2 --warmup 1 --spp-per-step 64 --no-cpu-baseline > "$O/c5_bench.json" 2> "$O/c5_bench.err" && line "$O/c5_bench.json" C5 || { tail -20 "$O/c5_bench.err"; exit 1; } ;;
   bench)
     tag=$1; shift; O="$R/gpurun_out/$tag"; mkdir -p "$O"
-    timeout -k 10 900 python3 bench.py "$@" > "$O/bench.json" 2> "$O/bench.err" && line "$O/bench.json" "$tag" || { tail -20 "$O/bench.err"; exit 1; } ;;
+    timeout -k 10 900 python3 bench.py --full "$@" > "$O/bench.json" 2> "$O/bench.err" && line "$O/bench.json" "$tag" || { tail -20 "$O/bench.err"; exit 1; } ;;
   env)
     tag=$1; var=${2%%=*}; vals=${2#*=}; shift 2; O="$R/gpurun_out/$tag"; mkdir -p "$O"
     for v in ${vals//,/ }; do
       f=$(basename "$v")  # (a value may be a path: JADE_HIP_LIB=.../libjade_hip_x.so)
-      env "$var=$v" timeout -k 10 600 python3 bench.py --no-cpu-baseline "$@" > "$O/${var}_$f.json" 2> "$O/${var}_$f.err" && line "$O/${var}_$f.json" "$var=$f" || { tail -20 "$O/${var}_$f.err"; exit 1; }
+      env "$var=$v" timeout -k 10 600 python3 bench.py --full --no-cpu-baseline "$@" > "$O/${var}_$f.json" 2> "$O/${var}_$f.err" && line "$O/${var}_$f.json" "$var=$f" || { tail -20 "$O/${var}_$f.err"; exit 1; }
     done ;;
   profile)
     bash tools/profile_set.sh "$@" ;;
