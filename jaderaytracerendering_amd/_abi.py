@@ -130,7 +130,14 @@ RT_SYMBOLS = {
 # include/jade_bvh.h (exported by libjade_hip.so)
 _BVH_SIG = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32),
                       C.POINTER(C.c_double)])
-BVH_SYMBOLS = {"jade_bvh_build_lbvh": _BVH_SIG, "jade_bvh_build_ploc": _BVH_SIG}
+BVH_SYMBOLS = {
+    "jade_bvh_build_lbvh": _BVH_SIG,
+    "jade_bvh_build_ploc": _BVH_SIG,
+    # adaptive sampling and its noise map (scene, params, min_spp, rel_error, error_floor, rgb, bgr8, tile_spp, stats)
+    "jade_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.POINTER(Stats)]),
+    "jade_render_error": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+}
 
 HOST_SYMBOLS = {
     "jadeh_last_error": (C.c_char_p, []),

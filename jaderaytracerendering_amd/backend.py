@@ -100,6 +100,7 @@ class Scene:
         st = _abi.Stats()
         self.backend.check(self.backend.lib.jade_render(self._h, C.byref(params), rgb.ctypes.data if want_rgb else None,
                                                         bgr.ctypes.data if want_bgr8 else None, C.byref(st)))
+        self._params = params  # (jade_render is begin + step + resolve: the render stays readable, e.g. by error_map)
         return rgb, bgr, st
 
     # progressive form
@@ -129,6 +130,40 @@ class Scene:
         else:
             self.backend.check(self.backend.lib.jade_render_resolve_ex(self._h, int(tonemap), float(limit), pr, pb))
         return rgb, bgr
+
+    def _hip_only(self, name):
+        """An include/jade_bvh.h entry point: JadeError(JADE_ERR_UNSUPPORTED) on a backend without it (the oracle)."""
+        fn = getattr(self.backend.lib, name, None)
+        if fn is None:
+            raise JadeError(_abi.JADE_ERR_UNSUPPORTED, f"{self.backend.path} has no {name} (HIP module only)")
+        fn.restype, fn.argtypes = _abi.BVH_SYMBOLS[name]
+        return fn
+
+    def render_adaptive(self, params, min_spp, rel_error, error_floor=0.01, want_rgb=True, want_bgr8=True):
+        """jade_render_adaptive: params.spp is the cap; each 16x16 tile stops at the first of min_spp, 2 min_spp, ... whose tile
+        error is <= rel_error.  Returns (rgb | None, bgr8 | None, tile_spp int32 [tiles_y, tiles_x] (0 = not owned), Stats)."""
+        fn = self._hip_only("jade_render_adaptive")
+        h, w = params.height, params.width
+        ts = _abi.TILE_SIZE
+        rgb = np.zeros((h, w, 3), np.float32) if want_rgb else None
+        bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
+        tile_spp = np.zeros(((h + ts - 1) // ts, (w + ts - 1) // ts), np.int32)
+        st = _abi.Stats()
+        self.backend.check(fn(self._h, C.byref(params), int(min_spp), float(rel_error), float(error_floor),
+                              rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None,
+                              tile_spp.ctypes.data, C.byref(st)))
+        self._params = params
+        return rgb, bgr, tile_spp, st
+
+    def error_map(self, error_floor=0.01):
+        """jade_render_error: [H, W] float32 relative standard error of each pixel's mean luminance (include/jade_bvh.h) for the
+        render in progress; NaN on tiles this rank does not own and where the sample count cannot be estimated."""
+        fn = self._hip_only("jade_render_error")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        out = np.full((self._params.height, self._params.width), np.nan, np.float32)
+        self.backend.check(fn(self._h, float(error_floor), out.ctypes.data))
+        return out
 
     def query(self, what):
         """jade_render_query: what the backend holds for the current render (_abi.Q_*)."""

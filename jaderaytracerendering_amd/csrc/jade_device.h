@@ -150,7 +150,11 @@ struct PathState {
   int32_t nslots;
   uint4* hdr;           // [npix] what every pass of every record reads, one 16-B word: {rng: Wang-hash state of the sample in
                         // flight, done: samples this record has finished, stage | depth << 8 | flags << 16, 0}.  Read in record
-                        // order by k_light (coalesced); for k_shade, whose records are scattered, one sector instead of three
+                        // order by k_light (coalesced); for k_shade, whose records are scattered, one sector instead of three.
+                        // Stop offset (jade_render_adaptive): a record of a tile that has converged gets (1 << 21) << per_log2 added to
+                        // `done` (per_log2 = log2(JADE_SAMPLE_LANES / rpp)) while it is idle: its next sample index moves up by exactly
+                        // 2^31, above every int32 target without wrapping, so every `sidx < target_spp` test finds no work for it.
+                        // k_init clears it.
   int32_t sum_lanes;    // partial sums kept per pixel: min(JADE_SAMPLE_LANES, announced spp rounded up to a power of two) >= rpp
   float* sum;           // [sum_lanes * npx][3] partial radiance sums per (lane, pixel), RGB side by side; sample s adds into lane s % JADE_SAMPLE_LANES
   // The context of a path in flight, four float4 = one aligned 64-B sector per record (only k_shade and a record k_light parks

@@ -42,9 +42,15 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 
+#include "jade_bvh.h"
 #include "jade_device.h"
 #include "jade_shade.h"
 #include "jade_trace.h"
+
+// jade_adaptive.hip: k_tile_error's launch (jade_render_adaptive, jade_render_error)
+hipError_t adaptive_tile_error(hipStream_t stream, uint32_t n_tiles, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
+                               const uint32_t* list, const int32_t* tile_n, double error_floor, float rel_error, int32_t target,
+                               uint32_t* next_list, uint32_t* next_count, int32_t* tile_spp, float* err_out, uint32_t* not_idle);
 
 // ------------------------------------------------------------------ kernels --
 
@@ -122,7 +128,8 @@ struct NextSample {
 };
 // (m, home) = (p / npx, p % npx): where record p sits; computed once per thread, an integer division each.
 // rpp and JADE_SAMPLE_LANES are powers of two, so everything else is shifts — and the 64-bit modulo of the
-// pixel rotation only runs when rotation is on (it is not, by default).
+// pixel rotation only runs when rotation is on (it is not, by default).  A record of a tile that adaptive sampling has stopped carries
+// the stop offset in `done` (PathState.hdr): its sidx is 2^31 above its last sample's, past any target.
 static __device__ __forceinline__ NextSample next_sample_mh(const PathState& P, uint32_t m, uint32_t home, uint32_t done) {
   const uint32_t rpp_log2 = 31u - (uint32_t)__clz(P.rpp);
   const uint32_t per_log2 = (31u - (uint32_t)__clz(JADE_SAMPLE_LANES)) - rpp_log2;  // samples per record per block = LANES / rpp
@@ -1859,10 +1866,12 @@ __global__ void k_heavy_pack(const uint32_t* heavy_regions, uint32_t region_cap,
 }
 
 // ACESToneMapping + gamma + BGR pack, PathTrace.cu:680-682, 1457-1473.
-__global__ void k_resolve(PathState P, RenderConst R, const int32_t* tile_ids, float inv_spp, int tonemap, float limit,
+// tile_inv (nullable): 1 / samples of each owned tile, after jade_render_adaptive; otherwise every tile has inv_spp
+__global__ void k_resolve(PathState P, RenderConst R, const int32_t* tile_ids, const float* tile_inv, float inv_spp, int tonemap, float limit,
                           float* out_rgb, uint8_t* out_bgr) {
   int p = blockIdx.x * blockDim.x + threadIdx.x;  // owned pixel
   if (p >= P.npx) return;
+  if (tile_inv) inv_spp = tile_inv[p >> 8];
   int px_, py_;
   bool valid = pixel_xy(R, tile_ids, p, &px_, &py_);
   jvec3 m = jv(0, 0, 0);
@@ -2047,7 +2056,15 @@ struct jade_scene {
   double tail_ms = 0;         // k_tail device time since the last advance() reported it
   uint64_t tail_launches = 0, tail_records = 0;
   hipEvent_t ev_batch[2 * JADE_CTL_RING] = {};  // k_trace timing of a batch of passes
+  // adaptive sampling (jade_render_adaptive, jade_adaptive.hip): samples of each owned tile once the render has ended (empty: every
+  // tile has spp_done), their reciprocals for k_resolve, the rounds' active lists, per-tile counts and {count, not-idle} word
+  std::vector<int32_t> tile_n;
+  bool adaptive_done = false;  // jade_render_step refuses until the next begin
+  DevBuf b_tile_inv, b_tile_n, b_alist[2], b_actl, b_err;
+  hipEvent_t ev_err[2] = {};
   ~jade_scene() {
+    for (hipEvent_t e : ev_err)
+      if (e) (void)hipEventDestroy(e);
     if (ev_resolve) (void)hipEventDestroy(ev_resolve);
     for (hipEvent_t e : ev_light)
       if (e) (void)hipEventDestroy(e);
@@ -2803,6 +2820,8 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->tail_pending = false;
   s->carried_active = 0;
   s->packets_given_up = 0;
+  s->tile_n.clear();
+  s->adaptive_done = false;
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
@@ -3295,6 +3314,7 @@ int jade_render_query(jade_scene* s, int what, int64_t* value) {
 int jade_render_step(jade_scene* s, int32_t spp, jade_stats* st) {
   if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
   if (spp < 0) return fail(JADE_ERR_INVALID, "negative spp");
+  if (s->adaptive_done) return fail(JADE_ERR_INVALID, "the adaptive render has ended: jade_render_begin starts a new one");
   HIP_TRY(hipSetDevice(s->device));
   if (s->ps.npix == 0 || spp == 0) {
     s->spp_done += spp;
@@ -3315,11 +3335,117 @@ int jade_render_flush(jade_scene* s, jade_stats* st) {
   return advance(s, s->spp_done, false, st);
 }
 
+// ---- adaptive sampling (include/jade_bvh.h; kernel: jade_adaptive.hip) ----
+// Rounds of step + flush at the targets min_spp, 2 min_spp, ... spp; after each round below the cap k_tile_error stops the converged
+// tiles (their records' sample counters move past every target, PathState.hdr) and lists the others.  The host waits once per round,
+// for the number of tiles that go on.  The render is begun with spp = the cap, so records per pixel and sum lanes are a cap render's.
+int jade_render_adaptive(jade_scene* s, const jade_render_params* rp, int32_t min_spp, float rel_error, float error_floor, float* out_rgb,
+                         uint8_t* out_bgr8, int32_t* out_tile_spp, jade_stats* st) {
+  if (!s || !rp) return fail(JADE_ERR_INVALID, "null argument");
+  if (rp->spp <= 0) return fail(JADE_ERR_INVALID, "spp (the cap) must be positive");
+  if (min_spp < 2 || min_spp > rp->spp || (min_spp & (min_spp - 1)) != 0)
+    return fail(JADE_ERR_INVALID, "min_spp must be a power of two with 2 <= min_spp <= spp");
+  if (!std::isfinite(rel_error) || !(rel_error > 0.0f)) return fail(JADE_ERR_INVALID, "rel_error must be finite and > 0");
+  if (!std::isfinite(error_floor) || !(error_floor > 0.0f)) return fail(JADE_ERR_INVALID, "error_floor must be finite and > 0");
+  if (s->tun.pixel_rotate) return fail(JADE_ERR_UNSUPPORTED, "adaptive sampling with JADE_PIXEL_ROTATE (records move between pixels)");
+  if (int rc = jade_render_begin(s, rp)) return rc;
+  const size_t nt = s->tile_ids.size();
+  uint32_t n_active = s->ps.npix ? (uint32_t)nt : 0u;
+  if (n_active) {
+    std::vector<uint32_t> all(nt);
+    for (size_t t = 0; t < nt; ++t) all[t] = (uint32_t)t;
+    std::vector<int32_t> cap(nt, rp->spp);  // a tile that never stops ends at the cap
+    HIP_TRY(upload(s->b_alist[0], all.data(), nt, s->stream));
+    HIP_TRY(upload(s->b_tile_n, cap.data(), nt, s->stream));
+    HIP_TRY(s->b_alist[1].alloc(nt * 4));
+    HIP_TRY(s->b_actl.alloc(8));
+    for (hipEvent_t& e : s->ev_err)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+  }
+  int cur = 0;
+  for (int32_t prev = 0, target = min_spp;;) {
+    if (int rc = jade_render_step(s, target - prev, st)) return rc;
+    if (int rc = jade_render_flush(s, st)) return rc;
+    if (target >= rp->spp || n_active == 0) break;
+    HIP_TRY(hipMemsetAsync(s->b_actl.p, 0, 8, s->stream));
+    HIP_TRY(hipEventRecord(s->ev_err[0], s->stream));
+    uint32_t* ctl = s->b_actl.as<uint32_t>();
+    HIP_TRY(adaptive_tile_error(s->stream, n_active, s->ps, s->rc, s->b_tiles.as<int32_t>(), s->b_alist[cur].as<uint32_t>(), nullptr, (double)error_floor,
+                                rel_error, target, s->b_alist[cur ^ 1].as<uint32_t>(), ctl, s->b_tile_n.as<int32_t>(), nullptr, ctl + 1));
+    HIP_TRY(hipEventRecord(s->ev_err[1], s->stream));
+    uint32_t h[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(h, ctl, 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    float ms = 0;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev_err[0], s->ev_err[1]));
+    if (st) {
+      st->kernel_ms += ms;
+      st->host_syncs += 1;
+    }
+    if (h[1]) return fail(JADE_ERR_DEVICE, "adaptive: " + std::to_string(h[1]) + " records of stopped tiles were not idle");  // (debug builds count them)
+    n_active = h[0];
+    cur ^= 1;
+    if (n_active == 0) break;
+    prev = target;
+    target = (int32_t)std::min<int64_t>(2 * (int64_t)target, rp->spp);
+  }
+  // each tile's count, once; its 1 / n exactly as resolve_to makes the uniform one
+  s->tile_n.assign(nt, rp->spp);
+  if (nt && s->ps.npix) {
+    HIP_TRY(hipMemcpyAsync(s->tile_n.data(), s->b_tile_n.p, nt * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    std::vector<float> inv(nt);
+    for (size_t t = 0; t < nt; ++t) inv[t] = (float)(1.0 / (double)s->tile_n[t]);
+    HIP_TRY(upload(s->b_tile_inv, inv.data(), nt, s->stream));
+  }
+  s->adaptive_done = true;
+  if (out_tile_spp) {
+    const size_t all = (size_t)s->rc.tiles_x * (size_t)((rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE);
+    std::fill(out_tile_spp, out_tile_spp + all, 0);
+    for (size_t t = 0; t < nt; ++t) out_tile_spp[s->tile_ids[t]] = s->tile_n[t];
+  }
+  if (!out_rgb && !out_bgr8) return jade_render_flush(s, nullptr);
+  return jade_render_resolve(s, out_rgb, out_bgr8);
+}
+
+int jade_render_error(jade_scene* s, float error_floor, float* out_error) {
+  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (!out_error) return fail(JADE_ERR_INVALID, "null argument");
+  if (!std::isfinite(error_floor) || !(error_floor > 0.0f)) return fail(JADE_ERR_INVALID, "error_floor must be finite and > 0");
+  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = jade_render_flush(s, nullptr)) return rc;
+  const int npx = s->ps.npx;
+  if (npx == 0) return JADE_OK;
+  const size_t nt = s->tile_ids.size();
+  std::vector<int32_t> n(nt, (int32_t)std::min<int64_t>(s->spp_done, INT32_MAX));
+  if (!s->tile_n.empty()) n = s->tile_n;
+  DevBuf b_n;
+  HIP_TRY(upload(b_n, n.data(), nt, s->stream));
+  HIP_TRY(s->b_err.alloc((size_t)npx * 4));
+  HIP_TRY(adaptive_tile_error(s->stream, (uint32_t)nt, s->ps, s->rc, s->b_tiles.as<int32_t>(), nullptr, b_n.as<int32_t>(), (double)error_floor, 0.0f, 0,
+                              nullptr, nullptr, nullptr, s->b_err.as<float>(), nullptr));
+  std::vector<float> e((size_t)npx);
+  HIP_TRY(hipMemcpyAsync(e.data(), s->b_err.p, e.size() * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  // scatter the compact tiles into the caller's map, as jade_render_resolve_ex does with the radiance
+  const int W = s->rp.width, H = s->rp.height, tx = s->rc.tiles_x;
+  for (size_t t = 0; t < nt; ++t) {
+    int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
+    int ww = std::min(JADE_TILE_SIZE, W - x0), hh = std::min(JADE_TILE_SIZE, H - y0);
+    for (int ly = 0; ly < hh; ++ly) memcpy(out_error + (size_t)(y0 + ly) * W + x0, e.data() + t * 256 + (size_t)ly * 16, (size_t)ww * 4);
+  }
+  return JADE_OK;
+}
+
 static int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream) {
   const int npix = s->ps.npx;
   if (npix == 0) return JADE_OK;
   float inv = (float)(1.0 / (double)s->spp_done);  // vec3(1.0 / spp), PathTrace.cu:1457
-  hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, s->ps, s->rc, s->b_tiles.as<int32_t>(), inv, tonemap, limit, dev_rgb, dev_bgr);
+  // after jade_render_adaptive: each tile's own (float)(1.0 / (double)n), made the same way (jade_render_adaptive)
+  const float* tile_inv = s->tile_n.empty() ? nullptr : s->b_tile_inv.as<float>();
+  hipLaunchKernelGGL(k_resolve, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, s->ps, s->rc, s->b_tiles.as<int32_t>(), tile_inv, inv, tonemap, limit,
+                     dev_rgb, dev_bgr);
   HIP_TRY(hipGetLastError());
   return JADE_OK;
 }

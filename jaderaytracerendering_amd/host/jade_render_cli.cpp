@@ -8,12 +8,15 @@
 #include <libgen.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
+#include "jade_bvh.h"
 #include "jade_host.hpp"
 
 using namespace jadehost;
@@ -26,9 +29,11 @@ struct Api {
   int (*scene_create)(const jade_scene_desc*, int, jade_scene**);
   void (*scene_destroy)(jade_scene*);
   int (*render)(jade_scene*, const jade_render_params*, float*, uint8_t*, jade_stats*);
+  // include/jade_bvh.h, looked up only for --adaptive: the oracle backend has no such entry point
+  int (*render_adaptive)(jade_scene*, const jade_render_params*, int32_t, float, float, float*, uint8_t*, int32_t*, jade_stats*) = nullptr;
 };
 
-static bool load_api(const std::string& path, Api& a) {
+static bool load_api(const std::string& path, Api& a, bool adaptive) {
   a.h = dlopen(path.c_str(), RTLD_NOW | RTLD_LOCAL);
   if (!a.h) {
     fprintf(stderr, "cannot load backend %s: %s\n", path.c_str(), dlerror());
@@ -43,6 +48,7 @@ static bool load_api(const std::string& path, Api& a) {
   SYM(scene_create, "jade_scene_create")
   SYM(scene_destroy, "jade_scene_destroy")
   SYM(render, "jade_render")
+  if (adaptive) { SYM(render_adaptive, "jade_render_adaptive") }
 #undef SYM
   if (a.abi_version() != JADE_ABI_VERSION) {
     // a stale pair would silently disagree on struct layouts (jade_stats, jade_render_params)
@@ -57,6 +63,10 @@ static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance]\n"
+          "                   [--adaptive REL [--min-spp N] [--error-floor F]]\n"
+          "  --adaptive REL: adaptive sampling (HIP backend only): each 16x16 tile stops at the first of N, 2N, 4N, ... samples at which\n"
+          "                  every pixel's relative standard error of the mean luminance is <= REL; --spp is the cap.  --min-spp N: a power of\n"
+          "                  two >= 2 (default 16); --error-floor F > 0 (default 0.01) is added to the mean in the error's denominator\n"
           "  --env-importance: environment-visibility rays drawn by the sky's luminance instead of uniformly (NOT the reference's samples: the\n"
           "                    same image with less noise under a sky with a sun; the oracle backend refuses it)\n"
           "  --reference-walk: every hitBVH query walks what the reference walks (nodes_visited / tris_tested equal the oracle's);\n"
@@ -69,6 +79,15 @@ int main(int argc, char** argv) {
   int width = 0, height = 0, spp = 0, device = 0;
   bool reference_walk = false;
   bool env_importance = false;
+  double adaptive = 0.0, error_floor = 0.01;
+  int min_spp = 16;
+  bool use_adaptive = false;
+  auto number = [](const char* flag, const char* v) {
+    char* end = nullptr;
+    const double x = strtod(v, &end);
+    if (end == v || *end != 0 || !std::isfinite(x)) { fprintf(stderr, "%s: not a finite number: %s\n", flag, v); exit(2); }
+    return x;
+  };
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
     auto need = [&](const char* what) -> const char* {
@@ -86,8 +105,15 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = atoi(need("--device"));
     else if (a == "--reference-walk") reference_walk = true;
     else if (a == "--env-importance") env_importance = true;
+    else if (a == "--adaptive") { adaptive = number("--adaptive", need("--adaptive")); use_adaptive = true; }
+    else if (a == "--min-spp") { const double v = number("--min-spp", need("--min-spp")); min_spp = v >= 0 && v <= (1 << 30) && v == (int)v ? (int)v : -1; }
+    else if (a == "--error-floor") error_floor = number("--error-floor", need("--error-floor"));
     else { usage(); return 2; }
   }
+  // bad values end here, before a scene is built or a backend loaded
+  if (use_adaptive && !(adaptive > 0.0)) { fprintf(stderr, "--adaptive must be > 0\n"); return 2; }
+  if (min_spp < 2 || (min_spp & (min_spp - 1)) != 0) { fprintf(stderr, "--min-spp must be a power of two >= 2\n"); return 2; }
+  if (!(error_floor > 0.0)) { fprintf(stderr, "--error-floor must be > 0\n"); return 2; }
   if (config.empty() == args_file.empty()) { usage(); return 2; }
   if (backend.empty()) {
     char self[4096];
@@ -128,13 +154,14 @@ int main(int argc, char** argv) {
   if (width > 0) cfg.width = width;
   if (height > 0) cfg.height = height;
   if (spp > 0) cfg.spp = spp;
+  if (use_adaptive && min_spp > cfg.spp) { fprintf(stderr, "--min-spp %d is above the cap --spp %d\n", min_spp, cfg.spp); return 2; }
 
   printf("Model load done:  %d Triangles.\n", builder.triangle_count());
   BuiltScene scene = builder.build(8);
   printf("BVH Build done: %zu nodes, depth %d, %.2f s.\n", scene.nodes.size(), scene.bvh_depth, scene.build_seconds);
 
   Api api;
-  if (!load_api(backend, api)) return 1;
+  if (!load_api(backend, api, use_adaptive)) return 1;
   jade_scene_desc desc = scene.desc();
   jade_scene* dev = nullptr;
   if (api.scene_create(&desc, device, &dev) != JADE_OK) { fprintf(stderr, "scene: %s\n", api.last_error()); return 1; }
@@ -151,15 +178,32 @@ int main(int argc, char** argv) {
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
   jade_stats st;
   memset(&st, 0, sizeof st);
-  printf("Start... %dx%d, %d spp on %s\n", rp.width, rp.height, rp.spp, api.backend_name());
-  if (api.render(dev, &rp, rgb.data(), bgr.data(), &st) != JADE_OK) { fprintf(stderr, "render: %s\n", api.last_error()); return 1; }
+  const int tiles = ((rp.width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE) * ((rp.height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE);
+  std::vector<int32_t> tile_spp(use_adaptive ? tiles : 0);
+  if (use_adaptive) {
+    printf("Start... %dx%d, adaptive %g (%d .. %d spp) on %s\n", rp.width, rp.height, adaptive, min_spp, rp.spp, api.backend_name());
+    if (api.render_adaptive(dev, &rp, min_spp, (float)adaptive, (float)error_floor, rgb.data(), bgr.data(), tile_spp.data(), &st) != JADE_OK) {
+      fprintf(stderr, "render: %s\n", api.last_error());
+      return 1;
+    }
+  } else {
+    printf("Start... %dx%d, %d spp on %s\n", rp.width, rp.height, rp.spp, api.backend_name());
+    if (api.render(dev, &rp, rgb.data(), bgr.data(), &st) != JADE_OK) { fprintf(stderr, "render: %s\n", api.last_error()); return 1; }
+  }
   api.scene_destroy(dev);
+  std::string hist;
+  if (use_adaptive) {  // tiles per final sample count
+    std::map<int32_t, int> h;
+    for (int32_t k : tile_spp) h[k] += 1;
+    for (const auto& kv : h) hist += (hist.empty() ? "" : ", ") + ("\"" + std::to_string(kv.first) + "\": " + std::to_string(kv.second));
+    hist = ", \"tile_spp\": {" + hist + "}";
+  }
   double rays = (double)(st.rays_primary + st.rays_secondary);
   printf("{\"rays\": %.0f, \"kernel_ms\": %.3f, \"mray_per_s\": %.3f, \"rays_primary\": %llu, \"rays_secondary\": %llu, "
-         "\"nodes_visited\": %llu, \"tris_tested\": %llu, \"shaded_hits\": %llu, \"samples\": %llu}\n",
+         "\"nodes_visited\": %llu, \"tris_tested\": %llu, \"shaded_hits\": %llu, \"samples\": %llu%s}\n",
          rays, st.kernel_ms, rays / st.kernel_ms / 1e3, (unsigned long long)st.rays_primary, (unsigned long long)st.rays_secondary,
          (unsigned long long)st.nodes_visited, (unsigned long long)st.tris_tested, (unsigned long long)st.shaded_hits,
-         (unsigned long long)st.samples);
+         (unsigned long long)st.samples, hist.c_str());
   bool ok;
   size_t dot = out.find_last_of('.');
   std::string ext = dot == std::string::npos ? "" : out.substr(dot);
