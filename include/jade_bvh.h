@@ -25,7 +25,8 @@
  * visited / triangles tested) differ between trees, as the trees do.
  *
  * The header also holds the HIP module's other entry points that the CPU
- * oracle does not implement: adaptive sampling and its noise map (below).
+ * oracle does not implement: adaptive sampling and its noise map, and the
+ * edge-aware denoiser (below).
  * Exported by libjade_hip.so only; the oracle has none of them.
  */
 #ifndef JADE_BVH_H
@@ -87,6 +88,65 @@ int jade_render_adaptive(jade_scene* scene, const jade_render_params* params, in
  * (pixel (x, y) at y*width + x); pixels of tiles not owned are left untouched.  Flushes first, like resolve.
  * Fails only when no render has been begun or no sample rendered. */
 int jade_render_error(jade_scene* scene, float error_floor, float* out_error);
+
+/* ---- Denoiser: an edge-aware a-trous filter guided by albedo, normal, depth and variance ----
+ *
+ * The spatial part of SVGF (Schied et al. 2017) over the a-trous wavelet filter of Dammertz et al. (2010).  Non-parity: the
+ * reference has no denoiser.  Every image below is width*height pixels laid out as out_rgb's (pixel (x, y) at y*width + x).
+ *
+ * Guides of pixel (x, y), over guide samples s = 0 .. G-1: the camera ray of sample s exactly as the render makes it (seed
+ * jade_rng_seed(x, y, frame + s), two jitter draws, origin = eye), walked with the reference walk (nearest hit, as
+ * jade_trace_rays).  t = (1,1,1), z = 0.  While the hit triangle is a mirror (reflex_mode == JADE_MIRROR), not emissive (the
+ * render's mirror test) and fewer than JADE_MAX_FULL_REFLEX_TIME mirror vertices have been passed: t *= brdf, z += hit
+ * distance, and the ray goes on from the hit point in direction n (2 (o.n)) - o, o = -d.  At the final vertex k: z += hit
+ * distance, a = t * brdf_k, n = norm_k negated if dot(norm_k, d) > 0.  A miss: a = t, n = 0, z = 0.  The guide of the pixel is
+ * the float sum over s in increasing order times (float)(1/G); the normal is not renormalised.
+ *
+ * Variance of pixel p: the variance of its mean luminance, the square of the pixel error's numerator above:
+ *   v = sum (Y_l - m)^2 / (K (K - 1))       (Y_l, m, K as above; fp64, stored as float; NaN where n cannot be estimated)
+ *
+ * Filter, pass i = 0 .. iterations-1 with step s = 2^i, luminance l = 0.3 r + 0.6 g + 0.1 b, h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *   g_p = the 3x3 blur of v with weights (1/4, 1/2, 1/4) x (1/4, 1/2, 1/4) over in-image taps, renormalised
+ *   for each in-image tap q = p + s (dx, dy), dx, dy in -2..2:
+ *     w_l = exp(-|l_p - l_q| / (sigma_luminance sqrt(g_p) + 1e-10))
+ *     w_n = 1 if both normals are 0, 0 if exactly one is, else max(0, nhat_p . nhat_q)^sigma_normal
+ *     w_z = exp(-|z_p - z_q| / (sigma_depth max(z_p, z_q) + 1e-10))
+ *     w_a = exp(-|a_p - a_q|_1 / sigma_albedo)
+ *     w   = h(dx) h(dy) w_l w_n w_z w_a
+ *   c'_p = sum w c_q / sum w          v'_p = sum w^2 v_q / (sum w)^2
+ * iterations = 0 returns the input colour bit for bit. */
+typedef struct jade_denoise_params {
+  int32_t iterations;    /* a-trous passes, 0..8; pass i uses a step of 2^i pixels; 0 = identity */
+  int32_t guide_spp;     /* camera samples averaged into the guides, 1..64 */
+  float sigma_luminance; /* > 0 */
+  float sigma_normal;    /* >= 0, exponent */
+  float sigma_depth;     /* > 0, relative */
+  float sigma_albedo;    /* > 0 */
+} jade_denoise_params;
+
+/* The defaults DESIGN.md 3.6 chose from its measurement. */
+void jade_denoise_defaults(jade_denoise_params* p);
+
+/* The denoiser's inputs for the owned tiles of the render in progress (flushes first, like resolve).  Each output is
+ * width*height floats (x3 for albedo and normal) in out_rgb's pixel layout; pixels of tiles this rank does not own are left
+ * untouched.  Any output may be null.  guide_spp: 1..64.  The variance is NaN where the pixel's sample count cannot give
+ * one, as jade_render_error's estimate is.  The render's sums, counters and next step are not changed. */
+int jade_render_guides(jade_scene* scene, int32_t guide_spp, float* out_albedo, float* out_normal, float* out_depth,
+                       float* out_variance);
+
+/* Denoise the render in progress on its device: resolve, variance and guides, then the filter, all on the device, one copy
+ * back.  Full frame only: tile_nranks > 1 gives JADE_ERR_UNSUPPORTED.  tonemap / limit as jade_render_resolve_ex.  Works
+ * after jade_render_adaptive too, with each tile's own count.  JADE_ERR_INVALID where a pixel's count cannot give a
+ * variance (n < 2, or n > 1024 and not a multiple of 1024).  Bit for bit jade_denoise_image on jade_render_resolve_ex's
+ * out_rgb and jade_render_guides' outputs.  The render is not changed. */
+int jade_render_denoise(jade_scene* scene, const jade_denoise_params* params, int tonemap, float limit, float* out_rgb,
+                        uint8_t* out_bgr8);
+
+/* The same filter on caller-provided host buffers (rgb and albedo / normal x3 floats per pixel).  This is what a multi-rank
+ * host calls after it has gathered rgb (resolve) and the guides (jade_render_guides) of every rank. */
+int jade_denoise_image(int device_id, int32_t width, int32_t height, const float* rgb, const float* variance,
+                       const float* albedo, const float* normal, const float* depth, const jade_denoise_params* params,
+                       float* out_rgb);
 
 #ifdef __cplusplus
 }

@@ -91,6 +91,13 @@ class Stats(C.Structure):
         return self.rays_primary + self.rays_secondary
 
 
+class DenoiseParams(C.Structure):  # == jade_denoise_params, include/jade_bvh.h
+    _fields_ = [
+        ("iterations", C.c_int32), ("guide_spp", C.c_int32),
+        ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("sigma_albedo", C.c_float),
+    ]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -137,6 +144,13 @@ BVH_SYMBOLS = {
     "jade_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(RenderParams), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.POINTER(Stats)]),
     "jade_render_error": (C.c_int, [C.c_void_p, C.c_float, C.c_void_p]),
+    # the denoiser: defaults, guides (scene, guide_spp, albedo, normal, depth, variance), the render's frame (scene, params, tonemap,
+    # limit, rgb, bgr8) and caller images (device, width, height, rgb, variance, albedo, normal, depth, params, out rgb)
+    "jade_denoise_defaults": (None, [C.POINTER(DenoiseParams)]),
+    "jade_render_guides": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jade_render_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "jade_denoise_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(DenoiseParams), C.c_void_p]),
 }
 
 HOST_SYMBOLS = {

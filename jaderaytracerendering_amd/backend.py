@@ -67,6 +67,36 @@ class Backend:
     def owned_tile_count(self, width, height, rank, nranks):
         return self.lib.jade_owned_tile_count(width, height, rank, nranks)
 
+    def hip_only(self, name):
+        """An include/jade_bvh.h entry point: JadeError(JADE_ERR_UNSUPPORTED) on a backend without it (the oracle)."""
+        fn = getattr(self.lib, name, None)
+        if fn is None:
+            raise JadeError(_abi.JADE_ERR_UNSUPPORTED, f"{self.path} has no {name} (HIP module only)")
+        fn.restype, fn.argtypes = _abi.BVH_SYMBOLS[name]
+        return fn
+
+    def denoise_defaults(self):
+        """jade_denoise_defaults: the DenoiseParams DESIGN.md 3.6 chose."""
+        p = _abi.DenoiseParams()
+        self.hip_only("jade_denoise_defaults")(C.byref(p))
+        return p
+
+    def denoise_image(self, rgb, variance, albedo, normal, depth, params=None, device_id=0):
+        """jade_denoise_image: the edge-aware filter (include/jade_bvh.h) on caller images - rgb, albedo, normal [H, W, 3], variance,
+        depth [H, W] - on device `device_id`.  params None: the defaults.  Returns the filtered rgb, float32 [H, W, 3]."""
+        fn = self.hip_only("jade_denoise_image")
+        if params is None:
+            params = self.denoise_defaults()
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        h, w = rgb.shape[:2]
+        ins = [np.ascontiguousarray(a, np.float32) for a in (variance, albedo, normal, depth)]
+        for a, shape in zip(ins, ((h, w), (h, w, 3), (h, w, 3), (h, w))):
+            if a.shape != shape:
+                raise ValueError(f"input of shape {a.shape}, expected {shape}")
+        out = np.zeros((h, w, 3), np.float32)
+        self.check(fn(int(device_id), int(w), int(h), rgb.ctypes.data, *[a.ctypes.data for a in ins], C.byref(params), out.ctypes.data))
+        return out
+
 
 class Scene:
     """A scene resident on the backend (PathTrace.cu:1618-1698 on the reference side)."""
@@ -164,6 +194,34 @@ class Scene:
         out = np.full((self._params.height, self._params.width), np.nan, np.float32)
         self.backend.check(fn(self._h, float(error_floor), out.ctypes.data))
         return out
+
+    def guides(self, guide_spp=4):
+        """jade_render_guides: the denoiser's inputs for the render in progress, a dict of float32 arrays - "albedo", "normal"
+        [H, W, 3], "depth", "variance" [H, W] - laid out as resolve's; tiles this rank does not own are NaN."""
+        fn = self._hip_only("jade_render_guides")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        h, w = self._params.height, self._params.width
+        out = {"albedo": np.full((h, w, 3), np.nan, np.float32), "normal": np.full((h, w, 3), np.nan, np.float32),
+               "depth": np.full((h, w), np.nan, np.float32), "variance": np.full((h, w), np.nan, np.float32)}
+        self.backend.check(fn(self._h, int(guide_spp), out["albedo"].ctypes.data, out["normal"].ctypes.data, out["depth"].ctypes.data,
+                              out["variance"].ctypes.data))
+        return out
+
+    def denoise(self, params=None, tonemap=None, limit=1.5, want_rgb=True, want_bgr8=True):
+        """jade_render_denoise: the render in progress, filtered on its device (full frame only).  params None: the defaults;
+        tonemap None: ACES.  Returns (rgb float32 [H, W, 3] | None, bgr8 uint8 [H, W, 3] | None)."""
+        fn = self._hip_only("jade_render_denoise")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        if params is None:
+            params = self.backend.denoise_defaults()
+        h, w = self._params.height, self._params.width
+        rgb = np.zeros((h, w, 3), np.float32) if want_rgb else None
+        bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
+        self.backend.check(fn(self._h, C.byref(params), _abi.TONEMAP_ACES if tonemap is None else int(tonemap), float(limit),
+                              rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None))
+        return rgb, bgr
 
     def query(self, what):
         """jade_render_query: what the backend holds for the current render (_abi.Q_*)."""

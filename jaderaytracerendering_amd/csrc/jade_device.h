@@ -282,3 +282,48 @@ static __device__ __forceinline__ void st3(float* a, int npix, int p, jvec3 v) {
   a[2 * npix + p] = v.z;
 }
 static __device__ __forceinline__ jvec3 V3(const float* p) { return jv(p[0], p[1], p[2]); }
+
+// The camera ray of sample `sidx` of pixel (x, y), PathTrace.cu:1428-1437: its direction (the origin is the eye).  *rng is left
+// after the two jitter draws.  The statements of k_shade's / k_light's camera ray; the denoiser's guide pass calls it
+// (jade_denoise.hip).  (The four copies in jade_hip.hip stay as they are: those kernels sit at their register limits.)
+static __device__ __forceinline__ jvec3 camera_ray_dir(const RenderConst& R, int x, int y, uint32_t sidx, uint32_t* rng) {
+  *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
+  float fx = (float)x + jade_rand(rng);
+  double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
+  float left_offset = (float)(lo * R.aspect);
+  float fy = (float)y + jade_rand(rng);
+  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  jvec3 dir = jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, R.cam);
+  return jv_normalize(dir);
+}
+
+// ACESToneMapping (or the preview's Reinhard operator) + gamma + BGR pack of one pixel's linear colour m, PathTrace.cu:669-682,
+// 1457-1473 / pass3.fsh:8-18: k_resolve's statements, shared with the denoiser's output kernel.  out: 3 bytes, B G R.
+static __device__ __forceinline__ void tone_pack_bgr8(jvec3 m, int tonemap, float limit, bool valid, uint8_t* out) {
+  float v[3] = {m.x, m.y, m.z};
+  float rein = 1.0f;
+  if (tonemap == JADE_TONEMAP_REINHARD) {  // toneMapping(c, limit), PathTrace.cu:669-672 / pass3.fsh:8-18
+    float luminance = (float)(0.3 * (double)m.x + 0.6 * (double)m.y + 0.1 * (double)m.z);
+    rein = (float)(1.0 / (1.0 + (double)(luminance / limit)));
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float x = v[k];
+    if (tonemap == JADE_TONEMAP_REINHARD) {
+      x = x * rein;
+    } else {
+      float num = x * (x * 2.51f + 0.03f);
+      float den = x * (x * 2.43f + 0.59f) + 0.14f;
+      x = num / den;
+    }
+    x = jade_powf(x, (float)(1.0 / 2.2));
+    x = x * 255.0f;
+    x = x > 255 ? 255 : x;
+    v[k] = x;
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float x = v[2 - k];
+    out[k] = (valid && x >= 0.0f) ? (uint8_t)x : (uint8_t)0;
+  }
+}

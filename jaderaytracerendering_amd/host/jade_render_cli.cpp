@@ -31,6 +31,10 @@ struct Api {
   int (*render)(jade_scene*, const jade_render_params*, float*, uint8_t*, jade_stats*);
   // include/jade_bvh.h, looked up only for --adaptive: the oracle backend has no such entry point
   int (*render_adaptive)(jade_scene*, const jade_render_params*, int32_t, float, float, float*, uint8_t*, int32_t*, jade_stats*) = nullptr;
+  // ... and only for --denoise / --guides (looked up with dlsym alone: without them the backend is refused with status 2)
+  void (*denoise_defaults)(jade_denoise_params*) = nullptr;
+  int (*render_denoise)(jade_scene*, const jade_denoise_params*, int, float, float*, uint8_t*) = nullptr;
+  int (*render_guides)(jade_scene*, int32_t, float*, float*, float*, float*) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -59,11 +63,24 @@ static bool load_api(const std::string& path, Api& a, bool adaptive) {
   return true;
 }
 
+// one channel: the "Pf" form of PFM (rows bottom to top, as write_pfm's)
+static bool write_pfm1(const std::string& path, const float* v, int width, int height) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "Pf\n%d %d\n-1.0\n", width, height);
+  const size_t n = (size_t)width * height;
+  const bool ok = fwrite(v, sizeof(float), n, f) == n;
+  return fclose(f) == 0 && ok;
+}
+
 static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance]\n"
-          "                   [--adaptive REL [--min-spp N] [--error-floor F]]\n"
+          "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
+          "  --denoise: write the frame filtered by the edge-aware denoiser (HIP backend only; include/jade_bvh.h, default parameters)\n"
+          "  --guides PREFIX: write the denoiser's inputs as PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_variance.pfm\n"
+          "                   (HIP backend only; 4 guide samples)\n"
           "  --adaptive REL: adaptive sampling (HIP backend only): each 16x16 tile stops at the first of N, 2N, 4N, ... samples at which\n"
           "                  every pixel's relative standard error of the mean luminance is <= REL; --spp is the cap.  --min-spp N: a power of\n"
           "                  two >= 2 (default 16); --error-floor F > 0 (default 0.01) is added to the mean in the error's denominator\n"
@@ -82,6 +99,8 @@ int main(int argc, char** argv) {
   double adaptive = 0.0, error_floor = 0.01;
   int min_spp = 16;
   bool use_adaptive = false;
+  bool use_denoise = false;
+  std::string guides;
   auto number = [](const char* flag, const char* v) {
     char* end = nullptr;
     const double x = strtod(v, &end);
@@ -108,6 +127,8 @@ int main(int argc, char** argv) {
     else if (a == "--adaptive") { adaptive = number("--adaptive", need("--adaptive")); use_adaptive = true; }
     else if (a == "--min-spp") { const double v = number("--min-spp", need("--min-spp")); min_spp = v >= 0 && v <= (1 << 30) && v == (int)v ? (int)v : -1; }
     else if (a == "--error-floor") error_floor = number("--error-floor", need("--error-floor"));
+    else if (a == "--denoise") use_denoise = true;
+    else if (a == "--guides") guides = need("--guides");
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
@@ -162,6 +183,16 @@ int main(int argc, char** argv) {
 
   Api api;
   if (!load_api(backend, api, use_adaptive)) return 1;
+  if (use_denoise || !guides.empty()) {
+    *(void**)(&api.denoise_defaults) = dlsym(api.h, "jade_denoise_defaults");
+    *(void**)(&api.render_denoise) = dlsym(api.h, "jade_render_denoise");
+    *(void**)(&api.render_guides) = dlsym(api.h, "jade_render_guides");
+    if (!api.denoise_defaults || !api.render_denoise || !api.render_guides) {
+      fprintf(stderr, "%s needs the HIP backend: %s has no jade_render_denoise / jade_render_guides\n", use_denoise ? "--denoise" : "--guides",
+              backend.c_str());
+      return 2;
+    }
+  }
   jade_scene_desc desc = scene.desc();
   jade_scene* dev = nullptr;
   if (api.scene_create(&desc, device, &dev) != JADE_OK) { fprintf(stderr, "scene: %s\n", api.last_error()); return 1; }
@@ -189,6 +220,24 @@ int main(int argc, char** argv) {
   } else {
     printf("Start... %dx%d, %d spp on %s\n", rp.width, rp.height, rp.spp, api.backend_name());
     if (api.render(dev, &rp, rgb.data(), bgr.data(), &st) != JADE_OK) { fprintf(stderr, "render: %s\n", api.last_error()); return 1; }
+  }
+  if (!guides.empty()) {
+    const size_t np = (size_t)rp.width * rp.height;
+    std::vector<float> ga(3 * np), gn(3 * np), gz(np), gv(np);
+    if (api.render_guides(dev, 4, ga.data(), gn.data(), gz.data(), gv.data()) != JADE_OK) { fprintf(stderr, "guides: %s\n", api.last_error()); return 1; }
+    const std::pair<const char*, const std::vector<float>*> files[] = {{"albedo", &ga}, {"normal", &gn}, {"depth", &gz}, {"variance", &gv}};
+    for (const auto& f : files) {
+      const std::string path = guides + "_" + f.first + ".pfm";
+      const bool ok = f.second->size() == 3 * np ? write_pfm(path, f.second->data(), rp.width, rp.height) : write_pfm1(path, f.second->data(), rp.width, rp.height);
+      if (!ok) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      printf("wrote %s\n", path.c_str());
+    }
+  }
+  if (use_denoise) {
+    jade_denoise_params dp;
+    api.denoise_defaults(&dp);
+    if (api.render_denoise(dev, &dp, JADE_TONEMAP_ACES, 0.0f, rgb.data(), bgr.data()) != JADE_OK) { fprintf(stderr, "denoise: %s\n", api.last_error()); return 1; }
+    printf("denoised: %d a-trous passes, %d guide samples\n", dp.iterations, dp.guide_spp);
   }
   api.scene_destroy(dev);
   std::string hist;
