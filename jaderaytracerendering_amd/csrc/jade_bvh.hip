@@ -28,26 +28,9 @@
 #include <string>
 #include <vector>
 
-#include "jade_bvh.h"
-
-int jade_fail(int code, const std::string& msg);  // jade_hip.hip: sets jade_last_error()
+#include "jade_runtime.h"
 
 namespace {
-
-#define BVH_TRY(expr)                                                                                 \
-  do {                                                                                                \
-    hipError_t e_ = (expr);                                                                           \
-    if (e_ != hipSuccess)                                                                             \
-      return jade_fail(e_ == hipErrorOutOfMemory ? JADE_ERR_NOMEM : JADE_ERR_DEVICE,                  \
-                       std::string(#expr) + ": " + hipGetErrorString(e_));                            \
-  } while (0)
-
-struct Buf {
-  void* p = nullptr;
-  ~Buf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 16); }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
 
 __device__ __forceinline__ uint32_t expand10(uint32_t v) {
   v = (v * 0x00010001u) & 0xFF0000FFu;
@@ -319,20 +302,15 @@ __global__ void k_ploc_offsets(int n, const int* left, const int* right, const i
 namespace {
 enum BuildKind { KIND_LBVH = 0, KIND_PLOC = 1 };
 
-struct Ev {  // destroyed on every return path
-  hipEvent_t e = nullptr;
-  ~Ev() { if (e) (void)hipEventDestroy(e); }
-};
-
 int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf_size, int device_id, int32_t* order_out,
               jade_bvh_node* nodes_out, int32_t max_nodes, int32_t* n_nodes_out, double* build_ms) {
   if (!tris || n <= 0 || !order_out || !nodes_out || !n_nodes_out) return jade_fail(JADE_ERR_INVALID, "null argument");
   if (leaf_size < 1 || leaf_size > 15) return jade_fail(JADE_ERR_INVALID, "leaf_size must be 1..15");
   if (n >= (1 << 27)) return jade_fail(JADE_ERR_UNSUPPORTED, "more than 2^27 triangles");
   int ndev = 0;
-  BVH_TRY(hipGetDeviceCount(&ndev));
+  HIP_TRY(hipGetDeviceCount(&ndev));
   if (device_id < 0 || device_id >= ndev) return jade_fail(JADE_ERR_DEVICE, "no such HIP device");
-  BVH_TRY(hipSetDevice(device_id));
+  HIP_TRY(hipSetDevice(device_id));
 
   // vertices only, and the centroid bounds (O(n) on the host, beside the packing loop)
   std::vector<float> verts((size_t)9 * n);
@@ -357,58 +335,58 @@ int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf
   }
 
   const int items = 2 * n - 1;
-  Buf b_verts, b_keys, b_keys2, b_lo, b_hi, b_left, b_right, b_first, b_last, b_parent, b_blo, b_bhi, b_arr, b_flags, b_slot,
+  DevBuf b_verts, b_keys, b_keys2, b_lo, b_hi, b_left, b_right, b_first, b_last, b_parent, b_blo, b_bhi, b_arr, b_flags, b_slot,
       b_nodes, b_tmp, b_count, b_offset, b_order, b_cid[2], b_cbox[2], b_nn, b_f64, b_p64;
-  BVH_TRY(b_verts.alloc(verts.size() * 4));
-  BVH_TRY(b_keys.alloc((size_t)n * 8));
-  BVH_TRY(b_keys2.alloc((size_t)n * 8));
-  BVH_TRY(b_lo.alloc((size_t)n * 12));
-  BVH_TRY(b_hi.alloc((size_t)n * 12));
-  BVH_TRY(b_left.alloc((size_t)n * 4));
-  BVH_TRY(b_right.alloc((size_t)n * 4));
-  BVH_TRY(b_parent.alloc((size_t)items * 4));
-  BVH_TRY(b_blo.alloc((size_t)items * 12));
-  BVH_TRY(b_bhi.alloc((size_t)items * 12));
-  BVH_TRY(b_count.alloc((size_t)items * 4));
-  BVH_TRY(b_offset.alloc((size_t)items * 4));
-  BVH_TRY(b_order.alloc((size_t)n * 4));
-  BVH_TRY(b_flags.alloc((size_t)items * 4));
-  BVH_TRY(b_slot.alloc((size_t)items * 4));
-  BVH_TRY(b_nodes.alloc((size_t)(items + 1) * sizeof(jade_bvh_node)));
+  HIP_TRY(b_verts.alloc(verts.size() * 4));
+  HIP_TRY(b_keys.alloc((size_t)n * 8));
+  HIP_TRY(b_keys2.alloc((size_t)n * 8));
+  HIP_TRY(b_lo.alloc((size_t)n * 12));
+  HIP_TRY(b_hi.alloc((size_t)n * 12));
+  HIP_TRY(b_left.alloc((size_t)n * 4));
+  HIP_TRY(b_right.alloc((size_t)n * 4));
+  HIP_TRY(b_parent.alloc((size_t)items * 4));
+  HIP_TRY(b_blo.alloc((size_t)items * 12));
+  HIP_TRY(b_bhi.alloc((size_t)items * 12));
+  HIP_TRY(b_count.alloc((size_t)items * 4));
+  HIP_TRY(b_offset.alloc((size_t)items * 4));
+  HIP_TRY(b_order.alloc((size_t)n * 4));
+  HIP_TRY(b_flags.alloc((size_t)items * 4));
+  HIP_TRY(b_slot.alloc((size_t)items * 4));
+  HIP_TRY(b_nodes.alloc((size_t)(items + 1) * sizeof(jade_bvh_node)));
   size_t tmp_sort = 0, tmp_scan = 0, tmp_scan64 = 0;
-  BVH_TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, b_keys.as<unsigned long long>(), b_keys2.as<unsigned long long>(), (size_t)n));
-  BVH_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, b_flags.as<int>(), b_slot.as<int>(), 0, (size_t)items, rocprim::plus<int>()));
+  HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_sort, b_keys.as<unsigned long long>(), b_keys2.as<unsigned long long>(), (size_t)n));
+  HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan, b_flags.as<int>(), b_slot.as<int>(), 0, (size_t)items, rocprim::plus<int>()));
   if (kind == KIND_LBVH) {
-    BVH_TRY(b_first.alloc((size_t)n * 4));
-    BVH_TRY(b_last.alloc((size_t)n * 4));
-    BVH_TRY(b_arr.alloc((size_t)n * 4));
+    HIP_TRY(b_first.alloc((size_t)n * 4));
+    HIP_TRY(b_last.alloc((size_t)n * 4));
+    HIP_TRY(b_arr.alloc((size_t)n * 4));
   } else {
     for (int k = 0; k < 2; ++k) {
-      BVH_TRY(b_cid[k].alloc((size_t)n * 4));
-      BVH_TRY(b_cbox[k].alloc((size_t)n * sizeof(Box6)));
+      HIP_TRY(b_cid[k].alloc((size_t)n * 4));
+      HIP_TRY(b_cbox[k].alloc((size_t)n * sizeof(Box6)));
     }
-    BVH_TRY(b_nn.alloc((size_t)n * 4));
-    BVH_TRY(b_f64.alloc((size_t)n * 8));
-    BVH_TRY(b_p64.alloc((size_t)n * 8));
-    BVH_TRY(rocprim::exclusive_scan(nullptr, tmp_scan64, b_f64.as<unsigned long long>(), b_p64.as<unsigned long long>(), 0ull, (size_t)n,
+    HIP_TRY(b_nn.alloc((size_t)n * 4));
+    HIP_TRY(b_f64.alloc((size_t)n * 8));
+    HIP_TRY(b_p64.alloc((size_t)n * 8));
+    HIP_TRY(rocprim::exclusive_scan(nullptr, tmp_scan64, b_f64.as<unsigned long long>(), b_p64.as<unsigned long long>(), 0ull, (size_t)n,
                                     rocprim::plus<unsigned long long>()));
   }
-  BVH_TRY(b_tmp.alloc(std::max(tmp_sort, std::max(tmp_scan, tmp_scan64))));
+  HIP_TRY(b_tmp.alloc(std::max(tmp_sort, std::max(tmp_scan, tmp_scan64))));
 
   hipStream_t st = nullptr;  // null stream: rocPRIM and the kernels below are ordered
-  BVH_TRY(hipMemcpy(b_verts.p, verts.data(), verts.size() * 4, hipMemcpyHostToDevice));
-  Ev e0, e1;
-  BVH_TRY(hipEventCreate(&e0.e));
-  BVH_TRY(hipEventCreate(&e1.e));
-  BVH_TRY(hipEventRecord(e0.e, st));
+  HIP_TRY(hipMemcpy(b_verts.p, verts.data(), verts.size() * 4, hipMemcpyHostToDevice));
+  DevEvent e0, e1;
+  HIP_TRY(e0.create());
+  HIP_TRY(e1.create());
+  HIP_TRY(hipEventRecord(e0.e, st));
   const unsigned bn = (unsigned)((n + 255) / 256), bi = (unsigned)((items + 255) / 256);
   hipLaunchKernelGGL(k_keys, dim3(bn), dim3(256), 0, st, b_verts.as<float>(), n, dmin, dinv, b_keys.as<unsigned long long>(),
                      b_lo.as<float>(), b_hi.as<float>());
-  BVH_TRY(rocprim::radix_sort_keys(b_tmp.p, tmp_sort, b_keys.as<unsigned long long>(), b_keys2.as<unsigned long long>(), (size_t)n, 0,
+  HIP_TRY(rocprim::radix_sort_keys(b_tmp.p, tmp_sort, b_keys.as<unsigned long long>(), b_keys2.as<unsigned long long>(), (size_t)n, 0,
                                    64, st));
   const unsigned long long* keys = b_keys2.as<unsigned long long>();
   if (kind == KIND_LBVH) {
-    BVH_TRY(hipMemsetAsync(b_arr.p, 0, (size_t)n * 4, st));
+    HIP_TRY(hipMemsetAsync(b_arr.p, 0, (size_t)n * 4, st));
     if (n > 1)
       hipLaunchKernelGGL(k_radix, dim3(bn), dim3(256), 0, st, keys, n, b_left.as<int>(), b_right.as<int>(), b_first.as<int>(),
                          b_last.as<int>(), b_parent.as<int>());
@@ -417,7 +395,7 @@ int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf
     hipLaunchKernelGGL(k_lbvh_ranges, dim3(bi), dim3(256), 0, st, n, b_first.as<int>(), b_last.as<int>(), b_count.as<int>(),
                        b_offset.as<int>());
   } else {
-    BVH_TRY(hipMemsetAsync(b_parent.p, 0xff, (size_t)items * 4, st));  // -1: the root keeps it
+    HIP_TRY(hipMemsetAsync(b_parent.p, 0xff, (size_t)items * 4, st));  // -1: the root keeps it
     hipLaunchKernelGGL(k_ploc_init, dim3(bn), dim3(256), 0, st, keys, n, b_lo.as<float>(), b_hi.as<float>(), b_blo.as<float>(),
                        b_bhi.as<float>(), b_count.as<int>(), b_cid[0].as<int>(), b_cbox[0].as<Box6>());
     int m = n, id_base = n - 1, cur = 0;
@@ -428,16 +406,16 @@ int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf
       const unsigned bm = (unsigned)((m + PLOC_BLOCK - 1) / PLOC_BLOCK);
       hipLaunchKernelGGL(k_ploc_nn, dim3(bm), dim3(PLOC_BLOCK), 0, st, m, b_cbox[cur].as<Box6>(), b_nn.as<int>());
       hipLaunchKernelGGL(k_ploc_mark, dim3(bm), dim3(PLOC_BLOCK), 0, st, m, b_nn.as<int>(), b_f64.as<unsigned long long>());
-      BVH_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_scan64, b_f64.as<unsigned long long>(), b_p64.as<unsigned long long>(), 0ull, (size_t)m,
+      HIP_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_scan64, b_f64.as<unsigned long long>(), b_p64.as<unsigned long long>(), 0ull, (size_t)m,
                                       rocprim::plus<unsigned long long>(), st));
       hipLaunchKernelGGL(k_ploc_apply, dim3(bm), dim3(PLOC_BLOCK), 0, st, m, id_base, b_nn.as<int>(), b_f64.as<unsigned long long>(),
                          b_p64.as<unsigned long long>(), b_cid[cur].as<int>(), b_cbox[cur].as<Box6>(), b_cid[cur ^ 1].as<int>(),
                          b_cbox[cur ^ 1].as<Box6>(), b_left.as<int>(), b_right.as<int>(), b_parent.as<int>(), b_blo.as<float>(),
                          b_bhi.as<float>(), b_count.as<int>());
       unsigned long long lastf = 0, lastp = 0;  // totals of the round: clusters kept, pairs merged
-      BVH_TRY(hipMemcpyAsync(&lastf, b_f64.as<unsigned long long>() + (m - 1), 8, hipMemcpyDeviceToHost, st));
-      BVH_TRY(hipMemcpyAsync(&lastp, b_p64.as<unsigned long long>() + (m - 1), 8, hipMemcpyDeviceToHost, st));
-      BVH_TRY(hipStreamSynchronize(st));
+      HIP_TRY(hipMemcpyAsync(&lastf, b_f64.as<unsigned long long>() + (m - 1), 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipMemcpyAsync(&lastp, b_p64.as<unsigned long long>() + (m - 1), 8, hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
       const unsigned long long tot = lastf + lastp;
       const int kept = (int)(tot & 0xffffffffull), merged = (int)(tot >> 32);
       if (merged <= 0 || kept != m - merged) return jade_fail(JADE_ERR_DEVICE, "PLOC round merged nothing");
@@ -450,31 +428,31 @@ int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf
                        b_count.as<int>(), b_offset.as<int>());
   }
   hipLaunchKernelGGL(k_flags, dim3(bi), dim3(256), 0, st, n, leaf_size, b_count.as<int>(), b_parent.as<int>(), b_flags.as<int>());
-  BVH_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_scan, b_flags.as<int>(), b_slot.as<int>(), 0, (size_t)items, rocprim::plus<int>(), st));
-  BVH_TRY(hipMemsetAsync(b_nodes.p, 0, sizeof(jade_bvh_node), st));
+  HIP_TRY(rocprim::exclusive_scan(b_tmp.p, tmp_scan, b_flags.as<int>(), b_slot.as<int>(), 0, (size_t)items, rocprim::plus<int>(), st));
+  HIP_TRY(hipMemsetAsync(b_nodes.p, 0, sizeof(jade_bvh_node), st));
   hipLaunchKernelGGL(k_emit, dim3(bi), dim3(256), 0, st, n, leaf_size, b_left.as<int>(), b_right.as<int>(), b_count.as<int>(),
                      b_offset.as<int>(), b_flags.as<int>(), b_slot.as<int>(), b_blo.as<float>(), b_bhi.as<float>(),
                      b_nodes.as<jade_bvh_node>());
   hipLaunchKernelGGL(k_order, dim3(bn), dim3(256), 0, st, keys, n, b_offset.as<int>(), b_order.as<int>());
-  BVH_TRY(hipGetLastError());
-  BVH_TRY(hipEventRecord(e1.e, st));
-  BVH_TRY(hipEventSynchronize(e1.e));
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e1.e, st));
+  HIP_TRY(hipEventSynchronize(e1.e));
   float ms = 0;
-  BVH_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
+  HIP_TRY(hipEventElapsedTime(&ms, e0.e, e1.e));
   if (build_ms) *build_ms = ms;
 
   int last_flag = 0, last_slot = 0;
-  BVH_TRY(hipMemcpy(&last_flag, b_flags.as<int>() + (items - 1), 4, hipMemcpyDeviceToHost));
-  BVH_TRY(hipMemcpy(&last_slot, b_slot.as<int>() + (items - 1), 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&last_flag, b_flags.as<int>() + (items - 1), 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&last_slot, b_slot.as<int>() + (items - 1), 4, hipMemcpyDeviceToHost));
   const int emitted = last_slot + last_flag;
   if (1 + emitted > max_nodes) return jade_fail(JADE_ERR_INVALID, "nodes_out too small (2*n + 1 always suffices)");
-  BVH_TRY(hipMemcpy(nodes_out, b_nodes.p, (size_t)(1 + emitted) * sizeof(jade_bvh_node), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(nodes_out, b_nodes.p, (size_t)(1 + emitted) * sizeof(jade_bvh_node), hipMemcpyDeviceToHost));
   // node 0: the reference's dummy record (PathTrace.cu:1557-1563)
   memset(&nodes_out[0], 0, sizeof(jade_bvh_node));
   nodes_out[0].left = 255; nodes_out[0].right = 128; nodes_out[0].n = 30;
   nodes_out[0].aa[0] = 1; nodes_out[0].aa[1] = 1; nodes_out[0].bb[1] = 1;
   *n_nodes_out = 1 + emitted;
-  BVH_TRY(hipMemcpy(order_out, b_order.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(order_out, b_order.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 }  // namespace

@@ -1,4 +1,4 @@
-// jade_denoise.hip — the denoiser's device side (include/jade_bvh.h: jade_render_guides, jade_render_denoise, jade_denoise_image).
+// jade_denoise.hip — the denoiser (include/jade_bvh.h: jade_render_guides, jade_render_denoise, jade_denoise_image): kernels and host side.
 //
 //   k_pixel_variance  one block of 256 threads per tile: each pixel's lanes of partial sums -> the variance of its mean luminance
 //                     (lane_moments, jade_lanes.h: k_tile_error's statements)
@@ -15,13 +15,14 @@
 //
 // The filter's record of a pixel is three float4: A = {r, g, b, variance} (the only part a pass writes), N = {nhat, depth},
 // L = {albedo, 0}.  A tap reads 48 B, from L2: a 5x5 footprint at step 2^i touches the same lines for neighbouring pixels.
-// The host glue sits beside jade_render_step in jade_hip.hip: the guide pass launches k_trace, which lives there.
-#include <hip/hip_runtime.h>
-
+// The guide pass's rays are walked by k_trace, which lives in jade_hip.hip: launch_trace (jade_runtime.h).
 #include <math.h>
 
-#include "jade_device.h"
+#include <cmath>
+#include <cstring>
+
 #include "jade_lanes.h"
+#include "jade_runtime.h"
 
 #define JADE_DN_BLOCK 256
 
@@ -240,67 +241,272 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_dn_out(const float4* A, int n
   if (out_bgr) tone_pack_bgr8(jv(a.x, a.y, a.z), tonemap, limit, true, out_bgr + 3 * (size_t)p);
 }
 
-// ------------------------------------------------------------------------------------------------------------- launches --
-// For jade_hip.hip (hidden: libjade_hip.so exports only what the headers declare).
+// ------------------------------------------------------------------------------------------------------------ host side --
 
-#define DN_HIDDEN __attribute__((visibility("hidden")))
 static inline unsigned dn_grid(size_t n) { return (unsigned)((n + JADE_DN_BLOCK - 1) / JADE_DN_BLOCK); }
 
-DN_HIDDEN hipError_t denoise_variance(hipStream_t stream, uint32_t n_tiles, const PathState& P, const int32_t* tile_n, int64_t n_all, float* var_out) {
-  if (n_tiles == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_pixel_variance, dim3(n_tiles), dim3(JADE_ERR_BLOCK), 0, stream, P, tile_n, n_all, var_out);
-  return hipGetLastError();
+void jade_denoise_defaults(jade_denoise_params* p) {
+  if (!p) return;
+  // of SVGF's 5 passes and sigma_l = 4 and the sweep around them, 3 passes and sigma_l = 2 gave the lowest relMSE of the
+  // denoised 64-spp frames of C2 and C3 (profiles/denoise_ab.json); sigma_n made no difference there and stays SVGF's 128
+  p->iterations = 3;
+  p->guide_spp = 4;
+  p->sigma_luminance = 2.0f;
+  p->sigma_normal = 128.0f;
+  p->sigma_depth = 0.1f;
+  p->sigma_albedo = 0.1f;
 }
 
-DN_HIDDEN hipError_t denoise_guide_camera(hipStream_t stream, const PathState& G, const RenderConst& R, const int32_t* tile_ids, const uint32_t* list,
-                                          uint32_t n, uint32_t sidx, float4* state, uint32_t* mirrors) {
-  if (n == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_guide_camera, dim3(dn_grid(n)), dim3(JADE_DN_BLOCK), 0, stream, G, R, tile_ids, list, n, sidx, state, mirrors);
-  return hipGetLastError();
+static int dn_check_params(const jade_denoise_params* dp) {
+  if (!dp) return jade_fail(JADE_ERR_INVALID, "null denoise parameters");
+  if (dp->iterations < 0 || dp->iterations > 8) return jade_fail(JADE_ERR_INVALID, "iterations must be 0..8");
+  if (dp->guide_spp < 1 || dp->guide_spp > 64) return jade_fail(JADE_ERR_INVALID, "guide_spp must be 1..64");
+  if (!std::isfinite(dp->sigma_luminance) || !(dp->sigma_luminance > 0.0f)) return jade_fail(JADE_ERR_INVALID, "sigma_luminance must be finite and > 0");
+  if (!std::isfinite(dp->sigma_normal) || !(dp->sigma_normal >= 0.0f)) return jade_fail(JADE_ERR_INVALID, "sigma_normal must be finite and >= 0");
+  if (!std::isfinite(dp->sigma_depth) || !(dp->sigma_depth > 0.0f)) return jade_fail(JADE_ERR_INVALID, "sigma_depth must be finite and > 0");
+  if (!std::isfinite(dp->sigma_albedo) || !(dp->sigma_albedo > 0.0f)) return jade_fail(JADE_ERR_INVALID, "sigma_albedo must be finite and > 0");
+  return JADE_OK;
 }
 
-DN_HIDDEN hipError_t denoise_guide_hits(hipStream_t stream, uint32_t n_max, const DevScene& S, const PathState& G, const uint32_t* queue, const uint32_t* count,
-                                        float4* state, uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g, uint32_t* next_queue,
-                                        uint32_t* next_count) {
-  if (n_max == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_guide_hits, dim3(dn_grid(n_max)), dim3(JADE_DN_BLOCK), 0, stream, S, G, queue, count, state, mirrors, acc_az, acc_n, last, inv_g,
-                     next_queue, next_count);
-  return hipGetLastError();
+// grow-only: the denoiser's buffers are allocated on first use and kept (they do not come out of the records' budget, which
+// jade_render_begin sizes before any of them exists)
+static hipError_t dn_alloc(DevBuf& b, size_t bytes) { return (b.p && b.bytes >= bytes) ? hipSuccess : b.alloc(bytes); }
+
+// Finish the paths the last step carried over, as resolve does; their work counters wait in dn_carried for the next step.
+static int dn_flush(jade_scene* s) {
+  jade_stats st{};
+  if (int rc = jade_render_flush(s, &st)) return rc;
+  s->dn_carried = st;  // (the flush took over what dn_carried held)
+  return JADE_OK;
 }
 
-DN_HIDDEN hipError_t denoise_pack_tiles(hipStream_t stream, const RenderConst& R, const int32_t* tile_ids, int npx, const float* rgb, const float* var,
-                                        const float4* acc_az, const float4* acc_n, float4* A, float4* N, float4* L) {
-  if (npx == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_dn_pack_tiles, dim3(dn_grid((size_t)npx)), dim3(JADE_DN_BLOCK), 0, stream, R, tile_ids, npx, rgb, var, acc_az, acc_n, A, N, L);
-  return hipGetLastError();
+// each owned tile's sample count: its own after jade_render_adaptive, otherwise spp_done
+static std::vector<int32_t> dn_tile_counts(const jade_scene* s) {
+  if (!s->tile_n.empty()) return s->tile_n;
+  return std::vector<int32_t>(s->tile_ids.size(), (int32_t)std::min<int64_t>(s->spp_done, INT32_MAX));
 }
 
-DN_HIDDEN hipError_t denoise_pack_image(hipStream_t stream, int npix, const float* rgb, const float* var, const float* alb, const float* nrm, const float* dep,
-                                        float4* A, float4* N, float4* L) {
-  if (npix == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_dn_pack_image, dim3(dn_grid((size_t)npix)), dim3(JADE_DN_BLOCK), 0, stream, npix, rgb, var, alb, nrm, dep, A, N, L);
-  return hipGetLastError();
+// the variance of every owned pixel into b_dn_var (compact layout)
+static int dn_variance(jade_scene* s) {
+  const size_t nt = s->tile_ids.size();
+  HIP_TRY(dn_alloc(s->b_dn_var, (size_t)s->ps.npx * 4));
+  DevBuf b_n;
+  const int32_t* tile_n = nullptr;
+  if (!s->tile_n.empty()) {
+    HIP_TRY(upload(b_n, s->tile_n.data(), nt, s->stream));
+    tile_n = b_n.as<int32_t>();
+  }
+  hipLaunchKernelGGL(k_pixel_variance, dim3((unsigned)nt), dim3(JADE_ERR_BLOCK), 0, s->stream, s->ps, tile_n, (int64_t)s->spp_done, s->b_dn_var.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipStreamSynchronize(s->stream));  // (b_n goes out of scope)
+  return JADE_OK;
 }
 
-// the passes, ping-pong between A[0] and A[1]; returns which of the two holds the result
-DN_HIDDEN hipError_t denoise_filter(hipStream_t stream, int W, int H, int iterations, float sl, float sn, float sz, float sa, float4* A0, float4* A1,
-                                    const float4* N, const float4* L, int* result) {
-  float4* a[2] = {A0, A1};
-  int cur = 0;
-  const DnSigma sg{sl, sn, sz, sa};
+// The guide pass: G camera samples of every owned in-image pixel, one sample after the other, into b_dn_az = {albedo, depth} and
+// b_dn_n = {normal, 0} (compact layout).  k_trace itself walks the rays (reference walk, nearest hit) on a throw-away PathState, with
+// queue words and work counters of its own: neither the render's state nor its statistics see these rays.  The host waits once per
+// k_trace launch, for the number of mirror continuations (a sample ends after at most JADE_MAX_FULL_REFLEX_TIME + 1 launches).
+static int dn_guides(jade_scene* s, int G) {
+  const size_t n = (size_t)s->ps.npx;
+  HIP_TRY(dn_alloc(s->b_dn_orgs, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_slot, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_hitp, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_state, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_mirrors, n * 4));
+  HIP_TRY(dn_alloc(s->b_dn_list, n * 4));
+  HIP_TRY(dn_alloc(s->b_dn_q[0], n * 4));
+  HIP_TRY(dn_alloc(s->b_dn_q[1], n * 4));
+  HIP_TRY(dn_alloc(s->b_dn_az, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_n, n * 16));
+  HIP_TRY(dn_alloc(s->b_dn_ctl, 2 * sizeof(QueueCtl)));
+  HIP_TRY(dn_alloc(s->b_dn_ctr, sizeof(DevCounters) * JADE_CTR_SHARDS));
+  if (!s->b_spill.p)
+    HIP_TRY(s->b_spill.alloc((size_t)(JADE_BVH_STACK_CAPACITY - JADE_LDS_STACK) * s->trace_blocks * JADE_TRACE_BLOCK * 4));
+  // the owned in-image pixels, in owned order: the first queue of every sample
+  std::vector<uint32_t> list;
+  list.reserve(n);
+  for_each_owned_tile(s->tile_ids, s->rp.width, s->rp.height, [&](size_t t, int, int, int ww, int hh) {
+    for (int l = 0; l < 256; ++l)
+      if ((l & 15) < ww && (l >> 4) < hh) list.push_back((uint32_t)(t * 256 + (size_t)l));
+  });
+  const uint32_t n_in = (uint32_t)list.size();
+  HIP_TRY(hipMemcpyAsync(s->b_dn_list.p, list.data(), (size_t)n_in * 4, hipMemcpyHostToDevice, s->stream));
+  HIP_TRY(hipMemsetAsync(s->b_dn_az.p, 0, n * 16, s->stream));
+  HIP_TRY(hipMemsetAsync(s->b_dn_n.p, 0, n * 16, s->stream));
+  PathState g{};
+  g.npix = (int32_t)n;
+  g.npx = (int32_t)n;
+  g.rpp = 1;
+  g.nslots = 1;
+  g.orgs = s->b_dn_orgs.as<float4>();
+  g.slot = s->b_dn_slot.as<float4>();
+  g.hitp = s->b_dn_hitp.as<float4>();
+  g.write_all_hits = 1u;  // every ray reports point and distance (as jade_trace_rays)
+  g.early_exit = 0u;      // the reference walk: the nearest hit
+  memcpy(g.eye, s->ps.eye, sizeof g.eye);
+  QueueCtl* qc = s->b_dn_ctl.as<QueueCtl>();
+  float4* state = s->b_dn_state.as<float4>();
+  uint32_t* mirrors = s->b_dn_mirrors.as<uint32_t>();
+  const float inv_g = (float)(1.0 / (double)G);
+  for (int smp = 0; smp < G && n_in; ++smp) {
+    hipLaunchKernelGGL(k_guide_camera, dim3(dn_grid(n_in)), dim3(JADE_DN_BLOCK), 0, s->stream, g, s->rc, s->b_tiles.as<int32_t>(), s->b_dn_list.as<uint32_t>(),
+                       n_in, (uint32_t)smp, state, mirrors);
+    HIP_TRY(hipGetLastError());
+    QueueCtl q0{};
+    q0.count = n_in;
+    HIP_TRY(hipMemcpyAsync(qc, &q0, sizeof q0, hipMemcpyHostToDevice, s->stream));
+    const uint32_t* queue = s->b_dn_list.as<uint32_t>();
+    uint32_t count = n_in;
+    int cur = 0, qi = 0;
+    for (;;) {
+      launch_trace(s, g, queue, qc + cur, s->b_spill.as<uint32_t>(), s->b_dn_ctr.as<DevCounters>(), count);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipMemsetAsync(qc + (cur ^ 1), 0, sizeof(QueueCtl), s->stream));
+      uint32_t* next_queue = s->b_dn_q[qi].as<uint32_t>();
+      hipLaunchKernelGGL(k_guide_hits, dim3(dn_grid(count)), dim3(JADE_DN_BLOCK), 0, s->stream, s->dev, g, queue, &qc[cur].count, state, mirrors,
+                         s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count);
+      HIP_TRY(hipGetLastError());
+      uint32_t next = 0;
+      HIP_TRY(hipMemcpyAsync(&next, &qc[cur ^ 1].count, 4, hipMemcpyDeviceToHost, s->stream));
+      HIP_TRY(hipStreamSynchronize(s->stream));
+      if (next == 0) break;
+      if (next > count) return jade_fail(JADE_ERR_DEVICE, "guide pass: the mirror queue grew");
+      queue = next_queue;
+      count = next;
+      cur ^= 1;
+      qi ^= 1;
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// compact tiles (npx entries of `stride` floats, the first `comps` of which are wanted; pixel t*256 + ly*16 + lx) -> the caller's image,
+// other ranks' pixels untouched
+static void dn_scatter(const jade_scene* s, const float* compact, int stride, int comps, float* out) {
+  const int W = s->rp.width;
+  for_each_owned_tile(s->tile_ids, W, s->rp.height, [&](size_t t, int x0, int y0, int ww, int hh) {
+    for (int ly = 0; ly < hh; ++ly)
+      for (int lx = 0; lx < ww; ++lx)
+        for (int k = 0; k < comps; ++k)
+          out[((size_t)(y0 + ly) * W + x0 + lx) * comps + k] = compact[(t * 256 + (size_t)ly * 16 + lx) * stride + k];
+  });
+}
+
+int jade_render_guides(jade_scene* s, int32_t guide_spp, float* out_albedo, float* out_normal, float* out_depth, float* out_variance) {
+  if (!s || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (guide_spp < 1 || guide_spp > 64) return jade_fail(JADE_ERR_INVALID, "guide_spp must be 1..64");
+  if (s->spp_done <= 0) return jade_fail(JADE_ERR_INVALID, "no samples rendered yet");
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = dn_flush(s)) return rc;
+  const size_t npx = (size_t)s->ps.npx;
+  if (npx == 0) return JADE_OK;
+  if (out_variance) {
+    if (int rc = dn_variance(s)) return rc;
+    std::vector<float> v(npx);
+    HIP_TRY(hipMemcpyAsync(v.data(), s->b_dn_var.p, npx * 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    dn_scatter(s, v.data(), 1, 1, out_variance);
+  }
+  if (out_albedo || out_normal || out_depth) {
+    if (int rc = dn_guides(s, guide_spp)) return rc;
+    std::vector<float> az(npx * 4), nn(npx * 4);
+    HIP_TRY(hipMemcpyAsync(az.data(), s->b_dn_az.p, npx * 16, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipMemcpyAsync(nn.data(), s->b_dn_n.p, npx * 16, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (out_albedo) dn_scatter(s, az.data(), 4, 3, out_albedo);
+    if (out_normal) dn_scatter(s, nn.data(), 4, 3, out_normal);
+    if (out_depth) dn_scatter(s, az.data() + 3, 4, 1, out_depth);
+  }
+  return JADE_OK;
+}
+
+// The filter on records already packed in b_dn_rec[0] (colour, variance), [2] (normal, depth), [3] (albedo): the passes, then one
+// output kernel into b_dn_rgb / b_dn_bgr (image layout).
+static int dn_filter_out(hipStream_t stream, int W, int H, const jade_denoise_params* dp, int tonemap, float limit, float* dev_rgb,
+                         uint8_t* dev_bgr, float4* const* rec) {
+  int cur = 0;  // the passes, ping-pong between rec[0] and rec[1]
+  const DnSigma sg{dp->sigma_luminance, dp->sigma_normal, dp->sigma_depth, dp->sigma_albedo};
   const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16));
-  for (int i = 0; i < iterations; ++i) {
-    hipLaunchKernelGGL(k_atrous, grid, dim3(JADE_DN_BLOCK), 0, stream, a[cur], N, L, a[cur ^ 1], W, H, 1 << i, sg);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+  for (int i = 0; i < dp->iterations; ++i) {
+    hipLaunchKernelGGL(k_atrous, grid, dim3(JADE_DN_BLOCK), 0, stream, rec[cur], rec[2], rec[3], rec[cur ^ 1], W, H, 1 << i, sg);
+    HIP_TRY(hipGetLastError());
     cur ^= 1;
   }
-  *result = cur;
-  return hipSuccess;
+  hipLaunchKernelGGL(k_dn_out, dim3(dn_grid((size_t)W * H)), dim3(JADE_DN_BLOCK), 0, stream, rec[cur], W * H, tonemap, limit, dev_rgb, dev_bgr);
+  HIP_TRY(hipGetLastError());
+  return JADE_OK;
 }
 
-DN_HIDDEN hipError_t denoise_out(hipStream_t stream, const float4* A, int npix, int tonemap, float limit, float* out_rgb, uint8_t* out_bgr) {
-  if (npix == 0) return hipSuccess;
-  hipLaunchKernelGGL(k_dn_out, dim3(dn_grid((size_t)npix)), dim3(JADE_DN_BLOCK), 0, stream, A, npix, tonemap, limit, out_rgb, out_bgr);
-  return hipGetLastError();
+int jade_render_denoise(jade_scene* s, const jade_denoise_params* dp, int tonemap, float limit, float* out_rgb, uint8_t* out_bgr8) {
+  if (!s || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (int rc = dn_check_params(dp)) return rc;
+  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return jade_fail(JADE_ERR_INVALID, "unknown tone operator");
+  if (s->spp_done <= 0) return jade_fail(JADE_ERR_INVALID, "no samples rendered yet");
+  if (s->rp.tile_nranks > 1)
+    return jade_fail(JADE_ERR_UNSUPPORTED, "jade_render_denoise needs the full frame: gather rgb and jade_render_guides, then jade_denoise_image");
+  for (int32_t n : dn_tile_counts(s))
+    if (!(n >= 2 && (n <= JADE_SAMPLE_LANES || n % JADE_SAMPLE_LANES == 0)))
+      return jade_fail(JADE_ERR_INVALID, "a tile's sample count (" + std::to_string(n) + ") cannot give a variance: n >= 2, and a multiple of " +
+                                        std::to_string(JADE_SAMPLE_LANES) + " above it");
+  HIP_TRY(hipSetDevice(s->device));
+  if (int rc = dn_flush(s)) return rc;
+  const int npx = s->ps.npx;
+  if (npx == 0) return JADE_OK;
+  const int W = s->rp.width, H = s->rp.height;
+  const size_t npix = (size_t)W * (size_t)H;
+  // the mean (k_resolve, compact tiles), the variance, the guides
+  HIP_TRY(dn_alloc(s->b_out_rgb, (size_t)npx * 12));
+  if (int rc = resolve_to(s, JADE_TONEMAP_ACES, 0.0f, s->b_out_rgb.as<float>(), nullptr, s->stream)) return rc;
+  if (int rc = dn_variance(s)) return rc;
+  if (int rc = dn_guides(s, dp->guide_spp)) return rc;
+  // scattered once into the filter's records, image layout
+  for (DevBuf& b : s->b_dn_rec) HIP_TRY(dn_alloc(b, npix * 16));
+  float4* rec[4] = {s->b_dn_rec[0].as<float4>(), s->b_dn_rec[1].as<float4>(), s->b_dn_rec[2].as<float4>(), s->b_dn_rec[3].as<float4>()};
+  hipLaunchKernelGGL(k_dn_pack_tiles, dim3(dn_grid((size_t)npx)), dim3(JADE_DN_BLOCK), 0, s->stream, s->rc, s->b_tiles.as<int32_t>(), npx, s->b_out_rgb.as<float>(),
+                     s->b_dn_var.as<float>(), s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), rec[0], rec[2], rec[3]);
+  HIP_TRY(hipGetLastError());
+  if (out_rgb) HIP_TRY(dn_alloc(s->b_dn_rgb, npix * 12));
+  if (out_bgr8) HIP_TRY(dn_alloc(s->b_dn_bgr, npix * 3));
+  if (int rc = dn_filter_out(s->stream, W, H, dp, tonemap, limit, out_rgb ? s->b_dn_rgb.as<float>() : nullptr,
+                             out_bgr8 ? s->b_dn_bgr.as<uint8_t>() : nullptr, rec))
+    return rc;
+  if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, s->b_dn_rgb.p, npix * 12, hipMemcpyDeviceToHost, s->stream));
+  if (out_bgr8) HIP_TRY(hipMemcpyAsync(out_bgr8, s->b_dn_bgr.p, npix * 3, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+int jade_denoise_image(int device_id, int32_t width, int32_t height, const float* rgb, const float* variance, const float* albedo, const float* normal,
+                       const float* depth, const jade_denoise_params* dp, float* out_rgb) {
+  if (!rgb || !variance || !albedo || !normal || !depth || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 3) return jade_fail(JADE_ERR_INVALID, "bad image size");
+  if (int rc = dn_check_params(dp)) return rc;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return jade_fail(JADE_ERR_DEVICE, "no HIP device");
+  if (device_id < 0 || device_id >= ndev) return jade_fail(JADE_ERR_INVALID, "device_id out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t npix = (size_t)width * (size_t)height;
+  hipStream_t stream = nullptr;
+  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+  struct StreamGuard {
+    hipStream_t s;
+    ~StreamGuard() { (void)hipStreamDestroy(s); }
+  } guard{stream};
+  DevBuf b_rgb, b_var, b_alb, b_nrm, b_dep, b_rec[4], b_out;
+  HIP_TRY(upload(b_rgb, rgb, npix * 3, stream));
+  HIP_TRY(upload(b_var, variance, npix, stream));
+  HIP_TRY(upload(b_alb, albedo, npix * 3, stream));
+  HIP_TRY(upload(b_nrm, normal, npix * 3, stream));
+  HIP_TRY(upload(b_dep, depth, npix, stream));
+  for (DevBuf& b : b_rec) HIP_TRY(b.alloc(npix * 16));
+  HIP_TRY(b_out.alloc(npix * 12));
+  float4* rec[4] = {b_rec[0].as<float4>(), b_rec[1].as<float4>(), b_rec[2].as<float4>(), b_rec[3].as<float4>()};
+  hipLaunchKernelGGL(k_dn_pack_image, dim3(dn_grid(npix)), dim3(JADE_DN_BLOCK), 0, stream, (int)npix, b_rgb.as<float>(), b_var.as<float>(), b_alb.as<float>(),
+                     b_nrm.as<float>(), b_dep.as<float>(), rec[0], rec[2], rec[3]);
+  HIP_TRY(hipGetLastError());
+  if (int rc = dn_filter_out(stream, width, height, dp, JADE_TONEMAP_ACES, 0.0f, b_out.as<float>(), nullptr, rec)) return rc;
+  HIP_TRY(hipMemcpyAsync(out_rgb, b_out.p, npix * 12, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return JADE_OK;
 }

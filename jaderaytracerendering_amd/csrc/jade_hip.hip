@@ -25,46 +25,32 @@
 // finished its samples), or until so few are active that the step hands them to the
 // next one (jade_render_flush).  There is no CPU fallback: if HIP is unavailable the
 // entry points return JADE_ERR_DEVICE.
+//
+// This file: the render kernels above, then the host side that drives them - jade_scene_create (upload, selftest, size_grids),
+// jade_render_begin, run_passes (the schedule of a step: PassRun and its pieces), step / flush / resolve, jade_trace_rays and
+// the JADE_DEBUG_EXPORTS entry points.  The rest of libjade_hip.so's host side sits beside the kernels it drives:
+//   jade_runtime.h       what the files share: jade_fail, HIP_TRY, DevBuf, DevEvent, Tunables, struct jade_scene, and the two
+//                        functions through which another file reaches a kernel of this one (launch_trace, resolve_to)
+//   jade_scene_prep.hip  prepare_scene: the caller's scene -> the records uploaded here; host only, no HIP call
+//   jade_adaptive.hip    jade_render_adaptive, jade_render_error + k_tile_error
+//   jade_denoise.hip     jade_render_guides, jade_render_denoise, jade_denoise_image + their kernels
+//   jade_multi.hip       jade_render_multi and its RCCL gather
+//   jade_bvh.hip         the BVH builders
 #include <hip/hip_runtime.h>
-
-#include <dlfcn.h>
-#include <rccl/rccl.h>  // types only: the library is loaded on first use (jade_render_multi on distinct devices)
 
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <thread>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "jade_bvh.h"
-#include "jade_device.h"
+#include "jade_runtime.h"
 #include "jade_shade.h"
 #include "jade_trace.h"
-
-// jade_adaptive.hip: k_tile_error's launch (jade_render_adaptive, jade_render_error)
-hipError_t adaptive_tile_error(hipStream_t stream, uint32_t n_tiles, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
-                               const uint32_t* list, const int32_t* tile_n, double error_floor, float rel_error, int32_t target,
-                               uint32_t* next_list, uint32_t* next_count, int32_t* tile_spp, float* err_out, uint32_t* not_idle);
-// jade_denoise.hip: the denoiser's launches (jade_render_guides, jade_render_denoise, jade_denoise_image)
-hipError_t denoise_variance(hipStream_t stream, uint32_t n_tiles, const PathState& P, const int32_t* tile_n, int64_t n_all, float* var_out);
-hipError_t denoise_guide_camera(hipStream_t stream, const PathState& G, const RenderConst& R, const int32_t* tile_ids, const uint32_t* list, uint32_t n,
-                                uint32_t sidx, float4* state, uint32_t* mirrors);
-hipError_t denoise_guide_hits(hipStream_t stream, uint32_t n_max, const DevScene& S, const PathState& G, const uint32_t* queue, const uint32_t* count,
-                              float4* state, uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g, uint32_t* next_queue,
-                              uint32_t* next_count);
-hipError_t denoise_pack_tiles(hipStream_t stream, const RenderConst& R, const int32_t* tile_ids, int npx, const float* rgb, const float* var,
-                              const float4* acc_az, const float4* acc_n, float4* A, float4* N, float4* L);
-hipError_t denoise_pack_image(hipStream_t stream, int npix, const float* rgb, const float* var, const float* alb, const float* nrm, const float* dep,
-                              float4* A, float4* N, float4* L);
-hipError_t denoise_filter(hipStream_t stream, int W, int H, int iterations, float sl, float sn, float sz, float sa, float4* A0, float4* A1,
-                          const float4* N, const float4* L, int* result);
-hipError_t denoise_out(hipStream_t stream, const float4* A, int npix, int tonemap, float limit, float* out_rgb, uint8_t* out_bgr);
 
 // ------------------------------------------------------------------ kernels --
 
@@ -93,14 +79,6 @@ static __device__ __forceinline__ void nt_st4(float4* p, float x, float y, float
 }
 
 
-struct alignas(8) QueueCtl {
-  uint32_t count;   // rays emitted by the last shade pass          } one 64-bit word: k_shade reserves its queue
-  uint32_t active;  // records with rays in flight after that pass } and list space with ONE atomic per block
-  uint32_t next;    // next unclaimed queue entry (trace)
-  uint32_t heavy;   // records k_shade_lean handed to k_shade this pass
-  uint32_t fp_bad;  // jade_fp_selftest result (checked once)
-  uint32_t pad[3];
-};
 
 // how many lanes of mask m sit below this one (v_mbcnt_lo + v_mbcnt_hi: two instructions, no per-lane mask kept in registers)
 static __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
@@ -219,22 +197,6 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
     if (wantm & (1u << j)) active_out[blk + sh_cnt[j * NW + w] + off[j]] = (uint32_t)(base + (size_t)j * JADE_ARM_BLOCK + threadIdx.x);
 }
 
-// A step hands its unfinished paths to the next step (or to flush) once fewer than JADE_CARRY_FRACTION of the records it
-// started with are still active.  The paths left are the long ones (jade: ~10 bounces against 1-2 for the sky and the
-// mirror floor): finishing them inside every step means dozens of thin passes per step, whose sparse record accesses
-// waste most of every cache line; carried over, they ride along with the next step's full passes and the thin tail
-// is paid once per render (round 1, C3: 364 -> 286 k_trace launches per 4096 spp, +3 % Mray/s at 0.02 against none).  What
-// is carried is work moved, not saved: the flush at the end of a render finishes it, so the fraction sets how long that
-// flush is - round 3, 4 x 1024 spp of C3 with the flush inside the clock: 0.001 / 0.002 / 0.003 / 0.005 / 0.02 / 0.05 = 708.6 /
-// 707.9 / 705.5 / 705.4 / 709.5 / 698 + 167 ms per step, with a final flush of 32 / 40 / 49 / 67 / 210 / 669 ms.  0.003: as fast as
-// any, and a render's last call returns in 49 ms.  JADE_CARRY_FRACTION in the environment overrides it (0 = only the
-// absolute floor below).
-#ifndef JADE_CARRY_FRACTION
-#define JADE_CARRY_FRACTION 0.003
-#endif
-#ifndef JADE_CARRY_RECORDS
-#define JADE_CARRY_RECORDS 32768u /* ... and in any case once fewer than this (and < 0.1 % of its records) are active */
-#endif
 #ifndef JADE_SHADE_BLOCK
 #define JADE_SHADE_BLOCK 512 /* threads per k_shade block: one queue + one list atomic per block (512: +1.8 % over 256; 1024: none) */
 #endif
@@ -902,7 +864,6 @@ __global__ void k_iota(uint32_t* v, uint32_t n) {
   for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) v[i] = i;
 }
 
-#define JADE_CTL_RING 96 /* QueueCtl records: entry 0 for passes the host follows one by one, all of them for a batch of passes (round 4: 96 - a 1024-spp step of C3 is ~65 passes down to its carry-over point, the flush ~65 more down to k_tail's threshold: one batch, one wait each; the launches behind the stop are empty) */
 #ifndef JADE_TRACE_WAVES
 #define JADE_TRACE_WAVES 5 /* waves per SIMD the register allocation leaves room for: 5 = at most 96 VGPRs (12 bytes of scratch) and 5 x 31 KB of LDS per CU.  Round 3, same process, C3 / statue close-up: 4 waves (102 VGPRs) 133.6 / 1037 ms of k_trace per 256-spp step, 5 waves 126.9 / 983 (round 2's "5 and 6 blocks per CU are no faster" was measured on a 102-VGPR build, which the hardware never ran at more than 4) */
 #endif
@@ -1253,9 +1214,6 @@ __global__ __launch_bounds__(JADE_TRACE_BLOCK, JADE_TRACE_WIDE_WAVES) void k_tra
 }
 #ifndef JADE_TAIL_WAVES
 #define JADE_TAIL_WAVES 2 /* k_tail holds k_shade's registers and k_trace's at once (152 VGPRs; at 4 waves per SIMD it spills 372 bytes); at most a few hundred waves ever run, so occupancy is not what it needs */
-#endif
-#ifndef JADE_TAIL_MAX
-#define JADE_TAIL_MAX 32768u /* records: a shorter active list is finished by k_tail instead of by further passes */
 #endif
 // k_tail: the end of a render's (or a small render's) paths in ONE launch - see TailArgs.  Binary units only: the walk is the
 // reference's in every mode, and early exits work as in k_trace (the limit travels in the slot).
@@ -1910,296 +1868,23 @@ __global__ void k_resolve(PathState P, RenderConst R, const int32_t* tile_ids, c
 // ---------------------------------------------------------------- host side --
 
 static thread_local std::string g_err;
-int jade_fail(int code, const std::string& msg) {  // shared with jade_bvh.hip
+int jade_fail(int code, const std::string& msg) {  // jade_runtime.h
   g_err = msg;
   return code;
 }
-static int fail(int code, const std::string& msg) { return jade_fail(code, msg); }
-#define HIP_TRY(expr)                                                                      \
-  do {                                                                                     \
-    hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(e_ == hipErrorOutOfMemory ? JADE_ERR_NOMEM : JADE_ERR_DEVICE,            \
-                  std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-  } while (0)
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    bytes = 0;
-    const hipError_t e = hipMalloc(&p, n ? n : 16);
-    if (e == hipSuccess) bytes = n;
-    else p = nullptr;
-    return e;
-  }
-  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-struct DevEvent {  // an event that is destroyed on every return path
-  hipEvent_t e = nullptr;
-  ~DevEvent() { if (e) (void)hipEventDestroy(e); }
-  hipError_t create() { return hipEventCreate(&e); }
-};
-
-#ifndef JADE_SORT_GEOMETRY_BYTES
-#define JADE_SORT_GEOMETRY_BYTES ((size_t)16 << 20) /* node + pair records above which the ray queue is ordered by default: four XCD L2s' worth */
-#endif
 #ifndef JADE_PACKET_GIVE_UP_LIMIT
 #define JADE_PACKET_GIVE_UP_LIMIT 0.25 /* share of a step's packets given up above which the next steps of the render use the per-lane first pass */
 #endif
-#ifndef JADE_PACKET_BUDGET
-#define JADE_PACKET_BUDGET 32 /* C3: k_light 153 / 159 / 167 / 181 ms per step at 16 / 32 / 64 / 128, and the step as a whole fastest at 32 (a lower budget hands more samples to the wavefront passes); C5: 32 / 33 / 36 ms at 16 / 32 / 64 */
-#endif
-// Development switches, read from the environment ONCE, at jade_scene_create (the product path reads no environment
-// variable per call).  Every one of them changes the schedule only, never a result (tests/test_gpu_parity.py).
-struct Tunables {
-  bool shade_split = true;    // JADE_SHADE_SPLIT=0: k_shade alone over the active list from the first pass on
-  bool fused = true;          // JADE_FUSED=0: the step's first pass as k_shade_lean + k_shade + k_trace instead of k_light
-  bool batching = true;       // JADE_BATCH=0: the host follows every pass
-  bool carry = true;          // JADE_CARRY=0: every step finishes all its paths
-  double carry_frac = JADE_CARRY_FRACTION;
-  bool log_passes = false;    // JADE_LOG_PASSES: one line per pass on stderr (forces one host wait per pass)
-  bool pixel_rotate = false;  // JADE_PIXEL_ROTATE=1
-  int records_per_pixel = 0;  // JADE_RECORDS_PER_PIXEL: test hook, results must not depend on it
-  int trace_blocks_per_cu = 0;  // JADE_TRACE_BLOCKS_PER_CU: occupancy sweeps
-  bool force_rccl = false;    // JADE_FORCE_RCCL=1 (tests): the RCCL path for a single share too
-  bool sort_keys_kernel = false;  // JADE_SORT_KEYS_KERNEL=1: the keys of an ordered queue come from k_ray_keys (a kernel per pass) instead of from the queueing kernel
-  int sort_mode = -1;         // JADE_SORT: order the ray queue by (kind, source triangle, octant) before every k_trace launch (host-followed
-                              // passes): 1 always, 0 never, unset = when the traversal's records do not fit the L2 (jade_scene.sort_rays)
-  uint32_t sort_min = 65536;  // JADE_SORT_MIN: queues shorter than this are traced as they are
-  bool light_packet = true;   // JADE_LIGHT_PACKET=0: the fused first pass walks its rays per lane (k_light) instead of as packets
-  int packet_budget = JADE_PACKET_BUDGET;  // JADE_PACKET_BUDGET: records a packet may read before it is given up and walked per lane
-  int wide_mode = -1;         // JADE_WIDE: with early exits k_trace walks four grandchildren per visit (k_trace_wide): 1 always, 0 never, unset =
-                              // when the traversal's records do not fit the L2 (the rule of sort_mode; jade_scene_create then builds wide records)
-  bool ray_records = true;    // JADE_RAY_RECORDS=0: k_trace's refill gathers every ray through its queue entry (before round 4)
-  bool shade_binned = false;  // JADE_SHADE_BINNED=1: k_shade_binned - the records of a block dealt by branch through LDS (measured level with k_shade: DESIGN.md 3.4)
-  bool tail = true;           // JADE_TAIL=0: no k_tail - the last paths are finished by passes, as before round 4
-  uint32_t tail_max = JADE_TAIL_MAX;  // JADE_TAIL_MAX: active records at or below which k_tail takes over
-  bool anyhit = true;         // JADE_ANYHIT=0: no occluder cache (JADE_WALK_EARLY_EXIT_CACHED then walks as JADE_WALK_EARLY_EXIT)
-  void read() {
-    auto flag0 = [](const char* n) { const char* e = getenv(n); return e && atoi(e) == 0; };
-    anyhit = !flag0("JADE_ANYHIT");
-    tail = !flag0("JADE_TAIL");
-    if (const char* e = getenv("JADE_TAIL_MAX")) tail_max = (uint32_t)atoi(e);
-    auto flag1 = [](const char* n) { const char* e = getenv(n); return e && atoi(e) > 0; };
-    shade_binned = flag1("JADE_SHADE_BINNED");
-    ray_records = !flag0("JADE_RAY_RECORDS");
-    shade_split = !flag0("JADE_SHADE_SPLIT");
-    fused = shade_split && !flag0("JADE_FUSED");
-    batching = !flag0("JADE_BATCH");
-    carry = !flag0("JADE_CARRY");
-    if (const char* e = getenv("JADE_CARRY_FRACTION")) carry_frac = atof(e);
-    log_passes = getenv("JADE_LOG_PASSES") != nullptr;
-    pixel_rotate = flag1("JADE_PIXEL_ROTATE");
-    if (const char* e = getenv("JADE_RECORDS_PER_PIXEL")) records_per_pixel = atoi(e);
-    if (const char* e = getenv("JADE_TRACE_BLOCKS_PER_CU")) trace_blocks_per_cu = atoi(e);
-    force_rccl = getenv("JADE_FORCE_RCCL") != nullptr;
-    light_packet = !flag0("JADE_LIGHT_PACKET");
-    if (const char* e = getenv("JADE_SORT")) sort_mode = atoi(e) > 0 ? 1 : 0;
-    if (const char* e = getenv("JADE_SORT_KEYS_KERNEL")) sort_keys_kernel = atoi(e) > 0;
-    if (const char* e = getenv("JADE_SORT_MIN")) sort_min = (uint32_t)atoi(e);
-    if (const char* e = getenv("JADE_PACKET_BUDGET")) packet_budget = atoi(e);
-    if (const char* e = getenv("JADE_WIDE")) wide_mode = atoi(e) > 0 ? 1 : 0;
-  }
-};
 
-struct jade_scene {
-  int device = 0;
-  Tunables tun;
-  hipStream_t stream = nullptr;
-  DevScene dev{};
-  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias;
-  bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
-  int n_emit = 0;
-  int bvh_depth = 0;
-  bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
-  // render state
-  bool have_rp = false;
-  jade_render_params rp{};
-  RenderConst rc{};
-  PathState ps{};
-  DevBuf b_sortkey, b_sortkey2, b_sortpos, b_sortq, b_sorttmp;  // JADE_SORT: keys in / out, the entries' positions, the ordered queue (of positions), rocPRIM's temporary storage
-  size_t sort_cap = 0, sort_tmp_bytes = 0;
-  double sort_ms = 0;
-  DevBuf b_state, b_sum, b_tiles, b_queue, b_rayq, b_active[2], b_ctl, b_ctr, b_spill, b_out_rgb, b_out_bgr, b_wavecnt;
-  std::vector<int32_t> tile_ids;
-  int trace_blocks = 0;
-  int trace_blocks_wide = 0;  // ... of k_trace_wide (fewer waves per SIMD)
-  int light_blocks = 0;       // persistent grid of k_light
-  int packet_blocks = 0;      // ... and of k_light_packet (0: the tree is too deep for the packet form)
-  double packets_given_up = 0;  // share of the last fused pass's packets that were given up (reset by jade_render_begin)
-  int64_t spp_done = 0;
-  bool tail_pending = false;  // the last step left its longest paths unfinished (jade_render_flush)
-  uint32_t carried_active = 0;  // ... this many records (0: unknown)
-  hipEvent_t ev[7] = {};      // run_passes' timing events, made once (ev0, ev1, ta, tb, sa, sb, sm)
-  hipEvent_t ev_resolve = nullptr;  // jade_render_resolve_tiles_device: caller's stream -> scene stream
-  uint64_t host_syncs = 0;    // host waits inside step/flush since the last advance() reported them
-  double light_ms = 0;        // k_light device time since then
-  hipEvent_t ev_light[2] = {};
-  hipEvent_t ev_tail[2] = {};
-  double tail_ms = 0;         // k_tail device time since the last advance() reported it
-  uint64_t tail_launches = 0, tail_records = 0;
-  hipEvent_t ev_batch[2 * JADE_CTL_RING] = {};  // k_trace timing of a batch of passes
-  // adaptive sampling (jade_render_adaptive, jade_adaptive.hip): samples of each owned tile once the render has ended (empty: every
-  // tile has spp_done), their reciprocals for k_resolve, the rounds' active lists, per-tile counts and {count, not-idle} word
-  std::vector<int32_t> tile_n;
-  bool adaptive_done = false;  // jade_render_step refuses until the next begin
-  DevBuf b_tile_inv, b_tile_n, b_alist[2], b_actl, b_err;
-  hipEvent_t ev_err[2] = {};
-  // denoiser (jade_denoise.hip), allocated on first use and kept: the guide pass's throw-away PathState (orgs, slot, hitp), per-pixel
-  // state {throughput, depth} and mirror count, the list of owned in-image pixels and two ray queues, its own queue words and work
-  // counters (the render's are not touched), the guide sums {albedo, depth} {normal, 0}, the variance, the filter's records (two
-  // colour buffers, normal + depth, albedo) and the output images
-  DevBuf b_dn_orgs, b_dn_slot, b_dn_hitp, b_dn_state, b_dn_mirrors, b_dn_list, b_dn_q[2], b_dn_ctl, b_dn_ctr, b_dn_az, b_dn_n, b_dn_var;
-  DevBuf b_dn_rec[4], b_dn_rgb, b_dn_bgr;
-  // the work counters of the flush a denoiser entry point made (carried paths finished early): handed to the next step / flush's
-  // statistics, so that a render's counters do not depend on whether it was denoised between its steps
-  jade_stats dn_carried{};
-  ~jade_scene() {
-    for (hipEvent_t e : ev_err)
-      if (e) (void)hipEventDestroy(e);
-    if (ev_resolve) (void)hipEventDestroy(ev_resolve);
-    for (hipEvent_t e : ev_light)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_tail)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev_batch)
-      if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-// Copies on `stream` and waits for it: the scene's stream is non-blocking, so a copy on the null stream would
-// not be ordered before the kernels launched on it.
-template <class T>
-static hipError_t upload(DevBuf& b, const T* src, size_t count, hipStream_t stream) {
-  hipError_t e = b.alloc(sizeof(T) * count);
-  if (e != hipSuccess) return e;
-  if (count) {
-    e = hipMemcpyAsync(b.p, src, sizeof(T) * count, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  }
-  return e;
-}
-
-// RCCL is loaded on first use (dlopen): the single-GPU product path never needs it, and a process that also hosts
-// PyTorch keeps whichever librccl it loaded first.
-namespace {
-struct Rccl {
-  void* h = nullptr;
-  ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-  ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-  ncclResult_t (*GroupStart)() = nullptr;
-  ncclResult_t (*GroupEnd)() = nullptr;
-  ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-  const char* (*GetErrorString)(ncclResult_t) = nullptr;
-  bool load(std::string* why) {
-    if (h) return true;
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"})
-      if ((h = dlopen(name, RTLD_NOW | RTLD_LOCAL))) break;
-    if (!h) { *why = std::string("cannot load librccl: ") + dlerror(); return false; }
-    auto sym = [&](const char* n) { void* p = dlsym(h, n); if (!p) *why = std::string("librccl lacks ") + n; return p; };
-    CommInitAll = (decltype(CommInitAll))sym("ncclCommInitAll");
-    CommDestroy = (decltype(CommDestroy))sym("ncclCommDestroy");
-    GroupStart = (decltype(GroupStart))sym("ncclGroupStart");
-    GroupEnd = (decltype(GroupEnd))sym("ncclGroupEnd");
-    Send = (decltype(Send))sym("ncclSend");
-    Recv = (decltype(Recv))sym("ncclRecv");
-    GetErrorString = (decltype(GetErrorString))sym("ncclGetErrorString");
-    return CommInitAll && CommDestroy && GroupStart && GroupEnd && Send && Recv && GetErrorString;
-  }
-};
-Rccl g_rccl;
-}  // namespace
-
-// Communicators are made once per device list and kept for the life of the process (ncclCommInitAll is a bootstrap of
-// all ranks: tens of milliseconds on 8 GPUs - not something to pay inside every frame).
-namespace {
-struct CommSet {
-  std::vector<int> devs;
-  std::vector<ncclComm_t> comms;
-};
-std::mutex g_comm_mu;
-std::vector<CommSet> g_comm_sets;
-}  // namespace
-
-// Gather of every share's resolved tile buffer (scenes[i]->b_out_rgb, npx * 3 floats) into `dst` on scenes[0]'s device,
-// share i at off[i]: one communicator per device from this one process, all sends and receives in one group.
-static int rccl_gather(jade_scene* const* scenes, int ndev, float* dst, const std::vector<size_t>& off) {
-  std::string why;
-  std::lock_guard<std::mutex> lock(g_comm_mu);  // one gather at a time per process: the communicators are shared
-  if (!g_rccl.load(&why)) return fail(JADE_ERR_DEVICE, why);
-  std::vector<int> devs(ndev);
-  for (int i = 0; i < ndev; ++i) devs[i] = scenes[i]->device;
-  CommSet* cs = nullptr;
-  for (CommSet& c : g_comm_sets)
-    if (c.devs == devs) cs = &c;
-  if (!cs) {
-    CommSet fresh;
-    fresh.devs = devs;
-    fresh.comms.assign(ndev, nullptr);
-    const ncclResult_t r = g_rccl.CommInitAll(fresh.comms.data(), ndev, devs.data());
-    if (r != ncclSuccess) return fail(JADE_ERR_DEVICE, std::string("ncclCommInitAll: ") + g_rccl.GetErrorString(r));
-    g_comm_sets.push_back(std::move(fresh));
-    cs = &g_comm_sets.back();
-  }
-  const std::vector<ncclComm_t>& comms = cs->comms;
-  // every exit below this line goes through GroupEnd: an open group would stall the next RCCL user of the process
-  ncclResult_t r = g_rccl.GroupStart();
-  const bool opened = r == ncclSuccess;
-  const char* dev_err = nullptr;
-  for (int i = 1; i < ndev && r == ncclSuccess && !dev_err; ++i) {
-    const size_t count = (size_t)scenes[i]->ps.npx * 3;
-    if (!count) continue;
-    if (hipSetDevice(scenes[i]->device) != hipSuccess) { dev_err = "hipSetDevice failed"; break; }
-    r = g_rccl.Send(scenes[i]->b_out_rgb.p, count, ncclFloat, 0, comms[i], scenes[i]->stream);
-    if (r != ncclSuccess) break;
-    if (hipSetDevice(scenes[0]->device) != hipSuccess) { dev_err = "hipSetDevice failed"; break; }
-    r = g_rccl.Recv(dst + off[i], count, ncclFloat, i, comms[0], scenes[0]->stream);
-  }
-  if (opened) {
-    const ncclResult_t r2 = g_rccl.GroupEnd();
-    if (r == ncclSuccess) r = r2;
-  }
-  if (dev_err || r != ncclSuccess) {
-    // a communicator that saw a failed send / receive / group may be in an error state: it is destroyed and forgotten, the next
-    // gather over these devices bootstraps fresh ones
-    for (size_t k = 0; k < g_comm_sets.size(); ++k)
-      if (&g_comm_sets[k] == cs) {
-        for (ncclComm_t c : g_comm_sets[k].comms)
-          if (c) (void)g_rccl.CommDestroy(c);
-        g_comm_sets.erase(g_comm_sets.begin() + (long)k);
-        break;
-      }
-    if (dev_err) return fail(JADE_ERR_DEVICE, dev_err);
-    return fail(JADE_ERR_DEVICE, std::string("RCCL gather: ") + g_rccl.GetErrorString(r));
-  }
-  // rank 0's own share does not travel; then every stream involved drains before the caller reads the buffer
-  hipError_t e = hipSetDevice(scenes[0]->device);
-  const size_t own = (size_t)scenes[0]->ps.npx * 12;
-  if (e == hipSuccess && own) e = hipMemcpyAsync(dst + off[0], scenes[0]->b_out_rgb.p, own, hipMemcpyDeviceToDevice, scenes[0]->stream);
-  for (int i = ndev - 1; i >= 0 && e == hipSuccess; --i) {
-    e = hipSetDevice(scenes[i]->device);
-    if (e == hipSuccess) e = hipStreamSynchronize(scenes[i]->stream);
-  }
-  if (e != hipSuccess) return fail(JADE_ERR_DEVICE, std::string("RCCL gather: ") + hipGetErrorString(e));
-  return JADE_OK;
-}
-
-extern "C" {
+// (the entry points below have C linkage from their declarations in jade_rt.h / jade_bvh.h)
 
 int jade_abi_version(void) { return JADE_ABI_VERSION; }
 const char* jade_backend_name(void) { return "hip-gfx950"; }
 const char* jade_last_error(void) { return g_err.c_str(); }
 
 int jade_device_count(int* n) {
-  if (!n) return fail(JADE_ERR_INVALID, "null argument");
+  if (!n) return jade_fail(JADE_ERR_INVALID, "null argument");
   *n = 0;
   HIP_TRY(hipGetDeviceCount(n));
   return JADE_OK;
@@ -2215,23 +1900,23 @@ int jade_owned_tile_count(int32_t width, int32_t height, int32_t rank, int32_t n
 }
 
 static int validate_desc(const jade_scene_desc* d, int* depth_out) {
-  if (d->abi_version != JADE_ABI_VERSION) return fail(JADE_ERR_INVALID, "abi_version mismatch");
+  if (d->abi_version != JADE_ABI_VERSION) return jade_fail(JADE_ERR_INVALID, "abi_version mismatch");
   if (d->n_triangles <= 0 || d->n_nodes < 2 || !d->triangles || !d->nodes)
-    return fail(JADE_ERR_INVALID, "scene needs triangles and a BVH (dummy node 0 + root 1)");
-  if (d->n_triangles >= JADE_MAX_TRIS) return fail(JADE_ERR_UNSUPPORTED, "too many triangles for the 27-bit leaf cursor (44.7 M)");
-  if (d->n_emit < 0 || (d->n_emit > 0 && !d->emit_indices)) return fail(JADE_ERR_INVALID, "bad emitter list");
+    return jade_fail(JADE_ERR_INVALID, "scene needs triangles and a BVH (dummy node 0 + root 1)");
+  if (d->n_triangles >= JADE_MAX_TRIS) return jade_fail(JADE_ERR_UNSUPPORTED, "too many triangles for the 27-bit leaf cursor (44.7 M)");
+  if (d->n_emit < 0 || (d->n_emit > 0 && !d->emit_indices)) return jade_fail(JADE_ERR_INVALID, "bad emitter list");
   if (!d->index_mapping || !d->prefix_area || d->n_objects <= 0 || !d->obj_segs)
-    return fail(JADE_ERR_INVALID, "missing mapping / prefix areas / object segments");
-  if (d->env_width <= 0 || d->env_height <= 0 || !d->env_rgb) return fail(JADE_ERR_INVALID, "missing environment map");
+    return jade_fail(JADE_ERR_INVALID, "missing mapping / prefix areas / object segments");
+  if (d->env_width <= 0 || d->env_height <= 0 || !d->env_rgb) return jade_fail(JADE_ERR_INVALID, "missing environment map");
   for (int i = 0; i < d->n_emit; ++i)
-    if (d->emit_indices[i] < 0 || d->emit_indices[i] >= d->n_triangles) return fail(JADE_ERR_INVALID, "emitter index out of range");
+    if (d->emit_indices[i] < 0 || d->emit_indices[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "emitter index out of range");
   for (int i = 0; i < d->n_triangles; ++i) {
-    if (d->index_mapping[i] < 0 || d->index_mapping[i] >= d->n_triangles) return fail(JADE_ERR_INVALID, "index_mapping out of range");
-    if (d->triangles[i].obj_idx < 0 || d->triangles[i].obj_idx >= d->n_objects) return fail(JADE_ERR_INVALID, "obj_idx out of range");
+    if (d->index_mapping[i] < 0 || d->index_mapping[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "index_mapping out of range");
+    if (d->triangles[i].obj_idx < 0 || d->triangles[i].obj_idx >= d->n_objects) return jade_fail(JADE_ERR_INVALID, "obj_idx out of range");
   }
   for (int i = 0; i < d->n_objects; ++i)
     if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
-      return fail(JADE_ERR_INVALID, "object segment out of range");
+      return jade_fail(JADE_ERR_INVALID, "object segment out of range");
   // walk the tree: ranges, cycles (visit budget), depth <= stack capacity - 1
   std::vector<std::pair<int, int>> st;
   st.push_back({1, 1});
@@ -2240,17 +1925,17 @@ static int validate_desc(const jade_scene_desc* d, int* depth_out) {
   while (!st.empty()) {
     auto [id, dp] = st.back();
     st.pop_back();
-    if (--budget < 0) return fail(JADE_ERR_UNSUPPORTED, "BVH malformed (cycle)");
-    if (dp > JADE_BVH_STACK_CAPACITY - 1) return fail(JADE_ERR_UNSUPPORTED, "BVH deeper than the traversal stack");
+    if (--budget < 0) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH malformed (cycle)");
+    if (dp > JADE_BVH_STACK_CAPACITY - 1) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH deeper than the traversal stack");
     depth = std::max(depth, dp);
     const jade_bvh_node& nd = d->nodes[id];
     if (nd.n > 0) {
-      if (nd.index < 0 || (int64_t)nd.index + nd.n > d->n_triangles) return fail(JADE_ERR_INVALID, "leaf range out of bounds");
-      if (nd.n > JADE_MAX_LEAF) return fail(JADE_ERR_UNSUPPORTED, "leaf with more than 15 triangles");
+      if (nd.index < 0 || (int64_t)nd.index + nd.n > d->n_triangles) return jade_fail(JADE_ERR_INVALID, "leaf range out of bounds");
+      if (nd.n > JADE_MAX_LEAF) return jade_fail(JADE_ERR_UNSUPPORTED, "leaf with more than 15 triangles");
       continue;
     }
     if (nd.left < 0 || nd.left >= d->n_nodes || nd.right < 0 || nd.right >= d->n_nodes)
-      return fail(JADE_ERR_INVALID, "child index out of range");
+      return jade_fail(JADE_ERR_INVALID, "child index out of range");
     if (nd.left > 0) st.push_back({nd.left, dp + 1});
     if (nd.right > 0) st.push_back({nd.right, dp + 1});
   }
@@ -2258,342 +1943,34 @@ static int validate_desc(const jade_scene_desc* d, int* depth_out) {
   return JADE_OK;
 }
 
-int jade_scene_create(const jade_scene_desc* d, int device_id, jade_scene** out) {
-  if (!d || !out) return fail(JADE_ERR_INVALID, "null argument");
-  int depth = 0;
-  int rc = validate_desc(d, &depth);
-  if (rc) return rc;
-  int ndev = 0;
-  HIP_TRY(hipGetDeviceCount(&ndev));
-  if (device_id < 0 || device_id >= ndev) return fail(JADE_ERR_DEVICE, "no such HIP device");
-  HIP_TRY(hipSetDevice(device_id));
-
-  // re-lay the BVH: compact the internal nodes, children's boxes in the parent.  Internal nodes are numbered by
-  // decreasing surface area of their own box (the SAH's measure of how often a node is visited), so that any prefix
-  // [0, k) of the array is a connected top of the tree - a child's box is never larger than its parent's, ties keep
-  // the breadth-first order - and k_trace can keep that prefix in LDS (jade_device.h, JADE_LDS_TOP_NODES).
-  const int nN = d->n_nodes;
-  std::vector<int32_t> compact(nN, -1);
-  int n_internal = 0;
-  {
-    std::vector<int32_t> bfs;  // internal nodes reachable from the root, breadth first
-    bfs.reserve(nN);
-    if (d->nodes[1].n <= 0) bfs.push_back(1);
-    for (size_t h = 0; h < bfs.size(); ++h) {
-      const jade_bvh_node& nd = d->nodes[bfs[h]];
-      if (nd.left > 0 && d->nodes[nd.left].n <= 0) bfs.push_back(nd.left);
-      if (nd.right > 0 && d->nodes[nd.right].n <= 0) bfs.push_back(nd.right);
-    }
-    auto area = [&](int i) {
-      const jade_bvh_node& nd = d->nodes[i];
-      const double x = (double)nd.bb[0] - nd.aa[0], y = (double)nd.bb[1] - nd.aa[1], z = (double)nd.bb[2] - nd.aa[2];
-      return x * y + y * z + z * x;
-    };
-    std::vector<double> ar(bfs.size());
-    for (size_t h = 0; h < bfs.size(); ++h) ar[h] = area(bfs[h]);
-    // a child inherits at most its parent's key, so a prefix of the order is always closed under "parent of"
-    std::vector<double> key(nN, 0.0);
-    for (size_t h = 0; h < bfs.size(); ++h) {
-      const int i = bfs[h];
-      if (h == 0) key[i] = ar[0];
-      const jade_bvh_node& nd = d->nodes[i];
-      for (int ch : {nd.left, nd.right})
-        if (ch > 0 && d->nodes[ch].n <= 0) key[ch] = std::min(key[i], area(ch));
-    }
-    std::vector<int32_t> order(bfs.size());
-    for (size_t h = 0; h < bfs.size(); ++h) order[h] = (int32_t)h;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[bfs[a]] > key[bfs[b]]; });
-    for (int32_t h : order) compact[bfs[h]] = n_internal++;
-    // internal nodes the root does not reach (none in a valid tree) keep a slot so that every record exists
-    for (int i = 1; i < nN; ++i)
-      if (d->nodes[i].n <= 0 && compact[i] < 0) compact[i] = n_internal++;
-  }
-  // vertex records hold two consecutive triangles of a leaf each (jade_trace.h): number the pairs leaf by leaf
-  std::vector<uint32_t> pair_first(nN, 0);
-  size_t n_pairs = 0;
-  {
-    std::vector<int> leaves;
-    for (int i = 1; i < nN; ++i)
-      if (d->nodes[i].n > 0) leaves.push_back(i);
-    std::sort(leaves.begin(), leaves.end(), [&](int a, int b) { return d->nodes[a].index < d->nodes[b].index; });
-    for (int i : leaves) {
-      pair_first[i] = (uint32_t)n_pairs;
-      n_pairs += (size_t)(d->nodes[i].n + 1) / 2;
-    }
-    if (n_pairs * 5 >= ((size_t)1 << 27)) return fail(JADE_ERR_UNSUPPORTED, "too many triangle pairs for the 27-bit leaf cursor");
-  }
-  auto ref_of = [&](int child) -> uint32_t {
-    if (child <= 0) return JADE_REF_NONE;
-    const jade_bvh_node& c = d->nodes[child];
-    if (c.n > 0) return JADE_REF_LEAF | ((pair_first[child] * 5u) << 4) | (uint32_t)((c.n + 1) / 2);  // bits 4-30: byte offset / 16 of the first pair record
-    return (uint32_t)compact[child];
-  };
-  std::vector<float4> nodes((size_t)4 * std::max(n_internal, 1));
-  bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
-  for (int i = 1; i < nN; ++i) {
-    const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
-    if (nd.left <= 0 || nd.right <= 0) missing_child = true;
-    float la[3] = {0, 0, 0}, lb[3] = {0, 0, 0}, ra[3] = {0, 0, 0}, rb[3] = {0, 0, 0};
-    if (nd.left > 0) { memcpy(la, d->nodes[nd.left].aa, 12); memcpy(lb, d->nodes[nd.left].bb, 12); }
-    if (nd.right > 0) { memcpy(ra, d->nodes[nd.right].aa, 12); memcpy(rb, d->nodes[nd.right].bb, 12); }
-    float4* o = &nodes[(size_t)4 * compact[i]];
-    o[0] = make_float4(la[0], ra[0], la[1], ra[1]);
-    o[1] = make_float4(la[2], ra[2], lb[0], rb[0]);
-    o[2] = make_float4(lb[1], rb[1], lb[2], rb[2]);
-    uint32_t refs[4] = {ref_of(nd.left), ref_of(nd.right), 0u, 0u};
-    memcpy(&o[3], refs, 16);
-  }
-  // the four-wide records (jade_device.h): node i's record holds its grandchildren - each child's own record, or the child twice
-  // if it is a leaf
-  // Built where the wide walk pays: measured with early exits, same process, k_trace per step: C5 (55 MB of node + pair records, bound
-  // by dependent 64-B sector misses) 180.0 -> 166.6 ms; C3 (3.8 MB, L2-resident: a unit's own instructions count, and a wide unit
-  // has more of them) 106.7 -> 110.2 ms, close-up 723 -> 755.  So: the rule of the ordered ray queue (JADE_SORT_GEOMETRY_BYTES);
-  // JADE_WIDE=0 / 1 overrides it.
-  std::vector<float4> nodes4;
-  Tunables tun0;
-  tun0.read();
-  const size_t geometry_bytes0 = ((size_t)4 * std::max(n_internal, 1) + (size_t)5 * std::max<size_t>(n_pairs, 1)) * sizeof(float4);
-  const bool want_wide = tun0.wide_mode < 0 ? geometry_bytes0 > JADE_SORT_GEOMETRY_BYTES : tun0.wide_mode > 0;
-  // The wide walk and the occluder cache both rest on "a ray that meets a node's box meets every ancestor's" (jade_trace.h), which
-  // holds when every child's box lies inside its parent's, bound by bound, with no NaN - true of any tree built by min / max over
-  // the triangles (this repo's builders, the reference's), but the caller's array is the caller's: a tree with padded,
-  // refitted or NaN boxes is walked with binary units from the root only, which needs no such property.
-  bool nested = true;
-  for (int i = 1; i < nN && nested; ++i) {
-    const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
-    for (int ch : {nd.left, nd.right}) {
-      if (ch <= 0) continue;
-      const jade_bvh_node& c = d->nodes[ch];
-      for (int a = 0; a < 3; ++a)
-        if (!(c.aa[a] >= nd.aa[a] && c.bb[a] <= nd.bb[a] && c.aa[a] <= c.bb[a])) nested = false;  // (a NaN fails every comparison)
-    }
-  }
-  // stack levels a walk may need (validate_desc bounds the binary walk's: depth <= capacity - 1): a wide unit pushes up to three
-  // entries for every two levels it descends; a walk that starts with the cached subtrees has three more under it
-  const bool wide_fits = 3 * ((depth + 1) / 2) + 1 + 3 <= JADE_BVH_STACK_CAPACITY;
-  const bool cache_fits = depth + 3 <= JADE_BVH_STACK_CAPACITY - 1;
-  if (JADE_WIDE_WALK && want_wide && !missing_child && n_internal > 0 && nested && wide_fits) {
-    nodes4.assign((size_t)8 * n_internal, make_float4(0, 0, 0, 0));
-    for (int i = 1; i < nN; ++i) {
-      const jade_bvh_node& nd = d->nodes[i];
-      if (nd.n > 0 || compact[i] < 0) continue;
-      float4* o = &nodes4[(size_t)8 * compact[i]];
-      uint32_t refs[4];
-      const int ch[2] = {nd.left, nd.right};
-      for (int h = 0; h < 2; ++h) {
-        const jade_bvh_node& c = d->nodes[ch[h]];
-        if (c.n > 0) {  // a leaf: its own box in both lanes of the half, one reference
-          o[3 * h + 0] = make_float4(c.aa[0], c.aa[0], c.aa[1], c.aa[1]);
-          o[3 * h + 1] = make_float4(c.aa[2], c.aa[2], c.bb[0], c.bb[0]);
-          o[3 * h + 2] = make_float4(c.bb[1], c.bb[1], c.bb[2], c.bb[2]);
-          refs[2 * h] = ref_of(ch[h]);
-          refs[2 * h + 1] = JADE_REF_NONE;
-        } else {
-          const float4* src = &nodes[(size_t)4 * compact[ch[h]]];
-          o[3 * h + 0] = src[0];
-          o[3 * h + 1] = src[1];
-          o[3 * h + 2] = src[2];
-          refs[2 * h] = ref_of(c.left);
-          refs[2 * h + 1] = ref_of(c.right);
-        }
-      }
-      memcpy(&o[6], refs, 16);
-    }
-  }
-  std::vector<float4> tverts((size_t)5 * std::max<size_t>(n_pairs, 1));
-  std::vector<int32_t> leaf_parent(nN, 0);
-  for (int i = 1; i < nN; ++i) {
-    const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
-    if (nd.left > 0 && d->nodes[nd.left].n > 0) leaf_parent[nd.left] = i;
-    if (nd.right > 0 && d->nodes[nd.right].n > 0) leaf_parent[nd.right] = i;
-  }
-  for (int i = 1; i < nN; ++i) {
-    const jade_bvh_node& nd = d->nodes[i];
-    for (int k = 0; k < nd.n; k += 2) {
-      const bool has_b = k + 1 < nd.n;
-      const jade_triangle& a = d->triangles[nd.index + k];
-      const jade_triangle& b = d->triangles[nd.index + k + (has_b ? 1 : 0)];  // an odd leaf's last record repeats A
-      float4* o = &tverts[5 * ((size_t)pair_first[i] + (size_t)k / 2)];
-      o[0] = make_float4(a.p1[0], b.p1[0], a.p1[1], b.p1[1]);
-      o[1] = make_float4(a.p1[2], b.p1[2], a.p2[0], b.p2[0]);
-      o[2] = make_float4(a.p2[1], b.p2[1], a.p2[2], b.p2[2]);
-      o[3] = make_float4(a.p3[0], b.p3[0], a.p3[1], b.p3[1]);
-      // flag word: bit 0 = B is a triangle; bits 1-31 = the leaf's parent + 1 (occluder cache, jade_trace.h; 0 = the root or none: a
-      // walk "from the root" is the whole walk, nothing to cache)
-      const int par = leaf_parent[i];
-      const uint32_t parent1 = (par > 1 && compact[par] > 0) ? (uint32_t)compact[par] + 1u : 0u;
-      const uint32_t tag[2] = {(uint32_t)(nd.index + k), (has_b ? 1u : 0u) | (parent1 << 1)};
-      float tagf[2];
-      memcpy(tagf, tag, 8);
-      o[4] = make_float4(a.p3[2], b.p3[2], tagf[0], tagf[1]);
-    }
-  }
-
-  // Guide tables for the BSSRDF exit-point search (jade_shade.h, begin_bounce; PathTrace.cu:1031-1048).  Per object with
-  // finite, non-decreasing prefix areas: Gn = the power of two >= 4 x its triangles cells, guide[c] = the first triangle i with
-  // fl(c / Gn * A) <= prefix[i] - the product rounded once to fp32, as the kernel's `u * A` is (this file is built
-  // -ffp-contract=off like the device code) - for c = 0 .. Gn, and one more entry so that cell Gn (u == 1) has an upper bound.
-  // An object whose prefix areas are not monotone or not finite gets Gn = 0: the kernel then bisects as the reference does.
-  std::vector<uint32_t> guide;
-  std::vector<uint2> guide_obj((size_t)d->n_objects, make_uint2(0u, 0u));
-  for (int o = 0; o < d->n_objects; ++o) {
-    const int b = d->obj_segs[o].begin_idx, e = d->obj_segs[o].end_idx;
-    bool ok = true;
-    for (int i = b; i <= e && ok; ++i) {
-      const float v = d->prefix_area[i];
-      ok = v == v && v >= 0.0f && v < 3.0e38f && (i == b || v >= d->prefix_area[i - 1]);
-    }
-    const size_t nt = (size_t)(e - b + 1);
-    if (!ok || nt < 2 || nt > ((size_t)1 << 21)) continue;
-    uint32_t gn = 1;
-    while (gn < 4 * nt) gn <<= 1;
-    const float A = d->prefix_area[e];
-    const size_t first = guide.size();
-    guide.resize(first + gn + 2);
-    int i = b;
-    for (uint32_t c = 0; c <= gn; ++c) {
-      const float u = (float)c / (float)gn;  // exact: both are powers of two apart
-      volatile float x = u * A;              // one rounding (volatile: no excess precision, whatever the host compiler does)
-      const float xv = x;
-      while (i < e && !(xv <= d->prefix_area[i])) ++i;
-      guide[first + c] = (uint32_t)i;
-    }
-    guide[first + gn + 1] = guide[first + gn];
-    guide_obj[(size_t)o] = make_uint2((uint32_t)first, gn);
-  }
-  if (guide.empty()) guide.push_back(0u);
-
-  // What shading reads of a triangle (jade_device.h, DevMaterial): the distinct {object, material} tuples of the caller's
-  // records - the reference copies an object's material into each of its triangles, PathTrace.cu:451 - and per triangle
-  // the flat normal + the number of its tuple.  Same bytes, read from 16 B + a cached table instead of a 112-B record.
-  std::vector<DevMaterial> mats;
-  std::vector<float4> tnorm((size_t)d->n_triangles);
-  {
-    std::map<std::string, uint32_t> seen;  // key: the 64 bytes of the tuple
-    std::string last_key;
-    uint32_t last_id = 0;
-    for (int i = 0; i < d->n_triangles; ++i) {
-      const jade_triangle& t = d->triangles[i];
-      DevMaterial m;
-      memcpy(m.emissive, t.emissive, 12);
-      memcpy(m.brdf, t.brdf, 12);
-      m.reflex_mode = t.reflex_mode;
-      m.refract_mode = t.refract_mode;
-      memcpy(m.refract_rate, t.refract_rate, 12);
-      memcpy(m.refract_albedo, t.refract_albedo, 12);
-      m.refract_index = t.refract_index;
-      m.obj_idx = t.obj_idx;
-      std::string key(reinterpret_cast<const char*>(&m), sizeof m);
-      uint32_t id;
-      if (i > 0 && key == last_key) {
-        id = last_id;
-      } else {
-        auto it = seen.find(key);
-        if (it == seen.end()) {
-          id = (uint32_t)mats.size();
-          mats.push_back(m);
-          seen.emplace(key, id);
-        } else {
-          id = it->second;
-        }
-        last_key = std::move(key);
-        last_id = id;
-      }
-      float idf;
-      memcpy(&idf, &id, 4);
-      tnorm[(size_t)i] = make_float4(t.norm[0], t.norm[1], t.norm[2], idf);
-    }
-  }
-
-  // Environment importance sampling (jade_render_params.env_sampling; non-parity): Vose's alias table over the texels, weight =
-  // (luminance + 1 % of the mean luminance) x sin(theta of the row's centre) - the floor keeps every texel drawable, so the
-  // estimator stays unbiased wherever the sky is not black
-  std::vector<uint4> env_alias;
-  {
-    const size_t W = (size_t)d->env_width, H = (size_t)d->env_height, N = W * H;
-    std::vector<double> wgt(N);
-    double lum_sum = 0;
-    for (size_t i = 0; i < N; ++i) {
-      const float* t = d->env_rgb + 3 * i;
-      const double l = 0.2126 * std::max(t[0], 0.0f) + 0.7152 * std::max(t[1], 0.0f) + 0.0722 * std::max(t[2], 0.0f);
-      wgt[i] = std::isfinite(l) ? l : 0.0;
-      lum_sum += wgt[i];
-    }
-    const double floor_l = lum_sum > 0 ? 0.01 * lum_sum / (double)N : 1.0;
-    double total = 0;
-    for (size_t j = 0; j < H; ++j) {
-      const double st = std::sin(JADE_PI_D * ((double)j + 0.5) / (double)H);
-      for (size_t i = 0; i < W; ++i) {
-        wgt[j * W + i] = (wgt[j * W + i] + floor_l) * st;
-        total += wgt[j * W + i];
-      }
-    }
-    std::vector<double> q(N);
-    std::vector<uint32_t> small, large, alias(N);
-    std::vector<float> accept(N, 1.0f);
-    for (size_t i = 0; i < N; ++i) {
-      q[i] = wgt[i] / total * (double)N;  // the texel's probability x N (mean 1)
-      alias[i] = (uint32_t)i;
-      (q[i] < 1.0 ? small : large).push_back((uint32_t)i);
-    }
-    std::vector<double> r = q;
-    while (!small.empty() && !large.empty()) {
-      const uint32_t a = small.back(), g = large.back();
-      small.pop_back();
-      accept[a] = (float)r[a];
-      alias[a] = g;
-      r[g] = (r[g] + r[a]) - 1.0;
-      if (r[g] < 1.0) { large.pop_back(); small.push_back(g); }
-    }
-    env_alias.resize(N);
-    for (size_t i = 0; i < N; ++i) {
-      const float ps = (float)q[i], pa = (float)q[alias[i]];
-      uint4 e;
-      memcpy(&e.x, &accept[i], 4);
-      e.y = alias[i];
-      memcpy(&e.z, &ps, 4);
-      memcpy(&e.w, &pa, 4);
-      env_alias[i] = e;
-    }
-  }
-
-  jade_scene* s = new (std::nothrow) jade_scene();
-  if (!s) return fail(JADE_ERR_NOMEM, "out of memory");
-  s->device = device_id;
-  s->tun.read();
-  s->n_emit = d->n_emit;
-  s->bvh_depth = depth;
+// uploads what prepare_scene made and the caller's own arrays, and points s->dev at them
+static int upload_scene(jade_scene* s, const jade_scene_desc* d, const ScenePrep& p) {
   hipError_t e = hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking);
-  if (e == hipSuccess) e = upload(s->b_nodes, nodes.data(), nodes.size(), s->stream);
-  if (e == hipSuccess && !nodes4.empty()) e = upload(s->b_nodes4, nodes4.data(), nodes4.size(), s->stream);
-  if (e == hipSuccess) e = upload(s->b_tverts, tverts.data(), tverts.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_nodes, p.nodes.data(), p.nodes.size(), s->stream);
+  if (e == hipSuccess && !p.nodes4.empty()) e = upload(s->b_nodes4, p.nodes4.data(), p.nodes4.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_tverts, p.tverts.data(), p.tverts.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_tris, d->triangles, (size_t)d->n_triangles, s->stream);
   if (e == hipSuccess) e = upload(s->b_emit, d->emit_indices, (size_t)d->n_emit, s->stream);
   if (e == hipSuccess) e = upload(s->b_mapping, d->index_mapping, (size_t)d->n_triangles, s->stream);
   if (e == hipSuccess) e = upload(s->b_prefix, d->prefix_area, (size_t)d->n_triangles, s->stream);
   if (e == hipSuccess) e = upload(s->b_segs, d->obj_segs, (size_t)d->n_objects, s->stream);
   if (e == hipSuccess) e = upload(s->b_env, d->env_rgb, (size_t)3 * d->env_width * d->env_height, s->stream);
-  if (e == hipSuccess) e = upload(s->b_env_alias, env_alias.data(), env_alias.size(), s->stream);
-  if (e == hipSuccess) e = upload(s->b_tnorm, tnorm.data(), tnorm.size(), s->stream);
-  if (e == hipSuccess) e = upload(s->b_mats, mats.data(), mats.size(), s->stream);
-  if (e == hipSuccess) e = upload(s->b_guide, guide.data(), guide.size(), s->stream);
-  if (e == hipSuccess) e = upload(s->b_guide_obj, guide_obj.data(), guide_obj.size(), s->stream);
-  const bool want_anyhit = s->tun.anyhit && nested && cache_fits && !missing_child && n_internal > 1;
+  if (e == hipSuccess) e = upload(s->b_env_alias, p.env_alias.data(), p.env_alias.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_tnorm, p.tnorm.data(), p.tnorm.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_mats, p.mats.data(), p.mats.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_guide, p.guide.data(), p.guide.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_guide_obj, p.guide_obj.data(), p.guide_obj.size(), s->stream);
+  const bool want_anyhit = s->tun.anyhit && p.nested && p.cache_fits && !p.missing_child && p.n_internal > 1;
   if (e == hipSuccess && want_anyhit) {
     e = s->b_anyhit.alloc((size_t)d->n_triangles * JADE_ANYHIT_KEYS * sizeof(uint4));
     if (e == hipSuccess) e = hipMemsetAsync(s->b_anyhit.p, 0, s->b_anyhit.bytes, s->stream);
   }
   if (e == hipSuccess) e = s->b_ctl.alloc(sizeof(QueueCtl) * (JADE_CTL_RING + 1));  // (+ 1: k_arm's count when the host does not wait for it)
   if (e == hipSuccess) e = s->b_ctr.alloc(sizeof(DevCounters) * JADE_CTR_SHARDS);
-  if (e != hipSuccess) {
-    delete s;
-    return fail(e == hipErrorOutOfMemory ? JADE_ERR_NOMEM : JADE_ERR_DEVICE, std::string("scene upload: ") + hipGetErrorString(e));
-  }
+  if (e != hipSuccess)
+    return jade_fail(e == hipErrorOutOfMemory ? JADE_ERR_NOMEM : JADE_ERR_DEVICE, std::string("scene upload: ") + hipGetErrorString(e));
   s->dev.nodes = s->b_nodes.as<float4>();
-  s->dev.nodes4 = nodes4.empty() ? nullptr : s->b_nodes4.as<float4>();
+  s->dev.nodes4 = p.nodes4.empty() ? nullptr : s->b_nodes4.as<float4>();
   s->dev.tverts = s->b_tverts.as<float4>();
   s->dev.tris = s->b_tris.as<jade_triangle>();
   s->dev.emit = s->b_emit.as<int32_t>();
@@ -2609,64 +1986,77 @@ int jade_scene_create(const jade_scene_desc* d, int device_id, jade_scene** out)
   s->dev.env_h = d->env_height;
   s->dev.n_tris = d->n_triangles;
   s->dev.n_emit = d->n_emit;
-  s->dev.root_ref = ref_of(1);
-  s->dev.top_k = (uint32_t)std::min(n_internal, (int)JADE_LDS_TOP_NODES);
-  s->dev.general_walk = missing_child ? 1u : 0u;
+  s->dev.root_ref = p.root_ref;
+  s->dev.top_k = (uint32_t)std::min(p.n_internal, (int)JADE_LDS_TOP_NODES);
+  s->dev.general_walk = p.missing_child ? 1u : 0u;
   s->dev.anyhit = want_anyhit ? s->b_anyhit.as<uint4>() : nullptr;
   s->dev.env_alias = s->b_env_alias.as<uint4>();
-  s->boxes_nested = nested;
+  s->boxes_nested = p.nested;
   // Ray ordering pays when the traversal's records do not fit the XCDs' L2s (C5: 55 MB, k_trace bound by the rate of 64-B sector
   // misses: 4 235 -> 5 275 Mray/s); on a tree that does (C3: 3.8 MB) it costs more than it gives
-  {
-    const size_t geometry_bytes = nodes.size() * sizeof(float4) + tverts.size() * sizeof(float4);
-    s->sort_rays = s->tun.sort_mode < 0 ? geometry_bytes > JADE_SORT_GEOMETRY_BYTES : s->tun.sort_mode > 0;
-  }
+  s->sort_rays = s->tun.sort_mode < 0 ? p.geometry_bytes > JADE_SORT_GEOMETRY_BYTES : s->tun.sort_mode > 0;
+  return JADE_OK;
+}
 
-  // the arithmetic contract of jade_fpmath.h, checked on the device once
-  hipLaunchKernelGGL(k_selftest, dim3(1), dim3(1), 0, s->stream, s->b_ctl.as<QueueCtl>(), 1.0f);
-  QueueCtl qc{};
-  e = hipMemcpyAsync(&qc, s->b_ctl.p, sizeof qc, hipMemcpyDeviceToHost, s->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-  if (e != hipSuccess || qc.fp_bad) {
-    std::string m = e != hipSuccess ? std::string("selftest: ") + hipGetErrorString(e)
-                                    : "device code was built with FP contraction on (see include/jade_fpmath.h)";
-    delete s;
-    return fail(JADE_ERR_DEVICE, m);
-  }
-  // persistent trace grid: as many blocks per CU as registers and the LDS columns (20 KB/block) allow
+// blocks per CU a persistent kernel gets: what the occupancy query allows, at least 1, at most `cap`
+template <class K>
+static int blocks_per_cu(K kernel, int cap) {
+  int n = 0;
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, JADE_TRACE_BLOCK, 0);
+  return std::min(std::max(n, 1), cap);
+}
+
+// persistent grids: as many blocks per CU as registers and the LDS columns (20 KB/block) allow
+static int size_grids(jade_scene* s, int depth) {
   hipDeviceProp_t prop;
-  if (hipError_t pe = hipGetDeviceProperties(&prop, device_id); pe != hipSuccess) {
-    delete s;
-    return fail(JADE_ERR_DEVICE, std::string("hipGetDeviceProperties: ") + hipGetErrorString(pe));
-  }
-  int per_cu = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_trace, JADE_TRACE_BLOCK, 0);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 8) per_cu = 8;
+  if (hipError_t pe = hipGetDeviceProperties(&prop, s->device); pe != hipSuccess)
+    return jade_fail(JADE_ERR_DEVICE, std::string("hipGetDeviceProperties: ") + hipGetErrorString(pe));
+  int per_cu = blocks_per_cu(k_trace, 8);
   if (s->tun.trace_blocks_per_cu >= 1 && s->tun.trace_blocks_per_cu < per_cu) per_cu = s->tun.trace_blocks_per_cu;  // development: occupancy sweeps
   if (s->tun.log_passes) fprintf(stderr, "[jade] k_trace: %d blocks of %d threads per CU, %d CUs\n", per_cu, JADE_TRACE_BLOCK, prop.multiProcessorCount);
   s->trace_blocks = prop.multiProcessorCount * per_cu;
-  {  // k_trace_wide keeps fewer waves: its own grid (the stack spill area is sized for the larger one)
-    int wide_cu = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&wide_cu, k_trace_wide, JADE_TRACE_BLOCK, 0);
-    if (wide_cu < 1) wide_cu = 1;
-    if (wide_cu > per_cu) wide_cu = per_cu;
-    s->trace_blocks_wide = prop.multiProcessorCount * wide_cu;
-  }
-  int light_cu = 0;
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&light_cu, k_light, JADE_TRACE_BLOCK, 0);
-  if (light_cu < 1) light_cu = 1;
-  if (light_cu > per_cu) light_cu = per_cu;  // the stack spill area is sized for the k_trace grid
-  s->light_blocks = prop.multiProcessorCount * light_cu;
-  if (depth <= JADE_PACKET_MAX_DEPTH) {
-    int pk_cu = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&pk_cu, k_light_packet, JADE_TRACE_BLOCK, 0);
-    if (pk_cu < 1) pk_cu = 1;
-    if (pk_cu > 8) pk_cu = 8;
-    s->packet_blocks = prop.multiProcessorCount * pk_cu;
-  }
+  // k_trace_wide keeps fewer waves: its own grid; it and k_light stay within k_trace's (the stack spill area is sized for that one)
+  s->trace_blocks_wide = prop.multiProcessorCount * blocks_per_cu(k_trace_wide, per_cu);
+  s->light_blocks = prop.multiProcessorCount * blocks_per_cu(k_light, per_cu);
+  if (depth <= JADE_PACKET_MAX_DEPTH) s->packet_blocks = prop.multiProcessorCount * blocks_per_cu(k_light_packet, 8);
   if (s->tun.log_passes) fprintf(stderr, "[jade] first pass: k_light %d blocks, k_light_packet %d blocks (tree depth %d)\n", s->light_blocks, s->packet_blocks, depth);
-  *out = s;
+  return JADE_OK;
+}
+
+// the arithmetic contract of jade_fpmath.h, checked on the device once
+static int selftest(jade_scene* s) {
+  hipLaunchKernelGGL(k_selftest, dim3(1), dim3(1), 0, s->stream, s->b_ctl.as<QueueCtl>(), 1.0f);
+  QueueCtl qc{};
+  hipError_t e = hipMemcpyAsync(&qc, s->b_ctl.p, sizeof qc, hipMemcpyDeviceToHost, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  if (e != hipSuccess) return jade_fail(JADE_ERR_DEVICE, std::string("selftest: ") + hipGetErrorString(e));
+  if (qc.fp_bad) return jade_fail(JADE_ERR_DEVICE, "device code was built with FP contraction on (see include/jade_fpmath.h)");
+  return JADE_OK;
+}
+
+int jade_scene_create(const jade_scene_desc* d, int device_id, jade_scene** out) {
+  if (!d || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  int depth = 0;
+  int rc = validate_desc(d, &depth);
+  if (rc) return rc;
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device_id < 0 || device_id >= ndev) return jade_fail(JADE_ERR_DEVICE, "no such HIP device");
+  HIP_TRY(hipSetDevice(device_id));
+  Tunables tun;
+  tun.read();
+  ScenePrep prep;
+  if ((rc = prepare_scene(*d, depth, tun, &prep))) return rc;
+  std::unique_ptr<jade_scene> s(new (std::nothrow) jade_scene());
+  if (!s) return jade_fail(JADE_ERR_NOMEM, "out of memory");
+  s->device = device_id;
+  s->tun = tun;
+  s->n_emit = d->n_emit;
+  s->bvh_depth = depth;
+  if ((rc = upload_scene(s.get(), d, prep))) return rc;
+  if ((rc = selftest(s.get()))) return rc;
+  if ((rc = size_grids(s.get(), depth))) return rc;
+  *out = s.release();
   return JADE_OK;
 }
 
@@ -2750,12 +2140,12 @@ static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lane
 }
 
 int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
-  if (!s || !rp) return fail(JADE_ERR_INVALID, "null argument");
+  if (!s || !rp) return jade_fail(JADE_ERR_INVALID, "null argument");
   if (rp->width <= 0 || rp->height <= 0 || rp->tile_nranks <= 0 || rp->tile_rank < 0 || rp->tile_rank >= rp->tile_nranks)
-    return fail(JADE_ERR_INVALID, "bad image size or tile partition");
+    return jade_fail(JADE_ERR_INVALID, "bad image size or tile partition");
   if (rp->walk != JADE_WALK_REFERENCE && rp->walk != JADE_WALK_EARLY_EXIT && rp->walk != JADE_WALK_EARLY_EXIT_CACHED)
-    return fail(JADE_ERR_INVALID, "unknown walk (JADE_WALK_*)");
-  if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+    return jade_fail(JADE_ERR_INVALID, "unknown walk (JADE_WALK_*)");
+  if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
@@ -2796,9 +2186,9 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   }
   const int64_t npix64 = npx64 * rpp;
   if (npix64 * nslots >= ((int64_t)1 << 32) || npix64 * 3 >= ((int64_t)1 << 31))
-    return fail(JADE_ERR_UNSUPPORTED, "pixels x records x (emitters + 2) exceeds the 32-bit ray-slot index");
+    return jade_fail(JADE_ERR_UNSUPPORTED, "pixels x records x (emitters + 2) exceeds the 32-bit ray-slot index");
   if (sums_bytes + (double)npix64 * bytes_per_record > (rp->max_state_bytes ? std::max(state_budget, 0.0) : 0.95 * (double)mem_free))
-    return fail(JADE_ERR_NOMEM, rp->max_state_bytes ? "frame does not fit max_state_bytes (partial sums + one record per pixel)"
+    return jade_fail(JADE_ERR_NOMEM, rp->max_state_bytes ? "frame does not fit max_state_bytes (partial sums + one record per pixel)"
                                                     : "frame does not fit the device memory (partial sums + one record per pixel)");
   if (s->tun.log_passes)
     fprintf(stderr, "[jade] %lld pixels x %d records, %.1f GB of path state + %.1f GB of partial sums in %d lanes (%.0f GB free)\n", (long long)npx64,
@@ -2834,16 +2224,6 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   return JADE_OK;
 }
 
-// Rays claimed per queue atomic: large launches amortise the atomic over up to
-// JADE_TRACE_CHUNK rays, small ones keep 64 so every wave gets work.
-static uint32_t trace_chunk(const jade_scene* s, uint32_t n_rays) {
-  uint64_t waves = (uint64_t)s->trace_blocks * (JADE_TRACE_BLOCK / 64);
-  uint64_t per = n_rays / (waves * 64 * 8);  // aim at >= 8 grabs per wave
-  if (per < 1) per = 1;
-  if (per > JADE_TRACE_CHUNK / 64) per = JADE_TRACE_CHUNK / 64;
-  return (uint32_t)per * 64u;
-}
-
 static hipError_t sum_counters(jade_scene* s, DevCounters* out) {
   std::vector<DevCounters> sh(JADE_CTR_SHARDS);
   hipError_t e = hipMemcpyAsync(sh.data(), s->b_ctr.p, sizeof(DevCounters) * JADE_CTR_SHARDS, hipMemcpyDeviceToHost, s->stream);
@@ -2864,353 +2244,423 @@ static hipError_t sum_counters(jade_scene* s, DevCounters* out) {
   return e;
 }
 
-// shade/trace passes until a shade pass emits no ray (or the step may carry the rest over).  The host follows the first
-// passes of a step one by one (it picks the schedule from the counts) and the list-mode passes in batches of 8-16.
-static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool may_carry, double* ms_out, double* trace_ms_out, uint64_t* launches_out) {
-  const int npix = s->ps.npix;
-  QueueCtl* qc = s->b_ctl.as<QueueCtl>();
-  for (hipEvent_t& e : s->ev)
-    if (!e) HIP_TRY(hipEventCreate(&e));
-  const hipEvent_t ev0 = s->ev[0], ev1 = s->ev[1], ta = s->ev[2], tb = s->ev[3], sa = s->ev[4], sb = s->ev[5], sm = s->ev[6];
-  HIP_TRY(hipEventRecord(ev0, s->stream));
-  bool trace_pending = false, carried = false;
+// ---- run_passes: the schedule of one step / flush ----
+
+// The per-call state of run_passes.  Its pieces below each do one thing to it; every one queues its work on s->stream in the order written.
+struct PassRun {
+  jade_scene* s;
+  uint32_t target_spp;
+  QueueCtl* qc;                       // s->b_ctl: entry 0 for passes the host follows, the ring for a batch
+  decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
+  bool batching, tail_ok;
+  uint32_t tail_max;                  // active records at or below which k_tail finishes the list
+  uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
+  uint32_t n_active = 0;
+  const uint32_t* arm_dev = nullptr;  // k_arm's count, on the device, when the host has not waited for it
+  uint32_t host_ctl[3] = {0, 0, 0};   // {count, active, next} of the last pass the host followed
+  int cur = 0, pass_no = 0;
+  bool have_list = true;              // b_active[cur] lists the active records
+  bool trace_pending = false;         // the k_trace launch timed by (TA, TB) is not accounted for yet
+  bool closed = false;                // EV1 is recorded and waited for: the last wait was also the wait for the end of the call
+  bool done = false;                  // the call ends with records still active (carried over), or with nothing emitted
   double trace_ms = 0;
   uint64_t launches = 0;
-  s->tail_pending = false;  // whatever an earlier step left is part of this call's work
-  // While at least a quarter of the records are active, a pass is k_shade_lean over all records
-  // (record order, no list) followed by k_shade over what it handed over; below that, k_shade alone
-  // over the active list, which k_arm rebuilds once at the switch.  JADE_SHADE_SPLIT=0: always the list.
-  const bool split_ok = s->tun.shade_split;
-  // JADE_FUSED=0: the first pass as shade / trace passes too (k_shade_lean), the schedule before k_light existed
-  const bool fused = s->tun.fused;
-  // the records with work in this step: all of them when the step gives every record a sample (k_light then walks the
-  // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them
-  uint32_t host_ctl[3] = {0, 0, 0};
-  uint32_t n_active;
-  const uint32_t* arm_dev = nullptr;  // k_arm's count, on the device, when the host has not waited for it
-  if (fused && s->ps.stride == 0 && (int64_t)target_spp - from_spp >= (int64_t)s->ps.rpp) {
-    n_active = (uint32_t)npix;
-  } else if ((int64_t)target_spp == from_spp && s->carried_active > 0 && s->tun.batching && !s->sort_rays && !s->tun.log_passes && s->ps.stride == 0) {
+  float shade_ms = 0, lean_ms = 0;    // JADE_LOG_PASSES
+  enum { EV0, EV1, TA, TB, SA, SB, SM };  // s->ev
+  hipEvent_t ev(int i) const { return s->ev[i].e; }
+  bool carry_now(uint32_t act) const { return act < carry_below; }
+};
+
+// The carry-over point: a step may leave its paths to the next one once fewer than this many records are active - fewer than
+// JADE_CARRY_RECORDS and than 1/1024 of the n_armed records the call started with, or fewer than carry_frac of them.  The host's
+// decision (PassRun::carry_now) and the device's (k_shade's stop_below, inside a batch) are both "active < this".
+static uint32_t carry_threshold(const jade_scene* s, bool may_carry, uint32_t n_armed) {
+  if (!may_carry) return 0;
+  const double frac = s->tun.carry_frac;
+  const uint64_t a = std::min<uint64_t>(JADE_CARRY_RECORDS, ((uint64_t)n_armed + 1023) / 1024);  // act < CARRY_RECORDS && act * 1024 < n_armed
+  const uint64_t b = frac > 0 ? (uint64_t)std::min(std::ceil(frac * (double)n_armed), 4294967295.0) : 0;  // act < frac * n_armed
+  return (uint32_t)std::max(a, b);
+}
+
+// Rays claimed per queue atomic: large launches amortise the atomic over up to
+// JADE_TRACE_CHUNK rays, small ones keep 64 so every wave gets work.
+static uint32_t trace_chunk(const jade_scene* s, uint32_t n_rays) {
+  uint64_t waves = (uint64_t)s->trace_blocks * (JADE_TRACE_BLOCK / 64);
+  uint64_t per = n_rays / (waves * 64 * 8);  // aim at >= 8 grabs per wave
+  if (per < 1) per = 1;
+  if (per > JADE_TRACE_CHUNK / 64) per = JADE_TRACE_CHUNK / 64;
+  return (uint32_t)per * 64u;
+}
+
+void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays) {
+  const bool wide = trace_wide(s->dev, P);
+  hipLaunchKernelGGL(wide ? k_trace_wide : k_trace, dim3((unsigned)(wide ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream,
+                     s->dev, P, queue, qc, spill, ctr, n_rays ? trace_chunk(s, n_rays) : 0u);
+}
+
+// k_arm: clears the first `clear_bytes` of *ctl, then lists the records with work in b_active[0] and counts them in ctl->active
+static int launch_arm(jade_scene* s, uint32_t target_spp, QueueCtl* ctl, size_t clear_bytes) {
+  HIP_TRY(hipMemsetAsync(ctl, 0, clear_bytes, s->stream));
+  const size_t per_block = (size_t)JADE_ARM_BLOCK * JADE_ARM_PER_THREAD;
+  hipLaunchKernelGGL(k_arm, dim3((unsigned)(((size_t)s->ps.npix + per_block - 1) / per_block)), dim3(JADE_ARM_BLOCK), 0, s->stream, s->ps, target_spp,
+                     s->b_active[0].as<uint32_t>(), ctl);
+  return JADE_OK;
+}
+
+// the chosen shade kernel over `list`: n entries, or - n_dev not null - as many as the device counted there; the records it leaves
+// active go to `next` (nullable)
+static void launch_shade(const PassRun& r, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
+                         const QueueCtl* prev, uint32_t stop_below) {
+  jade_scene* s = r.s;
+  hipLaunchKernelGGL(r.shade_kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, list,
+                     n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below);
+}
+
+// a finished k_trace launch, timed by the events (a, b)
+static int account_trace(PassRun& r, hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  HIP_TRY(hipEventElapsedTime(&t, a, b));
+  r.trace_ms += t;
+  r.launches += 1;
+  return JADE_OK;
+}
+// ... the one of the last host-followed pass, if it is still open (the stream has been waited for since)
+static int account_pending_trace(PassRun& r) {
+  if (!r.trace_pending) return JADE_OK;
+  r.trace_pending = false;
+  return account_trace(r, r.ev(PassRun::TA), r.ev(PassRun::TB));
+}
+
+// The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
+// records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.
+static int arm_step(PassRun& r, int64_t from_spp) {
+  jade_scene* s = r.s;
+  if (s->tun.fused && s->ps.stride == 0 && (int64_t)r.target_spp - from_spp >= (int64_t)s->ps.rpp) {
+    r.n_active = (uint32_t)s->ps.npix;
+  } else if ((int64_t)r.target_spp == from_spp && s->carried_active > 0 && s->tun.batching && !s->sort_rays && !s->tun.log_passes && s->ps.stride == 0) {
     // A flush: no sample is started, so the records with work are exactly the ones the last step carried over, and the host knows
-    // how many those were - k_arm lists them, the first pass of the batch below reads the count on the device, nobody waits.
-    QueueCtl* qa = qc + JADE_CTL_RING;
-    HIP_TRY(hipMemsetAsync(qa, 0, 12, s->stream));
-    hipLaunchKernelGGL(k_arm, dim3((unsigned)(((size_t)npix + JADE_ARM_BLOCK * JADE_ARM_PER_THREAD - 1) / (JADE_ARM_BLOCK * JADE_ARM_PER_THREAD))), dim3(JADE_ARM_BLOCK), 0, s->stream, s->ps, target_spp,
-                       s->b_active[0].as<uint32_t>(), qa);
-    n_active = s->carried_active;  // (an upper bound is all the grids need)
-    arm_dev = &qa->active;
+    // how many those were - k_arm lists them, the first pass of the batch reads the count on the device, nobody waits.
+    QueueCtl* qa = r.qc + JADE_CTL_RING;
+    if (int rc = launch_arm(s, r.target_spp, qa, 12)) return rc;
+    r.n_active = s->carried_active;  // (an upper bound is all the grids need)
+    r.arm_dev = &qa->active;
   } else {
-    HIP_TRY(hipMemsetAsync(qc, 0, 12, s->stream));
-    hipLaunchKernelGGL(k_arm, dim3((unsigned)(((size_t)npix + JADE_ARM_BLOCK * JADE_ARM_PER_THREAD - 1) / (JADE_ARM_BLOCK * JADE_ARM_PER_THREAD))), dim3(JADE_ARM_BLOCK), 0, s->stream, s->ps, target_spp,
-                       s->b_active[0].as<uint32_t>(), qc);
-    HIP_TRY(hipMemcpyAsync(host_ctl, qc, 12, hipMemcpyDeviceToHost, s->stream));
+    if (int rc = launch_arm(s, r.target_spp, r.qc, 12)) return rc;
+    HIP_TRY(hipMemcpyAsync(r.host_ctl, r.qc, 12, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
     s->host_syncs += 1;
-    n_active = host_ctl[1];
+    r.n_active = r.host_ctl[1];
   }
   s->carried_active = 0;
-  const uint32_t n_armed = n_active;  // records with work at the start of this call
-  int cur = 0, pass_no = 0;
-  const bool log_passes = s->tun.log_passes;
-  bool have_list = true;  // b_active[cur] lists the active records
-  bool light_timed = false;
-  float shade_ms = 0, lean_ms = 0;
-  const double carry_frac = s->tun.carry_frac;
-  auto carry_now = [&](uint32_t act) {
-    return may_carry && ((act < JADE_CARRY_RECORDS && (uint64_t)act * 1024 < (uint64_t)n_armed) ||
-                         (carry_frac > 0 && (double)act < carry_frac * (double)n_armed));
-  };
-  // JADE_BATCH=0: the host follows every pass (the schedule before batching existed)
-  const bool batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  bool closed_by_batch = false;  // the wait at the end of a batch was also the wait for the end of the step
-  // k_tail: once the active list is short - and is not about to be carried over - ONE launch finishes its records (every wave
-  // shades and traces its own 64 until they are out of samples).  The records' last rays have been traced: k_tail starts by shading.
-  // k_shade with the records dealt by branch through LDS (k_shade_binned), unless switched off - or the render draws its
-  // environment rays by importance: a bounce may then emit no ray at all and is folded in on the spot, which the binned form does not do
-  auto shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
-  const bool tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling;  // (k_tail shades with the parity code only)
-  const uint32_t tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
-  while (n_active) {
-    const bool lean_mode = split_ok && (uint64_t)n_active * 4 >= (uint64_t)npix;
-    if (tail_ok && !lean_mode && have_list && pass_no > 0 && !arm_dev && n_active <= tail_max && !carry_now(n_active)) {
-      TailArgs ta;
-      ta.R = s->rc;
-      ta.tile_ids = s->b_tiles.as<int32_t>();
-      ta.target_spp = target_spp;
-      ta.list = s->b_active[cur].as<uint32_t>();
-      ta.n_list = n_active;
-      ta.queue = s->b_queue.as<uint32_t>();
-      for (hipEvent_t& e : s->ev_tail)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-      HIP_TRY(hipEventRecord(s->ev_tail[0], s->stream));
-      hipLaunchKernelGGL(k_tail, dim3((n_active + JADE_TRACE_BLOCK - 1) / JADE_TRACE_BLOCK), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, ta,
-                         s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>());
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipEventRecord(s->ev_tail[1], s->stream));
-      HIP_TRY(hipEventRecord(ev1, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      s->host_syncs += 1;
-      float tt = 0;
-      HIP_TRY(hipEventElapsedTime(&tt, s->ev_tail[0], s->ev_tail[1]));
-      s->tail_ms += tt;
-      s->tail_launches += 1;
-      s->tail_records += n_active;
-      if (log_passes) fprintf(stderr, "[jade] tail: %u records finished by k_tail in %.3f ms\n", n_active, tt);
-      n_active = 0;
-      closed_by_batch = true;  // (ev1 is recorded and waited for)
+  return JADE_OK;
+}
+
+// k_tail: once the active list is short - and is not about to be carried over - ONE launch finishes its records (every wave
+// shades and traces its own 64 until they are out of samples).  The records' last rays have been traced: k_tail starts by shading.
+static int finish_by_tail(PassRun& r) {
+  jade_scene* s = r.s;
+  TailArgs ta;
+  ta.R = s->rc;
+  ta.tile_ids = s->b_tiles.as<int32_t>();
+  ta.target_spp = r.target_spp;
+  ta.list = s->b_active[r.cur].as<uint32_t>();
+  ta.n_list = r.n_active;
+  ta.queue = s->b_queue.as<uint32_t>();
+  HIP_TRY(ensure_events(s->ev_tail));
+  HIP_TRY(hipEventRecord(s->ev_tail[0], s->stream));
+  hipLaunchKernelGGL(k_tail, dim3((r.n_active + JADE_TRACE_BLOCK - 1) / JADE_TRACE_BLOCK), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, ta,
+                     s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(s->ev_tail[1], s->stream));
+  HIP_TRY(hipEventRecord(r.ev(PassRun::EV1), s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->host_syncs += 1;
+  float tt = 0;
+  HIP_TRY(hipEventElapsedTime(&tt, s->ev_tail[0], s->ev_tail[1]));
+  s->tail_ms += tt;
+  s->tail_launches += 1;
+  s->tail_records += r.n_active;
+  if (s->tun.log_passes) fprintf(stderr, "[jade] tail: %u records finished by k_tail in %.3f ms\n", r.n_active, tt);
+  r.n_active = 0;
+  r.closed = true;
+  return JADE_OK;
+}
+
+// A BATCH of list-mode passes without the host in between: pass j's k_shade takes its length from the record
+// count pass j-1 left on the device (QueueCtl ring), k_trace sizes its chunks itself; a pass that finds nothing
+// to do is three empty launches.  The host looks once per batch: where the paths ended, whether to carry.
+static int run_batch(PassRun& r) {
+  jade_scene* s = r.s;
+  QueueCtl* qc = r.qc;
+  const int B = JADE_CTL_RING;
+  const unsigned nbb = (r.n_active + JADE_SHADE_BLOCK - 1) / JADE_SHADE_BLOCK;  // the active count only shrinks: an upper bound for all
+  // the device stops at the carry-over point - passes of the batch behind it do nothing (k_shade) - and at the point below which
+  // k_tail finishes the list: the host then launches it (run_passes)
+  uint32_t stop_below = r.carry_below;
+  if (r.tail_ok) stop_below = std::max(stop_below, r.tail_max + 1u);
+  HIP_TRY(ensure_events(s->ev_batch));
+  HIP_TRY(hipMemsetAsync(qc, 0, sizeof(QueueCtl) * B, s->stream));
+  const int cur0 = r.cur;
+  for (int j = 0; j < B; ++j) {
+    launch_shade(r, nbb, s->b_active[r.cur].as<uint32_t>(), r.n_active, j ? &qc[j - 1].active : r.arm_dev, s->b_active[r.cur ^ 1].as<uint32_t>(), qc + j,
+                 j ? qc + (j - 1) : (const QueueCtl*)nullptr, stop_below);
+    r.cur ^= 1;
+    HIP_TRY(hipEventRecord(s->ev_batch[2 * j], s->stream));
+    launch_trace(s, s->ps, s->b_queue.as<uint32_t>(), qc + j, s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), 0u);
+    HIP_TRY(hipEventRecord(s->ev_batch[2 * j + 1], s->stream));
+  }
+  HIP_TRY(hipGetLastError());
+  QueueCtl host_ring[JADE_CTL_RING];
+  HIP_TRY(hipMemcpyAsync(host_ring, qc, sizeof(QueueCtl) * B, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipEventRecord(r.ev(PassRun::EV1), s->stream));  // the end of the call, if this batch is its last (recorded again otherwise)
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  s->host_syncs += 1;
+  if (int rc = account_pending_trace(r)) return rc;  // the k_trace launch of the pass before the batch
+  bool ended = false, stopped = false;
+  int real = 0;        // passes of the batch that ran (the rest found the paths ended, or the carry-over point reached)
+  int pass_timed = 0;  // k_trace launches of the batch accounted for so far
+  for (int j = 0; j < B; ++j) {
+    if (host_ring[j].count == 0) {
+      if (host_ring[j].active == 0) {  // this pass emitted nothing and left nothing active: every path has ended
+        // (a pass that ran and finished the last paths, or - behind it - one that found nothing to do)
+        if (j == 0 || host_ring[j - 1].count != 0) real = j + 1;
+        r.n_active = 0;
+        ended = true;
+      } else {  // the device stopped here: fewer than stop_below records are active
+        r.n_active = host_ring[j].active;
+        stopped = true;
+      }
       break;
     }
-    if (!lean_mode && have_list && batching && !log_passes && (pass_no > 0 || arm_dev)) {
-      // ---- a BATCH of list-mode passes without the host in between: pass j's k_shade takes its length from the record
-      // count pass j-1 left on the device (QueueCtl ring), k_trace sizes its chunks itself; a pass that finds nothing
-      // to do is three empty launches.  The host looks once per batch: where the paths ended, whether to carry.
-      const int B = JADE_CTL_RING;
-      const unsigned nbb = (n_active + JADE_SHADE_BLOCK - 1) / JADE_SHADE_BLOCK;  // the active count only shrinks: an upper bound for all
-      // the carry-over point, for the device: passes of the batch behind it do nothing (k_shade)
-      uint32_t stop_below = 0;
-      if (may_carry) {
-        const uint64_t a = std::min<uint64_t>(JADE_CARRY_RECORDS, ((uint64_t)n_armed + 1023) / 1024);  // act < CARRY_RECORDS && act * 1024 < n_armed
-        const uint64_t b = carry_frac > 0 ? (uint64_t)std::ceil(carry_frac * (double)n_armed) : 0;     // act < carry_frac * n_armed
-        stop_below = (uint32_t)std::min<uint64_t>(std::max(a, b), 0xffffffffu);
-      }
-      // ... and the point below which k_tail finishes the list: the batch stops there too, the host then launches it (above)
-      if (tail_ok) stop_below = std::max(stop_below, tail_max + 1u);
-      for (hipEvent_t& e : s->ev_batch)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-      HIP_TRY(hipMemsetAsync(qc, 0, sizeof(QueueCtl) * B, s->stream));
-      const int cur0 = cur;
-      for (int j = 0; j < B; ++j) {
-        hipLaunchKernelGGL(shade_kernel, dim3(nbb), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(),
-                           target_spp, s->b_active[cur].as<uint32_t>(), n_active, j ? &qc[j - 1].active : arm_dev,
-                           s->b_active[cur ^ 1].as<uint32_t>(), s->b_queue.as<uint32_t>(), qc + j, s->b_ctr.as<DevCounters>(),
-                           j ? qc + (j - 1) : (const QueueCtl*)nullptr, stop_below);
-        cur ^= 1;
-        HIP_TRY(hipEventRecord(s->ev_batch[2 * j], s->stream));
-        hipLaunchKernelGGL(trace_wide(s->dev, s->ps) ? k_trace_wide : k_trace, dim3((unsigned)(trace_wide(s->dev, s->ps) ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps,
-                           s->b_queue.as<uint32_t>(), qc + j, s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), 0u);
-        HIP_TRY(hipEventRecord(s->ev_batch[2 * j + 1], s->stream));
-      }
-      HIP_TRY(hipGetLastError());
-      QueueCtl host_ring[JADE_CTL_RING];
-      HIP_TRY(hipMemcpyAsync(host_ring, qc, sizeof(QueueCtl) * B, hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipEventRecord(ev1, s->stream));  // the end of the step, if this batch is its last (recorded again otherwise)
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      s->host_syncs += 1;
-      if (trace_pending) {  // the k_trace launch of the pass before the batch
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, ta, tb));
-        trace_ms += t;
-        launches += 1;
-        trace_pending = false;
-      }
-      bool ended = false, stopped = false;
-      int real = 0;        // passes of the batch that ran (the rest found the paths ended, or the carry-over point reached)
-      int pass_timed = 0;  // k_trace launches of the batch accounted for so far
-      for (int j = 0; j < B; ++j) {
-        if (host_ring[j].count == 0) {
-          if (host_ring[j].active == 0) {  // this pass emitted nothing and left nothing active: every path has ended
-            // (a pass that ran and finished the last paths, or - behind it - one that found nothing to do)
-            if (j == 0 || host_ring[j - 1].count != 0) real = j + 1;
-            n_active = 0;
-            ended = true;
-          } else {  // the device stopped here: fewer than stop_below records are active
-            n_active = host_ring[j].active;
-            stopped = true;
-          }
-          break;
-        }
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, s->ev_batch[2 * j], s->ev_batch[2 * j + 1]));
-        trace_ms += t;
-        launches += 1;
-        pass_timed = j + 1;
-        n_active = host_ring[j].active;
-        ++pass_no;
-        real = j + 1;
-      }
-      // the launches behind the end of the step were made all the same (k_trace leaves at its first instruction): they count
-      // as launches, with their few microseconds, so that launches and time are what a profiler sees
-      for (int j = pass_timed; j < B; ++j) {
-        float t = 0;
-        HIP_TRY(hipEventElapsedTime(&t, s->ev_batch[2 * j], s->ev_batch[2 * j + 1]));
-        trace_ms += t;
-        launches += 1;
-      }
-      cur = cur0 ^ (real & 1);  // the list the last pass that ran wrote
-      arm_dev = nullptr;        // (the host has seen a count since)
-      if (ended) {
-        closed_by_batch = true;
-        break;
-      }
-      if (carry_now(n_active) || (stopped && !(tail_ok && n_active <= tail_max))) {
-        s->tail_pending = true;
-        s->carried_active = n_active;
-        closed_by_batch = true;
-        break;
-      }
-      continue;  // (another batch - or, the list being short now, k_tail)
-    }
-    if (!lean_mode && !have_list) {
-      cur = 0;
-      HIP_TRY(hipMemsetAsync(qc, 0, 16, s->stream));
-      hipLaunchKernelGGL(k_arm, dim3((unsigned)(((size_t)npix + JADE_ARM_BLOCK * JADE_ARM_PER_THREAD - 1) / (JADE_ARM_BLOCK * JADE_ARM_PER_THREAD))), dim3(JADE_ARM_BLOCK), 0, s->stream, s->ps, target_spp,
-                         s->b_active[0].as<uint32_t>(), qc);
-      have_list = true;
-    }
-    HIP_TRY(hipMemsetAsync(qc, 0, 16, s->stream));  // count, active, next, heavy
-    if (log_passes) HIP_TRY(hipEventRecord(sa, s->stream));
-    const unsigned nb = (n_active + JADE_SHADE_BLOCK - 1) / JADE_SHADE_BLOCK;
-    if (lean_mode && fused && pass_no == 0) {
-      // the step's first pass, fused: light samples run to completion inside k_light, everything else is handed over
-      for (hipEvent_t& e : s->ev_light)
-        if (!e) HIP_TRY(hipEventCreate(&e));
-      HIP_TRY(hipEventRecord(s->ev_light[0], s->stream));
-      light_timed = true;
-      {
-        // packets, unless the last step gave most of them up (a frame the statue fills: every packet fans out, and the per-lane
-        // kernel is then the better first pass - same bits, so the choice is free to make per step)
-        const bool packet = s->tun.light_packet && s->packet_blocks > 0 && s->packets_given_up < JADE_PACKET_GIVE_UP_LIMIT;
-        const unsigned lb = (unsigned)std::min<size_t>((size_t)(packet ? s->packet_blocks : s->light_blocks), ((size_t)npix + JADE_TRACE_BLOCK - 1) / JADE_TRACE_BLOCK);
-        const uint32_t n_waves = lb * (JADE_TRACE_BLOCK / 64);
-        // a wave takes every n_waves-th chunk of 64 records: its region must hold all of them
-        const uint32_t region_cap = (uint32_t)((((size_t)npix + 63) / 64 + n_waves - 1) / n_waves) * 64u;
-        if ((size_t)region_cap * n_waves > s->b_active[0].bytes / 4 || (size_t)2 * n_waves * 4 > s->b_wavecnt.bytes)
-          return fail(JADE_ERR_DEVICE, "hand-over regions do not fit (internal sizing error)");
-        if (packet)
-          hipLaunchKernelGGL(k_light_packet, dim3(lb), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), target_spp,
-                             s->b_active[0].as<uint32_t>(), region_cap, s->b_wavecnt.as<uint32_t>(), s->b_ctr.as<DevCounters>(),
-                             (uint32_t)s->tun.packet_budget);
-        else
-          hipLaunchKernelGGL(k_light, dim3(lb), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), target_spp,
-                             s->b_active[0].as<uint32_t>(), region_cap, s->b_wavecnt.as<uint32_t>(), s->b_spill.as<uint32_t>(),
-                             s->b_ctr.as<DevCounters>());
-        hipLaunchKernelGGL(k_heavy_scan, dim3(1), dim3(1024), 0, s->stream, s->b_wavecnt.as<uint32_t>(), n_waves, qc);
-        hipLaunchKernelGGL(k_heavy_pack, dim3(n_waves), dim3(256), 0, s->stream, s->b_active[0].as<uint32_t>(), region_cap,
-                           s->b_wavecnt.as<uint32_t>(), n_waves, s->b_active[1].as<uint32_t>());
-      }
-      HIP_TRY(hipEventRecord(s->ev_light[1], s->stream));
-      if (log_passes) HIP_TRY(hipEventRecord(sm, s->stream));
-      // k_light has run every other record to the end of its samples, so the records this pass leaves active ARE the active
-      // list (written over k_light's regions, which k_heavy_pack has emptied): no k_arm scan of all records after it
-      hipLaunchKernelGGL(shade_kernel, dim3(nb), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(),
-                         target_spp, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, s->b_active[0].as<uint32_t>(), s->b_queue.as<uint32_t>(), qc,
-                         s->b_ctr.as<DevCounters>(), (const QueueCtl*)nullptr, 0u);
-      have_list = true;
-      cur = 0;
-    } else if (lean_mode) {
-      // b_active[1] carries the hand-over list; no active list is kept in this mode
-      hipLaunchKernelGGL(k_shade_lean, dim3((unsigned)((npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
-                         s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), target_spp, s->b_active[1].as<uint32_t>(),
-                         s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
-      if (log_passes) HIP_TRY(hipEventRecord(sm, s->stream));
-      // only a record that was active can be handed over: n_active bounds the grid, the count stays on the device
-      hipLaunchKernelGGL(shade_kernel, dim3(nb), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(),
-                         target_spp, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, (uint32_t*)nullptr, s->b_queue.as<uint32_t>(), qc,
-                         s->b_ctr.as<DevCounters>(), (const QueueCtl*)nullptr, 0u);
-      have_list = false;
-    } else {
-      if (log_passes) HIP_TRY(hipEventRecord(sm, s->stream));
-      hipLaunchKernelGGL(shade_kernel, dim3(nb), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(),
-                         target_spp, s->b_active[cur].as<uint32_t>(), n_active, (const uint32_t*)nullptr,
-                         s->b_active[cur ^ 1].as<uint32_t>(), s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), (const QueueCtl*)nullptr, 0u);
-      cur ^= 1;
-    }
-    HIP_TRY(hipGetLastError());
-    if (log_passes) HIP_TRY(hipEventRecord(sb, s->stream));
-    HIP_TRY(hipMemcpyAsync(host_ctl, qc, 12, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (int rc = account_trace(r, s->ev_batch[2 * j], s->ev_batch[2 * j + 1])) return rc;
+    pass_timed = j + 1;
+    r.n_active = host_ring[j].active;
+    ++r.pass_no;
+    real = j + 1;
+  }
+  // the launches behind the end of the step were made all the same (k_trace leaves at its first instruction): they count
+  // as launches, with their few microseconds, so that launches and time are what a profiler sees
+  for (int j = pass_timed; j < B; ++j)
+    if (int rc = account_trace(r, s->ev_batch[2 * j], s->ev_batch[2 * j + 1])) return rc;
+  r.cur = cur0 ^ (real & 1);  // the list the last pass that ran wrote
+  r.arm_dev = nullptr;        // (the host has seen a count since)
+  if (ended) {
+    r.closed = true;
+  } else if (r.carry_now(r.n_active) || (stopped && !(r.tail_ok && r.n_active <= r.tail_max))) {
+    s->tail_pending = true;
+    s->carried_active = r.n_active;
+    r.closed = true;
+    r.done = true;
+  }
+  return JADE_OK;  // (otherwise: another batch - or, the list being short now, k_tail)
+}
+
+// The step's first pass, fused: light samples run to completion inside k_light / k_light_packet, everything else is handed over
+// (k_heavy_scan, k_heavy_pack) in b_active[1], counted in qc->heavy.
+static int launch_first_pass(PassRun& r) {
+  jade_scene* s = r.s;
+  const int npix = s->ps.npix;
+  // packets, unless the last step gave most of them up (a frame the statue fills: every packet fans out, and the per-lane
+  // kernel is then the better first pass - same bits, so the choice is free to make per step)
+  const bool packet = s->tun.light_packet && s->packet_blocks > 0 && s->packets_given_up < JADE_PACKET_GIVE_UP_LIMIT;
+  const unsigned lb = (unsigned)std::min<size_t>((size_t)(packet ? s->packet_blocks : s->light_blocks), ((size_t)npix + JADE_TRACE_BLOCK - 1) / JADE_TRACE_BLOCK);
+  const uint32_t n_waves = lb * (JADE_TRACE_BLOCK / 64);
+  // a wave takes every n_waves-th chunk of 64 records: its region must hold all of them
+  const uint32_t region_cap = (uint32_t)((((size_t)npix + 63) / 64 + n_waves - 1) / n_waves) * 64u;
+  if ((size_t)region_cap * n_waves > s->b_active[0].bytes / 4 || (size_t)2 * n_waves * 4 > s->b_wavecnt.bytes)
+    return jade_fail(JADE_ERR_DEVICE, "hand-over regions do not fit (internal sizing error)");
+  if (packet)
+    hipLaunchKernelGGL(k_light_packet, dim3(lb), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
+                       s->b_active[0].as<uint32_t>(), region_cap, s->b_wavecnt.as<uint32_t>(), s->b_ctr.as<DevCounters>(),
+                       (uint32_t)s->tun.packet_budget);
+  else
+    hipLaunchKernelGGL(k_light, dim3(lb), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
+                       s->b_active[0].as<uint32_t>(), region_cap, s->b_wavecnt.as<uint32_t>(), s->b_spill.as<uint32_t>(),
+                       s->b_ctr.as<DevCounters>());
+  hipLaunchKernelGGL(k_heavy_scan, dim3(1), dim3(1024), 0, s->stream, s->b_wavecnt.as<uint32_t>(), n_waves, r.qc);
+  hipLaunchKernelGGL(k_heavy_pack, dim3(n_waves), dim3(256), 0, s->stream, s->b_active[0].as<uint32_t>(), region_cap,
+                     s->b_wavecnt.as<uint32_t>(), n_waves, s->b_active[1].as<uint32_t>());
+  return JADE_OK;
+}
+
+// One pass the host follows, its shading half: in one of three forms, then the wait for its counts (r.host_ctl).
+//   fused (a step's first pass)  k_light / k_light_packet, then the shade kernel over what they handed over
+//   lean                         k_shade_lean over all records (record order, no list), then the shade kernel over what it handed over
+//   list                         the shade kernel alone over the active list, which k_arm rebuilds first if a lean pass came before
+static int shade_pass(PassRun& r, bool lean_mode) {
+  jade_scene* s = r.s;
+  QueueCtl* qc = r.qc;
+  const bool log_passes = s->tun.log_passes;
+  const bool first_fused = lean_mode && s->tun.fused && r.pass_no == 0;
+  if (!lean_mode && !r.have_list) {
+    r.cur = 0;
+    if (int rc = launch_arm(s, r.target_spp, qc, 16)) return rc;
+    r.have_list = true;
+  }
+  HIP_TRY(hipMemsetAsync(qc, 0, 16, s->stream));  // count, active, next, heavy
+  if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SA), s->stream));
+  const unsigned nb = (r.n_active + JADE_SHADE_BLOCK - 1) / JADE_SHADE_BLOCK;
+  if (first_fused) {
+    HIP_TRY(ensure_events(s->ev_light));
+    HIP_TRY(hipEventRecord(s->ev_light[0], s->stream));
+    if (int rc = launch_first_pass(r)) return rc;
+    HIP_TRY(hipEventRecord(s->ev_light[1], s->stream));
+    if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
+    // k_light has run every other record to the end of its samples, so the records this pass leaves active ARE the active
+    // list (written over k_light's regions, which k_heavy_pack has emptied): no k_arm scan of all records after it
+    launch_shade(r, nb, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, s->b_active[0].as<uint32_t>(), qc, nullptr, 0u);
+    r.have_list = true;
+    r.cur = 0;
+  } else if (lean_mode) {
+    // b_active[1] carries the hand-over list; no active list is kept in this mode
+    hipLaunchKernelGGL(k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
+                       s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(),
+                       s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
+    if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
+    // only a record that was active can be handed over: n_active bounds the grid, the count stays on the device
+    launch_shade(r, nb, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, nullptr, qc, nullptr, 0u);
+    r.have_list = false;
+  } else {
+    if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
+    launch_shade(r, nb, s->b_active[r.cur].as<uint32_t>(), r.n_active, nullptr, s->b_active[r.cur ^ 1].as<uint32_t>(), qc, nullptr, 0u);
+    r.cur ^= 1;
+  }
+  HIP_TRY(hipGetLastError());
+  if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SB), s->stream));
+  HIP_TRY(hipMemcpyAsync(r.host_ctl, qc, 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
   s->host_syncs += 1;
-    if (light_timed) {  // (the stream was just synchronised)
-      float lt = 0;
-      HIP_TRY(hipEventElapsedTime(&lt, s->ev_light[0], s->ev_light[1]));
-      s->light_ms += lt;
-      light_timed = false;
-    }
-    if (log_passes) {
-      HIP_TRY(hipEventElapsedTime(&shade_ms, sa, sb));
-      HIP_TRY(hipEventElapsedTime(&lean_ms, sa, sm));
-    }
-    if (trace_pending) {
-      float t = 0;
-      HIP_TRY(hipEventElapsedTime(&t, ta, tb));
-      trace_ms += t;
-      launches += 1;
-      trace_pending = false;
-    }
-    n_active = host_ctl[1];
-    if (host_ctl[0] == 0) break;
-    const uint32_t* trace_queue = s->b_queue.as<uint32_t>();
-    HIP_TRY(hipEventRecord(ta, s->stream));  // (the ordering counts as trace time)
-    if (s->sort_rays && host_ctl[0] >= s->tun.sort_min && host_ctl[0] <= s->sort_cap) {
-      const uint32_t n = host_ctl[0];
-      // (the keys are in b_sortkey already: the shading kernel wrote each beside its queue entry - PathState.keyq, round 4; until then
-      // k_ray_keys made them here, from three scattered sectors per ray, 2 % of a C5 step.  JADE_SORT_KEYS_KERNEL=1 brings that back.)
-      if (s->tun.sort_keys_kernel)
-        hipLaunchKernelGGL(k_ray_keys, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ps, s->b_queue.as<uint32_t>(), n, s->b_sortkey.as<uint32_t>(),
-                           s->b_sortpos.as<uint32_t>(), s->n_emit, s->ps.key_tri_bits);
-      // The temporary storage was sized once, for (sort_cap entries, bits 0..32).  rocPRIM's need shrinks with the length and with
-      // the bit range (fewer digit places, fewer look-back states; a short queue takes its merge-sort path: two buffers of n), and a
-      // buffer that is too small is an error return, not a fault (rocprim/detail/temp_storage.hpp: partition) - asked again here,
-      // on the host, for THIS length, so that the claim is checked and not assumed ("the round-3 fault").
-      size_t need = 0;
-      HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 32u, s->stream));
-      if (need > s->sort_tmp_bytes) return fail(JADE_ERR_DEVICE, "ray-queue sort: temporary storage smaller than rocPRIM asks for this length (internal sizing error)");
-      size_t tmp = s->sort_tmp_bytes;
-      HIP_TRY(rocprim::radix_sort_pairs(s->b_sorttmp.p, tmp, s->b_sortkey.as<uint32_t>(), s->b_sortkey2.as<uint32_t>(), s->b_sortpos.as<uint32_t>(),
-                                        s->b_sortq.as<uint32_t>(), (size_t)n, 0u, 32u, s->stream));
-      trace_queue = s->b_sortq.as<uint32_t>();  // positions, in the order k_trace is to take them (PathState.idxq)
-    }
-    PathState tps = s->ps;
-    tps.idxq = trace_queue != s->b_queue.as<uint32_t>() ? s->b_queue.as<uint32_t>() : nullptr;
-    hipLaunchKernelGGL(trace_wide(s->dev, s->ps) ? k_trace_wide : k_trace, dim3((unsigned)(trace_wide(s->dev, s->ps) ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, tps,
-                       trace_queue, qc, s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(),
-                       trace_chunk(s, host_ctl[0]));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(tb, s->stream));
-    trace_pending = true;
-    if (carry_now(n_active)) {
-      // The few long paths left would take dozens of nearly empty passes: leave them suspended (their
-      // rays are traced, their hits wait to be folded in) for the next step's first pass, or for flush.
-      s->tail_pending = true;
-      s->carried_active = n_active;
-      carried = true;
-    }
-    if (log_passes) {
-      HIP_TRY(hipEventSynchronize(tb));
-      float t = 0;
-      HIP_TRY(hipEventElapsedTime(&t, ta, tb));
-      DevCounters cc{};  // development log only: node records and triangle tests of this launch (counters accumulate over the step)
-      HIP_TRY(sum_counters(s, &cc));
-      static thread_local unsigned long long v_prev = 0, t_prev = 0;
-      if (pass_no == 0 && (cc.nodes_visited < v_prev || cc.tris_tested < t_prev)) v_prev = t_prev = 0;
-      if (cc.nodes_visited < v_prev) v_prev = t_prev = 0;
-      fprintf(stderr, "[jade] pass %4d active %9u rays %9u shade %7.3f ms (lean %6.3f) trace %8.3f ms (%7.1f Mray/s) V/ray %6.1f T/ray %5.1f\n", pass_no,
-              n_active, host_ctl[0], shade_ms, lean_ms, t, host_ctl[0] / (t * 1e3), (double)(cc.nodes_visited - v_prev) / host_ctl[0],
-              (double)(cc.tris_tested - t_prev) / host_ctl[0]);
-      v_prev = cc.nodes_visited;
-      t_prev = cc.tris_tested;
-    }
-    ++pass_no;
-    if (carried) break;
+  if (first_fused) {  // (the stream was just synchronised)
+    float lt = 0;
+    HIP_TRY(hipEventElapsedTime(&lt, s->ev_light[0], s->ev_light[1]));
+    s->light_ms += lt;
   }
-  if (trace_pending) {  // the launch timed by (ta, tb) when the loop stopped right after it
-    HIP_TRY(hipEventSynchronize(tb));
-    float t = 0;
-    HIP_TRY(hipEventElapsedTime(&t, ta, tb));
-    trace_ms += t;
-    launches += 1;
-    trace_pending = false;
+  if (log_passes) {
+    HIP_TRY(hipEventElapsedTime(&r.shade_ms, r.ev(PassRun::SA), r.ev(PassRun::SB)));
+    HIP_TRY(hipEventElapsedTime(&r.lean_ms, r.ev(PassRun::SA), r.ev(PassRun::SM)));
   }
-  if (!closed_by_batch) {
-    HIP_TRY(hipEventRecord(ev1, s->stream));
-    HIP_TRY(hipEventSynchronize(ev1));
+  return account_pending_trace(r);
+}
+
+// Orders the queue of n rays by (kind, source triangle, octant) when the scene asks for it and the queue is long enough:
+// *trace_queue then is the list of positions in the order k_trace is to take them (PathState.idxq)
+static int order_queue(jade_scene* s, uint32_t n, const uint32_t** trace_queue) {
+  if (!(s->sort_rays && n >= s->tun.sort_min && n <= s->sort_cap)) return JADE_OK;
+  // (the keys are in b_sortkey already: the shading kernel wrote each beside its queue entry - PathState.keyq, round 4; until then
+  // k_ray_keys made them here, from three scattered sectors per ray, 2 % of a C5 step.  JADE_SORT_KEYS_KERNEL=1 brings that back.)
+  if (s->tun.sort_keys_kernel)
+    hipLaunchKernelGGL(k_ray_keys, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ps, s->b_queue.as<uint32_t>(), n, s->b_sortkey.as<uint32_t>(),
+                       s->b_sortpos.as<uint32_t>(), s->n_emit, s->ps.key_tri_bits);
+  // The temporary storage was sized once, for (sort_cap entries, bits 0..32).  rocPRIM's need shrinks with the length and with
+  // the bit range (fewer digit places, fewer look-back states; a short queue takes its merge-sort path: two buffers of n), and a
+  // buffer that is too small is an error return, not a fault (rocprim/detail/temp_storage.hpp: partition) - asked again here,
+  // on the host, for THIS length, so that the claim is checked and not assumed ("the round-3 fault").
+  size_t need = 0;
+  HIP_TRY(rocprim::radix_sort_pairs(nullptr, need, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n, 0u, 32u, s->stream));
+  if (need > s->sort_tmp_bytes) return jade_fail(JADE_ERR_DEVICE, "ray-queue sort: temporary storage smaller than rocPRIM asks for this length (internal sizing error)");
+  size_t tmp = s->sort_tmp_bytes;
+  HIP_TRY(rocprim::radix_sort_pairs(s->b_sorttmp.p, tmp, s->b_sortkey.as<uint32_t>(), s->b_sortkey2.as<uint32_t>(), s->b_sortpos.as<uint32_t>(),
+                                    s->b_sortq.as<uint32_t>(), (size_t)n, 0u, 32u, s->stream));
+  *trace_queue = s->b_sortq.as<uint32_t>();
+  return JADE_OK;
+}
+
+// JADE_LOG_PASSES: one line for the pass whose k_trace launch was just made (waits for it)
+static int log_pass(PassRun& r) {
+  jade_scene* s = r.s;
+  HIP_TRY(hipEventSynchronize(r.ev(PassRun::TB)));
+  float t = 0;
+  HIP_TRY(hipEventElapsedTime(&t, r.ev(PassRun::TA), r.ev(PassRun::TB)));
+  DevCounters cc{};  // development log only: node records and triangle tests of this launch (counters accumulate over the step)
+  HIP_TRY(sum_counters(s, &cc));
+  static thread_local unsigned long long v_prev = 0, t_prev = 0;
+  if (r.pass_no == 0 && (cc.nodes_visited < v_prev || cc.tris_tested < t_prev)) v_prev = t_prev = 0;
+  if (cc.nodes_visited < v_prev) v_prev = t_prev = 0;
+  fprintf(stderr, "[jade] pass %4d active %9u rays %9u shade %7.3f ms (lean %6.3f) trace %8.3f ms (%7.1f Mray/s) V/ray %6.1f T/ray %5.1f\n", r.pass_no,
+          r.n_active, r.host_ctl[0], r.shade_ms, r.lean_ms, t, r.host_ctl[0] / (t * 1e3), (double)(cc.nodes_visited - v_prev) / r.host_ctl[0],
+          (double)(cc.tris_tested - t_prev) / r.host_ctl[0]);
+  v_prev = cc.nodes_visited;
+  t_prev = cc.tris_tested;
+  return JADE_OK;
+}
+
+// One pass the host follows: shade, wait for the counts, then - unless nothing was emitted - order the queue and launch the trace,
+// which stays open (trace_pending) until the next wait.
+static int run_host_pass(PassRun& r, bool lean_mode) {
+  jade_scene* s = r.s;
+  if (int rc = shade_pass(r, lean_mode)) return rc;
+  r.n_active = r.host_ctl[1];
+  if (r.host_ctl[0] == 0) {
+    r.done = true;
+    return JADE_OK;
+  }
+  const uint32_t* trace_queue = s->b_queue.as<uint32_t>();
+  HIP_TRY(hipEventRecord(r.ev(PassRun::TA), s->stream));  // (the ordering counts as trace time)
+  if (int rc = order_queue(s, r.host_ctl[0], &trace_queue)) return rc;
+  PathState tps = s->ps;
+  tps.idxq = trace_queue != s->b_queue.as<uint32_t>() ? s->b_queue.as<uint32_t>() : nullptr;
+  launch_trace(s, tps, trace_queue, r.qc, s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), r.host_ctl[0]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(r.ev(PassRun::TB), s->stream));
+  r.trace_pending = true;
+  if (r.carry_now(r.n_active)) {
+    // The few long paths left would take dozens of nearly empty passes: leave them suspended (their
+    // rays are traced, their hits wait to be folded in) for the next step's first pass, or for flush.
+    s->tail_pending = true;
+    s->carried_active = r.n_active;
+    r.done = true;
+  }
+  if (s->tun.log_passes)
+    if (int rc = log_pass(r)) return rc;
+  ++r.pass_no;
+  return JADE_OK;
+}
+
+// shade/trace passes until a shade pass emits no ray (or the step may carry the rest over).  What runs next, by the records active:
+//   at least a quarter of all records (JADE_SHADE_SPLIT=0: never)     a pass the host follows, fused (a step's first) or lean
+//   a short list that is not about to be carried over                 k_tail finishes it: the end of the call
+//   a list, after the first pass (JADE_BATCH=0, ordered queues,       a batch of JADE_CTL_RING passes, one wait; it ends the call,
+//   JADE_LOG_PASSES: never)                                           carries over, or leaves a shorter list
+//   otherwise                                                         a pass the host follows, over the list
+static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool may_carry, double* ms_out, double* trace_ms_out, uint64_t* launches_out) {
+  HIP_TRY(ensure_events(s->ev));
+  PassRun r{s, target_spp, s->b_ctl.as<QueueCtl>()};
+  HIP_TRY(hipEventRecord(r.ev(PassRun::EV0), s->stream));
+  s->tail_pending = false;  // whatever an earlier step left is part of this call's work
+  if (int rc = arm_step(r, from_spp)) return rc;
+  r.carry_below = carry_threshold(s, may_carry, r.n_active);
+  // k_shade with the records dealt by branch through LDS (k_shade_binned), unless switched off - or the render draws its
+  // environment rays by importance: a bounce may then emit no ray at all and is folded in on the spot, which the binned form does not do
+  r.shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
+  r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling;  // (k_tail shades with the parity code only)
+  r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
+  while (r.n_active && !r.done) {
+    const bool lean_mode = s->tun.shade_split && (uint64_t)r.n_active * 4 >= (uint64_t)s->ps.npix;
+    const bool list_mode = !lean_mode && r.have_list;
+    int rc;
+    if (r.tail_ok && list_mode && r.pass_no > 0 && !r.arm_dev && r.n_active <= r.tail_max && !r.carry_now(r.n_active))
+      rc = finish_by_tail(r);
+    else if (list_mode && r.batching && !s->tun.log_passes && (r.pass_no > 0 || r.arm_dev))
+      rc = run_batch(r);
+    else
+      rc = run_host_pass(r, lean_mode);
+    if (rc) return rc;
+  }
+  if (r.trace_pending) {  // the launch timed by (TA, TB) when the loop stopped right after it
+    HIP_TRY(hipEventSynchronize(r.ev(PassRun::TB)));
+    if (int rc = account_pending_trace(r)) return rc;
+  }
+  if (!r.closed) {
+    HIP_TRY(hipEventRecord(r.ev(PassRun::EV1), s->stream));
+    HIP_TRY(hipEventSynchronize(r.ev(PassRun::EV1)));
     s->host_syncs += 1;
   }
   float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+  HIP_TRY(hipEventElapsedTime(&ms, r.ev(PassRun::EV0), r.ev(PassRun::EV1)));
   *ms_out = ms;
-  *trace_ms_out = trace_ms;
-  *launches_out = launches;
+  *trace_ms_out = r.trace_ms;
+  *launches_out = r.launches;
   return JADE_OK;
 }
 
@@ -3295,7 +2745,7 @@ static int grow_sums(jade_scene* s, int64_t spp_total) {
 }
 
 int jade_render_query(jade_scene* s, int what, int64_t* value) {
-  if (!s || !value || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (!s || !value || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
   switch (what) {
     case JADE_Q_RECORDS_PER_PIXEL: *value = s->ps.npix ? s->ps.rpp : 0; return JADE_OK;
     case JADE_Q_STATE_BYTES:
@@ -3304,7 +2754,7 @@ int jade_render_query(jade_scene* s, int what, int64_t* value) {
                           : 0;
       return JADE_OK;
     case JADE_Q_SUM_LANES: *value = s->ps.npix ? s->ps.sum_lanes : 0; return JADE_OK;
-    default: return fail(JADE_ERR_INVALID, "unknown query");
+    default: return jade_fail(JADE_ERR_INVALID, "unknown query");
   }
 }
 
@@ -3325,9 +2775,9 @@ static void dn_hand_over(jade_scene* s, jade_stats* st) {
 }
 
 int jade_render_step(jade_scene* s, int32_t spp, jade_stats* st) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
-  if (spp < 0) return fail(JADE_ERR_INVALID, "negative spp");
-  if (s->adaptive_done) return fail(JADE_ERR_INVALID, "the adaptive render has ended: jade_render_begin starts a new one");
+  if (!s || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (spp < 0) return jade_fail(JADE_ERR_INVALID, "negative spp");
+  if (s->adaptive_done) return jade_fail(JADE_ERR_INVALID, "the adaptive render has ended: jade_render_begin starts a new one");
   dn_hand_over(s, st);
   HIP_TRY(hipSetDevice(s->device));
   if (s->ps.npix == 0 || spp == 0) {
@@ -3343,117 +2793,14 @@ int jade_render_step(jade_scene* s, int32_t spp, jade_stats* st) {
 }
 
 int jade_render_flush(jade_scene* s, jade_stats* st) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (!s || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
   if (st) dn_hand_over(s, st);  // (the flushes inside resolve and the denoiser pass no statistics: the counters wait for the next step)
   if (!s->tail_pending || s->ps.npix == 0) return JADE_OK;
   HIP_TRY(hipSetDevice(s->device));
   return advance(s, s->spp_done, false, st);
 }
 
-// ---- adaptive sampling (include/jade_bvh.h; kernel: jade_adaptive.hip) ----
-// Rounds of step + flush at the targets min_spp, 2 min_spp, ... spp; after each round below the cap k_tile_error stops the converged
-// tiles (their records' sample counters move past every target, PathState.hdr) and lists the others.  The host waits once per round,
-// for the number of tiles that go on.  The render is begun with spp = the cap, so records per pixel and sum lanes are a cap render's.
-int jade_render_adaptive(jade_scene* s, const jade_render_params* rp, int32_t min_spp, float rel_error, float error_floor, float* out_rgb,
-                         uint8_t* out_bgr8, int32_t* out_tile_spp, jade_stats* st) {
-  if (!s || !rp) return fail(JADE_ERR_INVALID, "null argument");
-  if (rp->spp <= 0) return fail(JADE_ERR_INVALID, "spp (the cap) must be positive");
-  if (min_spp < 2 || min_spp > rp->spp || (min_spp & (min_spp - 1)) != 0)
-    return fail(JADE_ERR_INVALID, "min_spp must be a power of two with 2 <= min_spp <= spp");
-  if (!std::isfinite(rel_error) || !(rel_error > 0.0f)) return fail(JADE_ERR_INVALID, "rel_error must be finite and > 0");
-  if (!std::isfinite(error_floor) || !(error_floor > 0.0f)) return fail(JADE_ERR_INVALID, "error_floor must be finite and > 0");
-  if (s->tun.pixel_rotate) return fail(JADE_ERR_UNSUPPORTED, "adaptive sampling with JADE_PIXEL_ROTATE (records move between pixels)");
-  if (int rc = jade_render_begin(s, rp)) return rc;
-  const size_t nt = s->tile_ids.size();
-  uint32_t n_active = s->ps.npix ? (uint32_t)nt : 0u;
-  if (n_active) {
-    std::vector<uint32_t> all(nt);
-    for (size_t t = 0; t < nt; ++t) all[t] = (uint32_t)t;
-    std::vector<int32_t> cap(nt, rp->spp);  // a tile that never stops ends at the cap
-    HIP_TRY(upload(s->b_alist[0], all.data(), nt, s->stream));
-    HIP_TRY(upload(s->b_tile_n, cap.data(), nt, s->stream));
-    HIP_TRY(s->b_alist[1].alloc(nt * 4));
-    HIP_TRY(s->b_actl.alloc(8));
-    for (hipEvent_t& e : s->ev_err)
-      if (!e) HIP_TRY(hipEventCreate(&e));
-  }
-  int cur = 0;
-  for (int32_t prev = 0, target = min_spp;;) {
-    if (int rc = jade_render_step(s, target - prev, st)) return rc;
-    if (int rc = jade_render_flush(s, st)) return rc;
-    if (target >= rp->spp || n_active == 0) break;
-    HIP_TRY(hipMemsetAsync(s->b_actl.p, 0, 8, s->stream));
-    HIP_TRY(hipEventRecord(s->ev_err[0], s->stream));
-    uint32_t* ctl = s->b_actl.as<uint32_t>();
-    HIP_TRY(adaptive_tile_error(s->stream, n_active, s->ps, s->rc, s->b_tiles.as<int32_t>(), s->b_alist[cur].as<uint32_t>(), nullptr, (double)error_floor,
-                                rel_error, target, s->b_alist[cur ^ 1].as<uint32_t>(), ctl, s->b_tile_n.as<int32_t>(), nullptr, ctl + 1));
-    HIP_TRY(hipEventRecord(s->ev_err[1], s->stream));
-    uint32_t h[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(h, ctl, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev_err[0], s->ev_err[1]));
-    if (st) {
-      st->kernel_ms += ms;
-      st->host_syncs += 1;
-    }
-    if (h[1]) return fail(JADE_ERR_DEVICE, "adaptive: " + std::to_string(h[1]) + " records of stopped tiles were not idle");  // (debug builds count them)
-    n_active = h[0];
-    cur ^= 1;
-    if (n_active == 0) break;
-    prev = target;
-    target = (int32_t)std::min<int64_t>(2 * (int64_t)target, rp->spp);
-  }
-  // each tile's count, once; its 1 / n exactly as resolve_to makes the uniform one
-  s->tile_n.assign(nt, rp->spp);
-  if (nt && s->ps.npix) {
-    HIP_TRY(hipMemcpyAsync(s->tile_n.data(), s->b_tile_n.p, nt * 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    std::vector<float> inv(nt);
-    for (size_t t = 0; t < nt; ++t) inv[t] = (float)(1.0 / (double)s->tile_n[t]);
-    HIP_TRY(upload(s->b_tile_inv, inv.data(), nt, s->stream));
-  }
-  s->adaptive_done = true;
-  if (out_tile_spp) {
-    const size_t all = (size_t)s->rc.tiles_x * (size_t)((rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE);
-    std::fill(out_tile_spp, out_tile_spp + all, 0);
-    for (size_t t = 0; t < nt; ++t) out_tile_spp[s->tile_ids[t]] = s->tile_n[t];
-  }
-  if (!out_rgb && !out_bgr8) return jade_render_flush(s, nullptr);
-  return jade_render_resolve(s, out_rgb, out_bgr8);
-}
-
-int jade_render_error(jade_scene* s, float error_floor, float* out_error) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
-  if (!out_error) return fail(JADE_ERR_INVALID, "null argument");
-  if (!std::isfinite(error_floor) || !(error_floor > 0.0f)) return fail(JADE_ERR_INVALID, "error_floor must be finite and > 0");
-  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
-  HIP_TRY(hipSetDevice(s->device));
-  if (int rc = jade_render_flush(s, nullptr)) return rc;
-  const int npx = s->ps.npx;
-  if (npx == 0) return JADE_OK;
-  const size_t nt = s->tile_ids.size();
-  std::vector<int32_t> n(nt, (int32_t)std::min<int64_t>(s->spp_done, INT32_MAX));
-  if (!s->tile_n.empty()) n = s->tile_n;
-  DevBuf b_n;
-  HIP_TRY(upload(b_n, n.data(), nt, s->stream));
-  HIP_TRY(s->b_err.alloc((size_t)npx * 4));
-  HIP_TRY(adaptive_tile_error(s->stream, (uint32_t)nt, s->ps, s->rc, s->b_tiles.as<int32_t>(), nullptr, b_n.as<int32_t>(), (double)error_floor, 0.0f, 0,
-                              nullptr, nullptr, nullptr, s->b_err.as<float>(), nullptr));
-  std::vector<float> e((size_t)npx);
-  HIP_TRY(hipMemcpyAsync(e.data(), s->b_err.p, e.size() * 4, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  // scatter the compact tiles into the caller's map, as jade_render_resolve_ex does with the radiance
-  const int W = s->rp.width, H = s->rp.height, tx = s->rc.tiles_x;
-  for (size_t t = 0; t < nt; ++t) {
-    int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
-    int ww = std::min(JADE_TILE_SIZE, W - x0), hh = std::min(JADE_TILE_SIZE, H - y0);
-    for (int ly = 0; ly < hh; ++ly) memcpy(out_error + (size_t)(y0 + ly) * W + x0, e.data() + t * 256 + (size_t)ly * 16, (size_t)ww * 4);
-  }
-  return JADE_OK;
-}
-
-static int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream) {
+int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream) {
   const int npix = s->ps.npx;
   if (npix == 0) return JADE_OK;
   float inv = (float)(1.0 / (double)s->spp_done);  // vec3(1.0 / spp), PathTrace.cu:1457
@@ -3470,9 +2817,9 @@ int jade_render_resolve(jade_scene* s, float* out_rgb, uint8_t* out_bgr8) {
 }
 
 int jade_render_resolve_ex(jade_scene* s, int tonemap, float limit, float* out_rgb, uint8_t* out_bgr8) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
-  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return fail(JADE_ERR_INVALID, "unknown tone operator");
-  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
+  if (!s || !s->have_rp) return jade_fail(JADE_ERR_INVALID, "jade_render_begin not called");
+  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return jade_fail(JADE_ERR_INVALID, "unknown tone operator");
+  if (s->spp_done <= 0) return jade_fail(JADE_ERR_INVALID, "no samples rendered yet");
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = jade_render_flush(s, nullptr)) return rc;
   const int npix = s->ps.npx;
@@ -3493,298 +2840,35 @@ int jade_render_resolve_ex(jade_scene* s, int tonemap, float limit, float* out_r
   }
   HIP_TRY(hipStreamSynchronize(s->stream));
   // scatter the compact tiles into the caller's frame; other ranks' pixels untouched
-  const int W = s->rp.width, H = s->rp.height, tx = s->rc.tiles_x;
-  for (size_t t = 0; t < s->tile_ids.size(); ++t) {
-    int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
-    int ww = std::min(JADE_TILE_SIZE, W - x0), hh = std::min(JADE_TILE_SIZE, H - y0);
+  const int W = s->rp.width;
+  for_each_owned_tile(s->tile_ids, W, s->rp.height, [&](size_t t, int x0, int y0, int ww, int hh) {
     for (int ly = 0; ly < hh; ++ly) {
       size_t src = (t * 256 + (size_t)ly * 16) * 3, dst = ((size_t)(y0 + ly) * W + x0) * 3;
       if (out_rgb) memcpy(out_rgb + dst, hrgb.data() + src, (size_t)ww * 12);
       if (out_bgr8) memcpy(out_bgr8 + dst, hbgr.data() + src, (size_t)ww * 3);
     }
-  }
+  });
   return JADE_OK;
 }
 
 int jade_render_resolve_tiles_device(jade_scene* s, float* dev_tiles, void* stream) {
-  if (!s || !s->have_rp || !dev_tiles) return fail(JADE_ERR_INVALID, "bad arguments");
-  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
+  if (!s || !s->have_rp || !dev_tiles) return jade_fail(JADE_ERR_INVALID, "bad arguments");
+  if (s->spp_done <= 0) return jade_fail(JADE_ERR_INVALID, "no samples rendered yet");
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = jade_render_flush(s, nullptr)) return rc;
   HIP_TRY(hipStreamSynchronize(s->stream));
   if (int rc = resolve_to(s, JADE_TONEMAP_ACES, 0.0f, dev_tiles, nullptr, (hipStream_t)stream)) return rc;
   // k_resolve reads the partial sums on the CALLER's stream: the scene's own stream must not start the next
   // step (which adds to them) before it has finished
-  if (!s->ev_resolve) HIP_TRY(hipEventCreateWithFlags(&s->ev_resolve, hipEventDisableTiming));
+  if (!s->ev_resolve.e) HIP_TRY(hipEventCreateWithFlags(&s->ev_resolve.e, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(s->ev_resolve, (hipStream_t)stream));
   HIP_TRY(hipStreamWaitEvent(s->stream, s->ev_resolve, 0));
   return JADE_OK;
 }
 
-// ---- denoiser (include/jade_bvh.h; kernels: jade_denoise.hip) ----
-
-void jade_denoise_defaults(jade_denoise_params* p) {
-  if (!p) return;
-  // of SVGF's 5 passes and sigma_l = 4 and the sweep around them, 3 passes and sigma_l = 2 gave the lowest relMSE of the
-  // denoised 64-spp frames of C2 and C3 (profiles/denoise_ab.json); sigma_n made no difference there and stays SVGF's 128
-  p->iterations = 3;
-  p->guide_spp = 4;
-  p->sigma_luminance = 2.0f;
-  p->sigma_normal = 128.0f;
-  p->sigma_depth = 0.1f;
-  p->sigma_albedo = 0.1f;
-}
-
-static int dn_check_params(const jade_denoise_params* dp) {
-  if (!dp) return fail(JADE_ERR_INVALID, "null denoise parameters");
-  if (dp->iterations < 0 || dp->iterations > 8) return fail(JADE_ERR_INVALID, "iterations must be 0..8");
-  if (dp->guide_spp < 1 || dp->guide_spp > 64) return fail(JADE_ERR_INVALID, "guide_spp must be 1..64");
-  if (!std::isfinite(dp->sigma_luminance) || !(dp->sigma_luminance > 0.0f)) return fail(JADE_ERR_INVALID, "sigma_luminance must be finite and > 0");
-  if (!std::isfinite(dp->sigma_normal) || !(dp->sigma_normal >= 0.0f)) return fail(JADE_ERR_INVALID, "sigma_normal must be finite and >= 0");
-  if (!std::isfinite(dp->sigma_depth) || !(dp->sigma_depth > 0.0f)) return fail(JADE_ERR_INVALID, "sigma_depth must be finite and > 0");
-  if (!std::isfinite(dp->sigma_albedo) || !(dp->sigma_albedo > 0.0f)) return fail(JADE_ERR_INVALID, "sigma_albedo must be finite and > 0");
-  return JADE_OK;
-}
-
-// grow-only: the denoiser's buffers are allocated on first use and kept (they do not come out of the records' budget, which
-// jade_render_begin sizes before any of them exists)
-static hipError_t dn_alloc(DevBuf& b, size_t bytes) { return (b.p && b.bytes >= bytes) ? hipSuccess : b.alloc(bytes); }
-
-// Finish the paths the last step carried over, as resolve does; their work counters wait in dn_carried for the next step.
-static int dn_flush(jade_scene* s) {
-  jade_stats st{};
-  if (int rc = jade_render_flush(s, &st)) return rc;
-  s->dn_carried = st;  // (the flush took over what dn_carried held)
-  return JADE_OK;
-}
-
-// each owned tile's sample count: its own after jade_render_adaptive, otherwise spp_done
-static std::vector<int32_t> dn_tile_counts(const jade_scene* s) {
-  if (!s->tile_n.empty()) return s->tile_n;
-  return std::vector<int32_t>(s->tile_ids.size(), (int32_t)std::min<int64_t>(s->spp_done, INT32_MAX));
-}
-
-// the variance of every owned pixel into b_dn_var (compact layout)
-static int dn_variance(jade_scene* s) {
-  const size_t nt = s->tile_ids.size();
-  HIP_TRY(dn_alloc(s->b_dn_var, (size_t)s->ps.npx * 4));
-  DevBuf b_n;
-  const int32_t* tile_n = nullptr;
-  if (!s->tile_n.empty()) {
-    HIP_TRY(upload(b_n, s->tile_n.data(), nt, s->stream));
-    tile_n = b_n.as<int32_t>();
-  }
-  HIP_TRY(denoise_variance(s->stream, (uint32_t)nt, s->ps, tile_n, s->spp_done, s->b_dn_var.as<float>()));
-  HIP_TRY(hipStreamSynchronize(s->stream));  // (b_n goes out of scope)
-  return JADE_OK;
-}
-
-// The guide pass: G camera samples of every owned in-image pixel, one sample after the other, into b_dn_az = {albedo, depth} and
-// b_dn_n = {normal, 0} (compact layout).  k_trace itself walks the rays (reference walk, nearest hit) on a throw-away PathState, with
-// queue words and work counters of its own: neither the render's state nor its statistics see these rays.  The host waits once per
-// k_trace launch, for the number of mirror continuations (a sample ends after at most JADE_MAX_FULL_REFLEX_TIME + 1 launches).
-static int dn_guides(jade_scene* s, int G) {
-  const size_t n = (size_t)s->ps.npx;
-  HIP_TRY(dn_alloc(s->b_dn_orgs, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_slot, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_hitp, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_state, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_mirrors, n * 4));
-  HIP_TRY(dn_alloc(s->b_dn_list, n * 4));
-  HIP_TRY(dn_alloc(s->b_dn_q[0], n * 4));
-  HIP_TRY(dn_alloc(s->b_dn_q[1], n * 4));
-  HIP_TRY(dn_alloc(s->b_dn_az, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_n, n * 16));
-  HIP_TRY(dn_alloc(s->b_dn_ctl, 2 * sizeof(QueueCtl)));
-  HIP_TRY(dn_alloc(s->b_dn_ctr, sizeof(DevCounters) * JADE_CTR_SHARDS));
-  if (!s->b_spill.p)
-    HIP_TRY(s->b_spill.alloc((size_t)(JADE_BVH_STACK_CAPACITY - JADE_LDS_STACK) * s->trace_blocks * JADE_TRACE_BLOCK * 4));
-  // the owned in-image pixels, in owned order: the first queue of every sample
-  std::vector<uint32_t> list;
-  list.reserve(n);
-  const int W = s->rp.width, H = s->rp.height, tx = s->rc.tiles_x;
-  for (size_t t = 0; t < s->tile_ids.size(); ++t) {
-    const int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
-    for (int l = 0; l < 256; ++l)
-      if (x0 + (l & 15) < W && y0 + (l >> 4) < H) list.push_back((uint32_t)(t * 256 + (size_t)l));
-  }
-  const uint32_t n_in = (uint32_t)list.size();
-  HIP_TRY(hipMemcpyAsync(s->b_dn_list.p, list.data(), (size_t)n_in * 4, hipMemcpyHostToDevice, s->stream));
-  HIP_TRY(hipMemsetAsync(s->b_dn_az.p, 0, n * 16, s->stream));
-  HIP_TRY(hipMemsetAsync(s->b_dn_n.p, 0, n * 16, s->stream));
-  PathState g{};
-  g.npix = (int32_t)n;
-  g.npx = (int32_t)n;
-  g.rpp = 1;
-  g.nslots = 1;
-  g.orgs = s->b_dn_orgs.as<float4>();
-  g.slot = s->b_dn_slot.as<float4>();
-  g.hitp = s->b_dn_hitp.as<float4>();
-  g.write_all_hits = 1u;  // every ray reports point and distance (as jade_trace_rays)
-  g.early_exit = 0u;      // the reference walk: the nearest hit
-  memcpy(g.eye, s->ps.eye, sizeof g.eye);
-  QueueCtl* qc = s->b_dn_ctl.as<QueueCtl>();
-  float4* state = s->b_dn_state.as<float4>();
-  uint32_t* mirrors = s->b_dn_mirrors.as<uint32_t>();
-  const float inv_g = (float)(1.0 / (double)G);
-  for (int smp = 0; smp < G && n_in; ++smp) {
-    HIP_TRY(denoise_guide_camera(s->stream, g, s->rc, s->b_tiles.as<int32_t>(), s->b_dn_list.as<uint32_t>(), n_in, (uint32_t)smp, state, mirrors));
-    QueueCtl q0{};
-    q0.count = n_in;
-    HIP_TRY(hipMemcpyAsync(qc, &q0, sizeof q0, hipMemcpyHostToDevice, s->stream));
-    const uint32_t* queue = s->b_dn_list.as<uint32_t>();
-    uint32_t count = n_in;
-    int cur = 0, qi = 0;
-    for (;;) {
-      hipLaunchKernelGGL(k_trace, dim3((unsigned)s->trace_blocks), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, g, queue, qc + cur,
-                         s->b_spill.as<uint32_t>(), s->b_dn_ctr.as<DevCounters>(), trace_chunk(s, count));
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipMemsetAsync(qc + (cur ^ 1), 0, sizeof(QueueCtl), s->stream));
-      uint32_t* next_queue = s->b_dn_q[qi].as<uint32_t>();
-      HIP_TRY(denoise_guide_hits(s->stream, count, s->dev, g, queue, &qc[cur].count, state, mirrors, s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(),
-                                 smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count));
-      uint32_t next = 0;
-      HIP_TRY(hipMemcpyAsync(&next, &qc[cur ^ 1].count, 4, hipMemcpyDeviceToHost, s->stream));
-      HIP_TRY(hipStreamSynchronize(s->stream));
-      if (next == 0) break;
-      if (next > count) return fail(JADE_ERR_DEVICE, "guide pass: the mirror queue grew");
-      queue = next_queue;
-      count = next;
-      cur ^= 1;
-      qi ^= 1;
-    }
-  }
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return JADE_OK;
-}
-
-// compact tiles (npx entries of `stride` floats, the first `comps` of which are wanted; pixel t*256 + ly*16 + lx) -> the caller's image,
-// other ranks' pixels untouched
-static void dn_scatter(const jade_scene* s, const float* compact, int stride, int comps, float* out) {
-  const int W = s->rp.width, H = s->rp.height, tx = s->rc.tiles_x;
-  for (size_t t = 0; t < s->tile_ids.size(); ++t) {
-    const int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
-    const int ww = std::min(JADE_TILE_SIZE, W - x0), hh = std::min(JADE_TILE_SIZE, H - y0);
-    for (int ly = 0; ly < hh; ++ly)
-      for (int lx = 0; lx < ww; ++lx)
-        for (int k = 0; k < comps; ++k)
-          out[((size_t)(y0 + ly) * W + x0 + lx) * comps + k] = compact[(t * 256 + (size_t)ly * 16 + lx) * stride + k];
-  }
-}
-
-int jade_render_guides(jade_scene* s, int32_t guide_spp, float* out_albedo, float* out_normal, float* out_depth, float* out_variance) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
-  if (guide_spp < 1 || guide_spp > 64) return fail(JADE_ERR_INVALID, "guide_spp must be 1..64");
-  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
-  HIP_TRY(hipSetDevice(s->device));
-  if (int rc = dn_flush(s)) return rc;
-  const size_t npx = (size_t)s->ps.npx;
-  if (npx == 0) return JADE_OK;
-  if (out_variance) {
-    if (int rc = dn_variance(s)) return rc;
-    std::vector<float> v(npx);
-    HIP_TRY(hipMemcpyAsync(v.data(), s->b_dn_var.p, npx * 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    dn_scatter(s, v.data(), 1, 1, out_variance);
-  }
-  if (out_albedo || out_normal || out_depth) {
-    if (int rc = dn_guides(s, guide_spp)) return rc;
-    std::vector<float> az(npx * 4), nn(npx * 4);
-    HIP_TRY(hipMemcpyAsync(az.data(), s->b_dn_az.p, npx * 16, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipMemcpyAsync(nn.data(), s->b_dn_n.p, npx * 16, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    if (out_albedo) dn_scatter(s, az.data(), 4, 3, out_albedo);
-    if (out_normal) dn_scatter(s, nn.data(), 4, 3, out_normal);
-    if (out_depth) dn_scatter(s, az.data() + 3, 4, 1, out_depth);
-  }
-  return JADE_OK;
-}
-
-// The filter on records already packed in b_dn_rec[0] (colour, variance), [2] (normal, depth), [3] (albedo): the passes, then one
-// output kernel into b_dn_rgb / b_dn_bgr (image layout).
-static int dn_filter_out(hipStream_t stream, int W, int H, const jade_denoise_params* dp, int tonemap, float limit, float* dev_rgb,
-                         uint8_t* dev_bgr, float4* const* rec) {
-  int res = 0;
-  HIP_TRY(denoise_filter(stream, W, H, dp->iterations, dp->sigma_luminance, dp->sigma_normal, dp->sigma_depth, dp->sigma_albedo, rec[0], rec[1], rec[2],
-                         rec[3], &res));
-  HIP_TRY(denoise_out(stream, rec[res], W * H, tonemap, limit, dev_rgb, dev_bgr));
-  return JADE_OK;
-}
-
-int jade_render_denoise(jade_scene* s, const jade_denoise_params* dp, int tonemap, float limit, float* out_rgb, uint8_t* out_bgr8) {
-  if (!s || !s->have_rp) return fail(JADE_ERR_INVALID, "jade_render_begin not called");
-  if (int rc = dn_check_params(dp)) return rc;
-  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return fail(JADE_ERR_INVALID, "unknown tone operator");
-  if (s->spp_done <= 0) return fail(JADE_ERR_INVALID, "no samples rendered yet");
-  if (s->rp.tile_nranks > 1)
-    return fail(JADE_ERR_UNSUPPORTED, "jade_render_denoise needs the full frame: gather rgb and jade_render_guides, then jade_denoise_image");
-  for (int32_t n : dn_tile_counts(s))
-    if (!(n >= 2 && (n <= JADE_SAMPLE_LANES || n % JADE_SAMPLE_LANES == 0)))
-      return fail(JADE_ERR_INVALID, "a tile's sample count (" + std::to_string(n) + ") cannot give a variance: n >= 2, and a multiple of " +
-                                        std::to_string(JADE_SAMPLE_LANES) + " above it");
-  HIP_TRY(hipSetDevice(s->device));
-  if (int rc = dn_flush(s)) return rc;
-  const int npx = s->ps.npx;
-  if (npx == 0) return JADE_OK;
-  const int W = s->rp.width, H = s->rp.height;
-  const size_t npix = (size_t)W * (size_t)H;
-  // the mean (k_resolve, compact tiles), the variance, the guides
-  HIP_TRY(dn_alloc(s->b_out_rgb, (size_t)npx * 12));
-  if (int rc = resolve_to(s, JADE_TONEMAP_ACES, 0.0f, s->b_out_rgb.as<float>(), nullptr, s->stream)) return rc;
-  if (int rc = dn_variance(s)) return rc;
-  if (int rc = dn_guides(s, dp->guide_spp)) return rc;
-  // scattered once into the filter's records, image layout
-  for (DevBuf& b : s->b_dn_rec) HIP_TRY(dn_alloc(b, npix * 16));
-  float4* rec[4] = {s->b_dn_rec[0].as<float4>(), s->b_dn_rec[1].as<float4>(), s->b_dn_rec[2].as<float4>(), s->b_dn_rec[3].as<float4>()};
-  HIP_TRY(denoise_pack_tiles(s->stream, s->rc, s->b_tiles.as<int32_t>(), npx, s->b_out_rgb.as<float>(), s->b_dn_var.as<float>(), s->b_dn_az.as<float4>(),
-                             s->b_dn_n.as<float4>(), rec[0], rec[2], rec[3]));
-  if (out_rgb) HIP_TRY(dn_alloc(s->b_dn_rgb, npix * 12));
-  if (out_bgr8) HIP_TRY(dn_alloc(s->b_dn_bgr, npix * 3));
-  if (int rc = dn_filter_out(s->stream, W, H, dp, tonemap, limit, out_rgb ? s->b_dn_rgb.as<float>() : nullptr,
-                             out_bgr8 ? s->b_dn_bgr.as<uint8_t>() : nullptr, rec))
-    return rc;
-  if (out_rgb) HIP_TRY(hipMemcpyAsync(out_rgb, s->b_dn_rgb.p, npix * 12, hipMemcpyDeviceToHost, s->stream));
-  if (out_bgr8) HIP_TRY(hipMemcpyAsync(out_bgr8, s->b_dn_bgr.p, npix * 3, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  return JADE_OK;
-}
-
-int jade_denoise_image(int device_id, int32_t width, int32_t height, const float* rgb, const float* variance, const float* albedo, const float* normal,
-                       const float* depth, const jade_denoise_params* dp, float* out_rgb) {
-  if (!rgb || !variance || !albedo || !normal || !depth || !out_rgb) return fail(JADE_ERR_INVALID, "null argument");
-  if (width <= 0 || height <= 0 || (int64_t)width * height > INT32_MAX / 3) return fail(JADE_ERR_INVALID, "bad image size");
-  if (int rc = dn_check_params(dp)) return rc;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JADE_ERR_DEVICE, "no HIP device");
-  if (device_id < 0 || device_id >= ndev) return fail(JADE_ERR_INVALID, "device_id out of range");
-  HIP_TRY(hipSetDevice(device_id));
-  const size_t npix = (size_t)width * (size_t)height;
-  hipStream_t stream = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-  struct StreamGuard {
-    hipStream_t s;
-    ~StreamGuard() { (void)hipStreamDestroy(s); }
-  } guard{stream};
-  DevBuf b_rgb, b_var, b_alb, b_nrm, b_dep, b_rec[4], b_out;
-  HIP_TRY(upload(b_rgb, rgb, npix * 3, stream));
-  HIP_TRY(upload(b_var, variance, npix, stream));
-  HIP_TRY(upload(b_alb, albedo, npix * 3, stream));
-  HIP_TRY(upload(b_nrm, normal, npix * 3, stream));
-  HIP_TRY(upload(b_dep, depth, npix, stream));
-  for (DevBuf& b : b_rec) HIP_TRY(b.alloc(npix * 16));
-  HIP_TRY(b_out.alloc(npix * 12));
-  float4* rec[4] = {b_rec[0].as<float4>(), b_rec[1].as<float4>(), b_rec[2].as<float4>(), b_rec[3].as<float4>()};
-  HIP_TRY(denoise_pack_image(stream, (int)npix, b_rgb.as<float>(), b_var.as<float>(), b_alb.as<float>(), b_nrm.as<float>(), b_dep.as<float>(), rec[0], rec[2],
-                             rec[3]));
-  if (int rc = dn_filter_out(stream, width, height, dp, JADE_TONEMAP_ACES, 0.0f, b_out.as<float>(), nullptr, rec)) return rc;
-  HIP_TRY(hipMemcpyAsync(out_rgb, b_out.p, npix * 12, hipMemcpyDeviceToHost, stream));
-  HIP_TRY(hipStreamSynchronize(stream));
-  return JADE_OK;
-}
-
 int jade_render(jade_scene* s, const jade_render_params* rp, float* out_rgb, uint8_t* out_bgr8, jade_stats* st) {
-  if (!rp) return fail(JADE_ERR_INVALID, "null argument");
-  if (rp->spp <= 0) return fail(JADE_ERR_INVALID, "spp must be positive");
+  if (!rp) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (rp->spp <= 0) return jade_fail(JADE_ERR_INVALID, "spp must be positive");
   int rc = jade_render_begin(s, rp);
   if (rc) return rc;
   rc = jade_render_step(s, rp->spp, st);
@@ -3793,143 +2877,11 @@ int jade_render(jade_scene* s, const jade_render_params* rp, float* out_rgb, uin
   return jade_render_resolve(s, out_rgb, out_bgr8);
 }
 
-// host twin of k_resolve's tone map + pack (same jade_fpmath.h routines, same flags: same bits)
-static void tonemap_pack_host(const float* m, int tonemap, float limit, uint8_t* bgr) {
-  float v[3] = {m[0], m[1], m[2]};
-  float rein = 1.0f;
-  if (tonemap == JADE_TONEMAP_REINHARD) {
-    float luminance = (float)(0.3 * (double)m[0] + 0.6 * (double)m[1] + 0.1 * (double)m[2]);
-    rein = (float)(1.0 / (1.0 + (double)(luminance / limit)));
-  }
-  for (int k = 0; k < 3; ++k) {
-    float x = v[k];
-    if (tonemap == JADE_TONEMAP_REINHARD) {
-      x = x * rein;
-    } else {
-      float num = x * (x * 2.51f + 0.03f);
-      float den = x * (x * 2.43f + 0.59f) + 0.14f;
-      x = num / den;
-    }
-    x = jade_powf(x, (float)(1.0 / 2.2));
-    x = x * 255.0f;
-    x = x > 255 ? 255 : x;
-    v[k] = x;
-  }
-  for (int k = 0; k < 3; ++k) {
-    float x = v[2 - k];
-    bgr[k] = (x >= 0.0f) ? (uint8_t)x : (uint8_t)0;
-  }
-}
-
-int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_params* rp, float* out_rgb, uint8_t* out_bgr8,
-                      jade_stats* st) {
-  if (!scenes || ndev <= 0 || !rp) return fail(JADE_ERR_INVALID, "null argument");
-  if (rp->spp <= 0 || rp->width <= 0 || rp->height <= 0) return fail(JADE_ERR_INVALID, "bad image size or spp");
-  for (int i = 0; i < ndev; ++i)
-    if (!scenes[i]) return fail(JADE_ERR_INVALID, "null scene");
-  // 1. every device renders its share (one host thread each) and resolves it into a device buffer
-  std::vector<int> rcs(ndev, JADE_OK);
-  std::vector<std::string> msgs(ndev);
-  std::vector<jade_stats> sts(ndev);
-  for (auto& x : sts) memset(&x, 0, sizeof x);
-  auto work = [&](int i) {
-    jade_scene* s = scenes[i];
-    jade_render_params p = *rp;
-    p.tile_rank = i;
-    p.tile_nranks = ndev;
-    p.device_id = s->device;
-    int rc = jade_render_begin(s, &p);
-    if (rc == JADE_OK) rc = jade_render_step(s, p.spp, &sts[i]);
-    if (rc == JADE_OK) rc = jade_render_flush(s, &sts[i]);
-    if (rc == JADE_OK && s->ps.npx > 0) {
-      hipError_t e = s->b_out_rgb.alloc((size_t)s->ps.npx * 12);
-      if (e != hipSuccess) rc = jade_fail(JADE_ERR_NOMEM, "tile buffer allocation failed");
-      if (rc == JADE_OK) rc = resolve_to(s, JADE_TONEMAP_ACES, 0.0f, s->b_out_rgb.as<float>(), nullptr, s->stream);
-      if (rc == JADE_OK && hipStreamSynchronize(s->stream) != hipSuccess) rc = jade_fail(JADE_ERR_DEVICE, "stream sync failed");
-    }
-    rcs[i] = rc;
-    if (rc) msgs[i] = g_err;  // g_err is thread-local: carry the text back to the caller's thread
-  };
-  std::vector<std::thread> th;
-  for (int i = 1; i < ndev; ++i) th.emplace_back(work, i);
-  work(0);
-  for (auto& t : th) t.join();
-  for (int i = 0; i < ndev; ++i)
-    if (rcs[i]) return fail(rcs[i], "device share " + std::to_string(i) + ": " + msgs[i]);
-  // 2. the ONE exchange step: gather the compact tile buffers on the device of scenes[0].  Distinct devices: an RCCL
-  // gather over xGMI (ncclCommInitAll + grouped send/recv, the form ncclGather itself expands to, so
-  // that ranks may contribute different tile counts).  The same device several times (a one-GPU rehearsal of the
-  // partition): RCCL cannot put two ranks on one device, the shares are copied device-to-device instead.
-  jade_scene* s0 = scenes[0];
-  HIP_TRY(hipSetDevice(s0->device));
-  size_t total = 0;
-  std::vector<size_t> off(ndev);
-  for (int i = 0; i < ndev; ++i) {
-    off[i] = total;
-    total += (size_t)scenes[i]->ps.npx * 3;
-  }
-  DevBuf gather;
-  HIP_TRY(gather.alloc(total * 4));
-  bool distinct = true;
-  for (int i = 0; i < ndev; ++i)
-    for (int j = 0; j < i; ++j) distinct = distinct && scenes[i]->device != scenes[j]->device;
-  // JADE_FORCE_RCCL=1 (tests): take the RCCL path for a single share too - library load, communicator, empty group
-  if (distinct && (ndev > 1 || s0->tun.force_rccl)) {
-    if (int rc = rccl_gather(scenes, ndev, gather.as<float>(), off)) return rc;
-  } else {
-    for (int i = 0; i < ndev; ++i) {
-      size_t bytes = (size_t)scenes[i]->ps.npx * 12;
-      if (!bytes) continue;
-      HIP_TRY(hipMemcpyAsync(gather.as<float>() + off[i], scenes[i]->b_out_rgb.p, bytes, hipMemcpyDeviceToDevice, s0->stream));
-    }
-  }
-  std::vector<float> host(total);
-  HIP_TRY(hipMemcpyAsync(host.data(), gather.p, total * 4, hipMemcpyDeviceToHost, s0->stream));
-  HIP_TRY(hipStreamSynchronize(s0->stream));
-  // 3. un-tile into the caller's frame, tone-map once
-  const int W = rp->width, H = rp->height;
-  const int tx = (W + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
-  std::vector<float> frame;
-  float* dst_rgb = out_rgb;
-  if (!dst_rgb) {
-    frame.resize((size_t)W * H * 3);
-    dst_rgb = frame.data();
-  }
-  for (int i = 0; i < ndev; ++i) {
-    const jade_scene* s = scenes[i];
-    for (size_t t = 0; t < s->tile_ids.size(); ++t) {
-      int x0 = (s->tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (s->tile_ids[t] / tx) * JADE_TILE_SIZE;
-      int ww = std::min(JADE_TILE_SIZE, W - x0), hh = std::min(JADE_TILE_SIZE, H - y0);
-      for (int ly = 0; ly < hh; ++ly)
-        memcpy(dst_rgb + ((size_t)(y0 + ly) * W + x0) * 3, host.data() + off[i] + (t * 256 + (size_t)ly * 16) * 3, (size_t)ww * 12);
-    }
-  }
-  if (out_bgr8)
-    for (size_t p = 0; p < (size_t)W * H; ++p) tonemap_pack_host(dst_rgb + 3 * p, JADE_TONEMAP_ACES, 0.0f, out_bgr8 + 3 * p);
-  if (st)
-    for (int i = 0; i < ndev; ++i) {
-      st->rays_primary += sts[i].rays_primary; st->rays_secondary += sts[i].rays_secondary;
-      st->rays_shadow += sts[i].rays_shadow; st->rays_env += sts[i].rays_env; st->rays_indirect += sts[i].rays_indirect;
-      st->rays_mirror += sts[i].rays_mirror; st->rays_refract += sts[i].rays_refract; st->host_syncs += sts[i].host_syncs;
-      st->rays_inline += sts[i].rays_inline;
-      st->nodes_inline += sts[i].nodes_inline; st->tris_inline += sts[i].tris_inline;
-      st->rays_cached += sts[i].rays_cached; st->rays_tail += sts[i].rays_tail; st->nodes_tail += sts[i].nodes_tail; st->tris_tail += sts[i].tris_tail;
-      st->tail_ms = std::max(st->tail_ms, sts[i].tail_ms); st->tail_launches += sts[i].tail_launches;
-      st->light_ms = std::max(st->light_ms, sts[i].light_ms);
-      st->nodes_visited += sts[i].nodes_visited; st->tris_tested += sts[i].tris_tested;
-      st->shaded_hits += sts[i].shaded_hits; st->samples += sts[i].samples;
-      st->kernel_ms = std::max(st->kernel_ms, sts[i].kernel_ms);  // the shares run concurrently
-      st->trace_ms = std::max(st->trace_ms, sts[i].trace_ms);
-      st->trace_launches += sts[i].trace_launches;
-    }
-  return JADE_OK;
-}
-
 // limits (nullable): per ray, the distance below which a recorded hit ends the walk (JADE_WALK_EARLY_EXIT as k_shade asks
 // for it, jade_device.h); null = the reference's walk
 static int trace_rays_impl(jade_scene* s, int32_t n, const float* origins, const float* dirs, const int32_t* skip, const float* limits,
                            int32_t* hit_index, float* hit_dist, float* hit_point, jade_stats* st, bool cached = false) {
-  if (!s || n < 0 || !origins || !dirs || !skip || !hit_index) return fail(JADE_ERR_INVALID, "null argument");
+  if (!s || n < 0 || !origins || !dirs || !skip || !hit_index) return jade_fail(JADE_ERR_INVALID, "null argument");
   if (n == 0) return JADE_OK;
   HIP_TRY(hipSetDevice(s->device));
   // a throw-away PathState with one slot per "pixel"
@@ -3969,8 +2921,7 @@ static int trace_rays_impl(jade_scene* s, int32_t n, const float* origins, const
   HIP_TRY(ev0.create());
   HIP_TRY(ev1.create());
   HIP_TRY(hipEventRecord(ev0.e, s->stream));
-  hipLaunchKernelGGL(trace_wide(s->dev, P) ? k_trace_wide : k_trace, dim3((unsigned)(trace_wide(s->dev, P) ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream, s->dev, P, b_q.as<uint32_t>(),
-                     s->b_ctl.as<QueueCtl>(), b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), trace_chunk(s, (uint32_t)n));
+  launch_trace(s, P, b_q.as<uint32_t>(), s->b_ctl.as<QueueCtl>(), b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), (uint32_t)n);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipEventRecord(ev1.e, s->stream));
   HIP_TRY(hipEventSynchronize(ev1.e));
@@ -4015,19 +2966,20 @@ int jade_trace_rays(jade_scene* s, int32_t n, const float* origins, const float*
 #define JADE_DEBUG_EXPORTS JADE_TRACE_PROFILE
 #endif
 #if JADE_DEBUG_EXPORTS
+extern "C" {
 // Development / tests (not part of jade_rt.h): jade_trace_rays with a limit per ray - k_trace's early exit on its own, outside
 // the integrator.  For a ray whose nearest hit is not nearer than its limit the answer is the reference's; otherwise it is SOME
 // recorded hit nearer than the limit (which one depends on the schedule of the wave).
 int jade_debug_trace_rays_limit(jade_scene* s, int32_t n, const float* origins, const float* dirs, const int32_t* skip, const float* limits,
                                 int32_t* hit_index, float* hit_dist, float* hit_point, jade_stats* st) {
-  if (!limits) return fail(JADE_ERR_INVALID, "null argument");
+  if (!limits) return jade_fail(JADE_ERR_INVALID, "null argument");
   return trace_rays_impl(s, n, origins, dirs, skip, limits, hit_index, hit_dist, hit_point, st);
 }
 // ... and with the occluder cache (JADE_WALK_EARLY_EXIT_CACHED): a ray with a source triangle and a limit that is not a NaN is a
 // yes/no query keyed by that triangle (query kind: "towards emitter 0", or by octant in a scene without emitters)
 int jade_debug_trace_rays_cached(jade_scene* s, int32_t n, const float* origins, const float* dirs, const int32_t* skip, const float* limits,
                                  int32_t* hit_index, float* hit_dist, float* hit_point, jade_stats* st) {
-  if (!limits) return fail(JADE_ERR_INVALID, "null argument");
+  if (!limits) return jade_fail(JADE_ERR_INVALID, "null argument");
   return trace_rays_impl(s, n, origins, dirs, skip, limits, hit_index, hit_dist, hit_point, st, true);
 }
 // whether jade_scene_create found every child's box inside its parent's (1), what the wide walk and the occluder cache rest on; and
@@ -4044,9 +2996,9 @@ __global__ void k_debug_shadow_limit(DevScene S, int n, const float* o, const fl
   if (i < n) out[i] = shadow_limit(&S.tris[tri[i]], jv(o[3 * i], o[3 * i + 1], o[3 * i + 2]), jv(d[3 * i], d[3 * i + 1], d[3 * i + 2]));
 }
 int jade_debug_shadow_limit(jade_scene* s, int32_t n, const float* origins, const float* dirs, const int32_t* tri, float* limit) {
-  if (!s || n <= 0 || !origins || !dirs || !tri || !limit) return fail(JADE_ERR_INVALID, "null argument");
+  if (!s || n <= 0 || !origins || !dirs || !tri || !limit) return jade_fail(JADE_ERR_INVALID, "null argument");
   for (int i = 0; i < n; ++i)
-    if (tri[i] < 0 || tri[i] >= s->dev.n_tris) return fail(JADE_ERR_INVALID, "triangle index out of range");
+    if (tri[i] < 0 || tri[i] >= s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "triangle index out of range");
   HIP_TRY(hipSetDevice(s->device));
   const size_t N = (size_t)n;
   DevBuf bo, bd, bt, bl;
@@ -4066,8 +3018,8 @@ int jade_debug_shadow_limit(jade_scene* s, int32_t n, const float* origins, cons
 // runs), rays taken 64 at a time in the order given.  Like jade_trace_rays, plus per-ray counts of node records and triangle tests.
 int jade_debug_packet_rays(jade_scene* s, int32_t n, const float* origins, const float* dirs, const int32_t* skip, int32_t* hit_index,
                            float* hit_dist, float* hit_point, uint32_t* v_per_ray, uint32_t* t_per_ray, double* kernel_ms /* nullable */) {
-  if (!s || n <= 0 || !origins || !dirs || !skip || !hit_index || !hit_dist || !hit_point || !v_per_ray || !t_per_ray) return fail(JADE_ERR_INVALID, "null argument");
-  if (s->bvh_depth > JADE_PACKET_MAX_DEPTH) return fail(JADE_ERR_UNSUPPORTED, "tree too deep for the packet form");
+  if (!s || n <= 0 || !origins || !dirs || !skip || !hit_index || !hit_dist || !hit_point || !v_per_ray || !t_per_ray) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (s->bvh_depth > JADE_PACKET_MAX_DEPTH) return jade_fail(JADE_ERR_UNSUPPORTED, "tree too deep for the packet form");
   HIP_TRY(hipSetDevice(s->device));
   const size_t N = (size_t)n;
   DevBuf bo, bd, bs, bh, bt, bp, bv, bc;
@@ -4102,7 +3054,7 @@ int jade_debug_packet_rays(jade_scene* s, int32_t n, const float* origins, const
 // the same for k_light_packet's laps and counts (jade_trace.h, PKL_*)
 int jade_debug_packet_profile(unsigned long long* out, int n, int reset) {
 #if JADE_TRACE_PROFILE
-  if (!out || n < PKL_N) return fail(JADE_ERR_INVALID, "need room for PKL_N values");
+  if (!out || n < PKL_N) return jade_fail(JADE_ERR_INVALID, "need room for PKL_N values");
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_packet_prof), sizeof(unsigned long long) * PKL_N));
   if (reset) {
@@ -4112,12 +3064,12 @@ int jade_debug_packet_profile(unsigned long long* out, int n, int reset) {
   return PKL_N;
 #else
   (void)out; (void)n; (void)reset;
-  return -fail(JADE_ERR_UNSUPPORTED, "not a JADE_TRACE_PROFILE build");
+  return -jade_fail(JADE_ERR_UNSUPPORTED, "not a JADE_TRACE_PROFILE build");
 #endif
 }
 int jade_debug_trace_profile(unsigned long long* out, int n, int reset) {
 #if JADE_TRACE_PROFILE
-  if (!out || n < PL_N) return fail(JADE_ERR_INVALID, "need room for PL_N values");
+  if (!out || n < PL_N) return jade_fail(JADE_ERR_INVALID, "need room for PL_N values");
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace_prof), sizeof(unsigned long long) * PL_N));
   if (reset) {
@@ -4127,9 +3079,8 @@ int jade_debug_trace_profile(unsigned long long* out, int n, int reset) {
   return PL_N;
 #else
   (void)out; (void)n; (void)reset;
-  return -fail(JADE_ERR_UNSUPPORTED, "not a JADE_TRACE_PROFILE build");
+  return -jade_fail(JADE_ERR_UNSUPPORTED, "not a JADE_TRACE_PROFILE build");
 #endif
 }
-#endif  // JADE_DEBUG_EXPORTS
-
 }  // extern "C"
+#endif  // JADE_DEBUG_EXPORTS

@@ -1,0 +1,249 @@
+// jade_runtime.h — what more than one .hip file of libjade_hip.so needs on the host side: error reporting, the device buffer and
+// event guards, the development switches, struct jade_scene, and the few internal functions that cross files.  Nothing here is
+// exported: the library's boundary is include/jade_rt.h + jade_bvh.h (tests/test_abi.py).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <string>
+#include <vector>
+
+#include "jade_bvh.h"
+#include "jade_device.h"
+
+#define JADE_HIDDEN __attribute__((visibility("hidden")))
+
+struct alignas(8) QueueCtl {
+  uint32_t count;   // rays emitted by the last shade pass          } one 64-bit word: k_shade reserves its queue
+  uint32_t active;  // records with rays in flight after that pass } and list space with ONE atomic per block
+  uint32_t next;    // next unclaimed queue entry (trace)
+  uint32_t heavy;   // records k_shade_lean handed to k_shade this pass
+  uint32_t fp_bad;  // jade_fp_selftest result (checked once)
+  uint32_t pad[3];
+};
+
+// A step hands its unfinished paths to the next step (or to flush) once fewer than JADE_CARRY_FRACTION of the records it
+// started with are still active.  The paths left are the long ones (jade: ~10 bounces against 1-2 for the sky and the
+// mirror floor): finishing them inside every step means dozens of thin passes per step, whose sparse record accesses
+// waste most of every cache line; carried over, they ride along with the next step's full passes and the thin tail
+// is paid once per render (round 1, C3: 364 -> 286 k_trace launches per 4096 spp, +3 % Mray/s at 0.02 against none).  What
+// is carried is work moved, not saved: the flush at the end of a render finishes it, so the fraction sets how long that
+// flush is - round 3, 4 x 1024 spp of C3 with the flush inside the clock: 0.001 / 0.002 / 0.003 / 0.005 / 0.02 / 0.05 = 708.6 /
+// 707.9 / 705.5 / 705.4 / 709.5 / 698 + 167 ms per step, with a final flush of 32 / 40 / 49 / 67 / 210 / 669 ms.  0.003: as fast as
+// any, and a render's last call returns in 49 ms.  JADE_CARRY_FRACTION in the environment overrides it (0 = only the
+// absolute floor below).
+#ifndef JADE_CARRY_FRACTION
+#define JADE_CARRY_FRACTION 0.003
+#endif
+#ifndef JADE_CARRY_RECORDS
+#define JADE_CARRY_RECORDS 32768u /* ... and in any case once fewer than this (and < 0.1 % of its records) are active */
+#endif
+#define JADE_CTL_RING 96 /* QueueCtl records: entry 0 for passes the host follows one by one, all of them for a batch of passes (round 4: 96 - a 1024-spp step of C3 is ~65 passes down to its carry-over point, the flush ~65 more down to k_tail's threshold: one batch, one wait each; the launches behind the stop are empty) */
+#ifndef JADE_TAIL_MAX
+#define JADE_TAIL_MAX 32768u /* records: a shorter active list is finished by k_tail instead of by further passes */
+#endif
+#ifndef JADE_SORT_GEOMETRY_BYTES
+#define JADE_SORT_GEOMETRY_BYTES ((size_t)16 << 20) /* node + pair records above which the ray queue is ordered by default: four XCD L2s' worth */
+#endif
+#ifndef JADE_PACKET_BUDGET
+#define JADE_PACKET_BUDGET 32 /* C3: k_light 153 / 159 / 167 / 181 ms per step at 16 / 32 / 64 / 128, and the step as a whole fastest at 32 (a lower budget hands more samples to the wavefront passes); C5: 32 / 33 / 36 ms at 16 / 32 / 64 */
+#endif
+
+// sets the calling thread's jade_last_error() text and returns `code` (jade_hip.hip)
+int jade_fail(int code, const std::string& msg);
+#define HIP_TRY(expr)                                                                      \
+  do {                                                                                     \
+    hipError_t e_ = (expr);                                                                \
+    if (e_ != hipSuccess)                                                                  \
+      return jade_fail(e_ == hipErrorOutOfMemory ? JADE_ERR_NOMEM : JADE_ERR_DEVICE,       \
+                       std::string(#expr) + ": " + hipGetErrorString(e_));                 \
+  } while (0)
+
+struct DevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t n) {
+    if (p) { (void)hipFree(p); p = nullptr; }
+    bytes = 0;
+    const hipError_t e = hipMalloc(&p, n ? n : 16);
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+  }
+  template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+struct DevEvent {  // an event that is destroyed on every return path
+  hipEvent_t e = nullptr;
+  ~DevEvent() { if (e) (void)hipEventDestroy(e); }
+  hipError_t create() { return hipEventCreate(&e); }
+  operator hipEvent_t() const { return e; }
+};
+// the scene's events are made on first use and kept
+template <size_t N>
+static hipError_t ensure_events(DevEvent (&ev)[N]) {
+  for (DevEvent& e : ev)
+    if (!e.e)
+      if (const hipError_t r = e.create(); r != hipSuccess) return r;
+  return hipSuccess;
+}
+
+// Copies on `stream` and waits for it: the scene's stream is non-blocking, so a copy on the null stream would
+// not be ordered before the kernels launched on it.
+template <class T>
+static hipError_t upload(DevBuf& b, const T* src, size_t count, hipStream_t stream) {
+  hipError_t e = b.alloc(sizeof(T) * count);
+  if (e != hipSuccess) return e;
+  if (count) {
+    e = hipMemcpyAsync(b.p, src, sizeof(T) * count, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  }
+  return e;
+}
+
+// Development switches, read from the environment ONCE, at jade_scene_create (the product path reads no environment
+// variable per call).  Every one of them changes the schedule only, never a result (tests/test_gpu_parity.py).
+struct Tunables {
+  bool shade_split = true;    // JADE_SHADE_SPLIT=0: k_shade alone over the active list from the first pass on
+  bool fused = true;          // JADE_FUSED=0: the step's first pass as k_shade_lean + k_shade + k_trace instead of k_light
+  bool batching = true;       // JADE_BATCH=0: the host follows every pass
+  bool carry = true;          // JADE_CARRY=0: every step finishes all its paths
+  double carry_frac = JADE_CARRY_FRACTION;
+  bool log_passes = false;    // JADE_LOG_PASSES: one line per pass on stderr (forces one host wait per pass)
+  bool pixel_rotate = false;  // JADE_PIXEL_ROTATE=1
+  int records_per_pixel = 0;  // JADE_RECORDS_PER_PIXEL: test hook, results must not depend on it
+  int trace_blocks_per_cu = 0;  // JADE_TRACE_BLOCKS_PER_CU: occupancy sweeps
+  bool force_rccl = false;    // JADE_FORCE_RCCL=1 (tests): the RCCL path for a single share too
+  bool sort_keys_kernel = false;  // JADE_SORT_KEYS_KERNEL=1: the keys of an ordered queue come from k_ray_keys (a kernel per pass) instead of from the queueing kernel
+  int sort_mode = -1;         // JADE_SORT: order the ray queue by (kind, source triangle, octant) before every k_trace launch (host-followed
+                              // passes): 1 always, 0 never, unset = when the traversal's records do not fit the L2 (jade_scene.sort_rays)
+  uint32_t sort_min = 65536;  // JADE_SORT_MIN: queues shorter than this are traced as they are
+  bool light_packet = true;   // JADE_LIGHT_PACKET=0: the fused first pass walks its rays per lane (k_light) instead of as packets
+  int packet_budget = JADE_PACKET_BUDGET;  // JADE_PACKET_BUDGET: records a packet may read before it is given up and walked per lane
+  int wide_mode = -1;         // JADE_WIDE: with early exits k_trace walks four grandchildren per visit (k_trace_wide): 1 always, 0 never, unset =
+                              // when the traversal's records do not fit the L2 (the rule of sort_mode; jade_scene_create then builds wide records)
+  bool ray_records = true;    // JADE_RAY_RECORDS=0: k_trace's refill gathers every ray through its queue entry (before round 4)
+  bool shade_binned = false;  // JADE_SHADE_BINNED=1: k_shade_binned - the records of a block dealt by branch through LDS (measured level with k_shade: DESIGN.md 3.4)
+  bool tail = true;           // JADE_TAIL=0: no k_tail - the last paths are finished by passes, as before round 4
+  uint32_t tail_max = JADE_TAIL_MAX;  // JADE_TAIL_MAX: active records at or below which k_tail takes over
+  bool anyhit = true;         // JADE_ANYHIT=0: no occluder cache (JADE_WALK_EARLY_EXIT_CACHED then walks as JADE_WALK_EARLY_EXIT)
+  void read() {
+    auto flag0 = [](const char* n) { const char* e = getenv(n); return e && atoi(e) == 0; };
+    anyhit = !flag0("JADE_ANYHIT");
+    tail = !flag0("JADE_TAIL");
+    if (const char* e = getenv("JADE_TAIL_MAX")) tail_max = (uint32_t)atoi(e);
+    auto flag1 = [](const char* n) { const char* e = getenv(n); return e && atoi(e) > 0; };
+    shade_binned = flag1("JADE_SHADE_BINNED");
+    ray_records = !flag0("JADE_RAY_RECORDS");
+    shade_split = !flag0("JADE_SHADE_SPLIT");
+    fused = shade_split && !flag0("JADE_FUSED");
+    batching = !flag0("JADE_BATCH");
+    carry = !flag0("JADE_CARRY");
+    if (const char* e = getenv("JADE_CARRY_FRACTION")) carry_frac = atof(e);
+    log_passes = getenv("JADE_LOG_PASSES") != nullptr;
+    pixel_rotate = flag1("JADE_PIXEL_ROTATE");
+    if (const char* e = getenv("JADE_RECORDS_PER_PIXEL")) records_per_pixel = atoi(e);
+    if (const char* e = getenv("JADE_TRACE_BLOCKS_PER_CU")) trace_blocks_per_cu = atoi(e);
+    force_rccl = getenv("JADE_FORCE_RCCL") != nullptr;
+    light_packet = !flag0("JADE_LIGHT_PACKET");
+    if (const char* e = getenv("JADE_SORT")) sort_mode = atoi(e) > 0 ? 1 : 0;
+    if (const char* e = getenv("JADE_SORT_KEYS_KERNEL")) sort_keys_kernel = atoi(e) > 0;
+    if (const char* e = getenv("JADE_SORT_MIN")) sort_min = (uint32_t)atoi(e);
+    if (const char* e = getenv("JADE_PACKET_BUDGET")) packet_budget = atoi(e);
+    if (const char* e = getenv("JADE_WIDE")) wide_mode = atoi(e) > 0 ? 1 : 0;
+  }
+};
+
+struct jade_scene {
+  int device = 0;
+  Tunables tun;
+  hipStream_t stream = nullptr;
+  DevScene dev{};
+  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias;
+  bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
+  int n_emit = 0;
+  int bvh_depth = 0;
+  bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
+  // render state
+  bool have_rp = false;
+  jade_render_params rp{};
+  RenderConst rc{};
+  PathState ps{};
+  DevBuf b_sortkey, b_sortkey2, b_sortpos, b_sortq, b_sorttmp;  // JADE_SORT: keys in / out, the entries' positions, the ordered queue (of positions), rocPRIM's temporary storage
+  size_t sort_cap = 0, sort_tmp_bytes = 0;
+  double sort_ms = 0;
+  DevBuf b_state, b_sum, b_tiles, b_queue, b_rayq, b_active[2], b_ctl, b_ctr, b_spill, b_out_rgb, b_out_bgr, b_wavecnt;
+  std::vector<int32_t> tile_ids;
+  int trace_blocks = 0;
+  int trace_blocks_wide = 0;  // ... of k_trace_wide (fewer waves per SIMD)
+  int light_blocks = 0;       // persistent grid of k_light
+  int packet_blocks = 0;      // ... and of k_light_packet (0: the tree is too deep for the packet form)
+  double packets_given_up = 0;  // share of the last fused pass's packets that were given up (reset by jade_render_begin)
+  int64_t spp_done = 0;
+  bool tail_pending = false;  // the last step left its longest paths unfinished (jade_render_flush)
+  uint32_t carried_active = 0;  // ... this many records (0: unknown)
+  DevEvent ev[7];             // run_passes' timing events, made once (ev0, ev1, ta, tb, sa, sb, sm)
+  DevEvent ev_resolve;  // jade_render_resolve_tiles_device: caller's stream -> scene stream
+  uint64_t host_syncs = 0;    // host waits inside step/flush since the last advance() reported them
+  double light_ms = 0;        // k_light device time since then
+  DevEvent ev_light[2];
+  DevEvent ev_tail[2];
+  double tail_ms = 0;         // k_tail device time since the last advance() reported it
+  uint64_t tail_launches = 0, tail_records = 0;
+  DevEvent ev_batch[2 * JADE_CTL_RING];  // k_trace timing of a batch of passes
+  // adaptive sampling (jade_render_adaptive, jade_adaptive.hip): samples of each owned tile once the render has ended (empty: every
+  // tile has spp_done), their reciprocals for k_resolve, the rounds' active lists, per-tile counts and {count, not-idle} word
+  std::vector<int32_t> tile_n;
+  bool adaptive_done = false;  // jade_render_step refuses until the next begin
+  DevBuf b_tile_inv, b_tile_n, b_alist[2], b_actl, b_err;
+  DevEvent ev_err[2];
+  // denoiser (jade_denoise.hip), allocated on first use and kept: the guide pass's throw-away PathState (orgs, slot, hitp), per-pixel
+  // state {throughput, depth} and mirror count, the list of owned in-image pixels and two ray queues, its own queue words and work
+  // counters (the render's are not touched), the guide sums {albedo, depth} {normal, 0}, the variance, the filter's records (two
+  // colour buffers, normal + depth, albedo) and the output images
+  DevBuf b_dn_orgs, b_dn_slot, b_dn_hitp, b_dn_state, b_dn_mirrors, b_dn_list, b_dn_q[2], b_dn_ctl, b_dn_ctr, b_dn_az, b_dn_n, b_dn_var;
+  DevBuf b_dn_rec[4], b_dn_rgb, b_dn_bgr;
+  // the work counters of the flush a denoiser entry point made (carried paths finished early): handed to the next step / flush's
+  // statistics, so that a render's counters do not depend on whether it was denoised between its steps
+  jade_stats dn_carried{};
+  ~jade_scene() {
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+
+// What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
+struct ScenePrep {
+  std::vector<float4> nodes, nodes4, tverts, tnorm;  // binary records, wide records (empty: none), pair records, flat normal + material number
+  std::vector<uint32_t> guide;                        // BSSRDF exit-point guide tables ...
+  std::vector<uint2> guide_obj;                       // ... and each object's {first entry, cells}
+  std::vector<DevMaterial> mats;
+  std::vector<uint4> env_alias;
+  int n_internal = 0;
+  size_t n_pairs = 0;
+  bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
+  bool nested = true;          // every child's box lies inside its parent's
+  bool wide_fits = false, cache_fits = false;  // the traversal stack holds a wide walk / a walk that starts with the cached subtrees
+  uint32_t root_ref = 0;
+  size_t geometry_bytes = 0;   // node + pair records
+};
+JADE_HIDDEN int prepare_scene(const jade_scene_desc& d, int depth, const Tunables& tun, ScenePrep* out);
+
+// The two places where host code of one file needs a kernel of another (this tree is not built with -fgpu-rdc), both in jade_hip.hip:
+// the k_trace / k_trace_wide launch - kernel and grid chosen from (scene, P); n_rays sizes the chunks a wave claims, 0 = the kernel
+// sizes them from the queue's length on the device - and k_resolve over the owned pixels.  The caller asks hipGetLastError.
+JADE_HIDDEN void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays);
+JADE_HIDDEN int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream);
+
+// Visits the owned tiles of a W x H image in owned order: f(t, x0, y0, ww, hh) - owned tile t (its pixels are t*256 + ly*16 + lx in
+// the compact layout) covers ww x hh image pixels from (x0, y0).
+template <class F>
+static void for_each_owned_tile(const std::vector<int32_t>& tile_ids, int W, int H, F&& f) {
+  const int tx = (W + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
+  for (size_t t = 0; t < tile_ids.size(); ++t) {
+    const int x0 = (tile_ids[t] % tx) * JADE_TILE_SIZE, y0 = (tile_ids[t] / tx) * JADE_TILE_SIZE;
+    f(t, x0, y0, std::min(JADE_TILE_SIZE, W - x0), std::min(JADE_TILE_SIZE, H - y0));
+  }
+}

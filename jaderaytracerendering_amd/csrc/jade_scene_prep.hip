@@ -1,0 +1,346 @@
+// jade_scene_prep.hip — the host-only half of jade_scene_create: the caller's BVH, triangles and environment map turned into the
+// records the kernels read (jade_device.h, jade_trace.h).  No HIP call is made here; jade_hip.hip uploads what prepare_scene returns.
+#include <cmath>
+#include <cstring>
+#include <map>
+
+#include "jade_runtime.h"
+
+namespace {
+
+// Where the caller's nodes go: internal node -> its record, leaf -> its first pair record.
+struct Layout {
+  const jade_scene_desc* d;
+  std::vector<int32_t> compact;
+  std::vector<uint32_t> pair_first;
+  int n_internal = 0;
+  size_t n_pairs = 0;
+  void number_internal_nodes();
+  void number_pairs();
+  uint32_t ref_of(int child) const {
+    if (child <= 0) return JADE_REF_NONE;
+    const jade_bvh_node& c = d->nodes[child];
+    if (c.n > 0) return JADE_REF_LEAF | ((pair_first[child] * 5u) << 4) | (uint32_t)((c.n + 1) / 2);  // bits 4-30: byte offset / 16 of the first pair record
+    return (uint32_t)compact[child];
+  }
+};
+
+// Re-lay the BVH: compact the internal nodes, children's boxes in the parent.  Internal nodes are numbered by
+// decreasing surface area of their own box (the SAH's measure of how often a node is visited), so that any prefix
+// [0, k) of the array is a connected top of the tree - a child's box is never larger than its parent's, ties keep
+// the breadth-first order - and k_trace can keep that prefix in LDS (jade_device.h, JADE_LDS_TOP_NODES).
+void Layout::number_internal_nodes() {
+  const int nN = d->n_nodes;
+  compact.assign(nN, -1);
+  std::vector<int32_t> bfs;  // internal nodes reachable from the root, breadth first
+  bfs.reserve(nN);
+  if (d->nodes[1].n <= 0) bfs.push_back(1);
+  for (size_t h = 0; h < bfs.size(); ++h) {
+    const jade_bvh_node& nd = d->nodes[bfs[h]];
+    if (nd.left > 0 && d->nodes[nd.left].n <= 0) bfs.push_back(nd.left);
+    if (nd.right > 0 && d->nodes[nd.right].n <= 0) bfs.push_back(nd.right);
+  }
+  auto area = [&](int i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    const double x = (double)nd.bb[0] - nd.aa[0], y = (double)nd.bb[1] - nd.aa[1], z = (double)nd.bb[2] - nd.aa[2];
+    return x * y + y * z + z * x;
+  };
+  std::vector<double> ar(bfs.size());
+  for (size_t h = 0; h < bfs.size(); ++h) ar[h] = area(bfs[h]);
+  // a child inherits at most its parent's key, so a prefix of the order is always closed under "parent of"
+  std::vector<double> key(nN, 0.0);
+  for (size_t h = 0; h < bfs.size(); ++h) {
+    const int i = bfs[h];
+    if (h == 0) key[i] = ar[0];
+    const jade_bvh_node& nd = d->nodes[i];
+    for (int ch : {nd.left, nd.right})
+      if (ch > 0 && d->nodes[ch].n <= 0) key[ch] = std::min(key[i], area(ch));
+  }
+  std::vector<int32_t> order(bfs.size());
+  for (size_t h = 0; h < bfs.size(); ++h) order[h] = (int32_t)h;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[bfs[a]] > key[bfs[b]]; });
+  for (int32_t h : order) compact[bfs[h]] = n_internal++;
+  // internal nodes the root does not reach (none in a valid tree) keep a slot so that every record exists
+  for (int i = 1; i < nN; ++i)
+    if (d->nodes[i].n <= 0 && compact[i] < 0) compact[i] = n_internal++;
+}
+
+// vertex records hold two consecutive triangles of a leaf each (jade_trace.h): number the pairs leaf by leaf
+void Layout::number_pairs() {
+  const int nN = d->n_nodes;
+  pair_first.assign(nN, 0);
+  std::vector<int> leaves;
+  for (int i = 1; i < nN; ++i)
+    if (d->nodes[i].n > 0) leaves.push_back(i);
+  std::sort(leaves.begin(), leaves.end(), [&](int a, int b) { return d->nodes[a].index < d->nodes[b].index; });
+  for (int i : leaves) {
+    pair_first[i] = (uint32_t)n_pairs;
+    n_pairs += (size_t)(d->nodes[i].n + 1) / 2;
+  }
+}
+
+// the binary records: an internal node holds its children's boxes and references
+void binary_records(const jade_scene_desc* d, const Layout& lay, std::vector<float4>& nodes, bool* missing_child_out) {
+  const int nN = d->n_nodes;
+  nodes.assign((size_t)4 * std::max(lay.n_internal, 1), float4{});
+  bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
+  for (int i = 1; i < nN; ++i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    if (nd.n > 0) continue;
+    if (nd.left <= 0 || nd.right <= 0) missing_child = true;
+    float la[3] = {0, 0, 0}, lb[3] = {0, 0, 0}, ra[3] = {0, 0, 0}, rb[3] = {0, 0, 0};
+    if (nd.left > 0) { memcpy(la, d->nodes[nd.left].aa, 12); memcpy(lb, d->nodes[nd.left].bb, 12); }
+    if (nd.right > 0) { memcpy(ra, d->nodes[nd.right].aa, 12); memcpy(rb, d->nodes[nd.right].bb, 12); }
+    float4* o = &nodes[(size_t)4 * lay.compact[i]];
+    o[0] = make_float4(la[0], ra[0], la[1], ra[1]);
+    o[1] = make_float4(la[2], ra[2], lb[0], rb[0]);
+    o[2] = make_float4(lb[1], rb[1], lb[2], rb[2]);
+    uint32_t refs[4] = {lay.ref_of(nd.left), lay.ref_of(nd.right), 0u, 0u};
+    memcpy(&o[3], refs, 16);
+  }
+  *missing_child_out = missing_child;
+}
+
+// The wide walk and the occluder cache both rest on "a ray that meets a node's box meets every ancestor's" (jade_trace.h), which
+// holds when every child's box lies inside its parent's, bound by bound, with no NaN - true of any tree built by min / max over
+// the triangles (this repo's builders, the reference's), but the caller's array is the caller's: a tree with padded,
+// refitted or NaN boxes is walked with binary units from the root only, which needs no such property.
+bool boxes_nested(const jade_scene_desc* d) {
+  const int nN = d->n_nodes;
+  bool nested = true;
+  for (int i = 1; i < nN && nested; ++i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    if (nd.n > 0) continue;
+    for (int ch : {nd.left, nd.right}) {
+      if (ch <= 0) continue;
+      const jade_bvh_node& c = d->nodes[ch];
+      for (int a = 0; a < 3; ++a)
+        if (!(c.aa[a] >= nd.aa[a] && c.bb[a] <= nd.bb[a] && c.aa[a] <= c.bb[a])) nested = false;  // (a NaN fails every comparison)
+    }
+  }
+  return nested;
+}
+
+// the four-wide records (jade_device.h): node i's record holds its grandchildren - each child's own record, or the child twice
+// if it is a leaf
+void wide_records(const jade_scene_desc* d, const Layout& lay, const std::vector<float4>& nodes, std::vector<float4>& nodes4) {
+  const int nN = d->n_nodes;
+  nodes4.assign((size_t)8 * lay.n_internal, make_float4(0, 0, 0, 0));
+  for (int i = 1; i < nN; ++i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    if (nd.n > 0 || lay.compact[i] < 0) continue;
+    float4* o = &nodes4[(size_t)8 * lay.compact[i]];
+    uint32_t refs[4];
+    const int ch[2] = {nd.left, nd.right};
+    for (int h = 0; h < 2; ++h) {
+      const jade_bvh_node& c = d->nodes[ch[h]];
+      if (c.n > 0) {  // a leaf: its own box in both lanes of the half, one reference
+        o[3 * h + 0] = make_float4(c.aa[0], c.aa[0], c.aa[1], c.aa[1]);
+        o[3 * h + 1] = make_float4(c.aa[2], c.aa[2], c.bb[0], c.bb[0]);
+        o[3 * h + 2] = make_float4(c.bb[1], c.bb[1], c.bb[2], c.bb[2]);
+        refs[2 * h] = lay.ref_of(ch[h]);
+        refs[2 * h + 1] = JADE_REF_NONE;
+      } else {
+        const float4* src = &nodes[(size_t)4 * lay.compact[ch[h]]];
+        o[3 * h + 0] = src[0];
+        o[3 * h + 1] = src[1];
+        o[3 * h + 2] = src[2];
+        refs[2 * h] = lay.ref_of(c.left);
+        refs[2 * h + 1] = lay.ref_of(c.right);
+      }
+    }
+    memcpy(&o[6], refs, 16);
+  }
+}
+
+// the pair records: two consecutive triangles of a leaf each, vertices interleaved (jade_trace.h)
+void pair_records(const jade_scene_desc* d, const Layout& lay, std::vector<float4>& tverts) {
+  const int nN = d->n_nodes;
+  tverts.assign((size_t)5 * std::max<size_t>(lay.n_pairs, 1), float4{});
+  std::vector<int32_t> leaf_parent(nN, 0);
+  for (int i = 1; i < nN; ++i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    if (nd.n > 0) continue;
+    if (nd.left > 0 && d->nodes[nd.left].n > 0) leaf_parent[nd.left] = i;
+    if (nd.right > 0 && d->nodes[nd.right].n > 0) leaf_parent[nd.right] = i;
+  }
+  for (int i = 1; i < nN; ++i) {
+    const jade_bvh_node& nd = d->nodes[i];
+    for (int k = 0; k < nd.n; k += 2) {
+      const bool has_b = k + 1 < nd.n;
+      const jade_triangle& a = d->triangles[nd.index + k];
+      const jade_triangle& b = d->triangles[nd.index + k + (has_b ? 1 : 0)];  // an odd leaf's last record repeats A
+      float4* o = &tverts[5 * ((size_t)lay.pair_first[i] + (size_t)k / 2)];
+      o[0] = make_float4(a.p1[0], b.p1[0], a.p1[1], b.p1[1]);
+      o[1] = make_float4(a.p1[2], b.p1[2], a.p2[0], b.p2[0]);
+      o[2] = make_float4(a.p2[1], b.p2[1], a.p2[2], b.p2[2]);
+      o[3] = make_float4(a.p3[0], b.p3[0], a.p3[1], b.p3[1]);
+      // flag word: bit 0 = B is a triangle; bits 1-31 = the leaf's parent + 1 (occluder cache, jade_trace.h; 0 = the root or none: a
+      // walk "from the root" is the whole walk, nothing to cache)
+      const int par = leaf_parent[i];
+      const uint32_t parent1 = (par > 1 && lay.compact[par] > 0) ? (uint32_t)lay.compact[par] + 1u : 0u;
+      const uint32_t tag[2] = {(uint32_t)(nd.index + k), (has_b ? 1u : 0u) | (parent1 << 1)};
+      float tagf[2];
+      memcpy(tagf, tag, 8);
+      o[4] = make_float4(a.p3[2], b.p3[2], tagf[0], tagf[1]);
+    }
+  }
+}
+
+// Guide tables for the BSSRDF exit-point search (jade_shade.h, begin_bounce; PathTrace.cu:1031-1048).  Per object with
+// finite, non-decreasing prefix areas: Gn = the power of two >= 4 x its triangles cells, guide[c] = the first triangle i with
+// fl(c / Gn * A) <= prefix[i] - the product rounded once to fp32, as the kernel's `u * A` is (this file is built
+// -ffp-contract=off like the device code) - for c = 0 .. Gn, and one more entry so that cell Gn (u == 1) has an upper bound.
+// An object whose prefix areas are not monotone or not finite gets Gn = 0: the kernel then bisects as the reference does.
+void guide_tables(const jade_scene_desc* d, std::vector<uint32_t>& guide, std::vector<uint2>& guide_obj) {
+  guide_obj.assign((size_t)d->n_objects, make_uint2(0u, 0u));
+  for (int o = 0; o < d->n_objects; ++o) {
+    const int b = d->obj_segs[o].begin_idx, e = d->obj_segs[o].end_idx;
+    bool ok = true;
+    for (int i = b; i <= e && ok; ++i) {
+      const float v = d->prefix_area[i];
+      ok = v == v && v >= 0.0f && v < 3.0e38f && (i == b || v >= d->prefix_area[i - 1]);
+    }
+    const size_t nt = (size_t)(e - b + 1);
+    if (!ok || nt < 2 || nt > ((size_t)1 << 21)) continue;
+    uint32_t gn = 1;
+    while (gn < 4 * nt) gn <<= 1;
+    const float A = d->prefix_area[e];
+    const size_t first = guide.size();
+    guide.resize(first + gn + 2);
+    int i = b;
+    for (uint32_t c = 0; c <= gn; ++c) {
+      const float u = (float)c / (float)gn;  // exact: both are powers of two apart
+      volatile float x = u * A;              // one rounding (volatile: no excess precision, whatever the host compiler does)
+      const float xv = x;
+      while (i < e && !(xv <= d->prefix_area[i])) ++i;
+      guide[first + c] = (uint32_t)i;
+    }
+    guide[first + gn + 1] = guide[first + gn];
+    guide_obj[(size_t)o] = make_uint2((uint32_t)first, gn);
+  }
+  if (guide.empty()) guide.push_back(0u);
+}
+
+// What shading reads of a triangle (jade_device.h, DevMaterial): the distinct {object, material} tuples of the caller's
+// records - the reference copies an object's material into each of its triangles, PathTrace.cu:451 - and per triangle
+// the flat normal + the number of its tuple.  Same bytes, read from 16 B + a cached table instead of a 112-B record.
+void materials(const jade_scene_desc* d, std::vector<DevMaterial>& mats, std::vector<float4>& tnorm) {
+  tnorm.assign((size_t)d->n_triangles, float4{});
+  std::map<std::string, uint32_t> seen;  // key: the 64 bytes of the tuple
+  std::string last_key;
+  uint32_t last_id = 0;
+  for (int i = 0; i < d->n_triangles; ++i) {
+    const jade_triangle& t = d->triangles[i];
+    DevMaterial m;
+    memcpy(m.emissive, t.emissive, 12);
+    memcpy(m.brdf, t.brdf, 12);
+    m.reflex_mode = t.reflex_mode;
+    m.refract_mode = t.refract_mode;
+    memcpy(m.refract_rate, t.refract_rate, 12);
+    memcpy(m.refract_albedo, t.refract_albedo, 12);
+    m.refract_index = t.refract_index;
+    m.obj_idx = t.obj_idx;
+    std::string key(reinterpret_cast<const char*>(&m), sizeof m);
+    uint32_t id;
+    if (i > 0 && key == last_key) {
+      id = last_id;
+    } else {
+      auto it = seen.find(key);
+      if (it == seen.end()) {
+        id = (uint32_t)mats.size();
+        mats.push_back(m);
+        seen.emplace(key, id);
+      } else {
+        id = it->second;
+      }
+      last_key = std::move(key);
+      last_id = id;
+    }
+    float idf;
+    memcpy(&idf, &id, 4);
+    tnorm[(size_t)i] = make_float4(t.norm[0], t.norm[1], t.norm[2], idf);
+  }
+}
+
+// Environment importance sampling (jade_render_params.env_sampling; non-parity): Vose's alias table over the texels, weight =
+// (luminance + 1 % of the mean luminance) x sin(theta of the row's centre) - the floor keeps every texel drawable, so the
+// estimator stays unbiased wherever the sky is not black
+void env_alias_table(const jade_scene_desc* d, std::vector<uint4>& env_alias) {
+  const size_t W = (size_t)d->env_width, H = (size_t)d->env_height, N = W * H;
+  std::vector<double> wgt(N);
+  double lum_sum = 0;
+  for (size_t i = 0; i < N; ++i) {
+    const float* t = d->env_rgb + 3 * i;
+    const double l = 0.2126 * std::max(t[0], 0.0f) + 0.7152 * std::max(t[1], 0.0f) + 0.0722 * std::max(t[2], 0.0f);
+    wgt[i] = std::isfinite(l) ? l : 0.0;
+    lum_sum += wgt[i];
+  }
+  const double floor_l = lum_sum > 0 ? 0.01 * lum_sum / (double)N : 1.0;
+  double total = 0;
+  for (size_t j = 0; j < H; ++j) {
+    const double st = std::sin(JADE_PI_D * ((double)j + 0.5) / (double)H);
+    for (size_t i = 0; i < W; ++i) {
+      wgt[j * W + i] = (wgt[j * W + i] + floor_l) * st;
+      total += wgt[j * W + i];
+    }
+  }
+  std::vector<double> q(N);
+  std::vector<uint32_t> small, large, alias(N);
+  std::vector<float> accept(N, 1.0f);
+  for (size_t i = 0; i < N; ++i) {
+    q[i] = wgt[i] / total * (double)N;  // the texel's probability x N (mean 1)
+    alias[i] = (uint32_t)i;
+    (q[i] < 1.0 ? small : large).push_back((uint32_t)i);
+  }
+  std::vector<double> r = q;
+  while (!small.empty() && !large.empty()) {
+    const uint32_t a = small.back(), g = large.back();
+    small.pop_back();
+    accept[a] = (float)r[a];
+    alias[a] = g;
+    r[g] = (r[g] + r[a]) - 1.0;
+    if (r[g] < 1.0) { large.pop_back(); small.push_back(g); }
+  }
+  env_alias.resize(N);
+  for (size_t i = 0; i < N; ++i) {
+    const float ps = (float)q[i], pa = (float)q[alias[i]];
+    uint4 e;
+    memcpy(&e.x, &accept[i], 4);
+    e.y = alias[i];
+    memcpy(&e.z, &ps, 4);
+    memcpy(&e.w, &pa, 4);
+    env_alias[i] = e;
+  }
+}
+
+}  // namespace
+
+int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, ScenePrep* out) {
+  const jade_scene_desc* d = &desc;
+  Layout lay{d};
+  lay.number_internal_nodes();
+  lay.number_pairs();
+  if (lay.n_pairs * 5 >= ((size_t)1 << 27)) return jade_fail(JADE_ERR_UNSUPPORTED, "too many triangle pairs for the 27-bit leaf cursor");
+  out->n_internal = lay.n_internal;
+  out->n_pairs = lay.n_pairs;
+  out->root_ref = lay.ref_of(1);
+  binary_records(d, lay, out->nodes, &out->missing_child);
+  pair_records(d, lay, out->tverts);
+  out->geometry_bytes = out->nodes.size() * sizeof(float4) + out->tverts.size() * sizeof(float4);
+  out->nested = boxes_nested(d);
+  // stack levels a walk may need (validate_desc bounds the binary walk's: depth <= capacity - 1): a wide unit pushes up to three
+  // entries for every two levels it descends; a walk that starts with the cached subtrees has three more under it
+  out->wide_fits = 3 * ((depth + 1) / 2) + 1 + 3 <= JADE_BVH_STACK_CAPACITY;
+  out->cache_fits = depth + 3 <= JADE_BVH_STACK_CAPACITY - 1;
+  // The wide records are built where the wide walk pays: measured with early exits, same process, k_trace per step: C5 (55 MB of node +
+  // pair records, bound by dependent 64-B sector misses) 180.0 -> 166.6 ms; C3 (3.8 MB, L2-resident: a unit's own instructions count, and a wide unit
+  // has more of them) 106.7 -> 110.2 ms, close-up 723 -> 755.  So: the rule of the ordered ray queue (JADE_SORT_GEOMETRY_BYTES);
+  // JADE_WIDE=0 / 1 overrides it.
+  const bool want_wide = tun.wide_mode < 0 ? out->geometry_bytes > JADE_SORT_GEOMETRY_BYTES : tun.wide_mode > 0;
+  if (JADE_WIDE_WALK && want_wide && !out->missing_child && lay.n_internal > 0 && out->nested && out->wide_fits) wide_records(d, lay, out->nodes, out->nodes4);
+  guide_tables(d, out->guide, out->guide_obj);
+  materials(d, out->mats, out->tnorm);
+  env_alias_table(d, out->env_alias);
+  return JADE_OK;
+}
