@@ -41,7 +41,8 @@ $(LIBDIR)/libjade_hip_stack4.so: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) -DJADE_LDS_STACK=4 $(HIPFLAGS) -shared -o $@ $(HIP_SRC) -ldl
 
-# test-only build: the jade_debug_* entry points (raw rays with a limit, packets, shadow limits) that the piece-by-piece
+# test-only build: the jade_debug_* entry points (raw rays with a limit, packets, shadow limits; jade_fpmath.h's routines, the sky
+# lookup and the tone curve one element at a time, jade_debug_units.hip) that the piece-by-piece
 # GPU tests call; libjade_hip.so exports exactly what include/jade_rt.h + jade_bvh.h declare
 $(LIBDIR)/libjade_hip_debug.so: $(HIP_SRC) $(HIP_HDR)
 	@mkdir -p $(LIBDIR)

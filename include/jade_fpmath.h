@@ -311,7 +311,12 @@ JADE_HD float jade_atanf(float t) {
   return (jade_f2u(t) >> 31) ? -y : y;
 }
 
-/* atan2f(y, x), result in [-pi, pi]. */
+/* atan2f(y, x), result in [-pi, pi].  y = +-0 with x < 0 gives +-pi as atan2f does: the seam of the
+ * environment map (a direction on the -x axis with z = -0 reads column 0, PathTrace.cu:687).  The other
+ * signed-zero / infinity cases are simplified and kept: atan2(-0, x > 0) = +0 (u is the same), atan2(inf, inf) = NaN (an
+ * infinite direction normalises to NaN first), and atan2(+-0, -0) = 0 where atan2f gives +-pi.  That last one IS reached, by
+ * a direction exactly at a pole with x = -0, (-0, +-1, +-0): it reads the middle of the pole row where the reference reads
+ * its end.  Measure zero; DESIGN.md section 2, item 4. */
 JADE_HD float jade_atan2f(float y, float x) {
   const float pi = 3.14159265358979323846f;
   const float pio2 = 1.57079632679489661923f;
@@ -321,9 +326,9 @@ JADE_HD float jade_atan2f(float y, float x) {
     if (y == 0.0f) return 0.0f;
     return (y > 0.0f) ? pio2 : -pio2;
   }
-  if (y == 0.0f) return (x > 0.0f) ? 0.0f : pi;
+  /* x < 0: pi with the sign BIT of y, so that y = +-0 lands on +-pi (atan(-+0) = -+0 adds nothing); x > 0, y = +-0: 0 + (+-0) = +0 */
   if (x > 0.0f) w = 0.0f;
-  else w = (y > 0.0f) ? pi : -pi;
+  else w = jade_u2f(jade_f2u(pi) | (jade_f2u(y) & 0x80000000u));
   return w + jade_atanf(y / x);
 }
 

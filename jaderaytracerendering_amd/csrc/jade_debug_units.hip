@@ -1,0 +1,218 @@
+// jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
+// include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h) and the tone curve (tone_pack_bgr8, jade_device.h).
+// NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
+// (tests/test_gpu_fpmath.py, tests/test_gpu_env_lookup.py, tests/test_gpu_tone.py, tests/test_tone_spec.py).  Each kernel is elementwise: element i reads
+// row i of its inputs and writes row i of its outputs, nothing else.
+#include "jade_runtime.h"
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // jade_shade.h's non-inline statics this file does not call
+#include "jade_shade.h"
+#pragma clang diagnostic pop
+
+#if JADE_DEBUG_EXPORTS
+
+// One code per routine of jade_fpmath.h (tests/test_gpu_fpmath.py mirrors this list).  Every array element is 4 bytes wide; the
+// comment gives the elements per row of a, b, c -> out0, out1 ("-" = not read / not written, may be null).
+enum DebugFpOp {
+  FP_FLOOR = 0,      // a 1 -> 1
+  FP_SINCOS = 1,     // a 1 -> sin 1, cos 1
+  FP_LOG2 = 2,       // a 1 -> 1
+  FP_EXP2 = 3,       // a 1 -> 1
+  FP_POW = 4,        // a 1, b 1 -> 1
+  FP_ATAN = 5,       // a 1 -> 1
+  FP_ATAN2 = 6,      // a 1 (y), b 1 (x) -> 1
+  FP_ASIN = 7,       // a 1 -> 1
+  FP_FMIN = 8,       // a 1, b 1 -> 1
+  FP_FMAX = 9,       // a 1, b 1 -> 1
+  FP_SQRT = 10,      // a 1 -> 1
+  FP_DIV = 11,       // a 1, b 1 -> a / b
+  FP_RCP = 12,       // a 1 -> 1.0f / a
+  FP_DOT = 13,       // a 3, b 3 -> 1
+  FP_CROSS = 14,     // a 3, b 3 -> 3
+  FP_MIXED = 15,     // a 3, b 3, c 3 -> 1
+  FP_LEN = 16,       // a 3 -> 1
+  FP_NORMALIZE = 17, // a 3 -> 3
+  FP_TRANSFORM = 18, // a 3 (v), b 1 (f4), c: ONE matrix of 16 floats for all rows -> 3
+  FP_VDIV = 19,      // a 3, b 3 -> 3 (jv_div)
+  FP_VDIVS = 20,     // a 3, b 1 -> 3 (jv_divs)
+  FP_RNG_SEED = 21,  // a, b, c: uint32 px, py, frame -> uint32 seed
+  FP_RAND = 22,      // a: uint32 state, b: ONE int32 k for all rows -> out0 k floats (k successive jade_rand), out1 k uint32 (the state after each)
+  FP_SELFTEST = 23,  // a 1 (`one`) -> int32 jade_fp_selftest(one)
+  FP_N_OPS
+};
+
+struct DebugFpShape { int a, b, c, o0, o1; bool b_once, c_once; };
+static const DebugFpShape kFpShape[] = {  // one row per DebugFpOp, in its order
+    {1, 0, 0, 1, 0, false, false},  // FP_FLOOR
+    {1, 0, 0, 1, 1, false, false},  // FP_SINCOS
+    {1, 0, 0, 1, 0, false, false},  // FP_LOG2
+    {1, 0, 0, 1, 0, false, false},  // FP_EXP2
+    {1, 1, 0, 1, 0, false, false},  // FP_POW
+    {1, 0, 0, 1, 0, false, false},  // FP_ATAN
+    {1, 1, 0, 1, 0, false, false},  // FP_ATAN2
+    {1, 0, 0, 1, 0, false, false},  // FP_ASIN
+    {1, 1, 0, 1, 0, false, false},  // FP_FMIN
+    {1, 1, 0, 1, 0, false, false},  // FP_FMAX
+    {1, 0, 0, 1, 0, false, false},  // FP_SQRT
+    {1, 1, 0, 1, 0, false, false},  // FP_DIV
+    {1, 0, 0, 1, 0, false, false},  // FP_RCP
+    {3, 3, 0, 1, 0, false, false},  // FP_DOT
+    {3, 3, 0, 3, 0, false, false},  // FP_CROSS
+    {3, 3, 3, 1, 0, false, false},  // FP_MIXED
+    {3, 0, 0, 1, 0, false, false},  // FP_LEN
+    {3, 0, 0, 3, 0, false, false},  // FP_NORMALIZE
+    {3, 1, 16, 3, 0, false, true},  // FP_TRANSFORM
+    {3, 3, 0, 3, 0, false, false},  // FP_VDIV
+    {3, 1, 0, 3, 0, false, false},  // FP_VDIVS
+    {1, 1, 1, 1, 0, false, false},  // FP_RNG_SEED
+    {1, 1, 0, 1, 1, true, false},   // FP_RAND
+    {1, 0, 0, 1, 0, false, false},  // FP_SELFTEST
+};
+static_assert(sizeof kFpShape / sizeof kFpShape[0] == FP_N_OPS, "kFpShape needs one row per DebugFpOp");
+
+static __device__ __forceinline__ void put3(float* o, int i, jvec3 v) {
+  o[3 * i] = v.x;
+  o[3 * i + 1] = v.y;
+  o[3 * i + 2] = v.z;
+}
+
+__global__ void k_debug_fpmath(int op, int n, int k, const float* a, const float* b, const float* c, float* o0, float* o1) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* ua = reinterpret_cast<const uint32_t*>(a);
+  const uint32_t* ub = reinterpret_cast<const uint32_t*>(b);
+  const uint32_t* uc = reinterpret_cast<const uint32_t*>(c);
+  switch (op) {
+    case FP_FLOOR: o0[i] = jade_floorf(a[i]); break;
+    case FP_SINCOS: {
+      float s, cs;
+      jade_sincosf(a[i], &s, &cs);
+      o0[i] = s;
+      o1[i] = cs;
+      break;
+    }
+    case FP_LOG2: o0[i] = jade_log2f(a[i]); break;
+    case FP_EXP2: o0[i] = jade_exp2f(a[i]); break;
+    case FP_POW: o0[i] = jade_powf(a[i], b[i]); break;
+    case FP_ATAN: o0[i] = jade_atanf(a[i]); break;
+    case FP_ATAN2: o0[i] = jade_atan2f(a[i], b[i]); break;
+    case FP_ASIN: o0[i] = jade_asinf(a[i]); break;
+    case FP_FMIN: o0[i] = jade_fminf(a[i], b[i]); break;
+    case FP_FMAX: o0[i] = jade_fmaxf(a[i], b[i]); break;
+    case FP_SQRT: o0[i] = jade_sqrt(a[i]); break;
+    case FP_DIV: o0[i] = a[i] / b[i]; break;
+    case FP_RCP: o0[i] = 1.0f / a[i]; break;
+    case FP_DOT: o0[i] = jv_dot(V3(a + 3 * i), V3(b + 3 * i)); break;
+    case FP_CROSS: put3(o0, i, jv_cross(V3(a + 3 * i), V3(b + 3 * i))); break;
+    case FP_MIXED: o0[i] = jv_mixed(V3(a + 3 * i), V3(b + 3 * i), V3(c + 3 * i)); break;
+    case FP_LEN: o0[i] = jv_len(V3(a + 3 * i)); break;
+    case FP_NORMALIZE: put3(o0, i, jv_normalize(V3(a + 3 * i))); break;
+    case FP_TRANSFORM: put3(o0, i, jade_transform(V3(a + 3 * i), b[i], c)); break;
+    case FP_VDIV: put3(o0, i, jv_div(V3(a + 3 * i), V3(b + 3 * i))); break;
+    case FP_VDIVS: put3(o0, i, jv_divs(V3(a + 3 * i), b[i])); break;
+    case FP_RNG_SEED: reinterpret_cast<uint32_t*>(o0)[i] = jade_rng_seed(ua[i], ub[i], uc[i]); break;
+    case FP_RAND: {
+      uint32_t s = ua[i];
+      for (int j = 0; j < k; ++j) {
+        o0[(size_t)i * k + j] = jade_rand(&s);
+        reinterpret_cast<uint32_t*>(o1)[(size_t)i * k + j] = s;
+      }
+      break;
+    }
+    case FP_SELFTEST: reinterpret_cast<int32_t*>(o0)[i] = jade_fp_selftest(a[i]); break;
+    default: break;
+  }
+}
+
+__global__ void k_debug_sample_hdr(DevScene S, int n, const float* d, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) put3(out, i, sample_hdr(S, V3(d + 3 * i)));
+}
+
+__global__ void k_debug_tone_pack(int n, const float* rgb, int tonemap, float limit, uint8_t* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) tone_pack_bgr8(V3(rgb + 3 * i), tonemap, limit, true, out + 3 * (size_t)i);
+}
+
+static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
+
+static hipError_t upload0(DevBuf& b, const void* src, size_t elems) {  // on the null stream: these entry points have no scene
+  hipError_t e = b.alloc(4 * elems);
+  if (e == hipSuccess && elems) e = hipMemcpy(b.p, src, 4 * elems, hipMemcpyHostToDevice);
+  return e;
+}
+
+extern "C" {
+// out0 / out1 of routine `op` of jade_fpmath.h on n rows of a, b, c (host arrays; shapes: DebugFpOp).
+int jade_debug_fpmath(int device_id, int op, int32_t n, const void* a, const void* b, const void* c, void* out0, void* out1) {
+  if (op < 0 || op >= FP_N_OPS) return jade_fail(JADE_ERR_INVALID, "unknown op");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  const DebugFpShape& sh = kFpShape[op];
+  if (!a || (sh.b && !b) || (sh.c && !c) || !out0 || (sh.o1 && !out1)) return jade_fail(JADE_ERR_INVALID, "null argument");
+  int k = 1;
+  if (op == FP_RAND) {
+    k = *static_cast<const int32_t*>(b);
+    if (k <= 0 || (int64_t)k * n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "draw count out of range");
+  }
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf ba, bb, bc, b0, b1;
+  HIP_TRY(upload0(ba, a, sh.a * N));
+  HIP_TRY(upload0(bb, b, sh.b_once ? (size_t)sh.b : sh.b * N));
+  HIP_TRY(upload0(bc, c, sh.c_once ? (size_t)sh.c : sh.c * N));
+  HIP_TRY(b0.alloc(4 * sh.o0 * N * k));
+  HIP_TRY(b1.alloc(4 * sh.o1 * N * k));
+  hipLaunchKernelGGL(k_debug_fpmath, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, op, n, k, ba.as<float>(), bb.as<float>(),
+                     bc.as<float>(), b0.as<float>(), b1.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out0, b0.p, 4 * sh.o0 * N * k, hipMemcpyDeviceToHost));
+  if (sh.o1) HIP_TRY(hipMemcpy(out1, b1.p, 4 * sh.o1 * N * k, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// out_rgb[i] = sample_hdr(scene, dirs[i]): the environment lookup every sky sample runs.
+int jade_debug_sample_hdr(jade_scene* s, int32_t n, const float* dirs, float* out_rgb) {
+  if (!s || !dirs || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (!s->dev.env || s->dev.env_w <= 0 || s->dev.env_h <= 0) return jade_fail(JADE_ERR_INVALID, "the scene has no environment map");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bd, bo;
+  HIP_TRY(upload(bd, dirs, 3 * N, s->stream));
+  HIP_TRY(bo.alloc(N * 12));
+  hipLaunchKernelGGL(k_debug_sample_hdr, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bd.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_rgb, bo.p, N * 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// out_bgr[i] = tone_pack_bgr8(rgb[i], tonemap, limit, valid = true): k_resolve's and k_dn_out's statements.
+int jade_debug_tone_pack(int device_id, int32_t n, const float* rgb, int tonemap, float limit, uint8_t* out_bgr) {
+  if (!rgb || !out_bgr) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return jade_fail(JADE_ERR_INVALID, "unknown tone operator");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bo;
+  HIP_TRY(upload0(bi, rgb, 3 * N));
+  HIP_TRY(bo.alloc(3 * N));
+  hipLaunchKernelGGL(k_debug_tone_pack, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), tonemap, limit, bo.as<uint8_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out_bgr, bo.p, 3 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// ... and the same function compiled for the HOST: what jade_render_multi packs the gathered frame with (jade_multi.hip).  No HIP call.
+int jade_debug_tone_pack_host(int32_t n, const float* rgb, int tonemap, float limit, uint8_t* out_bgr) {
+  if (n < 0 || !rgb || !out_bgr) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return jade_fail(JADE_ERR_INVALID, "unknown tone operator");
+  for (int32_t i = 0; i < n; ++i) {
+    const float* m = rgb + 3 * (size_t)i;
+    tone_pack_bgr8(jv(m[0], m[1], m[2]), tonemap, limit, true, out_bgr + 3 * (size_t)i);
+  }
+  return JADE_OK;
+}
+}  // extern "C"
+
+#endif  // JADE_DEBUG_EXPORTS

@@ -298,8 +298,9 @@ static __device__ __forceinline__ jvec3 camera_ray_dir(const RenderConst& R, int
 }
 
 // ACESToneMapping (or the preview's Reinhard operator) + gamma + BGR pack of one pixel's linear colour m, PathTrace.cu:669-682,
-// 1457-1473 / pass3.fsh:8-18: k_resolve's statements, shared with the denoiser's output kernel.  out: 3 bytes, B G R.
-static __device__ __forceinline__ void tone_pack_bgr8(jvec3 m, int tonemap, float limit, bool valid, uint8_t* out) {
+// 1457-1473 / pass3.fsh:8-18: k_resolve's statements, shared with the denoiser's output kernel and - compiled for the host, from
+// the same jade_fpmath.h routines under the same flags - with jade_render_multi's pack of the gathered frame.  out: 3 bytes, B G R.
+static __host__ __device__ __forceinline__ void tone_pack_bgr8(jvec3 m, int tonemap, float limit, bool valid, uint8_t* out) {
   float v[3] = {m.x, m.y, m.z};
   float rein = 1.0f;
   if (tonemap == JADE_TONEMAP_REINHARD) {  // toneMapping(c, limit), PathTrace.cu:669-672 / pass3.fsh:8-18
@@ -312,9 +313,16 @@ static __device__ __forceinline__ void tone_pack_bgr8(jvec3 m, int tonemap, floa
     if (tonemap == JADE_TONEMAP_REINHARD) {
       x = x * rein;
     } else {
-      float num = x * (x * 2.51f + 0.03f);
-      float den = x * (x * 2.43f + 0.59f) + 0.14f;
-      x = num / den;
+      if (jade_fabs(x) > 1.0e18f) {
+        // x * x would overflow from 1.2e19 on and leave inf / inf = NaN, a black byte for the brightest pixels: the same quotient
+        // divided through by x * x (every such value lies above 1, so its byte is 255 either way)
+        float r = 1.0f / x;
+        x = (2.51f + 0.03f * r) / ((2.43f + 0.59f * r) + (0.14f * r) * r);
+      } else {
+        float num = x * (x * 2.51f + 0.03f);
+        float den = x * (x * 2.43f + 0.59f) + 0.14f;
+        x = num / den;
+      }
     }
     x = jade_powf(x, (float)(1.0 / 2.2));
     x = x * 255.0f;

@@ -2962,9 +2962,7 @@ int jade_trace_rays(jade_scene* s, int32_t n, const float* origins, const float*
 
 // ---- development / test entry points: NOT part of jade_rt.h and NOT in libjade_hip.so.  Only builds with -DJADE_DEBUG_EXPORTS=1
 // have them: libjade_hip_debug.so (make hipvariants; tests/conftest.py `hip_debug`) and the JADE_TRACE_PROFILE build.
-#ifndef JADE_DEBUG_EXPORTS
-#define JADE_DEBUG_EXPORTS JADE_TRACE_PROFILE
-#endif
+// (jade_runtime.h gives JADE_DEBUG_EXPORTS its default; the piece-by-piece arithmetic entry points are in jade_debug_units.hip.)
 #if JADE_DEBUG_EXPORTS
 extern "C" {
 // Development / tests (not part of jade_rt.h): jade_trace_rays with a limit per ray - k_trace's early exit on its own, outside

@@ -116,34 +116,6 @@ static int rccl_gather(jade_scene* const* scenes, int ndev, float* dst, const st
   return JADE_OK;
 }
 
-// host twin of k_resolve's tone map + pack (same jade_fpmath.h routines, same flags: same bits)
-static void tonemap_pack_host(const float* m, int tonemap, float limit, uint8_t* bgr) {
-  float v[3] = {m[0], m[1], m[2]};
-  float rein = 1.0f;
-  if (tonemap == JADE_TONEMAP_REINHARD) {
-    float luminance = (float)(0.3 * (double)m[0] + 0.6 * (double)m[1] + 0.1 * (double)m[2]);
-    rein = (float)(1.0 / (1.0 + (double)(luminance / limit)));
-  }
-  for (int k = 0; k < 3; ++k) {
-    float x = v[k];
-    if (tonemap == JADE_TONEMAP_REINHARD) {
-      x = x * rein;
-    } else {
-      float num = x * (x * 2.51f + 0.03f);
-      float den = x * (x * 2.43f + 0.59f) + 0.14f;
-      x = num / den;
-    }
-    x = jade_powf(x, (float)(1.0 / 2.2));
-    x = x * 255.0f;
-    x = x > 255 ? 255 : x;
-    v[k] = x;
-  }
-  for (int k = 0; k < 3; ++k) {
-    float x = v[2 - k];
-    bgr[k] = (x >= 0.0f) ? (uint8_t)x : (uint8_t)0;
-  }
-}
-
 int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_params* rp, float* out_rgb, uint8_t* out_bgr8,
                       jade_stats* st) {
   if (!scenes || ndev <= 0 || !rp) return jade_fail(JADE_ERR_INVALID, "null argument");
@@ -223,7 +195,8 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
         memcpy(dst_rgb + ((size_t)(y0 + ly) * W + x0) * 3, host.data() + off[i] + (t * 256 + (size_t)ly * 16) * 3, (size_t)ww * 12);
     });
   if (out_bgr8)
-    for (size_t p = 0; p < (size_t)W * H; ++p) tonemap_pack_host(dst_rgb + 3 * p, JADE_TONEMAP_ACES, 0.0f, out_bgr8 + 3 * p);
+    for (size_t p = 0; p < (size_t)W * H; ++p)  // k_resolve's own statements on the host (tone_pack_bgr8, jade_device.h): the same bits
+      tone_pack_bgr8(jv(dst_rgb[3 * p], dst_rgb[3 * p + 1], dst_rgb[3 * p + 2]), JADE_TONEMAP_ACES, 0.0f, true, out_bgr8 + 3 * p);
   if (st)
     for (int i = 0; i < ndev; ++i) {
       st->rays_primary += sts[i].rays_primary; st->rays_secondary += sts[i].rays_secondary;

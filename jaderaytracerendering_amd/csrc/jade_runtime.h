@@ -14,6 +14,16 @@
 
 #define JADE_HIDDEN __attribute__((visibility("hidden")))
 
+// The jade_debug_* entry points (jade_hip.hip, jade_debug_units.hip): only in builds with -DJADE_DEBUG_EXPORTS=1
+// (libjade_hip_debug.so) and in a -DJADE_TRACE_PROFILE=1 build; libjade_hip.so has none of them (tests/test_abi.py).
+#ifndef JADE_DEBUG_EXPORTS
+#if defined(JADE_TRACE_PROFILE) && JADE_TRACE_PROFILE
+#define JADE_DEBUG_EXPORTS 1
+#else
+#define JADE_DEBUG_EXPORTS 0
+#endif
+#endif
+
 struct alignas(8) QueueCtl {
   uint32_t count;   // rays emitted by the last shade pass          } one 64-bit word: k_shade reserves its queue
   uint32_t active;  // records with rays in flight after that pass } and list space with ONE atomic per block

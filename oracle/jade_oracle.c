@@ -1059,9 +1059,16 @@ static void tonemap_pack(jvec3 c, int mode, float limit, uint8_t* bgr) {
     if (mode == JADE_TONEMAP_REINHARD) {
       x = x * rein;
     } else {
-      float num = x * (x * 2.51f + 0.03f);
-      float den = x * (x * 2.43f + 0.59f) + 0.14f;
-      x = num / den;
+      if (jade_fabs(x) > 1.0e18f) {
+        /* x * x would overflow from 1.2e19 on and leave inf / inf = NaN, a black byte for the brightest pixels: the same quotient
+         * divided through by x * x (every such value lies above 1, so its byte is 255 either way) */
+        float r = 1.0f / x;
+        x = (2.51f + 0.03f * r) / ((2.43f + 0.59f * r) + (0.14f * r) * r);
+      } else {
+        float num = x * (x * 2.51f + 0.03f);
+        float den = x * (x * 2.43f + 0.59f) + 0.14f;
+        x = num / den;
+      }
     }
     x = jade_powf(x, (float)(1.0 / 2.2));
     x = x * 255.0f;
@@ -1174,6 +1181,27 @@ static int owns_pixel_s(const jade_scene* s, int x, int y) {
     return tid < s->tile_keep_n && s->tile_keep[tid];
   }
   return 1;
+}
+
+/* Checker-only exports (NOT part of jade_rt.h) of two pieces the integrator runs, one element at a time, so that tests can put
+ * them next to an independent float64 statement (tests/env_spec.py, tests/test_tone_spec.py) and next to the HIP module's copies
+ * (libjade_hip_debug.so: jade_debug_sample_hdr, jade_debug_tone_pack). */
+int jade_oracle_sample_hdr(jade_scene* s, int32_t n, const float* dirs, float* out_rgb) {
+  if (!s || n < 0 || !dirs || !out_rgb) return fail(JADE_ERR_INVALID, "null argument");
+  for (int32_t i = 0; i < n; ++i) {
+    jvec3 c = sample_hdr(s, V3(dirs + 3 * (size_t)i));
+    out_rgb[3 * (size_t)i] = c.x;
+    out_rgb[3 * (size_t)i + 1] = c.y;
+    out_rgb[3 * (size_t)i + 2] = c.z;
+  }
+  return JADE_OK;
+}
+/* the statements jade_render_resolve_ex runs on a pixel's mean */
+int jade_oracle_tone_pack(int32_t n, const float* rgb, int tonemap, float limit, uint8_t* out_bgr) {
+  if (n < 0 || !rgb || !out_bgr) return fail(JADE_ERR_INVALID, "null argument");
+  if (tonemap != JADE_TONEMAP_ACES && tonemap != JADE_TONEMAP_REINHARD) return fail(JADE_ERR_INVALID, "unknown tone operator");
+  for (int32_t i = 0; i < n; ++i) tonemap_pack(V3(rgb + 3 * (size_t)i), tonemap, limit, out_bgr + 3 * (size_t)i);
+  return JADE_OK;
 }
 
 /* Checker-only extension (NOT part of jade_rt.h; the HIP module has no such entry point): restrict the renders that

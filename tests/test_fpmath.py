@@ -1,4 +1,5 @@
-"""include/jade_fpmath.h: the arithmetic contract both backends rely on (CPU side)."""
+"""include/jade_fpmath.h: the arithmetic contract both backends rely on (CPU side: accuracy and special values of the host build).
+Its GPU twin, tests/test_gpu_fpmath.py, asks the device build of the same header for the same bits."""
 import ctypes
 
 import numpy as np
