@@ -25,8 +25,8 @@
  * visited / triangles tested) differ between trees, as the trees do.
  *
  * The header also holds the HIP module's other entry points that the CPU
- * oracle does not implement: adaptive sampling and its noise map, and the
- * edge-aware denoiser (below).
+ * oracle does not implement: adaptive sampling and its noise map, the
+ * edge-aware denoiser, and exposure with its luminance meter (below).
  * Exported by libjade_hip.so only; the oracle has none of them.
  */
 #ifndef JADE_BVH_H
@@ -147,6 +147,83 @@ int jade_render_denoise(jade_scene* scene, const jade_denoise_params* params, in
 int jade_denoise_image(int device_id, int32_t width, int32_t height, const float* rgb, const float* variance,
                        const float* albedo, const float* normal, const float* depth, const jade_denoise_params* params,
                        float* out_rgb);
+
+/* ---- Exposure: a luminance histogram of the frame, an exposure chosen from it, and the tone pack of the exposed frame ----
+ *
+ * Non-parity: the reference tone-maps the raw mean (PathTrace.cu:1457-1473), which is what jade_render_resolve_ex does and goes
+ * on doing.  Here the linear mean m of a pixel is multiplied by one exposure e for the whole frame before the tone curve:
+ *   bytes = the tone pack of jade_render_resolve_ex (ACES or Reinhard, gamma, BGR) applied to (e * m.r, e * m.g, e * m.b),
+ *   each product one float multiplication.  out_rgb is never scaled.  e = 1 gives jade_render_resolve_ex's bytes.
+ *
+ * Luminance of a pixel with linear colour (r, g, b) - the Reinhard operator's statement (PathTrace.cu:669-672):
+ *   Y = (float)(0.3 * (double)r + 0.6 * (double)g + 0.1 * (double)b)          (added from left to right)
+ * Class of a pixel, decided in this order: non-finite (Y is a NaN or +-inf), negative (Y < 0), zero (Y == +-0), positive.
+ * Bin of a positive Y, with u the 32 bits of the float Y:
+ *   b = clamp((int)(u >> 20) - 760, 0, JADE_METER_BINS - 1)
+ * i.e. the exponent and the top three bits of the mantissa: 8 bins per stop over the 64 stops [2^-32, 2^32), Y = 1.0f in bin 256.
+ * Bin b, with E = (b >> 3) - 32 and k = b & 7, covers [2^E (1 + k/8), 2^E (1 + (k+1)/8)).  No logarithm is taken per pixel.
+ * Subnormals and everything else below the range count in bin 0, everything above it (up to FLT_MAX) in bin 511.
+ *
+ * The histogram is integers, so it does not depend on the order in which pixels are counted, and it is additive: the meters of
+ * the ranks of a tile partition, added field by field (minimum and maximum of lum_min / lum_max over the ranks with positive
+ * pixels), are the meter of the frame.
+ *
+ * The exposure of a meter under AUTO (jade_meter_exposure; host code, double precision):
+ *   N = sum of bins, lo = p_lo N, hi = p_hi N
+ *   for b = 0 .. 511 in increasing order, C = sum of bins[j] over j < b:
+ *     w_b = max(0, min(C + bins[b], hi) - max(C, lo))         the part of the bin's pixels inside the window of ranks [lo, hi]
+ *     l_b = E + log2(1 + (2 k + 1) / 16)                      log2 of the bin's centre
+ *   L = (sum w_b l_b) / (sum w_b), both summed in increasing b
+ *   e = (float)(key * exp2(-L)), or 1.0f if sum w_b is 0; then clamped to [min_exposure, max_exposure]
+ * With the window [0, 1] this is Reinhard's log-average key (Reinhard et al. 2002): the frame's geometric mean luminance goes to
+ * `key`.  The window leaves out the darkest and the brightest pixels (a sun, black borders).  Under MANUAL e = exposure.
+ * Of the parameters only those of the mode in use are checked. */
+#define JADE_METER_BINS 512
+typedef struct jade_meter {
+  uint64_t bins[JADE_METER_BINS];
+  uint64_t n_positive;     /* == sum of bins */
+  uint64_t n_zero, n_negative, n_nonfinite;
+  float lum_min, lum_max;  /* over the positive pixels, exact values; both 0 when n_positive == 0 */
+} jade_meter;
+
+#define JADE_EXPOSURE_MANUAL 0
+#define JADE_EXPOSURE_AUTO 1
+typedef struct jade_display_params {
+  int32_t tonemap;                  /* JADE_TONEMAP_*, as jade_render_resolve_ex */
+  float limit;                      /* ... and its Reinhard limit */
+  int32_t exposure_mode;            /* JADE_EXPOSURE_* */
+  float exposure;                   /* MANUAL: the multiplier; finite, > 0 */
+  float key;                        /* AUTO: finite, > 0 */
+  float p_lo, p_hi;                 /* AUTO: 0 <= p_lo < p_hi <= 1 */
+  float min_exposure, max_exposure; /* AUTO: 0 < min_exposure <= max_exposure, finite */
+} jade_display_params;
+
+/* ACES, MANUAL with exposure 1, key 0.18, window [0.05, 0.95], clamp [2^-16, 2^16] (limit 1.5, used by Reinhard only). */
+void jade_display_defaults(jade_display_params* p);
+
+/* The exposure above.  Makes no HIP call: callable without a GPU.  `m` may be null under MANUAL.  Invalid parameters (a null
+ * pointer, an unknown mode, a value outside the ranges above) return a NaN and set jade_last_error. */
+float jade_meter_exposure(const jade_meter* m, const jade_display_params* p);
+
+/* The meter of the render in progress (after jade_render_begin + steps, or after jade_render_adaptive, where each tile is
+ * divided by its own count) over the in-image pixels of the owned tiles: the classes' counts add up to that number of pixels.
+ * Flushes first, like resolve; fails as jade_render_resolve_ex does before begin or with no sample rendered.  The render's sums,
+ * counters and next step are not changed. */
+int jade_render_meter(jade_scene* scene, jade_meter* out);
+
+/* Resolve with exposure.  out_rgb (nullable): the linear mean, NOT scaled - jade_render_resolve_ex's bit for bit.  out_bgr8
+ * (nullable): the tone pack of e * mean as stated above, with e = jade_meter_exposure(this rank's own meter, params).
+ * exposure_used, meter_out: nullable; the meter is taken under AUTO or when meter_out is given.  Pixels of tiles this rank does
+ * not own are left untouched.  A tile partition that wants ONE exposure for the frame adds the ranks' meters
+ * (jade_render_meter), calls jade_meter_exposure on the sum and resolves every rank under MANUAL with that value. */
+int jade_render_resolve_exposed(jade_scene* scene, const jade_display_params* params, float* out_rgb, uint8_t* out_bgr8,
+                                float* exposure_used, jade_meter* meter_out);
+
+/* The same on a caller's host frame, width*height pixels in out_rgb's layout, every pixel counted: what exposes a denoised
+ * frame (jade_render_denoise, jade_denoise_image) or the gathered frame of several ranks (jade_render_multi).  out_bgr8 is
+ * nullable (meter only), as are exposure_used and meter_out. */
+int jade_expose_image(int device_id, int32_t width, int32_t height, const float* rgb, const jade_display_params* params,
+                      uint8_t* out_bgr8, float* exposure_used, jade_meter* meter_out);
 
 #ifdef __cplusplus
 }

@@ -11,8 +11,8 @@ missing.  The CPU oracle under oracle/ is test infrastructure and is never
 imported from here.
 """
 from . import _abi, backend, host  # noqa: F401
-from .backend import Backend, JadeError, hip, make_params, params_from_config  # noqa: F401
+from .backend import Backend, JadeError, Meter, hip, make_params, params_from_config  # noqa: F401
 from .host import HostScene, SceneBuilder, build_config  # noqa: F401
 
-__all__ = ["Backend", "JadeError", "hip", "make_params", "params_from_config", "HostScene", "SceneBuilder",
+__all__ = ["Backend", "JadeError", "Meter", "hip", "make_params", "params_from_config", "HostScene", "SceneBuilder",
            "build_config", "backend", "host"]

@@ -16,6 +16,8 @@ TONEMAP_ACES, TONEMAP_REINHARD = 0, 1
 Q_RECORDS_PER_PIXEL, Q_STATE_BYTES, Q_SUM_LANES = 0, 1, 2
 WALK_REFERENCE, WALK_EARLY_EXIT, WALK_EARLY_EXIT_CACHED = 0, 1, 2
 ENV_REFERENCE, ENV_IMPORTANCE = 0, 1
+EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1
+METER_BINS = 512
 
 f3 = C.c_float * 3
 f16 = C.c_float * 16
@@ -98,6 +100,23 @@ class DenoiseParams(C.Structure):  # == jade_denoise_params, include/jade_bvh.h
     ]
 
 
+class MeterStruct(C.Structure):  # == jade_meter, include/jade_bvh.h
+    _fields_ = [
+        ("bins", C.c_uint64 * METER_BINS),
+        ("n_positive", C.c_uint64), ("n_zero", C.c_uint64), ("n_negative", C.c_uint64), ("n_nonfinite", C.c_uint64),
+        ("lum_min", C.c_float), ("lum_max", C.c_float),
+    ]
+
+
+class DisplayParams(C.Structure):  # == jade_display_params, include/jade_bvh.h
+    _fields_ = [
+        ("tonemap", C.c_int32), ("limit", C.c_float),
+        ("exposure_mode", C.c_int32), ("exposure", C.c_float),
+        ("key", C.c_float), ("p_lo", C.c_float), ("p_hi", C.c_float),
+        ("min_exposure", C.c_float), ("max_exposure", C.c_float),
+    ]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -151,6 +170,15 @@ BVH_SYMBOLS = {
     "jade_render_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "jade_denoise_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.POINTER(DenoiseParams), C.c_void_p]),
+    # exposure: defaults, the policy (meter, params) -> e, the render's meter, the exposed resolve (scene, params, rgb, bgr8, exposure
+    # used, meter) and caller images (device, width, height, rgb, params, bgr8, exposure used, meter)
+    "jade_display_defaults": (None, [C.POINTER(DisplayParams)]),
+    "jade_meter_exposure": (C.c_float, [C.POINTER(MeterStruct), C.POINTER(DisplayParams)]),
+    "jade_render_meter": (C.c_int, [C.c_void_p, C.POINTER(MeterStruct)]),
+    "jade_render_resolve_exposed": (C.c_int, [C.c_void_p, C.POINTER(DisplayParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_float),
+                                              C.POINTER(MeterStruct)]),
+    "jade_expose_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(DisplayParams), C.c_void_p,
+                                    C.POINTER(C.c_float), C.POINTER(MeterStruct)]),
 }
 
 HOST_SYMBOLS = {

@@ -39,6 +39,60 @@ def params_from_config(cfg, **kw):
     return make_params(cfg.width, cfg.height, kw.pop("spp"), list(cfg.eye), list(cfg.camera), **kw)
 
 
+class Meter:
+    """jade_meter (include/jade_bvh.h): the luminance histogram of a frame - `bins` (uint64 [512], 8 per stop over [2^-32, 2^32)), the
+    counts of the zero, negative and non-finite pixels, and the smallest and largest positive luminance (float32; 0 without positive
+    pixels).  Integers, so meters add: `a + b` is the meter of two ranks' tiles together."""
+
+    def __init__(self, bins=None, n_zero=0, n_negative=0, n_nonfinite=0, lum_min=0.0, lum_max=0.0):
+        self.bins = np.zeros(_abi.METER_BINS, np.uint64) if bins is None else np.array(bins, np.uint64).reshape(_abi.METER_BINS)
+        self.n_zero, self.n_negative, self.n_nonfinite = int(n_zero), int(n_negative), int(n_nonfinite)
+        self.lum_min, self.lum_max = np.float32(lum_min), np.float32(lum_max)
+
+    @property
+    def n_positive(self):
+        return int(self.bins.sum())
+
+    @property
+    def total(self):
+        """Pixels metered: the four classes together."""
+        return self.n_positive + self.n_zero + self.n_negative + self.n_nonfinite
+
+    @classmethod
+    def from_struct(cls, m):
+        return cls(np.ctypeslib.as_array(m.bins).copy(), m.n_zero, m.n_negative, m.n_nonfinite, m.lum_min, m.lum_max)
+
+    def to_struct(self):
+        m = _abi.MeterStruct()
+        m.bins[:] = [int(v) for v in self.bins]
+        m.n_positive, m.n_zero, m.n_negative, m.n_nonfinite = self.n_positive, self.n_zero, self.n_negative, self.n_nonfinite
+        m.lum_min, m.lum_max = float(self.lum_min), float(self.lum_max)
+        return m
+
+    def __add__(self, other):
+        both = [m for m in (self, other) if m.n_positive]
+        return Meter(self.bins + other.bins, self.n_zero + other.n_zero, self.n_negative + other.n_negative,
+                     self.n_nonfinite + other.n_nonfinite, min((m.lum_min for m in both), default=0.0),
+                     max((m.lum_max for m in both), default=0.0))
+
+    def __eq__(self, other):
+        return (isinstance(other, Meter) and np.array_equal(self.bins, other.bins)
+                and (self.n_zero, self.n_negative, self.n_nonfinite) == (other.n_zero, other.n_negative, other.n_nonfinite)
+                and self.lum_min.tobytes() == other.lum_min.tobytes() and self.lum_max.tobytes() == other.lum_max.tobytes())
+
+    __hash__ = None
+
+    def __repr__(self):
+        return (f"Meter(positive={self.n_positive}, zero={self.n_zero}, negative={self.n_negative}, nonfinite={self.n_nonfinite}, "
+                f"lum=[{self.lum_min!r}, {self.lum_max!r}])")
+
+    @staticmethod
+    def bin_edges():
+        """float64 [513]: bin b covers [edges[b], edges[b + 1]) - 2^E (1 + k/8) with E = (b >> 3) - 32, k = b & 7."""
+        b = np.arange(_abi.METER_BINS + 1)
+        return np.ldexp(1.0 + (b & 7) / 8.0, (b >> 3) - 32)
+
+
 class Backend:
     def __init__(self, path):
         if not os.path.exists(path):
@@ -98,6 +152,53 @@ class Backend:
         return out
 
 
+    def display_defaults(self):
+        """jade_display_defaults: ACES, manual exposure 1; key 0.18, window [0.05, 0.95], clamp [2^-16, 2^16] for auto."""
+        p = _abi.DisplayParams()
+        self.hip_only("jade_display_defaults")(C.byref(p))
+        return p
+
+    def display_params(self, exposure, tonemap=None, limit=1.5):
+        """The DisplayParams of an `exposure` argument: a DisplayParams is taken as it is; a number is a manual multiplier; "auto"
+        is the defaults' histogram policy.  tonemap None: ACES."""
+        if isinstance(exposure, _abi.DisplayParams):
+            return exposure
+        p = self.display_defaults()
+        p.tonemap, p.limit = _abi.TONEMAP_ACES if tonemap is None else int(tonemap), float(limit)
+        if isinstance(exposure, str):
+            if exposure != "auto":
+                raise ValueError(f"exposure {exposure!r}: a number, \"auto\" or a DisplayParams")
+            p.exposure_mode = _abi.EXPOSURE_AUTO
+        else:
+            p.exposure_mode, p.exposure = _abi.EXPOSURE_MANUAL, float(exposure)
+        return p
+
+    def meter_exposure(self, meter, display):
+        """jade_meter_exposure: the exposure `display` chooses for `meter` (a Meter; may be None under manual), a float holding
+        the float32 value.  Host code: needs no GPU.  JadeError(JADE_ERR_INVALID) for parameters outside their ranges."""
+        fn = self.hip_only("jade_meter_exposure")
+        e = fn(C.byref(meter.to_struct()) if meter is not None else None, C.byref(display))
+        if e != e:
+            raise JadeError(_abi.JADE_ERR_INVALID, self.lib.jade_last_error().decode())
+        return e
+
+    def expose_image(self, rgb, display=None, want_bgr8=True, device_id=0):
+        """jade_expose_image: meter, exposure and tone pack of a caller's frame rgb [H, W, 3] (a denoised frame, the gathered frame of
+        several ranks) on device `device_id`.  display None: the defaults.  Returns (bgr8 uint8 [H, W, 3] | None, exposure, Meter)."""
+        fn = self.hip_only("jade_expose_image")
+        if display is None:
+            display = self.display_defaults()
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"rgb of shape {rgb.shape}, expected [H, W, 3]")
+        h, w = rgb.shape[:2]
+        bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
+        e, m = C.c_float(0.0), _abi.MeterStruct()
+        self.check(fn(int(device_id), int(w), int(h), rgb.ctypes.data, C.byref(display), bgr.ctypes.data if want_bgr8 else None,
+                      C.byref(e), C.byref(m)))
+        return bgr, e.value, Meter.from_struct(m)
+
+
 class Scene:
     """A scene resident on the backend (PathTrace.cu:1618-1698 on the reference side)."""
 
@@ -149,12 +250,21 @@ class Scene:
         self.backend.check(self.backend.lib.jade_render_flush(self._h, C.byref(st)))
         return st
 
-    def resolve(self, want_rgb=True, want_bgr8=True, tonemap=None, limit=1.5):
-        """tonemap None/ACES: PathTrace.cu:680-682; _abi.TONEMAP_REINHARD: the preview's pass3.fsh operator."""
+    def resolve(self, want_rgb=True, want_bgr8=True, tonemap=None, limit=1.5, exposure=None):
+        """tonemap None/ACES: PathTrace.cu:680-682; _abi.TONEMAP_REINHARD: the preview's pass3.fsh operator.
+        exposure None: (rgb, bgr8) of jade_render_resolve / _resolve_ex.  Otherwise jade_render_resolve_exposed (HIP module only): a
+        number is a manual multiplier, "auto" the histogram policy with the defaults, a DisplayParams is taken as it is (tonemap and
+        limit included); returns (rgb - never scaled, bgr8 of exposure x rgb, the exposure used, the Meter of this rank's pixels)."""
         h, w = self._params.height, self._params.width
         rgb = np.zeros((h, w, 3), np.float32) if want_rgb else None
         bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
         pr, pb = (rgb.ctypes.data if want_rgb else None), (bgr.ctypes.data if want_bgr8 else None)
+        if exposure is not None:
+            fn = self._hip_only("jade_render_resolve_exposed")
+            dp = self.backend.display_params(exposure, tonemap, limit)
+            e, m = C.c_float(0.0), _abi.MeterStruct()
+            self.backend.check(fn(self._h, C.byref(dp), pr, pb, C.byref(e), C.byref(m)))
+            return rgb, bgr, e.value, Meter.from_struct(m)
         if tonemap is None:
             self.backend.check(self.backend.lib.jade_render_resolve(self._h, pr, pb))
         else:
@@ -222,6 +332,13 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(params), _abi.TONEMAP_ACES if tonemap is None else int(tonemap), float(limit),
                               rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None))
         return rgb, bgr
+
+    def meter(self):
+        """jade_render_meter: the Meter of the render in progress over the in-image pixels of the owned tiles."""
+        fn = self._hip_only("jade_render_meter")
+        m = _abi.MeterStruct()
+        self.backend.check(fn(self._h, C.byref(m)))
+        return Meter.from_struct(m)
 
     def query(self, what):
         """jade_render_query: what the backend holds for the current render (_abi.Q_*)."""

@@ -218,6 +218,8 @@ struct jade_scene {
   // the work counters of the flush a denoiser entry point made (carried paths finished early): handed to the next step / flush's
   // statistics, so that a render's counters do not depend on whether it was denoised between its steps
   jade_stats dn_carried{};
+  // exposure (jade_expose.hip), allocated on first use and kept: k_meter's rows (one histogram per block) and their sum
+  DevBuf b_ex_rows, b_ex_meter;
   ~jade_scene() {
     if (stream) (void)hipStreamDestroy(stream);
   }

@@ -35,6 +35,10 @@ struct Api {
   void (*denoise_defaults)(jade_denoise_params*) = nullptr;
   int (*render_denoise)(jade_scene*, const jade_denoise_params*, int, float, float*, uint8_t*) = nullptr;
   int (*render_guides)(jade_scene*, int32_t, float*, float*, float*, float*) = nullptr;
+  // ... and only for --exposure / --histogram
+  void (*display_defaults)(jade_display_params*) = nullptr;
+  int (*render_resolve_exposed)(jade_scene*, const jade_display_params*, float*, uint8_t*, float*, jade_meter*) = nullptr;
+  int (*expose_image)(int, int32_t, int32_t, const float*, const jade_display_params*, uint8_t*, float*, jade_meter*) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -78,6 +82,13 @@ static void usage() {
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
+          "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
+          "  --exposure EV: the frame is multiplied by 2^EV before the tone curve (HIP backend only; the .pfm output is never scaled)\n"
+          "  --exposure auto: the multiplier comes from the frame's luminance histogram (include/jade_bvh.h): the log-average luminance of\n"
+          "                   the pixels between the LO and HI quantiles (default 0.05,0.95) goes to K (default 0.18)\n"
+          "  --histogram FILE: the luminance histogram as text: 512 lines `lower edge, count` (8 bins per stop from 2^-32), then the\n"
+          "                    counts of the positive, zero, negative and non-finite pixels and the smallest / largest positive luminance\n"
+          "                    (HIP backend only).  With --denoise both read the denoised frame\n"
           "  --denoise: write the frame filtered by the edge-aware denoiser (HIP backend only; include/jade_bvh.h, default parameters)\n"
           "  --guides PREFIX: write the denoiser's inputs as PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_variance.pfm\n"
           "                   (HIP backend only; 4 guide samples)\n"
@@ -101,6 +112,9 @@ int main(int argc, char** argv) {
   bool use_adaptive = false;
   bool use_denoise = false;
   std::string guides;
+  bool use_exposure = false, auto_exposure = false, have_key = false, have_window = false;
+  double exposure_ev = 0.0, key = 0.18, win_lo = 0.05, win_hi = 0.95;
+  std::string histogram;
   auto number = [](const char* flag, const char* v) {
     char* end = nullptr;
     const double x = strtod(v, &end);
@@ -129,12 +143,32 @@ int main(int argc, char** argv) {
     else if (a == "--error-floor") error_floor = number("--error-floor", need("--error-floor"));
     else if (a == "--denoise") use_denoise = true;
     else if (a == "--guides") guides = need("--guides");
+    else if (a == "--exposure") {
+      const char* v = need("--exposure");
+      use_exposure = true;
+      auto_exposure = strcmp(v, "auto") == 0;
+      if (!auto_exposure) exposure_ev = number("--exposure", v);
+    }
+    else if (a == "--key") { key = number("--key", need("--key")); have_key = true; }
+    else if (a == "--exposure-window") {
+      const std::string v = need("--exposure-window");
+      const size_t comma = v.find(',');
+      if (comma == std::string::npos) { fprintf(stderr, "--exposure-window: expected LO,HI: %s\n", v.c_str()); return 2; }
+      win_lo = number("--exposure-window", v.substr(0, comma).c_str());
+      win_hi = number("--exposure-window", v.substr(comma + 1).c_str());
+      have_window = true;
+    }
+    else if (a == "--histogram") histogram = need("--histogram");
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
   if (use_adaptive && !(adaptive > 0.0)) { fprintf(stderr, "--adaptive must be > 0\n"); return 2; }
   if (min_spp < 2 || (min_spp & (min_spp - 1)) != 0) { fprintf(stderr, "--min-spp must be a power of two >= 2\n"); return 2; }
   if (!(error_floor > 0.0)) { fprintf(stderr, "--error-floor must be > 0\n"); return 2; }
+  if (use_exposure && !auto_exposure && !(std::fabs(exposure_ev) <= 64.0)) { fprintf(stderr, "--exposure must be auto or within -64 .. 64 stops\n"); return 2; }
+  if ((have_key || have_window) && !auto_exposure) { fprintf(stderr, "--key and --exposure-window belong to --exposure auto\n"); return 2; }
+  if (!(key > 0.0) || !std::isfinite((float)key) || !((float)key > 0.0f)) { fprintf(stderr, "--key must be > 0\n"); return 2; }
+  if (!(win_lo >= 0.0 && (float)win_lo < (float)win_hi && win_hi <= 1.0)) { fprintf(stderr, "--exposure-window needs 0 <= LO < HI <= 1\n"); return 2; }
   if (config.empty() == args_file.empty()) { usage(); return 2; }
   if (backend.empty()) {
     char self[4096];
@@ -193,6 +227,16 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (use_exposure || !histogram.empty()) {
+    *(void**)(&api.display_defaults) = dlsym(api.h, "jade_display_defaults");
+    *(void**)(&api.render_resolve_exposed) = dlsym(api.h, "jade_render_resolve_exposed");
+    *(void**)(&api.expose_image) = dlsym(api.h, "jade_expose_image");
+    if (!api.display_defaults || !api.render_resolve_exposed || !api.expose_image) {
+      fprintf(stderr, "%s needs the HIP backend: %s has no jade_render_resolve_exposed / jade_expose_image\n", use_exposure ? "--exposure" : "--histogram",
+              backend.c_str());
+      return 2;
+    }
+  }
   jade_scene_desc desc = scene.desc();
   jade_scene* dev = nullptr;
   if (api.scene_create(&desc, device, &dev) != JADE_OK) { fprintf(stderr, "scene: %s\n", api.last_error()); return 1; }
@@ -238,6 +282,36 @@ int main(int argc, char** argv) {
     api.denoise_defaults(&dp);
     if (api.render_denoise(dev, &dp, JADE_TONEMAP_ACES, 0.0f, rgb.data(), bgr.data()) != JADE_OK) { fprintf(stderr, "denoise: %s\n", api.last_error()); return 1; }
     printf("denoised: %d a-trous passes, %d guide samples\n", dp.iterations, dp.guide_spp);
+  }
+  if (use_exposure || !histogram.empty()) {
+    // the bytes again, from exposure x frame; the linear frame (a .pfm output) stays as it is
+    jade_display_params dp;
+    api.display_defaults(&dp);
+    if (auto_exposure) {
+      dp.exposure_mode = JADE_EXPOSURE_AUTO;
+      dp.key = (float)key;
+      dp.p_lo = (float)win_lo;
+      dp.p_hi = (float)win_hi;
+    } else {
+      dp.exposure = (float)std::exp2(exposure_ev);
+    }
+    float e = 0.0f;
+    jade_meter m;
+    const int rc = use_denoise ? api.expose_image(device, rp.width, rp.height, rgb.data(), &dp, bgr.data(), &e, &m)
+                               : api.render_resolve_exposed(dev, &dp, nullptr, bgr.data(), &e, &m);
+    if (rc != JADE_OK) { fprintf(stderr, "exposure: %s\n", api.last_error()); return 1; }
+    printf("exposure: x%.9g (%+.3f EV%s), luminance %.9g .. %.9g over %llu positive pixels\n", e, std::log2((double)e), auto_exposure ? ", auto" : "",
+           m.lum_min, m.lum_max, (unsigned long long)m.n_positive);
+    if (!histogram.empty()) {
+      FILE* f = fopen(histogram.c_str(), "w");
+      if (!f) { fprintf(stderr, "cannot write %s\n", histogram.c_str()); return 1; }
+      for (int b = 0; b < JADE_METER_BINS; ++b)  // bin b starts at 2^E (1 + k/8), E = (b >> 3) - 32, k = b & 7
+        fprintf(f, "%.17g %llu\n", std::ldexp(1.0 + (b & 7) / 8.0, (b >> 3) - 32), (unsigned long long)m.bins[b]);
+      fprintf(f, "positive %llu\nzero %llu\nnegative %llu\nnonfinite %llu\nlum_min %.9g\nlum_max %.9g\n", (unsigned long long)m.n_positive,
+              (unsigned long long)m.n_zero, (unsigned long long)m.n_negative, (unsigned long long)m.n_nonfinite, m.lum_min, m.lum_max);
+      if (fclose(f) != 0) { fprintf(stderr, "cannot write %s\n", histogram.c_str()); return 1; }
+      printf("wrote %s\n", histogram.c_str());
+    }
   }
   api.scene_destroy(dev);
   std::string hist;

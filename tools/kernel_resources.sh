@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-for f in jade_hip jade_bvh jade_adaptive jade_denoise; do
+for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose; do
 /opt/rocm/bin/hipcc "$@" -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -mfma -I"$R/include" -I"$R/jaderaytracerendering_amd/csrc" \
   -c "$R/jaderaytracerendering_amd/csrc/$f.hip" -o "$T/x.o" -Rpass-analysis=kernel-resource-usage 2>&1 |
@@ -22,9 +22,10 @@ for line in sys.stdin:
         rows[cur][m.group(1).strip()] = int(m.group(2))
 for k, v in rows.items():
     m = re.match(r"^_Z\d+(k_[a-z_0-9]+?)(?=\d|P|$)", k)
-    if not m:
+    t = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILb([01])EE", k)  # a kernel template over one bool: k_name<0> / k_name<1>
+    if not m and not t:
         continue
-    name = m.group(1)
+    name = "%s<%s>" % (t.group(1), t.group(2)) if t else m.group(1)
     print("%-16s VGPR %3d AGPR %3d SGPR %3d scratch %4d B  LDS %6d B  occupancy %d" % (name, v.get("VGPRs", -1), v.get("AGPRs", 0), v.get("TotalSGPRs", v.get("SGPRs", -1)), v.get("ScratchSize [bytes/lane]", v.get("ScratchSize", 0)), v.get("LDS Size [bytes/block]", v.get("LDS Size", 0)), v.get("Occupancy [waves/SIMD]", v.get("Occupancy", -1))))
 '
 done
