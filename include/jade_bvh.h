@@ -225,6 +225,63 @@ int jade_render_resolve_exposed(jade_scene* scene, const jade_display_params* pa
 int jade_expose_image(int device_id, int32_t width, int32_t height, const float* rgb, const jade_display_params* params,
                       uint8_t* out_bgr8, float* exposure_used, jade_meter* meter_out);
 
+/* ---- Glare: a light-conserving bloom pyramid ahead of the tone pack ----
+ *
+ * Non-parity: the reference has no glare.  A share s of every pixel's light is scattered over a pyramid of ever wider blurs and added
+ * back, so that a pixel brighter than white shows as a halo instead of as flat white.  Linear and image-space: the render is not
+ * changed.  Every image below is width*height pixels laid out as out_rgb's (pixel (x, y) at y*width + x).
+ *
+ * Source: L_0 = c, the linear frame; a pixel with any non-finite channel enters L_0 as (0, 0, 0).
+ *
+ * REDUCE, h = (1, 4, 6, 4, 1)/16, W_{k+1} = ceil(W_k / 2), H_{k+1} = ceil(H_k / 2) (a 1x1 level stays 1x1):
+ *   L_{k+1}(x, y) = sum over i, j = -2..2 of h(i) h(j) L_k(clamp(2x + i), clamp(2y + j))
+ * with the coordinates clamped to the level (the border is replicated: a constant frame does not darken at its edges).  Separable:
+ * rows first (x), then columns (y); each 1-D sum is added in increasing i.
+ *
+ * EXPAND to a finer level of n columns from m, per axis, source indices clamped to [0, m-1]:
+ *   even x = 2j:     (1/8) a(j-1) + (3/4) a(j) + (1/8) a(j+1)        (added from left to right)
+ *   odd  x = 2j + 1: (1/2) a(j) + (1/2) a(j+1)
+ * Rows (y) first, then columns (x).  Both operators keep a constant, and away from the borders both keep the sum of the frame: a
+ * source pixel gives 1/2 per axis to the coarser level, and EXPAND gives it back.
+ *
+ * Weights: w_k = f^(k-1) / sum over j = 1..levels of f^(j-1), computed in double on the host and passed on as float.
+ *
+ * Accumulation, from the top down:
+ *   A_levels = w_levels L_levels
+ *   A_k      = w_k L_k + EXPAND(A_{k+1})          k = levels-1 .. 1
+ *   B        = EXPAND(A_1)                        at frame size
+ * Output: out = (1 - s) L_0 + s B, with (1 - s) one float subtraction and each product and the sum one float operation.  A pixel
+ * that was non-finite in c is written back as its input, bit for bit.  strength == 0 returns the input bit for bit (-0.0 and NaN
+ * payloads included) without running the pyramid, as iterations = 0 does in the denoiser.
+ *
+ * The defaults are a look, not a measurement: see DESIGN.md 3.8. */
+typedef struct jade_glare_params {
+  int32_t levels;   /* 1..12 pyramid levels */
+  float strength;   /* s in [0, 1]: the share of every pixel's light that is scattered */
+  float falloff;    /* f, finite and > 0: level k (1-based) weighs f^(k-1), normalised over the levels */
+} jade_glare_params;
+
+/* levels 6, strength 0.1, falloff 0.5. */
+void jade_glare_defaults(jade_glare_params* p);
+
+/* Glare of a caller's host frame on device `device_id`.  out_rgb == rgb is allowed.  A null pointer, a bad size (as
+ * jade_denoise_image; also a height above 1048560 = 16 * 65535 rows, which the kernels' grids do not hold) or a parameter outside
+ * its range or non-finite returns JADE_ERR_INVALID before any HIP call; device_id is checked as jade_denoise_image checks it.
+ * This is what glares a denoised frame (jade_render_denoise -> jade_glare_image -> jade_expose_image) or the gathered frame of
+ * several ranks. */
+int jade_glare_image(int device_id, int32_t width, int32_t height, const float* rgb, const jade_glare_params* params,
+                     float* out_rgb);
+
+/* Glare the render in progress on its device, one copy back: flush (as resolve), resolve (after jade_render_adaptive with each
+ * tile's own count), the pyramid, the meter of the glared frame under AUTO, jade_meter_exposure, the tone pack of e x glared colour.
+ * display may be null: jade_display_defaults.  out_rgb (nullable): the glared linear frame, NOT scaled by e - bit for bit
+ * jade_glare_image of jade_render_resolve_ex's out_rgb.  out_bgr8, exposure_used (nullable): bit for bit jade_expose_image of that
+ * glared frame under `display`.  Full frame only: tile_nranks > 1 gives JADE_ERR_UNSUPPORTED (gather, then jade_glare_image).
+ * Fails as jade_render_resolve_ex does before begin or with no sample rendered.  The render's sums, counters and next step are
+ * not changed. */
+int jade_render_glare(jade_scene* scene, const jade_glare_params* params, const jade_display_params* display,
+                      float* out_rgb, uint8_t* out_bgr8, float* exposure_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -117,6 +117,10 @@ class DisplayParams(C.Structure):  # == jade_display_params, include/jade_bvh.h
     ]
 
 
+class GlareParams(C.Structure):  # == jade_glare_params, include/jade_bvh.h
+    _fields_ = [("levels", C.c_int32), ("strength", C.c_float), ("falloff", C.c_float)]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -179,6 +183,12 @@ BVH_SYMBOLS = {
                                               C.POINTER(MeterStruct)]),
     "jade_expose_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(DisplayParams), C.c_void_p,
                                     C.POINTER(C.c_float), C.POINTER(MeterStruct)]),
+    # glare: defaults, caller images (device, width, height, rgb, params, out rgb) and the render's frame (scene, params, display
+    # params or null, rgb, bgr8, exposure used)
+    "jade_glare_defaults": (None, [C.POINTER(GlareParams)]),
+    "jade_glare_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GlareParams), C.c_void_p]),
+    "jade_render_glare": (C.c_int, [C.c_void_p, C.POINTER(GlareParams), C.POINTER(DisplayParams), C.c_void_p, C.c_void_p,
+                                    C.POINTER(C.c_float)]),
 }
 
 HOST_SYMBOLS = {

@@ -198,6 +198,26 @@ class Backend:
                       C.byref(e), C.byref(m)))
         return bgr, e.value, Meter.from_struct(m)
 
+    def glare_defaults(self):
+        """jade_glare_defaults: 6 levels, strength 0.1, falloff 0.5 - a look, not a measurement."""
+        p = _abi.GlareParams()
+        self.hip_only("jade_glare_defaults")(C.byref(p))
+        return p
+
+    def glare_image(self, rgb, params=None, device_id=0):
+        """jade_glare_image: the bloom pyramid (include/jade_bvh.h) on a caller's linear frame rgb [H, W, 3] (a denoised frame, the
+        gathered frame of several ranks) on device `device_id`.  params None: the defaults.  Returns the glared rgb, float32 [H, W, 3]."""
+        fn = self.hip_only("jade_glare_image")
+        if params is None:
+            params = self.glare_defaults()
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"rgb of shape {rgb.shape}, expected [H, W, 3]")
+        h, w = rgb.shape[:2]
+        out = np.zeros((h, w, 3), np.float32)
+        self.check(fn(int(device_id), int(w), int(h), rgb.ctypes.data, C.byref(params), out.ctypes.data))
+        return out
+
 
 class Scene:
     """A scene resident on the backend (PathTrace.cu:1618-1698 on the reference side)."""
@@ -332,6 +352,23 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(params), _abi.TONEMAP_ACES if tonemap is None else int(tonemap), float(limit),
                               rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None))
         return rgb, bgr
+
+    def glare(self, params=None, display=None, want_rgb=True, want_bgr8=True):
+        """jade_render_glare: the render in progress, glared on its device (full frame only), metered and tone-packed.  params None:
+        the glare defaults; display None: jade_display_defaults.  Returns (rgb float32 [H, W, 3] | None - the glared linear frame,
+        never scaled, bgr8 uint8 [H, W, 3] | None, the exposure used)."""
+        fn = self._hip_only("jade_render_glare")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        if params is None:
+            params = self.backend.glare_defaults()
+        h, w = self._params.height, self._params.width
+        rgb = np.zeros((h, w, 3), np.float32) if want_rgb else None
+        bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
+        e = C.c_float(0.0)
+        self.backend.check(fn(self._h, C.byref(params), C.byref(display) if display is not None else None,
+                              rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None, C.byref(e)))
+        return rgb, bgr, e.value
 
     def meter(self):
         """jade_render_meter: the Meter of the render in progress over the in-image pixels of the owned tiles."""

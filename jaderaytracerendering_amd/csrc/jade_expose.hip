@@ -178,14 +178,14 @@ float jade_meter_exposure(const jade_meter* m, const jade_display_params* p) {
   return e;
 }
 
-static int ex_check(const jade_display_params* p) {
+JADE_HIDDEN int ex_check(const jade_display_params* p) {
   if (const char* bad = ex_bad_params(p)) return jade_fail(JADE_ERR_INVALID, bad);
   if (p->tonemap != JADE_TONEMAP_ACES && p->tonemap != JADE_TONEMAP_REINHARD) return jade_fail(JADE_ERR_INVALID, "unknown tone operator");
   return JADE_OK;
 }
 
 // grow-only, as the denoiser's buffers
-static hipError_t ex_alloc(DevBuf& b, size_t bytes) { return (b.p && b.bytes >= bytes) ? hipSuccess : b.alloc(bytes); }
+JADE_HIDDEN hipError_t ex_alloc(DevBuf& b, size_t bytes) { return (b.p && b.bytes >= bytes) ? hipSuccess : b.alloc(bytes); }
 
 // Finish the paths the last step carried over, as resolve does; their work counters wait in dn_carried for the next step (the
 // denoiser's hand-over, jade_denoise.hip).
@@ -197,8 +197,8 @@ static int ex_flush(jade_scene* s) {
 }
 
 // The meter of n pixels at dev_rgb (tile_ids: compact tiles of a render; null: a plain image) - two kernels, 2 KB back, one wait.
-static int ex_meter(DevBuf& b_rows, DevBuf& b_words, const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, hipStream_t stream,
-                    jade_meter* out) {
+JADE_HIDDEN int ex_meter(DevBuf& b_rows, DevBuf& b_words, const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, hipStream_t stream,
+                         jade_meter* out) {
   memset(out, 0, sizeof *out);
   if (n <= 0) return JADE_OK;
   const int blocks = std::min((n + JADE_EX_BLOCK - 1) / JADE_EX_BLOCK, JADE_EX_MAX_BLOCKS);
@@ -228,8 +228,8 @@ static int ex_meter(DevBuf& b_rows, DevBuf& b_words, const float* dev_rgb, int n
   return JADE_OK;
 }
 
-static void ex_launch_pack(const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, float e, const jade_display_params* p,
-                           uint8_t* dev_bgr, hipStream_t stream) {
+JADE_HIDDEN void ex_launch_pack(const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, float e, const jade_display_params* p,
+                                uint8_t* dev_bgr, hipStream_t stream) {
   const dim3 grid((unsigned)((n + JADE_EX_BLOCK - 1) / JADE_EX_BLOCK));
   if (tile_ids)
     hipLaunchKernelGGL(k_expose_pack<true>, grid, dim3(JADE_EX_BLOCK), 0, stream, dev_rgb, n, R, tile_ids, e, (int)p->tonemap, p->limit, dev_bgr);
@@ -238,7 +238,7 @@ static void ex_launch_pack(const float* dev_rgb, int n, const RenderConst& R, co
 }
 
 // flush + k_resolve into b_out_rgb (compact tiles), what both render entry points start with
-static int ex_resolve(jade_scene* s) {
+JADE_HIDDEN int ex_resolve(jade_scene* s) {
   HIP_TRY(hipSetDevice(s->device));
   if (int rc = ex_flush(s)) return rc;
   if (s->ps.npx == 0) return JADE_OK;

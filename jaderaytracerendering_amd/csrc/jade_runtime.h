@@ -220,6 +220,9 @@ struct jade_scene {
   jade_stats dn_carried{};
   // exposure (jade_expose.hip), allocated on first use and kept: k_meter's rows (one histogram per block) and their sum
   DevBuf b_ex_rows, b_ex_meter;
+  // glare (jade_glare.hip), allocated on first use and kept: the frame in image layout (glared in place), its bytes, and every level
+  // of the pyramid in one allocation
+  DevBuf b_gl_rgb, b_gl_bgr, b_gl_pyr;
   ~jade_scene() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -248,6 +251,17 @@ JADE_HIDDEN int prepare_scene(const jade_scene_desc& d, int depth, const Tunable
 // sizes them from the queue's length on the device - and k_resolve over the owned pixels.  The caller asks hipGetLastError.
 JADE_HIDDEN void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays);
 JADE_HIDDEN int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream);
+
+// What the glare (jade_glare.hip) takes from exposure (jade_expose.hip) rather than copying it: the check of display parameters, the
+// grow-only allocation, flush + k_resolve into b_out_rgb (compact tiles), the meter of n pixels at dev_rgb (tile_ids: compact tiles of
+// a render; null: a plain image - two kernels, 2 KB back, one wait) and the launch of the tone pack of e x colour.
+JADE_HIDDEN int ex_check(const jade_display_params* p);
+JADE_HIDDEN hipError_t ex_alloc(DevBuf& b, size_t bytes);
+JADE_HIDDEN int ex_resolve(jade_scene* s);
+JADE_HIDDEN int ex_meter(DevBuf& b_rows, DevBuf& b_words, const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, hipStream_t stream,
+                         jade_meter* out);
+JADE_HIDDEN void ex_launch_pack(const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, float e, const jade_display_params* p,
+                                uint8_t* dev_bgr, hipStream_t stream);
 
 // Visits the owned tiles of a W x H image in owned order: f(t, x0, y0, ww, hh) - owned tile t (its pixels are t*256 + ly*16 + lx in
 // the compact layout) covers ww x hh image pixels from (x0, y0).

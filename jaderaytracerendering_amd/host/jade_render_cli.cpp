@@ -39,6 +39,10 @@ struct Api {
   void (*display_defaults)(jade_display_params*) = nullptr;
   int (*render_resolve_exposed)(jade_scene*, const jade_display_params*, float*, uint8_t*, float*, jade_meter*) = nullptr;
   int (*expose_image)(int, int32_t, int32_t, const float*, const jade_display_params*, uint8_t*, float*, jade_meter*) = nullptr;
+  // ... and only for --glare
+  void (*glare_defaults)(jade_glare_params*) = nullptr;
+  int (*glare_image)(int, int32_t, int32_t, const float*, const jade_glare_params*, float*) = nullptr;
+  int (*render_glare)(jade_scene*, const jade_glare_params*, const jade_display_params*, float*, uint8_t*, float*) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -82,13 +86,17 @@ static void usage() {
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
+          "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
+          "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
+          "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
+          "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
           "  --exposure EV: the frame is multiplied by 2^EV before the tone curve (HIP backend only; the .pfm output is never scaled)\n"
           "  --exposure auto: the multiplier comes from the frame's luminance histogram (include/jade_bvh.h): the log-average luminance of\n"
           "                   the pixels between the LO and HI quantiles (default 0.05,0.95) goes to K (default 0.18)\n"
           "  --histogram FILE: the luminance histogram as text: 512 lines `lower edge, count` (8 bins per stop from 2^-32), then the\n"
           "                    counts of the positive, zero, negative and non-finite pixels and the smallest / largest positive luminance\n"
-          "                    (HIP backend only).  With --denoise both read the denoised frame\n"
+          "                    (HIP backend only).  With --denoise and / or --glare both read the denoised / glared frame\n"
           "  --denoise: write the frame filtered by the edge-aware denoiser (HIP backend only; include/jade_bvh.h, default parameters)\n"
           "  --guides PREFIX: write the denoiser's inputs as PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_variance.pfm\n"
           "                   (HIP backend only; 4 guide samples)\n"
@@ -115,6 +123,8 @@ int main(int argc, char** argv) {
   bool use_exposure = false, auto_exposure = false, have_key = false, have_window = false;
   double exposure_ev = 0.0, key = 0.18, win_lo = 0.05, win_hi = 0.95;
   std::string histogram;
+  bool use_glare = false, have_glare_levels = false, have_glare_falloff = false;
+  double glare_strength = 0.0, glare_levels = 6, glare_falloff = 0.5;
   auto number = [](const char* flag, const char* v) {
     char* end = nullptr;
     const double x = strtod(v, &end);
@@ -159,6 +169,9 @@ int main(int argc, char** argv) {
       have_window = true;
     }
     else if (a == "--histogram") histogram = need("--histogram");
+    else if (a == "--glare") { glare_strength = number("--glare", need("--glare")); use_glare = true; }
+    else if (a == "--glare-levels") { glare_levels = number("--glare-levels", need("--glare-levels")); have_glare_levels = true; }
+    else if (a == "--glare-falloff") { glare_falloff = number("--glare-falloff", need("--glare-falloff")); have_glare_falloff = true; }
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
@@ -169,6 +182,10 @@ int main(int argc, char** argv) {
   if ((have_key || have_window) && !auto_exposure) { fprintf(stderr, "--key and --exposure-window belong to --exposure auto\n"); return 2; }
   if (!(key > 0.0) || !std::isfinite((float)key) || !((float)key > 0.0f)) { fprintf(stderr, "--key must be > 0\n"); return 2; }
   if (!(win_lo >= 0.0 && (float)win_lo < (float)win_hi && win_hi <= 1.0)) { fprintf(stderr, "--exposure-window needs 0 <= LO < HI <= 1\n"); return 2; }
+  if ((have_glare_levels || have_glare_falloff) && !use_glare) { fprintf(stderr, "--glare-levels and --glare-falloff belong to --glare\n"); return 2; }
+  if (!(glare_strength >= 0.0 && glare_strength <= 1.0)) { fprintf(stderr, "--glare must be within 0 .. 1\n"); return 2; }
+  if (!(glare_levels >= 1 && glare_levels <= 12 && glare_levels == (int)glare_levels)) { fprintf(stderr, "--glare-levels must be a whole number 1 .. 12\n"); return 2; }
+  if (!((float)glare_falloff > 0.0f) || !std::isfinite((float)glare_falloff)) { fprintf(stderr, "--glare-falloff must be > 0\n"); return 2; }
   if (config.empty() == args_file.empty()) { usage(); return 2; }
   if (backend.empty()) {
     char self[4096];
@@ -227,13 +244,24 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  if (use_exposure || !histogram.empty()) {
+  if (use_glare) {
+    *(void**)(&api.glare_defaults) = dlsym(api.h, "jade_glare_defaults");
+    *(void**)(&api.glare_image) = dlsym(api.h, "jade_glare_image");
+    *(void**)(&api.render_glare) = dlsym(api.h, "jade_render_glare");
+    if (!api.glare_defaults || !api.glare_image || !api.render_glare) {
+      fprintf(stderr, "--glare needs the HIP backend: %s has no jade_render_glare / jade_glare_image\n", backend.c_str());
+      return 2;
+    }
+  }
+  // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
+  const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
+  if (need_display) {
     *(void**)(&api.display_defaults) = dlsym(api.h, "jade_display_defaults");
     *(void**)(&api.render_resolve_exposed) = dlsym(api.h, "jade_render_resolve_exposed");
     *(void**)(&api.expose_image) = dlsym(api.h, "jade_expose_image");
     if (!api.display_defaults || !api.render_resolve_exposed || !api.expose_image) {
-      fprintf(stderr, "%s needs the HIP backend: %s has no jade_render_resolve_exposed / jade_expose_image\n", use_exposure ? "--exposure" : "--histogram",
-              backend.c_str());
+      fprintf(stderr, "%s needs the HIP backend: %s has no jade_render_resolve_exposed / jade_expose_image\n",
+              use_exposure ? "--exposure" : !histogram.empty() ? "--histogram" : "--glare with --denoise", backend.c_str());
       return 2;
     }
   }
@@ -283,9 +311,9 @@ int main(int argc, char** argv) {
     if (api.render_denoise(dev, &dp, JADE_TONEMAP_ACES, 0.0f, rgb.data(), bgr.data()) != JADE_OK) { fprintf(stderr, "denoise: %s\n", api.last_error()); return 1; }
     printf("denoised: %d a-trous passes, %d guide samples\n", dp.iterations, dp.guide_spp);
   }
-  if (use_exposure || !histogram.empty()) {
-    // the bytes again, from exposure x frame; the linear frame (a .pfm output) stays as it is
-    jade_display_params dp;
+  jade_display_params dp;
+  memset(&dp, 0, sizeof dp);
+  if (need_display) {
     api.display_defaults(&dp);
     if (auto_exposure) {
       dp.exposure_mode = JADE_EXPOSURE_AUTO;
@@ -295,13 +323,41 @@ int main(int argc, char** argv) {
     } else {
       dp.exposure = (float)std::exp2(exposure_ev);
     }
+  }
+  bool bytes_exposed = false;  // jade_render_glare made the bytes under dp already
+  if (use_glare) {
+    jade_glare_params gp;
+    api.glare_defaults(&gp);
+    gp.strength = (float)glare_strength;
+    gp.levels = (int32_t)glare_levels;
+    gp.falloff = (float)glare_falloff;
+    int rc;
+    float e = 1.0f;
+    if (use_denoise) {
+      // a denoised frame is on the host by now; its bytes come from jade_expose_image below
+      rc = api.glare_image(device, rp.width, rp.height, rgb.data(), &gp, rgb.data());
+    } else if (!histogram.empty()) {
+      // the histogram wants the meter, which only jade_expose_image hands back: the glared frame alone here, bytes and meter below
+      rc = api.render_glare(dev, &gp, nullptr, rgb.data(), nullptr, nullptr);
+    } else {
+      // the whole chain on the render's device: glare, meter, exposure and tone pack, one copy back
+      rc = api.render_glare(dev, &gp, use_exposure ? &dp : nullptr, rgb.data(), bgr.data(), &e);
+      bytes_exposed = use_exposure;
+    }
+    if (rc != JADE_OK) { fprintf(stderr, "glare: %s\n", api.last_error()); return 1; }
+    printf("glare: strength %.9g over %d levels, falloff %.9g\n", gp.strength, gp.levels, gp.falloff);
+    if (bytes_exposed) printf("exposure: x%.9g (%+.3f EV%s)\n", e, std::log2((double)e), auto_exposure ? ", auto" : "");
+  }
+  if (need_display && !bytes_exposed) {
+    // the bytes again, from exposure x frame; the linear frame (a .pfm output) stays as it is
     float e = 0.0f;
     jade_meter m;
-    const int rc = use_denoise ? api.expose_image(device, rp.width, rp.height, rgb.data(), &dp, bgr.data(), &e, &m)
+    const int rc = use_denoise || use_glare ? api.expose_image(device, rp.width, rp.height, rgb.data(), &dp, bgr.data(), &e, &m)
                                : api.render_resolve_exposed(dev, &dp, nullptr, bgr.data(), &e, &m);
     if (rc != JADE_OK) { fprintf(stderr, "exposure: %s\n", api.last_error()); return 1; }
-    printf("exposure: x%.9g (%+.3f EV%s), luminance %.9g .. %.9g over %llu positive pixels\n", e, std::log2((double)e), auto_exposure ? ", auto" : "",
-           m.lum_min, m.lum_max, (unsigned long long)m.n_positive);
+    if (use_exposure || !histogram.empty())
+      printf("exposure: x%.9g (%+.3f EV%s), luminance %.9g .. %.9g over %llu positive pixels\n", e, std::log2((double)e), auto_exposure ? ", auto" : "",
+             m.lum_min, m.lum_max, (unsigned long long)m.n_positive);
     if (!histogram.empty()) {
       FILE* f = fopen(histogram.c_str(), "w");
       if (!f) { fprintf(stderr, "cannot write %s\n", histogram.c_str()); return 1; }

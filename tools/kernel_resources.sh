@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose; do
+for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose jade_glare; do
 /opt/rocm/bin/hipcc "$@" -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -mfma -I"$R/include" -I"$R/jaderaytracerendering_amd/csrc" \
   -c "$R/jaderaytracerendering_amd/csrc/$f.hip" -o "$T/x.o" -Rpass-analysis=kernel-resource-usage 2>&1 |
