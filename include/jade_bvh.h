@@ -40,18 +40,64 @@ extern "C" {
 
 /* triangles: n records in ORIGINAL order (only p1, p2, p3 are read), host memory.
  * order_out[n]:   sorted position -> original index (the caller reorders its triangles with it)
- * nodes_out[max_nodes], *n_nodes_out: the tree; 2*n + 1 entries always suffice
+ * nodes_out[max_nodes], *n_nodes_out: the tree; 2*n + 1 entries always suffice.  With fewer than the tree needs the call
+ *                 returns JADE_ERR_INVALID and writes nothing.
  * build_ms (nullable): device time of the build kernels (sort included), without the copies
- * leaf_size: 1..15 (the reference uses 8) */
+ * leaf_size: 1..15 (the reference uses 8)
+ * JADE_ERR_INVALID: a null pointer (build_ms excepted), n <= 0, leaf_size outside 1..15, a non-finite vertex (below);
+ * JADE_ERR_UNSUPPORTED: n >= 2^27; JADE_ERR_DEVICE: no device of that id.
+ *
+ * ---- The tree, stated ----
+ * Both builders are deterministic, and what they build is fixed here completely enough to be built a second time, bit for
+ * bit: tests/bvh_ref.py does so in numpy and tests/test_gpu_bvh_exact.py compares.  Every operation below is ONE float32
+ * operation, correctly rounded, nothing contracted, denormals kept.
+ *
+ * [Centroid and keys]
+ *   c      = ((p1 + p2) + p3) / 3                                 per axis
+ *   cmin, cmax = the minimum and maximum of c over the triangles, per axis
+ *   scale  = 1023.999f / (cmax - cmin) where cmax > cmin, else 0  (an axis without extent; a denormal extent gives +inf)
+ *   q      = (c - cmin) * scale, clamped to [0, 1023] with a NaN (0 * inf, inf * 0) going to 0, then truncated to an integer
+ *   code   = the three 10-bit values interleaved, x highest: bit k of qx at bit 3k + 2, of qy at 3k + 1, of qz at 3k
+ *   key    = code << 32 | original index                          64 bits, unique; sorted ascending
+ *   The box of a triangle is the minimum and maximum of its three vertices, the box of a node the union (min, max) of its
+ *   children's: no arithmetic, so a box does not depend on the tree's shape above or below it.
+ *
+ * [LBVH]  The binary radix tree of the keys (Karras 2012).  A node over the key range [a, b], a < b, splits after the last
+ *   key that shares with key[a] more leading bits than key[b] does; the lower keys are the left child.  Triangles with one
+ *   code are split on the bits of their indices.
+ *
+ * [PLOC]  Clusters form a row, at first the triangles in key order.  One round:
+ *   - Every cluster i looks at the positions j != i with |j - i| <= 16 inside the row and chooses the j with the least
+ *     tuple (A, d, (low / d) & 1, low), compared lexicographically, where d = |j - i|, low = min(i, j), the division is the
+ *     integers', and A = (x * y + y * z) + z * x in float32 of the extents x, y, z (maximum corner - minimum corner) of the
+ *     union of the two boxes.  Equal areas are ties, +inf = +inf included; a NaN area (inf * 0: an extent that overflows
+ *     beside a flat one) counts as +inf.  The tuple belongs to the PAIR and no two pairs share one, so the least pair of the
+ *     row is always mutual: every round merges, whatever the areas.  The third member makes a row of equal areas pair up as
+ *     (0, 1), (2, 3), ... instead of chaining.
+ *   - Pairs that chose each other merge.  The lower position keeps its place in the row and is the LEFT child, the upper
+ *     one leaves the row and is the right child; everyone else stays, in order.
+ *   Rounds repeat until one cluster is left: the root.
+ *
+ * [Both builders]
+ *   - A subtree of <= leaf_size triangles is ONE leaf (the topmost such subtree: nothing below it is emitted).
+ *   - Triangle order (order_out): depth-first through the binary tree, left before right.  For the LBVH that is the key
+ *     order.  A leaf's triangles are [index, index + n - 1] of it.
+ *   - [Records] node 0 is the reference's dummy (left 255, right 128, n 30, index 0, aa (1, 1, 0), bb (0, 1, 0)), the root is
+ *     node 1, a leaf has left = right = 0 and n > 0, an internal node n = index = 0 and both children > 0.  WHICH number a
+ *     node gets beyond that is not part of the contract; two trees are the same if they agree walked together from node 1.
+ *
+ * [Non-finite input]  A triangle with a NaN or an infinite vertex coordinate is refused by both builders with
+ *   JADE_ERR_INVALID, and jade_last_error names the first such triangle.  (A NaN box is nobody's nearest neighbour, and
+ *   PLOC used to end with JADE_ERR_DEVICE "merged nothing" on it while the LBVH built a tree.)  Finite coordinates of any
+ *   magnitude build: where (p1 + p2) + p3 overflows the centroid is +-inf and the rules above still give every q. */
 int jade_bvh_build_lbvh(const jade_triangle* triangles, int32_t n, int32_t leaf_size, int device_id,
                         int32_t* order_out, jade_bvh_node* nodes_out, int32_t max_nodes,
                         int32_t* n_nodes_out, double* build_ms);
 
-/* Same contract, better tree: PLOC (parallel locally-ordered clustering).  Clusters - at first the triangles in Morton
- * order - are merged bottom-up, each with the neighbour within 16 positions whose union with it has the smallest
- * surface area, i.e. by the measure the reference's sweep-SAH builder minimises top-down (PathTrace.cu:532-628)
- * rather than by the Morton code's bits; subtrees of <= leaf_size triangles become leaves as in the reference
- * (:525-529).  Tens of rounds of four small kernels: milliseconds at 870 k triangles. */
+/* Same contract, better tree: PLOC (parallel locally-ordered clustering, Meister & Bittner 2018).  Clusters are merged
+ * bottom-up by the surface area of their union, i.e. by the measure the reference's sweep-SAH builder minimises top-down
+ * (PathTrace.cu:532-628) rather than by the Morton code's bits; subtrees of <= leaf_size triangles become leaves as in the
+ * reference (:525-529).  Tens of rounds of four small kernels: milliseconds at 870 k triangles. */
 int jade_bvh_build_ploc(const jade_triangle* triangles, int32_t n, int32_t leaf_size, int device_id,
                         int32_t* order_out, jade_bvh_node* nodes_out, int32_t max_nodes,
                         int32_t* n_nodes_out, double* build_ms);

@@ -24,6 +24,7 @@
 #include <rocprim/functional.hpp>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -206,8 +207,11 @@ __global__ void k_ploc_init(const unsigned long long* keys, int n, const float* 
   cbox[k] = b;
 }
 
-// nearest neighbour by surface area of the union, within PLOC_RADIUS positions.  The cost of a pair is symmetric and
-// ties are broken by the pair's (low, high) positions, so "i chose j and j chose i" is well defined.
+// nearest neighbour by surface area of the union, within PLOC_RADIUS positions: the minimum of the tuple include/jade_bvh.h
+// states, (area, distance, (low / distance) & 1, low).  The tuple is a property of the PAIR, both ends evaluate it alike and
+// no two pairs share it, so the least pair overall is always mutual: every round merges.  The first candidate is taken
+// whatever its area and +inf == +inf is a tie like any other (a sentinel "best = 3.0e38f" used to leave a cluster whose
+// unions all overflow without a partner, and the build failed).  inf * 0 of an overflowed extent and a flat one counts as +inf.
 __global__ __launch_bounds__(PLOC_BLOCK) void k_ploc_nn(int m, const Box6* cbox, int* nn) {
   __shared__ Box6 tile[PLOC_BLOCK + 2 * PLOC_RADIUS];
   const int base = blockIdx.x * PLOC_BLOCK - PLOC_RADIUS;
@@ -219,19 +223,20 @@ __global__ __launch_bounds__(PLOC_BLOCK) void k_ploc_nn(int m, const Box6* cbox,
   const int i = blockIdx.x * PLOC_BLOCK + threadIdx.x;
   if (i >= m) return;
   const Box6 me = tile[threadIdx.x + PLOC_RADIUS];
-  float best = 3.0e38f;
+  float best = 0.0f;
   int bj = -1;
   for (int d = -PLOC_RADIUS; d <= PLOC_RADIUS; ++d) {
     const int j = i + d;
     if (d == 0 || j < 0 || j >= m) continue;
-    const float a = union_area(me, tile[threadIdx.x + PLOC_RADIUS + d]);
+    float a = union_area(me, tile[threadIdx.x + PLOC_RADIUS + d]);
+    if (a != a) a = __builtin_inff();
     // Same area: a total order on PAIRS that both ends evaluate alike, so that the best pair overall is always mutual -
     // and one that cannot chain.  With "the pair with the lowest low end" every cluster of a row of equal areas (a ribbon,
     // instanced duplicates) chose its lower neighbour and ONE pair merged per round (600 identical triangles: 599 rounds).
     // Nearer in Morton order first; of the two neighbours at the same distance dd, the one whose pair starts at an even
     // multiple of dd - (2k, 2k+1), (4k, 4k+2), (4k+1, 4k+3), ...: disjoint pairs, so half of such a row merges per round.
-    bool better = a < best;
-    if (a == best && bj >= 0) {
+    bool better = bj < 0 || a < best;
+    if (bj >= 0 && a == best) {
       const int d1 = d < 0 ? -d : d, d0 = bj > i ? bj - i : i - bj;
       const int lo1 = i < j ? i : j, lo0 = i < bj ? i : bj;
       const int odd1 = (lo1 / d1) & 1, odd0 = (lo0 / d0) & 1;
@@ -314,13 +319,17 @@ int build_bvh(BuildKind kind, const jade_triangle* tris, int32_t n, int32_t leaf
 
   // vertices only, and the centroid bounds (O(n) on the host, beside the packing loop)
   std::vector<float> verts((size_t)9 * n);
-  float cmin[3] = {3e38f, 3e38f, 3e38f}, cmax[3] = {-3e38f, -3e38f, -3e38f};
+  float cmin[3] = {INFINITY, INFINITY, INFINITY}, cmax[3] = {-INFINITY, -INFINITY, -INFINITY};
   for (int i = 0; i < n; ++i) {
     const jade_triangle& t = tris[i];
     float* v = &verts[9 * (size_t)i];
     memcpy(v, t.p1, 12);
     memcpy(v + 3, t.p2, 12);
     memcpy(v + 6, t.p3, 12);
+    // [Non-finite input] of include/jade_bvh.h: a NaN box is nobody's partner; refused up front, by both builders alike
+    for (int k = 0; k < 9; ++k)
+      if (!std::isfinite(v[k]))
+        return jade_fail(JADE_ERR_INVALID, "triangle " + std::to_string(i) + " has a non-finite vertex coordinate");
     for (int k = 0; k < 3; ++k) {
       float c = (v[k] + v[3 + k] + v[6 + k]) / 3.0f;
       cmin[k] = c < cmin[k] ? c : cmin[k];

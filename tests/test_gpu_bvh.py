@@ -6,6 +6,7 @@ image agrees with the SAH scene's image up to the reference's tree-dependent cor
 import numpy as np
 import pytest
 
+from bvh_ref import check_invariants as _check_invariants
 from conftest import B, J, counters, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -15,32 +16,6 @@ def _builder(name):
     b = J.SceneBuilder()
     cfg = b.config(name)
     return b, cfg
-
-
-def _check_invariants(hs, leaf_max=8):
-    ni, nf, v = hs.node_i32(), hs.node_f32(), hs.vertices()
-    nT = hs.n_triangles
-    assert tuple(ni[0, :3]) == (255, 128, 30)
-    seen = np.zeros(nT, np.int32)
-    stack, depth = [(1, 1)], 0
-    while stack:
-        i, d = stack.pop()
-        depth = max(depth, d)
-        l, r, n, first = ni[i, :4]
-        aa, bb = nf[i, 4:7], nf[i, 7:10]
-        if n > 0:
-            assert 1 <= n <= leaf_max and l == 0 and r == 0
-            seen[first:first + n] += 1
-            tv = v[first:first + n].reshape(-1, 3)
-            assert np.array_equal(tv.min(0), aa) and np.array_equal(tv.max(0), bb)
-        else:
-            assert l > 0 and r > 0
-            # parent box = union of the children's boxes, exactly
-            assert np.array_equal(np.minimum(nf[l, 4:7], nf[r, 4:7]), aa) and np.array_equal(np.maximum(nf[l, 7:10], nf[r, 7:10]), bb)
-            stack += [(l, d + 1), (r, d + 1)]
-    assert (seen == 1).all() and depth == hs.bvh_depth < 127
-    assert np.array_equal(np.sort(hs.a["mapping"]), np.arange(nT))
-    return depth
 
 
 @pytest.mark.parametrize("kind", ["lbvh", "ploc"])
