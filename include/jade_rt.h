@@ -166,11 +166,51 @@ typedef struct jade_render_params {
    * mode)"): proportionally to the environment map's luminance x sin(theta) per texel, weighted by 1 / pdf (a direction on the wrong
    * side of the surface contributes nothing and no ray is traced for it).  A different estimator of the SAME integral: the image
    * converges to the same mean with less noise under a sky with a sun, and is NOT the reference's sample for sample - none of the
-   * parity claims apply to it, and the oracle refuses it (JADE_ERR_UNSUPPORTED). */
+   * parity claims apply to it, and the oracle refuses it (JADE_ERR_UNSUPPORTED).  Stated draw by draw below, at JADE_ENV_IMPORTANCE. */
   int32_t env_sampling;
 } jade_render_params;
 #define JADE_ENV_REFERENCE 0
+/* JADE_ENV_IMPORTANCE, completely (tests/env_importance_spec.py is this text in float64).  W x H = env_width x env_height,
+ * N = W * H, texel t = j * W + i (row j from the top, column i); PI = 3.1415926 (PathTrace.cu:36); fl() rounds to fp32.
+ *
+ * The distribution.  l_t = 0.2126 max(r, 0) + 0.7152 max(g, 0) + 0.0722 max(b, 0) of texel t, and 0 where that is not finite (a
+ * NaN or an infinite channel); floor = 0.01 * (sum of l) / N, or 1 if the sum is 0 (a black map);
+ *     w_t = (l_t + floor) * sin(PI * (j + 0.5) / H),     p_t = w_t / (sum of w),     q_t = p_t * N     (mean 1, every q_t > 0).
+ * The table (made once, at jade_scene_create) has N entries {accept, alias, q_own, q_alias}: a draw that lands in slot s takes
+ * texel s with probability accept_s and texel alias_s otherwise (alias_s < N; 0 <= accept_s <= 1, and alias_s = s where accept_s = 1),
+ * such that texel t is drawn with probability P_t = (accept_t + sum over s != t with alias_s = t of (1 - accept_s)) / N = p_t up
+ * to the fp32 rounding of accept: |P_t - p_t| <= (1 + m_t) * 2^-24 / N with m_t the number of slots whose alias is t.  q_own =
+ * fl(q_s) and q_alias = fl(q_{alias_s}): the density the weight below divides by is the INTENDED one, p.  Which small texel is
+ * paired with which large one is not part of this statement.
+ *
+ * A draw takes four uniforms u1..u4 from the sample's stream, in this order, where the reference draws the two of its uniform
+ * direction (PathTrace.cu:968-971, 1111-1114, 1304-1307) - each is jade_rand's fl(uint32) * 2^-32, in [0, 1], 1.0f included:
+ *     slot   s = min((uint32)fl(u1 * fl(N)), N - 1)                    (the product in fp32: a discrete decision)
+ *     own    iff u2 < accept_s;      t = own ? s : alias_s,   q = own ? q_own_s : q_alias_s;      j = t / W, i = t - j * W
+ *     u = (i + u3) / W,   v = (j + u4) / H,   theta = fl(PI) * v,   phi = fl(2 PI) * (u - 0.5)
+ *     direction = (st * cos(phi), cos(theta), st * sin(phi))   with st = max(sin(theta), 0)
+ *     ratio = fl(PI) * st / q
+ * The direction is the one SampleSphericalMap (PathTrace.cu:686-692) sends to the point (u, v) of the map; its density over
+ * directions is q / (2 pi^2 sin(theta)) - the map (u, v) -> direction has the Jacobian 2 pi^2 sin(theta) - and ratio is the
+ * reference's density, 1 / (2 pi), over that.  theta reaches fl(PI) = 3.14159250 (u4 = 1.0f in the bottom row), 1.5e-7 short of pi, so
+ * the sine is >= 0 on the whole range; the clamp makes ratio >= 0 hold whatever an fp32 sine rounds to at that end (jade_sincosf
+ * gives +1.51e-7 there and nothing below 0 on [0, fl(PI)], so today the clamp changes no value); a pole's direction is (0, +-1, 0)
+ * up to rounding.
+ * The device evaluates u, v, theta, phi, the sines and the products in fp32 (include/jade_fpmath.h); every component of the
+ * direction is then within 2.81e-6 of this statement.
+ *
+ * The wrong side.  Where the reference flips its direction into the surface's hemisphere (the diffuse and SSS-diffuse branch:
+ * dot(direction, n) * dot(out, n) < 0; the BSSRDF branch: dot(direction, n_exit) * dot(exit - entry, n_exit) < 0), this mode
+ * does NOT flip: no ray is traced, nothing is added for the environment at this vertex (it is not counted in rays_env either),
+ * and the four uniforms stay drawn - every later draw of the sample is where it would be.  Otherwise the environment ray is
+ * traced as the reference's is, and where it meets nothing the reference's term - sampleHdr(direction) x its weight, 2 PI
+ * included - is added multiplied by ratio.  Nothing else of the sample changes.
+ *
+ * Map size.  The slot is formed from a 24-bit uniform and reaches every slot only while N <= 2^24: jade_render_begin refuses this
+ * mode (JADE_ERR_UNSUPPORTED) on a scene whose map has more texels than JADE_ENV_IMPORTANCE_MAX_TEXELS - an 8192 x 4096 map renders
+ * with JADE_ENV_REFERENCE only (jade_scene_create accepts it). */
 #define JADE_ENV_IMPORTANCE 1
+#define JADE_ENV_IMPORTANCE_MAX_TEXELS 16777216 /* 2^24 */
 #define JADE_WALK_REFERENCE 0
 #define JADE_WALK_EARLY_EXIT 1
 /* JADE_WALK_EARLY_EXIT plus an occluder cache (ABI 7).  The reference tests a leaf's triangles iff the ray meets the leaf's box

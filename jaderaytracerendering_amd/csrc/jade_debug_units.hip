@@ -1,7 +1,8 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
-// include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h) and the tone curve (tone_pack_bgr8, jade_device.h).
+// include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
+// and its table, env_alias_table, jade_scene_prep.hip) and the tone curve (tone_pack_bgr8, jade_device.h).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
-// (tests/test_gpu_fpmath.py, tests/test_gpu_env_lookup.py, tests/test_gpu_tone.py, tests/test_tone_spec.py).  Each kernel is elementwise: element i reads
+// (tests/test_gpu_fpmath.py, tests/test_gpu_env_lookup.py, tests/test_gpu_env_importance.py, tests/test_gpu_tone.py, tests/test_tone_spec.py).  Each kernel is elementwise: element i reads
 // row i of its inputs and writes row i of its outputs, nothing else.
 #include "jade_runtime.h"
 #pragma clang diagnostic push
@@ -129,6 +130,22 @@ __global__ void k_debug_sample_hdr(DevScene S, int n, const float* d, float* out
   if (i < n) put3(out, i, sample_hdr(S, V3(d + 3 * i)));
 }
 
+// row i: the importance draw with the four uniforms u[4 i ..] (jade_rt.h, JADE_ENV_IMPORTANCE)
+__global__ void k_debug_env_sample(DevScene S, int n, const float* u, float* dir, float* ratio, uint32_t* texel) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  put3(dir, i, env_sample_at(S, u + 4 * i, ratio + i, texel + i));
+}
+
+// row i: the draw as the shading kernel makes it, from RNG state rng[i]; the state it leaves is written back
+__global__ void k_debug_env_sample_rng(DevScene S, int n, uint32_t* rng, float* dir, float* ratio) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t state = rng[i];
+  put3(dir, i, env_sample(S, &state, ratio + i));
+  rng[i] = state;
+}
+
 __global__ void k_debug_tone_pack(int n, const float* rgb, int tonemap, float limit, uint8_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) tone_pack_bgr8(V3(rgb + 3 * i), tonemap, limit, true, out + 3 * (size_t)i);
@@ -186,6 +203,74 @@ int jade_debug_sample_hdr(jade_scene* s, int32_t n, const float* dirs, float* ou
   HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }
+
+static int env_sample_scene_ok(const jade_scene* s) {
+  if (!s->dev.env_alias || !env_importance_fits(s->dev.env_w, s->dev.env_h))
+    return jade_fail(JADE_ERR_UNSUPPORTED, "the scene's environment map is not one JADE_ENV_IMPORTANCE takes");
+  return JADE_OK;
+}
+
+// (out_dir[i], out_ratio[i], out_texel[i]) = env_sample's body on the uniforms u[i][0..3]: the draw of JADE_ENV_IMPORTANCE.
+// out_texel: the texel in bits 0..24, bit 31 set iff the slot's own texel was taken.
+int jade_debug_env_sample(jade_scene* s, int32_t n, const float* u, float* out_dir, float* out_ratio, uint32_t* out_texel) {
+  if (!s || !u || !out_dir || !out_ratio || !out_texel) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (int rc = env_sample_scene_ok(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bu, bd, br, bt;
+  HIP_TRY(upload(bu, u, 4 * N, s->stream));
+  HIP_TRY(bd.alloc(N * 12));
+  HIP_TRY(br.alloc(N * 4));
+  HIP_TRY(bt.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_env_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bu.as<float>(), bd.as<float>(),
+                     br.as<float>(), bt.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_dir, bd.p, N * 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_ratio, br.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_texel, bt.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// ... and the wrapper the shading kernel calls, from the RNG states rng_in[i]: rng_out[i] is the state after the draw (its count and order).
+int jade_debug_env_sample_rng(jade_scene* s, int32_t n, const uint32_t* rng_in, uint32_t* rng_out, float* out_dir, float* out_ratio) {
+  if (!s || !rng_in || !rng_out || !out_dir || !out_ratio) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (int rc = env_sample_scene_ok(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bs, bd, br;
+  HIP_TRY(upload(bs, rng_in, N, s->stream));
+  HIP_TRY(bd.alloc(N * 12));
+  HIP_TRY(br.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_env_sample_rng, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bs.as<uint32_t>(), bd.as<float>(),
+                     br.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rng_out, bs.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_dir, bd.p, N * 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_ratio, br.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// env_alias_table (jade_scene_prep.hip) on a w x h map: out_u32x4[t] = {accept, alias, q_own, q_alias} as bits.  No HIP call.
+int jade_debug_env_alias_host(int32_t w, int32_t h, const float* rgb, uint32_t* out_u32x4) {
+  if (w <= 0 || h <= 0 || !rgb || !out_u32x4) return jade_fail(JADE_ERR_INVALID, "bad argument");
+  if (!env_importance_fits(w, h)) return jade_fail(JADE_ERR_UNSUPPORTED, "more texels than JADE_ENV_IMPORTANCE_MAX_TEXELS");
+  std::vector<uint4> table;
+  env_alias_table(w, h, rgb, table);
+  for (size_t t = 0; t < table.size(); ++t) {
+    out_u32x4[4 * t] = table[t].x;
+    out_u32x4[4 * t + 1] = table[t].y;
+    out_u32x4[4 * t + 2] = table[t].z;
+    out_u32x4[4 * t + 3] = table[t].w;
+  }
+  return JADE_OK;
+}
+
+// The map sizes jade_render_begin takes with JADE_ENV_IMPORTANCE (its own predicate, env_importance_fits): 1 / 0.  No HIP call.
+int jade_debug_env_importance_fits(int32_t w, int32_t h) { return env_importance_fits(w, h) ? 1 : 0; }
 
 // out_bgr[i] = tone_pack_bgr8(rgb[i], tonemap, limit, valid = true): k_resolve's and k_dn_out's statements.
 int jade_debug_tone_pack(int device_id, int32_t n, const float* rgb, int tonemap, float limit, uint8_t* out_bgr) {

@@ -2146,6 +2146,8 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   if (rp->walk != JADE_WALK_REFERENCE && rp->walk != JADE_WALK_EARLY_EXIT && rp->walk != JADE_WALK_EARLY_EXIT_CACHED)
     return jade_fail(JADE_ERR_INVALID, "unknown walk (JADE_WALK_*)");
   if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (rp->env_sampling == JADE_ENV_IMPORTANCE && !env_importance_fits(s->dev.env_w, s->dev.env_h))
+    return jade_fail(JADE_ERR_UNSUPPORTED, "env_sampling: JADE_ENV_IMPORTANCE takes environment maps of at most 2^24 texels (JADE_ENV_IMPORTANCE_MAX_TEXELS)");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();

@@ -245,6 +245,12 @@ struct ScenePrep {
   size_t geometry_bytes = 0;   // node + pair records
 };
 JADE_HIDDEN int prepare_scene(const jade_scene_desc& d, int depth, const Tunables& tun, ScenePrep* out);
+// ... its alias table over the environment map's texels (JADE_ENV_IMPORTANCE, include/jade_rt.h), and the map sizes that mode takes:
+// env_sample (jade_shade.h) forms the slot from a 24-bit uniform, which reaches every slot of at most 2^24
+JADE_HIDDEN void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb, std::vector<uint4>& env_alias);
+static inline bool env_importance_fits(int32_t env_width, int32_t env_height) {
+  return env_width > 0 && env_height > 0 && (uint64_t)env_width * (uint64_t)env_height <= JADE_ENV_IMPORTANCE_MAX_TEXELS;
+}
 
 // The two places where host code of one file needs a kernel of another (this tree is not built with -fgpu-rdc), both in jade_hip.hip:
 // the k_trace / k_trace_wide launch - kernel and grid chosen from (scene, P); n_rays sizes the chunks a wave claims, 0 = the kernel

@@ -263,15 +263,18 @@ void materials(const jade_scene_desc* d, std::vector<DevMaterial>& mats, std::ve
   }
 }
 
+}  // namespace
+
 // Environment importance sampling (jade_render_params.env_sampling; non-parity): Vose's alias table over the texels, weight =
 // (luminance + 1 % of the mean luminance) x sin(theta of the row's centre) - the floor keeps every texel drawable, so the
-// estimator stays unbiased wherever the sky is not black
-void env_alias_table(const jade_scene_desc* d, std::vector<uint4>& env_alias) {
-  const size_t W = (size_t)d->env_width, H = (size_t)d->env_height, N = W * H;
+// estimator stays unbiased wherever the sky is not black.  include/jade_rt.h (JADE_ENV_IMPORTANCE) states the weight and what an
+// entry means; how small and large texels are paired is not part of that statement.  No HIP call.
+void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb, std::vector<uint4>& env_alias) {
+  const size_t W = (size_t)env_width, H = (size_t)env_height, N = W * H;
   std::vector<double> wgt(N);
   double lum_sum = 0;
   for (size_t i = 0; i < N; ++i) {
-    const float* t = d->env_rgb + 3 * i;
+    const float* t = env_rgb + 3 * i;
     const double l = 0.2126 * std::max(t[0], 0.0f) + 0.7152 * std::max(t[1], 0.0f) + 0.0722 * std::max(t[2], 0.0f);
     wgt[i] = std::isfinite(l) ? l : 0.0;
     lum_sum += wgt[i];
@@ -314,8 +317,6 @@ void env_alias_table(const jade_scene_desc* d, std::vector<uint4>& env_alias) {
   }
 }
 
-}  // namespace
-
 int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, ScenePrep* out) {
   const jade_scene_desc* d = &desc;
   Layout lay{d};
@@ -341,6 +342,6 @@ int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, S
   if (JADE_WIDE_WALK && want_wide && !out->missing_child && lay.n_internal > 0 && out->nested && out->wide_fits) wide_records(d, lay, out->nodes, out->nodes4);
   guide_tables(d, out->guide, out->guide_obj);
   materials(d, out->mats, out->tnorm);
-  env_alias_table(d, out->env_alias);
+  env_alias_table(d->env_width, d->env_height, d->env_rgb, out->env_alias);
   return JADE_OK;
 }

@@ -73,28 +73,45 @@ static __device__ __forceinline__ jvec3 sphere_dir(uint32_t* rng) {  // PathTrac
   return jv(sine_theta * cs, sine_theta * sn, cosine_theta);
 }
 
-// Environment importance sampling (jade_render_params.env_sampling = JADE_ENV_IMPORTANCE; NOT the reference's estimator): a texel of
-// the map by the alias method, a point in it uniformly, the direction SampleSphericalMap (PathTrace.cu:686-692) maps to that point.
-// ratio = (pdf of the reference's uniform hemisphere sampling, 1 / 2 pi) / (pdf of this direction): what the reference's weight is
-// multiplied with.  Four draws.
-static __device__ __forceinline__ jvec3 env_sample(const DevScene& S, uint32_t* rng, float* ratio) {
-  const uint32_t W = (uint32_t)S.env_w, N = W * (uint32_t)S.env_h;
-  uint32_t idx = (uint32_t)(jade_rand(rng) * (float)N);
+// Environment importance sampling (jade_render_params.env_sampling = JADE_ENV_IMPORTANCE; NOT the reference's estimator), as
+// include/jade_rt.h states it draw by draw: a texel of the map by the alias method (u1 the slot, u2 own / alias), a point in it
+// uniformly (u3, u4), the direction SampleSphericalMap (PathTrace.cu:686-692) maps to that point.  ratio = (pdf of the reference's
+// uniform hemisphere sampling, 1 / 2 pi) / (pdf of this direction): what the reference's weight is multiplied with; never negative.
+// The body takes its uniforms from `next` where it needs them - u1 (the slot), u2 (own / alias), u3, u4 (the point) - so that the
+// shading kernel's code is what it was with jade_rand written in those four places, and a test can feed the four numbers
+// (jade_debug_units.hip).  *texel: the texel drawn, bit 31 = own (tests only; a caller that passes a dead variable pays nothing for it).
+template <class NextUniform>
+static __device__ __forceinline__ jvec3 env_sample_with(const DevScene& S, NextUniform next, float* ratio, uint32_t* texel) {
+  const uint32_t W = (uint32_t)S.env_w, N = W * (uint32_t)S.env_h;  // N <= 2^24: jade_render_begin refuses the mode otherwise
+  uint32_t idx = (uint32_t)(next() * (float)N);
   idx = idx < N ? idx : N - 1u;
-  const float u2 = jade_rand(rng);
+  const float u2 = next();
   const uint4 e = S.env_alias[idx];
   const bool own = u2 < jade_u2f(e.x);
   const float pdf_n = jade_u2f(own ? e.z : e.w);  // the chosen texel's probability x N
   idx = own ? idx : e.y;
+  *texel = idx | (own ? 0x80000000u : 0u);
   const uint32_t j = idx / W, i = idx - j * W;
-  const float u = ((float)i + jade_rand(rng)) / (float)W, v = ((float)j + jade_rand(rng)) / (float)S.env_h;
+  const float u3 = next();
+  const float u = ((float)i + u3) / (float)W, v = ((float)j + next()) / (float)S.env_h;
   const float theta = (float)JADE_PI_D * v, phi = (float)(2.0 * JADE_PI_D) * (u - 0.5f);
   float st, ct, sp, cp;
   jade_sincosf(theta, &st, &ct);
   jade_sincosf(phi, &sp, &cp);
+  st = st > 0.0f ? st : 0.0f;  // a weight is never negative, whatever a sine rounds to at theta = fl(PI) (u4 = 1 in the bottom row; jade_sincosf: +1.5e-7)
   // pdf(direction) = pdf_n / (2 pi^2 sin theta); against 1 / (2 pi): ratio = pi sin theta / pdf_n
   *ratio = (float)JADE_PI_D * st / pdf_n;
   return jv(st * cp, ct, st * sp);
+}
+// ... with four successive jade_rand draws: what bounce_branch calls
+static __device__ __forceinline__ jvec3 env_sample(const DevScene& S, uint32_t* rng, float* ratio) {
+  uint32_t texel;
+  return env_sample_with(S, [rng]() { return jade_rand(rng); }, ratio, &texel);
+}
+// ... and with four given numbers
+static __device__ __forceinline__ jvec3 env_sample_at(const DevScene& S, const float* u4, float* ratio, uint32_t* texel) {
+  int k = 0;
+  return env_sample_with(S, [u4, &k]() { return u4[k++]; }, ratio, texel);
 }
 
 static __device__ __forceinline__ jvec3 tri_point(const jade_triangle* t, float rx, float ry) {

@@ -159,7 +159,7 @@ def _spec_guide(S, x, y, p, frame):
 
 
 class _Geometry:
-    """What jade_spec.Scene.hit reads of a scene (jade_spec.Scene itself wants a constant environment; the guides never look at it)."""
+    """What jade_spec.Scene.hit reads of a scene (the geometry alone: the guides never look at the environment)."""
     hit = jade_spec.Scene.hit
 
     def __init__(self, hs):

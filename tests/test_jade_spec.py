@@ -9,7 +9,11 @@ reference"; what this adds is a second, independently written statement of the s
 A sample counts as agreeing when every channel is within 1e-4 relative (north_star's tolerance; fp32 + own libm vs
 float64 + numpy - measured worst case 5e-6); up to 2 % may disagree (a decision that fp32 and fp64 take differently, such
 as a shadow ray grazing an edge - none does at the time of writing).  Samples whose BSSRDF exit point lies in the plane
-of the entry point are left out: the reference decides two ray sides there by the sign of rounding noise (jade_spec.bssrdf)."""
+of the entry point are left out: the reference decides two ray sides there by the sign of rounding noise (jade_spec.bssrdf).
+
+Under a TEXTURED sky (an 8 x 4 map with one bright texel; tests/env_spec.py's float64 lookup) the same comparison runs on the jade
+cube and on an open floor, in the reference's mode on both backends and with env_sampling = JADE_ENV_IMPORTANCE - which the oracle
+refuses - on the HIP module alone: there jade_spec follows include/jade_rt.h through tests/env_importance_spec.py, sample for sample."""
 import numpy as np
 import pytest
 
@@ -35,7 +39,15 @@ LIGHT = dict(emissive=(20, 18, 15), brdf=(0.3, 0.3, 0.3))
 FLOOR = dict(brdf=(0.6, 0.5, 0.4))
 
 
-def build(kind):
+def sky_map():
+    """8 x 4 texels in [1, 8], one of them bright (above the lookup's clamp at 10, so that luminance and looked-up colour differ)."""
+    rng = np.random.default_rng(84)
+    env = (1.0 + 7.0 * rng.random((4, 8, 3))).astype(np.float32)
+    env[1, 5] = (60.0, 50.0, 40.0)
+    return env
+
+
+def build(kind, sky=False):
     b = J.SceneBuilder()
     rot = H.transform_matrix(rot_deg=(20, 30, 0))
     if kind == "jade_cube":
@@ -46,22 +58,27 @@ def build(kind):
         # along the diagonal, so that a path entering through triangle 1 leaves through triangle 0 out of its own plane.
         v = np.array([[-1, -1, 0], [1, -1, 0], [1, 1, 0], [-1, 1, 0.9]], np.float32)
         b.add_mesh(v, QUAD_I, H.material(**JADE), H.transform_matrix(rot_deg=(-25, 15, 0)))
+    elif kind != "open_floor":  # (a diffuse floor under the light and the open sky, nothing else)
+        raise ValueError(kind)
     b.add_mesh(quad(1.5, 0.5, flip=True), QUAD_I, H.material(**LIGHT))
     b.add_mesh(quad(-0.9, 3.0), QUAD_I, H.material(**FLOOR))
-    b.set_env_constant(0.5, 0.6, 0.8)
+    if sky:
+        b.set_env_data(sky_map())
+    else:
+        b.set_env_constant(0.5, 0.6, 0.8)
     return b.build()
 
 
-def compare(backend, kind, size, frames, need):
-    hs = build(kind)
-    S = jade_spec.Scene(hs)
+def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_REFERENCE):
+    hs = build(kind, sky)
+    S = jade_spec.Scene(hs, env_sampling)
     eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
     seen = {}
     bad = []
     n = skipped = 0
     with backend.scene(hs) as sc:
         for frame in frames:
-            p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2)
+            p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2, env_sampling=env_sampling)
             rgb, _, _ = sc.render(p, want_bgr8=False)
             for y in range(size):
                 for x in range(size):
@@ -100,3 +117,41 @@ def test_oracle_matches_float64_spec(oracle, kind):
 @pytest.mark.parametrize("kind", sorted(CASES))
 def test_hip_matches_float64_spec(hip, kind):
     compare(hip, kind, **CASES[kind])
+
+
+# Under the textured sky.  `need`: half of what jade_spec alone counts on these pixels (all of them agree on the oracle in the reference's mode).
+SKY_CASES = {
+    ("jade_cube", "reference"): dict(size=12, frames=(0, 1, 2), need={"diffuse": 110, "bssrdf": 9, "mirror": 31, "sss": 18, "sky": 76}),
+    ("open_floor", "reference"): dict(size=12, frames=(0, 1, 2), need={"diffuse": 119, "sky": 95}),
+    ("jade_cube", "importance"): dict(size=12, frames=(0, 1, 2), need={"diffuse": 110, "bssrdf": 7, "mirror": 32, "sss": 21, "sky": 76,
+                                                                         "env-importance": 88, "env-noenv": 48}),
+    ("open_floor", "importance"): dict(size=12, frames=(0, 1, 2), need={"diffuse": 119, "sky": 95, "env-importance": 79, "env-noenv": 40}),
+}
+ENV_MODES = {"reference": _abi.ENV_REFERENCE, "importance": _abi.ENV_IMPORTANCE}
+
+
+@pytest.mark.parametrize("kind", ["jade_cube", "open_floor"])
+def test_oracle_matches_float64_spec_under_a_textured_sky(oracle, kind):
+    seen, bad, n, skipped = compare(oracle, kind, sky=True, **SKY_CASES[kind, "reference"])
+    assert bad == 0, "the map was chosen so that no sample disagrees on the oracle"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,mode", sorted(SKY_CASES))
+def test_hip_matches_float64_spec_under_a_textured_sky(hip, kind, mode):
+    compare(hip, kind, sky=True, env_sampling=ENV_MODES[mode], **SKY_CASES[kind, mode])
+
+
+def test_importance_spec_needs_no_gpu_and_the_oracle_refuses_the_mode(oracle):
+    """jade_spec's importance arm runs on the CPU (its table comes from the host); the oracle states the reference's estimator only."""
+    hs = build("open_floor", sky=True)
+    S = jade_spec.Scene(hs, _abi.ENV_IMPORTANCE)
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    tr = []
+    for x in range(12):
+        assert np.isfinite(jade_spec.sample(S, x, 2, 12, 12, eye, cam, 0, tr)).all()
+    assert "env-importance" in tr and "env-noenv" in tr
+    with oracle.scene(hs) as so:
+        with pytest.raises(B.JadeError) as ei:
+            so.render(B.make_params(12, 12, 1, eye, cam, threads=2, env_sampling=_abi.ENV_IMPORTANCE))
+    assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
