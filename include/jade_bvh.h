@@ -26,7 +26,8 @@
  *
  * The header also holds the HIP module's other entry points that the CPU
  * oracle does not implement: adaptive sampling and its noise map, the
- * edge-aware denoiser, and exposure with its luminance meter (below).
+ * edge-aware denoiser, exposure with its luminance meter, glare, and the
+ * thin-lens camera (below).
  * Exported by libjade_hip.so only; the oracle has none of them.
  */
 #ifndef JADE_BVH_H
@@ -147,6 +148,9 @@ int jade_render_error(jade_scene* scene, float error_floor, float* out_error);
  * distance, and the ray goes on from the hit point in direction n (2 (o.n)) - o, o = -d.  At the final vertex k: z += hit
  * distance, a = t * brdf_k, n = norm_k negated if dot(norm_k, d) > 0.  A miss: a = t, n = 0, z = 0.  The guide of the pixel is
  * the float sum over s in increasing order times (float)(1/G); the normal is not renormalised.
+ * The guides follow the lens: in a render begun under a lens (jade_scene_set_lens, below) guide sample s takes its origin and its
+ * direction by "The lens, stated" - four draws instead of two - and everything after that is the statement above.  The guides then
+ * have the blurred edges the frame has; pinhole guides would tell the filter to keep edges that are not there.
  *
  * Variance of pixel p: the variance of its mean luminance, the square of the pixel error's numerator above:
  *   v = sum (Y_l - m)^2 / (K (K - 1))       (Y_l, m, K as above; fp64, stored as float; NaN where n cannot be estimated)
@@ -327,6 +331,49 @@ int jade_glare_image(int device_id, int32_t width, int32_t height, const float* 
  * not changed. */
 int jade_render_glare(jade_scene* scene, const jade_glare_params* params, const jade_display_params* display,
                       float* out_rgb, uint8_t* out_bgr8, float* exposure_used);
+
+/* ---- Thin lens: depth of field ----
+ *
+ * Non-parity: the reference's camera is a pinhole (PathTrace.cu:1428-1437).  The lens is a property of the scene handle, read by the
+ * next jade_render_begin - so by whatever begins a render: jade_render, jade_render_adaptive, jade_render_multi (per scene) - and a
+ * render in progress keeps the lens it began with.  With no lens, or aperture_radius == 0, every kernel, schedule, bit and counter is
+ * the pinhole's; the mode is entered only for aperture_radius > 0.  It is another estimator of another image: none of jade_rt.h's
+ * parity statements apply to it, as for JADE_ENV_IMPORTANCE.  It composes with JADE_ENV_IMPORTANCE, adaptive sampling, the denoiser,
+ * exposure and glare.
+ *
+ * ---- The lens, stated ----
+ * tests/lens_spec.py is this text in float64.  Every operation below is ONE float32 operation, nothing contracted; jade_transform,
+ * normalize and jade_sincosf are include/jade_fpmath.h's routines.  A = aperture_radius, a disk in the camera's plane z = 0, in the
+ * units of the scene; the plane of focus is camera-space z = -focus_distance.
+ *
+ * For sample s of pixel (x, y) the stream is seeded as jade_rt.h says.  u1, u2 are the two jitter draws and give left_offset and
+ * up_offset by the pinhole's statements, unchanged.  Then two more draws u3, u4, in this order, BEFORE any draw of the path:
+ *   r   = A * sqrt(u3)
+ *   phi = fl(2 PI) * u4                      PI = 3.1415926 as everywhere; (sn, cs) = jade_sincosf(phi)
+ *   lx  = r * cs,  ly = r * sn               the lens point (lx, ly, 0) in camera space: uniform over the disk
+ *   k   = focus_distance / 1.5f              one float division, on the host, once per render
+ *   d_c = (left_offset * k - lx, up_offset * k - ly, -1.5f * k)
+ *   dir    = normalize(jade_transform(d_c, 0, camera))
+ *   origin = eye + jade_transform((lx, ly, 0), 0, camera)         three float additions
+ * The pinhole ray of the same jitter and every lens ray of it meet in the plane of focus, at (left_offset, up_offset, -1.5) * k.  A
+ * point at camera depth z shows as a disk of radius 0.75 * height * A * |1/z - 1/focus_distance| pixels.  Every later draw of the
+ * sample sits two places further on in the stream than the pinhole's.  jade_stats.rays_primary still counts one query per sample.
+ *
+ * The schedule under a lens is the list schedule (the first pass is shaded and traced by separate kernels): there is
+ * no fused first pass yet, so rays_inline and tail_launches are 0.  Results do not depend on steps, tile partitions or records per
+ * pixel, as for the pinhole.
+ *
+ * jade_scene_set_lens: lens == null, or aperture_radius == 0: the pinhole.  aperture_radius must be finite and >= 0; focus_distance
+ * must be finite and > 0 whenever aperture_radius > 0 and is not checked otherwise (of the parameters only those in use are checked,
+ * as for exposure).  JADE_ERR_INVALID leaves the previous lens in place.
+ * jade_render_multi: all scenes must carry the same lens, bit for bit, else JADE_ERR_INVALID before anything is launched. */
+typedef struct jade_lens_params {
+  float aperture_radius; /* A >= 0, scene units; 0 = the pinhole */
+  float focus_distance;  /* > 0: depth of the plane of focus along the camera's axis */
+} jade_lens_params;
+
+int jade_scene_set_lens(jade_scene* scene, const jade_lens_params* lens);
+int jade_scene_get_lens(jade_scene* scene, jade_lens_params* out);
 
 #ifdef __cplusplus
 }

@@ -85,6 +85,15 @@ void jadeh_transform_matrix(const float rot_deg[3], const float trans[3], const 
 void jadeh_camera_orbit(float r, float up_deg, float rot_deg, const float center[3], float eye_out[3],
                         float cam_out[16]);
 
+/* Autofocus for the thin lens (include/jade_bvh.h): the depth, along the camera's axis, of what pixel (px, py) of the frame `params`
+ * describes shows at its centre.  The pinhole ray of that pixel with both jitter draws replaced by 0.5 is traced with `trace_rays`,
+ * the backend's jade_trace_rays (this library links against no backend), and *out = hit distance * 1.5 / |(left_offset, up_offset,
+ * -1.5)|: what jade_lens_params.focus_distance wants.  A miss (the sky) is an error, as is a pixel outside the frame. */
+typedef int (*jadeh_trace_rays_fn)(jade_scene* scene, int32_t n, const float* origins, const float* dirs, const int32_t* skip,
+                                   int32_t* hit_index, float* hit_dist, float* hit_point, jade_stats* stats);
+int jadeh_focus_distance(jadeh_trace_rays_fn trace_rays, jade_scene* scene, const jade_render_params* params, int px, int py,
+                         float* out);
+
 int jadeh_write_bmp(const char* path, const uint8_t* bgr, int w, int h);
 int jadeh_write_ppm(const char* path, const uint8_t* bgr, int w, int h);
 int jadeh_write_pfm(const char* path, const float* rgb, int w, int h);

@@ -121,6 +121,10 @@ class GlareParams(C.Structure):  # == jade_glare_params, include/jade_bvh.h
     _fields_ = [("levels", C.c_int32), ("strength", C.c_float), ("falloff", C.c_float)]
 
 
+class LensParams(C.Structure):  # == jade_lens_params, include/jade_bvh.h
+    _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -189,6 +193,9 @@ BVH_SYMBOLS = {
     "jade_glare_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GlareParams), C.c_void_p]),
     "jade_render_glare": (C.c_int, [C.c_void_p, C.POINTER(GlareParams), C.POINTER(DisplayParams), C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_float)]),
+    # the thin lens of a scene handle (scene, lens or null) / (scene, out)
+    "jade_scene_set_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),
+    "jade_scene_get_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),
 }
 
 HOST_SYMBOLS = {
@@ -217,6 +224,8 @@ HOST_SYMBOLS = {
     "jadeh_scene_build_seconds": (C.c_double, [C.c_void_p]),
     "jadeh_transform_matrix": (None, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jadeh_camera_orbit": (None, [C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # autofocus (the backend's jade_trace_rays, scene, params, px, py, out)
+    "jadeh_focus_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "jadeh_write_bmp": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "jadeh_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "jadeh_write_pfm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),

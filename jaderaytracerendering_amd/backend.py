@@ -370,6 +370,36 @@ class Scene:
                               rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None, C.byref(e)))
         return rgb, bgr, e.value
 
+    def set_lens(self, aperture_radius, focus_distance=0.0):
+        """jade_scene_set_lens: a thin lens of radius `aperture_radius` (scene units) focused at depth `focus_distance` along the
+        camera's axis, for every render this handle begins from now on (HIP module only; non-parity: include/jade_bvh.h, "The lens,
+        stated").  set_lens(None), or a radius of 0: the pinhole.  JadeError(JADE_ERR_INVALID) leaves the previous lens in place."""
+        fn = self._hip_only("jade_scene_set_lens")
+        if aperture_radius is None:
+            self.backend.check(fn(self._h, None))
+            return
+        lens = _abi.LensParams(float(aperture_radius), float(focus_distance))
+        self.backend.check(fn(self._h, C.byref(lens)))
+
+    def lens(self):
+        """jade_scene_get_lens: (aperture_radius, focus_distance) as set; (0.0, 0.0) for a handle that never got a lens."""
+        fn = self._hip_only("jade_scene_get_lens")
+        lens = _abi.LensParams()
+        self.backend.check(fn(self._h, C.byref(lens)))
+        return lens.aperture_radius, lens.focus_distance
+
+    def focus_distance(self, params, px, py):
+        """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
+        (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that
+        shows the sky, or lies outside the frame, raises RuntimeError."""
+        from . import host
+        lib = host.host_lib()
+        out = C.c_float(0.0)
+        trace = C.cast(self.backend.lib.jade_trace_rays, C.c_void_p)
+        if lib.jadeh_focus_distance(trace, self._h, C.byref(params), int(px), int(py), C.byref(out)) != 0:
+            raise RuntimeError(lib.jadeh_last_error().decode())
+        return out.value
+
     def meter(self):
         """jade_render_meter: the Meter of the render in progress over the in-image pixels of the owned tiles."""
         fn = self._hip_only("jade_render_meter")

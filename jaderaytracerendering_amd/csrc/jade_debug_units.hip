@@ -1,9 +1,12 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip) and the tone curve (tone_pack_bgr8, jade_device.h).
+// and its table, env_alias_table, jade_scene_prep.hip), the tone curve (tone_pack_bgr8, jade_device.h) and the thin-lens ray (lens_ray,
+// jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
 // (tests/test_gpu_fpmath.py, tests/test_gpu_env_lookup.py, tests/test_gpu_env_importance.py, tests/test_gpu_tone.py, tests/test_tone_spec.py).  Each kernel is elementwise: element i reads
 // row i of its inputs and writes row i of its outputs, nothing else.
+#include <cstring>
+
 #include "jade_runtime.h"
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // jade_shade.h's non-inline statics this file does not call
@@ -151,6 +154,42 @@ __global__ void k_debug_tone_pack(int n, const float* rgb, int tonemap, float li
   if (i < n) tone_pack_bgr8(V3(rgb + 3 * i), tonemap, limit, true, out + 3 * (size_t)i);
 }
 
+// A row of the lens ray's test entries, 32 floats: x, y, W, H (whole numbers), eye[3], cam[16], A, f, u1, u2, u3, u4, 3 unused.
+// The jitter statements are the render's (camera_ray_dir, jade_device.h) with u1, u2 in place of the two draws; k = f / 1.5f as
+// jade_render_begin forms it.  out: origin[3], dir[3].
+#define LENS_ROW 32
+static __host__ __device__ __forceinline__ void debug_lens_row(const float* row, float* out) {
+  const float x = row[0], y = row[1];
+  const double two_over_w = 2.0 / (double)(int)row[2], two_over_h = 2.0 / (double)(int)row[3];
+  const double aspect = (double)(int)row[2] / (double)(int)row[3];
+  const float fx = (float)(int)x + row[25];
+  const double lo = -1.0 + two_over_w * ((double)fx - 0.5);
+  const float left_offset = (float)(lo * aspect);
+  const float fy = (float)(int)y + row[26];
+  const float up_offset = (float)(-1.0 + two_over_h * ((double)fy - 0.5));
+  const float k = row[24] / 1.5f;
+  jvec3 o, d;
+  lens_ray(row + 7, row + 4, row[23], k, left_offset, up_offset, row[27], row[28], &o, &d);
+  out[0] = o.x; out[1] = o.y; out[2] = o.z;
+  out[3] = d.x; out[4] = d.y; out[5] = d.z;
+}
+__global__ void k_debug_lens_ray(int n, const float* rows, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) debug_lens_row(rows + (size_t)LENS_ROW * i, out + 6 * (size_t)i);
+}
+// row i: the lens ray as the shading kernel draws it, for sample sidx[i] of pixel (px[i], py[i]); the stream's state after the four draws
+__global__ void k_debug_lens_ray_rng(RenderConst R, float lens_k, int n, const int32_t* px, const int32_t* py, const uint32_t* sidx, float* out,
+                                     uint32_t* rng_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t rng;
+  jvec3 o;
+  const jvec3 d = camera_ray_lens(R, lens_k, px[i], py[i], sidx[i], &rng, &o);
+  put3(out, 2 * i, o);
+  put3(out, 2 * i + 1, d);
+  rng_out[i] = rng;
+}
+
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
 
 static hipError_t upload0(DevBuf& b, const void* src, size_t elems) {  // on the null stream: these entry points have no scene
@@ -296,6 +335,59 @@ int jade_debug_tone_pack_host(int32_t n, const float* rgb, int tonemap, float li
     const float* m = rgb + 3 * (size_t)i;
     tone_pack_bgr8(jv(m[0], m[1], m[2]), tonemap, limit, true, out_bgr + 3 * (size_t)i);
   }
+  return JADE_OK;
+}
+
+// The lens ray (lens_ray, jade_device.h; include/jade_bvh.h "The lens, stated") on n rows of LENS_ROW floats (above): out[i] = origin[3],
+// dir[3].  The HOST build of the function, no HIP call: what tests/test_lens_cpu.py holds against the float64 statement.
+int jade_debug_lens_ray_host(int32_t n, const float* rows, float* out) {
+  if (n < 0 || !rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  for (int32_t i = 0; i < n; ++i) debug_lens_row(rows + (size_t)LENS_ROW * i, out + 6 * (size_t)i);
+  return JADE_OK;
+}
+
+// ... and the same rows on the device.
+int jade_debug_lens_ray(int device_id, int32_t n, const float* rows, float* out) {
+  if (!rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / LENS_ROW) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bo;
+  HIP_TRY(upload0(bi, rows, LENS_ROW * N));
+  HIP_TRY(bo.alloc(24 * N));
+  hipLaunchKernelGGL(k_debug_lens_ray, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 24 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// The lens ray from the stream, as the render draws it: sample sidx[i] of pixel (px[i], py[i]) of a width x height frame from (eye,
+// camera) with `frame`, under lens (A, f).  out[i] = origin[3], dir[3]; rng_out[i] = the stream's state after the four draws.
+int jade_debug_lens_ray_rng(int device_id, int32_t n, int32_t width, int32_t height, uint32_t frame, const float* eye, const float* camera, float A, float f,
+                            const int32_t* px, const int32_t* py, const uint32_t* sidx, float* out, uint32_t* rng_out) {
+  if (!eye || !camera || !px || !py || !sidx || !out || !rng_out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows || width <= 0 || height <= 0) return jade_fail(JADE_ERR_INVALID, "row count or frame size out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  RenderConst R{};
+  R.width = width; R.height = height; R.tiles_x = (width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE; R.frame = frame;
+  memcpy(R.eye, eye, sizeof R.eye);
+  memcpy(R.cam, camera, sizeof R.cam);
+  R.lens_radius = A;
+  R.two_over_w = 2.0 / (double)width;   // (jade_render_begin's statements)
+  R.two_over_h = 2.0 / (double)height;
+  R.aspect = (double)width / (double)height;
+  const size_t N = (size_t)n;
+  DevBuf bx, by, bs, bo, br;
+  HIP_TRY(upload0(bx, px, N));
+  HIP_TRY(upload0(by, py, N));
+  HIP_TRY(upload0(bs, sidx, N));
+  HIP_TRY(bo.alloc(24 * N));
+  HIP_TRY(br.alloc(4 * N));
+  hipLaunchKernelGGL(k_debug_lens_ray_rng, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, R, f / 1.5f, n, bx.as<int32_t>(), by.as<int32_t>(),
+                     bs.as<uint32_t>(), bo.as<float>(), br.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 24 * N, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rng_out, br.p, 4 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 }  // extern "C"

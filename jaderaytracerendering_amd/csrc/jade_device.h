@@ -23,6 +23,7 @@
 // shaded vertex, not once per intersection test).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "jade_fpmath.h"
@@ -168,6 +169,8 @@ struct PathState {
   float4* ctx;
   float4* aux;          // [npix] {aux.xyz, auxi}
   float eye[3];         // origin of every camera ray (skip == JADE_SKIP_CAMERA): not stored per record
+  float lens_k;         // thin lens (include/jade_bvh.h, "The lens, stated"): focus_distance / 1.5f, 0 for the pinhole.  It sits in what was
+                        // padding before the next pointer: no other field moves, and only the lens kernels read it
   float4* orgs;         // [npix] {origin shared by this record's pending rays, source triangle of those rays (int bits)}
   // Ray slots, two float4 per slot and a record's slots side by side: slot[(p * nslots + k) * 2] = {direction, hit (int bits:
   // -2 inactive, -1 queued / miss, >= 0 triangle)}, [.. + 1] = {hit point, HitResult.distance of the best hit as k_trace
@@ -230,8 +233,12 @@ struct RenderConst {
   uint32_t frame;
   float eye[3];
   float cam[16];
+  float lens_radius;  // thin lens: the aperture radius A, 0 for the pinhole (with PathState.lens_k); in what was padding before the doubles
   double two_over_w, two_over_h, aspect;
 };
+// (the kernels at their register limits take both structs by value: their arguments must stay where they are)
+static_assert(sizeof(RenderConst) == 120 && offsetof(RenderConst, two_over_w) == 96, "RenderConst: the lens radius fills padding, nothing moves");
+static_assert(offsetof(PathState, lens_k) == 76 && offsetof(PathState, orgs) == 80, "PathState: lens_k fills padding, nothing moves");
 
 // Work counters are sharded: a block adds into shard blockIdx % JADE_CTR_SHARDS
 // (one 64-B line each) so that a million waves do not serialise on one address
@@ -295,6 +302,37 @@ static __device__ __forceinline__ jvec3 camera_ray_dir(const RenderConst& R, int
   float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
   jvec3 dir = jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, R.cam);
   return jv_normalize(dir);
+}
+
+// The thin-lens ray (include/jade_bvh.h, "The lens, stated"; non-parity) of the jitter (left_offset, up_offset) - camera_ray_dir's
+// statements give those - and the two lens draws u3, u4: A = aperture radius, k = focus_distance / 1.5f.  One fp32 operation per
+// operation written.  Compiled for the host too: that build is what tests/test_lens_cpu.py holds against the float64 statement.
+static __host__ __device__ __forceinline__ void lens_ray(const float* cam, const float* eye, float A, float k, float left_offset, float up_offset,
+                                                         float u3, float u4, jvec3* origin, jvec3* dir) {
+  const float r = A * jade_sqrt(u3);
+  const float phi = (float)(2.0 * JADE_PI_D) * u4;
+  float sn, cs;
+  jade_sincosf(phi, &sn, &cs);
+  const float lx = r * cs, ly = r * sn;  // the lens point (lx, ly, 0) in camera space: uniform over the disk
+  const jvec3 d_c = jv(left_offset * k - lx, up_offset * k - ly, -1.5f * k);  // towards the pinhole ray's point on the plane of focus
+  *dir = jv_normalize(jade_transform(d_c, 0.0f, cam));
+  const jvec3 l = jade_transform(jv(lx, ly, 0.0f), 0.0f, cam);
+  *origin = jv(eye[0] + l.x, eye[1] + l.y, eye[2] + l.z);
+}
+// ... of sample `sidx` of pixel (x, y) under the lens (R.lens_radius, k): camera_ray_dir's seed and jitter draws, then u3, u4.  *rng is left
+// after the four draws.  The statements of shade_record's lens arm (jade_hip.hip); the denoiser's guide pass calls it.
+static __device__ __forceinline__ jvec3 camera_ray_lens(const RenderConst& R, float k, int x, int y, uint32_t sidx, uint32_t* rng, jvec3* origin) {
+  *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
+  float fx = (float)x + jade_rand(rng);
+  double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
+  float left_offset = (float)(lo * R.aspect);
+  float fy = (float)y + jade_rand(rng);
+  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  const float u3 = jade_rand(rng);
+  const float u4 = jade_rand(rng);
+  jvec3 dir;
+  lens_ray(R.cam, R.eye, R.lens_radius, k, left_offset, up_offset, u3, u4, origin, &dir);
+  return dir;
 }
 
 // ACESToneMapping (or the preview's Reinhard operator) + gamma + BGR pack of one pixel's linear colour m, PathTrace.cu:669-682,

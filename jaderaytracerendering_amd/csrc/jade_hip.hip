@@ -211,7 +211,8 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // the sky and pure mirrors: it hands every other record to the full kernel through `defer`
 // (either untouched, or parked at ST_VERTEX with its path state stored).  Same statements either
 // way: the lean paths are the shared helpers consume_mirror / begin_bounce_lean / bounce_mirror.
-template <bool LEAN, bool ENVIS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the k_shade*_lens kernels only)
+template <bool LEAN, bool ENVIS = false, bool LENS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer) {
   const int npix = P.npix;
@@ -363,9 +364,20 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         float left_offset = (float)(lo * R.aspect);
         float fy = (float)y + jade_rand(&c.rng);
         float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
-        jvec3 dir = jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, R.cam);
-        dir = jv_normalize(dir);
-        reinterpret_cast<int*>(P.orgs + p)[3] = JADE_SKIP_CAMERA;  // no source triangle, and the origin is the eye: k_trace takes it from P.eye
+        jvec3 dir;
+        if (LENS) {
+          // two more draws before any draw of the path, and an origin of the ray's own: stored with "no source triangle" (-1), which
+          // shade_tail, k_trace's refill and k_ray_keys read as they read jade_trace_rays' rays
+          const float u3 = jade_rand(&c.rng);
+          const float u4 = jade_rand(&c.rng);
+          jvec3 org;
+          lens_ray(R.cam, R.eye, R.lens_radius, P.lens_k, left_offset, up_offset, u3, u4, &org, &dir);
+          px.set_origin(org, -1);
+        } else {
+          dir = jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, R.cam);
+          dir = jv_normalize(dir);
+          reinterpret_cast<int*>(P.orgs + p)[3] = JADE_SKIP_CAMERA;  // no source triangle, and the origin is the eye: k_trace takes it from P.eye
+        }
         px.set_dir(0, dir);
         px.set_hit(0, -1);
         c.n_emit_rays = 1;
@@ -512,7 +524,7 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-template <bool ENVIS>
+template <bool ENVIS, bool LENS = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
@@ -534,7 +546,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS>(S, P, R, tile_ids, target_spp, p, c, st, defer);
+  shade_record<false, ENVIS, LENS>(S, P, R, tile_ids, target_spp, p, c, st, defer);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -549,6 +561,19 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_en
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below) {
   shade_kernel_body<true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
+}
+// ... and under a thin lens (jade_scene_set_lens, non-parity): the kernels that carry the lens ray, with either environment sampling
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below) {
+  shade_kernel_body<false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_envis_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below) {
+  shade_kernel_body<true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -834,6 +859,19 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean(DevScene S, Path
   uint32_t st;
   bool defer;
   shade_record<true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
+  shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
+}
+// ... under a thin lens: the same kernel with the lens ray in its camera arm
+__global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                                                      uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
+                                                                      QueueCtl* qc, DevCounters* ctr) {
+  const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  ShadeCtx c;
+  c.n_emit_rays = 0;
+  c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
+  uint32_t st;
+  bool defer;
+  shade_record<true, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 
@@ -2066,6 +2104,25 @@ void jade_scene_destroy(jade_scene* s) {
   delete s;
 }
 
+// The thin lens of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_lens(jade_scene* s, const jade_lens_params* lens) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (!lens) {
+    s->lens = jade_lens_params{};
+    return JADE_OK;
+  }
+  if (!std::isfinite(lens->aperture_radius) || !(lens->aperture_radius >= 0.0f)) return jade_fail(JADE_ERR_INVALID, "aperture_radius must be finite and >= 0");
+  if (lens->aperture_radius > 0.0f && (!std::isfinite(lens->focus_distance) || !(lens->focus_distance > 0.0f)))
+    return jade_fail(JADE_ERR_INVALID, "focus_distance must be finite and > 0 with an open aperture");
+  s->lens = *lens;
+  return JADE_OK;
+}
+int jade_scene_get_lens(jade_scene* s, jade_lens_params* out) {
+  if (!s || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *out = s->lens;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -2204,6 +2261,9 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   R.two_over_w = 2.0 / (double)rp->width;
   R.two_over_h = 2.0 / (double)rp->height;
   R.aspect = (double)rp->width / (double)rp->height;
+  // the scene's lens as it is now: the render keeps it whatever jade_scene_set_lens is told before the next begin
+  R.lens_radius = s->lens.aperture_radius > 0.0f ? s->lens.aperture_radius : 0.0f;
+  const float lens_k = R.lens_radius > 0.0f ? s->lens.focus_distance / 1.5f : 0.0f;  // k of the statement: one float division
   s->spp_done = 0;
   s->tail_pending = false;
   s->carried_active = 0;
@@ -2217,6 +2277,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->ps.early_exit = rp->walk == JADE_WALK_EARLY_EXIT_CACHED ? 2u : rp->walk == JADE_WALK_EARLY_EXIT ? 1u : 0u;
   s->ps.env_sampling = rp->env_sampling == JADE_ENV_IMPORTANCE ? 1u : 0u;
   memcpy(s->ps.eye, rp->eye, sizeof s->ps.eye);
+  s->ps.lens_k = lens_k;  // (setup_state wrote the record layout into s->ps)
   HIP_TRY(upload(s->b_tiles, s->tile_ids.data(), s->tile_ids.size(), s->stream));
   HIP_TRY(hipMemsetAsync(s->b_ctr.p, 0, sizeof(DevCounters) * JADE_CTR_SHARDS, s->stream));
   hipLaunchKernelGGL(k_init, dim3((unsigned)((npix64 + 255) / 256)), dim3(256), 0, s->stream, s->ps);
@@ -2333,11 +2394,17 @@ static int account_pending_trace(PassRun& r) {
   return account_trace(r, r.ev(PassRun::TA), r.ev(PassRun::TB));
 }
 
+// A render under a thin lens (jade_scene_set_lens; taken by jade_render_begin) runs the lens kernels: k_shade_lean_lens + k_shade_lens /
+// k_shade_envis_lens + k_trace, the schedule JADE_FUSED=0 JADE_TAIL=0 gives the pinhole.  k_light, k_light_packet, k_tail and
+// k_shade_binned have no lens form, so JADE_FUSED, JADE_LIGHT_PACKET, JADE_TAIL and JADE_SHADE_BINNED have no effect there.
+static bool lens_on(const jade_scene* s) { return s->rc.lens_radius > 0.0f; }
+static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !lens_on(s); }
+
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
 // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.
 static int arm_step(PassRun& r, int64_t from_spp) {
   jade_scene* s = r.s;
-  if (s->tun.fused && s->ps.stride == 0 && (int64_t)r.target_spp - from_spp >= (int64_t)s->ps.rpp) {
+  if (fused_first_pass(s) && s->ps.stride == 0 && (int64_t)r.target_spp - from_spp >= (int64_t)s->ps.rpp) {
     r.n_active = (uint32_t)s->ps.npix;
   } else if ((int64_t)r.target_spp == from_spp && s->carried_active > 0 && s->tun.batching && !s->sort_rays && !s->tun.log_passes && s->ps.stride == 0) {
     // A flush: no sample is started, so the records with work are exactly the ones the last step carried over, and the host knows
@@ -2493,7 +2560,7 @@ static int shade_pass(PassRun& r, bool lean_mode) {
   jade_scene* s = r.s;
   QueueCtl* qc = r.qc;
   const bool log_passes = s->tun.log_passes;
-  const bool first_fused = lean_mode && s->tun.fused && r.pass_no == 0;
+  const bool first_fused = lean_mode && fused_first_pass(s) && r.pass_no == 0;
   if (!lean_mode && !r.have_list) {
     r.cur = 0;
     if (int rc = launch_arm(s, r.target_spp, qc, 16)) return rc;
@@ -2515,7 +2582,7 @@ static int shade_pass(PassRun& r, bool lean_mode) {
     r.cur = 0;
   } else if (lean_mode) {
     // b_active[1] carries the hand-over list; no active list is kept in this mode
-    hipLaunchKernelGGL(k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
+    hipLaunchKernelGGL(lens_on(s) ? k_shade_lean_lens : k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
                        s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(),
                        s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
     if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
@@ -2634,8 +2701,9 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   // k_shade with the records dealt by branch through LDS (k_shade_binned), unless switched off - or the render draws its
   // environment rays by importance: a bounce may then emit no ray at all and is folded in on the spot, which the binned form does not do
   r.shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
+  if (lens_on(s)) r.shade_kernel = s->ps.env_sampling ? k_shade_envis_lens : k_shade_lens;
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling;  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !lens_on(s);  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   while (r.n_active && !r.done) {
     const bool lean_mode = s->tun.shade_split && (uint64_t)r.n_active * 4 >= (uint64_t)s->ps.npix;

@@ -122,6 +122,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   if (rp->spp <= 0 || rp->width <= 0 || rp->height <= 0) return jade_fail(JADE_ERR_INVALID, "bad image size or spp");
   for (int i = 0; i < ndev; ++i)
     if (!scenes[i]) return jade_fail(JADE_ERR_INVALID, "null scene");
+  // one frame, one camera: every share is rendered under the same lens (jade_scene_set_lens), bit for bit
+  for (int i = 1; i < ndev; ++i)
+    if (memcmp(&scenes[i]->lens, &scenes[0]->lens, sizeof(jade_lens_params)) != 0)
+      return jade_fail(JADE_ERR_INVALID, "the scenes carry different lenses (jade_scene_set_lens): scene " + std::to_string(i) + " against scene 0");
   // 1. every device renders its share (one host thread each) and resolves it into a device buffer
   std::vector<int> rcs(ndev, JADE_OK);
   std::vector<std::string> msgs(ndev);

@@ -175,6 +175,7 @@ struct jade_scene {
   bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
   int n_emit = 0;
   int bvh_depth = 0;
+  jade_lens_params lens{};    // jade_scene_set_lens: what the next jade_render_begin takes (the render in progress keeps its own: rc.lens_radius, ps.lens_k)
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;

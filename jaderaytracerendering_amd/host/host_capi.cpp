@@ -1,5 +1,6 @@
 // host_capi.cpp — C entry points over the host scene pipeline, for the CLI,
 // the Python bindings (ctypes) and the tests.  Declared in jade_host_c.h.
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -202,6 +203,28 @@ void jadeh_transform_matrix(const float rot_deg[3], const float trans[3], const 
 }
 void jadeh_camera_orbit(float r, float up_deg, float rot_deg, const float center[3], float eye_out[3], float cam_out[16]) {
   camera_orbit(r, up_deg, rot_deg, center, eye_out, cam_out);
+}
+
+int jadeh_focus_distance(jadeh_trace_rays_fn trace_rays, jade_scene* scene, const jade_render_params* p, int px, int py, float* out) {
+  if (!trace_rays || !scene || !p || !out) return fail("focus_distance: bad arguments");
+  if (p->width <= 0 || p->height <= 0 || px < 0 || py < 0 || px >= p->width || py >= p->height) return fail("focus_distance: pixel outside the frame");
+  // the camera ray's statements (PathTrace.cu:1428-1437) with 0.5 for both jitter draws
+  const double aspect = (double)p->width / (double)p->height;
+  const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
+  const float left_offset = (float)((-1.0 + 2.0 / (double)p->width * ((double)fx - 0.5)) * aspect);
+  const float up_offset = (float)(-1.0 + 2.0 / (double)p->height * ((double)fy - 0.5));
+  const jvec3 d = jv_normalize(jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, p->camera));
+  const float o3[3] = {p->eye[0], p->eye[1], p->eye[2]}, d3[3] = {d.x, d.y, d.z};
+  const int32_t skip = -1;
+  int32_t hit = -1;
+  float dist = 0.0f, point[3] = {0, 0, 0};
+  jade_stats st;
+  memset(&st, 0, sizeof st);
+  if (trace_rays(scene, 1, o3, d3, &skip, &hit, &dist, point, &st) != JADE_OK) return fail("focus_distance: jade_trace_rays failed");
+  if (hit < 0) return fail("focus_distance: pixel (" + std::to_string(px) + ", " + std::to_string(py) + ") sees no surface");
+  const double len = std::sqrt((double)left_offset * left_offset + (double)up_offset * up_offset + 2.25);
+  *out = (float)((double)dist * 1.5 / len);
+  return 0;
 }
 
 int jadeh_write_bmp(const char* path, const uint8_t* bgr, int w, int h) { return write_bmp(path, bgr, w, h) ? 0 : fail("write_bmp failed"); }

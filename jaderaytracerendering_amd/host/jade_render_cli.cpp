@@ -18,6 +18,7 @@
 
 #include "jade_bvh.h"
 #include "jade_host.hpp"
+#include "jade_host_c.h"
 
 using namespace jadehost;
 
@@ -43,6 +44,9 @@ struct Api {
   void (*glare_defaults)(jade_glare_params*) = nullptr;
   int (*glare_image)(int, int32_t, int32_t, const float*, const jade_glare_params*, float*) = nullptr;
   int (*render_glare)(jade_scene*, const jade_glare_params*, const jade_display_params*, float*, uint8_t*, float*) = nullptr;
+  // ... and only for --aperture (jade_trace_rays: --focus-at)
+  int (*scene_set_lens)(jade_scene*, const jade_lens_params*) = nullptr;
+  jadeh_trace_rays_fn trace_rays = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -88,6 +92,11 @@ static void usage() {
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
+          "                   [--aperture A (--focus D | --focus-at PX,PY)]\n"
+          "  --aperture A: a thin lens of radius A >= 0 (scene units) instead of the pinhole: depth of field (HIP backend only; NOT the\n"
+          "                reference's samples; include/jade_bvh.h).  It needs exactly one of --focus D, the depth D > 0 of the plane of focus\n"
+          "                along the camera's axis, and --focus-at PX,PY, which focuses on what the centre of pixel (PX, PY) shows (row 0 =\n"
+          "                the bottom row) and prints the distance found; onto the sky it exits 1\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -125,6 +134,8 @@ int main(int argc, char** argv) {
   std::string histogram;
   bool use_glare = false, have_glare_levels = false, have_glare_falloff = false;
   double glare_strength = 0.0, glare_levels = 6, glare_falloff = 0.5;
+  bool use_aperture = false, have_focus = false, have_focus_at = false;
+  double aperture = 0.0, focus = 0.0, focus_px = 0, focus_py = 0;
   auto number = [](const char* flag, const char* v) {
     char* end = nullptr;
     const double x = strtod(v, &end);
@@ -172,6 +183,16 @@ int main(int argc, char** argv) {
     else if (a == "--glare") { glare_strength = number("--glare", need("--glare")); use_glare = true; }
     else if (a == "--glare-levels") { glare_levels = number("--glare-levels", need("--glare-levels")); have_glare_levels = true; }
     else if (a == "--glare-falloff") { glare_falloff = number("--glare-falloff", need("--glare-falloff")); have_glare_falloff = true; }
+    else if (a == "--aperture") { aperture = number("--aperture", need("--aperture")); use_aperture = true; }
+    else if (a == "--focus") { focus = number("--focus", need("--focus")); have_focus = true; }
+    else if (a == "--focus-at") {
+      const std::string v = need("--focus-at");
+      const size_t comma = v.find(',');
+      if (comma == std::string::npos) { fprintf(stderr, "--focus-at: expected PX,PY: %s\n", v.c_str()); return 2; }
+      focus_px = number("--focus-at", v.substr(0, comma).c_str());
+      focus_py = number("--focus-at", v.substr(comma + 1).c_str());
+      have_focus_at = true;
+    }
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
@@ -186,6 +207,14 @@ int main(int argc, char** argv) {
   if (!(glare_strength >= 0.0 && glare_strength <= 1.0)) { fprintf(stderr, "--glare must be within 0 .. 1\n"); return 2; }
   if (!(glare_levels >= 1 && glare_levels <= 12 && glare_levels == (int)glare_levels)) { fprintf(stderr, "--glare-levels must be a whole number 1 .. 12\n"); return 2; }
   if (!((float)glare_falloff > 0.0f) || !std::isfinite((float)glare_falloff)) { fprintf(stderr, "--glare-falloff must be > 0\n"); return 2; }
+  if ((have_focus || have_focus_at) && !use_aperture) { fprintf(stderr, "--focus and --focus-at belong to --aperture\n"); return 2; }
+  if (use_aperture && have_focus == have_focus_at) { fprintf(stderr, "--aperture needs exactly one of --focus D and --focus-at PX,PY\n"); return 2; }
+  if (use_aperture && (!(aperture >= 0.0) || !std::isfinite((float)aperture))) { fprintf(stderr, "--aperture must be >= 0\n"); return 2; }
+  if (have_focus && (!((float)focus > 0.0f) || !std::isfinite((float)focus))) { fprintf(stderr, "--focus must be > 0\n"); return 2; }
+  if (have_focus_at && !(focus_px >= 0 && focus_py >= 0 && focus_px <= (1 << 30) && focus_py <= (1 << 30) && focus_px == (int)focus_px && focus_py == (int)focus_py)) {
+    fprintf(stderr, "--focus-at needs two whole numbers PX,PY >= 0\n");
+    return 2;
+  }
   if (config.empty() == args_file.empty()) { usage(); return 2; }
   if (backend.empty()) {
     char self[4096];
@@ -226,6 +255,10 @@ int main(int argc, char** argv) {
   if (width > 0) cfg.width = width;
   if (height > 0) cfg.height = height;
   if (spp > 0) cfg.spp = spp;
+  if (have_focus_at && (focus_px >= cfg.width || focus_py >= cfg.height)) {
+    fprintf(stderr, "--focus-at %d,%d lies outside the %d x %d frame\n", (int)focus_px, (int)focus_py, cfg.width, cfg.height);
+    return 2;
+  }
   if (use_adaptive && min_spp > cfg.spp) { fprintf(stderr, "--min-spp %d is above the cap --spp %d\n", min_spp, cfg.spp); return 2; }
 
   printf("Model load done:  %d Triangles.\n", builder.triangle_count());
@@ -253,6 +286,14 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (use_aperture) {
+    *(void**)(&api.scene_set_lens) = dlsym(api.h, "jade_scene_set_lens");
+    *(void**)(&api.trace_rays) = dlsym(api.h, "jade_trace_rays");
+    if (!api.scene_set_lens || !api.trace_rays) {
+      fprintf(stderr, "--aperture needs the HIP backend: %s has no jade_scene_set_lens\n", backend.c_str());
+      return 2;
+    }
+  }
   // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
   const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
   if (need_display) {
@@ -277,6 +318,20 @@ int main(int argc, char** argv) {
   rp.device_id = device;
   rp.walk = reference_walk ? JADE_WALK_REFERENCE : JADE_WALK_EARLY_EXIT;
   rp.env_sampling = env_importance ? JADE_ENV_IMPORTANCE : JADE_ENV_REFERENCE;  // (non-parity: another estimator of the same image; HIP backend only)
+  if (use_aperture) {
+    jade_lens_params lens;
+    lens.aperture_radius = (float)aperture;
+    lens.focus_distance = (float)focus;
+    if (have_focus_at) {
+      if (jadeh_focus_distance(api.trace_rays, dev, &rp, (int)focus_px, (int)focus_py, &lens.focus_distance) != 0) {
+        fprintf(stderr, "--focus-at: %s\n", jadeh_last_error());
+        return 1;
+      }
+      printf("focus: pixel (%d, %d) is %.9g away along the axis\n", (int)focus_px, (int)focus_py, lens.focus_distance);
+    }
+    if (api.scene_set_lens(dev, &lens) != JADE_OK) { fprintf(stderr, "lens: %s\n", api.last_error()); return 1; }
+    printf("lens: aperture radius %.9g, focus distance %.9g\n", lens.aperture_radius, lens.focus_distance);
+  }
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
   jade_stats st;
