@@ -53,7 +53,7 @@ extern "C" {
 /* Fixed constants of the integrator (PathTrace.cu:32-39); not parameters. */
 #define JADE_TILE_SIZE 16
 #define JADE_STACK_CAPACITY 128     /* bounce pushes per sample */
-#define JADE_BVH_STACK_CAPACITY 128 /* traversal stack entries */
+#define JADE_BVH_STACK_CAPACITY 128 /* traversal stack entries: a BVH of up to 127 levels (the root is level 1) is accepted, and walked at that depth by tests/test_gpu_deep_trees.py; 128 levels are refused (JADE_ERR_UNSUPPORTED) */
 #define JADE_MAX_FULL_REFLEX_TIME 32
 
 /* Sample scheduling (this ABI's definition; the reference races 31 cuRAND

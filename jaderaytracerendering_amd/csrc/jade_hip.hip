@@ -2191,6 +2191,10 @@ static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lane
     hipLaunchKernelGGL(k_iota, dim3(1024), dim3(256), 0, s->stream, s->b_sortpos.as<uint32_t>(), (uint32_t)std::min<size_t>(cap, 0xffffffffu));
     HIP_TRY(hipGetLastError());
   }
+  // The stack spill area: level k >= JADE_LDS_STACK of thread gtid is word (k - JADE_LDS_STACK) * grid threads + gtid, so the last level an
+  // accepted tree can fill (JADE_BVH_STACK_CAPACITY - 1) ends below these 120 x (k_trace's grid) words for every kernel whose grid is
+  // no larger than k_trace's: k_trace_wide and k_light (size_grids), k_tail (run_passes clamps its list), the guide pass and
+  // jade_trace_rays (launch_trace).  tests/test_gpu_deep_trees.py::test_grids_stay_within_the_spill_area holds the grids to it.
   if (!s->b_spill.p)
     HIP_TRY(s->b_spill.alloc((size_t)(JADE_BVH_STACK_CAPACITY - JADE_LDS_STACK) * s->trace_blocks * JADE_TRACE_BLOCK * 4));
   return JADE_OK;
@@ -2705,6 +2709,8 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
   r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !lens_on(s);  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
+  // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
+  r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);
   while (r.n_active && !r.done) {
     const bool lean_mode = s->tun.shade_split && (uint64_t)r.n_active * 4 >= (uint64_t)s->ps.npix;
     const bool list_mode = !lean_mode && r.have_list;
@@ -3055,6 +3061,17 @@ int jade_debug_trace_rays_cached(jade_scene* s, int32_t n, const float* origins,
 int jade_debug_scene_flags(jade_scene* s) {
   if (!s) return -1;
   return (s->boxes_nested ? 1 : 0) | (s->dev.nodes4 ? 2 : 0) | (s->dev.anyhit ? 4 : 0);
+}
+// the persistent grids size_grids chose, in blocks of JADE_TRACE_BLOCK threads: k_trace's, k_trace_wide's, k_light's, k_light_packet's (0: the
+// tree is too deep for the packet form).  The stack spill area holds JADE_BVH_STACK_CAPACITY - JADE_LDS_STACK levels for out[0] blocks:
+// no kernel that is handed the area may be launched with more (setup_state; tests/test_gpu_deep_trees.py).  Host code only.
+int jade_debug_scene_grids(jade_scene* s, int32_t out[4]) {
+  if (!s || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  out[0] = s->trace_blocks;
+  out[1] = s->trace_blocks_wide;
+  out[2] = s->light_blocks;
+  out[3] = s->packet_blocks;
+  return JADE_OK;
 }
 
 // Development / tests (not part of jade_rt.h): shadow_limit (jade_shade.h) for n rays against triangle tri (BVH order): what

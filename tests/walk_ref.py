@@ -1,0 +1,397 @@
+"""Deep trees over a given triangle order, and a model of the stack each form of the walk keeps (jade_trace.h).
+
+Trees.  A leaf is (index, n) over the triangle array as it stands, so ANY recursive split of the triangles is a legal BVH for
+hitBVH (PathTrace.cu:795-859); boxes are min / max of the float32 vertices, so children nest exactly (what the wide walk and the
+occluder cache rest on, jade_scene_prep.hip: boxes_nested).  A tree is written as nested tuples - ("leaf", index, n) or
+("node", left, right), a child None being the reference's "child 0" - and laid out in the 10-word node records the module takes
+(left, right, n, index, aa[3], bb[3]; node 0 a dummy, node 1 the root).  Depth counts the root as level 1, as validate_desc does:
+JADE_BVH_STACK_CAPACITY - 1 = 127 levels are accepted.
+
+  comb(D)              D triangles in planes z = k, one split off per level (the one with the largest z): D levels
+  bushy_comb(D)        ... with a two-level subtree of four single-triangle leaves on the other side at every second level: a wide
+                       unit (node_decide4) on the spine sees four grandchildren and pushes three
+  spine_over(hs, L)    L comb levels on top of a balanced median split of the rest of an existing scene's order
+
+Stacked along z, not x: the reference's barycentric solve takes the x / y components of the projected triangle (PathTrace.cu:736-739),
+so a triangle in a plane x = const met head-on divides 0 by 0 and is never reported - by the oracle and by the kernels alike.
+
+Model.  walk(tree, o, d, skip) restates in float32 numpy what decides the SHAPE of a walk - near child first by d1 < d2, a box
+entered iff the slab value is > 0 (slab below: test_box_monotone._slab with the oracle's NaN rules), no pruning - and returns per ray the node records read (V), the
+triangle tests (T), the leaves in the order met, and the high-water mark of the stack under three rules:
+  ha       the reference's rule (oracle: stack[128]): the far child is deferred whenever both are met.  The figure is the number of
+           entries waiting while the top one is followed - what jade_oracle_stack_histogram counts; the array holds one more
+  hb       the binary unit (node_decide): nothing is pushed when the near child is a leaf that is queued now
+  hb_full  ... and when that leaf finds the lane's FIFO full every time (k_light: node_decide with room = false): one more push,
+           which is rule a again
+  hc       the wide unit, unordered form (node_decide4; wide_records): a node's record holds its four grandchildren - a child that is a
+           leaf fills one slot, its twin slot is empty - the first box met in slot order is next, the others met are pushed so that
+           they come off in slot order: up to three pushes for two levels.  A walk that starts from the occluder cache's four
+           subtrees (anyhit_seed) has three more entries under it: WIDE_CACHED_EXTRA.  `roomy` and `leaf_now` move a pop from one
+           unit to the next and change no height, so the model leaves them out.
+"""
+import re
+
+import numpy as np
+
+from jaderaytracerendering_amd import host as H
+from jaderaytracerendering_amd.host import HostScene
+
+LDS_STACK = 8            # JADE_LDS_STACK: levels in a lane's LDS column; level k >= 8 is spill[(k - 8) * stride + gtid]
+STACK_CAPACITY = 128     # JADE_BVH_STACK_CAPACITY
+PACKET_MAX_DEPTH = 63    # JADE_PACKET_MAX_DEPTH
+WIDE_CACHED_EXTRA = 3    # anyhit_seed: way 0 is walked, the other three lie under it
+
+
+def wide_fits(depth):    # prepare_scene
+    return 3 * ((depth + 1) // 2) + 1 + 3 <= STACK_CAPACITY
+
+
+def cache_fits(depth):   # prepare_scene
+    return depth + 3 <= STACK_CAPACITY - 1
+
+
+# ------------------------------------------------------------------------------------------------------------- trees --
+
+def leaf(index, n=1):
+    return ("leaf", int(index), int(n))
+
+
+def node(left, right):
+    return ("node", left, right)
+
+
+def tree_depth(t):
+    """Levels, the root being level 1 (validate_desc)."""
+    best, todo = 0, [(t, 1)]
+    while todo:
+        t, lv = todo.pop()
+        best = max(best, lv)
+        if t[0] == "node":
+            todo += [(c, lv + 1) for c in t[1:] if c is not None]
+    return best
+
+
+def tree_nodes(tree, verts):
+    """The (N, 10) uint32 node array of `tree` over the (nT, 3, 3) float32 vertices: boxes bottom-up by min / max."""
+    recs = [None, None]  # [left, right, n, index, aa, bb]; 0: the dummy, 1: the root
+
+    def emit(t, me):
+        if t[0] == "leaf":
+            p = verts[t[1]:t[1] + t[2]].reshape(-1, 3)
+            recs[me] = [0, 0, t[2], t[1], p.min(0), p.max(0)]
+            return
+        ids = []
+        for c in t[1:]:
+            if c is None:
+                ids.append(0)
+            else:
+                recs.append(None)
+                ids.append(len(recs) - 1)
+        for c, i in zip(t[1:], ids):
+            if c is not None:
+                emit(c, i)
+        kids = [recs[i] for i in ids if i > 0]
+        recs[me] = [ids[0], ids[1], 0, 0, np.min([k[4] for k in kids], 0), np.max([k[5] for k in kids], 0)]
+
+    emit(tree, 1)
+    nodes = np.zeros((len(recs), 10), np.uint32)
+    ni, nf = nodes.view(np.int32), nodes.view(np.float32)
+    for i, r in enumerate(recs[1:], 1):
+        ni[i, :4] = r[:4]
+        nf[i, 4:7], nf[i, 7:10] = r[4], r[5]
+    return nodes
+
+
+def with_tree(hs, tree):
+    """A copy of the scene with only "nodes" replaced."""
+    arrays = {k: np.array(v, copy=True) for k, v in hs.a.items()}
+    arrays["nodes"] = tree_nodes(tree, hs.vertices())
+    return HostScene(arrays, tree_depth(tree), 0.0)
+
+
+def _plane_triangles(z, seed):
+    """One triangle per entry of z, in the plane z = z[k]: the same footprint (|x| <= 1, |y| <= 1, the apex up) moved about by up to
+    0.15, so that every ray along z through the core |x| < 0.25, -0.5 < y < 0 meets every one of them."""
+    rng = np.random.default_rng(seed)
+    n = len(z)
+    j = ((rng.random((n, 2)) - 0.5) * 0.3).astype(np.float32)
+    v = np.zeros((n, 3, 3), np.float32)
+    v[:, 0, :2], v[:, 1, :2], v[:, 2, :2] = j + np.float32([-1, -1]), j + np.float32([1, -1]), j + np.float32([0, 1])
+    v[:, :, 2] = np.asarray(z, np.float32)[:, None]
+    return v
+
+
+def _mesh_scene(verts):
+    b = H.SceneBuilder()
+    try:
+        b.add_mesh(verts.reshape(-1, 3), np.arange(3 * len(verts), dtype=np.int32).reshape(-1, 3), H.material(brdf=(0.5,) * 3))
+        b.set_env_sky(16, 8)
+        return b.build()
+    finally:
+        b.close()
+
+
+def _by_z(hs):
+    """Triangle indices of the scene as it stands, by increasing z (the builder's order is its own)."""
+    z = hs.vertices()[:, 0, 2]
+    order = np.argsort(z, kind="stable")
+    assert (np.diff(z[order]) > 0).all() and (hs.vertices()[:, :, 2] == z[:, None]).all()
+    return [int(i) for i in order]
+
+
+def comb(D, missing=0, seed=1):
+    """D levels, D triangles in the planes z = 0 .. D - 1: the node at level j has the triangle with the largest z left as one child
+    (on either side, by a coin per level) and the comb over the others as the other.  A ray along +z from below meets the comb
+    first and the leaf second at every level - D - 2 entries under rule b - and a ray along -z a leaf first, every time.
+    missing = m: every m-th spine leaf is dropped (child index 0): the module's general walk."""
+    hs = _mesh_scene(_plane_triangles(np.arange(D), seed))
+    tri = _by_z(hs)
+    coin = np.random.default_rng(seed + 100).integers(0, 2, D)
+    t = node(leaf(tri[1]), leaf(tri[0])) if coin[D - 1] else node(leaf(tri[0]), leaf(tri[1]))
+    for level in range(D - 2, 0, -1):  # the node at `level` splits off triangle D - level
+        lf = leaf(tri[D - level]) if not (missing and level % missing == 0) else None
+        t = node(lf, t) if coin[level] else node(t, lf)
+    out = with_tree(hs, t)
+    assert out.bvh_depth == D
+    return out
+
+
+def bushy_comb(D, seed=2):
+    """D levels.  The spine node at level l (l = 1, 3, 5 ...) has, left, a node whose children are the spine's next node (level
+    l + 2) and a leaf and, right, a subtree of four single-triangle leaves on two levels: its wide record holds four grandchildren,
+    the spine in slot 0, and a ray along z meets all of them - three pushes for two levels.  z falls with the level."""
+    z = []
+
+    def take(zv):
+        z.append(zv)
+        return len(z) - 1
+
+    def spine(l, c):  # c: the z of this stretch
+        r = D - l
+        if r == 1:
+            return node(leaf(take(c)), leaf(take(c + 0.5)))
+        if r == 2:
+            return node(node(leaf(take(c)), leaf(take(c + 0.3))), leaf(take(c + 0.6)))
+        lone = leaf(take(c))
+        bush = node(node(leaf(take(c + 0.2)), leaf(take(c + 0.4))), node(leaf(take(c + 0.6)), leaf(take(c + 0.8))))
+        return node(node(spine(l + 2, c - 1.0), lone), bush)
+
+    t = spine(1, float(D))
+    hs = _mesh_scene(_plane_triangles(z, seed))
+    # the tree names triangles by their number in z[]; the scene's order is the builder's
+    zs = hs.vertices()[:, 0, 2]
+    where = {float(np.float32(v)): i for i, v in enumerate(zs)}
+    assert len(where) == len(z)
+
+    def rename(t):
+        if t[0] == "leaf":
+            return leaf(where[float(np.float32(z[t[1]]))])
+        return node(rename(t[1]), rename(t[2]))
+
+    out = with_tree(hs, rename(t))
+    assert out.bvh_depth == D
+    return out
+
+
+def _balanced(lo, hi, leaf_size):
+    if hi - lo <= leaf_size:
+        return leaf(lo, hi - lo)
+    mid = (lo + hi) // 2
+    return node(_balanced(lo, mid, leaf_size), _balanced(mid, hi, leaf_size))
+
+
+def spine_over(hs, L, missing=0, peel=3, leaf_size=4):
+    """L comb levels on top of a balanced median split (by index, leaves of up to leaf_size triangles) of the rest of the scene's
+    order: level j splits the next `peel` triangles of the order off as one leaf (the builders' orders keep neighbours together, so
+    such a leaf has a box of some size, and a ray through the first object meets many of them: test_walk_ref_cpu.py).  The scene
+    keeps its triangles, materials, emitters and environment."""
+    assert 1 <= peel <= 15 and L * peel < hs.n_triangles
+    t = _balanced(L * peel, hs.n_triangles, leaf_size)
+    for j in range(L, 0, -1):
+        lf = leaf((j - 1) * peel, peel) if not (missing and j % missing == 0) else None
+        t = node(lf, t) if j % 3 else node(t, lf)
+    return with_tree(hs, t)
+
+
+def spine_to_depth(hs, depth, peel=3, leaf_size=4):
+    """spine_over with as many comb levels as make the tree `depth` levels deep."""
+    for L in range(depth):
+        if L * peel < hs.n_triangles and tree_depth(_balanced(L * peel, hs.n_triangles, leaf_size)) + L == depth:
+            out = spine_over(hs, L, peel=peel, leaf_size=leaf_size)
+            assert out.bvh_depth == depth
+            return out
+    raise ValueError(f"no spine makes {depth} levels")
+
+
+# -------------------------------------------------------------------------------------------------------------- rays --
+
+def comb_rays(hs, seed=3):
+    """Seven packets of 64 for a tree over _plane_triangles: 0 the +z bundle (every box met, the comb first: the greatest height);
+    1 the -z bundle (a leaf first at every step); 2 origins spread along the comb, up and down (a wave holds every height at once);
+    3 tilted rays that leave the comb half-way; 4 rays that start on a triangle and skip it; 5 axis-parallel rays, some of them
+    from a triangle's own plane (0 * inf: the NaN-faithful unit) among ordinary ones; 6 the +z bundle again, every fourth lane
+    starting under the last few planes (a stack that stays in LDS beside 48 that spill)."""
+    rng = np.random.default_rng(seed)
+    v = hs.vertices()
+    z = v[:, 0, 2]
+    z0, z1 = float(z.min()), float(z.max())
+    n = 64 * 7
+    o, d = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+    skip = np.full(n, -1, np.int32)
+    core = lambda k: np.stack([rng.uniform(-0.25, 0.25, k), rng.uniform(-0.5, 0.0, k)], 1)  # noqa: E731
+    tilt = lambda k: rng.uniform(2e-4, 1e-3, (k, 2)) * rng.choice([-1.0, 1.0], (k, 2)) * 25.0 / max(z1 - z0, 25.0)  # noqa: E731
+    for p in range(7):
+        s = slice(64 * p, 64 * p + 64)
+        o[s, :2], d[s, :2], d[s, 2] = core(64), tilt(64), 1.0
+        o[s, 2] = z0 - 1.0 - rng.random(64)
+    o[64:128, 2] = z1 + 1.0 + rng.random(64)
+    d[64:128, 2] = -1.0
+    o[128:192, 2] = rng.uniform(z0 - 1, z1 + 1, 64)
+    d[128:192, 2] = rng.choice([-1.0, 1.0], 64)
+    reach = rng.uniform(0.3, 0.7, 64) * (z1 - z0 + 1)
+    d[192:256, 0] = rng.choice([-1.0, 1.0], 64) * 1.3 / reach
+    d[192:256, 1] = rng.uniform(-0.3, 0.3, 64) / reach
+    k = rng.integers(0, len(v), 64)
+    o[256:320] = v[k].mean(1)
+    d[256:320, 2] = rng.choice([-1.0, 1.0], 64)
+    skip[256:320] = k
+    d[320:352, :2] = 0.0                                       # along z exactly: 1 / 0 = inf in x and y
+    d[352:360] = [1, 0, 0]
+    d[360:368] = [0, -1, 0]
+    o[352:368] = v[rng.integers(0, len(v), 16)].mean(1)        # ... in a triangle's own plane: (z - o.z) * inf = NaN
+    o[368:376, 2] = z[rng.integers(0, len(v), 8)]
+    d[368:376] = [0.3, 0.1, 0]
+    o[384 + 3:448:4, 2] = rng.uniform(max(z1 - 8.0, z0 - 1.0), z1 - 1.0, 16)
+    return np.ascontiguousarray(o), np.ascontiguousarray(d), skip
+
+
+# ------------------------------------------------------------------------------------------------------------- model --
+
+def slab(aa, bb, o, d):
+    """hitAABB (PathTrace.cu:758-771) in float32 for the boxes aa, bb [N, 3] and one ray: test_box_monotone._slab, whose reductions
+    are written for rays without a NaN, with the reductions as the oracle and the kernels have them - tmax / tmin by the reference's
+    ternaries (a NaN goes to the second operand), then fminf / fmaxf, which DROP a NaN operand (jade_fpmath.h) - so that the model
+    also follows the rays that take the NaN-faithful unit.  The same values wherever no NaN occurs (test_walk_ref_cpu.py)."""
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        inv = (np.float32(1.0) / d).astype(np.float32)
+        f = ((bb - o) * inv).astype(np.float32)
+        n = ((aa - o) * inv).astype(np.float32)
+        tmax = np.where(f > n, f, n)
+        tmin = np.where(f < n, f, n)
+        fmin = lambda a, b: np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.where(b < a, b, a)))  # noqa: E731
+        fmax = lambda a, b: np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.where(b > a, b, a)))  # noqa: E731
+        t1 = fmin(tmax[:, 0], fmin(tmax[:, 1], tmax[:, 2]))
+        t0 = fmax(tmin[:, 0], fmax(tmin[:, 1], tmin[:, 2]))
+        return np.where(t1 >= t0, np.where(t0 > 0, t0, t1), np.float32(-1))
+
+
+class Tree:
+    def __init__(self, hs):
+        ni, nf = hs.node_i32(), hs.node_f32()
+        self.left, self.right, self.cnt, self.index = (ni[:, k].tolist() for k in range(4))
+        self.aa, self.bb = nf[:, 4:7].astype(np.float32), nf[:, 7:10].astype(np.float32)
+        internal = [i for i in range(1, len(self.cnt)) if self.cnt[i] <= 0]
+        self.missing_child = any(self.left[i] <= 0 or self.right[i] <= 0 for i in internal)
+
+
+def walk(T, o, d, skip=-1):
+    """One ray through T (a Tree): dict of V, T, leaves (node numbers in the order met), ha, hb, hb_full, and - for a tree without
+    missing children - hc, V_wide (the child records a purely wide walk counts) and wide_leaves (the leaves it meets, in its order:
+    the reference's set for a ray with a finite origin and 1 / d, test_box_monotone.py)."""
+    val = slab(T.aa, T.bb, np.asarray(o, np.float32), np.asarray(d, np.float32))
+    with np.errstate(invalid="ignore"):
+        met = (val > 0).tolist()
+    dist = val.tolist()  # (float32 values as doubles: `<` between them is float32's)
+    left, right, cnt, index = T.left, T.right, T.cnt, T.index
+    out = {}
+
+    # ---- a: hitBVH as the oracle writes it
+    stack, V, Tn, leaves, deepest = [1], 1, 0, [], 0
+    while stack:
+        deepest = max(deepest, len(stack) - 1)
+        top = stack.pop()
+        if cnt[top] > 0:
+            leaves.append(top)
+            Tn += cnt[top] - (1 if index[top] <= skip < index[top] + cnt[top] else 0)
+            continue
+        l, r = left[top], right[top]
+        V += (l > 0) + (r > 0)
+        m1, m2 = l > 0 and met[l], r > 0 and met[r]
+        if m1 and m2:
+            stack += [r, l] if dist[l] < dist[r] else [l, r]
+        elif m1:
+            stack.append(l)
+        elif m2:
+            stack.append(r)
+    out.update(V=V, T=Tn, leaves=leaves, ha=deepest)
+
+    # ---- b: node_decide, with room for the leaf met (k_trace; k_light while its FIFO has room) and without
+    for key, room in (("hb", True), ("hb_full", False)):
+        cur, stack, high, order = 1, [], 0, []
+        while cur is not None:
+            if cnt[cur] > 0:
+                order.append(cur)
+                cur = stack.pop() if stack else None
+                continue
+            l, r = left[cur], right[cur]
+            m1, m2 = l > 0 and met[l], r > 0 and met[r]
+            if m1 and m2:
+                near, far = (l, r) if dist[l] < dist[r] else (r, l)
+                if cnt[near] > 0 and room:
+                    order.append(near)
+                    cur = far
+                else:
+                    stack.append(far)
+                    high = max(high, len(stack))
+                    cur = near
+            elif m1 or m2:
+                cur = l if m1 else r
+            else:
+                cur = stack.pop() if stack else None
+        assert order == leaves, "the binary unit meets the leaves in the reference's order"
+        out[key] = high
+
+    # ---- c: node_decide4 over wide_records
+    if not T.missing_child and cnt[1] <= 0:
+        cur, stack, high, Vw, seen = 1, [], 0, 1, []
+        while cur is not None:
+            if cnt[cur] > 0:
+                seen.append(cur)
+                cur = stack.pop() if stack else None
+                continue
+            slots = []
+            for c in (left[cur], right[cur]):
+                slots += [c, None] if cnt[c] > 0 else [left[c], right[c]]
+            Vw += sum(s is not None for s in slots)
+            hit = [s for s in slots if s is not None and met[s]]
+            if not hit:
+                cur = stack.pop() if stack else None
+                continue
+            stack += hit[:0:-1]  # the others met, last slot first: they come off in slot order
+            high = max(high, len(stack))
+            cur = hit[0]
+        out.update(hc=high, V_wide=Vw, wide_leaves=seen)
+    return out
+
+
+def walk_batch(hs, o, d, skip):
+    T = Tree(hs)
+    return [walk(T, o[i], d[i], int(skip[i])) for i in range(len(o))]
+
+
+# ---------------------------------------------------------------------------------------- the trees the tests share --
+
+TREES = ("comb9", "comb10", "comb11", "comb12", "comb63", "comb64", "comb82", "comb83", "comb124", "comb125", "comb127",
+         "bushy82", "bushy83", "comb100m5")  # shallow to deep, then the special ones
+_cache = {}
+
+
+def deep_tree(name):
+    """(HostScene, (o, d, skip), [walk() of every ray]) of one of TREES, made once."""
+    if name not in _cache:
+        m = re.fullmatch(r"(comb|bushy)(\d+)(?:m(\d+))?", name)
+        D = int(m.group(2))
+        hs = comb(D, missing=int(m.group(3) or 0)) if m.group(1) == "comb" else bushy_comb(D)
+        rays = comb_rays(hs)
+        _cache[name] = (hs, rays, walk_batch(hs, *rays))
+    return _cache[name]
