@@ -113,7 +113,48 @@ typedef struct jade_obj_seg {
 
 /* Everything `render_pixel` reads (PathTrace.cu:1418 + 639-648).  All
  * pointers are host pointers; jade_scene_create copies, the caller keeps
- * ownership. */
+ * ownership.
+ *
+ * What is checked is ranges - every index names an element, every segment
+ * lies inside the array with begin <= end, the tree can be walked - and ONE value
+ * (an object's total area, below).  Beyond that
+ * the arrays are read the way PathTrace.cu reads them, whatever they hold, and
+ * both backends give the same frame.  In particular NOT assumed:
+ *   prefix_area    need not be a running sum.  Per object the BSSRDF search
+ *                  (:1031-1048) bisects [begin_idx, end_idx] with u * prefix[end_idx]
+ *                  and returns the LAST midpoint it looked at (0 for an object of one
+ *                  or two triangles: index_mapping[0]).  The HIP module answers from
+ *                  a table when the object's values are finite, non-negative, below
+ *                  3e38 and non-decreasing; any other object costs it the
+ *                  reference's bisection, ~log2(n) dependent loads per BSSRDF vertex,
+ *                  with the same result.  A comparison with a NaN ends the search at
+ *                  that midpoint (the reference would not return).  One value is
+ *                  more than a search key: an object's total, prefix_area[end_idx],
+ *                  multiplies the radiance that leaves through the object (:1105,
+ *                  :1160).  Not finite, it gives rates of inf and NaN, whose sum
+ *                  depends on the order of summation (the HIP module adds a path's
+ *                  radiance forward, the reference unwinds a stack: same counters,
+ *                  NaN in other pixels), and at u = 0 a search key of NaN.  So
+ *                  jade_scene_create refuses, with JADE_ERR_INVALID in both
+ *                  backends, a scene that has SUB_SURFACE triangles and an object
+ *                  whose total is NaN or +-inf; without such triangles
+ *                  prefix_area is never read by a render.  Radiance that overflows
+ *                  for other reasons (emission or areas near FLT_MAX) is outside the
+ *                  parity statement in the same way.
+ *   index_mapping  need not be a permutation, nor stay inside the object: the exit
+ *                  triangle is index_mapping[midpoint], and its refract_rate,
+ *                  refract_index, norm and obj_idx are that triangle's own.
+ *   emit_indices   is walked as given, one shadow ray per entry and vertex:
+ *                  duplicates are sampled twice, an entry that does not emit adds
+ *                  its zero, an emissive triangle that is not listed lights the
+ *                  scene only where a path hits it, and n_emit = 0 is legal.
+ *   obj_segs       may overlap, and need not cover the triangles whose obj_idx names
+ *                  them: obj_idx only selects the segment to search.
+ *   norm           is used as given - never normalised, re-derived from the
+ *                  vertices or oriented.
+ *   materials      are per TRIANGLE (words 13-27 of the record): neighbouring
+ *                  triangles of one object may differ in every field, the two
+ *                  emissive thresholds (1.4e-5, 1.5e-4) included. */
 typedef struct jade_scene_desc {
   uint32_t abi_version;           /* JADE_ABI_VERSION */
   int32_t n_triangles;            /* nTriangles_dv */

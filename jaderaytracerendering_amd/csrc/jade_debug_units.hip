@@ -1,7 +1,8 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip), the tone curve (tone_pack_bgr8, jade_device.h) and the thin-lens ray (lens_ray,
-// jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py).
+// and its table, env_alias_table, jade_scene_prep.hip), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
+// jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py) and the BSSRDF branch's exit-triangle search (exit_search, jade_shade.h, and
+// its tables, guide_tables, jade_scene_prep.hip; tests/test_area_search_cpu.py, tests/test_gpu_area_search.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
 // (tests/test_gpu_fpmath.py, tests/test_gpu_env_lookup.py, tests/test_gpu_env_importance.py, tests/test_gpu_tone.py, tests/test_tone_spec.py).  Each kernel is elementwise: element i reads
 // row i of its inputs and writes row i of its outputs, nothing else.
@@ -188,6 +189,15 @@ __global__ void k_debug_lens_ray_rng(RenderConst R, float lens_k, int n, const i
   put3(out, 2 * i, o);
   put3(out, 2 * i + 1, d);
   rng_out[i] = rng;
+}
+
+// row i: the BSSRDF branch's exit triangle for the draw u[i] on object obj_idx[i] - the last midpoint, and what S.mapping makes of it
+__global__ void k_debug_exit_search(DevScene S, int n, const int32_t* obj_idx, const float* u, int32_t* middle, int32_t* mapped) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int m = exit_search(S, obj_idx[i], u[i]);
+  middle[i] = m;
+  mapped[i] = S.mapping[m];
 }
 
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
@@ -388,6 +398,63 @@ int jade_debug_lens_ray_rng(int device_id, int32_t n, int32_t width, int32_t hei
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out, bo.p, 24 * N, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(rng_out, br.p, 4 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+// guide_tables (jade_scene_prep.hip) on the caller's arrays: out_guide_obj[2 o] = object o's first entry, [2 o + 1] = its cells Gn (0:
+// no table, the kernel bisects); out_guide[0 .. *out_n_guide) = the entries.  guide_cap: the entries out_guide holds (the tables never
+// need more than 8 x n_triangles + 2 x n_objects + 1 when the objects' segments are disjoint; more is refused, nothing is written past
+// it).  Of the desc only n_triangles, n_objects, prefix_area and obj_segs are read, and the segments are checked as jade_scene_create
+// checks them.  No HIP call.
+int jade_debug_guide_tables_host(const jade_scene_desc* d, uint32_t* out_guide_obj, uint32_t* out_guide, int32_t guide_cap, int32_t* out_n_guide) {
+  if (!d || !out_guide_obj || !out_guide || !out_n_guide || guide_cap < 0) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (d->n_triangles <= 0 || d->n_objects <= 0 || !d->prefix_area || !d->obj_segs) return jade_fail(JADE_ERR_INVALID, "missing prefix areas / object segments");
+  for (int i = 0; i < d->n_objects; ++i)
+    if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
+      return jade_fail(JADE_ERR_INVALID, "object segment out of range");
+  std::vector<uint32_t> guide;
+  std::vector<uint2> guide_obj;
+  guide_tables(d, guide, guide_obj);
+  if (guide.size() > (size_t)guide_cap) return jade_fail(JADE_ERR_INVALID, "out_guide is too small");
+  for (size_t o = 0; o < guide_obj.size(); ++o) {
+    out_guide_obj[2 * o] = guide_obj[o].x;
+    out_guide_obj[2 * o + 1] = guide_obj[o].y;
+  }
+  memcpy(out_guide, guide.data(), 4 * guide.size());
+  *out_n_guide = (int32_t)guide.size();
+  return JADE_OK;
+}
+
+// The rows jade_debug_exit_search runs: every obj_idx[i] names an object and every u[i] lies in [0, 1] (a NaN does not).  exit_search
+// forms its table cell from u x Gn: a row outside that range would read past the object's table - a wild read on a device, which no
+// assertion there could catch - so the rows are refused here, on the host, before anything is launched.  No HIP call.
+int jade_debug_exit_search_rows(int32_t n_objects, int32_t n, const int32_t* obj_idx, const float* u) {
+  if (!obj_idx || !u) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  for (int32_t i = 0; i < n; ++i) {
+    if (obj_idx[i] < 0 || obj_idx[i] >= n_objects) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": obj_idx out of range");
+    if (!(u[i] >= 0.0f && u[i] <= 1.0f)) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": u outside [0, 1]");
+  }
+  return JADE_OK;
+}
+
+// out_middle[i] = exit_search(scene, obj_idx[i], u[i]) (jade_shade.h: the BSSRDF branch's search, before the mapping), out_mapped[i] =
+// index_mapping[out_middle[i]]: one thread per row.  Every row is checked first (jade_debug_exit_search_rows; a null scene has no objects).
+int jade_debug_exit_search(jade_scene* s, int32_t n, const int32_t* obj_idx, const float* u, int32_t* out_middle, int32_t* out_mapped) {
+  if (!out_middle || !out_mapped) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (int rc = jade_debug_exit_search_rows(s ? s->n_objects : 0, n, obj_idx, u)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bo, bu, bm, bp;
+  HIP_TRY(upload(bo, obj_idx, N, s->stream));
+  HIP_TRY(upload(bu, u, N, s->stream));
+  HIP_TRY(bm.alloc(N * 4));
+  HIP_TRY(bp.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_exit_search, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bo.as<int32_t>(), bu.as<float>(),
+                     bm.as<int32_t>(), bp.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_middle, bm.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_mapped, bp.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }
 }  // extern "C"

@@ -1955,6 +1955,15 @@ static int validate_desc(const jade_scene_desc* d, int* depth_out) {
   for (int i = 0; i < d->n_objects; ++i)
     if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
       return jade_fail(JADE_ERR_INVALID, "object segment out of range");
+  // prefix_area is read by the BSSRDF branch alone.  Most of it only steers the search (any value will do, jade_rt.h), but an object's
+  // total, prefix_area[end_idx], is a FACTOR of that branch's radiance (PathTrace.cu:1105, 1160): not finite, it makes rates of inf
+  // and NaN, whose sum depends on the order of summation - this module adds a path's radiance forward where the reference unwinds
+  // its stacks - and at u = 0 the reference's search does not end.  Refused by both backends where the branch can run.
+  bool sub_surface = false;
+  for (int i = 0; i < d->n_triangles && !sub_surface; ++i) sub_surface = d->triangles[i].refract_mode == JADE_SUB_SURFACE;
+  for (int i = 0; i < d->n_objects && sub_surface; ++i)
+    if (!std::isfinite(d->prefix_area[d->obj_segs[i].end_idx]))
+      return jade_fail(JADE_ERR_INVALID, "an object's total prefix_area is not finite in a scene with SUB_SURFACE triangles");
   // walk the tree: ranges, cycles (visit budget), depth <= stack capacity - 1
   std::vector<std::pair<int, int>> st;
   st.push_back({1, 1});
@@ -2090,6 +2099,7 @@ int jade_scene_create(const jade_scene_desc* d, int device_id, jade_scene** out)
   s->device = device_id;
   s->tun = tun;
   s->n_emit = d->n_emit;
+  s->n_objects = d->n_objects;
   s->bvh_depth = depth;
   if ((rc = upload_scene(s.get(), d, prep))) return rc;
   if ((rc = selftest(s.get()))) return rc;

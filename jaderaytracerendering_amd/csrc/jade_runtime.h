@@ -174,6 +174,7 @@ struct jade_scene {
   DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias;
   bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
   int n_emit = 0;
+  int n_objects = 0;
   int bvh_depth = 0;
   jade_lens_params lens{};    // jade_scene_set_lens: what the next jade_render_begin takes (the render in progress keeps its own: rc.lens_radius, ps.lens_k)
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
@@ -246,6 +247,8 @@ struct ScenePrep {
   size_t geometry_bytes = 0;   // node + pair records
 };
 JADE_HIDDEN int prepare_scene(const jade_scene_desc& d, int depth, const Tunables& tun, ScenePrep* out);
+// ... its guide tables for the BSSRDF exit-point search (exit_search, jade_shade.h): per object {first entry, cells Gn}, and the entries
+JADE_HIDDEN void guide_tables(const jade_scene_desc* d, std::vector<uint32_t>& guide, std::vector<uint2>& guide_obj);
 // ... its alias table over the environment map's texels (JADE_ENV_IMPORTANCE, include/jade_rt.h), and the map sizes that mode takes:
 // env_sample (jade_shade.h) forms the slot from a 24-bit uniform, which reaches every slot of at most 2^24
 JADE_HIDDEN void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb, std::vector<uint4>& env_alias);

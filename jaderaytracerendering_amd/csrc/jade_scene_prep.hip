@@ -187,11 +187,14 @@ void pair_records(const jade_scene_desc* d, const Layout& lay, std::vector<float
   }
 }
 
+}  // namespace
+
 // Guide tables for the BSSRDF exit-point search (jade_shade.h, begin_bounce; PathTrace.cu:1031-1048).  Per object with
 // finite, non-decreasing prefix areas: Gn = the power of two >= 4 x its triangles cells, guide[c] = the first triangle i with
 // fl(c / Gn * A) <= prefix[i] - the product rounded once to fp32, as the kernel's `u * A` is (this file is built
 // -ffp-contract=off like the device code) - for c = 0 .. Gn, and one more entry so that cell Gn (u == 1) has an upper bound.
-// An object whose prefix areas are not monotone or not finite gets Gn = 0: the kernel then bisects as the reference does.
+// An object whose prefix areas are not monotone or not finite gets Gn = 0: the kernel then bisects as the reference does.  No HIP call
+// (libjade_hip_debug.so's jade_debug_guide_tables_host returns these tables as they are, tests/test_area_search_cpu.py).
 void guide_tables(const jade_scene_desc* d, std::vector<uint32_t>& guide, std::vector<uint2>& guide_obj) {
   guide_obj.assign((size_t)d->n_objects, make_uint2(0u, 0u));
   for (int o = 0; o < d->n_objects; ++o) {
@@ -221,6 +224,8 @@ void guide_tables(const jade_scene_desc* d, std::vector<uint32_t>& guide, std::v
   }
   if (guide.empty()) guide.push_back(0u);
 }
+
+namespace {
 
 // What shading reads of a triangle (jade_device.h, DevMaterial): the distinct {object, material} tuples of the caller's
 // records - the reference copies an object's material into each of its triangles, PathTrace.cu:451 - and per triangle

@@ -350,6 +350,43 @@ static __device__ __forceinline__ int bounce_classify(const DevScene& S, ShadeCt
   }
   return BT_MIRROR;
 }
+// The BSSRDF branch's search for the exit triangle (PathTrace.cu:1031-1048), on the draw u_area of [0, 1]: the LAST midpoint the
+// reference's bisection of object obj_idx's prefix areas looks at, before S.mapping (bounce_branch draws u_area and maps the result;
+// libjade_hip_debug.so's jade_debug_exit_search runs this function alone, row by row, tests/test_gpu_area_search.py).
+static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx, float u_area) {
+  const jade_obj_seg seg = S.segs[obj_idx];
+  float random_idx = u_area * S.prefix[seg.end_idx];
+  int left = seg.begin_idx, right = seg.end_idx, middle = 0;
+  const uint2 gd = S.guide_obj[obj_idx];
+  if (gd.y != 0u) {
+    // The reference bisects prefix[] (:1031-1048): ~17 DEPENDENT loads, the longest latency chain of this kernel, and what
+    // it returns is not the boundary but the LAST midpoint it looked at.  Both are reproduced without the chain: the
+    // boundary b = the first i with random_idx <= prefix[i] comes from a guide table (jade_scene_create: prefix is
+    // checked to be finite and non-decreasing, so "random_idx <= prefix[mid]" is "mid >= b"; the cell's bounds hold
+    // because rounding is monotone: c / Gn <= u implies fl(c / Gn * A) <= fl(u * A)), then the bisection is replayed
+    // on indices alone.
+    const uint32_t cell = (uint32_t)(u_area * (float)gd.y);  // u in [0, 1], Gn a power of two: exact
+    const uint32_t* gp = S.guide + gd.x + cell;
+    const uint32_t b_hi = gp[1];
+    uint32_t b = gp[0];
+    while (b < b_hi && !(random_idx <= S.prefix[b])) ++b;
+    while (left < right - 1) {
+      middle = (left + right) / 2;
+      if ((uint32_t)middle >= b) right = middle;
+      else left = middle;
+    }
+  } else {
+    while (left < right - 1) {
+      middle = (left + right) / 2;
+      float pm = S.prefix[middle];
+      if (random_idx <= pm) right = middle;
+      else if (random_idx >= pm) left = middle;
+      else break;
+    }
+  }
+  return middle;
+}
+
 // The branch itself: its draws, its rays (written through px), stage / flags / n_emit_rays.  Returns false if the path ended at
 // this vertex (*l_final holds the last l_dir).  `type` is uniform over the waves k_shade runs it for.
 // ENVIS: jade_render_params.env_sampling = JADE_ENV_IMPORTANCE (compiled apart: the parity kernels carry none of its code)
@@ -367,38 +404,7 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
   if (type == BT_BSSRDF) {
     {
       // ---- BSSRDF, PathTrace.cu:1029-1178 ----
-      const jade_obj_seg seg = S.segs[ot->obj_idx];
-      const float u_area = jade_rand(&c.rng);
-      float random_idx = u_area * S.prefix[seg.end_idx];
-      int left = seg.begin_idx, right = seg.end_idx, middle = 0;
-      const uint2 gd = S.guide_obj[ot->obj_idx];
-      if (gd.y != 0u) {
-        // The reference bisects prefix[] (:1031-1048): ~17 DEPENDENT loads, the longest latency chain of this kernel, and what
-        // it returns is not the boundary but the LAST midpoint it looked at.  Both are reproduced without the chain: the
-        // boundary b = the first i with random_idx <= prefix[i] comes from a guide table (jade_scene_create: prefix is
-        // checked to be finite and non-decreasing, so "random_idx <= prefix[mid]" is "mid >= b"; the cell's bounds hold
-        // because rounding is monotone: c / Gn <= u implies fl(c / Gn * A) <= fl(u * A)), then the bisection is replayed
-        // on indices alone.
-        const uint32_t cell = (uint32_t)(u_area * (float)gd.y);  // u in [0, 1], Gn a power of two: exact
-        const uint32_t* gp = S.guide + gd.x + cell;
-        const uint32_t b_hi = gp[1];
-        uint32_t b = gp[0];
-        while (b < b_hi && !(random_idx <= S.prefix[b])) ++b;
-        while (left < right - 1) {
-          middle = (left + right) / 2;
-          if ((uint32_t)middle >= b) right = middle;
-          else left = middle;
-        }
-      } else {
-        while (left < right - 1) {
-          middle = (left + right) / 2;
-          float pm = S.prefix[middle];
-          if (random_idx <= pm) right = middle;
-          else if (random_idx >= pm) left = middle;
-          else break;
-        }
-      }
-      middle = S.mapping[middle];
+      int middle = S.mapping[exit_search(S, ot->obj_idx, jade_rand(&c.rng))];
       float rand_x = jade_rand(&c.rng);
       float rand_y = jade_rand(&c.rng);
       if (rand_x + rand_y > 1) {

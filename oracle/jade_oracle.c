@@ -1145,6 +1145,15 @@ int jade_scene_create(const jade_scene_desc* d, int device_id, jade_scene** out)
   for (int i = 0; i < d->n_objects; ++i)
     if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
       return fail(JADE_ERR_INVALID, "object segment out of range");
+  /* an object's total prefix_area[end_idx] is a factor of the BSSRDF branch's radiance (PathTrace.cu:1105, 1160) and, times u, the
+   * key of its search, which never ends on a NaN (u = 0): not finite, it is refused where that branch can run (jade_rt.h) */
+  {
+    int sub_surface = 0;
+    for (int i = 0; i < d->n_triangles && !sub_surface; ++i) sub_surface = d->triangles[i].refract_mode == JADE_SUB_SURFACE;
+    for (int i = 0; i < d->n_objects && sub_surface; ++i)
+      if (!isfinite(d->prefix_area[d->obj_segs[i].end_idx]))
+        return fail(JADE_ERR_INVALID, "an object's total prefix_area is not finite in a scene with SUB_SURFACE triangles");
+  }
   if (!bvh_depth_ok(d)) return fail(JADE_ERR_UNSUPPORTED, "BVH malformed or deeper than the traversal stack");
 
   jade_scene* s = (jade_scene*)calloc(1, sizeof *s);

@@ -247,6 +247,8 @@ def bssrdf(S, rng, obj, src, out, n, k, trace):
             right = mid
         elif xi >= S.prefix[mid]:
             left = mid
+        else:
+            break                                # a NaN area: the reference would spin; the oracle and the module stop here
     m = int(S.mapping[mid])                      # the LAST mid tried (0 if the loop never ran), quirk 10
     rx, ry = next(rng), next(rng)
     Q = S.point(m, rx, ry)

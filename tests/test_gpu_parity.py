@@ -15,6 +15,7 @@ import pytest
 
 from conftest import assert_cached_walk_equals_reference_walk, B, J, assert_early_exit_equals_reference_walk, config_scene, counters, rel_l2
 from jaderaytracerendering_amd import _abi
+from scene_shapes import SCHEDULES, set_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -233,14 +234,8 @@ def test_result_independent_of_shade_schedule(hip, monkeypatch):
         p = B.params_from_config(cfg, spp=spp)
         p.width, p.height = 40, 36
         ref = None
-        #            split fused batch packet budget wide (k_trace_wide for the walk=1 frame) tail (k_tail finishes short lists; 0: passes to the end)
-        #            binned (k_shade deals its records by branch through LDS; 0: every thread runs its own record's whole bounce)
-        #            records (k_trace refills from 48-B ray records the shading kernels wrote; 0: it gathers each ray through its queue entry)
-        for v in (("1", "1", "1", "1", "32", "0", "1", "1", "1"), ("1", "1", "1", "0", "32", "1", "0", "1", "0"), ("1", "1", "1", "1", "3", "1", "1", "0", "1"), ("1", "1", "1", "1", "100000", "0", "0", "0", "0"),
-                  ("1", "0", "1", "1", "32", "1", "0", "1", "1"), ("0", "1", "1", "1", "32", "0", "1", "1", "0"), ("1", "1", "0", "1", "32", "1", "0", "1", "1"), ("1", "1", "0", "1", "32", "0", "1", "0", "0"),
-                  ("1", "0", "1", "1", "32", "0", "1", "0", "1"), ("0", "1", "0", "1", "32", "0", "0", "1", "1")):
-            for key, val in zip(("JADE_SHADE_SPLIT", "JADE_FUSED", "JADE_BATCH", "JADE_LIGHT_PACKET", "JADE_PACKET_BUDGET", "JADE_WIDE", "JADE_TAIL", "JADE_SHADE_BINNED", "JADE_RAY_RECORDS"), v):
-                monkeypatch.setenv(key, val)
+        for v in SCHEDULES:  # (tests/scene_shapes.py: the ten settings, shared with tests/test_gpu_scene_shapes.py)
+            set_schedule(monkeypatch, v)
             with hip.scene(hs) as sc:
                 rgb, bgr, st = sc.render(p)
                 early = sc.render(_with_walk(p, _abi.WALK_EARLY_EXIT))  # ... and so must the frame with early exits, in every schedule

@@ -1,0 +1,80 @@
+"""Caller-shaped scenes through the parity bar: tests/scene_shapes.py's variants, oracle against HIP module.
+
+Every scene any other test shades comes out of SceneBuilder, whose prefix areas, mapping, emitter list, segments, normals and
+materials are tidier than include/jade_rt.h asks.  jade_scene_create derives the guide tables, the de-duplicated material table and
+the emitter walk from exactly those arrays, so each variant is held to the project's bar (tests/test_gpu_parity.py): every work counter
+equal, NaN / +inf / -inf at the same pixels and channels, the finite radiance within 1e-4 relative L2, BGR8 at most 1 apart.  Three
+variants - per-triangle materials, emission around both emissive tests, tiny jade objects at the array's end - also render bit for
+bit the same under the ten shading schedules and the three walks, and the first of them through the denoiser's guide pass."""
+import numpy as np
+import pytest
+
+from conftest import (COUNTER_KEYS, assert_cached_walk_equals_reference_walk, assert_early_exit_equals_reference_walk, counters, rel_l2)
+from jaderaytracerendering_amd import _abi
+
+import scene_shapes as SS
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-4  # relative L2 on pre-tonemap radiance (BASELINE.json north_star)
+
+
+@pytest.mark.parametrize("name", ["base"] + list(SS.RENDERED))
+def test_variant_meets_the_parity_bar(oracle, hip, name):
+    r_o, b_o, st_o = SS.oracle_frame(oracle, name)
+    with hip.scene(SS.scene(name)) as sh:
+        r_h, b_h, st_h = sh.render(SS.params())
+    c_h, c_o = counters(st_h), counters(st_o)
+    assert set(c_h) == set(COUNTER_KEYS)
+    assert c_h == c_o, {k: (c_h[k], c_o[k]) for k in c_h if c_h[k] != c_o[k]}
+    for what, f in (("NaN", np.isnan), ("+inf", np.isposinf), ("-inf", np.isneginf)):
+        assert np.array_equal(f(r_h), f(r_o)), f"{what} at other pixels or channels: {int(f(r_h).sum())} against {int(f(r_o).sum())}"
+    fin = np.isfinite(r_o)
+    err = rel_l2(r_h[fin], r_o[fin])
+    diff = np.abs(b_h.astype(np.int16) - b_o.astype(np.int16))
+    print(f"{name}: relative L2 {err:.3g} over {int(fin.sum())} finite values, {int((~fin).sum())} not finite; BGR8 differs on {int((diff != 0).sum())} bytes, by at most {int(diff.max())}")
+    assert err <= TOL, f"relative L2 {err:g}"
+    assert diff.max() <= 1
+
+
+@pytest.mark.parametrize("name", SS.SCHEDULED)
+def test_variant_is_the_same_bits_under_every_schedule_and_walk(hip, monkeypatch, name):
+    hs = SS.scene(name)
+    p = SS.params()
+    ref = None
+    for v in SS.SCHEDULES:
+        SS.set_schedule(monkeypatch, v)
+        with hip.scene(hs) as sc:
+            rgb, bgr, st = sc.render(p)
+            early = sc.render(SS.params(walk=_abi.WALK_EARLY_EXIT))
+            assert_cached_walk_equals_reference_walk(sc, p, (rgb, bgr, st))
+        # (fewer=False: "early exits read fewer node records" did not hold for "thresholds" under one of these schedules - 222 255
+        # against the reference walk's 211 608, the frame and every other counter equal.  That variant ends most paths at their first
+        # vertex, so it has few yes/no rays to save on; the boxes stand ON the floor, so a ray through a contact face ties between two
+        # leaves, and the wide walk, which half of the schedules force on this 150-triangle tree, walks such a ray a second time.)
+        assert_early_exit_equals_reference_walk((rgb, bgr, st), early, fewer=False)
+        if ref is None:
+            ref = (rgb, bgr, counters(st))
+        else:
+            assert np.array_equal(rgb.view(np.uint32), ref[0].view(np.uint32)) and np.array_equal(bgr, ref[1]), v
+            assert counters(st) == ref[2], v
+
+
+def test_guides_of_the_patchwork_match_the_spec(hip):
+    """jade_render_guides reads the material through the de-duplicated table (mats + tnorm.w): with five materials per object the
+    albedo, the mirror decision and the normal must still be the hit triangle's own (test_gpu_denoise.py's float64 statement and bars)."""
+    from test_gpu_denoise import _Geometry, _spec_guide
+    hs = SS.scene("patchwork")
+    p = SS.params()
+    p.spp, p.width, p.height = 4, 16, 12  # (the float64 statement takes 20 ms a pixel)
+    S = _Geometry(hs)
+    with hip.scene(hs) as sc:
+        sc.begin(p)
+        sc.step(4)
+        g = sc.guides(1)
+    ok = 0
+    for y in range(p.height):
+        for x in range(p.width):
+            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            ok += bool(np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6))
+    assert ok >= 0.99 * p.width * p.height, f"{ok} of {p.width * p.height} pixels agree with the spec"

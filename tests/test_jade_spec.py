@@ -13,7 +13,10 @@ of the entry point are left out: the reference decides two ray sides there by th
 
 Under a TEXTURED sky (an 8 x 4 map with one bright texel; tests/env_spec.py's float64 lookup) the same comparison runs on the jade
 cube and on an open floor, in the reference's mode on both backends and with env_sampling = JADE_ENV_IMPORTANCE - which the oracle
-refuses - on the HIP module alone: there jade_spec follows include/jade_rt.h through tests/env_importance_spec.py, sample for sample."""
+refuses - on the HIP module alone: there jade_spec follows include/jade_rt.h through tests/env_importance_spec.py, sample for sample.
+
+The `patchwork` kind gives the cube's triangles four different materials: what shading reads per TRIANGLE (the module: through its
+de-duplicated material table) and what it reads per object must not be confused by either backend."""
 import numpy as np
 import pytest
 
@@ -47,7 +50,26 @@ def sky_map():
     return env
 
 
+def patchwork(sky=False):
+    """build("jade_cube") with glass_cube's glass, the light's and the floor's material rows dealt over every second of the cube's 12
+    triangles, the others staying jade (words 13-27 of a triangle record; obj_idx, geometry and norm stay): a BSSRDF path leaves through a
+    triangle whose refract_rate and refract_index are not jade's, a refracted ray meets jade and diffuse faces inside the cube, and
+    two triangles of the cube are lights.  emit_indices lists every emissive triangle."""
+    hs, glass = build("jade_cube", sky), build("glass_cube", sky)
+    tri, obj = hs.a["triangles"], hs.tri_i32()[:, 0]
+    rows = [tri[obj == 0][0, 13:28], glass.a["triangles"][glass.tri_i32()[:, 0] == 0][0, 13:28], tri[obj == 1][0, 13:28], tri[obj == 2][0, 13:28]]
+    cube = np.flatnonzero(obj == 0)
+    assert len(cube) == 12
+    for k, i in enumerate(cube):
+        tri[i, 13:28] = rows[(0, 1, 0, 2, 0, 3)[k % 6]]
+    hs.a["emit"] = np.flatnonzero((hs.tri_f32()[:, 13:16] > np.float32(1.4e-5)).any(1)).astype(np.int32)
+    assert len(hs.a["emit"]) == 4
+    return hs
+
+
 def build(kind, sky=False):
+    if kind == "patchwork":
+        return patchwork(sky)
     b = J.SceneBuilder()
     rot = H.transform_matrix(rot_deg=(20, 30, 0))
     if kind == "jade_cube":
@@ -105,6 +127,9 @@ CASES = {
     "jade_cube": dict(size=12, frames=(0, 1, 2), need={"bssrdf": 15, "sss": 30, "mirror": 50, "diffuse": 150}),
     "jade_fold": dict(size=12, frames=(0, 1, 2), need={"bssrdf": 20, "sss": 30, "mirror": 50}),
     "glass_cube": dict(size=12, frames=(0, 1, 2), need={"refract": 40, "refract-open": 2, "mirror": 40}),
+    # per-triangle materials (patchwork above).  `need`: half of what jade_spec alone counts per branch on these pixels - 308 diffuse,
+    # 50 mirror, 10 refract, 202 sky, 18 sss, 6 bssrdf (7 more leave through their own face and are left out), 1 refract-open
+    "patchwork": dict(size=12, frames=(0, 1, 2, 3), need={"bssrdf": 3, "diffuse": 154, "mirror": 25, "refract": 5, "sky": 101, "sss": 9}),
 }
 
 
