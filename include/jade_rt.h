@@ -52,7 +52,16 @@ extern "C" {
 
 /* Fixed constants of the integrator (PathTrace.cu:32-39); not parameters. */
 #define JADE_TILE_SIZE 16
-#define JADE_STACK_CAPACITY 128     /* bounce pushes per sample */
+/* JADE_STACK_CAPACITY: bounce pushes per sample.  The reference loops `while (stack_offset < 128)` and then unwinds its (dir, rate)
+ * stacks from whatever l_dir the last iteration left (PathTrace.cu:1410-1413).  A sample whose 128th push fills the stacks therefore
+ * traces that push's continuation ray, shades nothing at the vertex it finds (128 shaded vertices, not 129), and returns the
+ * unwinding SEEDED WITH THE LAST BOUNCE'S l_dir - which that bounce has already pushed as stack_dir[127]: the term counts twice, the
+ * second time through stack_indir_rate[127].  (0 for a mirror or refraction push, whose l_dir is 0.)  Every backend reproduces
+ * this; a forward-summing one returns acc + thr * l_dir with the 128th push already in acc and thr.
+ * JADE_MAX_FULL_REFLEX_TIME: iterations of the refraction loop (PathTrace.cu:1196).  A ray still inside after the 32nd - reflected
+ * there, totally or by its draw - leaves the loop as it is: the roulette draw and the exit ray follow in that direction, 33
+ * refraction rays in all.  tests/long_paths.py makes samples that reach either limit; tests/test_gpu_long_paths.py renders them. */
+#define JADE_STACK_CAPACITY 128
 #define JADE_BVH_STACK_CAPACITY 128 /* traversal stack entries: a BVH of up to 127 levels (the root is level 1) is accepted, and walked at that depth by tests/test_gpu_deep_trees.py; 128 levels are refused (JADE_ERR_UNSUPPORTED) */
 #define JADE_MAX_FULL_REFLEX_TIME 32
 

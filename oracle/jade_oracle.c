@@ -596,6 +596,19 @@ static int nonemissive(const jade_triangle* t) {
   return t->emissive[0] < 1.5e-4f && t->emissive[1] < 1.5e-4f && t->emissive[2] < 1.5e-4f;
 }
 
+/* Checker-only (jade_oracle_path_probe, jade_oracle_path_lengths below): what path_tracing leaves in the probe its thread points at -
+ * stack_offset and l_dir as the bounce loop left them, the two stacks before they are unwound, and how many refraction loops ran
+ * all their JADE_MAX_FULL_REFLEX_TIME iterations.  pushes stays -1 for a sample that never reached path_tracing (it saw the sky)
+ * and is -2 for one that returned 0 from inside the refraction loop (PathTrace.cu:1231). */
+typedef struct {
+  int32_t pushes;
+  int32_t chains_exhausted;
+  jvec3 l_dir;
+  jvec3* stack_dir;  /* [JADE_STACK_CAPACITY] each, or NULL */
+  jvec3* stack_rate;
+} path_probe;
+static __thread path_probe* t_probe;
+
 /* PathTrace.cu:905-1416 */
 static jvec3 path_tracing(const jade_scene* s, HitResult hit, jvec3 direction, uint32_t* rng, counters* c) {
   const jade_triangle* T = s->tris;
@@ -875,8 +888,10 @@ static jvec3 path_tracing(const jade_scene* s, HitResult hit, jvec3 direction, u
               break;
             }
           } else {
+            if (t_probe) t_probe->pushes = -2;
             return jv(0, 0, 0); /* PathTrace.cu:1231 */
           }
+          if (t_probe && i == JADE_MAX_FULL_REFLEX_TIME - 1) t_probe->chains_exhausted++;
         }
 
         float rr_result = jade_rand(rng);
@@ -1011,6 +1026,14 @@ static jvec3 path_tracing(const jade_scene* s, HitResult hit, jvec3 direction, u
     }
   }
 
+  if (t_probe) {
+    t_probe->pushes = stack_offset;
+    t_probe->l_dir = l_dir;
+    for (int i = 0; i < stack_offset && t_probe->stack_dir; ++i) {
+      t_probe->stack_dir[i] = stack_dir[i];
+      t_probe->stack_rate[i] = stack_indir_rate[i];
+    }
+  }
   for (int i = stack_offset - 1; i >= 0; --i) {
     l_dir = jv_mul(l_dir, stack_indir_rate[i]);
     l_dir = jv_add(l_dir, stack_dir[i]);
@@ -1240,6 +1263,63 @@ int jade_oracle_set_tile_filter(jade_scene* s, const int32_t* tile_ids, int32_t 
   if (!s->tile_keep) return fail(JADE_ERR_NOMEM, "out of memory");
   s->tile_keep_n = mx + 1;
   for (int i = 0; i < n; ++i) s->tile_keep[tile_ids[i]] = 1;
+  return JADE_OK;
+}
+
+/* Checker-only extensions (NOT part of jade_rt.h; the HIP module has no such entry points), for the tests of the two limits on a
+ * path's length (tests/long_paths.py).  Both run single samples of pixel (px, py) of the frame `rp` describes, on the calling thread,
+ * and touch no render in progress.
+ * jade_oracle_path_lengths: for each of the n samples whose stream is seeded with frame = frame_first + i (sample 0 of a render
+ * with that rp->frame), the pushes (stack_offset at the loop's exit; -1 sky, -2 returned from an open refraction), the refraction
+ * rays traced and the refraction loops that ran all JADE_MAX_FULL_REFLEX_TIME iterations.
+ * jade_oracle_path_probe: one sample (frame = rp->frame + sample) - the pushes, l_dir at the loop's exit, the two stacks
+ * (float [JADE_STACK_CAPACITY][3] each; the first `pushes` rows are written) and the sample's colour as render_sample returns it. */
+static int probe_sample(jade_scene* s, const jade_render_params* rp, int px, int py, uint32_t frame, path_probe* pr, counters* c, jvec3* color) {
+  pr->pushes = -1;
+  pr->chains_exhausted = 0;
+  pr->l_dir = jv(0, 0, 0);
+  uint32_t rng = jade_rng_seed((uint32_t)px, (uint32_t)py, frame);
+  t_probe = pr;
+  *color = render_sample(s, rp, px, py, &rng, c);
+  t_probe = NULL;
+  return JADE_OK;
+}
+int jade_oracle_path_lengths(jade_scene* s, const jade_render_params* rp, int32_t px, int32_t py, uint32_t frame_first, int32_t n,
+                             int32_t* out_pushes, uint32_t* out_refract_rays, int32_t* out_chains_exhausted) {
+  if (!s || !rp || n < 0 || !out_pushes || !out_refract_rays || !out_chains_exhausted) return fail(JADE_ERR_INVALID, "null argument");
+  if (rp->width <= 0 || rp->height <= 0 || px < 0 || py < 0 || px >= rp->width || py >= rp->height) return fail(JADE_ERR_INVALID, "pixel outside the frame");
+  for (int32_t i = 0; i < n; ++i) {
+    path_probe pr = {0};
+    counters c;
+    memset(&c, 0, sizeof c);
+    jvec3 color;
+    probe_sample(s, rp, px, py, frame_first + (uint32_t)i, &pr, &c, &color);
+    out_pushes[i] = pr.pushes;
+    out_refract_rays[i] = (uint32_t)c.rays_refract;
+    out_chains_exhausted[i] = pr.chains_exhausted;
+  }
+  return JADE_OK;
+}
+int jade_oracle_path_probe(jade_scene* s, const jade_render_params* rp, int32_t px, int32_t py, uint32_t sample, int32_t* out_pushes,
+                           float* out_l_dir, float* out_stack_dir, float* out_stack_rate, float* out_color) {
+  if (!s || !rp || !out_pushes || !out_l_dir || !out_stack_dir || !out_stack_rate || !out_color) return fail(JADE_ERR_INVALID, "null argument");
+  if (rp->width <= 0 || rp->height <= 0 || px < 0 || py < 0 || px >= rp->width || py >= rp->height) return fail(JADE_ERR_INVALID, "pixel outside the frame");
+  path_probe pr = {0};
+  pr.stack_dir = (jvec3*)calloc(2 * JADE_STACK_CAPACITY, sizeof(jvec3));
+  if (!pr.stack_dir) return fail(JADE_ERR_NOMEM, "out of memory");
+  pr.stack_rate = pr.stack_dir + JADE_STACK_CAPACITY;
+  counters c;
+  memset(&c, 0, sizeof c);
+  jvec3 color;
+  probe_sample(s, rp, px, py, rp->frame + sample, &pr, &c, &color);
+  *out_pushes = pr.pushes;
+  out_l_dir[0] = pr.l_dir.x; out_l_dir[1] = pr.l_dir.y; out_l_dir[2] = pr.l_dir.z;
+  for (int i = 0; i < pr.pushes; ++i) {
+    out_stack_dir[3 * i] = pr.stack_dir[i].x; out_stack_dir[3 * i + 1] = pr.stack_dir[i].y; out_stack_dir[3 * i + 2] = pr.stack_dir[i].z;
+    out_stack_rate[3 * i] = pr.stack_rate[i].x; out_stack_rate[3 * i + 1] = pr.stack_rate[i].y; out_stack_rate[3 * i + 2] = pr.stack_rate[i].z;
+  }
+  out_color[0] = color.x; out_color[1] = color.y; out_color[2] = color.z;
+  free(pr.stack_dir);
   return JADE_OK;
 }
 

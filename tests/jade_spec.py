@@ -142,8 +142,12 @@ def emissive(S, k, thr):
     return bool((S.emis[k] > thr).any())
 
 
-def path_tracing(S, rng, obj, src, out, trace):
-    """pathTracing(hit, direction), section 9.5.  `trace` collects the branch taken at every vertex."""
+def path_tracing(S, rng, obj, src, out, trace, info=None):
+    """pathTracing(hit, direction), section 9.5.  `trace` collects the branch taken at every vertex; `info` (a dict, optional) gets
+    what the loop left behind: "pushes" = len(stack), "l_dir", the "stack" itself, and "chains" = the refraction loops that ran all
+    their 32 iterations (tests/long_paths.py)."""
+    if info is not None:
+        info.update(pushes=0, chains=0)
     stack = []
     L = np.zeros(3)
     nE = len(S.emit)
@@ -168,7 +172,7 @@ def path_tracing(S, rng, obj, src, out, trace):
                     L, nxt = bssrdf(S, rng, obj, src, out, n, k, trace)
             else:
                 trace.append("refract")
-                res = direct_refraction(S, rng, obj, src, out, n, k)
+                res = direct_refraction(S, rng, obj, src, out, n, k, info)
                 if res is None:
                     trace.append("refract-open")
                     return np.zeros(3)          # PathTrace.cu:1231: the whole sample is 0
@@ -183,6 +187,8 @@ def path_tracing(S, rng, obj, src, out, trace):
             break
         push_dir, rate, obj, src, out = nxt
         stack.append((push_dir, rate))
+    if info is not None:
+        info.update(pushes=len(stack), l_dir=L.copy(), stack=list(stack))
     for d, r in reversed(stack):                # PathTrace.cu:1410-1413
         L = L * r + d
     return L
@@ -309,7 +315,7 @@ def bssrdf(S, rng, obj, src, out, n, k, trace):
     return L, None
 
 
-def direct_refraction(S, rng, obj, src, out, n, k):
+def direct_refraction(S, rng, obj, src, out, n, k, info=None):
     eta = S.eta[obj]
     R0 = ((1 - eta) / (1 + eta)) ** 2
     Fi = R0 + (1 - R0) * (1 - abs(n @ out)) ** 5
@@ -334,6 +340,9 @@ def direct_refraction(S, rng, obj, src, out, n, k):
         else:
             rate = rate * ((1.0 - Fo) * 1.25)
             break
+    else:
+        if info is not None:
+            info["chains"] += 1
     if not next(rng) < RR:
         return np.zeros(3), None
     h, hp = S.hit(origin, t, prev)
@@ -353,7 +362,7 @@ def mirror(S, rng, obj, src, out, n, fr, k):
     return S.sky(r) * fr * kk, None
 
 
-def sample(S, x, y, width, height, eye, cam, frame, trace=None):
+def sample(S, x, y, width, height, eye, cam, frame, trace=None, info=None):
     """One sample of pixel (x, y): section 9.2 camera ray, 9.6 pixel assembly."""
     rng = wang_stream(x, y, frame)
     trace = trace if trace is not None else []
@@ -368,4 +377,4 @@ def sample(S, x, y, width, height, eye, cam, frame, trace=None):
     if h < 0:
         trace.append("sky")
         return S.sky(d)
-    return S.emis[h] + path_tracing(S, rng, h, hp, -d, trace)
+    return S.emis[h] + path_tracing(S, rng, h, hp, -d, trace, info)
