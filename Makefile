@@ -79,6 +79,14 @@ asan-check:
 	cd $(ROOT)/tests/_build/asan && for c in tiny tinyjade C1; do \
 	  ASAN_OPTIONS=detect_leaks=1 ./jade_render --config $$c --width 48 --height 40 --spp 3 --backend ./libjade_oracle.so --out o_$$c.bmp || exit 1; done
 	cd $(ROOT)/tests/_build/asan && ./jade_render --config C2 --width 24 --height 24 --spp 2 --backend ./libjade_oracle.so --out o_C2.ppm
+	# caller-shaped trees (tests/tree_shapes.py --dump): validate_desc + prepare_scene, and the oracle with its cached walk, stand-alone
+	cd $(ROOT) && python3 tests/tree_shapes.py --dump $(ROOT)/tests/_build/tree_shapes
+	$(HIPCC) --offload-host-only -x hip -std=c++17 -O1 -g $(FPFLAGS) -fsanitize=address,undefined -fno-omit-frame-pointer -I$(ROOT)/include -I$(PKG)/csrc \
+	  -o $(ROOT)/tests/_build/asan/prep_shapes $(ROOT)/tests/native/prep_shapes_main.cpp $(PKG)/csrc/jade_scene_prep.hip -ldl
+	gcc -std=gnu11 -ffp-contract=off -mfma $(SAN) -DJADE_ORACLE_PROBE -I$(ROOT)/include -o $(ROOT)/tests/_build/asan/oracle_shapes \
+	  $(ROOT)/tests/native/oracle_shapes_main.c $(ROOT)/oracle/jade_oracle.c -lpthread -lm
+	ASAN_OPTIONS=detect_leaks=1 $(ROOT)/tests/_build/asan/prep_shapes $(ROOT)/tests/_build/tree_shapes
+	ASAN_OPTIONS=detect_leaks=1 $(ROOT)/tests/_build/asan/oracle_shapes $(ROOT)/tests/_build/tree_shapes
 	@echo "asan-check: clean"
 
 clean:

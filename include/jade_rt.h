@@ -106,7 +106,27 @@ typedef struct jade_triangle {
 /* == BVHNode_cu, PathTrace.cu:341-345 (40 bytes).  nodes[0] is a dummy, the
  * root is nodes[1], a child index of 0 means "none", n > 0 marks a leaf
  * holding triangles [index, index + n - 1] (PathTrace.cu:525-529, 804, 825,
- * 1557-1565). */
+ * 1557-1565).
+ *
+ * The array is the caller's; what it has to be is what hitBVH (:795-859) needs:
+ *   - Only the nodes the root reaches through child indices are ever read, by
+ *     either backend - checked (ranges), laid out, walked.  Whatever else the
+ *     array holds - spare capacity behind or between the nodes of the tree, zeros,
+ *     stale records with indices far out of range - is never looked at.
+ *   - A node may be reached along several paths: a leaf or a subtree with two
+ *     parents, left == right.  It is walked once per path, as the reference walks
+ *     it (a triangle met twice is tested twice and counted twice), as long as the
+ *     whole walk - every node once per path to it - stays within 4 * n_nodes + 8
+ *     visits; a longer one (a cycle never ends) is JADE_ERR_UNSUPPORTED, as is a path
+ *     of more than JADE_BVH_STACK_CAPACITY - 1 levels.
+ *   - Leaves may overlap, and a triangle may lie in no leaf: it is then never
+ *     hit, though emit_indices may still list it and index_mapping may still name it.
+ *   - A leaf's box need not contain its triangles, nor a parent's box its
+ *     children's: a box that a ray does not enter (hitAABB, :758-771, value > 0)
+ *     hides what lies under it, exactly as in the reference.
+ *   - n <= 0 is an internal node, whatever `index` holds; n < 0 is as good as 0.
+ *   - An internal node may lack one child or both (index 0); under a root
+ *     without children every ray misses. */
 typedef struct jade_bvh_node {
   int32_t left, right;
   int32_t n, index;
@@ -125,7 +145,8 @@ typedef struct jade_obj_seg {
  * ownership.
  *
  * What is checked is ranges - every index names an element, every segment
- * lies inside the array with begin <= end, the tree can be walked - and ONE value
+ * lies inside the array with begin <= end, the tree can be walked from its root
+ * (jade_bvh_node above: nodes the root does not reach are not read) - and ONE value
  * (an object's total area, below).  Beyond that
  * the arrays are read the way PathTrace.cu reads them, whatever they hold, and
  * both backends give the same frame.  In particular NOT assumed:

@@ -424,6 +424,31 @@ int jade_debug_guide_tables_host(const jade_scene_desc* d, uint32_t* out_guide_o
   return JADE_OK;
 }
 
+// validate_desc + prepare_scene (jade_scene_prep.hip) on the caller's descriptor, as jade_scene_create runs them, and what they made:
+// the binary records, the wide records (none unless wide_mode > 0, or < 0 and the records outgrow the L2: Tunables.wide_mode - the
+// environment is not read) and the pair records, as float4s, and info[0 .. 11) = their three counts in float4s, root_ref, n_internal,
+// n_pairs, missing_child, nested, wide_fits, cache_fits, the tree's levels.  cap[3]: the float4s each array holds (4, 8 and 40 x n_nodes
+// always do); more is refused, nothing is written past it.  A descriptor jade_scene_create refuses is refused with the same code.  No HIP
+// call (tests/test_scene_prep_cpu.py).
+int jade_debug_prepare_scene_host(const jade_scene_desc* d, int32_t wide_mode, const int64_t cap[3], float* out_nodes, float* out_nodes4, float* out_tverts,
+                                  int64_t info[11]) {
+  if (!d || !cap || !out_nodes || !out_nodes4 || !out_tverts || !info) return jade_fail(JADE_ERR_INVALID, "null argument");
+  int depth = 0;
+  if (int rc = validate_desc(d, &depth)) return rc;
+  Tunables tun;
+  tun.wide_mode = wide_mode;
+  ScenePrep p;
+  if (int rc = prepare_scene(*d, depth, tun, &p)) return rc;
+  if ((int64_t)p.nodes.size() > cap[0] || (int64_t)p.nodes4.size() > cap[1] || (int64_t)p.tverts.size() > cap[2]) return jade_fail(JADE_ERR_INVALID, "an output array is too small");
+  memcpy(out_nodes, p.nodes.data(), sizeof(float4) * p.nodes.size());
+  if (!p.nodes4.empty()) memcpy(out_nodes4, p.nodes4.data(), sizeof(float4) * p.nodes4.size());
+  memcpy(out_tverts, p.tverts.data(), sizeof(float4) * p.tverts.size());
+  const int64_t v[11] = {(int64_t)p.nodes.size(), (int64_t)p.nodes4.size(), (int64_t)p.tverts.size(), (int64_t)p.root_ref, p.n_internal, (int64_t)p.n_pairs,
+                         p.missing_child, p.nested, p.wide_fits, p.cache_fits, depth};
+  memcpy(info, v, sizeof v);
+  return JADE_OK;
+}
+
 // The rows jade_debug_exit_search runs: every obj_idx[i] names an object and every u[i] lies in [0, 1] (a NaN does not).  exit_search
 // forms its table cell from u x Gn: a row outside that range would read past the object's table - a wild read on a device, which no
 // assertion there could catch - so the rows are refused here, on the host, before anything is launched.  No HIP call.

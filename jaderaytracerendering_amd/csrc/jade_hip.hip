@@ -31,7 +31,7 @@
 // the JADE_DEBUG_EXPORTS entry points.  The rest of libjade_hip.so's host side sits beside the kernels it drives:
 //   jade_runtime.h       what the files share: jade_fail, HIP_TRY, DevBuf, DevEvent, Tunables, struct jade_scene, and the two
 //                        functions through which another file reaches a kernel of this one (launch_trace, resolve_to)
-//   jade_scene_prep.hip  prepare_scene: the caller's scene -> the records uploaded here; host only, no HIP call
+//   jade_scene_prep.hip  validate_desc + prepare_scene: the caller's scene -> the records uploaded here; host only, no HIP call
 //   jade_adaptive.hip    jade_render_adaptive, jade_render_error + k_tile_error
 //   jade_denoise.hip     jade_render_guides, jade_render_denoise, jade_denoise_image + their kernels
 //   jade_multi.hip       jade_render_multi and its RCCL gather
@@ -1935,59 +1935,6 @@ int jade_owned_tile_count(int32_t width, int32_t height, int32_t rank, int32_t n
   for (int y = 0; y < ty; ++y)
     for (int x = 0; x < tx; ++x) count += (x + y) % nranks == rank;
   return count;
-}
-
-static int validate_desc(const jade_scene_desc* d, int* depth_out) {
-  if (d->abi_version != JADE_ABI_VERSION) return jade_fail(JADE_ERR_INVALID, "abi_version mismatch");
-  if (d->n_triangles <= 0 || d->n_nodes < 2 || !d->triangles || !d->nodes)
-    return jade_fail(JADE_ERR_INVALID, "scene needs triangles and a BVH (dummy node 0 + root 1)");
-  if (d->n_triangles >= JADE_MAX_TRIS) return jade_fail(JADE_ERR_UNSUPPORTED, "too many triangles for the 27-bit leaf cursor (44.7 M)");
-  if (d->n_emit < 0 || (d->n_emit > 0 && !d->emit_indices)) return jade_fail(JADE_ERR_INVALID, "bad emitter list");
-  if (!d->index_mapping || !d->prefix_area || d->n_objects <= 0 || !d->obj_segs)
-    return jade_fail(JADE_ERR_INVALID, "missing mapping / prefix areas / object segments");
-  if (d->env_width <= 0 || d->env_height <= 0 || !d->env_rgb) return jade_fail(JADE_ERR_INVALID, "missing environment map");
-  for (int i = 0; i < d->n_emit; ++i)
-    if (d->emit_indices[i] < 0 || d->emit_indices[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "emitter index out of range");
-  for (int i = 0; i < d->n_triangles; ++i) {
-    if (d->index_mapping[i] < 0 || d->index_mapping[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "index_mapping out of range");
-    if (d->triangles[i].obj_idx < 0 || d->triangles[i].obj_idx >= d->n_objects) return jade_fail(JADE_ERR_INVALID, "obj_idx out of range");
-  }
-  for (int i = 0; i < d->n_objects; ++i)
-    if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
-      return jade_fail(JADE_ERR_INVALID, "object segment out of range");
-  // prefix_area is read by the BSSRDF branch alone.  Most of it only steers the search (any value will do, jade_rt.h), but an object's
-  // total, prefix_area[end_idx], is a FACTOR of that branch's radiance (PathTrace.cu:1105, 1160): not finite, it makes rates of inf
-  // and NaN, whose sum depends on the order of summation - this module adds a path's radiance forward where the reference unwinds
-  // its stacks - and at u = 0 the reference's search does not end.  Refused by both backends where the branch can run.
-  bool sub_surface = false;
-  for (int i = 0; i < d->n_triangles && !sub_surface; ++i) sub_surface = d->triangles[i].refract_mode == JADE_SUB_SURFACE;
-  for (int i = 0; i < d->n_objects && sub_surface; ++i)
-    if (!std::isfinite(d->prefix_area[d->obj_segs[i].end_idx]))
-      return jade_fail(JADE_ERR_INVALID, "an object's total prefix_area is not finite in a scene with SUB_SURFACE triangles");
-  // walk the tree: ranges, cycles (visit budget), depth <= stack capacity - 1
-  std::vector<std::pair<int, int>> st;
-  st.push_back({1, 1});
-  int64_t budget = 4 * (int64_t)d->n_nodes + 8;
-  int depth = 0;
-  while (!st.empty()) {
-    auto [id, dp] = st.back();
-    st.pop_back();
-    if (--budget < 0) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH malformed (cycle)");
-    if (dp > JADE_BVH_STACK_CAPACITY - 1) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH deeper than the traversal stack");
-    depth = std::max(depth, dp);
-    const jade_bvh_node& nd = d->nodes[id];
-    if (nd.n > 0) {
-      if (nd.index < 0 || (int64_t)nd.index + nd.n > d->n_triangles) return jade_fail(JADE_ERR_INVALID, "leaf range out of bounds");
-      if (nd.n > JADE_MAX_LEAF) return jade_fail(JADE_ERR_UNSUPPORTED, "leaf with more than 15 triangles");
-      continue;
-    }
-    if (nd.left < 0 || nd.left >= d->n_nodes || nd.right < 0 || nd.right >= d->n_nodes)
-      return jade_fail(JADE_ERR_INVALID, "child index out of range");
-    if (nd.left > 0) st.push_back({nd.left, dp + 1});
-    if (nd.right > 0) st.push_back({nd.right, dp + 1});
-  }
-  *depth_out = depth;
-  return JADE_OK;
 }
 
 // uploads what prepare_scene made and the caller's own arrays, and points s->dev at them

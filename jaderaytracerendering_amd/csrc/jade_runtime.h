@@ -246,6 +246,8 @@ struct ScenePrep {
   uint32_t root_ref = 0;
   size_t geometry_bytes = 0;   // node + pair records
 };
+// validate_desc first (the ranges, the tree walked from the root: *depth_out = its levels), then prepare_scene on what it accepted
+JADE_HIDDEN int validate_desc(const jade_scene_desc* d, int* depth_out);
 JADE_HIDDEN int prepare_scene(const jade_scene_desc& d, int depth, const Tunables& tun, ScenePrep* out);
 // ... its guide tables for the BSSRDF exit-point search (exit_search, jade_shade.h): per object {first entry, cells Gn}, and the entries
 JADE_HIDDEN void guide_tables(const jade_scene_desc* d, std::vector<uint32_t>& guide, std::vector<uint2>& guide_obj);

@@ -3,16 +3,22 @@
 #include <cmath>
 #include <cstring>
 #include <map>
+#include <utility>
 
 #include "jade_runtime.h"
 
 namespace {
 
-// Where the caller's nodes go: internal node -> its record, leaf -> its first pair record.
+// Where the caller's nodes go: internal node -> its record, leaf -> its first pair record.  Only what the root reaches is laid out
+// (include/jade_rt.h, jade_bvh_node): the reference's hitBVH never reads another node, so whatever lies in the rest of the caller's
+// array - spare capacity, junk - is never read here either.  A node the root reaches along several paths gets ONE record.
 struct Layout {
   const jade_scene_desc* d;
   std::vector<int32_t> compact;
   std::vector<uint32_t> pair_first;
+  std::vector<int32_t> internals;    // the distinct internal nodes the root reaches, every parent before its children
+  std::vector<int32_t> leaves;       // the distinct leaves the root reaches, in the order the internal nodes name them
+  std::vector<int32_t> leaf_parent;  // leaf -> the first internal node of `internals` that names it (0: none, the root is a leaf)
   int n_internal = 0;
   size_t n_pairs = 0;
   void number_internal_nodes();
@@ -32,13 +38,43 @@ struct Layout {
 void Layout::number_internal_nodes() {
   const int nN = d->n_nodes;
   compact.assign(nN, -1);
-  std::vector<int32_t> bfs;  // internal nodes reachable from the root, breadth first
+  leaf_parent.assign(nN, 0);
+  auto internal = [&](int i) { return i > 0 && d->nodes[i].n <= 0; };
+  // The internal nodes the root reaches, each once.  The caller's "tree" may name a node from several parents (validate_desc bounds
+  // the walk, so there is no cycle): a node is taken once all the edges into it have been followed, which puts every parent before
+  // its children and, on a tree, is the breadth-first order.
+  std::vector<int32_t> edges_in(nN, 0);
+  {
+    std::vector<uint8_t> seen(nN, 0);
+    std::vector<int32_t> todo;
+    if (internal(1)) { seen[1] = 1; todo.push_back(1); }
+    while (!todo.empty()) {
+      const jade_bvh_node& nd = d->nodes[todo.back()];
+      todo.pop_back();
+      for (int ch : {nd.left, nd.right})
+        if (internal(ch)) {
+          ++edges_in[ch];
+          if (!seen[ch]) { seen[ch] = 1; todo.push_back(ch); }
+        }
+    }
+  }
+  std::vector<int32_t>& bfs = internals;
   bfs.reserve(nN);
-  if (d->nodes[1].n <= 0) bfs.push_back(1);
+  std::vector<uint8_t> leaf_seen(nN, 0);
+  if (internal(1)) bfs.push_back(1);
+  else { leaf_seen[1] = 1; leaves.push_back(1); }
   for (size_t h = 0; h < bfs.size(); ++h) {
     const jade_bvh_node& nd = d->nodes[bfs[h]];
-    if (nd.left > 0 && d->nodes[nd.left].n <= 0) bfs.push_back(nd.left);
-    if (nd.right > 0 && d->nodes[nd.right].n <= 0) bfs.push_back(nd.right);
+    for (int ch : {nd.left, nd.right}) {
+      if (ch <= 0) continue;
+      if (internal(ch)) {
+        if (--edges_in[ch] == 0) bfs.push_back(ch);
+      } else if (!leaf_seen[ch]) {
+        leaf_seen[ch] = 1;
+        leaves.push_back(ch);
+        leaf_parent[ch] = bfs[h];
+      }
+    }
   }
   auto area = [&](int i) {
     const jade_bvh_node& nd = d->nodes[i];
@@ -47,33 +83,33 @@ void Layout::number_internal_nodes() {
   };
   std::vector<double> ar(bfs.size());
   for (size_t h = 0; h < bfs.size(); ++h) ar[h] = area(bfs[h]);
-  // a child inherits at most its parent's key, so a prefix of the order is always closed under "parent of"
+  // a child inherits at most its parents' keys, so a prefix of the order is always closed under "parent of"
   std::vector<double> key(nN, 0.0);
+  std::vector<uint8_t> keyed(nN, 0);
   for (size_t h = 0; h < bfs.size(); ++h) {
     const int i = bfs[h];
     if (h == 0) key[i] = ar[0];
     const jade_bvh_node& nd = d->nodes[i];
     for (int ch : {nd.left, nd.right})
-      if (ch > 0 && d->nodes[ch].n <= 0) key[ch] = std::min(key[i], area(ch));
+      if (internal(ch)) {
+        const double k = std::min(key[i], area(ch));
+        key[ch] = keyed[ch] ? std::min(key[ch], k) : k;
+        keyed[ch] = 1;
+      }
   }
   std::vector<int32_t> order(bfs.size());
   for (size_t h = 0; h < bfs.size(); ++h) order[h] = (int32_t)h;
   std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return key[bfs[a]] > key[bfs[b]]; });
   for (int32_t h : order) compact[bfs[h]] = n_internal++;
-  // internal nodes the root does not reach (none in a valid tree) keep a slot so that every record exists
-  for (int i = 1; i < nN; ++i)
-    if (d->nodes[i].n <= 0 && compact[i] < 0) compact[i] = n_internal++;
 }
 
-// vertex records hold two consecutive triangles of a leaf each (jade_trace.h): number the pairs leaf by leaf
+// vertex records hold two consecutive triangles of a leaf each (jade_trace.h): number the pairs leaf by leaf, by first triangle
+// (leaves may overlap: those that start at the same triangle keep the order in which the tree names them)
 void Layout::number_pairs() {
-  const int nN = d->n_nodes;
-  pair_first.assign(nN, 0);
-  std::vector<int> leaves;
-  for (int i = 1; i < nN; ++i)
-    if (d->nodes[i].n > 0) leaves.push_back(i);
-  std::sort(leaves.begin(), leaves.end(), [&](int a, int b) { return d->nodes[a].index < d->nodes[b].index; });
-  for (int i : leaves) {
+  pair_first.assign(d->n_nodes, 0);
+  std::vector<int32_t> by_index = leaves;
+  std::stable_sort(by_index.begin(), by_index.end(), [&](int a, int b) { return d->nodes[a].index < d->nodes[b].index; });
+  for (int i : by_index) {
     pair_first[i] = (uint32_t)n_pairs;
     n_pairs += (size_t)(d->nodes[i].n + 1) / 2;
   }
@@ -81,12 +117,10 @@ void Layout::number_pairs() {
 
 // the binary records: an internal node holds its children's boxes and references
 void binary_records(const jade_scene_desc* d, const Layout& lay, std::vector<float4>& nodes, bool* missing_child_out) {
-  const int nN = d->n_nodes;
   nodes.assign((size_t)4 * std::max(lay.n_internal, 1), float4{});
   bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
-  for (int i = 1; i < nN; ++i) {
+  for (int i : lay.internals) {
     const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
     if (nd.left <= 0 || nd.right <= 0) missing_child = true;
     float la[3] = {0, 0, 0}, lb[3] = {0, 0, 0}, ra[3] = {0, 0, 0}, rb[3] = {0, 0, 0};
     if (nd.left > 0) { memcpy(la, d->nodes[nd.left].aa, 12); memcpy(lb, d->nodes[nd.left].bb, 12); }
@@ -104,31 +138,26 @@ void binary_records(const jade_scene_desc* d, const Layout& lay, std::vector<flo
 // The wide walk and the occluder cache both rest on "a ray that meets a node's box meets every ancestor's" (jade_trace.h), which
 // holds when every child's box lies inside its parent's, bound by bound, with no NaN - true of any tree built by min / max over
 // the triangles (this repo's builders, the reference's), but the caller's array is the caller's: a tree with padded,
-// refitted or NaN boxes is walked with binary units from the root only, which needs no such property.
-bool boxes_nested(const jade_scene_desc* d) {
-  const int nN = d->n_nodes;
-  bool nested = true;
-  for (int i = 1; i < nN && nested; ++i) {
+// refitted or NaN boxes is walked with binary units from the root only, which needs no such property.  Over the nodes the root reaches.
+bool boxes_nested(const jade_scene_desc* d, const Layout& lay) {
+  for (int i : lay.internals) {
     const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
     for (int ch : {nd.left, nd.right}) {
       if (ch <= 0) continue;
       const jade_bvh_node& c = d->nodes[ch];
       for (int a = 0; a < 3; ++a)
-        if (!(c.aa[a] >= nd.aa[a] && c.bb[a] <= nd.bb[a] && c.aa[a] <= c.bb[a])) nested = false;  // (a NaN fails every comparison)
+        if (!(c.aa[a] >= nd.aa[a] && c.bb[a] <= nd.bb[a] && c.aa[a] <= c.bb[a])) return false;  // (a NaN fails every comparison)
     }
   }
-  return nested;
+  return true;
 }
 
 // the four-wide records (jade_device.h): node i's record holds its grandchildren - each child's own record, or the child twice
 // if it is a leaf
 void wide_records(const jade_scene_desc* d, const Layout& lay, const std::vector<float4>& nodes, std::vector<float4>& nodes4) {
-  const int nN = d->n_nodes;
   nodes4.assign((size_t)8 * lay.n_internal, make_float4(0, 0, 0, 0));
-  for (int i = 1; i < nN; ++i) {
+  for (int i : lay.internals) {
     const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0 || lay.compact[i] < 0) continue;
     float4* o = &nodes4[(size_t)8 * lay.compact[i]];
     uint32_t refs[4];
     const int ch[2] = {nd.left, nd.right};
@@ -155,16 +184,8 @@ void wide_records(const jade_scene_desc* d, const Layout& lay, const std::vector
 
 // the pair records: two consecutive triangles of a leaf each, vertices interleaved (jade_trace.h)
 void pair_records(const jade_scene_desc* d, const Layout& lay, std::vector<float4>& tverts) {
-  const int nN = d->n_nodes;
   tverts.assign((size_t)5 * std::max<size_t>(lay.n_pairs, 1), float4{});
-  std::vector<int32_t> leaf_parent(nN, 0);
-  for (int i = 1; i < nN; ++i) {
-    const jade_bvh_node& nd = d->nodes[i];
-    if (nd.n > 0) continue;
-    if (nd.left > 0 && d->nodes[nd.left].n > 0) leaf_parent[nd.left] = i;
-    if (nd.right > 0 && d->nodes[nd.right].n > 0) leaf_parent[nd.right] = i;
-  }
-  for (int i = 1; i < nN; ++i) {
+  for (int i : lay.leaves) {
     const jade_bvh_node& nd = d->nodes[i];
     for (int k = 0; k < nd.n; k += 2) {
       const bool has_b = k + 1 < nd.n;
@@ -177,7 +198,7 @@ void pair_records(const jade_scene_desc* d, const Layout& lay, std::vector<float
       o[3] = make_float4(a.p3[0], b.p3[0], a.p3[1], b.p3[1]);
       // flag word: bit 0 = B is a triangle; bits 1-31 = the leaf's parent + 1 (occluder cache, jade_trace.h; 0 = the root or none: a
       // walk "from the root" is the whole walk, nothing to cache)
-      const int par = leaf_parent[i];
+      const int par = lay.leaf_parent[i];
       const uint32_t parent1 = (par > 1 && lay.compact[par] > 0) ? (uint32_t)lay.compact[par] + 1u : 0u;
       const uint32_t tag[2] = {(uint32_t)(nd.index + k), (has_b ? 1u : 0u) | (parent1 << 1)};
       float tagf[2];
@@ -322,6 +343,61 @@ void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb
   }
 }
 
+// What jade_scene_create checks of the caller's descriptor before anything is derived from it: ranges, and a walk of the tree from the
+// root - the nodes the root does not reach are not read (include/jade_rt.h).  No HIP call.
+int validate_desc(const jade_scene_desc* d, int* depth_out) {
+  if (d->abi_version != JADE_ABI_VERSION) return jade_fail(JADE_ERR_INVALID, "abi_version mismatch");
+  if (d->n_triangles <= 0 || d->n_nodes < 2 || !d->triangles || !d->nodes)
+    return jade_fail(JADE_ERR_INVALID, "scene needs triangles and a BVH (dummy node 0 + root 1)");
+  if (d->n_triangles >= JADE_MAX_TRIS) return jade_fail(JADE_ERR_UNSUPPORTED, "too many triangles for the 27-bit leaf cursor (44.7 M)");
+  if (d->n_emit < 0 || (d->n_emit > 0 && !d->emit_indices)) return jade_fail(JADE_ERR_INVALID, "bad emitter list");
+  if (!d->index_mapping || !d->prefix_area || d->n_objects <= 0 || !d->obj_segs)
+    return jade_fail(JADE_ERR_INVALID, "missing mapping / prefix areas / object segments");
+  if (d->env_width <= 0 || d->env_height <= 0 || !d->env_rgb) return jade_fail(JADE_ERR_INVALID, "missing environment map");
+  for (int i = 0; i < d->n_emit; ++i)
+    if (d->emit_indices[i] < 0 || d->emit_indices[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "emitter index out of range");
+  for (int i = 0; i < d->n_triangles; ++i) {
+    if (d->index_mapping[i] < 0 || d->index_mapping[i] >= d->n_triangles) return jade_fail(JADE_ERR_INVALID, "index_mapping out of range");
+    if (d->triangles[i].obj_idx < 0 || d->triangles[i].obj_idx >= d->n_objects) return jade_fail(JADE_ERR_INVALID, "obj_idx out of range");
+  }
+  for (int i = 0; i < d->n_objects; ++i)
+    if (d->obj_segs[i].begin_idx < 0 || d->obj_segs[i].end_idx >= d->n_triangles || d->obj_segs[i].begin_idx > d->obj_segs[i].end_idx)
+      return jade_fail(JADE_ERR_INVALID, "object segment out of range");
+  // prefix_area is read by the BSSRDF branch alone.  Most of it only steers the search (any value will do, jade_rt.h), but an object's
+  // total, prefix_area[end_idx], is a FACTOR of that branch's radiance (PathTrace.cu:1105, 1160): not finite, it makes rates of inf
+  // and NaN, whose sum depends on the order of summation - this module adds a path's radiance forward where the reference unwinds
+  // its stacks - and at u = 0 the reference's search does not end.  Refused by both backends where the branch can run.
+  bool sub_surface = false;
+  for (int i = 0; i < d->n_triangles && !sub_surface; ++i) sub_surface = d->triangles[i].refract_mode == JADE_SUB_SURFACE;
+  for (int i = 0; i < d->n_objects && sub_surface; ++i)
+    if (!std::isfinite(d->prefix_area[d->obj_segs[i].end_idx]))
+      return jade_fail(JADE_ERR_INVALID, "an object's total prefix_area is not finite in a scene with SUB_SURFACE triangles");
+  // walk the tree: ranges, cycles (visit budget), depth <= stack capacity - 1
+  std::vector<std::pair<int, int>> st;
+  st.push_back({1, 1});
+  int64_t budget = 4 * (int64_t)d->n_nodes + 8;
+  int depth = 0;
+  while (!st.empty()) {
+    auto [id, dp] = st.back();
+    st.pop_back();
+    if (--budget < 0) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH malformed (cycle)");
+    if (dp > JADE_BVH_STACK_CAPACITY - 1) return jade_fail(JADE_ERR_UNSUPPORTED, "BVH deeper than the traversal stack");
+    depth = std::max(depth, dp);
+    const jade_bvh_node& nd = d->nodes[id];
+    if (nd.n > 0) {
+      if (nd.index < 0 || (int64_t)nd.index + nd.n > d->n_triangles) return jade_fail(JADE_ERR_INVALID, "leaf range out of bounds");
+      if (nd.n > JADE_MAX_LEAF) return jade_fail(JADE_ERR_UNSUPPORTED, "leaf with more than 15 triangles");
+      continue;
+    }
+    if (nd.left < 0 || nd.left >= d->n_nodes || nd.right < 0 || nd.right >= d->n_nodes)
+      return jade_fail(JADE_ERR_INVALID, "child index out of range");
+    if (nd.left > 0) st.push_back({nd.left, dp + 1});
+    if (nd.right > 0) st.push_back({nd.right, dp + 1});
+  }
+  *depth_out = depth;
+  return JADE_OK;
+}
+
 int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, ScenePrep* out) {
   const jade_scene_desc* d = &desc;
   Layout lay{d};
@@ -334,7 +410,7 @@ int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, S
   binary_records(d, lay, out->nodes, &out->missing_child);
   pair_records(d, lay, out->tverts);
   out->geometry_bytes = out->nodes.size() * sizeof(float4) + out->tverts.size() * sizeof(float4);
-  out->nested = boxes_nested(d);
+  out->nested = boxes_nested(d, lay);
   // stack levels a walk may need (validate_desc bounds the binary walk's: depth <= capacity - 1): a wide unit pushes up to three
   // entries for every two levels it descends; a walk that starts with the cached subtrees has three more under it
   out->wide_fits = 3 * ((depth + 1) / 2) + 1 + 3 <= JADE_BVH_STACK_CAPACITY;

@@ -321,10 +321,24 @@ static void occ_prepare(const jade_scene* s) {
     for (size_t i = 0; i < n; ++i) g_occ[i] = -1;
     g_tri_leaf = (int32_t*)calloc((size_t)nt, sizeof(int32_t));
     g_parent = (int32_t*)calloc((size_t)s->d.n_nodes, sizeof(int32_t));
+    /* only the nodes the root reaches (include/jade_rt.h, jade_bvh_node): the rest of the caller's array is never read */
+    uint8_t* reached = (uint8_t*)calloc((size_t)s->d.n_nodes, 1);
+    int32_t* todo = (int32_t*)malloc(sizeof(int32_t) * (size_t)s->d.n_nodes);
+    int sp = 0;
+    reached[1] = 1; todo[sp++] = 1;
+    while (sp > 0) {
+      const jade_bvh_node* nd = &s->nodes[todo[--sp]];
+      if (nd->n > 0) continue;
+      if (nd->left > 0 && !reached[nd->left]) { reached[nd->left] = 1; todo[sp++] = nd->left; }
+      if (nd->right > 0 && !reached[nd->right]) { reached[nd->right] = 1; todo[sp++] = nd->right; }
+    }
+    free(todo);
     for (int k = 1; k < s->d.n_nodes; ++k) {
+      if (!reached[k]) continue;
       if (s->nodes[k].n > 0) { for (int i = 0; i < s->nodes[k].n; ++i) g_tri_leaf[s->nodes[k].index + i] = k; }
       else { if (s->nodes[k].left > 0) g_parent[s->nodes[k].left] = k; if (s->nodes[k].right > 0) g_parent[s->nodes[k].right] = k; }
     }
+    free(reached);
     __atomic_store_n(&g_occ_scene, s, __ATOMIC_RELEASE);
   }
   pthread_mutex_unlock(&g_occ_mu);

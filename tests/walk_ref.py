@@ -61,10 +61,13 @@ def node(left, right):
 
 
 def tree_depth(t):
-    """Levels, the root being level 1 (validate_desc)."""
-    best, todo = 0, [(t, 1)]
+    """Levels, the root being level 1 (validate_desc): the longest path, a shared sub-tuple counted once per level it is met at."""
+    best, todo, seen = 0, [(t, 1)], set()
     while todo:
         t, lv = todo.pop()
+        if (id(t), lv) in seen:
+            continue
+        seen.add((id(t), lv))
         best = max(best, lv)
         if t[0] == "node":
             todo += [(c, lv + 1) for c in t[1:] if c is not None]
@@ -72,25 +75,35 @@ def tree_depth(t):
 
 
 def tree_nodes(tree, verts):
-    """The (N, 10) uint32 node array of `tree` over the (nT, 3, 3) float32 vertices: boxes bottom-up by min / max."""
+    """The (N, 10) uint32 node array of `tree` over the (nT, 3, 3) float32 vertices: boxes bottom-up by min / max.  A sub-tuple that
+    occurs more than once AS THE SAME OBJECT (x = node(...); node(x, x), or x under two parents) is emitted once and referenced from
+    every place it occurs: a node with several parents (tests/tree_shapes.py).  Equal tuples that are distinct objects stay distinct
+    nodes.  An internal node without children gets the box [0, 0]."""
     recs = [None, None]  # [left, right, n, index, aa, bb]; 0: the dummy, 1: the root
+    placed = {}          # id(sub-tuple) -> its node
 
     def emit(t, me):
         if t[0] == "leaf":
             p = verts[t[1]:t[1] + t[2]].reshape(-1, 3)
             recs[me] = [0, 0, t[2], t[1], p.min(0), p.max(0)]
             return
-        ids = []
+        ids, fresh = [], []
         for c in t[1:]:
             if c is None:
                 ids.append(0)
+            elif id(c) in placed:
+                ids.append(placed[id(c)])
             else:
                 recs.append(None)
+                placed[id(c)] = len(recs) - 1
                 ids.append(len(recs) - 1)
-        for c, i in zip(t[1:], ids):
-            if c is not None:
-                emit(c, i)
+                fresh.append((c, len(recs) - 1))
+        for c, i in fresh:
+            emit(c, i)
         kids = [recs[i] for i in ids if i > 0]
+        if not kids:
+            recs[me] = [0, 0, 0, 0, np.zeros(3, np.float32), np.zeros(3, np.float32)]
+            return
         recs[me] = [ids[0], ids[1], 0, 0, np.min([k[4] for k in kids], 0), np.max([k[5] for k in kids], 0)]
 
     emit(tree, 1)
