@@ -26,8 +26,8 @@
  *
  * The header also holds the HIP module's other entry points that the CPU
  * oracle does not implement: adaptive sampling and its noise map, the
- * edge-aware denoiser, exposure with its luminance meter, glare, and the
- * thin-lens camera (below).
+ * edge-aware denoiser, exposure with its luminance meter, glare, the
+ * thin-lens camera and the camera shutter (below).
  * Exported by libjade_hip.so only; the oracle has none of them.
  */
 #ifndef JADE_BVH_H
@@ -151,6 +151,8 @@ int jade_render_error(jade_scene* scene, float error_floor, float* out_error);
  * The guides follow the lens: in a render begun under a lens (jade_scene_set_lens, below) guide sample s takes its origin and its
  * direction by "The lens, stated" - four draws instead of two - and everything after that is the statement above.  The guides then
  * have the blurred edges the frame has; pinhole guides would tell the filter to keep edges that are not there.
+ * They follow the shutter in the same way: in a render begun under a shutter (jade_scene_set_shutter, below) guide sample s takes its
+ * origin and direction by "The shutter, stated" - three draws, or five under a lens.
  *
  * Variance of pixel p: the variance of its mean luminance, the square of the pixel error's numerator above:
  *   v = sum (Y_l - m)^2 / (K (K - 1))       (Y_l, m, K as above; fp64, stored as float; NaN where n cannot be estimated)
@@ -374,6 +376,59 @@ typedef struct jade_lens_params {
 
 int jade_scene_set_lens(jade_scene* scene, const jade_lens_params* lens);
 int jade_scene_get_lens(jade_scene* scene, jade_lens_params* out);
+
+/* ---- Camera shutter: motion blur between two camera poses ----
+ *
+ * Non-parity, like the lens: the reference renders an instant.  The shutter is a property of the scene handle, read by the next
+ * jade_render_begin - so by jade_render, jade_render_adaptive, jade_render_multi (per scene) - and a render in progress keeps the
+ * shutter it began with.  The shutter opens at the pose of jade_render_params (eye, camera) and closes at (eye_close, camera_close);
+ * every sample draws a time of its own within the exposure and is traced from the pose at that time.  With no shutter every kernel,
+ * schedule, bit and counter is today's, for the pinhole and under a lens alike.  The mode is entered whenever a shutter is set, even one
+ * whose two poses are equal.  It composes with the lens (depth of field and motion blur together, as a camera gives them), with
+ * JADE_ENV_IMPORTANCE, adaptive sampling, the denoiser (the guides follow the shutter as they follow the lens), exposure and glare.
+ * Only the camera moves: the scene is the same at every time.
+ *
+ * ---- The shutter, stated ----
+ * tests/shutter_spec.py is this text in float64.  Every operation below is ONE float32 operation, nothing contracted.
+ *
+ * For sample s of pixel (x, y) the stream is seeded as jade_rt.h says.  u1, u2 are the two jitter draws and give left_offset and
+ * up_offset by the pinhole's statements, unchanged.  Under a lens (aperture_radius > 0) u3 and u4 follow, as "The lens, stated" says.
+ * Then ONE more draw ut, BEFORE any draw of the path.
+ * On the host, once per render, one float subtraction each:
+ *   t_span = t_close - t_open
+ *   de[i]  = eye_close[i] - eye[i]                   i = 0, 1, 2
+ *   dc[j]  = camera_close[j] - camera[j]             for the nine entries jade_transform(v, 0, .) multiplies by v: j = 0, 1, 2, 4, 5, 6, 8, 9, 10
+ * Per sample:
+ *   t        = t_open + ut * t_span                  a multiplication, then an addition
+ *   eye_t[i] = eye[i] + t * de[i]                    a multiplication, then an addition
+ *   cam_t[j] = camera[j] + t * dc[j]                 a multiplication, then an addition; every other entry of cam_t is camera's
+ *   no lens:  dir = normalize(jade_transform((left_offset, up_offset, -1.5f), 0, cam_t));  origin = eye_t
+ *   lens:     the statements of "The lens, stated" from r to origin, with cam_t and eye_t in place of camera and eye
+ * Every later draw of the sample sits one place further on in the stream than without a shutter: the path's first draw is the
+ * fourth of the stream without a lens and the sixth with one.  jade_stats.rays_primary still counts one query per sample.
+ *
+ * A property of the mode: the matrix is interpolated entry by entry, not as a rotation.  Between two poses that differ by a rotation
+ * by theta about an axis, the matrix at mid-exposure is the rotation by theta / 2 shrunk by cos(theta / 2) across that axis (along
+ * the axis nothing changes): a direction is normalised afterwards, so what remains is a view compressed by that factor across
+ * the axis - 0.4 % at 10 degrees, 3.4 % at 30 - and a sweep that is uniform in the chord, not in the angle.  Keep theta small: a few
+ * degrees per exposure.  It is a recommendation and is not checked; a longer move is several exposures, each a render of its own
+ * with its own two poses.  With a lens, the aperture disk lies in the plane the interpolated matrix spans and is shrunk with it.
+ *
+ * The schedule is the lens's list schedule: no fused first pass, no tail kernel; rays_inline and tail_launches
+ * are 0.  Results do not depend on steps, tile partitions or records per pixel.
+ *
+ * jade_scene_set_shutter: shutter == null: no shutter.  All 19 pose floats must be finite; t_open and t_close must be finite with
+ * 0 <= t_open <= t_close <= 1 (t_open == t_close: every sample at that one time).  JADE_ERR_INVALID leaves the previous shutter in
+ * place.  jade_scene_get_shutter: *is_set = 1 and *out = the shutter as set, or *is_set = 0 and *out zeroed; either may be null.
+ * jade_render_multi: all scenes must carry the same shutter, bit for bit, or none, else JADE_ERR_INVALID before anything is launched. */
+typedef struct jade_shutter_params {
+  float eye_close[3];      /* the eye when the shutter closes; it opens at jade_render_params.eye */
+  float camera_close[16];  /* the camera matrix when it closes; same layout as jade_render_params' */
+  float t_open, t_close;   /* 0 <= t_open <= t_close <= 1: the part of the move the exposure covers */
+} jade_shutter_params;
+
+int jade_scene_set_shutter(jade_scene* scene, const jade_shutter_params* shutter);
+int jade_scene_get_shutter(jade_scene* scene, jade_shutter_params* out, int* is_set);
 
 #ifdef __cplusplus
 }

@@ -94,6 +94,16 @@ typedef int (*jadeh_trace_rays_fn)(jade_scene* scene, int32_t n, const float* or
 int jadeh_focus_distance(jadeh_trace_rays_fn trace_rays, jade_scene* scene, const jade_render_params* params, int px, int py,
                          float* out);
 
+/* A second camera pose for the shutter (include/jade_bvh.h, jade_shutter_params): the pose (eye, cam) after two moves, in this order.
+ * First a truck: the eye is translated by truck[3], given in camera space (x along the right column, y along the up column, z along
+ * the third column, which points backwards); null = no truck.  Then a rotation by orbit_deg degrees, right-handed, about the axis
+ * through pivot[3] parallel to the camera's up column: the eye and the three direction columns all turn.  pivot == null: the eye
+ * itself, after the truck - a pan.  The pivot at the subject is the turntable.  Computed in double and rounded once; columns 12 .. 14
+ * of cam_out carry the new eye as jadeh_camera_orbit's do.  A zero move returns the pose bit for bit.  Returns 0, or -1
+ * (jadeh_last_error) on a null pose, a non-finite argument or an up column of length 0.  The outputs may alias the inputs. */
+int jadeh_camera_move(const float eye[3], const float cam[16], const float truck[3], float orbit_deg, const float pivot[3],
+                      float eye_out[3], float cam_out[16]);
+
 int jadeh_write_bmp(const char* path, const uint8_t* bgr, int w, int h);
 int jadeh_write_ppm(const char* path, const uint8_t* bgr, int w, int h);
 int jadeh_write_pfm(const char* path, const float* rgb, int w, int h);

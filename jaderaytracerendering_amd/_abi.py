@@ -125,6 +125,10 @@ class LensParams(C.Structure):  # == jade_lens_params, include/jade_bvh.h
     _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
 
 
+class ShutterParams(C.Structure):  # == jade_shutter_params, include/jade_bvh.h
+    _fields_ = [("eye_close", f3), ("camera_close", C.c_float * 16), ("t_open", C.c_float), ("t_close", C.c_float)]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -196,6 +200,9 @@ BVH_SYMBOLS = {
     # the thin lens of a scene handle (scene, lens or null) / (scene, out)
     "jade_scene_set_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),
     "jade_scene_get_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),
+    # the shutter of a scene handle (scene, shutter or null) / (scene, out, is_set)
+    "jade_scene_set_shutter": (C.c_int, [C.c_void_p, C.POINTER(ShutterParams)]),
+    "jade_scene_get_shutter": (C.c_int, [C.c_void_p, C.POINTER(ShutterParams), C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {
@@ -226,6 +233,8 @@ HOST_SYMBOLS = {
     "jadeh_camera_orbit": (None, [C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     # autofocus (the backend's jade_trace_rays, scene, params, px, py, out)
     "jadeh_focus_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderParams), C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    # a second pose for the shutter (eye, cam, truck or null, orbit_deg, pivot or null, eye_out, cam_out)
+    "jadeh_camera_move": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "jadeh_write_bmp": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "jadeh_write_ppm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),
     "jadeh_write_pfm": (C.c_int, [C.c_char_p, C.c_void_p, C.c_int, C.c_int]),

@@ -388,6 +388,32 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(lens)))
         return lens.aperture_radius, lens.focus_distance
 
+    def set_shutter(self, eye_close, camera_close=None, t_open=0.0, t_close=1.0):
+        """jade_scene_set_shutter: every render this handle begins from now on opens its shutter at the pose of its params and closes it at
+        (eye_close, camera_close); each sample is traced from the pose at a time of its own within [t_open, t_close] of that move (HIP
+        module only; non-parity: include/jade_bvh.h, "The shutter, stated").  set_shutter(None) removes it.
+        JadeError(JADE_ERR_INVALID) leaves the previous shutter in place."""
+        fn = self._hip_only("jade_scene_set_shutter")
+        if eye_close is None:
+            self.backend.check(fn(self._h, None))
+            return
+        e = np.asarray(eye_close, np.float32).ravel()
+        m = np.asarray(camera_close, np.float32).ravel()
+        if e.shape != (3,) or m.shape != (16,):
+            raise ValueError("set_shutter wants eye_close[3] and camera_close[16]")
+        sh = _abi.ShutterParams(_abi.f3(*e.tolist()), (C.c_float * 16)(*m.tolist()), float(t_open), float(t_close))
+        self.backend.check(fn(self._h, C.byref(sh)))
+
+    def shutter(self):
+        """jade_scene_get_shutter: (eye_close[3], camera_close[16], t_open, t_close) as set, or None for a handle without a shutter."""
+        fn = self._hip_only("jade_scene_get_shutter")
+        sh = _abi.ShutterParams()
+        is_set = C.c_int(0)
+        self.backend.check(fn(self._h, C.byref(sh), C.byref(is_set)))
+        if not is_set.value:
+            return None
+        return np.array(sh.eye_close[:], np.float32), np.array(sh.camera_close[:], np.float32), sh.t_open, sh.t_close
+
     def focus_distance(self, params, px, py):
         """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
         (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that

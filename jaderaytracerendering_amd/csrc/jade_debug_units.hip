@@ -200,6 +200,44 @@ __global__ void k_debug_exit_search(DevScene S, int n, const int32_t* obj_idx, c
   mapped[i] = S.mapping[m];
 }
 
+// A row of the shutter ray's test entries, 64 floats: the lens row's first 29 (x, y, W, H, eye[3], cam[16], A, f, u1 .. u4; A == 0: no lens),
+// then ut, t_open, t_close, eye_close[3], cam_close[16], 13 unused.  The constants are formed as jade_render_begin forms them
+// (shutter_const, jade_device.h).  out: origin[3], dir[3].
+#define SHUTTER_ROW 64
+static __host__ __device__ __forceinline__ void debug_shutter_row(const float* row, float* out) {
+  const float x = row[0], y = row[1];
+  const double two_over_w = 2.0 / (double)(int)row[2], two_over_h = 2.0 / (double)(int)row[3];
+  const double aspect = (double)(int)row[2] / (double)(int)row[3];
+  const float fx = (float)(int)x + row[25];
+  const double lo = -1.0 + two_over_w * ((double)fx - 0.5);
+  const float left_offset = (float)(lo * aspect);
+  const float fy = (float)(int)y + row[26];
+  const float up_offset = (float)(-1.0 + two_over_h * ((double)fy - 0.5));
+  const float A = row[23];
+  const float k = A > 0.0f ? row[24] / 1.5f : 0.0f;
+  const ShutterConst H = shutter_const(row + 4, row + 7, row + 32, row + 35, row[30], row[31]);
+  jvec3 o, d;
+  shutter_ray(row + 7, row + 4, H, A, k, left_offset, up_offset, row[27], row[28], row[29], &o, &d);
+  out[0] = o.x; out[1] = o.y; out[2] = o.z;
+  out[3] = d.x; out[4] = d.y; out[5] = d.z;
+}
+__global__ void k_debug_shutter_ray(int n, const float* rows, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) debug_shutter_row(rows + (size_t)SHUTTER_ROW * i, out + 6 * (size_t)i);
+}
+// row i: the shutter ray as the shading kernel draws it, for sample sidx[i] of pixel (px[i], py[i]); the stream's state after the three or five draws
+__global__ void k_debug_shutter_ray_rng(RenderConst R, ShutterConst H, float lens_k, int n, const int32_t* px, const int32_t* py, const uint32_t* sidx,
+                                        float* out, uint32_t* rng_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  uint32_t rng;
+  jvec3 o;
+  const jvec3 d = camera_ray_shutter(R, H, lens_k, px[i], py[i], sidx[i], &rng, &o);
+  put3(out, 2 * i, o);
+  put3(out, 2 * i + 1, d);
+  rng_out[i] = rng;
+}
+
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
 
 static hipError_t upload0(DevBuf& b, const void* src, size_t elems) {  // on the null stream: these entry points have no scene
@@ -480,6 +518,61 @@ int jade_debug_exit_search(jade_scene* s, int32_t n, const int32_t* obj_idx, con
   HIP_TRY(hipMemcpyAsync(out_middle, bm.p, N * 4, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(out_mapped, bp.p, N * 4, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// The shutter ray (shutter_ray, jade_device.h; include/jade_bvh.h "The shutter, stated") on n rows of SHUTTER_ROW floats (above): out[i] =
+// origin[3], dir[3].  The HOST build of the function, no HIP call: what tests/test_shutter_cpu.py holds against the float64 statement.
+int jade_debug_shutter_ray_host(int32_t n, const float* rows, float* out) {
+  if (n < 0 || !rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  for (int32_t i = 0; i < n; ++i) debug_shutter_row(rows + (size_t)SHUTTER_ROW * i, out + 6 * (size_t)i);
+  return JADE_OK;
+}
+
+// ... and the same rows on the device.
+int jade_debug_shutter_ray(int device_id, int32_t n, const float* rows, float* out) {
+  if (!rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / SHUTTER_ROW) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bo;
+  HIP_TRY(upload0(bi, rows, SHUTTER_ROW * N));
+  HIP_TRY(bo.alloc(24 * N));
+  hipLaunchKernelGGL(k_debug_shutter_ray, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 24 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// The shutter ray from the stream, as the render draws it: sample sidx[i] of pixel (px[i], py[i]) of a width x height frame from (eye,
+// camera) with `frame`, under lens (A, f) - A == 0: none - and the shutter `sh`.  out[i] = origin[3], dir[3]; rng_out[i] = the stream's
+// state after the three (no lens) or five draws.
+int jade_debug_shutter_ray_rng(int device_id, int32_t n, int32_t width, int32_t height, uint32_t frame, const float* eye, const float* camera, float A, float f,
+                               const jade_shutter_params* sh, const int32_t* px, const int32_t* py, const uint32_t* sidx, float* out, uint32_t* rng_out) {
+  if (!eye || !camera || !sh || !px || !py || !sidx || !out || !rng_out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows || width <= 0 || height <= 0) return jade_fail(JADE_ERR_INVALID, "row count or frame size out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  RenderConst R{};
+  R.width = width; R.height = height; R.tiles_x = (width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE; R.frame = frame;
+  memcpy(R.eye, eye, sizeof R.eye);
+  memcpy(R.cam, camera, sizeof R.cam);
+  R.lens_radius = A > 0.0f ? A : 0.0f;
+  R.two_over_w = 2.0 / (double)width;   // (jade_render_begin's statements)
+  R.two_over_h = 2.0 / (double)height;
+  R.aspect = (double)width / (double)height;
+  const ShutterConst H = shutter_const(eye, camera, sh->eye_close, sh->camera_close, sh->t_open, sh->t_close);
+  const size_t N = (size_t)n;
+  DevBuf bx, by, bs, bo, br;
+  HIP_TRY(upload0(bx, px, N));
+  HIP_TRY(upload0(by, py, N));
+  HIP_TRY(upload0(bs, sidx, N));
+  HIP_TRY(bo.alloc(24 * N));
+  HIP_TRY(br.alloc(4 * N));
+  hipLaunchKernelGGL(k_debug_shutter_ray_rng, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, R, H, A > 0.0f ? f / 1.5f : 0.0f, n, bx.as<int32_t>(),
+                     by.as<int32_t>(), bs.as<uint32_t>(), bo.as<float>(), br.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 24 * N, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rng_out, br.p, 4 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 }  // extern "C"

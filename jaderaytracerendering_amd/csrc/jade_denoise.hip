@@ -90,6 +90,22 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera_lens(PathState G
   state[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
   mirrors[p] = 0u;
 }
+// ... and in a render under a shutter (H = that render's constants), with a lens or without
+__global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera_shutter(PathState G, RenderConst R, float lens_k, const int32_t* tile_ids, const uint32_t* list,
+                                                                        uint32_t n, uint32_t sidx, float4* state, uint32_t* mirrors, ShutterConst H) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int p = (int)list[i];
+  int x, y;
+  (void)dn_pixel_xy(R, tile_ids, p, &x, &y);
+  uint32_t rng;
+  jvec3 org;
+  const jvec3 dir = camera_ray_shutter(R, H, lens_k, x, y, sidx, &rng, &org);
+  G.orgs[p] = make_float4(org.x, org.y, org.z, __int_as_float(-1));
+  G.slot[p] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
+  state[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+  mirrors[p] = 0u;
+}
 
 // The hits of the rays queue[0 .. *count): a mirror vertex (reflex_mode == JADE_MIRROR, not emissive by bounce_mirror's test, fewer than
 // JADE_MAX_FULL_REFLEX_TIME passed) goes on with bounce_mirror's reflected ray, appended to next_queue; anything else ends the sample
@@ -366,7 +382,10 @@ static int dn_guides(jade_scene* s, int G) {
   uint32_t* mirrors = s->b_dn_mirrors.as<uint32_t>();
   const float inv_g = (float)(1.0 / (double)G);
   for (int smp = 0; smp < G && n_in; ++smp) {
-    if (s->rc.lens_radius > 0.0f)
+    if (s->sh_on)
+      hipLaunchKernelGGL(k_guide_camera_shutter, dim3(dn_grid(n_in)), dim3(JADE_DN_BLOCK), 0, s->stream, g, s->rc, s->ps.lens_k, s->b_tiles.as<int32_t>(),
+                         s->b_dn_list.as<uint32_t>(), n_in, (uint32_t)smp, state, mirrors, s->sh);
+    else if (s->rc.lens_radius > 0.0f)
       hipLaunchKernelGGL(k_guide_camera_lens, dim3(dn_grid(n_in)), dim3(JADE_DN_BLOCK), 0, s->stream, g, s->rc, s->ps.lens_k, s->b_tiles.as<int32_t>(),
                          s->b_dn_list.as<uint32_t>(), n_in, (uint32_t)smp, state, mirrors);
     else

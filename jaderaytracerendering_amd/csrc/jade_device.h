@@ -335,6 +335,64 @@ static __device__ __forceinline__ jvec3 camera_ray_lens(const RenderConst& R, fl
   return dir;
 }
 
+// The shutter's constants (include/jade_bvh.h, "The shutter, stated"; non-parity), formed by jade_render_begin with one float subtraction
+// each: a by-value argument of the shutter kernels alone, so that RenderConst and PathState stay as every other kernel takes them.
+struct ShutterConst {
+  float de[3];   // eye_close - eye
+  float dc[9];   // camera_close - camera for the nine entries jade_transform(v, 0, .) multiplies by v: dc[3 * col + row] belongs to cam[4 * col + row]
+  float t_open;
+  float t_span;  // t_close - t_open
+};
+static __host__ __device__ __forceinline__ ShutterConst shutter_const(const float* eye, const float* cam, const float* eye_close, const float* cam_close,
+                                                                      float t_open, float t_close) {
+  ShutterConst H;
+  for (int i = 0; i < 3; ++i) H.de[i] = eye_close[i] - eye[i];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) H.dc[3 * c + r] = cam_close[4 * c + r] - cam[4 * c + r];
+  H.t_open = t_open;
+  H.t_span = t_close - t_open;
+  return H;
+}
+// The camera ray under a shutter: the time t of the draw ut, the pose at t - eye and matrix interpolated entry by entry, a multiplication
+// and then an addition each - and from that pose the pinhole ray (A == 0) or lens_ray (A > 0; k as there) of the jitter.  One fp32 operation
+// per operation written.  Compiled for the host too: that build is what tests/test_shutter_cpu.py holds against the float64 statement.
+static __host__ __device__ __forceinline__ void shutter_ray(const float* cam, const float* eye, const ShutterConst& H, float A, float k, float left_offset,
+                                                            float up_offset, float u3, float u4, float ut, jvec3* origin, jvec3* dir) {
+  const float t = H.t_open + ut * H.t_span;
+  float eye_t[3], cam_t[16];
+  for (int i = 0; i < 3; ++i) eye_t[i] = eye[i] + t * H.de[i];
+  for (int j = 0; j < 16; ++j) cam_t[j] = cam[j];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) cam_t[4 * c + r] = cam[4 * c + r] + t * H.dc[3 * c + r];
+  if (A > 0.0f) {
+    lens_ray(cam_t, eye_t, A, k, left_offset, up_offset, u3, u4, origin, dir);
+  } else {
+    *dir = jv_normalize(jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, cam_t));
+    *origin = jv(eye_t[0], eye_t[1], eye_t[2]);
+  }
+}
+// ... of sample `sidx` of pixel (x, y): camera_ray_dir's seed and jitter draws, u3 and u4 under a lens (R.lens_radius > 0, k as for
+// camera_ray_lens), then ut.  *rng is left after the three or five draws.  The statements of shade_record's shutter arm (jade_hip.hip);
+// the denoiser's guide pass calls it.
+static __device__ __forceinline__ jvec3 camera_ray_shutter(const RenderConst& R, const ShutterConst& H, float k, int x, int y, uint32_t sidx, uint32_t* rng,
+                                                           jvec3* origin) {
+  *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
+  float fx = (float)x + jade_rand(rng);
+  double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
+  float left_offset = (float)(lo * R.aspect);
+  float fy = (float)y + jade_rand(rng);
+  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  float u3 = 0.0f, u4 = 0.0f;
+  if (R.lens_radius > 0.0f) {
+    u3 = jade_rand(rng);
+    u4 = jade_rand(rng);
+  }
+  const float ut = jade_rand(rng);
+  jvec3 dir;
+  shutter_ray(R.cam, R.eye, H, R.lens_radius, k, left_offset, up_offset, u3, u4, ut, origin, &dir);
+  return dir;
+}
+
 // ACESToneMapping (or the preview's Reinhard operator) + gamma + BGR pack of one pixel's linear colour m, PathTrace.cu:669-682,
 // 1457-1473 / pass3.fsh:8-18: k_resolve's statements, shared with the denoiser's output kernel and - compiled for the host, from
 // the same jade_fpmath.h routines under the same flags - with jade_render_multi's pack of the gathered frame.  out: 3 bytes, B G R.

@@ -212,9 +212,12 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // (either untouched, or parked at ST_VERTEX with its path state stored).  Same statements either
 // way: the lean paths are the shared helpers consume_mirror / begin_bounce_lean / bounce_mirror.
 // LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the k_shade*_lens kernels only)
-template <bool LEAN, bool ENVIS = false, bool LENS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// SHUTTER: the camera ray leaves the pose of a time drawn within the exposure, through a lens or not (include/jade_bvh.h, "The shutter,
+// stated"; non-parity; the k_shade*_shutter kernels only, which pass their ShutterConst as H)
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
-                                                    uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer) {
+                                                    uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
+                                                    const ShutterConst* H = nullptr) {
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -365,7 +368,18 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         float fy = (float)y + jade_rand(&c.rng);
         float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
         jvec3 dir;
-        if (LENS) {
+        if (SHUTTER) {
+          // the lens's two draws if there is a lens (wave-uniform), then the time's; the origin is the ray's own, stored as the lens's is
+          float u3 = 0.0f, u4 = 0.0f;
+          if (R.lens_radius > 0.0f) {
+            u3 = jade_rand(&c.rng);
+            u4 = jade_rand(&c.rng);
+          }
+          const float ut = jade_rand(&c.rng);
+          jvec3 org;
+          shutter_ray(R.cam, R.eye, *H, R.lens_radius, P.lens_k, left_offset, up_offset, u3, u4, ut, &org, &dir);
+          px.set_origin(org, -1);
+        } else if (LENS) {
           // two more draws before any draw of the path, and an origin of the ray's own: stored with "no source triangle" (-1), which
           // shade_tail, k_trace's refill and k_ray_keys read as they read jade_trace_rays' rays
           const float u3 = jade_rand(&c.rng);
@@ -524,11 +538,11 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-template <bool ENVIS, bool LENS = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below) {
+                                               uint32_t stop_below, const ShutterConst* H = nullptr) {
   const uint32_t n = n_dev ? *n_dev : n_host;
   // A pass of a batch (prev = the pass before it, on the device): nothing to do once the paths have ended (that pass
   // emitted no ray) or once fewer than stop_below records are active - the point where the host would hand the rest to
@@ -546,7 +560,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS>(S, P, R, tile_ids, target_spp, p, c, st, defer);
+  shade_record<false, ENVIS, LENS, SHUTTER>(S, P, R, tile_ids, target_spp, p, c, st, defer, H);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -574,6 +588,19 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_en
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below) {
   shade_kernel_body<true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
+}
+// ... and under a shutter (jade_scene_set_shutter, non-parity), with a lens or without: the shutter's constants are one more argument, the last
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, ShutterConst H) {
+  shade_kernel_body<false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &H);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_envis_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, ShutterConst H) {
+  shade_kernel_body<true, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &H);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -872,6 +899,19 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_lens(DevScene S,
   uint32_t st;
   bool defer;
   shade_record<true, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
+  shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
+}
+// ... under a shutter: the same kernel with the shutter ray in its camera arm
+__global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                                                         uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
+                                                                         QueueCtl* qc, DevCounters* ctr, ShutterConst H) {
+  const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  ShadeCtx c;
+  c.n_emit_rays = 0;
+  c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
+  uint32_t st;
+  bool defer;
+  shade_record<true, false, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer, &H);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 
@@ -2080,6 +2120,31 @@ int jade_scene_get_lens(jade_scene* s, jade_lens_params* out) {
   return JADE_OK;
 }
 
+// The shutter of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_shutter(jade_scene* s, const jade_shutter_params* sh) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (!sh) {
+    s->shutter = jade_shutter_params{};
+    s->shutter_set = false;
+    return JADE_OK;
+  }
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite(sh->eye_close[i])) return jade_fail(JADE_ERR_INVALID, "eye_close must be finite");
+  for (int j = 0; j < 16; ++j)
+    if (!std::isfinite(sh->camera_close[j])) return jade_fail(JADE_ERR_INVALID, "camera_close must be finite");
+  if (!std::isfinite(sh->t_open) || !std::isfinite(sh->t_close) || !(0.0f <= sh->t_open && sh->t_open <= sh->t_close && sh->t_close <= 1.0f))
+    return jade_fail(JADE_ERR_INVALID, "the shutter interval must satisfy 0 <= t_open <= t_close <= 1");
+  s->shutter = *sh;
+  s->shutter_set = true;
+  return JADE_OK;
+}
+int jade_scene_get_shutter(jade_scene* s, jade_shutter_params* out, int* is_set) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (out) *out = s->shutter_set ? s->shutter : jade_shutter_params{};
+  if (is_set) *is_set = s->shutter_set ? 1 : 0;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -2239,6 +2304,9 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->ps.env_sampling = rp->env_sampling == JADE_ENV_IMPORTANCE ? 1u : 0u;
   memcpy(s->ps.eye, rp->eye, sizeof s->ps.eye);
   s->ps.lens_k = lens_k;  // (setup_state wrote the record layout into s->ps)
+  // ... and its shutter: the constants of the statement, one float subtraction each
+  s->sh_on = s->shutter_set;
+  s->sh = s->sh_on ? shutter_const(rp->eye, rp->camera, s->shutter.eye_close, s->shutter.camera_close, s->shutter.t_open, s->shutter.t_close) : ShutterConst{};
   HIP_TRY(upload(s->b_tiles, s->tile_ids.data(), s->tile_ids.size(), s->stream));
   HIP_TRY(hipMemsetAsync(s->b_ctr.p, 0, sizeof(DevCounters) * JADE_CTR_SHARDS, s->stream));
   hipLaunchKernelGGL(k_init, dim3((unsigned)((npix64 + 255) / 256)), dim3(256), 0, s->stream, s->ps);
@@ -2276,6 +2344,7 @@ struct PassRun {
   uint32_t target_spp;
   QueueCtl* qc;                       // s->b_ctl: entry 0 for passes the host follows, the ring for a batch
   decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
+  decltype(&k_shade_shutter) shade_kernel_shutter = nullptr;  // under a shutter: the kernel launched instead, with s->sh as its last argument
   bool batching, tail_ok;
   uint32_t tail_max;                  // active records at or below which k_tail finishes the list
   uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
@@ -2336,8 +2405,12 @@ static int launch_arm(jade_scene* s, uint32_t target_spp, QueueCtl* ctl, size_t 
 static void launch_shade(const PassRun& r, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
                          const QueueCtl* prev, uint32_t stop_below) {
   jade_scene* s = r.s;
-  hipLaunchKernelGGL(r.shade_kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, list,
-                     n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below);
+  if (r.shade_kernel_shutter)
+    hipLaunchKernelGGL(r.shade_kernel_shutter, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
+                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, s->sh);
+  else
+    hipLaunchKernelGGL(r.shade_kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, list,
+                       n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below);
 }
 
 // a finished k_trace launch, timed by the events (a, b)
@@ -2358,8 +2431,12 @@ static int account_pending_trace(PassRun& r) {
 // A render under a thin lens (jade_scene_set_lens; taken by jade_render_begin) runs the lens kernels: k_shade_lean_lens + k_shade_lens /
 // k_shade_envis_lens + k_trace, the schedule JADE_FUSED=0 JADE_TAIL=0 gives the pinhole.  k_light, k_light_packet, k_tail and
 // k_shade_binned have no lens form, so JADE_FUSED, JADE_LIGHT_PACKET, JADE_TAIL and JADE_SHADE_BINNED have no effect there.
+// A render under a shutter (jade_scene_set_shutter) runs the same schedule with the shutter kernels, which handle "with a lens" and "without"
+// themselves.  What the schedule asks is own_origin: the camera ray has an origin of its own, stored per record.
 static bool lens_on(const jade_scene* s) { return s->rc.lens_radius > 0.0f; }
-static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !lens_on(s); }
+static bool shutter_on(const jade_scene* s) { return s->sh_on; }
+static bool own_origin(const jade_scene* s) { return lens_on(s) || shutter_on(s); }
+static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s); }
 
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
 // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.
@@ -2543,9 +2620,14 @@ static int shade_pass(PassRun& r, bool lean_mode) {
     r.cur = 0;
   } else if (lean_mode) {
     // b_active[1] carries the hand-over list; no active list is kept in this mode
-    hipLaunchKernelGGL(lens_on(s) ? k_shade_lean_lens : k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
-                       s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(),
-                       s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
+    if (shutter_on(s))
+      hipLaunchKernelGGL(k_shade_lean_shutter, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream,
+                         s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(), s->b_queue.as<uint32_t>(), qc,
+                         s->b_ctr.as<DevCounters>(), s->sh);
+    else
+      hipLaunchKernelGGL(lens_on(s) ? k_shade_lean_lens : k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
+                         s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(),
+                         s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
     if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
     // only a record that was active can be handed over: n_active bounds the grid, the count stays on the device
     launch_shade(r, nb, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, nullptr, qc, nullptr, 0u);
@@ -2663,8 +2745,9 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   // environment rays by importance: a bounce may then emit no ray at all and is folded in on the spot, which the binned form does not do
   r.shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
   if (lens_on(s)) r.shade_kernel = s->ps.env_sampling ? k_shade_envis_lens : k_shade_lens;
+  if (shutter_on(s)) r.shade_kernel_shutter = s->ps.env_sampling ? k_shade_envis_shutter : k_shade_shutter;
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !lens_on(s);  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s);  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
   r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);

@@ -177,6 +177,10 @@ struct jade_scene {
   int n_objects = 0;
   int bvh_depth = 0;
   jade_lens_params lens{};    // jade_scene_set_lens: what the next jade_render_begin takes (the render in progress keeps its own: rc.lens_radius, ps.lens_k)
+  jade_shutter_params shutter{};  // jade_scene_set_shutter, if shutter_set: what the next jade_render_begin takes ...
+  bool shutter_set = false;
+  ShutterConst sh{};          // ... and what the render in progress took: the argument of the shutter kernels, if sh_on
+  bool sh_on = false;
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;

@@ -66,6 +66,23 @@ def camera_orbit(r=4.0, up_deg=0.0, rot_deg=0.0, center=(0, 0, 0)):
     return eye, cam
 
 
+def camera_move(eye, cam, truck=None, orbit_deg=0.0, pivot=None):
+    """jadeh_camera_move: (eye[3], camera[16]) after a truck (a translation in camera space) and then a rotation by `orbit_deg` about the
+    axis through `pivot` parallel to the camera's up column (pivot None: the eye, a pan) - a second pose for Scene.set_shutter."""
+    e = np.ascontiguousarray(eye, np.float32)
+    m = np.ascontiguousarray(cam, np.float32)
+    t = None if truck is None else np.ascontiguousarray(truck, np.float32)
+    c = None if pivot is None else np.ascontiguousarray(pivot, np.float32)
+    assert e.shape == (3,) and m.shape == (16,) and (t is None or t.shape == (3,)) and (c is None or c.shape == (3,))
+    eye_out = np.zeros(3, np.float32)
+    cam_out = np.zeros(16, np.float32)
+    lib = host_lib()
+    if lib.jadeh_camera_move(e.ctypes.data, m.ctypes.data, None if t is None else t.ctypes.data, float(orbit_deg),
+                             None if c is None else c.ctypes.data, eye_out.ctypes.data, cam_out.ctypes.data) != 0:
+        raise RuntimeError(lib.jadeh_last_error().decode())
+    return eye_out, cam_out
+
+
 class HostScene:
     """Flattened scene: the arrays that cross the jade_rt.h boundary."""
 

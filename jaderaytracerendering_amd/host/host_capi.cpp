@@ -227,6 +227,53 @@ int jadeh_focus_distance(jadeh_trace_rays_fn trace_rays, jade_scene* scene, cons
   return 0;
 }
 
+int jadeh_camera_move(const float eye[3], const float cam[16], const float truck[3], float orbit_deg, const float pivot[3], float eye_out[3],
+                      float cam_out[16]) {
+  if (!eye || !cam || !eye_out || !cam_out) return fail("camera_move: bad arguments");
+  bool finite = std::isfinite(orbit_deg);
+  for (int i = 0; i < 3; ++i) finite = finite && std::isfinite(eye[i]) && (!truck || std::isfinite(truck[i])) && (!pivot || std::isfinite(pivot[i]));
+  for (int j = 0; j < 16; ++j) finite = finite && std::isfinite(cam[j]);
+  if (!finite) return fail("camera_move: non-finite argument");
+  double e[3], col[3][3], a[3];
+  for (int c = 0; c < 3; ++c)
+    for (int r = 0; r < 3; ++r) col[c][r] = cam[4 * c + r];
+  const double ulen = std::sqrt(col[1][0] * col[1][0] + col[1][1] * col[1][1] + col[1][2] * col[1][2]);
+  if (!(ulen > 0.0)) return fail("camera_move: the camera's up column has length 0");
+  for (int r = 0; r < 3; ++r) a[r] = col[1][r] / ulen;
+  // the truck, in camera space
+  const bool trucked = truck && (truck[0] != 0.0f || truck[1] != 0.0f || truck[2] != 0.0f);  // (a zero move returns the pose bit for bit, a -0 included)
+  for (int r = 0; r < 3; ++r) e[r] = trucked ? (double)eye[r] + (col[0][r] * truck[0] + col[1][r] * truck[1] + col[2][r] * truck[2]) : (double)eye[r];
+  // the rotation about the axis through the pivot (Rodrigues): v cos + (a x v) sin + a (a . v) (1 - cos)
+  const double th = (double)orbit_deg * 0.017453292519943295;
+  const double cs = std::cos(th), sn = std::sin(th);
+  auto rotate = [&](const double v[3], double out[3]) {
+    if (orbit_deg == 0.0f) {
+      for (int r = 0; r < 3; ++r) out[r] = v[r];
+      return;
+    }
+    const double d = a[0] * v[0] + a[1] * v[1] + a[2] * v[2];
+    const double x[3] = {a[1] * v[2] - a[2] * v[1], a[2] * v[0] - a[0] * v[2], a[0] * v[1] - a[1] * v[0]};
+    for (int r = 0; r < 3; ++r) out[r] = v[r] * cs + x[r] * sn + a[r] * d * (1.0 - cs);
+  };
+  double rel[3], turned[3], centre[3];
+  for (int r = 0; r < 3; ++r) centre[r] = pivot ? (double)pivot[r] : e[r];
+  for (int r = 0; r < 3; ++r) rel[r] = e[r] - centre[r];
+  rotate(rel, turned);
+  float m[16];
+  memcpy(m, cam, sizeof m);
+  for (int c = 0; c < 3; ++c) {
+    double t[3];
+    rotate(col[c], t);
+    for (int r = 0; r < 3; ++r) m[4 * c + r] = (float)t[r];
+  }
+  for (int r = 0; r < 3; ++r) {
+    eye_out[r] = orbit_deg == 0.0f ? (float)e[r] : (float)(centre[r] + turned[r]);
+    m[12 + r] = eye_out[r];
+  }
+  memcpy(cam_out, m, sizeof m);
+  return 0;
+}
+
 int jadeh_write_bmp(const char* path, const uint8_t* bgr, int w, int h) { return write_bmp(path, bgr, w, h) ? 0 : fail("write_bmp failed"); }
 int jadeh_write_ppm(const char* path, const uint8_t* bgr, int w, int h) { return write_ppm(path, bgr, w, h) ? 0 : fail("write_ppm failed"); }
 int jadeh_write_pfm(const char* path, const float* rgb, int w, int h) { return write_pfm(path, rgb, w, h) ? 0 : fail("write_pfm failed"); }

@@ -47,6 +47,8 @@ struct Api {
   // ... and only for --aperture (jade_trace_rays: --focus-at)
   int (*scene_set_lens)(jade_scene*, const jade_lens_params*) = nullptr;
   jadeh_trace_rays_fn trace_rays = nullptr;
+  // ... and only for --shutter-truck / --shutter-orbit
+  int (*scene_set_shutter)(jade_scene*, const jade_shutter_params*) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -97,6 +99,12 @@ static void usage() {
           "                reference's samples; include/jade_bvh.h).  It needs exactly one of --focus D, the depth D > 0 of the plane of focus\n"
           "                along the camera's axis, and --focus-at PX,PY, which focuses on what the centre of pixel (PX, PY) shows (row 0 =\n"
           "                the bottom row) and prints the distance found; onto the sky it exits 1\n"
+          "                   [--shutter-truck DX,DY,DZ] [--shutter-orbit DEG [--shutter-pivot X,Y,Z]] [--shutter-interval T0,T1]\n"
+          "  --shutter-truck / --shutter-orbit: motion blur (HIP backend only; NOT the reference's samples; include/jade_bvh.h).  The shutter\n"
+          "                opens at the configuration's pose and closes at that pose moved by DX,DY,DZ in camera space (x right, y up, z\n"
+          "                backwards) and then turned by DEG degrees about the axis through X,Y,Z parallel to the camera's up (default: the\n"
+          "                eye, a pan; the subject's position gives a turntable).  --shutter-interval T0,T1 with 0 <= T0 <= T1 <= 1 exposes\n"
+          "                that part of the move only (default 0,1).  Keep DEG to a few degrees; with --aperture, both blurs apply\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -136,11 +144,24 @@ int main(int argc, char** argv) {
   double glare_strength = 0.0, glare_levels = 6, glare_falloff = 0.5;
   bool use_aperture = false, have_focus = false, have_focus_at = false;
   double aperture = 0.0, focus = 0.0, focus_px = 0, focus_py = 0;
+  bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
+  double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
     char* end = nullptr;
     const double x = strtod(v, &end);
     if (end == v || *end != 0 || !std::isfinite(x)) { fprintf(stderr, "%s: not a finite number: %s\n", flag, v); exit(2); }
     return x;
+  };
+  // n finite numbers separated by commas
+  auto numbers = [&](const char* flag, const char* v, double* out, int n) {
+    std::string rest = v;
+    for (int k = 0; k < n; ++k) {
+      const size_t comma = rest.find(',');
+      if ((comma == std::string::npos) != (k == n - 1)) { fprintf(stderr, "%s: expected %d numbers separated by commas: %s\n", flag, n, v); return false; }
+      out[k] = number(flag, rest.substr(0, comma).c_str());
+      if (k < n - 1) rest = rest.substr(comma + 1);
+    }
+    return true;
   };
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -193,6 +214,10 @@ int main(int argc, char** argv) {
       focus_py = number("--focus-at", v.substr(comma + 1).c_str());
       have_focus_at = true;
     }
+    else if (a == "--shutter-truck") { if (!numbers("--shutter-truck", need("--shutter-truck"), truck, 3)) return 2; have_truck = true; }
+    else if (a == "--shutter-orbit") { orbit_deg = number("--shutter-orbit", need("--shutter-orbit")); have_orbit = true; }
+    else if (a == "--shutter-pivot") { if (!numbers("--shutter-pivot", need("--shutter-pivot"), pivot, 3)) return 2; have_pivot = true; }
+    else if (a == "--shutter-interval") { if (!numbers("--shutter-interval", need("--shutter-interval"), interval, 2)) return 2; have_interval = true; }
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
@@ -213,6 +238,18 @@ int main(int argc, char** argv) {
   if (have_focus && (!((float)focus > 0.0f) || !std::isfinite((float)focus))) { fprintf(stderr, "--focus must be > 0\n"); return 2; }
   if (have_focus_at && !(focus_px >= 0 && focus_py >= 0 && focus_px <= (1 << 30) && focus_py <= (1 << 30) && focus_px == (int)focus_px && focus_py == (int)focus_py)) {
     fprintf(stderr, "--focus-at needs two whole numbers PX,PY >= 0\n");
+    return 2;
+  }
+  const bool use_shutter = have_truck || have_orbit;
+  if ((have_pivot && !have_orbit) || (have_interval && !use_shutter)) {
+    fprintf(stderr, "--shutter-pivot belongs to --shutter-orbit, --shutter-interval to --shutter-truck or --shutter-orbit\n");
+    return 2;
+  }
+  for (int i = 0; i < 3; ++i)
+    if (!std::isfinite((float)truck[i]) || !std::isfinite((float)pivot[i])) { fprintf(stderr, "--shutter-truck and --shutter-pivot must be finite\n"); return 2; }
+  if (!std::isfinite((float)orbit_deg)) { fprintf(stderr, "--shutter-orbit must be finite\n"); return 2; }
+  if (!((float)interval[0] >= 0.0f && (float)interval[0] <= (float)interval[1] && (float)interval[1] <= 1.0f)) {
+    fprintf(stderr, "--shutter-interval needs 0 <= T0 <= T1 <= 1\n");
     return 2;
   }
   if (config.empty() == args_file.empty()) { usage(); return 2; }
@@ -294,6 +331,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (use_shutter) {
+    *(void**)(&api.scene_set_shutter) = dlsym(api.h, "jade_scene_set_shutter");
+    if (!api.scene_set_shutter) {
+      fprintf(stderr, "--shutter-truck / --shutter-orbit need the HIP backend: %s has no jade_scene_set_shutter\n", backend.c_str());
+      return 2;
+    }
+  }
   // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
   const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
   if (need_display) {
@@ -331,6 +375,19 @@ int main(int argc, char** argv) {
     }
     if (api.scene_set_lens(dev, &lens) != JADE_OK) { fprintf(stderr, "lens: %s\n", api.last_error()); return 1; }
     printf("lens: aperture radius %.9g, focus distance %.9g\n", lens.aperture_radius, lens.focus_distance);
+  }
+  if (use_shutter) {
+    jade_shutter_params sh;
+    const float truck_f[3] = {(float)truck[0], (float)truck[1], (float)truck[2]}, pivot_f[3] = {(float)pivot[0], (float)pivot[1], (float)pivot[2]};
+    if (jadeh_camera_move(rp.eye, rp.camera, truck_f, (float)orbit_deg, have_pivot ? pivot_f : nullptr, sh.eye_close, sh.camera_close) != 0) {
+      fprintf(stderr, "shutter: %s\n", jadeh_last_error());
+      return 1;
+    }
+    sh.t_open = (float)interval[0];
+    sh.t_close = (float)interval[1];
+    if (api.scene_set_shutter(dev, &sh) != JADE_OK) { fprintf(stderr, "shutter: %s\n", api.last_error()); return 1; }
+    printf("shutter: closes at eye (%.9g, %.9g, %.9g), exposure %.9g .. %.9g of the move\n", sh.eye_close[0], sh.eye_close[1], sh.eye_close[2], sh.t_open,
+           sh.t_close);
   }
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
