@@ -487,6 +487,12 @@ int jade_debug_prepare_scene_host(const jade_scene_desc* d, int32_t wide_mode, c
   return JADE_OK;
 }
 
+// The two queue rules of jade_runtime.h as setup_state and launch_trace use them (tests/test_queue_rules_cpu.py): the ray-record boundary of a
+// queue of `slots` positions (enabled: Tunables.ray_records; hook: JADE_RAYQ_CAP), and the rays a wave of k_trace claims per queue atomic in a
+// launch of n_rays over `waves` waves (hook: JADE_TRACE_CHUNK_RAYS).  The environment is not read.  No HIP call.
+int64_t jade_debug_ray_record_cap_host(uint64_t slots, int32_t enabled, int64_t hook) { return (int64_t)ray_record_cap((size_t)slots, enabled != 0, hook); }
+uint32_t jade_debug_trace_chunk_host(uint32_t n_rays, uint64_t waves, uint32_t hook) { return trace_chunk_for(n_rays, waves, hook); }
+
 // The rows jade_debug_exit_search runs: every obj_idx[i] names an object and every u[i] lies in [0, 1] (a NaN does not).  exit_search
 // forms its table cell from u x Gn: a row outside that range would read past the object's table - a wild read on a device, which no
 // assertion there could catch - so the rows are refused here, on the host, before anything is launched.  No HIP call.

@@ -2180,11 +2180,11 @@ static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lane
   // ray records for the head of the queue (PathState.rayq): as many as an eighth of all slots - a pass after the fused first one
   // queues rays for a few per cent of the records - but every slot of a small render; none when switched off
   {
-    size_t cap = s->tun.ray_records ? std::max<size_t>((K * N + 7) / 8, std::min<size_t>(K * N, (size_t)1 << 22)) : 0;
-    cap = std::min<size_t>(cap, K * N);
+    const size_t cap = ray_record_cap(K * N, s->tun.ray_records, 0);
     if (cap) HIP_TRY(s->b_rayq.alloc(cap * 48));
     P.rayq = cap ? s->b_rayq.as<float4>() : nullptr;
-    P.rayq_cap = (uint32_t)std::min<size_t>(cap, 0xffffffffu);
+    // (JADE_RAYQ_CAP lowers the boundary, not the allocation: a position either side of a lowered boundary is still inside b_rayq)
+    P.rayq_cap = (uint32_t)std::min<size_t>(ray_record_cap(K * N, s->tun.ray_records, s->tun.rayq_cap), 0xffffffffu);
   }
   // b_active[0] doubles as k_light's per-wave hand-over regions: up to 64 records of slack per wave of its grid
   const size_t first_pass_blocks = (size_t)std::max(s->light_blocks, s->packet_blocks);
@@ -2294,6 +2294,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->tail_pending = false;
   s->carried_active = 0;
   s->packets_given_up = 0;
+  s->rays_recorded = s->rays_indexed = 0;
   s->tile_n.clear();
   s->adaptive_done = false;
   s->dn_carried = jade_stats{};
@@ -2375,20 +2376,26 @@ static uint32_t carry_threshold(const jade_scene* s, bool may_carry, uint32_t n_
   return (uint32_t)std::max(a, b);
 }
 
-// Rays claimed per queue atomic: large launches amortise the atomic over up to
-// JADE_TRACE_CHUNK rays, small ones keep 64 so every wave gets work.
+// Rays claimed per queue atomic (trace_chunk_for, jade_runtime.h).  n_rays = 0 - a pass of a batch (run_batch), whose queue length only the
+// device knows: 0, "size them yourself" - unless JADE_TRACE_CHUNK_RAYS names the size: then the device takes the host's value here too.
 static uint32_t trace_chunk(const jade_scene* s, uint32_t n_rays) {
-  uint64_t waves = (uint64_t)s->trace_blocks * (JADE_TRACE_BLOCK / 64);
-  uint64_t per = n_rays / (waves * 64 * 8);  // aim at >= 8 grabs per wave
-  if (per < 1) per = 1;
-  if (per > JADE_TRACE_CHUNK / 64) per = JADE_TRACE_CHUNK / 64;
-  return (uint32_t)per * 64u;
+  const uint32_t hook = s->tun.trace_chunk_rays;
+  if (n_rays == 0) return trace_chunk_hook_ok(hook) ? hook : 0u;
+  return trace_chunk_for(n_rays, (uint64_t)s->trace_blocks * (JADE_TRACE_BLOCK / 64), hook);
 }
 
 void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays) {
   const bool wide = trace_wide(s->dev, P);
   hipLaunchKernelGGL(wide ? k_trace_wide : k_trace, dim3((unsigned)(wide ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream,
-                     s->dev, P, queue, qc, spill, ctr, n_rays ? trace_chunk(s, n_rays) : 0u);
+                     s->dev, P, queue, qc, spill, ctr, trace_chunk(s, n_rays));
+}
+
+// A k_trace launch of a render took the n rays of queue positions 0 .. n-1 (an ordered queue: the same positions in another order): those
+// below the record boundary came as records, the rest through the index queue.  Host arithmetic on a count the host has read anyway.
+static void count_queue(jade_scene* s, uint32_t n) {
+  const uint32_t below = std::min(n, s->ps.rayq_cap);
+  s->rays_recorded += below;
+  s->rays_indexed += n - below;
 }
 
 // k_arm: clears the first `clear_bytes` of *ctl, then lists the records with work in b_active[0] and counts them in ctl->active
@@ -2540,6 +2547,7 @@ static int run_batch(PassRun& r) {
       break;
     }
     if (int rc = account_trace(r, s->ev_batch[2 * j], s->ev_batch[2 * j + 1])) return rc;
+    count_queue(s, host_ring[j].count);
     pass_timed = j + 1;
     r.n_active = host_ring[j].active;
     ++r.pass_no;
@@ -2713,6 +2721,7 @@ static int run_host_pass(PassRun& r, bool lean_mode) {
   tps.idxq = trace_queue != s->b_queue.as<uint32_t>() ? s->b_queue.as<uint32_t>() : nullptr;
   launch_trace(s, tps, trace_queue, r.qc, s->b_spill.as<uint32_t>(), s->b_ctr.as<DevCounters>(), r.host_ctl[0]);
   HIP_TRY(hipGetLastError());
+  count_queue(s, r.host_ctl[0]);
   HIP_TRY(hipEventRecord(r.ev(PassRun::TB), s->stream));
   r.trace_pending = true;
   if (r.carry_now(r.n_active)) {
@@ -3111,6 +3120,15 @@ int jade_debug_scene_grids(jade_scene* s, int32_t out[4]) {
   out[1] = s->trace_blocks_wide;
   out[2] = s->light_blocks;
   out[3] = s->packet_blocks;
+  return JADE_OK;
+}
+// the rays k_trace took, since jade_render_begin, from queue positions below the record boundary (out[0]: as ray records) and at or beyond it
+// (out[1]: through the index queue) - summed over the launches whose queue counts the host reads (run_host_pass, run_batch).  k_tail's own rays
+// are not counted: it runs with no records.  Host code only.
+int jade_debug_ray_record_use(jade_scene* s, int64_t out[2]) {
+  if (!s || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  out[0] = s->rays_recorded;
+  out[1] = s->rays_indexed;
   return JADE_OK;
 }
 

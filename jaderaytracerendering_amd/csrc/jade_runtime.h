@@ -139,6 +139,11 @@ struct Tunables {
   bool tail = true;           // JADE_TAIL=0: no k_tail - the last paths are finished by passes, as before round 4
   uint32_t tail_max = JADE_TAIL_MAX;  // JADE_TAIL_MAX: active records at or below which k_tail takes over
   bool anyhit = true;         // JADE_ANYHIT=0: no occluder cache (JADE_WALK_EARLY_EXIT_CACHED then walks as JADE_WALK_EARLY_EXIT)
+  long long rayq_cap = 0;     // JADE_RAYQ_CAP=<entries>: test hook - lowers PathState.rayq_cap (never raises it; b_rayq keeps the rule's size), so that a
+                              // small render queues rays on both sides of the record boundary (ray_record_cap; tests/test_gpu_ray_records.py).  <= 0: the rule
+  uint32_t trace_chunk_rays = 0;  // JADE_TRACE_CHUNK_RAYS=<64|128|...|512>: test hook - the rays a wave of k_trace claims per queue atomic, in place of the
+                              // rule's answer on the host and on the device (trace_chunk_for; tests/test_gpu_trace_chunks.py); k_tail claims nothing.
+                              // Anything but a multiple of 64 in 64..512 is ignored.  Results must depend on neither hook
   void read() {
     auto flag0 = [](const char* n) { const char* e = getenv(n); return e && atoi(e) == 0; };
     anyhit = !flag0("JADE_ANYHIT");
@@ -163,8 +168,32 @@ struct Tunables {
     if (const char* e = getenv("JADE_SORT_MIN")) sort_min = (uint32_t)atoi(e);
     if (const char* e = getenv("JADE_PACKET_BUDGET")) packet_budget = atoi(e);
     if (const char* e = getenv("JADE_WIDE")) wide_mode = atoi(e) > 0 ? 1 : 0;
+    if (const char* e = getenv("JADE_RAYQ_CAP")) rayq_cap = atoll(e);
+    if (const char* e = getenv("JADE_TRACE_CHUNK_RAYS")) trace_chunk_rays = (uint32_t)atoi(e);
   }
 };
+
+// The ray queue's record boundary (setup_state): of `slots` queue positions the first ray_record_cap have a 48-B ray record (PathState.rayq) -
+// an eighth of all slots, but every slot of a render of up to 2^22; none when the records are switched off.  hook > 0 (JADE_RAYQ_CAP) may
+// only lower the answer.  Pure: no HIP call, no scene (tests/test_queue_rules_cpu.py).
+static inline size_t ray_record_cap(size_t slots, bool enabled, long long hook) {
+  size_t cap = enabled ? std::max<size_t>((slots + 7) / 8, std::min<size_t>(slots, (size_t)1 << 22)) : 0;
+  cap = std::min<size_t>(cap, slots);
+  if (hook > 0) cap = std::min<size_t>(cap, (size_t)hook);
+  return cap;
+}
+// Rays claimed per queue atomic by a wave of k_trace: large launches amortise the atomic over up to JADE_TRACE_CHUNK rays, small ones keep
+// 64 so every wave gets work (the aim: >= 8 claims per wave).  trace_body states the same rule on the device for batched passes, whose
+// queue length the host has not seen.  hook (JADE_TRACE_CHUNK_RAYS): a multiple of 64 in 64..JADE_TRACE_CHUNK replaces the answer, anything
+// else is ignored.  Pure.
+static inline bool trace_chunk_hook_ok(uint32_t hook) { return hook >= 64u && hook <= (uint32_t)JADE_TRACE_CHUNK && hook % 64u == 0u; }
+static inline uint32_t trace_chunk_for(uint32_t n_rays, uint64_t waves, uint32_t hook) {
+  if (trace_chunk_hook_ok(hook)) return hook;
+  uint64_t per = n_rays / (std::max<uint64_t>(waves, 1) * 64 * 8);
+  if (per < 1) per = 1;
+  if (per > JADE_TRACE_CHUNK / 64) per = JADE_TRACE_CHUNK / 64;
+  return (uint32_t)per * 64u;
+}
 
 struct jade_scene {
   int device = 0;
@@ -200,6 +229,8 @@ struct jade_scene {
   int64_t spp_done = 0;
   bool tail_pending = false;  // the last step left its longest paths unfinished (jade_render_flush)
   uint32_t carried_active = 0;  // ... this many records (0: unknown)
+  int64_t rays_recorded = 0, rays_indexed = 0;  // rays k_trace took since jade_render_begin from queue positions below PathState.rayq_cap / at or beyond it,
+                                                // from the queue counts the host reads anyway (count_queue; jade_debug_ray_record_use)
   DevEvent ev[7];             // run_passes' timing events, made once (ev0, ev1, ta, tb, sa, sb, sm)
   DevEvent ev_resolve;  // jade_render_resolve_tiles_device: caller's stream -> scene stream
   uint64_t host_syncs = 0;    // host waits inside step/flush since the last advance() reported them

@@ -1,0 +1,207 @@
+"""The record boundary of the ray queue ("Ray records"): positions below PathState.rayq_cap are written by shade_tail as 48-byte
+ray records and started by k_trace's refill with walk_begin_prepared; positions at or beyond it go through the index queue and walk_begin.
+The rule gives every slot of a render below 4 M slots a record and JADE_RAY_RECORDS=0 gives none, so no other test has rays on BOTH sides -
+which is what every lens or shutter frame above 4 M records, and C5's ordered 4K frame, run.  JADE_RAYQ_CAP (a test hook: it lowers the
+boundary, never the allocation) puts the boundary inside the queues of three small frames.
+
+Held: every case is, in every float of the radiance, every byte and every counter, the JADE_RAY_RECORDS=0 render of the same schedule; one
+render per frame is held to the oracle at tests/test_gpu_parity.py's bar.  Every case that claims to cross the boundary runs on
+libjade_hip_debug.so and asserts it: jade_debug_ray_record_use reports the rays taken from each side (host arithmetic on the queue counts).
+
+Node records and triangle tests under early exits: which recorded hit ends a walk depends on the other rays of its wave, and a wave's
+second claim on the queue races with the other waves', so on these frames the two counts differ between two runs of ONE configuration
+(tinyjade, JADE_TAIL=0, early exits, three runs: 307 925 / 308 075 / 307 713 node records).  The early-exit cases therefore hold every
+counter but those two, and test_single_wave_passes_count_the_same_work_under_early_exits holds those two where they are a function of the
+inputs: a frame whose every pass is at most 512 rays, claimed whole by one wave (JADE_TRACE_CHUNK_RAYS=512)."""
+import pytest
+
+import queue_hooks as Q
+from conftest import WALK_KEYS, COUNTER_KEYS
+from jaderaytracerendering_amd import _abi
+from test_gpu_parity import TOL, _assert_parity
+
+pytestmark = pytest.mark.gpu
+
+CAPS = (1, 63, 64, 65, 100, 4096)  # around a wave's 64 positions; 4096: above every queue of these frames under the default schedule
+NOT_WALK = tuple(k for k in COUNTER_KEYS if k not in WALK_KEYS)
+
+
+def _cap(n):
+    return {"JADE_RAYQ_CAP": str(n)}
+
+
+def _crossed(out, what):
+    below, beyond = out[3]
+    print(f"record use {what}: {below} below the boundary, {beyond} at or beyond it")
+    assert below > 0 and beyond > 0, f"{what}: the boundary was not crossed ({below} below, {beyond} beyond)"
+
+
+# ------------------------------------------------------------------------------------------ references, rendered once per module --
+
+@pytest.fixture(scope="module")
+def refs(hip_debug):
+    """Per frame, under the default schedule: the JADE_RAY_RECORDS=0 render, and the render under the rule."""
+    out = {}
+    for name in ("tiny", "tinyjade", "C2"):
+        none = Q.render(hip_debug, name, {"JADE_RAY_RECORDS": "0"})
+        rule = Q.render(hip_debug, name, {})
+        out[name] = (none, rule)
+    return out
+
+
+@pytest.fixture(scope="module")
+def oracle_frames(oracle):
+    out = {}
+    for name in ("tiny", "tinyjade", "C2"):
+        hs, p, _ = Q.frame(name)
+        with oracle.scene(hs) as so:
+            out[name] = so.render(p)
+    return out
+
+
+def test_the_rule_gives_these_frames_records_only_and_the_switch_none(refs):
+    """What the suite ran so far: all records, or all indices.  (And the count is what it says: the same rays either way.)"""
+    for name, (none, rule) in refs.items():
+        assert none[3][0] == 0 and none[3][1] > 0, name
+        assert rule[3] == (none[3][1], 0), name
+        Q.assert_same_frame(rule, none, name)
+
+
+# ----------------------------------------------------------------------------------------------- caps under the default schedule --
+
+@pytest.mark.parametrize("name", ["tiny", "tinyjade", "C2"])
+def test_caps_under_the_default_schedule(hip_debug, refs, oracle_frames, name):
+    none, rule = refs[name]
+    total = none[3][1]
+    for cap in CAPS:
+        out = Q.render(hip_debug, name, _cap(cap))
+        Q.assert_same_frame(out, none, (name, cap))
+        assert sum(out[3]) == total, (name, cap, out[3])
+        if cap == 4096:
+            assert out[3] == (total, 0), f"{name}: a queue of this frame is longer than 4096 ({out[3]})"
+        else:
+            _crossed(out, (name, cap))
+        if cap == 100:  # the oracle's frame, at the parity bar of tests/test_gpu_parity.py
+            err = _assert_parity(oracle_frames[name], out[:3], TOL)
+            print(f"{name} cap 100 against the oracle: relative L2 {err:.3g}")
+    # about half the longest queue: halve c from the total until some queue is longer than c - the longest then lies in (c, 2c]
+    c = total
+    while Q.render(hip_debug, name, _cap(c))[3][1] == 0:
+        c //= 2
+        assert c >= 1
+    half = max(3 * c // 4, 1)
+    out = Q.render(hip_debug, name, _cap(half))
+    Q.assert_same_frame(out, none, (name, "half", half))
+    _crossed(out, (name, f"half = {half}"))
+    assert out[3][0] >= half and out[3][1] > half // 3, "the longest queue has about as many rays on either side"
+
+
+def test_the_product_library_reads_the_hook(hip, refs):
+    """libjade_hip.so has no jade_debug_ray_record_use; its host code and its kernels are the debug library's."""
+    for name in ("tiny", "tinyjade"):
+        for cap in (65, 100):
+            out = Q.render(hip, name, _cap(cap))
+            Q.assert_same_frame(out, refs[name][0], (name, cap, "libjade_hip.so"))
+            assert out[3] is None
+
+
+# --------------------------------------------------------------------------------------------------- schedules at caps 65 and 100 --
+
+def _lens(sc, p):
+    sc.set_lens(*Q.LENS)
+
+
+def _shutter(sc, p):
+    sc.set_shutter(*Q.shutter_close(p))
+
+
+def _shutter_lens(sc, p):
+    sc.set_lens(*Q.LENS)
+    sc.set_shutter(*Q.shutter_close(p))
+
+
+EARLY, CACHED = _abi.WALK_EARLY_EXIT, _abi.WALK_EARLY_EXIT_CACHED
+SORT = {"JADE_SORT": "1", "JADE_SORT_MIN": "64"}
+SCHEDULES = {
+    "fused=0": dict(env={"JADE_FUSED": "0"}),
+    "batch=0": dict(env={"JADE_BATCH": "0"}),
+    "shade-split=0": dict(env={"JADE_SHADE_SPLIT": "0"}),
+    "tail=0": dict(env={"JADE_TAIL": "0"}),  # (the frames are small enough for k_tail to finish them after one pass: without it, ~190 batched launches)
+    "fused=0,tail=0,batch=0": dict(env={"JADE_FUSED": "0", "JADE_TAIL": "0", "JADE_BATCH": "0"}),  # every ray through the queue, every pass host-followed
+    "shade-binned=1": dict(env={"JADE_SHADE_BINNED": "1"}),
+    "early-exit": dict(walk=EARLY),
+    "early-exit,tail=0": dict(env={"JADE_TAIL": "0"}, walk=EARLY),
+    "early-exit-cached": dict(walk=CACHED),
+    "early-exit-cached-twice": dict(env={"JADE_TAIL": "0"}, walk=CACHED, renders=2),  # the second render of a handle: a warm occluder cache
+    "wide,early-exit": dict(env={"JADE_WIDE": "1", "JADE_TAIL": "0"}, walk=EARLY),
+    "wide,early-exit-cached-twice": dict(env={"JADE_WIDE": "1"}, walk=CACHED, renders=2),
+    "lens": dict(prepare=_lens),
+    "shutter": dict(prepare=_shutter),
+    "shutter+lens": dict(prepare=_shutter_lens),
+    "shutter+lens,early-exit": dict(prepare=_shutter_lens, walk=EARLY),
+    "sorted": dict(env=SORT),
+    "sorted,keys-kernel": dict(env={**SORT, "JADE_SORT_KEYS_KERNEL": "1"}),
+    "sorted,lens": dict(env=SORT, prepare=_lens),
+    "steps,carry=0.01": dict(env={"JADE_CARRY_FRACTION": "0.01"}, steps=(2, 1, 1)),
+    "steps,carry=0.01,tail=0": dict(env={"JADE_CARRY_FRACTION": "0.01", "JADE_TAIL": "0"}, steps=(2, 1, 1)),
+}
+
+
+@pytest.mark.parametrize("schedule", sorted(SCHEDULES))
+def test_schedules_at_caps_65_and_100(hip_debug, schedule):
+    s = SCHEDULES[schedule]
+    env = s.get("env", {})
+    kw = {k: v for k, v in s.items() if k != "env"}
+    keys = NOT_WALK if kw.get("walk", _abi.WALK_REFERENCE) != _abi.WALK_REFERENCE else None  # (the module's docstring)
+    for name, caps in (("tinyjade", (65, 100)), ("tiny", (65,))):
+        none = Q.render(hip_debug, name, {**env, "JADE_RAY_RECORDS": "0"}, **kw)
+        assert none[3][0] == 0 and none[3][1] > 0
+        for cap in caps:
+            out = Q.render(hip_debug, name, {**env, **_cap(cap)}, **kw)
+            Q.assert_same_frame(out, none, (schedule, name, cap), keys)
+            assert sum(out[3]) == none[3][1], "the same rays go through the queue whatever the boundary"
+            _crossed(out, (schedule, name, cap))
+            if keys is not None:
+                assert out[2].rays_cached <= out[2].rays_shadow + out[2].rays_env
+
+
+def test_the_ordered_frame_under_other_schedules(hip_debug):
+    """C2's frame (an ordered queue: sorted positions gather from both sides of the boundary) without k_tail, unfused, and with early exits."""
+    for env, walk in (({"JADE_TAIL": "0"}, _abi.WALK_REFERENCE), ({"JADE_FUSED": "0"}, _abi.WALK_REFERENCE), ({"JADE_TAIL": "0"}, EARLY),
+                      ({"JADE_SORT_KEYS_KERNEL": "1", "JADE_WIDE": "1"}, EARLY)):
+        keys = NOT_WALK if walk != _abi.WALK_REFERENCE else None
+        none = Q.render(hip_debug, "C2", {**env, "JADE_RAY_RECORDS": "0"}, walk=walk)
+        for cap in (65, 100):
+            out = Q.render(hip_debug, "C2", {**env, **_cap(cap)}, walk=walk)
+            Q.assert_same_frame(out, none, (env, walk, cap), keys)
+            _crossed(out, (env, walk, cap))
+
+
+# ------------------------------------------------------------------------------------- early exits, where the work is reproducible --
+
+@pytest.mark.parametrize("name", ["tinyjade-11x11", "C2-11x11"])
+def test_single_wave_passes_count_the_same_work_under_early_exits(hip_debug, name):
+    """11 x 11 pixels with one record each (JADE_RECORDS_PER_PIXEL=1), unfused and without k_tail: no pass queues more than 121 x 4 = 484
+    rays, and with JADE_TRACE_CHUNK_RAYS=512 the first wave to claim takes the whole queue.  One wave is one instruction stream: which lane
+    takes which ray, and so where every early exit falls, is a function of the queue alone - and a ray is the same values as a record and
+    through its index.  So node records and triangle tests are held too: a record that lost its limit (its walk never ends early) shows
+    here and nowhere in the frame."""
+    base = {"JADE_FUSED": "0", "JADE_TAIL": "0", "JADE_TRACE_CHUNK_RAYS": "512"}
+    for extra in ({}, {"JADE_WIDE": "1"}, {"JADE_BATCH": "0"}):
+        env = {**base, **extra}
+        whole = Q.render(hip_debug, name, {**env, **_cap(512)}, walk=EARLY)
+        assert whole[3][1] == 0 and whole[3][0] > 0, f"a pass queued more than 512 rays ({whole[3]})"
+        ref_walk = Q.render(hip_debug, name, {**env, "JADE_RAY_RECORDS": "0"})
+        none = Q.render(hip_debug, name, {**env, "JADE_RAY_RECORDS": "0"}, walk=EARLY)
+        again = Q.render(hip_debug, name, {**env, "JADE_RAY_RECORDS": "0"}, walk=EARLY)
+        Q.assert_same_frame(again, none, (extra, "the same configuration twice"))
+        Q.assert_same_frame(none, ref_walk, (extra, "early exits"), NOT_WALK)
+        print(f"{name} {extra}: node records {none[2].nodes_visited} / {ref_walk[2].nodes_visited}, triangle tests {none[2].tris_tested} / "
+              f"{ref_walk[2].tris_tested} with early exits / without, {none[2].rays} rays")
+        assert none[2].nodes_visited <= ref_walk[2].nodes_visited and none[2].tris_tested <= ref_walk[2].tris_tested
+        assert none[2].nodes_visited + none[2].tris_tested < ref_walk[2].nodes_visited + ref_walk[2].tris_tested, "early exits leave no work out here: the frame cannot show a lost limit"
+        Q.assert_same_frame(whole, none, (extra, 512))
+        for cap in (33, 65, 100):
+            out = Q.render(hip_debug, name, {**env, **_cap(cap)}, walk=EARLY)
+            Q.assert_same_frame(out, none, (extra, cap))
+            _crossed(out, (name, extra, cap))
