@@ -430,6 +430,68 @@ typedef struct jade_shutter_params {
 int jade_scene_set_shutter(jade_scene* scene, const jade_shutter_params* shutter);
 int jade_scene_get_shutter(jade_scene* scene, jade_shutter_params* out, int* is_set);
 
+/* ---- One-light sampling: one emitter per vertex, drawn by power ----
+ *
+ * Non-parity: the reference sends one shadow ray to EVERY entry of emit_indices at every diffuse, SSS-diffuse and BSSRDF vertex
+ * (PathTrace.cu:945-, 1085-, 1281-), so rays, random draws and the size of a path record all grow with the emitter count.  Under
+ * JADE_LIGHTS_ONE such a vertex draws ONE entry, with probability proportional to area x luminance of emission plus a floor, traces
+ * that entry's shadow ray as the reference traces it and divides its term by the probability: another estimator of the SAME integral,
+ * not the reference's sample for sample - none of jade_rt.h's parity statements apply to it, as for JADE_ENV_IMPORTANCE.  A path record
+ * then has min(n_emit, 1) + 2 ray slots whatever n_emit is, so the records per pixel (JADE_Q_RECORDS_PER_PIXEL) and the largest frame
+ * that fits no longer depend on the emitter count.  The mode is a property of the scene handle, read by the next jade_render_begin - so
+ * by jade_render, jade_render_adaptive, jade_render_multi (per scene) - and a render in progress keeps the mode it began with.
+ * JADE_LIGHTS_ALL (0, the default) is today's render in every kernel, bit and counter.  JADE_LIGHTS_ONE composes with both env_sampling
+ * values, the three walks, tile partitions, progressive steps, adaptive sampling, the guides and the denoiser, exposure and glare.
+ *
+ * ---- The lights, stated ----
+ * tests/lights_spec.py is this text in float64.  nE = n_emit; entry i names triangle t_i = emit_indices[i].  Duplicates are separate
+ * entries, and an entry whose triangle does not emit is still an entry.  fl() rounds to fp32.
+ *
+ * The distribution.  a_i = the area the integrator itself multiplies the entry's term by - 0.5f * sqrt(dot(c, c)) with c = cross(p2 - p1,
+ * p3 - p1), every operation one fp32 operation (tri_size, PathTrace.cu:897-903) - and 0 where that is not finite;
+ * l_i = 0.2126 max(er, 0) + 0.7152 max(eg, 0) + 0.0722 max(eb, 0) of t_i's emission, and 0 where that is not finite (a NaN or an
+ * infinite channel); w_i = a_i * l_i, and 0 where that is not finite; floor = 0.01 * (sum of w) / nE, or 1 if the sum is 0;
+ *     p_i = (w_i + floor) / (sum over j of (w_j + floor)),     q_i = p_i * nE     (mean 1, every p_i > 0).
+ * l, w, floor, p and q are formed in double.  The table (made once, at jade_scene_create, by the builder of JADE_ENV_IMPORTANCE's table)
+ * has nE entries {accept, alias, q_own, q_alias}: a draw that lands in slot s takes entry s with probability accept_s and entry alias_s
+ * otherwise (alias_s < nE; 0 <= accept_s <= 1, and alias_s = s where accept_s = 1), such that entry i is drawn with probability
+ * P_i = (accept_i + sum over s != i with alias_s = i of (1 - accept_s)) / nE = p_i up to the fp32 rounding of accept:
+ * |P_i - p_i| <= (1 + m_i) * 2^-24 / nE with m_i the number of slots whose alias is i.  q_own = fl(q_s) and q_alias = fl(q_{alias_s}):
+ * the probability the weight below divides by is the INTENDED one, p.  Which small entry is paired with which large one is not part
+ * of this statement.
+ *
+ * The draw.  Where the reference draws (rand_x, rand_y) for entry 0 (PathTrace.cu:945-, 1085-, 1281-) this mode draws FOUR uniforms
+ * u1..u4 from the sample's stream, in this order, and nothing for the other entries - each is jade_rand's fl(uint32) * 2^-32, in
+ * [0, 1], 1.0f included:
+ *     slot    s = min((uint32)fl(u1 * fl(nE)), nE - 1)                  (the product in fp32: a discrete decision)
+ *     own     iff u2 < accept_s;      i = own ? s : alias_s,   q = own ? q_own_s : q_alias_s
+ *     (rx, ry) = (u3, u4), folded as the reference folds them: if rx + ry > 1 then rx = 1 - rx, ry = 1 - ry
+ *     weight  = fl(fl(nE) / q)                                          (= 1 / p_i up to rounding)
+ * Everything the reference then does for entry i is done for this ONE entry: the point p1 + (p2 - p1) rx + (p3 - p1) ry on t_i; in the
+ * diffuse and SSS-diffuse branch the side test dot(point - vertex, n) * dot(out, n) < 0 and its `continue` (no ray; the four uniforms
+ * stay drawn, every later draw of the sample is where it would be); the shadow ray and its early-exit limit; the hit test
+ * "hitBVH's triangle == t_i"; the entry's term, statement for statement.  The term is multiplied by weight, one fp32 multiplication
+ * per channel, before it is added to l_dir.  nE = 0 draws nothing and traces nothing: the render is JADE_LIGHTS_ALL's in every bit
+ * and counter.  Nothing else of the sample changes: the environment ray (either env_sampling), the roulette and the indirect ray
+ * follow as they do in the reference, behind four draws where the reference has made 2 nE.
+ * The estimator is unbiased because every p_i > 0: E[weight * term_i] = sum over i of p_i * term_i / p_i, the reference's sum.
+ * jade_stats.rays_shadow counts at most one shadow ray per sampling vertex.
+ *
+ * The schedule is JADE_ENV_IMPORTANCE's: the fused first pass stays (it samples no emitter), there is no tail kernel
+ * (tail_launches is 0) and JADE_SHADE_BINNED is ignored.  Results do not depend on steps, tile partitions or records per pixel.
+ *
+ * jade_scene_set_light_sampling: an unknown mode returns JADE_ERR_INVALID and leaves the previous mode in place.
+ * jade_render_begin refuses JADE_LIGHTS_ONE with JADE_ERR_UNSUPPORTED on a scene with more than JADE_LIGHTS_ONE_MAX_ENTRIES emitter
+ * entries (the slot is formed from a 24-bit uniform and reaches every slot only up to 2^24), and together with a lens
+ * (jade_scene_set_lens, aperture_radius > 0) or a shutter (jade_scene_set_shutter): those kernels do not exist yet.
+ * jade_render_multi: all scenes must carry the same mode, else JADE_ERR_INVALID before anything is launched. */
+#define JADE_LIGHTS_ALL 0
+#define JADE_LIGHTS_ONE 1
+#define JADE_LIGHTS_ONE_MAX_ENTRIES 16777216 /* 2^24 */
+
+int jade_scene_set_light_sampling(jade_scene* scene, int mode);
+int jade_scene_get_light_sampling(jade_scene* scene, int* mode);
+
 #ifdef __cplusplus
 }
 #endif

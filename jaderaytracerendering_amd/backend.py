@@ -414,6 +414,22 @@ class Scene:
             return None
         return np.array(sh.eye_close[:], np.float32), np.array(sh.camera_close[:], np.float32), sh.t_open, sh.t_close
 
+    def set_light_sampling(self, mode):
+        """jade_scene_set_light_sampling: _abi.LIGHTS_ALL (the default: a shadow ray to every emitter entry at every sampling vertex, as the
+        reference does) or _abi.LIGHTS_ONE (one entry per vertex, drawn by power and weighted by 1 / its probability; HIP module only;
+        non-parity: include/jade_bvh.h, "The lights, stated").  Taken by the next render this handle begins.
+        JadeError(JADE_ERR_INVALID) leaves the previous mode in place."""
+        fn = self._hip_only("jade_scene_set_light_sampling")
+        self.backend.check(fn(self._h, int(mode)))
+
+    @property
+    def light_sampling(self):
+        """jade_scene_get_light_sampling: the mode the next render of this handle takes."""
+        fn = self._hip_only("jade_scene_get_light_sampling")
+        mode = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(mode)))
+        return mode.value
+
     def focus_distance(self, params, px, py):
         """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
         (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that

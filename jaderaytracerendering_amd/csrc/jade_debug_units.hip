@@ -1,6 +1,6 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
+// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
 // jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py) and the BSSRDF branch's exit-triangle search (exit_search, jade_shade.h, and
 // its tables, guide_tables, jade_scene_prep.hip; tests/test_area_search_cpu.py, tests/test_gpu_area_search.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
@@ -142,6 +142,22 @@ __global__ void k_debug_env_sample(DevScene S, int n, const float* u, float* dir
 }
 
 // row i: the draw as the shading kernel makes it, from RNG state rng[i]; the state it leaves is written back
+// light_sample's body on the four uniforms of row i: the entry drawn, the folded (rx, ry), and the weight twice - as the draw forms it
+// and as consume forms it again from the entry alone (light_weight)
+__global__ void k_debug_light_sample(const uint4* table, uint32_t nE, int n, const float* u, uint32_t* entry, float* rxy, float* weight) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* u4 = u + 4 * i;
+  int k = 0;
+  float rx, ry, w;
+  const uint32_t e = light_sample_with(table, nE, [u4, &k]() { return u4[k++]; }, &rx, &ry, &w);
+  entry[i] = e;
+  rxy[2 * i] = rx;
+  rxy[2 * i + 1] = ry;
+  weight[2 * i] = w;
+  weight[2 * i + 1] = light_weight(table, nE, e);
+}
+
 __global__ void k_debug_env_sample_rng(DevScene S, int n, uint32_t* rng, float* dir, float* ratio) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -353,6 +369,48 @@ int jade_debug_env_alias_host(int32_t w, int32_t h, const float* rgb, uint32_t* 
     out_u32x4[4 * t + 2] = table[t].z;
     out_u32x4[4 * t + 3] = table[t].w;
   }
+  return JADE_OK;
+}
+
+// light_alias_table (jade_scene_prep.hip) on the n_emit entries emit_indices of n_triangles caller's records: out_u32x4[i] = {accept, alias,
+// q_own, q_alias} as bits.  No HIP call.
+int jade_debug_light_table_host(const jade_triangle* triangles, int32_t n_triangles, const int32_t* emit_indices, int32_t n_emit, uint32_t* out_u32x4) {
+  if (!triangles || n_triangles <= 0 || n_emit < 0 || (n_emit > 0 && (!emit_indices || !out_u32x4))) return jade_fail(JADE_ERR_INVALID, "bad argument");
+  if (!light_sampling_fits(n_emit)) return jade_fail(JADE_ERR_UNSUPPORTED, "more emitter entries than JADE_LIGHTS_ONE_MAX_ENTRIES");
+  for (int32_t i = 0; i < n_emit; ++i)
+    if (emit_indices[i] < 0 || emit_indices[i] >= n_triangles) return jade_fail(JADE_ERR_INVALID, "emitter index out of range");
+  std::vector<uint4> table;
+  light_alias_table(triangles, emit_indices, n_emit, table);
+  for (size_t t = 0; t < table.size(); ++t) {
+    out_u32x4[4 * t] = table[t].x;
+    out_u32x4[4 * t + 1] = table[t].y;
+    out_u32x4[4 * t + 2] = table[t].z;
+    out_u32x4[4 * t + 3] = table[t].w;
+  }
+  return JADE_OK;
+}
+
+// (out_entry[i], out_rxy[i][0..1], out_weight[i][0..1]) = light_sample's body on the uniforms u[i][0..3], over the scene's own table: the
+// draw of JADE_LIGHTS_ONE.  out_weight: {the draw's weight, light_weight of the entry drawn}.
+int jade_debug_light_sample(jade_scene* s, int32_t n, const float* u, uint32_t* out_entry, float* out_rxy, float* out_weight) {
+  if (!s || !u || !out_entry || !out_rxy || !out_weight) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (s->n_emit <= 0 || !light_sampling_fits(s->n_emit) || s->b_light_alias.bytes != (size_t)s->n_emit * sizeof(uint4))
+    return jade_fail(JADE_ERR_UNSUPPORTED, "the scene's emitter list is not one JADE_LIGHTS_ONE draws from");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bu, be, bx, bw;
+  HIP_TRY(upload(bu, u, 4 * N, s->stream));
+  HIP_TRY(be.alloc(N * 4));
+  HIP_TRY(bx.alloc(N * 8));
+  HIP_TRY(bw.alloc(N * 8));
+  hipLaunchKernelGGL(k_debug_light_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, (const uint4*)s->b_light_alias.as<uint4>(),
+                     (uint32_t)s->n_emit, n, bu.as<float>(), be.as<uint32_t>(), bx.as<float>(), bw.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_entry, be.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_rxy, bx.p, N * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_weight, bw.p, N * 8, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }
 

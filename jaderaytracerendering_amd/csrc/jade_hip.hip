@@ -214,10 +214,12 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the k_shade*_lens kernels only)
 // SHUTTER: the camera ray leaves the pose of a time drawn within the exposure, through a lens or not (include/jade_bvh.h, "The shutter,
 // stated"; non-parity; the k_shade*_shutter kernels only, which pass their ShutterConst as H)
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// LIGHTS: one emitter per sampling vertex, drawn from the table `lights` (include/jade_bvh.h, "The lights, stated"; non-parity; the
+// k_shade_lights* kernels only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
-                                                    const ShutterConst* H = nullptr) {
+                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr) {
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -278,6 +280,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
       }
     }
     uint32_t done = done0;
+    uint32_t light = LIGHTS ? hdr0.w : 0u;  // JADE_LIGHTS_ONE: the emitter entry the bounce in flight drew
     jvec3 l_final;
     bool finished = false;  // a sample ended: colour in `color`
     jvec3 color = jv(0, 0, 0);
@@ -300,7 +303,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS>(S, px, c, &l_final);
+      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS>(S, px, c, &l_final, lights, light);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
       } else if (r == CONSUME_EMITTED) {
@@ -332,13 +335,13 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           defer = true;
           break;
         }
-        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS>(S, px, c, &l_final)) {
+        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS>(S, px, c, &l_final, lights, &light)) {
           st = c.stage;
           if (!ENVIS || c.n_emit_rays != 0) break;
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
           // emitter, the roulette ended the path) has all its results already - nothing is visible: folded in right here (with the
           // reference's sampling there is always the environment ray)
-          const int r = consume<ENVIS>(S, px, c, &l_final);
+          const int r = consume<ENVIS, LIGHTS>(S, px, c, &l_final, lights, light);
           if (r == CONSUME_VERTEX) {
             st = ST_VERTEX;
             continue;
@@ -411,7 +414,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         c.c_cls += st == ST_MIRROR ? (1u << 16) : (1u << 24);
       }
     }
-    P.hdr[p] = make_uint4(c.rng, done, st | (c.depth << 8) | (c.flags << 16), 0u);
+    P.hdr[p] = make_uint4(c.rng, done, st | (c.depth << 8) | (c.flags << 16), light);
     if ((st >= ST_DIFFUSE && st <= ST_REFRACT_EXIT) || st == ST_VERTEX) {
       // (aux and auxi - P.aux - are begin_bounce's and consume's: written through Px while this record was shaded)
       float4* cx = P.ctx + (size_t)p * 4;
@@ -538,11 +541,11 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const ShutterConst* H = nullptr) {
+                                               uint32_t stop_below, const ShutterConst* H = nullptr, const uint4* lights = nullptr) {
   const uint32_t n = n_dev ? *n_dev : n_host;
   // A pass of a batch (prev = the pass before it, on the device): nothing to do once the paths have ended (that pass
   // emitted no ray) or once fewer than stop_below records are active - the point where the host would hand the rest to
@@ -560,7 +563,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER>(S, P, R, tile_ids, target_spp, p, c, st, defer, H);
+  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -601,6 +604,20 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_en
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below, ShutterConst H) {
   shade_kernel_body<true, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &H);
+}
+// ... and with one emitter per vertex (jade_scene_set_light_sampling = JADE_LIGHTS_ONE, non-parity), under either environment sampling: the
+// two kernels that carry that code.  The alias table over the scene's emitter entries is one more argument, the last.
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<true, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1990,6 +2007,7 @@ static int upload_scene(jade_scene* s, const jade_scene_desc* d, const ScenePrep
   if (e == hipSuccess) e = upload(s->b_segs, d->obj_segs, (size_t)d->n_objects, s->stream);
   if (e == hipSuccess) e = upload(s->b_env, d->env_rgb, (size_t)3 * d->env_width * d->env_height, s->stream);
   if (e == hipSuccess) e = upload(s->b_env_alias, p.env_alias.data(), p.env_alias.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_light_alias, p.light_alias.data(), p.light_alias.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_tnorm, p.tnorm.data(), p.tnorm.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_mats, p.mats.data(), p.mats.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_guide, p.guide.data(), p.guide.size(), s->stream);
@@ -2145,6 +2163,19 @@ int jade_scene_get_shutter(jade_scene* s, jade_shutter_params* out, int* is_set)
   return JADE_OK;
 }
 
+// The light sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_light_sampling(jade_scene* s, int mode) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (mode != JADE_LIGHTS_ALL && mode != JADE_LIGHTS_ONE) return jade_fail(JADE_ERR_INVALID, "unknown light sampling (JADE_LIGHTS_*)");
+  s->light_sampling = mode;
+  return JADE_OK;
+}
+int jade_scene_get_light_sampling(jade_scene* s, int* mode) {
+  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *mode = s->light_sampling;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -2231,13 +2262,21 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
   if (rp->env_sampling == JADE_ENV_IMPORTANCE && !env_importance_fits(s->dev.env_w, s->dev.env_h))
     return jade_fail(JADE_ERR_UNSUPPORTED, "env_sampling: JADE_ENV_IMPORTANCE takes environment maps of at most 2^24 texels (JADE_ENV_IMPORTANCE_MAX_TEXELS)");
+  const bool lights_one = s->light_sampling == JADE_LIGHTS_ONE;
+  if (lights_one && !light_sampling_fits(s->n_emit))
+    return jade_fail(JADE_ERR_UNSUPPORTED, "light sampling: JADE_LIGHTS_ONE takes at most 2^24 emitter entries (JADE_LIGHTS_ONE_MAX_ENTRIES)");
+  if (lights_one && (s->lens.aperture_radius > 0.0f || s->shutter_set))
+    return jade_fail(JADE_ERR_UNSUPPORTED, std::string("light sampling: JADE_LIGHTS_ONE (jade_scene_set_light_sampling) does not run together with ") +
+                                               (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
+                                               " yet: those kernels are not built");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
   for (int y = 0; y < ty; ++y)
     for (int x = 0; x < tx; ++x)
       if ((x + y) % rp->tile_nranks == rp->tile_rank) s->tile_ids.push_back(y * tx + x);
-  const int nslots = s->n_emit + 2;
+  // the record's layout: a shadow slot per emitter entry - or one for the entry drawn (JADE_LIGHTS_ONE) -, the environment ray's, the indirect ray's
+  const int nslots = (lights_one ? std::min(s->n_emit, 1) : s->n_emit) + 2;
   const int64_t npx64 = (int64_t)s->tile_ids.size() * 256;
   // Records per pixel: as many paths in flight as JADE_RECORD_MEMORY of the free device memory holds (the
   // partial sums come out of the same share), whatever the image share of this GPU: more records = fewer,
@@ -2271,7 +2310,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   }
   const int64_t npix64 = npx64 * rpp;
   if (npix64 * nslots >= ((int64_t)1 << 32) || npix64 * 3 >= ((int64_t)1 << 31))
-    return jade_fail(JADE_ERR_UNSUPPORTED, "pixels x records x (emitters + 2) exceeds the 32-bit ray-slot index");
+    return jade_fail(JADE_ERR_UNSUPPORTED, "pixels x records x (emitters + 2) exceeds the 32-bit ray-slot index");  // (JADE_LIGHTS_ONE: x 3 at most)
   if (sums_bytes + (double)npix64 * bytes_per_record > (rp->max_state_bytes ? std::max(state_budget, 0.0) : 0.95 * (double)mem_free))
     return jade_fail(JADE_ERR_NOMEM, rp->max_state_bytes ? "frame does not fit max_state_bytes (partial sums + one record per pixel)"
                                                     : "frame does not fit the device memory (partial sums + one record per pixel)");
@@ -2298,6 +2337,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->tile_n.clear();
   s->adaptive_done = false;
   s->dn_carried = jade_stats{};
+  s->lights_on = lights_one;  // the scene's light sampling as it is now: the render keeps it, like its lens
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
@@ -2346,6 +2386,7 @@ struct PassRun {
   QueueCtl* qc;                       // s->b_ctl: entry 0 for passes the host follows, the ring for a batch
   decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
   decltype(&k_shade_shutter) shade_kernel_shutter = nullptr;  // under a shutter: the kernel launched instead, with s->sh as its last argument
+  decltype(&k_shade_lights) shade_kernel_lights = nullptr;    // JADE_LIGHTS_ONE: the kernel launched instead, with the emitters' alias table as its last argument
   bool batching, tail_ok;
   uint32_t tail_max;                  // active records at or below which k_tail finishes the list
   uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
@@ -2386,8 +2427,13 @@ static uint32_t trace_chunk(const jade_scene* s, uint32_t n_rays) {
 
 void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays) {
   const bool wide = trace_wide(s->dev, P);
+  // k_trace tells a shadow ray from an environment ray by its slot number against n_emit (anyhit_key): it is handed the shadow slots of
+  // the render's LAYOUT, which under JADE_LIGHTS_ONE is not the length of the scene's list (the single-slot callers - the guide pass,
+  // jade_trace_rays - ask about slot 0 alone, which reads the same against either count)
+  DevScene S = s->dev;
+  if (s->lights_on) S.n_emit = std::min(s->n_emit, 1);
   hipLaunchKernelGGL(wide ? k_trace_wide : k_trace, dim3((unsigned)(wide ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream,
-                     s->dev, P, queue, qc, spill, ctr, trace_chunk(s, n_rays));
+                     S, P, queue, qc, spill, ctr, trace_chunk(s, n_rays));
 }
 
 // A k_trace launch of a render took the n rays of queue positions 0 .. n-1 (an ordered queue: the same positions in another order): those
@@ -2412,7 +2458,11 @@ static int launch_arm(jade_scene* s, uint32_t target_spp, QueueCtl* ctl, size_t 
 static void launch_shade(const PassRun& r, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
                          const QueueCtl* prev, uint32_t stop_below) {
   jade_scene* s = r.s;
-  if (r.shade_kernel_shutter)
+  if (r.shade_kernel_lights)
+    hipLaunchKernelGGL(r.shade_kernel_lights, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
+                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below,
+                       (const uint4*)s->b_light_alias.as<uint4>());
+  else if (r.shade_kernel_shutter)
     hipLaunchKernelGGL(r.shade_kernel_shutter, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
                        list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, s->sh);
   else
@@ -2670,7 +2720,7 @@ static int order_queue(jade_scene* s, uint32_t n, const uint32_t** trace_queue) 
   // k_ray_keys made them here, from three scattered sectors per ray, 2 % of a C5 step.  JADE_SORT_KEYS_KERNEL=1 brings that back.)
   if (s->tun.sort_keys_kernel)
     hipLaunchKernelGGL(k_ray_keys, dim3((n + 255) / 256), dim3(256), 0, s->stream, s->ps, s->b_queue.as<uint32_t>(), n, s->b_sortkey.as<uint32_t>(),
-                       s->b_sortpos.as<uint32_t>(), s->n_emit, s->ps.key_tri_bits);
+                       s->b_sortpos.as<uint32_t>(), s->ps.nslots - 2, s->ps.key_tri_bits);  // (the layout's shadow slots: JADE_LIGHTS_ONE has one)
   // The temporary storage was sized once, for (sort_cap entries, bits 0..32).  rocPRIM's need shrinks with the length and with
   // the bit range (fewer digit places, fewer look-back states; a short queue takes its merge-sort path: two buffers of n), and a
   // buffer that is too small is an error return, not a fault (rocprim/detail/temp_storage.hpp: partition) - asked again here,
@@ -2755,8 +2805,10 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   r.shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
   if (lens_on(s)) r.shade_kernel = s->ps.env_sampling ? k_shade_envis_lens : k_shade_lens;
   if (shutter_on(s)) r.shade_kernel_shutter = s->ps.env_sampling ? k_shade_envis_shutter : k_shade_shutter;
+  // one emitter per vertex (jade_render_begin refuses it under a lens or a shutter): its own kernels, JADE_SHADE_BINNED has no effect
+  if (s->lights_on) r.shade_kernel_lights = s->ps.env_sampling ? k_shade_lights_envis : k_shade_lights;
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s);  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s) && !s->lights_on;  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
   r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);

@@ -200,7 +200,7 @@ struct jade_scene {
   Tunables tun;
   hipStream_t stream = nullptr;
   DevScene dev{};
-  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias;
+  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias, b_light_alias;
   bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
   int n_emit = 0;
   int n_objects = 0;
@@ -210,6 +210,8 @@ struct jade_scene {
   bool shutter_set = false;
   ShutterConst sh{};          // ... and what the render in progress took: the argument of the shutter kernels, if sh_on
   bool sh_on = false;
+  int light_sampling = JADE_LIGHTS_ALL;  // jade_scene_set_light_sampling: what the next jade_render_begin takes ...
+  bool lights_on = false;     // ... and what the render in progress took: JADE_LIGHTS_ONE (its records have min(n_emit, 1) + 2 slots)
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;
@@ -273,6 +275,7 @@ struct ScenePrep {
   std::vector<uint2> guide_obj;                       // ... and each object's {first entry, cells}
   std::vector<DevMaterial> mats;
   std::vector<uint4> env_alias;
+  std::vector<uint4> light_alias;                     // JADE_LIGHTS_ONE: the alias table over emit_indices (n_emit entries)
   int n_internal = 0;
   size_t n_pairs = 0;
   bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
@@ -292,6 +295,11 @@ JADE_HIDDEN void env_alias_table(int32_t env_width, int32_t env_height, const fl
 static inline bool env_importance_fits(int32_t env_width, int32_t env_height) {
   return env_width > 0 && env_height > 0 && (uint64_t)env_width * (uint64_t)env_height <= JADE_ENV_IMPORTANCE_MAX_TEXELS;
 }
+// ... its alias table over the emitter entries (JADE_LIGHTS_ONE, include/jade_bvh.h "The lights, stated": weight = area x luminance of
+// emission + a floor), made by env_alias_table's builder, and the emitter counts that mode takes: light_sample (jade_shade.h) forms the
+// slot from a 24-bit uniform, as env_sample does
+JADE_HIDDEN void light_alias_table(const jade_triangle* triangles, const int32_t* emit_indices, int32_t n_emit, std::vector<uint4>& light_alias);
+static inline bool light_sampling_fits(int64_t n_emit) { return n_emit >= 0 && n_emit <= JADE_LIGHTS_ONE_MAX_ENTRIES; }
 
 // The two places where host code of one file needs a kernel of another (this tree is not built with -fgpu-rdc), both in jade_hip.hip:
 // the k_trace / k_trace_wide launch - kernel and grid chosen from (scene, P); n_rays sizes the chunks a wave claims, 0 = the kernel

@@ -295,6 +295,7 @@ void materials(const jade_scene_desc* d, std::vector<DevMaterial>& mats, std::ve
 // (luminance + 1 % of the mean luminance) x sin(theta of the row's centre) - the floor keeps every texel drawable, so the
 // estimator stays unbiased wherever the sky is not black.  include/jade_rt.h (JADE_ENV_IMPORTANCE) states the weight and what an
 // entry means; how small and large texels are paired is not part of that statement.  No HIP call.
+static void alias_table_of(const std::vector<double>& wgt, double total, std::vector<uint4>& table);
 void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb, std::vector<uint4>& env_alias) {
   const size_t W = (size_t)env_width, H = (size_t)env_height, N = W * H;
   std::vector<double> wgt(N);
@@ -314,11 +315,18 @@ void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb
       total += wgt[j * W + i];
     }
   }
+  alias_table_of(wgt, total, env_alias);
+}
+
+// Vose's alias table for the weights wgt (sum: total > 0): entry i = {accept, alias, fl(q_i), fl(q_alias)} with q_i = wgt_i / total x N.
+// Shared by the environment's texels (above) and the emitter entries (light_alias_table, below).
+static void alias_table_of(const std::vector<double>& wgt, double total, std::vector<uint4>& env_alias) {
+  const size_t N = wgt.size();
   std::vector<double> q(N);
   std::vector<uint32_t> small, large, alias(N);
   std::vector<float> accept(N, 1.0f);
   for (size_t i = 0; i < N; ++i) {
-    q[i] = wgt[i] / total * (double)N;  // the texel's probability x N (mean 1)
+    q[i] = wgt[i] / total * (double)N;  // the entry's probability x N (mean 1)
     alias[i] = (uint32_t)i;
     (q[i] < 1.0 ? small : large).push_back((uint32_t)i);
   }
@@ -341,6 +349,37 @@ void env_alias_table(int32_t env_width, int32_t env_height, const float* env_rgb
     memcpy(&e.w, &pa, 4);
     env_alias[i] = e;
   }
+}
+
+// One-light sampling (jade_scene_set_light_sampling = JADE_LIGHTS_ONE; non-parity): the alias table over the entries of emit_indices,
+// weight = area x luminance of emission + 1 % of the mean of that - the floor keeps every entry drawable, so the estimator stays
+// unbiased whatever an entry's triangle emits.  include/jade_bvh.h ("The lights, stated") states the weight and what an entry means.  The
+// area is the one the integrator multiplies an entry's term by: tri_size's statements (jade_shade.h; PathTrace.cu:897-903) in fp32.  No HIP call.
+void light_alias_table(const jade_triangle* triangles, const int32_t* emit_indices, int32_t n_emit, std::vector<uint4>& light_alias) {
+  const size_t N = n_emit > 0 ? (size_t)n_emit : 0;
+  light_alias.clear();
+  if (N == 0) return;
+  std::vector<double> wgt(N);
+  double sum = 0;
+  for (size_t i = 0; i < N; ++i) {
+    const jade_triangle& t = triangles[emit_indices[i]];
+    const jvec3 p1 = jv(t.p1[0], t.p1[1], t.p1[2]);
+    const jvec3 cp = jv_cross(jv_sub(jv(t.p2[0], t.p2[1], t.p2[2]), p1), jv_sub(jv(t.p3[0], t.p3[1], t.p3[2]), p1));
+    const float area = 0.5f * jade_sqrt(jv_dot(cp, cp));
+    const double a = std::isfinite(area) ? (double)area : 0.0;
+    double l = 0.2126 * std::max(t.emissive[0], 0.0f) + 0.7152 * std::max(t.emissive[1], 0.0f) + 0.0722 * std::max(t.emissive[2], 0.0f);
+    if (!std::isfinite(l)) l = 0.0;
+    const double w = a * l;
+    wgt[i] = std::isfinite(w) ? w : 0.0;
+    sum += wgt[i];
+  }
+  const double floor_w = sum > 0 ? 0.01 * sum / (double)N : 1.0;
+  double total = 0;
+  for (size_t i = 0; i < N; ++i) {
+    wgt[i] += floor_w;
+    total += wgt[i];
+  }
+  alias_table_of(wgt, total, light_alias);
 }
 
 // What jade_scene_create checks of the caller's descriptor before anything is derived from it: ranges, and a walk of the tree from the
@@ -424,5 +463,6 @@ int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, S
   guide_tables(d, out->guide, out->guide_obj);
   materials(d, out->mats, out->tnorm);
   env_alias_table(d->env_width, d->env_height, d->env_rgb, out->env_alias);
+  if (light_sampling_fits(d->n_emit)) light_alias_table(d->triangles, d->emit_indices, d->n_emit, out->light_alias);  // (a longer list renders with JADE_LIGHTS_ALL only)
   return JADE_OK;
 }

@@ -114,6 +114,41 @@ static __device__ __forceinline__ jvec3 env_sample_at(const DevScene& S, const f
   return env_sample_with(S, [u4, &k]() { return u4[k++]; }, ratio, texel);
 }
 
+// One-light sampling (jade_scene_set_light_sampling = JADE_LIGHTS_ONE; NOT the reference's estimator), as include/jade_bvh.h states it
+// draw by draw ("The lights, stated"): an entry of emit_indices by the alias method over `table` (nE entries {accept, alias, q_own, q_alias},
+// light_alias_table, jade_scene_prep.hip; one 16-B gather per draw) - u1 the slot, u2 own / alias - then the reference's two numbers for
+// the point on that entry's triangle (u3, u4), folded as the reference folds them.  Returns the entry; *weight = fl(nE) / q, what the
+// entry's term is multiplied with.  The uniforms come from `next`, as env_sample_with's do.  nE >= 1 (<= 2^24: jade_render_begin).
+template <class NextUniform>
+static __device__ __forceinline__ uint32_t light_sample_with(const uint4* table, uint32_t nE, NextUniform next, float* rx, float* ry, float* weight) {
+  uint32_t s = (uint32_t)(next() * (float)nE);
+  s = s < nE ? s : nE - 1u;
+  const float u2 = next();
+  const uint4 e = table[s];
+  const bool own = u2 < jade_u2f(e.x);
+  const float q = jade_u2f(own ? e.z : e.w);  // the chosen entry's probability x nE
+  float x = next();
+  float y = next();
+  if (x + y > 1) {
+    x = 1 - x;
+    y = 1 - y;
+  }
+  *rx = x;
+  *ry = y;
+  *weight = (float)nE / q;
+  return own ? s : e.y;
+}
+// ... with four successive jade_rand draws: what bounce_branch calls (the weight is consume's to form, below)
+static __device__ __forceinline__ uint32_t light_sample(const uint4* table, uint32_t nE, uint32_t* rng, float* rx, float* ry) {
+  float weight;
+  return light_sample_with(table, nE, [rng]() { return jade_rand(rng); }, rx, ry, &weight);
+}
+// The weight of entry i again, where its shadow ray's answer is folded in: q_alias of a slot is q_own of the entry it names, bit for bit
+// (both are fl(q_i)), so the weight is a function of the entry alone and does not travel with the record.
+static __device__ __forceinline__ float light_weight(const uint4* table, uint32_t nE, uint32_t i) {
+  return (float)nE / jade_u2f(table[i].z);
+}
+
 static __device__ __forceinline__ jvec3 tri_point(const jade_triangle* t, float rx, float ry) {
   jvec3 p1 = V3(t->p1);
   return jv_add(jv_add(p1, jv_scale(jv_sub(V3(t->p2), p1), rx)), jv_scale(jv_sub(V3(t->p3), p1), ry));
@@ -390,12 +425,17 @@ static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx
 // The branch itself: its draws, its rays (written through px), stage / flags / n_emit_rays.  Returns false if the path ended at
 // this vertex (*l_final holds the last l_dir).  `type` is uniform over the waves k_shade runs it for.
 // ENVIS: jade_render_params.env_sampling = JADE_ENV_IMPORTANCE (compiled apart: the parity kernels carry none of its code)
-template <bool ENVIS = false>
-static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final) {
+// LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h; compiled apart likewise, k_shade_lights*): ONE entry of S.emit, drawn from `lights`, in
+// slot 0; nL = the shadow slots of the record's layout, so the environment ray sits in slot nL and the indirect ray in slot nL + 1.
+// *light = the entry drawn: it travels with the record (the fourth word of PathState.hdr, shade_record) to consume.
+template <bool ENVIS = false, bool LIGHTS = false>
+static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final,
+                                                     const uint4* lights = nullptr, uint32_t* light = nullptr) {
   const jade_triangle* T = S.tris;  // vertices only
   const ShadeTri ots = shade_tri(S, c.obj);
   const DevMaterial* ot = ots.m;
   const int nE = S.n_emit;
+  const int nL = LIGHTS ? (nE > 0 ? 1 : 0) : nE;
   const float RR_F = (float)JADE_RR_RATE_D;
   const jvec3 n = ots.norm;
   *l_final = jv(0, 0, 0);  // (as bounce_classify left it: a worker thread of k_shade brings its own)
@@ -433,14 +473,21 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
 
       px.set_origin(random_point, middle);
       px.set_aux(bssrdf);
-      for (int i = 0; i < nE; ++i) {
-        float rx = jade_rand(&c.rng);
-        float ry = jade_rand(&c.rng);
-        if (rx + ry > 1) {
-          rx = 1 - rx;
-          ry = 1 - ry;
+      for (int i = 0; i < nL; ++i) {
+        float rx, ry;
+        int ei = i;
+        if (LIGHTS) {
+          *light = light_sample(lights, (uint32_t)nE, &c.rng, &rx, &ry);
+          ei = (int)*light;
+        } else {
+          rx = jade_rand(&c.rng);
+          ry = jade_rand(&c.rng);
+          if (rx + ry > 1) {
+            rx = 1 - rx;
+            ry = 1 - ry;
+          }
         }
-        const jade_triangle* et = &T[S.emit[i]];
+        const jade_triangle* et = &T[S.emit[ei]];
         jvec3 random_emit_point = tri_point(et, rx, ry);
         const jvec3 sd = jv_sub(random_emit_point, random_point);
         px.set_dir(i, sd);
@@ -452,19 +499,19 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
         float ratio;
         const jvec3 ray_direction = env_sample(S, &c.rng, &ratio);
         if (jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) {
-          px.set_hit(nE, -2);
+          px.set_hit(nL, -2);
           noenv = STF_NOENV;
         } else {
-          px.set_dir(nE, ray_direction);
-          px.set_limit(nE, JADE_INF_F);
+          px.set_dir(nL, ray_direction);
+          px.set_limit(nL, JADE_INF_F);
           px.set_auxi(__float_as_int(ratio));
           c.n_emit_rays++;
         }
       } else {
         jvec3 ray_direction = sphere_dir(&c.rng);
         if (jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) ray_direction = jv_neg(ray_direction);
-        px.set_dir(nE, ray_direction);
-        px.set_limit(nE, JADE_INF_F);  // environment visibility: any recorded hit
+        px.set_dir(nL, ray_direction);
+        px.set_limit(nL, JADE_INF_F);  // environment visibility: any recorded hit
         c.n_emit_rays++;
       }
       jvec3 ray_direction = sphere_dir(&c.rng);
@@ -474,11 +521,11 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
       c.flags = noenv;
       if (rr_result < RR_F) {
         c.flags |= STF_RR;
-        px.set_dir(nE + 1, ray_direction);
-        px.set_hit(nE + 1, -1);
+        px.set_dir(nL + 1, ray_direction);
+        px.set_hit(nL + 1, -1);
         c.n_emit_rays++;
       } else {
-        px.set_hit(nE + 1, -2);
+        px.set_hit(nL + 1, -2);
       }
       return true;
     }
@@ -511,14 +558,21 @@ diffuse_like:
   {
     px.set_origin(c.src, c.obj);
     const float side = jv_dot(c.out, n);
-    for (int i = 0; i < nE; ++i) {
-      float rand_x = jade_rand(&c.rng);
-      float rand_y = jade_rand(&c.rng);
-      if (rand_x + rand_y > 1) {
-        rand_x = 1 - rand_x;
-        rand_y = 1 - rand_y;
+    for (int i = 0; i < nL; ++i) {
+      float rand_x, rand_y;
+      int ei = i;
+      if (LIGHTS) {
+        *light = light_sample(lights, (uint32_t)nE, &c.rng, &rand_x, &rand_y);
+        ei = (int)*light;
+      } else {
+        rand_x = jade_rand(&c.rng);
+        rand_y = jade_rand(&c.rng);
+        if (rand_x + rand_y > 1) {
+          rand_x = 1 - rand_x;
+          rand_y = 1 - rand_y;
+        }
       }
-      const jade_triangle* et = &T[S.emit[i]];
+      const jade_triangle* et = &T[S.emit[ei]];
       jvec3 random_point = tri_point(et, rand_x, rand_y);
       jvec3 obj_light_direction = jv_sub(random_point, c.src);
       px.set_dir(i, obj_light_direction);
@@ -533,19 +587,19 @@ diffuse_like:
       float ratio;
       const jvec3 ray_direction = env_sample(S, &c.rng, &ratio);
       if (jv_dot(ray_direction, n) * side < 0) {
-        px.set_hit(nE, -2);
+        px.set_hit(nL, -2);
         c.flags |= STF_NOENV;
       } else {
-        px.set_dir(nE, ray_direction);
-        px.set_limit(nE, JADE_INF_F);
+        px.set_dir(nL, ray_direction);
+        px.set_limit(nL, JADE_INF_F);
         px.set_auxi(__float_as_int(ratio));
         c.n_emit_rays++;
       }
     } else {
       jvec3 ray_direction = sphere_dir(&c.rng);
       if (jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
-      px.set_dir(nE, ray_direction);
-      px.set_limit(nE, JADE_INF_F);  // environment visibility: any recorded hit
+      px.set_dir(nL, ray_direction);
+      px.set_limit(nL, JADE_INF_F);  // environment visibility: any recorded hit
       c.n_emit_rays++;
     }
     float rr_result = jade_rand(&c.rng);
@@ -553,11 +607,11 @@ diffuse_like:
       jvec3 ray_direction = sphere_dir(&c.rng);
       if (jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
       c.flags |= STF_RR;
-      px.set_dir(nE + 1, ray_direction);
-      px.set_hit(nE + 1, -1);
+      px.set_dir(nL + 1, ray_direction);
+      px.set_hit(nL + 1, -1);
       c.n_emit_rays++;
     } else {
-      px.set_hit(nE + 1, -2);
+      px.set_hit(nL + 1, -2);
     }
     return true;
   }
@@ -565,11 +619,12 @@ diffuse_like:
 
 // Sample the bounce at the current vertex and emit its rays.  Returns false
 // if the path ended at this vertex (l_final holds the last l_dir).
-template <bool ENVIS = false>
-static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final) {
+template <bool ENVIS = false, bool LIGHTS = false>
+static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr,
+                                    uint32_t* light = nullptr) {
   const int type = bounce_classify(S, c, l_final);
   if (type == BT_END) return false;
-  return bounce_branch<ENVIS>(type, S, px, c, l_final);
+  return bounce_branch<ENVIS, LIGHTS>(type, S, px, c, l_final, lights, light);
 }
 
 // Outcome of folding the pending rays' results into the path.
@@ -599,10 +654,12 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // moved to a new vertex (c.obj/src/out updated); CONSUME_END: it ended with
 // *l_final; CONSUME_ZERO: pathTracing returned 0 (:1231); CONSUME_EMITTED: the
 // refraction loop issued its next ray.
-template <bool ENVIS = false>
-static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final) {
+// LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight (bounce_branch)
+template <bool ENVIS = false, bool LIGHTS = false>
+static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u) {
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
+  const int nL = LIGHTS ? (nE > 0 ? 1 : 0) : nE;
   const float PI_F = (float)JADE_PI_D;
   const float RR_F = (float)JADE_RR_RATE_D;
   const ShadeTri ots = shade_tri(S, c.obj);
@@ -615,9 +672,9 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
   if (c.stage == ST_DIFFUSE) {
     const bool sss = (c.flags & STF_SSS) != 0;
     const jvec3 f = sss ? jv_scale(V3(ot->refract_albedo), (float)(1.0 / JADE_PI_D)) : obj_hit_fr;
-    for (int i = 0; i < nE; ++i) {
+    for (int i = 0; i < nL; ++i) {
       int h = px.hit(i);
-      int emit_tri_idx = S.emit[i];
+      int emit_tri_idx = S.emit[LIGHTS ? (int)light : i];
       if (h >= 0 && h == emit_tri_idx) {
         jvec3 ld = px.dir(i);
         const ShadeTri t_i = shade_tri(S, emit_tri_idx);
@@ -626,11 +683,12 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
         w = jv_scale(w, jade_fabs(jv_dot(n, ld) * jv_dot(t_i.norm, ld)));
         w = jv_divs(jv_divs(w, dls), dls);
         w = jv_scale(w, tri_size(&T[emit_tri_idx]));
+        if (LIGHTS) w = jv_scale(w, light_weight(lights, (uint32_t)nE, light));  // x 1 / (the probability the entry was drawn with)
         l_dir = jv_add(l_dir, w);
       }
     }
-    if (ENVIS ? px.hit(nE) == -1 : px.hit(nE) < 0) {  // (-1: traced and nothing hit; -2: no environment ray this bounce - env_sampling only)
-      jvec3 rd = px.dir(nE);
+    if (ENVIS ? px.hit(nL) == -1 : px.hit(nL) < 0) {  // (-1: traced and nothing hit; -2: no environment ray this bounce - env_sampling only)
+      jvec3 rd = px.dir(nL);
       jvec3 w = jv_mul(sample_hdr(S, rd), f);
       w = jv_scale(w, jade_fabs(jv_dot(n, rd)));
       w = jv_scale(jv_scale(w, 2.0f), PI_F);
@@ -640,12 +698,12 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     l_dir = jv_scale(l_dir, sss ? (float)(k / JADE_SSS_RATE_D) : (float)k);
     *l_final = l_dir;
     if (!(c.flags & STF_RR)) return CONSUME_END;
-    int nh = px.hit(nE + 1);
+    int nh = px.hit(nL + 1);
     if (nh >= 0 && nonemissive(shade_tri(S, nh).m)) {
-      jvec3 rd = jv_neg(px.dir(nE + 1));
+      jvec3 rd = jv_neg(px.dir(nL + 1));
       jvec3 indir_rate = jv_divs(jv_scale(obj_hit_fr, jade_fabs(jv_dot(rd, n))), RR_F);
       jvec3 rate = sss ? jv_divs(jv_scale(indir_rate, (float)k), (float)JADE_SSS_RATE_D) : jv_scale(indir_rate, (float)k);
-      c.src = px.hpt(nE + 1);
+      c.src = px.hpt(nL + 1);
       c.out = rd;
       c.obj = nh;
       return path_push(c, l_dir, rate) ? CONSUME_END : CONSUME_VERTEX;
@@ -662,9 +720,9 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     const float eta = t_i->refract_index;
     const float R0 = (eta - 1) / (eta + 1) * (eta - 1) / (eta + 1);
     const float area_total = S.prefix[S.segs[t_i->obj_idx].end_idx];
-    for (int i = 0; i < nE; ++i) {
+    for (int i = 0; i < nL; ++i) {
       int h = px.hit(i);
-      int emit_tri_idx = S.emit[i];
+      int emit_tri_idx = S.emit[LIGHTS ? (int)light : i];
       if (h >= 0 && h == emit_tri_idx) {
         jvec3 ld = px.dir(i);
         const ShadeTri emit_i = shade_tri(S, emit_tri_idx);
@@ -677,11 +735,12 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
         w = jv_scale(w, tri_size(&T[emit_tri_idx]));
         w = jv_divs(w, PI_F);
         w = jv_scale(w, area_total);
+        if (LIGHTS) w = jv_scale(w, light_weight(lights, (uint32_t)nE, light));
         l_dir = jv_add(l_dir, w);
       }
     }
-    if (ENVIS ? px.hit(nE) == -1 : px.hit(nE) < 0) {
-      jvec3 rd = px.dir(nE);
+    if (ENVIS ? px.hit(nL) == -1 : px.hit(nL) < 0) {
+      jvec3 rd = px.dir(nL);
       float fresnel_rate_o = schlick_out(R0, jade_fabs(jv_dot(rd, t_norm)));
       jvec3 w = jv_mul(jv_scale(sample_hdr(S, rd), fresnel_rate_o), bssrdf);
       w = jv_scale(jv_scale(w, jade_fabs(jv_dot(t_norm, rd))), 2.0f);
@@ -691,16 +750,16 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     l_dir = jv_scale(l_dir, (float)(k / (1 - JADE_SSS_RATE_D)));
     *l_final = l_dir;
     if (!(c.flags & STF_RR)) return CONSUME_END;
-    int nh = px.hit(nE + 1);
+    int nh = px.hit(nL + 1);
     if (nh >= 0 && nonemissive(shade_tri(S, nh).m)) {
-      jvec3 rd = jv_neg(px.dir(nE + 1));
+      jvec3 rd = jv_neg(px.dir(nL + 1));
       float fresnel_rate_o = schlick_out(R0, jade_fabs(jv_dot(rd, t_norm)));
       jvec3 indir_rate = jv_scale(bssrdf, fresnel_rate_o);
       indir_rate = jv_scale(indir_rate, jade_fabs(jv_dot(rd, t_norm)));
       indir_rate = jv_scale(indir_rate, area_total);
       indir_rate = jv_divs(jv_scale(indir_rate, 2.0f), RR_F);
       jvec3 rate = jv_divs(jv_scale(indir_rate, (float)k), (float)(1 - JADE_SSS_RATE_D));
-      c.src = px.hpt(nE + 1);
+      c.src = px.hpt(nL + 1);
       c.out = rd;
       c.obj = nh;
       return path_push(c, l_dir, rate) ? CONSUME_END : CONSUME_VERTEX;

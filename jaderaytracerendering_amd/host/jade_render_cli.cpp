@@ -49,6 +49,8 @@ struct Api {
   jadeh_trace_rays_fn trace_rays = nullptr;
   // ... and only for --shutter-truck / --shutter-orbit
   int (*scene_set_shutter)(jade_scene*, const jade_shutter_params*) = nullptr;
+  // ... and only for --one-light
+  int (*scene_set_light_sampling)(jade_scene*, int) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -90,7 +92,7 @@ static bool write_pfm1(const std::string& path, const float* v, int width, int h
 static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
-          "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance]\n"
+          "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance] [--one-light]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -105,6 +107,9 @@ static void usage() {
           "                backwards) and then turned by DEG degrees about the axis through X,Y,Z parallel to the camera's up (default: the\n"
           "                eye, a pan; the subject's position gives a turntable).  --shutter-interval T0,T1 with 0 <= T0 <= T1 <= 1 exposes\n"
           "                that part of the move only (default 0,1).  Keep DEG to a few degrees; with --aperture, both blurs apply\n"
+          "  --one-light: every diffuse and sub-surface vertex sends ONE shadow ray, to an emitter drawn by power, instead of one to every emitter\n"
+          "               (HIP backend only; NOT the reference's samples; include/jade_bvh.h).  For scenes with many emissive triangles; not together\n"
+          "               with --aperture or --shutter-*\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -144,6 +149,7 @@ int main(int argc, char** argv) {
   double glare_strength = 0.0, glare_levels = 6, glare_falloff = 0.5;
   bool use_aperture = false, have_focus = false, have_focus_at = false;
   double aperture = 0.0, focus = 0.0, focus_px = 0, focus_py = 0;
+  bool one_light = false;
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -180,6 +186,7 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = atoi(need("--device"));
     else if (a == "--reference-walk") reference_walk = true;
     else if (a == "--env-importance") env_importance = true;
+    else if (a == "--one-light") one_light = true;
     else if (a == "--adaptive") { adaptive = number("--adaptive", need("--adaptive")); use_adaptive = true; }
     else if (a == "--min-spp") { const double v = number("--min-spp", need("--min-spp")); min_spp = v >= 0 && v <= (1 << 30) && v == (int)v ? (int)v : -1; }
     else if (a == "--error-floor") error_floor = number("--error-floor", need("--error-floor"));
@@ -338,6 +345,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (one_light) {
+    *(void**)(&api.scene_set_light_sampling) = dlsym(api.h, "jade_scene_set_light_sampling");
+    if (!api.scene_set_light_sampling) {
+      fprintf(stderr, "--one-light needs the HIP backend: %s has no jade_scene_set_light_sampling\n", backend.c_str());
+      return 2;
+    }
+  }
   // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
   const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
   if (need_display) {
@@ -389,6 +403,8 @@ int main(int argc, char** argv) {
     printf("shutter: closes at eye (%.9g, %.9g, %.9g), exposure %.9g .. %.9g of the move\n", sh.eye_close[0], sh.eye_close[1], sh.eye_close[2], sh.t_open,
            sh.t_close);
   }
+  if (one_light && api.scene_set_light_sampling(dev, JADE_LIGHTS_ONE) != JADE_OK) { fprintf(stderr, "light sampling: %s\n", api.last_error()); return 1; }
+  const char* lights_note = one_light ? ", one light per vertex" : "";
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
   jade_stats st;
@@ -396,13 +412,13 @@ int main(int argc, char** argv) {
   const int tiles = ((rp.width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE) * ((rp.height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE);
   std::vector<int32_t> tile_spp(use_adaptive ? tiles : 0);
   if (use_adaptive) {
-    printf("Start... %dx%d, adaptive %g (%d .. %d spp) on %s\n", rp.width, rp.height, adaptive, min_spp, rp.spp, api.backend_name());
+    printf("Start... %dx%d, adaptive %g (%d .. %d spp) on %s%s\n", rp.width, rp.height, adaptive, min_spp, rp.spp, api.backend_name(), lights_note);
     if (api.render_adaptive(dev, &rp, min_spp, (float)adaptive, (float)error_floor, rgb.data(), bgr.data(), tile_spp.data(), &st) != JADE_OK) {
       fprintf(stderr, "render: %s\n", api.last_error());
       return 1;
     }
   } else {
-    printf("Start... %dx%d, %d spp on %s\n", rp.width, rp.height, rp.spp, api.backend_name());
+    printf("Start... %dx%d, %d spp on %s%s\n", rp.width, rp.height, rp.spp, api.backend_name(), lights_note);
     if (api.render(dev, &rp, rgb.data(), bgr.data(), &st) != JADE_OK) { fprintf(stderr, "render: %s\n", api.last_error()); return 1; }
   }
   if (!guides.empty()) {

@@ -1,0 +1,471 @@
+"""One-light sampling on the device (include/jade_bvh.h, "The lights, stated"; jade_scene_set_light_sampling): the draw against
+tests/lights_spec.py bit for bit, the two anchors (no emitter entry: JADE_LIGHTS_ALL's render; the default mode: today's), the
+invariants every mode is held to, the work and the memory the mode is for, the integral it estimates, and what it refuses."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import lights_spec as spec
+import test_gpu_lens as GL
+from conftest import B, ROOT, counters
+from jaderaytracerendering_amd import _abi, host as H
+from jaderaytracerendering_amd.host import HostScene
+
+pytestmark = pytest.mark.gpu
+
+CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
+all_counters, same_bits, _with = GL.all_counters, GL.same_bits, GL._with
+W, HH, SPP = 48, 40, 6
+QUAD_I = np.int32([[0, 1, 2], [0, 2, 3]])
+
+
+# ------------------------------------------------------------------------------------------------------------------ the scenes --
+
+def _jade():
+    return H.material(brdf=(0.3, 0.4, 0.5), reflex_mode=_abi.MIRROR, refract_mode=_abi.SUB_SURFACE, refract_rate=(0.3, 0.4, 0.5),
+                      refract_albedo=(0.3, 0.5, 0.7), refract_index=2.66)
+
+
+def _build(freq):
+    """A diffuse slab, a diffuse ball, a small SUB_SURFACE box (so the diffuse, the SSS-diffuse and the BSSRDF branch all sample the
+    emitters), a geodesic lamp of 20 freq^2 triangles and two quad lights of unequal power, under a 16 x 8 sky."""
+    b = H.SceneBuilder()
+    try:
+        T = H.transform_matrix
+        b.add_proc("box", 0, H.material(brdf=(0.6, 0.5, 0.4)), T(trans=(0, -1.1, 0), scale=(7, 0.2, 7)))
+        b.add_proc("geodesic", 2, H.material(brdf=(0.5, 0.6, 0.5)), T(trans=(-1.1, -0.45, 0.2), scale=(0.5,) * 3))
+        b.add_proc("box", 0, _jade(), T(rot_deg=(0, 35, 0), trans=(0.55, -0.7, 0.9), scale=(0.6,) * 3))
+        b.add_proc("geodesic", freq, H.material(emissive=(30, 27, 22), brdf=(0.3,) * 3), T(trans=(0.3, 1.3, 0.4), scale=(0.25,) * 3))
+        big = np.float32([[-2.6, 0.2, -1.8], [-1.4, 0.2, -1.8], [-1.4, 1.4, -1.8], [-2.6, 1.4, -1.8]])
+        b.add_mesh(big, QUAD_I, H.material(emissive=(9, 12, 15), brdf=(0.3,) * 3))
+        small = np.float32([[1.8, -0.6, 1.6], [2.1, -0.6, 1.3], [2.1, -0.3, 1.3], [1.8, -0.3, 1.6]])
+        b.add_mesh(small, QUAD_I, H.material(emissive=(40, 10, 4), brdf=(0.3,) * 3))
+        b.set_env_sky(16, 8)
+        return b.build()
+    finally:
+        b.close()
+
+
+_scenes = {}
+
+
+def lamp_scene(name="lamp"):
+    """"lamp": the 80-triangle lamp and the two quads, 84 entries.  "lamp82" / "lamp3" / "lamp1": the same triangles with 82 (the lamp
+    and one triangle of each quad), 3 and 1 of them listed - an emissive triangle need not be listed (it is then found by hitting it
+    only).  "none": none listed.  "big": the lamp at frequency 64, 81 920 + 4 entries."""
+    if name not in _scenes:
+        if name == "lamp":
+            hs = _build(2)
+            assert len(hs.a["emit"]) == 84
+        elif name == "big":
+            hs = _build(64)
+            assert len(hs.a["emit"]) == 81924
+        else:
+            base = lamp_scene("lamp")
+            hs = HostScene({k: np.array(v, copy=True) for k, v in base.a.items()}, base.bvh_depth)
+            e = base.a["emit"]
+            tf = base.tri_f32()
+            lamp = [i for i in e if tf[i, 13] == 30]
+            quads = [i for i in e if tf[i, 13] != 30]
+            assert len(lamp) == 80 and len(quads) == 4
+            pick = {"lamp82": lamp + [quads[0], quads[2]], "lamp3": [lamp[7], quads[0], quads[3]], "lamp1": [quads[1]], "none": []}[name]
+            hs.a["emit"] = np.int32(pick)
+        _scenes[name] = hs
+    return _scenes[name]
+
+
+def params(spp=SPP, w=W, h=HH, **kw):
+    eye, cam = H.camera_orbit(5.0, 20.0, 30.0)
+    return B.make_params(w, h, spp, eye, cam, **kw)
+
+
+def render(hip, name, p, mode):
+    with hip.scene(lamp_scene(name)) as sc:
+        sc.set_light_sampling(mode)
+        return sc.render(p)
+
+
+@pytest.fixture(scope="module")
+def one_ref(hip):
+    """The lamp scene, one light per vertex, 6 spp: what the invariants below compare with."""
+    return render(hip, "lamp", params(), _abi.LIGHTS_ONE)
+
+
+@pytest.fixture(scope="module")
+def all_ref(hip):
+    return render(hip, "lamp", params(), _abi.LIGHTS_ALL)
+
+
+# ------------------------------------------------------------------------------------------------------ 1. the draw, bit for bit --
+
+def _rows(table, n_random=4096):
+    """Uniforms [n, 4]: random rows, every slot with u2 exactly at, just below and just above its accept, u1 in {0, 1.0f} and at every slot
+    boundary, (u3, u4) on both sides of the fold and on it."""
+    n = len(table)
+    rng = np.random.default_rng(5 + n)
+    u = rng.random((n_random, 4)).astype(np.float32)
+    one = np.float32(1)
+    edge = []
+    for s in range(n):
+        u1 = np.float32((s + 0.5) / n)
+        acc = table["accept"][s]
+        for u2 in (acc, np.nextafter(acc, np.float32(-1)), np.nextafter(acc, np.float32(2)), np.float32(0), one):
+            edge.append((u1, min(max(u2, np.float32(0)), one), rng.random(dtype=np.float32), rng.random(dtype=np.float32)))
+        b = np.float32(s / n)
+        for u1b in (b, np.nextafter(b, np.float32(-1)), np.nextafter(b, np.float32(2))):
+            edge.append((min(max(u1b, np.float32(0)), one), rng.random(dtype=np.float32), rng.random(dtype=np.float32), rng.random(dtype=np.float32)))
+    for u1 in (np.float32(0), one):
+        for u3, u4 in ((0.5, 0.5), (0.25, 0.75), (1, 1), (0, 0), (1, 0), (0.75, 0.2500001), (0.6, 0.7), (1, 1e-30)):
+            edge.append((u1, rng.random(dtype=np.float32), np.float32(u3), np.float32(u4)))
+    return np.concatenate([u, np.array(edge, np.float32)])
+
+
+@pytest.mark.parametrize("name", ["lamp1", "lamp3", "lamp82"])
+def test_device_draw_equals_the_statement_bit_for_bit(hip_debug, name):
+    hs = lamp_scene(name)
+    n = len(hs.a["emit"])
+    assert n == {"lamp1": 1, "lamp3": 3, "lamp82": 82}[name]
+    table = spec.table_of(hip_debug.lib, hs.tri_f32(), hs.a["emit"])
+    p = spec.weights(hs.tri_f32(), hs.a["emit"])
+    assert np.abs(spec.implied(table) - p).max() < 1e-6
+    u = _rows(table)
+    assert len(u) >= 4096 and (u[:, 0] == 0).any() and (u[:, 0] == 1).any()
+    assert n == 1 or (u[:, 1] == table["accept"][spec.slot_of(u[:, 0], n)]).sum() >= n
+    with hip_debug.scene(hs) as sc:
+        entry, rx, ry, w_draw, w_entry = spec.sample_device(sc, u)
+    want_entry, own, want_rx, want_ry, want_w = spec.draw_f32(table, *u.T)
+    bad = np.flatnonzero(entry != want_entry)
+    assert len(bad) == 0, (len(bad), u[bad[0]], entry[bad[0]], want_entry[bad[0]])
+    assert same_bits(rx, want_rx) and same_bits(ry, want_ry)
+    assert same_bits(w_draw, want_w), np.flatnonzero(w_draw != want_w)[:5]
+    assert same_bits(w_entry, want_w), "consume forms the weight again from the entry alone: the same float"
+    assert (rx + ry <= 1).all() and (rx >= 0).all() and (ry >= 0).all()
+    if n > 1:
+        assert own.any() and (~own).any()
+
+
+def test_device_draw_refuses_a_scene_without_entries(hip_debug):
+    with hip_debug.scene(lamp_scene("none")) as sc:
+        with pytest.raises(B.JadeError) as ei:
+            spec.sample_device(sc, np.zeros((4, 4), np.float32))
+    assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. the anchors --
+
+def test_without_emitter_entries_one_light_is_all_lights_in_every_float_and_counter(hip):
+    p = params()
+    a = render(hip, "none", p, _abi.LIGHTS_ALL)
+    o = render(hip, "none", p, _abi.LIGHTS_ONE)
+    assert same_bits(a[0], o[0]) and np.array_equal(a[1], o[1])
+    assert counters(a[2]) == counters(o[2]) and a[2].rays_shadow == 0
+
+
+def test_the_default_mode_is_todays_render_after_a_round_trip(hip, all_ref):
+    hs = lamp_scene("lamp")
+    with hip.scene(hs) as sc:
+        assert sc.light_sampling == _abi.LIGHTS_ALL
+        fresh = sc.render(params())
+    with hip.scene(hs) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        assert sc.light_sampling == _abi.LIGHTS_ONE
+        sc.set_light_sampling(_abi.LIGHTS_ALL)
+        assert sc.light_sampling == _abi.LIGHTS_ALL
+        back = sc.render(params())
+    for got in (fresh, back):
+        assert same_bits(got[0], all_ref[0]) and np.array_equal(got[1], all_ref[1])
+        assert all_counters(got[2]) == all_counters(all_ref[2])
+    assert fresh[2].rays_inline > 0, "the fused first pass runs"
+
+
+# ------------------------------------------------------------------------------------------------------------- 3. the invariants --
+
+def _is_ref(out, ref, what=""):
+    assert same_bits(out[0], ref[0]) and np.array_equal(out[1], ref[1]), what
+    assert counters(out[2]) == counters(ref[2]), what
+
+
+def test_the_frame_is_finite_lit_and_not_all_lights(one_ref, all_ref):
+    rgb, bgr, st = one_ref
+    assert np.isfinite(rgb).all() and rgb.max() > 0 and st.samples == W * HH * SPP
+    assert not same_bits(rgb, all_ref[0])
+    assert st.rays_inline > 0 and st.tail_launches == 0, "the fused first pass stays, the tail kernel does not run"
+    # the camera rays and what they meet are the same in both modes
+    assert st.rays_primary == all_ref[2].rays_primary
+
+
+def test_the_same_bits_twice(hip, one_ref):
+    _is_ref(render(hip, "lamp", params(), _abi.LIGHTS_ONE), one_ref)
+
+
+@pytest.mark.parametrize("walk", [_abi.WALK_REFERENCE, _abi.WALK_EARLY_EXIT, _abi.WALK_EARLY_EXIT_CACHED])
+def test_the_same_bits_under_the_three_walks(hip, one_ref, walk):
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        for _ in range(2 if walk == _abi.WALK_EARLY_EXIT_CACHED else 1):  # (the second time with what the first left in the cache)
+            rgb, bgr, st = sc.render(params(walk=walk))
+            assert same_bits(rgb, one_ref[0]) and np.array_equal(bgr, one_ref[1])
+            c, r = counters(st), counters(one_ref[2])
+            assert {k: v for k, v in c.items() if k not in ("nodes_visited", "tris_tested")} == {k: v for k, v in r.items() if k not in ("nodes_visited", "tris_tested")}
+
+
+def test_steps_equal_one_call(hip, one_ref):
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        sc.begin(params())
+        st = _abi.Stats()
+        for _ in range(3):
+            sc.step(2, st)
+        sc.set_light_sampling(_abi.LIGHTS_ALL)  # a render in progress keeps the mode it began with
+        sc.flush(st)
+        rgb, bgr = sc.resolve()
+    _is_ref((rgb, bgr, st), one_ref, "3 steps of 2 + flush")
+
+
+def test_two_tile_shares_assemble_to_the_frame(hip, one_ref):
+    acc, acc_b = np.zeros_like(one_ref[0]), np.zeros_like(one_ref[1])
+    tot = {k: 0 for k in counters(one_ref[2])}
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        for r in range(2):
+            part, part_b, st = sc.render(params(tile_rank=r, tile_nranks=2))
+            assert not ((acc != 0) & (part != 0)).any()
+            acc += part
+            acc_b += part_b
+            for k, v in counters(st).items():
+                tot[k] += v
+    assert same_bits(acc, one_ref[0]) and np.array_equal(acc_b, one_ref[1])
+    assert tot == counters(one_ref[2])
+
+
+SCHEDULES = [
+    dict(JADE_RECORDS_PER_PIXEL="1"), dict(JADE_FUSED="0"), dict(JADE_SHADE_SPLIT="0", JADE_BATCH="0", JADE_RAY_RECORDS="0"),
+    dict(JADE_SORT="1", JADE_SORT_MIN="64"), dict(JADE_SORT="1", JADE_SORT_MIN="64", JADE_SORT_KEYS_KERNEL="1"),
+    # switches of kernels this mode does not run: no effect
+    dict(JADE_SHADE_BINNED="1", JADE_TAIL="1"), dict(JADE_TAIL="0", JADE_LIGHT_PACKET="0"),
+]
+
+
+@pytest.mark.parametrize("env", SCHEDULES, ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
+def test_records_per_pixel_and_schedules_are_one_result(hip, one_ref, monkeypatch, env):
+    """JADE_RECORDS_PER_PIXEL=1 against the default (6 spp: 8 records per pixel), and the schedules that change how a ray's kind is
+    read off its slot number (ordered queues, with the keys from either kernel)."""
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        sc.begin(params())
+        rpp = sc.query(_abi.Q_RECORDS_PER_PIXEL)
+        out = sc.render(params(walk=_abi.WALK_EARLY_EXIT))
+    assert rpp == (1 if "JADE_RECORDS_PER_PIXEL" in env else 8)
+    assert same_bits(out[0], one_ref[0]) and np.array_equal(out[1], one_ref[1]), env
+    c, r = counters(out[2]), counters(one_ref[2])
+    assert {k: v for k, v in c.items() if k not in ("nodes_visited", "tris_tested")} == {k: v for k, v in r.items() if k not in ("nodes_visited", "tris_tested")}
+
+
+def test_secondary_rays_are_the_sum_of_their_five_parts(one_ref):
+    st = one_ref[2]
+    assert st.rays_secondary == st.rays_shadow + st.rays_env + st.rays_indirect + st.rays_mirror + st.rays_refract
+    assert min(st.rays_shadow, st.rays_env, st.rays_indirect, st.rays_mirror) > 0
+
+
+def test_with_environment_importance_on_top(hip, one_ref):
+    p = params(env_sampling=_abi.ENV_IMPORTANCE)
+    a = render(hip, "lamp", p, _abi.LIGHTS_ONE)
+    b = render(hip, "lamp", p, _abi.LIGHTS_ONE)
+    assert same_bits(a[0], b[0]) and counters(a[2]) == counters(b[2])
+    assert np.isfinite(a[0]).all() and not same_bits(a[0], one_ref[0])
+    st = a[2]
+    assert st.rays_secondary == st.rays_shadow + st.rays_env + st.rays_indirect + st.rays_mirror + st.rays_refract
+    # at most one shadow ray per sampling vertex; a vertex whose sky direction lay on the wrong side has no environment ray, so the
+    # vertices are counted by the all-lights render of the same mode: 84 slots each, of which the side test drops some
+    assert 0 < st.rays_shadow and st.tail_launches == 0
+
+
+def test_adaptive_sampling_and_the_denoiser_run_on_top(hip):
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        rgb, bgr, tile_spp, st = sc.render_adaptive(params(spp=32), 8, 0.05)
+        assert np.isfinite(rgb).all() and (tile_spp >= 8).all() and st.tail_launches == 0
+        sc.render(params(spp=8))
+        dn, _ = sc.denoise()
+        assert np.isfinite(dn).all() and dn.max() > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------- 4. the work --
+
+def test_at_most_one_shadow_ray_per_sampling_vertex(one_ref, all_ref):
+    """JADE_ENV_REFERENCE sends one environment ray per sampling vertex, so rays_env counts the vertices."""
+    one, al = one_ref[2], all_ref[2]
+    assert 0 < one.rays_shadow <= one.rays_env
+    assert al.rays_shadow > al.rays_env
+    assert al.rays_shadow <= 84 * al.rays_env
+
+
+# ----------------------------------------------------------------------------------------------------------------- 5. the memory --
+
+def _bytes_per_record(n_shadow_slots):
+    """jade_render_begin: bytes_per_record = 4 (34 + 5 nslots) + 6 nslots with nslots = shadow slots + 2 (ray records on, the default)."""
+    nslots = n_shadow_slots + 2
+    return 4 * (34 + 5 * nslots) + 6 * nslots
+
+
+def test_records_per_pixel_do_not_fall_with_the_emitter_count(hip):
+    """Under one fixed max_state_bytes the 81 924-entry scene gets at least the records per pixel in this mode that the 82-entry
+    scene gets with all lights.  The bound is chosen so that the 82-entry scene's all-lights records (84 slots) fit 16 times per
+    pixel and not 32 times: partial sums 12 x 64 lanes x npx, records npx x rpp x bytes_per_record."""
+    spp = 64
+    npx = ((W + 15) // 16) * ((HH + 15) // 16) * 256
+    budget = 12 * 64 * npx + npx * 16 * _bytes_per_record(82) + 4096
+    assert budget < 12 * 64 * npx + npx * 32 * _bytes_per_record(82)
+    p = params(spp=spp)
+    p.max_state_bytes = budget
+    with hip.scene(lamp_scene("lamp82")) as sc:
+        sc.begin(p)
+        rpp_all_82 = sc.query(_abi.Q_RECORDS_PER_PIXEL)
+    with hip.scene(lamp_scene("big")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        sc.begin(p)
+        rpp_one_big = sc.query(_abi.Q_RECORDS_PER_PIXEL)
+    assert rpp_all_82 == 16
+    assert rpp_one_big >= rpp_all_82 and rpp_one_big == 64
+
+
+def test_a_frame_all_lights_has_no_memory_for_renders_with_one_light(hip):
+    """max_state_bytes = twice what this mode needs for 256 x 256 at one record per pixel: partial sums 12 x 1 lane x npx + npx x
+    bytes_per_record(1 shadow slot) = 4 (34 + 5 x 3) + 6 x 3 = 214 bytes.  With all lights one record has 81 926 slots, 2.13 MB: a 64 x 64
+    frame's 4 096 records are 8.7 GB and JADE_ERR_NOMEM under that bound, and 256 x 256 is refused outright (the 32-bit slot index)."""
+    npx = 256 * 256
+    budget = 2 * (12 * npx + npx * _bytes_per_record(1))
+    assert _bytes_per_record(1) == 214
+    assert 64 * 64 * _bytes_per_record(81924) > budget and 64 * 64 * (81924 + 2) < 2 ** 32 <= npx * (81924 + 2)
+    with hip.scene(lamp_scene("big")) as sc:
+        small = params(spp=1, w=64, h=64)
+        small.max_state_bytes = budget
+        with pytest.raises(B.JadeError) as ei:
+            sc.begin(small)
+        assert ei.value.code == _abi.JADE_ERR_NOMEM
+        large = params(spp=1, w=256, h=256)
+        large.max_state_bytes = budget
+        with pytest.raises(B.JadeError) as ei:
+            sc.begin(large)
+        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        rgb, bgr, st = sc.render(large)
+        assert sc.query(_abi.Q_RECORDS_PER_PIXEL) == 1
+    assert st.samples == 256 * 256 and np.isfinite(rgb).all() and rgb.max() > 0
+    assert 0 < st.rays_shadow <= st.rays_env
+
+
+# ----------------------------------------------------------------------------------------------------------- 6. the same integral --
+
+WELCH_K = 8
+WELCH_SPP = 8      # the smallest power of two at which the scaled group is told apart (measured: see the test's docstring)
+WELCH_LIMIT = 4.5
+
+
+def welch_t(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float((a.mean() - b.mean()) / np.sqrt(a.var(ddof=1) / len(a) + b.var(ddof=1) / len(b)))
+
+
+def welch_totals(hip, spp):
+    """Per mode, the WELCH_K totals of radiance over the lit pixels: frames of independent samples (frame = 1000 k), both modes from the
+    same seeds.  Lit pixels: those that do not look straight into a lamp - every channel below 4, the weakest lamp channel - in an
+    all-lights frame of other samples (frame = 500 000); the same pixels for every frame of both groups."""
+    hs = lamp_scene("lamp")
+    with hip.scene(hs) as sc:
+        mask = (sc.render(params(spp=64, frame=500000))[0] < 4).all(-1)
+        assert 0.5 < mask.mean() < 1
+        totals = {}
+        for mode in (_abi.LIGHTS_ALL, _abi.LIGHTS_ONE):
+            sc.set_light_sampling(mode)
+            totals[mode] = [float(sc.render(params(spp=spp, frame=1000 * k))[0].astype(np.float64)[mask].sum()) for k in range(WELCH_K)]
+    return totals[_abi.LIGHTS_ALL], totals[_abi.LIGHTS_ONE]
+
+
+def test_both_modes_estimate_the_same_integral(hip):
+    """Welch's t of eight totals per mode, |t| < 4.5 (two-sided p about 5e-4 at these degrees of freedom); with one group scaled by
+    1.03 the same statistic must exceed 4.5, or the test could not fail.  The seeds are fixed: every run gives the same numbers.
+    Measured on an MI355X, (t, t with one light x 1.03, t with all lights x 1.03) at 1 / 2 / 4 / 8 / 16 / 32 / 64 spp:
+    (-0.59, -3.10, +1.93) (-0.18, -3.56, +3.23) (+0.40, -4.23, +5.08) (+0.64, -8.82, +10.22) (+0.75, -11.16, +12.68) (-0.03, -15.96, +15.74)
+    (-0.41, -24.21, +23.18): 8 spp is the smallest power of two at which both scaled groups are told apart.  Totals at 8 spp: all
+    lights 2880.9 +- 12.8, one light 2875.2 +- 21.8."""
+    a, o = welch_totals(hip, WELCH_SPP)
+    t = welch_t(a, o)
+    t_up = welch_t(a, np.array(o) * 1.03)
+    t_down = welch_t(np.array(a) * 1.03, o)
+    print(f"welch: spp {WELCH_SPP}  all {np.mean(a):.6g} +- {np.std(a, ddof=1):.3g}  one {np.mean(o):.6g} +- {np.std(o, ddof=1):.3g}  "
+          f"t {t:+.3f}  one x 1.03: {t_up:+.3f}  all x 1.03: {t_down:+.3f}")
+    assert abs(t) < WELCH_LIMIT
+    assert abs(t_up) > WELCH_LIMIT and abs(t_down) > WELCH_LIMIT
+
+
+# -------------------------------------------------------------------------------------------------------------- 7. the refusals --
+
+def test_the_oracle_has_no_such_entry_point(oracle):
+    with oracle.scene(lamp_scene("lamp1")) as so:
+        with pytest.raises(B.JadeError) as ei:
+            so.set_light_sampling(_abi.LIGHTS_ONE)
+        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
+        with pytest.raises(B.JadeError):
+            so.light_sampling
+
+
+def test_an_unknown_mode_is_invalid_and_leaves_the_mode(hip):
+    with hip.scene(lamp_scene("lamp1")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        for bad in (2, -1, 255):
+            with pytest.raises(B.JadeError) as ei:
+                sc.set_light_sampling(bad)
+            assert ei.value.code == _abi.JADE_ERR_INVALID
+            assert sc.light_sampling == _abi.LIGHTS_ONE
+
+
+def test_a_lens_or_a_shutter_is_refused_by_name(hip, one_ref):
+    p = params()
+    eye, cam = np.array(p.eye[:], np.float32), np.array(p.camera[:], np.float32)
+    with hip.scene(lamp_scene("lamp")) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        sc.set_lens(0.05, 4.0)
+        with pytest.raises(B.JadeError) as ei:
+            sc.begin(p)
+        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_LIGHTS_ONE" in str(ei.value) and "lens" in str(ei.value)
+        sc.set_lens(0.0)
+        sc.set_shutter(eye, cam)
+        with pytest.raises(B.JadeError) as ei:
+            sc.render(p)
+        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_LIGHTS_ONE" in str(ei.value) and "shutter" in str(ei.value)
+        sc.set_shutter(None)
+        _is_ref(sc.render(p), one_ref, "the refusals left the handle usable")
+        # ... and with all lights both still render
+        sc.set_light_sampling(_abi.LIGHTS_ALL)
+        sc.set_lens(0.05, 4.0)
+        assert np.isfinite(sc.render(p)[0]).all()
+
+
+def test_render_multi_refuses_scenes_of_different_modes(hip, one_ref):
+    p = params()
+    hs = lamp_scene("lamp")
+    with hip.scene(hs) as s0, hip.scene(hs) as s1:
+        s0.set_light_sampling(_abi.LIGHTS_ONE)
+        with pytest.raises(B.JadeError) as ei:
+            B.render_multi(hip, [s0, s1], p)
+        assert ei.value.code == _abi.JADE_ERR_INVALID and "light sampling" in str(ei.value)
+        s1.set_light_sampling(_abi.LIGHTS_ONE)
+        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
+    assert same_bits(rgb, one_ref[0]) and np.array_equal(bgr, one_ref[1])
+
+
+def test_the_command_line(tmp_path):
+    out = tmp_path / "one.ppm"
+    r = subprocess.run([CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4", "--one-light", "--out", str(out)],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    start = [ln for ln in r.stdout.splitlines() if ln.startswith("Start...")]
+    assert len(start) == 1 and start[0].endswith("on hip-gfx950, one light per vertex") and out.exists()
+    r = subprocess.run([CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4", "--one-light", "--backend",
+                        os.path.join(ROOT, "oracle", "libjade_oracle.so"), "--out", str(out)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--one-light needs the HIP backend" in r.stderr
