@@ -444,7 +444,9 @@ int jade_scene_get_shutter(jade_scene* scene, jade_shutter_params* out, int* is_
  * values, the three walks, tile partitions, progressive steps, adaptive sampling, the guides and the denoiser, exposure and glare.
  *
  * ---- The lights, stated ----
- * tests/lights_spec.py is this text in float64.  nE = n_emit; entry i names triangle t_i = emit_indices[i].  Duplicates are separate
+ * tests/lights_spec.py is this text in float64 for the draw itself, and the light_sampling arm of tests/jade_spec.py for what the
+ * integrator does with a draw (where the four uniforms sit in each branch's stream, the entry's term and its weight, what follows).
+ * nE = n_emit; entry i names triangle t_i = emit_indices[i].  Duplicates are separate
  * entries, and an entry whose triangle does not emit is still an entry.  fl() rounds to fp32.
  *
  * The distribution.  a_i = the area the integrator itself multiplies the entry's term by - 0.5f * sqrt(dot(c, c)) with c = cross(p2 - p1,

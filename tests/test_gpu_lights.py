@@ -1,6 +1,7 @@
 """One-light sampling on the device (include/jade_bvh.h, "The lights, stated"; jade_scene_set_light_sampling): the draw against
 tests/lights_spec.py bit for bit, the two anchors (no emitter entry: JADE_LIGHTS_ALL's render; the default mode: today's), the
-invariants every mode is held to, the work and the memory the mode is for, the integral it estimates, and what it refuses."""
+invariants every mode is held to, the work and the memory the mode is for, the integral it estimates, what it refuses, and (section 8)
+the render against tests/jade_spec.py's one-light arm, sample for sample: how the shading kernels USE a draw."""
 import os
 import subprocess
 
@@ -469,3 +470,73 @@ def test_the_command_line(tmp_path):
     r = subprocess.run([CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4", "--one-light", "--backend",
                         os.path.join(ROOT, "oracle", "libjade_oracle.so"), "--out", str(out)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 2 and "--one-light needs the HIP backend" in r.stderr
+
+
+# ------------------------------------------------------------------------ 8. the render against the float64 statement, sample for sample --
+# How bounce_branch<.., LIGHTS> and consume<.., LIGHTS> USE a draw: jade_spec's one-light arm (include/jade_bvh.h's text in float64; checked
+# without a GPU in tests/test_lights_spec_cpu.py) against 12 x 12 frames at 1 spp, by test_jade_spec.compare and its bar, unchanged: a
+# sample agrees when every channel is within 1e-4 relative (floor 1e-3), at most 2 % may disagree, bssrdf-coplanar samples are left out
+# (here: at most 5 % of a case).
+
+import test_jade_spec as TJ  # noqa: E402
+
+_checked = {}
+
+
+def checked(hip, case):
+    """compare() of one case of TJ.LIGHT_CASES, once per session: (seen, bad, n, skipped, {"frames", "worst"})."""
+    if case not in _checked:
+        c = TJ.LIGHT_CASES[case]
+        out = {}
+        r = TJ.compare(hip, c["kind"], c["size"], c["frames"], c["need"], sky=c.get("sky", False), env_sampling=c.get("env_sampling", _abi.ENV_REFERENCE),
+                       light_sampling=_abi.LIGHTS_ONE, max_left_out=0.05, out=out)
+        _checked[case] = r + (out,)
+    return _checked[case]
+
+
+def one_light_frames(hip, case, kind=None):
+    """The frames of a case as compare renders them, from a scene handle of its own (kind: another emitter list of the same geometry)."""
+    c = TJ.LIGHT_CASES[case]
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    with hip.scene(TJ.build(kind or c["kind"], c.get("sky", False))) as sc:
+        sc.set_light_sampling(_abi.LIGHTS_ONE)
+        return {f: sc.render(B.make_params(c["size"], c["size"], 1, eye, cam, frame=f, threads=2, env_sampling=c.get("env_sampling", _abi.ENV_REFERENCE)),
+                             want_bgr8=False)[0] for f in c["frames"]}
+
+
+@pytest.mark.parametrize("case", sorted(TJ.LIGHT_CASES))
+def test_the_render_is_the_float64_statement_sample_for_sample(hip, case):
+    """two_lamps: two lamps of unequal power, a duplicate entry and a listed non-emitter (own and alias, the side test's `continue`, lit
+    and shadowed, in the diffuse, SSS-diffuse and BSSRDF branch); ..._sky and ..._sky_importance: under the textured sky in both
+    env_sampling modes - k_shade_lights_envis, four light draws before four environment draws; one_entry: nE = 1, weight exactly 1, only the
+    four-for-two draw count differs from all lights; fan: 24 entries over 3.4 orders of magnitude, weights above 100, aliases
+    frequent, a lit sample with a weight above 50 must agree; dark_list: only non-emitters listed - every term is zero and the draws
+    still move everything behind them.
+
+    Measured on the MI355X, samples compared / disagreeing / left out, and the worst relative error of an agreeing sample:
+    two_lamps 560 / 0 / 16, 3.1e-6; two_lamps_sky 422 / 0 / 10, 4.6e-6; two_lamps_sky_importance 421 / 0 / 11, 7.7e-6; one_entry 422 / 0 / 10,
+    3.1e-6; fan 560 / 0 / 16, 1.7e-5; dark_list 422 / 0 / 10, 1.7e-5 (the bar is 1e-4; the all-lights cases' worst is 5e-6)."""
+    seen, bad, n, skipped, out = checked(hip, case)
+    assert n + skipped == len(TJ.LIGHT_CASES[case]["frames"]) * 144
+    assert out["worst"] <= 1e-4
+
+
+def test_a_dark_list_still_moves_the_draws(hip):
+    """Every term of the dark list is zero, so its frames and the frames of the same triangles with NO list gather the same light - from
+    other draws: four uniforms per sampling vertex against none."""
+    _, _, _, _, out = checked(hip, "dark_list")
+    bare = one_light_frames(hip, "dark_list", kind="no_list")
+    for f, rgb in out["frames"].items():
+        assert not same_bits(rgb, bare[f])
+
+
+@pytest.mark.parametrize("env", [SCHEDULES[1], SCHEDULES[3], SCHEDULES[0]], ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
+def test_the_checked_frames_are_the_same_bits_under_other_schedules(hip, monkeypatch, env):
+    """The unfused first pass, ordered queues and one record per pixel give the very arrays that were compared with the statement: the
+    schedule matrix of section 3 hangs on a frame that has been checked."""
+    _, _, _, _, out = checked(hip, "two_lamps")
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
+    again = one_light_frames(hip, "two_lamps")
+    for f, rgb in out["frames"].items():
+        assert same_bits(again[f], rgb), (env, f)
