@@ -494,6 +494,66 @@ int jade_scene_get_shutter(jade_scene* scene, jade_shutter_params* out, int* is_
 int jade_scene_set_light_sampling(jade_scene* scene, int mode);
 int jade_scene_get_light_sampling(jade_scene* scene, int* mode);
 
+/* ---- Cosine-weighted bounce sampling ----
+ *
+ * Non-parity: at every diffuse, SSS-diffuse and BSSRDF vertex the reference draws its environment ray and its indirect ray uniformly on
+ * the sphere, flips them into a hemisphere (pdf 1 / 2 pi) and weighs them with a bare |dot(n, d)| (PathTrace.cu:968-974, 992-998,
+ * 1111-1117, 1136-1142, 1304-1310, 1328-1334).  Under JADE_BOUNCE_COSINE those two rays are drawn with pdf cos / pi about the normal
+ * instead, and the cosine leaves the weight: another estimator of the SAME integral, not the reference's sample for sample - none of
+ * jade_rt.h's parity statements apply to it, as for JADE_ENV_IMPORTANCE and JADE_LIGHTS_ONE.  The rays per vertex, the number of draws
+ * and their places in the sample's stream, and the layout of a path record are the reference's.  The mode is a property of the scene
+ * handle, read by the next jade_render_begin - so by jade_render, jade_render_adaptive, jade_render_multi (per scene) - and a render in
+ * progress keeps the mode it began with.  JADE_BOUNCE_UNIFORM (0, the default) is today's render in every kernel, bit and counter.
+ * JADE_BOUNCE_COSINE composes with both env_sampling values (under JADE_ENV_IMPORTANCE the environment ray stays the importance draw
+ * with its own weight, and only the indirect ray changes), both light samplings, the three walks, tile partitions, progressive steps,
+ * adaptive sampling, the guides and the denoiser, exposure and glare.
+ *
+ * ---- The bounce, stated ----
+ * tests/bounce_spec.py is this text in float64.  fl() rounds to fp32; every operation below is one fp32 operation unless it says double.
+ * Where the reference's sphere direction takes two uniforms from the sample's stream (cosine first, angle second) this mode takes the
+ * same two, u1 then u2 - each jade_rand's fl(uint32) * 2^-32, in [0, 1], 1.0f included.
+ *
+ * Axis.  n is the normal the branch already uses - the vertex's flat normal at a diffuse or SSS-diffuse vertex, the exit triangle's
+ * (t_norm) at a BSSRDF vertex - as stored, of any length.  nn = dot(n, n) = fma(n.z, n.z, fma(n.y, n.y, n.x * n.x)).
+ *   If !(nn > 0 && nn < inf) the vertex FALLS BACK: the direction is the reference's sphere direction on the same two uniforms
+ *   (cos = fl(2 (double(u1) - 0.5)), sin = sqrt(1 - cos * cos), phi as below, d = (sin * cos phi, sin * sin phi, cos)) with the
+ *   reference's own flip, and every weight is the reference's.
+ *   Otherwise a = s * (n / sqrt(nn)), the division per component, with s = -1 where the reference would flip a direction along +n and +1
+ *   elsewhere: diffuse / SSS-diffuse, both rays: s = -1 iff side < 0 (side = dot(out, n));  BSSRDF environment ray: s = -1 iff
+ *   dot(inner, t_norm) < 0;  BSSRDF indirect ray: s = -1 iff dot(inner, t_norm) > 0 - the OPPOSITE hemisphere, as the reference has it.
+ * Frame (branchless; Duff, Burgess, Christensen, Hery, Kensler, Liani, Villemin: Building an Orthonormal Basis, Revisited, JCGT 2017):
+ *     sg = a.z >= 0 ? 1 : -1        (-0 counts as >= 0)
+ *     p  = -1 / (sg + a.z)
+ *     q  = (a.x * a.y) * p
+ *     t  = (1 + ((sg * a.x) * a.x) * p,   sg * q,                -sg * a.x)
+ *     b  = (q,                            sg + (a.y * a.y) * p,  -a.y)
+ * Direction.  r = sqrt(u1), cz = sqrt(1 - u1);  phi = fl(2 pi * double(u2)), the product in double, as the reference forms it;
+ * (sn, cs) = jade_sincosf(phi);
+ *     d = (t * (r * cs) + b * (r * sn)) + a * cz          (per component: three products, two sums, in this order)
+ * so that dot(d, a) = cz up to rounding: pdf(d) = cz / pi.
+ * Weight.  Against the reference's pdf 1 / 2 pi its term is multiplied by 1 / (2 cz), and |dot(n, d)| / (2 cz) = sqrt(nn) / 2: the
+ * module uses that closed form.  In the four places where the reference multiplies by |dot(n, d)| - the environment term and the
+ * indirect rate of the diffuse / SSS-diffuse branch, the environment term and the indirect rate of the BSSRDF branch (there with t_norm)
+ * - this mode multiplies by 0.5f * sqrt(nn) instead, unless the vertex falls back (the predicate is formed again from the same normal),
+ * and changes nothing else of the statement: Schlick's term of |dot(d, t_norm)| is part of the integrand and stays.  Nothing travels
+ * with the record.  There is no division by cz, so u1 = 1.0f - a direction in the tangent plane - carries a finite weight.
+ * Under JADE_ENV_IMPORTANCE the environment ray and its term are that mode's, unchanged; the indirect ray is this mode's.
+ * The estimator is unbiased because pdf > 0 wherever the integrand's cosine is: E[f / pdf] over the hemisphere is the reference's.
+ * jade_stats: every counter keeps its meaning; nodes_visited and tris_tested differ because the rays do.
+ *
+ * The schedule is JADE_ENV_IMPORTANCE's: the fused first pass stays (it draws no hemisphere direction), there is no tail
+ * kernel (tail_launches is 0) and JADE_SHADE_BINNED is ignored.  Results do not depend on steps, tile partitions or records per pixel.
+ *
+ * jade_scene_set_bounce_sampling: an unknown mode returns JADE_ERR_INVALID and leaves the previous mode in place.
+ * jade_render_begin refuses JADE_BOUNCE_COSINE with JADE_ERR_UNSUPPORTED together with a lens (jade_scene_set_lens, aperture_radius > 0)
+ * or a shutter (jade_scene_set_shutter): those kernels do not exist yet.
+ * jade_render_multi: all scenes must carry the same mode, else JADE_ERR_INVALID before anything is launched. */
+#define JADE_BOUNCE_UNIFORM 0
+#define JADE_BOUNCE_COSINE 1
+
+int jade_scene_set_bounce_sampling(jade_scene* scene, int mode);
+int jade_scene_get_bounce_sampling(jade_scene* scene, int* mode);
+
 #ifdef __cplusplus
 }
 #endif

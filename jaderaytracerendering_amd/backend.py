@@ -430,6 +430,22 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(mode)))
         return mode.value
 
+    def set_bounce_sampling(self, mode):
+        """jade_scene_set_bounce_sampling: _abi.BOUNCE_UNIFORM (the default: environment and indirect rays uniform over the hemisphere, as
+        the reference draws them) or _abi.BOUNCE_COSINE (drawn with pdf cos / pi about the normal, the cosine taken out of the weight; HIP
+        module only; non-parity: include/jade_bvh.h, "The bounce, stated").  Taken by the next render this handle begins.
+        JadeError(JADE_ERR_INVALID) leaves the previous mode in place."""
+        fn = self._hip_only("jade_scene_set_bounce_sampling")
+        self.backend.check(fn(self._h, int(mode)))
+
+    @property
+    def bounce_sampling(self):
+        """jade_scene_get_bounce_sampling: the mode the next render of this handle takes."""
+        fn = self._hip_only("jade_scene_get_bounce_sampling")
+        mode = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(mode)))
+        return mode.value
+
     def focus_distance(self, params, px, py):
         """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
         (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that

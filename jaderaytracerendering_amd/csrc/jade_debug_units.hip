@@ -1,6 +1,6 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
+// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table; the cosine bounce draw, cosine_dir_with), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
 // jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py) and the BSSRDF branch's exit-triangle search (exit_search, jade_shade.h, and
 // its tables, guide_tables, jade_scene_prep.hip; tests/test_area_search_cpu.py, tests/test_gpu_area_search.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
@@ -163,6 +163,26 @@ __global__ void k_debug_env_sample_rng(DevScene S, int n, uint32_t* rng, float* 
   if (i >= n) return;
   uint32_t state = rng[i];
   put3(dir, i, env_sample(S, &state, ratio + i));
+  rng[i] = state;
+}
+
+// cosine_dir_with's body (jade_shade.h; include/jade_bvh.h "The bounce, stated") on row i = (n[3], s, u1, u2): the direction and whether
+// the normal gave no axis ...
+__global__ void k_debug_bounce_dir(int n, const float* rows, float* dir, int32_t* fallback) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + 6 * (size_t)i;
+  bool fb;
+  put3(dir, i, cosine_dir_at(r + 4, jv(r[0], r[1], r[2]), r[3], &fb));
+  fallback[i] = fb ? 1 : 0;
+}
+// ... and the wrapper the shading kernel calls, on row i = (n[3], s) from RNG state rng[i]; the state it leaves is written back
+__global__ void k_debug_bounce_dir_rng(int n, const float* rows, uint32_t* rng, float* dir) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + 4 * (size_t)i;
+  uint32_t state = rng[i];
+  put3(dir, i, cosine_dir_rng(&state, jv(r[0], r[1], r[2]), r[3]));
   rng[i] = state;
 }
 
@@ -411,6 +431,40 @@ int jade_debug_light_sample(jade_scene* s, int32_t n, const float* u, uint32_t* 
   HIP_TRY(hipMemcpyAsync(out_rxy, bx.p, N * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(out_weight, bw.p, N * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// out_dir[i], out_fallback[i] = the draw of JADE_BOUNCE_COSINE (cosine_dir_with, jade_shade.h) on rows[i] = (n[3], s, u1, u2), 6 floats.
+int jade_debug_bounce_dir(int device_id, int32_t n, const float* rows, float* out_dir, int32_t* out_fallback) {
+  if (!rows || !out_dir || !out_fallback) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / 6) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bd, bf;
+  HIP_TRY(upload0(bi, rows, 6 * N));
+  HIP_TRY(bd.alloc(12 * N));
+  HIP_TRY(bf.alloc(4 * N));
+  hipLaunchKernelGGL(k_debug_bounce_dir, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), bd.as<float>(), bf.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out_dir, bd.p, 12 * N, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_fallback, bf.p, 4 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// ... and as bounce_branch draws it: rows[i] = (n[3], s), 4 floats, from the RNG states rng_in[i]; rng_out[i] is the state after the draw.
+int jade_debug_bounce_dir_rng(int device_id, int32_t n, const float* rows, const uint32_t* rng_in, uint32_t* rng_out, float* out_dir) {
+  if (!rows || !rng_in || !rng_out || !out_dir) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / 4) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bs, bd;
+  HIP_TRY(upload0(bi, rows, 4 * N));
+  HIP_TRY(upload0(bs, rng_in, N));
+  HIP_TRY(bd.alloc(12 * N));
+  hipLaunchKernelGGL(k_debug_bounce_dir_rng, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), bs.as<uint32_t>(), bd.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(rng_out, bs.p, 4 * N, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_dir, bd.p, 12 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 

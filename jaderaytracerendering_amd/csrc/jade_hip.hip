@@ -216,7 +216,9 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // stated"; non-parity; the k_shade*_shutter kernels only, which pass their ShutterConst as H)
 // LIGHTS: one emitter per sampling vertex, drawn from the table `lights` (include/jade_bvh.h, "The lights, stated"; non-parity; the
 // k_shade_lights* kernels only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// COSINE: the environment and indirect rays of a sampling vertex are drawn with pdf cos / pi about the normal (include/jade_bvh.h, "The bounce,
+// stated"; non-parity; the k_shade_cos* kernels only).  Nothing of it travels with the record.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
                                                     const ShutterConst* H = nullptr, const uint4* lights = nullptr) {
@@ -303,7 +305,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS>(S, px, c, &l_final, lights, light);
+      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, light);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
       } else if (r == CONSUME_EMITTED) {
@@ -335,13 +337,13 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           defer = true;
           break;
         }
-        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS>(S, px, c, &l_final, lights, &light)) {
+        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, &light)) {
           st = c.stage;
           if (!ENVIS || c.n_emit_rays != 0) break;
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
           // emitter, the roulette ended the path) has all its results already - nothing is visible: folded in right here (with the
           // reference's sampling there is always the environment ray)
-          const int r = consume<ENVIS, LIGHTS>(S, px, c, &l_final, lights, light);
+          const int r = consume<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, light);
           if (r == CONSUME_VERTEX) {
             st = ST_VERTEX;
             continue;
@@ -541,7 +543,7 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
@@ -563,7 +565,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights);
+  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -618,6 +620,33 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_li
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below, const uint4* lights) {
   shade_kernel_body<true, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+// ... and with cosine-weighted bounce sampling (jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE, non-parity), under either environment
+// sampling and either light sampling: the four kernels that carry that code.  All take k_shade_lights' arguments; `lights` is read by
+// the *_lights* two only.
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<false, false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<true, false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights) {
+  shade_kernel_body<true, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2176,6 +2205,19 @@ int jade_scene_get_light_sampling(jade_scene* s, int* mode) {
   return JADE_OK;
 }
 
+// The bounce sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_bounce_sampling(jade_scene* s, int mode) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (mode != JADE_BOUNCE_UNIFORM && mode != JADE_BOUNCE_COSINE) return jade_fail(JADE_ERR_INVALID, "unknown bounce sampling (JADE_BOUNCE_*)");
+  s->bounce_sampling = mode;
+  return JADE_OK;
+}
+int jade_scene_get_bounce_sampling(jade_scene* s, int* mode) {
+  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *mode = s->bounce_sampling;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -2269,6 +2311,11 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
     return jade_fail(JADE_ERR_UNSUPPORTED, std::string("light sampling: JADE_LIGHTS_ONE (jade_scene_set_light_sampling) does not run together with ") +
                                                (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
                                                " yet: those kernels are not built");
+  const bool cosine = s->bounce_sampling == JADE_BOUNCE_COSINE;
+  if (cosine && (s->lens.aperture_radius > 0.0f || s->shutter_set))
+    return jade_fail(JADE_ERR_UNSUPPORTED, std::string("bounce sampling: JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling) does not run together with ") +
+                                               (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
+                                               " yet: those kernels are not built");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
@@ -2338,6 +2385,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->adaptive_done = false;
   s->dn_carried = jade_stats{};
   s->lights_on = lights_one;  // the scene's light sampling as it is now: the render keeps it, like its lens
+  s->cosine_on = cosine;      // ... and its bounce sampling
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
@@ -2386,7 +2434,7 @@ struct PassRun {
   QueueCtl* qc;                       // s->b_ctl: entry 0 for passes the host follows, the ring for a batch
   decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
   decltype(&k_shade_shutter) shade_kernel_shutter = nullptr;  // under a shutter: the kernel launched instead, with s->sh as its last argument
-  decltype(&k_shade_lights) shade_kernel_lights = nullptr;    // JADE_LIGHTS_ONE: the kernel launched instead, with the emitters' alias table as its last argument
+  decltype(&k_shade_lights) shade_kernel_lights = nullptr;    // JADE_LIGHTS_ONE or JADE_BOUNCE_COSINE: the kernel launched instead, with the emitters' alias table as its last argument
   bool batching, tail_ok;
   uint32_t tail_max;                  // active records at or below which k_tail finishes the list
   uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
@@ -2807,8 +2855,11 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   if (shutter_on(s)) r.shade_kernel_shutter = s->ps.env_sampling ? k_shade_envis_shutter : k_shade_shutter;
   // one emitter per vertex (jade_render_begin refuses it under a lens or a shutter): its own kernels, JADE_SHADE_BINNED has no effect
   if (s->lights_on) r.shade_kernel_lights = s->ps.env_sampling ? k_shade_lights_envis : k_shade_lights;
+  // cosine-weighted bounces (refused under a lens or a shutter likewise): its own kernels under either light sampling, with the same arguments
+  if (s->cosine_on)
+    r.shade_kernel_lights = s->lights_on ? (s->ps.env_sampling ? k_shade_cos_lights_envis : k_shade_cos_lights) : (s->ps.env_sampling ? k_shade_cos_envis : k_shade_cos);
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s) && !s->lights_on;  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s) && !s->lights_on && !s->cosine_on;  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
   r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);

@@ -134,6 +134,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->light_sampling != scenes[0]->light_sampling)
       return jade_fail(JADE_ERR_INVALID, "the scenes carry different light sampling modes (jade_scene_set_light_sampling): scene " + std::to_string(i) + " against scene 0");
+  // ... and with the same bounce sampling (jade_scene_set_bounce_sampling)
+  for (int i = 1; i < ndev; ++i)
+    if (scenes[i]->bounce_sampling != scenes[0]->bounce_sampling)
+      return jade_fail(JADE_ERR_INVALID, "the scenes carry different bounce sampling modes (jade_scene_set_bounce_sampling): scene " + std::to_string(i) + " against scene 0");
   // 1. every device renders its share (one host thread each) and resolves it into a device buffer
   std::vector<int> rcs(ndev, JADE_OK);
   std::vector<std::string> msgs(ndev);

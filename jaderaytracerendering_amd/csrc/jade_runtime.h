@@ -212,6 +212,8 @@ struct jade_scene {
   bool sh_on = false;
   int light_sampling = JADE_LIGHTS_ALL;  // jade_scene_set_light_sampling: what the next jade_render_begin takes ...
   bool lights_on = false;     // ... and what the render in progress took: JADE_LIGHTS_ONE (its records have min(n_emit, 1) + 2 slots)
+  int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling: what the next jade_render_begin takes ...
+  bool cosine_on = false;     // ... and what the render in progress took: JADE_BOUNCE_COSINE (the k_shade_cos* kernels; same records, same rays)
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;

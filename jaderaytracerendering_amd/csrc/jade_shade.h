@@ -149,6 +149,56 @@ static __device__ __forceinline__ float light_weight(const uint4* table, uint32_
   return (float)nE / jade_u2f(table[i].z);
 }
 
+// Cosine-weighted bounce sampling (jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE; NOT the reference's estimator), as include/jade_bvh.h
+// states it ("The bounce, stated"): where sphere_dir takes its two uniforms this takes the same two - u1 first, u2 second, from `next` -
+// and forms a direction with pdf cos / pi about the axis a = sign * n / |n|, in a branchless frame (Duff et al. 2017).  s: a number whose
+// sign is the side - the axis points along -n where s < 0 - and, where the normal gives no axis (*fallback: n.n is 0, infinite or NaN),
+// what the reference multiplies dot(direction, n) with in its flip: the direction is then sphere_dir's on the same two uniforms, flipped
+// if dot(direction, n) * s < 0.  The kernels pass the very product term of the reference's flip (side, dot(inner, t_norm) or its
+// negation), so a fallback vertex is the reference's statement; a test passes +-1.  The weight is consume's to form (cosine_weight).
+template <class NextUniform>
+static __device__ __forceinline__ jvec3 cosine_dir_with(NextUniform next, jvec3 n, float s, bool* fallback) {
+  const float u1 = next();
+  const float fai_value = (float)(2.0 * JADE_PI_D * (double)next());
+  float sn, cs;
+  jade_sincosf(fai_value, &sn, &cs);
+  const float nn = jv_dot(n, n);
+  if (!(nn > 0 && nn < jade_u2f(0x7f800000u))) {  // (+inf: JADE_INF_F is the reference's finite INF)
+    *fallback = true;
+    const float cosine_theta = (float)(2.0 * ((double)u1 - 0.5));  // sphere_dir, PathTrace.cu:968-971
+    const float sine_theta = jade_sqrt(1.0f - cosine_theta * cosine_theta);
+    const jvec3 d = jv(sine_theta * cs, sine_theta * sn, cosine_theta);
+    return jv_dot(d, n) * s < 0 ? jv_neg(d) : d;
+  }
+  *fallback = false;
+  jvec3 a = jv_divs(n, jade_sqrt(nn));
+  if (s < 0) a = jv_neg(a);
+  const float sg = a.z >= 0 ? 1.0f : -1.0f;
+  const float p = -1.0f / (sg + a.z);
+  const float q = a.x * a.y * p;
+  const jvec3 t = jv(1.0f + sg * a.x * a.x * p, sg * q, -sg * a.x);
+  const jvec3 b = jv(q, sg + a.y * a.y * p, -a.y);
+  const float r = jade_sqrt(u1), cz = jade_sqrt(1.0f - u1);
+  return jv_add(jv_add(jv_scale(t, r * cs), jv_scale(b, r * sn)), jv_scale(a, cz));
+}
+// ... with two successive jade_rand draws: what bounce_branch calls
+static __device__ __forceinline__ jvec3 cosine_dir_rng(uint32_t* rng, jvec3 n, float s) {
+  bool fallback;
+  return cosine_dir_with([rng]() { return jade_rand(rng); }, n, s, &fallback);
+}
+// ... and with two given numbers
+static __device__ __forceinline__ jvec3 cosine_dir_at(const float* u2, jvec3 n, float s, bool* fallback) {
+  int k = 0;
+  return cosine_dir_with([u2, &k]() { return u2[k++]; }, n, s, fallback);
+}
+// What consume multiplies with where the reference has |dot(n, rd)|: pdf cos / pi against the reference's 1 / 2 pi makes the factor
+// |dot(n, rd)| / (2 cos) = |n| / 2, formed from the normal alone - no division by the cosine, nothing travels with the record.  A normal
+// that gave no axis (cosine_dir_with's predicate, re-formed here) keeps the reference's factor.
+static __device__ __forceinline__ float cosine_weight(jvec3 n, jvec3 rd) {
+  const float nn = jv_dot(n, n);
+  return (nn > 0 && nn < jade_u2f(0x7f800000u)) ? 0.5f * jade_sqrt(nn) : jade_fabs(jv_dot(n, rd));
+}
+
 static __device__ __forceinline__ jvec3 tri_point(const jade_triangle* t, float rx, float ry) {
   jvec3 p1 = V3(t->p1);
   return jv_add(jv_add(p1, jv_scale(jv_sub(V3(t->p2), p1), rx)), jv_scale(jv_sub(V3(t->p3), p1), ry));
@@ -428,7 +478,9 @@ static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx
 // LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h; compiled apart likewise, k_shade_lights*): ONE entry of S.emit, drawn from `lights`, in
 // slot 0; nL = the shadow slots of the record's layout, so the environment ray sits in slot nL and the indirect ray in slot nL + 1.
 // *light = the entry drawn: it travels with the record (the fourth word of PathState.hdr, shade_record) to consume.
-template <bool ENVIS = false, bool LIGHTS = false>
+// COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"; compiled apart likewise, k_shade_cos*): the environment ray - unless
+// ENVIS draws it - and the indirect ray come from cosine_dir_rng in place of sphere_dir and its flip, on the same two draws.
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
 static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final,
                                                      const uint4* lights = nullptr, uint32_t* light = nullptr) {
   const jade_triangle* T = S.tris;  // vertices only
@@ -508,14 +560,15 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
           c.n_emit_rays++;
         }
       } else {
-        jvec3 ray_direction = sphere_dir(&c.rng);
-        if (jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) ray_direction = jv_neg(ray_direction);
+        jvec3 ray_direction = COSINE ? cosine_dir_rng(&c.rng, t_norm, jv_dot(inner_direction, t_norm)) : sphere_dir(&c.rng);
+        if (!COSINE && jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) ray_direction = jv_neg(ray_direction);
         px.set_dir(nL, ray_direction);
         px.set_limit(nL, JADE_INF_F);  // environment visibility: any recorded hit
         c.n_emit_rays++;
       }
-      jvec3 ray_direction = sphere_dir(&c.rng);
-      if (jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) > 0) ray_direction = jv_neg(ray_direction);
+      // (COSINE: the opposite hemisphere, as the reference has it)
+      jvec3 ray_direction = COSINE ? cosine_dir_rng(&c.rng, t_norm, -jv_dot(inner_direction, t_norm)) : sphere_dir(&c.rng);
+      if (!COSINE && jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) > 0) ray_direction = jv_neg(ray_direction);
       float rr_result = jade_rand(&c.rng);
       c.stage = ST_BSSRDF;
       c.flags = noenv;
@@ -596,16 +649,16 @@ diffuse_like:
         c.n_emit_rays++;
       }
     } else {
-      jvec3 ray_direction = sphere_dir(&c.rng);
-      if (jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
+      jvec3 ray_direction = COSINE ? cosine_dir_rng(&c.rng, n, side) : sphere_dir(&c.rng);
+      if (!COSINE && jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
       px.set_dir(nL, ray_direction);
       px.set_limit(nL, JADE_INF_F);  // environment visibility: any recorded hit
       c.n_emit_rays++;
     }
     float rr_result = jade_rand(&c.rng);
     if (rr_result < RR_F) {
-      jvec3 ray_direction = sphere_dir(&c.rng);
-      if (jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
+      jvec3 ray_direction = COSINE ? cosine_dir_rng(&c.rng, n, side) : sphere_dir(&c.rng);
+      if (!COSINE && jv_dot(ray_direction, n) * side < 0) ray_direction = jv_neg(ray_direction);
       c.flags |= STF_RR;
       px.set_dir(nL + 1, ray_direction);
       px.set_hit(nL + 1, -1);
@@ -619,12 +672,12 @@ diffuse_like:
 
 // Sample the bounce at the current vertex and emit its rays.  Returns false
 // if the path ended at this vertex (l_final holds the last l_dir).
-template <bool ENVIS = false, bool LIGHTS = false>
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
 static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr,
                                     uint32_t* light = nullptr) {
   const int type = bounce_classify(S, c, l_final);
   if (type == BT_END) return false;
-  return bounce_branch<ENVIS, LIGHTS>(type, S, px, c, l_final, lights, light);
+  return bounce_branch<ENVIS, LIGHTS, COSINE>(type, S, px, c, l_final, lights, light);
 }
 
 // Outcome of folding the pending rays' results into the path.
@@ -655,7 +708,8 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // *l_final; CONSUME_ZERO: pathTracing returned 0 (:1231); CONSUME_EMITTED: the
 // refraction loop issued its next ray.
 // LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight (bounce_branch)
-template <bool ENVIS = false, bool LIGHTS = false>
+// COSINE: where a ray came from cosine_dir_rng, the reference's |dot(normal, direction)| is cosine_weight - four places, nothing else
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
 static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u) {
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
@@ -690,7 +744,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     if (ENVIS ? px.hit(nL) == -1 : px.hit(nL) < 0) {  // (-1: traced and nothing hit; -2: no environment ray this bounce - env_sampling only)
       jvec3 rd = px.dir(nL);
       jvec3 w = jv_mul(sample_hdr(S, rd), f);
-      w = jv_scale(w, jade_fabs(jv_dot(n, rd)));
+      w = jv_scale(w, COSINE && !ENVIS ? cosine_weight(n, rd) : jade_fabs(jv_dot(n, rd)));
       w = jv_scale(jv_scale(w, 2.0f), PI_F);
       if (ENVIS) w = jv_scale(w, __int_as_float(px.auxi()));  // x (1 / 2 pi) / pdf: the reference's weight is 1 / its own pdf
       l_dir = jv_add(l_dir, w);
@@ -701,7 +755,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     int nh = px.hit(nL + 1);
     if (nh >= 0 && nonemissive(shade_tri(S, nh).m)) {
       jvec3 rd = jv_neg(px.dir(nL + 1));
-      jvec3 indir_rate = jv_divs(jv_scale(obj_hit_fr, jade_fabs(jv_dot(rd, n))), RR_F);
+      jvec3 indir_rate = jv_divs(jv_scale(obj_hit_fr, COSINE ? cosine_weight(n, rd) : jade_fabs(jv_dot(rd, n))), RR_F);
       jvec3 rate = sss ? jv_divs(jv_scale(indir_rate, (float)k), (float)JADE_SSS_RATE_D) : jv_scale(indir_rate, (float)k);
       c.src = px.hpt(nL + 1);
       c.out = rd;
@@ -743,7 +797,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       jvec3 rd = px.dir(nL);
       float fresnel_rate_o = schlick_out(R0, jade_fabs(jv_dot(rd, t_norm)));
       jvec3 w = jv_mul(jv_scale(sample_hdr(S, rd), fresnel_rate_o), bssrdf);
-      w = jv_scale(jv_scale(w, jade_fabs(jv_dot(t_norm, rd))), 2.0f);
+      w = jv_scale(jv_scale(w, COSINE && !ENVIS ? cosine_weight(t_norm, rd) : jade_fabs(jv_dot(t_norm, rd))), 2.0f);
       if (ENVIS) w = jv_scale(w, __int_as_float(px.auxi()));
       l_dir = jv_add(l_dir, w);
     }
@@ -755,7 +809,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       jvec3 rd = jv_neg(px.dir(nL + 1));
       float fresnel_rate_o = schlick_out(R0, jade_fabs(jv_dot(rd, t_norm)));
       jvec3 indir_rate = jv_scale(bssrdf, fresnel_rate_o);
-      indir_rate = jv_scale(indir_rate, jade_fabs(jv_dot(rd, t_norm)));
+      indir_rate = jv_scale(indir_rate, COSINE ? cosine_weight(t_norm, rd) : jade_fabs(jv_dot(rd, t_norm)));
       indir_rate = jv_scale(indir_rate, area_total);
       indir_rate = jv_divs(jv_scale(indir_rate, 2.0f), RR_F);
       jvec3 rate = jv_divs(jv_scale(indir_rate, (float)k), (float)(1 - JADE_SSS_RATE_D));

@@ -1,0 +1,124 @@
+"""The sample-for-sample cases of cosine-weighted bounce sampling: their scenes, the driver that holds a backend's 1-spp frames against
+tests/bounce_spec.py's arm (test_jade_spec.compare's bar, unchanged: 1e-4 relative per channel with a floor of 1e-3, at most 2 % of the
+samples disagreeing, bssrdf-coplanar samples left out) and the `need` tables.  tests/test_gpu_bounce.py compares on the device;
+tests/test_bounce_spec_cpu.py counts what the arm alone reaches, without a GPU."""
+import numpy as np
+
+import bounce_spec
+import test_jade_spec as TJ
+from conftest import B
+from jaderaytracerendering_amd import _abi, host as H
+
+MAX_LEFT_OUT = 0.05
+
+
+def bent_cube():
+    """jade_cube with the stored normal of every third triangle scaled by 2.5 (cos-nonunit: the reference's weights scale with it, the
+    mode's closed form takes sqrt(nn) / 2) and the normal of one floor triangle zeroed (cos-fallback: the reference's direction, no flip,
+    a zero weight)."""
+    hs = TJ.build("jade_cube")
+    t = hs.tri_f32()
+    t[::3, 10:13] *= np.float32(2.5)
+    floor = np.flatnonzero(hs.tri_i32()[:, 0] == hs.tri_i32()[:, 0].max())
+    assert len(floor) == 2
+    t[floor[0], 10:13] = 0
+    return hs
+
+
+def build(kind, sky=False):
+    return bent_cube() if kind == "bent_cube" else TJ.build(kind, sky)
+
+
+def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_REFERENCE, light_sampling=_abi.LIGHTS_ALL, out=None, count_only=False):
+    """test_jade_spec.compare for JADE_BOUNCE_COSINE.  count_only: no backend - what the arm alone counts per tag and leaves out."""
+    hs = build(kind, sky)
+    S = bounce_spec.Scene(hs, env_sampling, light_sampling)
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    seen, bad, kept = {}, [], {}
+    n = skipped = 0
+    worst = 0.0
+
+    def run(sc):
+        nonlocal n, skipped, worst
+        for frame in frames:
+            if sc is not None:
+                p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2, env_sampling=env_sampling)
+                rgb, _, _ = sc.render(p, want_bgr8=False)
+                kept[frame] = rgb
+            for y in range(size):
+                for x in range(size):
+                    tr = []
+                    want = bounce_spec.sample(S, x, y, size, size, eye, cam, frame, tr)
+                    if "bssrdf-coplanar" in tr:
+                        skipped += 1
+                        continue
+                    n += 1
+                    got = want if sc is None else rgb[y, x].astype(np.float64)
+                    if bool((np.abs(got - want) <= 1e-4 * np.maximum(np.abs(want), 1e-3)).all()):
+                        worst = max(worst, float((np.abs(got - want) / np.maximum(np.abs(want), 1e-3)).max()))
+                        for t in set(tr):
+                            seen[t] = seen.get(t, 0) + 1
+                    else:
+                        bad.append((frame, x, y, tr, got, want))
+
+    if count_only:
+        run(None)
+    else:
+        with backend.scene(hs) as sc:
+            sc.set_bounce_sampling(_abi.BOUNCE_COSINE)
+            if light_sampling != _abi.LIGHTS_ALL:
+                sc.set_light_sampling(light_sampling)
+            run(sc)
+    print(f"compare cosine {kind} sky={sky} env_sampling={env_sampling} light_sampling={light_sampling}: {n} compared, {len(bad)} disagree, "
+          f"{skipped} left out, worst relative error {worst:.3g}, seen {dict(sorted(seen.items()))}")
+    if out is not None:
+        out.update(frames=kept, worst=worst, seen=seen, bad=bad)
+    assert skipped <= MAX_LEFT_OUT * (n + skipped), f"{skipped} of {n + skipped} samples left out as bssrdf-coplanar"
+    assert len(bad) <= 0.02 * n, f"{len(bad)} of {n} samples disagree with the float64 spec, e.g. {bad[:3]}"
+    for tag, count in need.items():
+        assert seen.get(tag, 0) >= count, f"only {seen.get(tag, 0)} agreeing samples went through '{tag}' ({seen})"
+    return seen, len(bad), n, skipped
+
+
+# 12 x 12 frames at 1 spp.  `need`: half of what the arm alone counts for every tag on these samples (the comment above each case;
+# tests/test_bounce_spec_cpu.py holds the tables to these counts and the frames to the 5 % that may be left out).
+IMP, ONE = _abi.ENV_IMPORTANCE, _abi.LIGHTS_ONE
+CASES = {
+    # the arm alone: 413 samples, 19 left out (4.4 %): 13 bssrdf, 241 cos-env, 211 cos-indirect, 219 diffuse, 60 mirror, 152 sky, 34 sss
+    "jade_cube": dict(kind="jade_cube", size=12, frames=(0, 1, 2),
+                      need={"bssrdf": 6, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "mirror": 30, "sky": 76, "sss": 17}),
+    # 432 samples, none left out: 239 cos-env, 211 cos-indirect, 239 diffuse, 191 sky
+    "open_floor": dict(kind="open_floor", size=12, frames=(0, 1, 2), need={"cos-env": 119, "cos-indirect": 105, "diffuse": 119, "sky": 95}),
+    # under the textured sky (TJ.sky_map) the draws, so the counts, are the constant sky's
+    "jade_cube_sky": dict(kind="jade_cube", sky=True, size=12, frames=(0, 1, 2),
+                          need={"bssrdf": 6, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "mirror": 30, "sky": 76, "sss": 17}),
+    "open_floor_sky": dict(kind="open_floor", sky=True, size=12, frames=(0, 1, 2), need={"cos-env": 119, "cos-indirect": 105, "diffuse": 119, "sky": 95}),
+    # with JADE_ENV_IMPORTANCE the environment ray is that mode's (no cos-env), the indirect ray this mode's.  418 samples, 14 left out
+    # (3.2 %): 17 bssrdf, 226 cos-indirect, 221 diffuse, 170 env-importance, 99 env-noenv, 71 mirror, 152 sky, 45 sss
+    "jade_cube_sky_importance": dict(kind="jade_cube", sky=True, env_sampling=IMP, size=12, frames=(0, 1, 2),
+                                     need={"bssrdf": 8, "cos-indirect": 113, "diffuse": 110, "env-importance": 85, "env-noenv": 49, "mirror": 35,
+                                           "sky": 76, "sss": 22}),
+    # 432 samples, none left out: 213 cos-indirect, 239 diffuse, 158 env-importance, 81 env-noenv, 191 sky
+    "open_floor_sky_importance": dict(kind="open_floor", sky=True, env_sampling=IMP, size=12, frames=(0, 1, 2),
+                                      need={"cos-indirect": 106, "diffuse": 119, "env-importance": 79, "env-noenv": 40, "sky": 95}),
+    # 570 samples, 6 left out (1.0 %): 8 bssrdf, 326 cos-env, 297 cos-indirect, 308 diffuse, 54 mirror, 8 refract, 1 refract-open, 202 sky, 19 sss
+    "patchwork": dict(kind="patchwork", size=12, frames=(0, 1, 2, 3),
+                      need={"bssrdf": 4, "cos-env": 163, "cos-indirect": 148, "diffuse": 154, "mirror": 27, "refract": 4, "sky": 101, "sss": 9}),
+    # JADE_LIGHTS_ONE on top (k_shade_cos_lights): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
+    # 219 diffuse, 116 diffuse-lit, 80 light-alias, 136 light-lit, 176 light-own, 116 light-shadowed, 15 light-side, 60 mirror, 142 sky, 34 sss, 15 sss-lit
+    "two_lamps_sky": dict(kind="two_lamps", sky=True, light_sampling=ONE, size=12, frames=(0, 1, 2),
+                          need={"bssrdf": 6, "bssrdf-lit": 3, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "diffuse-lit": 58, "light-alias": 40,
+                                "light-lit": 68, "light-own": 88, "light-shadowed": 58, "light-side": 7, "mirror": 30, "sky": 71, "sss": 17, "sss-lit": 7}),
+    # ... and both (k_shade_cos_lights_envis): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse,
+    # 118 diffuse-lit, 170 env-importance, 99 env-noenv, 87 light-alias, 138 light-lit, 180 light-own, 120 light-shadowed, 21 light-side,
+    # 71 mirror, 142 sky, 45 sss, 18 sss-lit
+    "two_lamps_sky_importance": dict(kind="two_lamps", sky=True, env_sampling=IMP, light_sampling=ONE, size=12, frames=(0, 1, 2),
+                                     need={"bssrdf": 8, "bssrdf-lit": 5, "cos-indirect": 113, "diffuse": 110, "diffuse-lit": 59, "env-importance": 85,
+                                           "env-noenv": 49, "light-alias": 43, "light-lit": 69, "light-own": 90, "light-shadowed": 60, "light-side": 10,
+                                           "mirror": 35, "sky": 71, "sss": 22, "sss-lit": 9}),
+    # normals scaled and zeroed (bent_cube): 417 samples, 15 left out (3.5 %): 14 bssrdf, 179 cos-env, 65 cos-fallback, 154 cos-indirect,
+    # 15 cos-nonunit, 218 diffuse, 60 mirror, 152 sky, 33 sss
+    "bent_cube": dict(kind="bent_cube", size=12, frames=(0, 1, 2),
+                      need={"bssrdf": 7, "cos-env": 89, "cos-fallback": 32, "cos-indirect": 77, "cos-nonunit": 7, "diffuse": 109, "mirror": 30,
+                            "sky": 76, "sss": 16}),
+}

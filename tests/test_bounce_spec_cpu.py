@@ -1,0 +1,391 @@
+"""tests/bounce_spec.py - the float64 statement of cosine-weighted bounce sampling (include/jade_bvh.h, "The bounce, stated") - checked
+without a GPU: the geometry of a draw, the pdf its weight assumes (from the Jacobian, not from the weight), the fallback, and that at a
+diffuse, an SSS-diffuse and a BSSRDF vertex the expectation of the mode's environment and indirect terms is the reference's.  Every check
+is a function of the draw it checks and is also run on a damaged draw, which must fail it."""
+import math
+
+import numpy as np
+import pytest
+
+import bounce_spec as spec
+import jade_spec
+from jade_spec import PI
+from jaderaytracerendering_amd import host as H
+from test_jade_spec import build
+
+F32 = np.float32
+
+
+def good_rows():
+    """The rows of spec.rows() whose normal gives an axis, as (n, s, u1, u2)."""
+    r = spec.rows()
+    r = r[~spec.falls_back(r[:, :3])]
+    return r[:, :3], r[:, 3], r[:, 4], r[:, 5]
+
+
+def unit_axis(n, s):
+    n = np.asarray(n, np.float64)
+    return np.where(np.asarray(s)[:, None] < 0, -1.0, 1.0) * n / np.sqrt((n * n).sum(-1))[:, None]
+
+
+# ---- damaged draws: each is the statement with one thing wrong -------------------------------------------------------------------
+
+def draw_swapped(n, s, u1, u2):
+    """cz from sqrt(u1): still a cosine-distributed direction, but not the one the statement names for (u1, u2)."""
+    u1 = np.asarray(u1, F32)
+    return spec.draw(n, s, (1 - u1.astype(np.float64)).astype(F32), u2)
+
+
+def draw_long(n, s, u1, u2):
+    d, fb, cz = spec.draw(n, s, u1, u2)
+    return d * 1.001, fb, cz
+
+
+def draw_uniform(n, s, u1, u2):
+    """A uniform hemisphere about the axis (dot(d, a) = u1) under the cosine weight."""
+    n = np.asarray(n, F32).reshape(-1, 3)
+    a = spec.axis(n, np.broadcast_to(np.asarray(s, F32).reshape(-1), (len(n),)))
+    t, b = spec.frame(a)
+    u1 = np.broadcast_to(np.asarray(u1, np.float64).reshape(-1), (len(n),))
+    phi = 2 * PI * np.broadcast_to(np.asarray(u2, np.float64).reshape(-1), (len(n),))
+    r = np.sqrt(1 - u1 * u1)
+    return t * (r * np.cos(phi))[:, None] + b * (r * np.sin(phi))[:, None] + a * u1[:, None], spec.falls_back(n), u1
+
+
+def draw_no_flip(n, s, u1, u2):
+    d, fb, cz = spec.draw(n, s, u1, u2)
+    n = np.asarray(n, F32).reshape(-1, 3).astype(np.float64)
+    with np.errstate(invalid="ignore"):
+        flipped = fb & ((d * n).sum(-1) * np.asarray(s, np.float64) > 0) & ((d * n).sum(-1) * np.asarray(s, np.float64) != 0)
+    back = np.zeros(len(d), bool)
+    back[np.flatnonzero(flipped)[::2]] = True      # undo every second flip
+    return np.where(back[:, None], -d, d), fb, cz
+
+
+def frame_one_sign(a):
+    """The frame without sg (Frisvad's): singular at a.z = -1."""
+    ax, ay, az = a[:, 0], a[:, 1], a[:, 2]
+    with np.errstate(all="ignore"):
+        p = -1.0 / (1.0 + az)
+        q = ax * ay * p
+        return np.stack([1 + ax * ax * p, q, -ax], -1), np.stack([q, 1 + ay * ay * p, -ay], -1)
+
+
+# ---- the checks ----------------------------------------------------------------------------------------------------------------------
+
+def check_unit_length(draw):
+    n, s, u1, u2 = good_rows()
+    d, fb, _ = draw(n, s, u1, u2)
+    assert not fb.any()
+    assert np.abs(np.sqrt((d * d).sum(-1)) - 1).max() < 1e-12
+
+
+def check_cosine_to_the_axis(draw):
+    n, s, u1, u2 = good_rows()
+    d, _, _ = draw(n, s, u1, u2)
+    cz = np.sqrt(1 - u1.astype(np.float64))
+    got = (d * unit_axis(n, s)).sum(-1)
+    assert (cz >= 0).all() and np.abs(got - cz).max() < 1e-12, np.abs(got - cz).max()
+
+
+def check_frame(frame):
+    n, s, _, _ = good_rows()
+    a = spec.axis(n, s)
+    t, b = frame(a)
+    for v, w, want in ((t, t, 1), (b, b, 1), (t, b, 0), (t, a, 0), (b, a, 0)):
+        assert np.abs((v * w).sum(-1) - want).max() < 1e-12
+    assert np.abs(np.cross(t, b) - a).max() < 1e-12, "right-handed: t x b = a"
+
+
+def check_closed_form_weight(draw):
+    """|dot(n, d)| / (2 cz) = sqrt(nn) / 2 wherever cz > 1e-3 (relative 1e-9: float64 on a quotient of order 1 / 1e-3)."""
+    n, s, u1, u2 = good_rows()
+    d, _, _ = draw(n, s, u1, u2)
+    cz = np.sqrt(1 - u1.astype(np.float64))
+    m = cz > 1e-3
+    n64 = n.astype(np.float64)
+    nn = (n64 * n64).sum(-1)
+    got = np.abs((n64 * d).sum(-1))[m] / (2 * cz[m])
+    assert m.sum() > 1000 and np.abs(got / (np.sqrt(nn[m]) / 2) - 1).max() < 1e-9
+
+
+def check_pdf_by_the_jacobian(draw):
+    """pdf(d) = 1 / |dd/du1 x dd/du2| by central differences with h = 2^-10 at uniforms that are multiples of 2^-8 in [1/8, 7/8] (u +- h
+    are fp32 numbers), against cz / pi.  Tolerance 5e-4 relative: the truncation is h^2 / 6 * |d'''| / |d'|, at most 0.75 / u1^2 * 1.6e-7 =
+    8e-6 for sqrt(u1) at u1 = 1/8 and the same for sqrt(1 - u1) at 7/8; phi is rounded to fp32 (2^-24 * 2 pi at most) over a step of
+    2 pi h: 6e-5 of the derivative; 3.1415926 for pi: 2e-8."""
+    h = 2.0 ** -10
+    g = np.arange(32, 225, 16) / 256.0
+    u1, u2 = [x.reshape(-1) for x in np.meshgrid(g, g)]
+    ok, _ = spec.normal_sets()
+    worst = 0.0
+    for n in ok[::7]:
+        for s in (1.0, -1.0):
+            nn = np.repeat(n[None], len(u1), 0)
+            f = lambda a, b: draw(nn, np.full(len(u1), s, F32), a.astype(F32), b.astype(F32))[0]
+            d1 = (f(u1 + h, u2) - f(u1 - h, u2)) / (2 * h)
+            d2 = (f(u1, u2 + h) - f(u1, u2 - h)) / (2 * h)
+            c = np.cross(d1, d2)
+            pdf = 1 / np.sqrt((c * c).sum(-1))
+            worst = max(worst, float(np.abs(pdf / (np.sqrt(1 - u1) / math.pi) - 1).max()))
+    assert worst < 5e-4, worst
+
+
+def check_mean_cosine(draw):
+    """u1 uniform: E[dot(d, a)] = E[sqrt(1 - u)] = 2/3, variance 1/2 - 4/9 = 1/18; within 4 standard errors of 4 096 draws."""
+    rng = np.random.default_rng(23)
+    k = 4096
+    u = rng.random((k, 2)).astype(F32)
+    n = np.repeat(F32([[0.36, -0.48, 0.8]]), k, 0)
+    s = np.ones(k, F32)
+    d, _, _ = draw(n, s, u[:, 0], u[:, 1])
+    mean = float((d * unit_axis(n, s)).sum(-1).mean())
+    assert abs(mean - 2 / 3) < 4 * math.sqrt(1 / 18 / k), mean
+
+
+def check_fallback(draw):
+    """A normal that gives no axis: jade_spec.sphere_dir's direction on the two uniforms, negated where dot(d, n) * s < 0 (1e-6: phi is
+    rounded to fp32 in the statement and not in jade_spec)."""
+    r = spec.rows()
+    r = r[spec.falls_back(r[:, :3])]
+    assert len(r) > 1000
+    d, fb, cz = draw(r[:, :3], r[:, 3], r[:, 4], r[:, 5])
+    assert fb.all() and np.isnan(cz).all()
+    flips = 0
+    for row, got in zip(r[::3], d[::3]):
+        want = jade_spec.sphere_dir(iter([float(row[4]), float(row[5])]))
+        with np.errstate(invalid="ignore", over="ignore"):
+            side = (want @ row[:3].astype(np.float64)) * float(row[3])
+        if abs(side) < 1e-5 or (np.abs(want[np.isinf(row[:3])]) < 1e-5).any():
+            continue                  # (the side of a direction in the plane is rounding's: so is the sign of 1e-12 * inf)
+        if side < 0:                  # (a NaN product flips nothing)
+            want = -want
+            flips += 1
+        assert np.abs(got - want).max() < 1e-6, (row, got, want)
+    assert flips > 50
+
+
+@pytest.mark.parametrize("check,damaged", [
+    (check_unit_length, draw_long), (check_cosine_to_the_axis, draw_swapped), (check_closed_form_weight, draw_swapped),
+    (check_pdf_by_the_jacobian, draw_swapped), (check_mean_cosine, draw_uniform), (check_fallback, draw_no_flip)],
+    ids=lambda f: f.__name__)
+def test_the_draw(check, damaged):
+    check(spec.draw)
+    with pytest.raises(AssertionError):
+        check(damaged)
+
+
+def test_the_frame_is_orthonormal():
+    check_frame(spec.frame)
+    with pytest.raises(AssertionError):
+        check_frame(frame_one_sign)
+
+
+def test_predicate_and_tags_on_the_row_set():
+    ok, none = spec.normal_sets()
+    assert not spec.falls_back(ok).any() and spec.falls_back(none).all()
+    assert len(spec.rows()) == (len(ok) + len(none)) * 2 * 7 * 6 + 4096
+    nn = spec.nn_f32(ok)
+    assert (np.abs(nn - 1) > 1e-3).sum() >= 4 * 64 and (np.abs(nn - 1) <= 1e-3).sum() >= 64
+
+
+# ---- unbiasedness at a vertex ------------------------------------------------------------------------------------------------------
+
+def nearest(S, o, D, skip):
+    """jade_spec.Scene.hit over rows D [k, 3]: the index of the nearest triangle hit, -1 for none (the same statements, vectorised)."""
+    dn = D / np.sqrt((D * D).sum(-1))[:, None]
+    best = np.full(len(D), np.inf)
+    bi = np.full(len(D), -1)
+    for k in range(S.n):
+        if k == skip:
+            continue
+        a, b, c = S.p1[k], S.p2[k], S.p3[k]
+        proj = lambda p: p - dn * (dn @ (p - o))[:, None]
+        a2, b2, c2 = proj(a), proj(b), proj(c)
+        pa, pb, pc = a2 - o, b2 - o, c2 - o
+        s1 = (dn * np.cross(pa, pb)).sum(-1)
+        s2 = (dn * np.cross(pb, pc)).sum(-1)
+        s3 = (dn * np.cross(pc, pa)).sum(-1)
+        inside = ((s1 > 0) & (s2 > 0) & (s3 > 0)) | ((s1 < 0) & (s2 < 0) & (s3 < 0))
+        e1, e2, q = b2 - a2, c2 - a2, o - a2
+        div = e1[:, 0] * e2[:, 1] - e1[:, 1] * e2[:, 0]
+        with np.errstate(all="ignore"):
+            al = (e2[:, 1] * q[:, 0] - e2[:, 0] * q[:, 1]) / div
+            be = (-e1[:, 1] * q[:, 0] + e1[:, 0] * q[:, 1]) / div
+            P = a + np.outer(al, b - a) + np.outer(be, c - a)
+            dist = ((P - o) * dn).sum(-1)
+        take = inside & (div != 0) & (dist > 0) & (dist < best)
+        best = np.where(take, dist, best)
+        bi = np.where(take, k, bi)
+    return bi
+
+
+def frozen_sky(W):
+    """A smooth, positive stand-in for the environment: the same function of the direction for both arms."""
+    return np.stack([1.0 + 0.5 * W[:, 0], 0.8 + 0.3 * W[:, 1] * W[:, 1], 0.6 + 0.4 * W[:, 2]], -1)
+
+
+def turn_about(n, angle):
+    """The rotation by `angle` about n (Rodrigues)."""
+    a = n / math.sqrt(n @ n)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + math.sin(angle) * K + (1 - math.cos(angle)) * (K @ K)
+
+
+def vertex_terms(S, draw, cosine, o, skip, n32, side_env, side_ind, grid, fo=None):
+    """The expectation, over a grid x grid midpoint rule in (u1, u2), of the environment term sky(w) [Fo(w)] g(w) V(w) and of the
+    indirect rate [Fo(w)] g(w) [the ray meets a non-emissive triangle] of one vertex - g = |dot(n, w)| with the reference's
+    direction (cosine = False) or sqrt(nn) / 2 with the mode's (True).  Visibility and the sky are frozen functions of the direction;
+    the constant factors common to both arms (f, 2 pi, Rd, 1 / RR, k) are left out.
+    The frozen visibility is the scene's, seen from the vertex, turned by 0.37 rad about the vertex normal (the hemisphere is kept; the
+    expectations of the two arms are equal under ANY fixed visibility).  Unturned, the quadrature itself is not sound on these scenes:
+    the reference arm's grid lines of constant u2 are meridians about the world's z axis, the light's and the floor's edges parallel to
+    z lie ON meridians from any vertex, and a jump along a grid line makes the midpoint rule err by O(1 / grid) with a sign that depends
+    on the grid's phase - the SSS vertex then reads 0.36829 / 0.36846 / 0.36841 / 0.36708 at 64 / 128 / 256 / 512 (Monte Carlo:
+    0.36728 +- 0.00014) while the cosine arm holds 0.36777 .. 0.36780: halving the grid does not show that error."""
+    u = (np.arange(grid) + 0.5) / grid
+    u1, u2 = [x.reshape(-1).astype(F32) for x in np.meshgrid(u, u)]
+    n = n32.astype(np.float64)
+    turn = turn_about(n, 0.37)
+    out = []
+    for side, want_hit in ((side_env, False), (side_ind, True)):
+        if cosine:
+            W, fb, _ = draw(np.repeat(n32[None], len(u1), 0), np.full(len(u1), -1.0 if side < 0 else 1.0, F32), u1, u2)
+            assert not fb.any()
+            g = np.full(len(u1), math.sqrt(n @ n) / 2)
+        else:
+            W = spec.sphere_dir_at(u1, u2)
+            W = np.where((((W @ n) * side) < 0)[:, None], -W, W)
+            g = np.abs(W @ n)
+        h = nearest(S, o, W @ turn.T, skip)
+        if fo is not None:
+            g = g * fo(W)
+        if want_hit:
+            ok = (h >= 0) & np.array([k < 0 or bool((S.emis[k] < 1.5e-4).all()) for k in h])
+            out.append(np.array([(g * ok).mean()]))
+        else:
+            out.append((frozen_sky(W) * (g * (h < 0))[:, None]).mean(0))
+    return np.concatenate(out)
+
+
+def vertices(kind):
+    """A diffuse, an SSS-diffuse and a BSSRDF vertex of the scene: (name, origin, skipped triangle, normal, side of the environment
+    ray, side of the indirect ray, Fo or None)."""
+    hs = build(kind)
+    S = spec.Scene(hs)
+    eye, _ = H.camera_orbit(2.8, 20.0, 10.0)
+    eye = np.asarray(eye, np.float64)
+    out = []
+    floor = [k for k in range(S.n) if S.reflex[k] == 0 and S.refract[k] == 0 and not (S.emis[k] > 0).any()]
+    k = floor[0]
+    src = S.point(k, 0.37, 0.21)
+    side = (eye - src) @ S.norm[k]
+    out.append(("diffuse", src, k, S.norm32[k], side, side, None))
+    jade = [k for k in range(S.n) if S.refract[k] == 1]
+    if jade:
+        k = max(jade, key=lambda j: S.norm[j][1])                      # the face turned most upwards
+        src = S.point(k, 0.3, 0.3)
+        side = (eye - src) @ S.norm[k]
+        out.append(("sss", src, k, S.norm32[k], side, side, None))
+        m = next(j for j in jade if abs(S.norm[j] @ S.norm[k]) < 0.5)   # leaves through a face of another plane
+        Q = S.point(m, 0.25, 0.4)
+        inn = (Q - src) @ S.norm[m]
+        assert abs(inn) > 1e-3
+        R0 = ((S.eta[m] - 1) / (S.eta[m] + 1)) ** 2
+        fo = lambda W, nm=S.norm[m]: R0 - (1 - R0) * (1 - np.abs(W @ nm)) ** 5
+        out.append(("bssrdf", Q, m, S.norm32[m], inn, -inn, fo))
+    return S, out
+
+
+def check_unbiased(draw, kind):
+    """At every vertex: the two arms' expectations on the 256 x 256 grid differ by less than the grid's own convergence - what each
+    arm's value changes by when the grid is halved, summed over both arms - in the L1 norm over the four numbers (the environment
+    term's three channels and the indirect rate)."""
+    S, vs = vertices(kind)
+    assert [v[0] for v in vs] == (["diffuse", "sss", "bssrdf"] if kind == "jade_cube" else ["diffuse"])
+    for name, o, skip, n32, se, si, fo in vs:
+        e = {(c, g): vertex_terms(S, draw, c, o, skip, n32, se, si, g, fo) for c in (False, True) for g in (128, 256)}
+        change = np.abs(e[False, 256] - e[False, 128]).sum() + np.abs(e[True, 256] - e[True, 128]).sum()
+        differ = np.abs(e[True, 256] - e[False, 256]).sum()
+        print(f"{kind} {name}: uniform {e[False, 256]}, cosine {e[True, 256]}, differ {differ:.3g}, change on halving {change:.3g}")
+        assert e[False, 256][:3].min() > 0.02 and (kind == "open_floor" or name == "sss" or e[False, 256][3] > 0.02), "the terms are exercised"
+        assert differ < change, (kind, name, differ, change)
+
+
+@pytest.mark.parametrize("kind", ["jade_cube", "open_floor"])
+def test_the_expectation_is_the_uniform_arms(kind):
+    check_unbiased(spec.draw, kind)
+    with pytest.raises(AssertionError):
+        check_unbiased(draw_uniform, kind)
+
+
+# ---- the per-sample arm --------------------------------------------------------------------------------------------------------------
+
+def test_the_arm_draws_as_many_uniforms_as_the_reference_arm():
+    """Same rays, same number of draws, same places in the stream: on every sample both arms consume the same count of uniforms up to
+    the first vertex at which their paths part (they part only through what a direction hits), and a sample whose first vertex ends
+    the path consumes the same count in all."""
+    hs = build("open_floor")
+    S = spec.Scene(hs)
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+
+    class Counting:
+        def __init__(self, it):
+            self.it, self.n = it, 0
+
+        def __iter__(self):
+            return self
+
+        def __next__(self):
+            self.n += 1
+            return next(self.it)
+
+    real = jade_spec.wang_stream
+    counts = {}
+    try:
+        for arm in (jade_spec, spec):
+            made = []
+
+            def stream(x, y, frame):
+                made.append(Counting(real(x, y, frame)))
+                return made[-1]
+
+            jade_spec.wang_stream = stream
+            for x in range(12):
+                tr = []
+                arm.sample(S, x, 3, 12, 12, eye, cam, 0, tr)
+                counts.setdefault((x, tuple(t for t in tr if not t.startswith("cos-"))), []).append(made[-1].n)
+    finally:
+        jade_spec.wang_stream = real
+    same = [v for v in counts.values() if len(v) == 2]
+    assert len(same) >= 6 and all(a == b for a, b in same), counts
+
+
+def test_tags():
+    hs = build("jade_cube")
+    S = spec.Scene(hs)
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    tr = []
+    for y in range(0, 12, 2):
+        for x in range(12):
+            assert np.isfinite(spec.sample(S, x, y, 12, 12, eye, cam, 0, tr)).all()
+    assert "cos-env" in tr and "cos-indirect" in tr and "cos-fallback" not in tr and "cos-nonunit" not in tr
+
+
+# ---- the cases the device is compared on -----------------------------------------------------------------------------------------
+
+import bounce_cases as BC  # noqa: E402
+
+
+@pytest.mark.parametrize("case", sorted(BC.CASES))
+def test_the_scenes_reach_what_the_device_tests_demand(case):
+    """The arm alone on a case's samples: at most 5 % are left out as bssrdf-coplanar (compare asserts it), `need` demands half of what
+    the arm counts for every tag it meets at least twice, and the cos-* tags the case is there for are among them."""
+    c = BC.CASES[case]
+    out = {}
+    BC.compare(None, count_only=True, out=out, **c)
+    seen = out["seen"]
+    assert {k: v // 2 for k, v in seen.items() if v >= 2} == c["need"], {k: v // 2 for k, v in sorted(seen.items())}
+    assert "cos-indirect" in c["need"] and ("cos-env" in c["need"]) == (c.get("env_sampling", 0) == 0)
+    if case == "bent_cube":
+        assert "cos-fallback" in c["need"] and "cos-nonunit" in c["need"]
