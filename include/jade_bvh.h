@@ -554,6 +554,78 @@ int jade_scene_get_light_sampling(jade_scene* scene, int* mode);
 int jade_scene_set_bounce_sampling(jade_scene* scene, int mode);
 int jade_scene_get_bounce_sampling(jade_scene* scene, int* mode);
 
+/* ---- Multiple importance sampling of the emitters ----
+ *
+ * Non-parity, on top of JADE_BOUNCE_COSINE: the emitter term of a diffuse or SSS-diffuse vertex, Le f |n.l| |ne.l| / (l.l)^2 A, has no
+ * bound as the vertex approaches the emitter, and an indirect ray that lands on an emitter is thrown away (the path ends with nothing
+ * when the hit is not `nonemissive`).  Under JADE_DIRECT_MIS the emitter rays and the indirect ray are two techniques for the SAME
+ * integral over the emitters listed in emit_indices, combined with the balance heuristic: every emitter term is multiplied by a weight
+ * in [0, 1], and an indirect ray that lands on a listed emitter adds that emitter's light with the complementary weight.  Every weighted
+ * emitter term is then at most pi f Le |n| |ne| mu (below).  It costs no ray, no draw and no word of a path record: rays, draws, their
+ * places in the sample's stream, the record layout, path lengths and EVERY jade_stats counter are JADE_BOUNCE_COSINE's; only radiance
+ * changes.  None of jade_rt.h's parity statements apply.  The mode is a property of the scene handle, read by the next
+ * jade_render_begin, and a render in progress keeps the mode it began with.  JADE_DIRECT_RAYS (0, the default) is today's render in every
+ * kernel, bit and counter.  It composes with what JADE_BOUNCE_COSINE composes with: both env_sampling values, both light samplings, the
+ * three walks, tile partitions, progressive steps, adaptive sampling, the guides and the denoiser, exposure and glare.
+ *
+ * ---- The direct light, stated ----
+ * tests/mis_spec.py is this text in float64.  fl() rounds to fp32; every operation below is one fp32 operation unless it says double;
+ * dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)).  It applies at diffuse and SSS-diffuse vertices only.  A BSSRDF vertex is
+ * JADE_BOUNCE_COSINE's, unchanged: its emitter rays have no side test and its indirect ray takes the opposite hemisphere, so the two
+ * techniques do not sample one domain there.
+ *
+ * The table (made once, at jade_scene_create, on the host): two numbers (m, M) per triangle h.  h is WEIGHTED iff it fails the
+ * reference's indirect-hit test `nonemissive` (not all three channels of its emission < 1.5e-4f - so a NaN channel counts), its area
+ * A = tri_size(h) (0.5f * sqrt(dot(c, c)), c = cross(p2 - p1, p3 - p1), PathTrace.cu:897-903) is finite and > 0, and nne = dot(ne, ne) of
+ * its stored normal ne is finite and > 0.  For a weighted h, m(h) = fl(the number of entries of emit_indices that name h) and
+ * M(h) = fl((sum over those entries i, in list order, of double(q_own_i)) / double(nE)), the probability with which JADE_LIGHTS_ONE's
+ * table realises them (q_own_i: "The lights, stated"; 0 where n_emit exceeds JADE_LIGHTS_ONE_MAX_ENTRIES and that table is not made).
+ * For every other triangle - an emitter that is not listed, a listed triangle that does not emit or emits below the threshold, a
+ * degenerate one - both are 0.  mu(h) = m(h) under JADE_LIGHTS_ALL and M(h) under JADE_LIGHTS_ONE.
+ *
+ * The densities, from a vector l from the vertex to a point of h and the vertex's stored normal n (nn = dot(n, n)), both per solid angle:
+ *     ll = dot(l, l);  rl = sqrt(ll)
+ *     pA = ((ll * rl) * sqrt(nne)) / (A * |dot(ne, l)|)          (a uniform point of h)
+ *     PL = mu(h) * pA
+ *     pB = |dot(n, l)| / ((rl * sqrt(nn)) * fl(pi))               (the cosine bounce; pi = the reference's 3.1415926)
+ *     w_L = 1 / (1 + pB / PL)                                      (= PL / (PL + pB))
+ *     g_B = ((m(h) * (|dot(n, l)| / rl)) * sqrt(nne)) / (PL + pB)
+ * One function forms them on both sides: on the emitter side l = the shadow ray's direction as recorded (point - vertex, not
+ * normalised), on the bounce side l = fl(hit point - vertex), the indirect ray's recorded hit point.
+ * Edges.  If m(h) is not > 0 (h is not weighted), or the vertex falls back under JADE_BOUNCE_COSINE (!(nn > 0 && nn < inf)):
+ * w_L = 1 and g_B = 0 - no weight, no bounce term.  dot(ne, l) = 0 or an overflowing numerator gives pA = PL = inf: w_L = 1 / (1 + 0) = 1
+ * (the term it multiplies is 0 in the first case) and g_B = 0.  PL = 0 by underflow with pB > 0: pB / PL = inf, w_L = 0, and the bounce
+ * term carries everything.  pB = 0 with PL > 0: w_L = 1.  NaN arises only from l.l = 0 (where today's term is NaN as well), from
+ * numerator and denominator of pA overflowing together, or from PL and pB both 0; there is no inf / inf for l.l > 0 otherwise.
+ *
+ * The emitter term.  An emitter term whose entry names a weighted triangle is JADE_BOUNCE_COSINE's term times w_L, one multiplication
+ * per channel - under JADE_LIGHTS_ONE after the multiplication by that mode's weight.  An entry whose triangle is not weighted keeps its
+ * term.
+ * The bounce term.  When the vertex survived the roulette, its indirect ray's nearest hit is h and h is weighted,
+ *     T_B = ((Le(h) * f) * g_B) / fl(0.9)            per channel
+ * is added to l_dir BEFORE the vertex's scale (k, or k / 0.5 at an SSS-diffuse vertex); f is the factor of the vertex's direct light
+ * (brdf fl(1 / pi) at a diffuse vertex, refract_albedo fl(1 / pi) at an SSS-diffuse one - not the indirect rate's brdf).  The path ends
+ * there as it does in the reference.  With omega = l / |l|, T_B = m Le f |n.omega| sqrt(nne) / (PL + pB) / RR.
+ * Why the integral is unchanged.  Per listed entry the reference's expectation is the integral of Le f |n.omega| sqrt(nne) V over the
+ * hemisphere on the vertex's side (the area measure dA = d omega ll rl sqrt(nne) / |ne.l| turns its term into that).  At every
+ * (omega, h) the m emitter samples carry w_L = PL / (PL + pB) each, and the bounce sample - drawn with density pB, kept with
+ * probability RR - carries m pB / (PL + pB): together m, the reference's count.  Both techniques see the same visibility (nearest hit
+ * from the vertex, its own triangle excluded) and the same side.  Unweighted triangles contribute exactly as before.
+ * The bound: term x w_L <= term x PL / pB = pi f Le sqrt(nn) sqrt(nne) mu per entry (under JADE_LIGHTS_ONE x 1 / p_i), and
+ * T_B <= m Le f |n.omega| sqrt(nne) / pB / RR = pi f Le sqrt(nn) sqrt(nne) m / RR.
+ *
+ * The schedule is JADE_BOUNCE_COSINE's.  Results do not depend on steps, tile partitions or records per pixel.
+ *
+ * jade_scene_set_direct_sampling: an unknown mode returns JADE_ERR_INVALID and leaves the previous mode in place.
+ * jade_render_begin refuses JADE_DIRECT_MIS without JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling) with JADE_ERR_UNSUPPORTED; a
+ * lens or a shutter is refused by JADE_BOUNCE_COSINE's own check.
+ * jade_render_multi: all scenes must carry the same mode, else JADE_ERR_INVALID before anything is launched. */
+#define JADE_DIRECT_RAYS 0
+#define JADE_DIRECT_MIS 1
+
+int jade_scene_set_direct_sampling(jade_scene* scene, int mode);
+int jade_scene_get_direct_sampling(jade_scene* scene, int* mode);
+
 #ifdef __cplusplus
 }
 #endif

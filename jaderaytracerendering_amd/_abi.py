@@ -18,6 +18,7 @@ WALK_REFERENCE, WALK_EARLY_EXIT, WALK_EARLY_EXIT_CACHED = 0, 1, 2
 ENV_REFERENCE, ENV_IMPORTANCE = 0, 1
 LIGHTS_ALL, LIGHTS_ONE = 0, 1  # include/jade_bvh.h, jade_scene_set_light_sampling
 BOUNCE_UNIFORM, BOUNCE_COSINE = 0, 1  # include/jade_bvh.h, jade_scene_set_bounce_sampling
+DIRECT_RAYS, DIRECT_MIS = 0, 1  # include/jade_bvh.h, jade_scene_set_direct_sampling
 EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1
 METER_BINS = 512
 
@@ -211,6 +212,9 @@ BVH_SYMBOLS = {
     # the bounce sampling of a scene handle (scene, mode) / (scene, out)
     "jade_scene_set_bounce_sampling": (C.c_int, [C.c_void_p, C.c_int]),
     "jade_scene_get_bounce_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # the direct sampling of a scene handle (scene, mode) / (scene, out)
+    "jade_scene_set_direct_sampling": (C.c_int, [C.c_void_p, C.c_int]),
+    "jade_scene_get_direct_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {

@@ -446,6 +446,22 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(mode)))
         return mode.value
 
+    def set_direct_sampling(self, mode):
+        """jade_scene_set_direct_sampling: _abi.DIRECT_RAYS (the default: the emitter rays alone gather the listed emitters' light) or
+        _abi.DIRECT_MIS (the emitter rays and the indirect ray weighed against each other with the balance heuristic; needs
+        _abi.BOUNCE_COSINE at the next render; HIP module only; non-parity: include/jade_bvh.h, "The direct light, stated").  Taken by the
+        next render this handle begins.  JadeError(JADE_ERR_INVALID) leaves the previous mode in place."""
+        fn = self._hip_only("jade_scene_set_direct_sampling")
+        self.backend.check(fn(self._h, int(mode)))
+
+    @property
+    def direct_sampling(self):
+        """jade_scene_get_direct_sampling: the mode the next render of this handle takes."""
+        fn = self._hip_only("jade_scene_get_direct_sampling")
+        mode = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(mode)))
+        return mode.value
+
     def focus_distance(self, params, px, py):
         """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
         (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that

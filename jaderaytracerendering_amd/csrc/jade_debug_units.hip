@@ -1,6 +1,6 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table; the cosine bounce draw, cosine_dir_with), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
+// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table; the cosine bounce draw, cosine_dir_with; the weights of JADE_DIRECT_MIS, mis_terms, and its table, mis_table), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
 // jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py) and the BSSRDF branch's exit-triangle search (exit_search, jade_shade.h, and
 // its tables, guide_tables, jade_scene_prep.hip; tests/test_area_search_cpu.py, tests/test_gpu_area_search.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
@@ -184,6 +184,18 @@ __global__ void k_debug_bounce_dir_rng(int n, const float* rows, uint32_t* rng, 
   uint32_t state = rng[i];
   put3(dir, i, cosine_dir_rng(&state, jv(r[0], r[1], r[2]), r[3]));
   rng[i] = state;
+}
+
+// mis_terms (jade_shade.h; include/jade_bvh.h "The direct light, stated") on row i = (n[3], ne[3], A, m, mu, l[3], Le, f), 14 floats:
+// out[2 i] = w_L, out[2 i + 1] = T_B of one channel = ((Le * f) * g_B) / fl(0.9), as consume forms it
+__global__ void k_debug_mis_terms(int n, const float* rows, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + 14 * (size_t)i;
+  float w_L, g_B;
+  mis_terms(jv(r[0], r[1], r[2]), jv(r[3], r[4], r[5]), r[6], r[7], r[8], jv(r[9], r[10], r[11]), &w_L, &g_B);
+  out[2 * (size_t)i] = w_L;
+  out[2 * (size_t)i + 1] = r[12] * r[13] * g_B / (float)JADE_RR_RATE_D;
 }
 
 __global__ void k_debug_tone_pack(int n, const float* rgb, int tonemap, float limit, uint8_t* out) {
@@ -431,6 +443,38 @@ int jade_debug_light_sample(jade_scene* s, int32_t n, const float* u, uint32_t* 
   HIP_TRY(hipMemcpyAsync(out_rxy, bx.p, N * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(out_weight, bw.p, N * 8, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// mis_table (jade_scene_prep.hip) on n_triangles caller's records and the n_emit entries emit_indices, with light_alias_table's table
+// where that is made: out_m_M[2 h] = m(h), out_m_M[2 h + 1] = M(h).  No HIP call.
+int jade_debug_mis_table_host(const jade_triangle* triangles, int32_t n_triangles, const int32_t* emit_indices, int32_t n_emit, float* out_m_M) {
+  if (!triangles || n_triangles <= 0 || n_emit < 0 || (n_emit > 0 && !emit_indices) || !out_m_M) return jade_fail(JADE_ERR_INVALID, "bad argument");
+  for (int32_t i = 0; i < n_emit; ++i)
+    if (emit_indices[i] < 0 || emit_indices[i] >= n_triangles) return jade_fail(JADE_ERR_INVALID, "emitter index out of range");
+  std::vector<uint4> alias;
+  if (light_sampling_fits(n_emit)) light_alias_table(triangles, emit_indices, n_emit, alias);
+  std::vector<float2> table;
+  mis_table(triangles, n_triangles, emit_indices, n_emit, alias, table);
+  for (size_t h = 0; h < table.size(); ++h) {
+    out_m_M[2 * h] = table[h].x;
+    out_m_M[2 * h + 1] = table[h].y;
+  }
+  return JADE_OK;
+}
+
+// out[i] = (w_L, T_B of one channel) of mis_terms (jade_shade.h) on rows[i] = (n[3], ne[3], A, m, mu, l[3], Le, f), 14 floats.
+int jade_debug_mis_terms(int device_id, int32_t n, const float* rows, float* out) {
+  if (!rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / 14) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bo;
+  HIP_TRY(upload0(bi, rows, 14 * N));
+  HIP_TRY(bo.alloc(8 * N));
+  hipLaunchKernelGGL(k_debug_mis_terms, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 8 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 

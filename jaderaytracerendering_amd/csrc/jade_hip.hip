@@ -218,10 +218,12 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // k_shade_lights* kernels only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
 // COSINE: the environment and indirect rays of a sampling vertex are drawn with pdf cos / pi about the normal (include/jade_bvh.h, "The bounce,
 // stated"; non-parity; the k_shade_cos* kernels only).  Nothing of it travels with the record.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// MIS: the emitter rays and the indirect ray weighed against each other (include/jade_bvh.h, "The direct light, stated"; non-parity; the
+// k_shade_cos_mis* kernels only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
-                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr) {
+                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr) {
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -305,7 +307,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, light);
+      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS, COSINE, MIS>(S, px, c, &l_final, lights, light, mis);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
       } else if (r == CONSUME_EMITTED) {
@@ -343,7 +345,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
           // emitter, the roulette ended the path) has all its results already - nothing is visible: folded in right here (with the
           // reference's sampling there is always the environment ray)
-          const int r = consume<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, light);
+          const int r = consume<ENVIS, LIGHTS, COSINE, MIS>(S, px, c, &l_final, lights, light, mis);
           if (r == CONSUME_VERTEX) {
             st = ST_VERTEX;
             continue;
@@ -543,11 +545,12 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const ShutterConst* H = nullptr, const uint4* lights = nullptr) {
+                                               uint32_t stop_below, const ShutterConst* H = nullptr, const uint4* lights = nullptr,
+                                               const float2* mis = nullptr) {
   const uint32_t n = n_dev ? *n_dev : n_host;
   // A pass of a batch (prev = the pass before it, on the device): nothing to do once the paths have ended (that pass
   // emitted no ray) or once fewer than stop_below records are active - the point where the host would hand the rest to
@@ -565,7 +568,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights);
+  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -647,6 +650,33 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_co
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below, const uint4* lights) {
   shade_kernel_body<true, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
+}
+// ... and with multiple importance sampling of the emitters on top of the cosine bounce (jade_scene_set_direct_sampling = JADE_DIRECT_MIS,
+// non-parity): the four kernels that carry that code.  All take the k_shade_cos* arguments and the per-triangle table {m, M} (mis_table,
+// jade_scene_prep.hip) as one more, the last.
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
+  shade_kernel_body<false, false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
+  shade_kernel_body<true, false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
+  shade_kernel_body<false, false, false, true, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
+}
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
+  shade_kernel_body<true, false, false, true, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2037,6 +2067,7 @@ static int upload_scene(jade_scene* s, const jade_scene_desc* d, const ScenePrep
   if (e == hipSuccess) e = upload(s->b_env, d->env_rgb, (size_t)3 * d->env_width * d->env_height, s->stream);
   if (e == hipSuccess) e = upload(s->b_env_alias, p.env_alias.data(), p.env_alias.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_light_alias, p.light_alias.data(), p.light_alias.size(), s->stream);
+  if (e == hipSuccess) e = upload(s->b_mis, p.mis.data(), p.mis.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_tnorm, p.tnorm.data(), p.tnorm.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_mats, p.mats.data(), p.mats.size(), s->stream);
   if (e == hipSuccess) e = upload(s->b_guide, p.guide.data(), p.guide.size(), s->stream);
@@ -2218,6 +2249,19 @@ int jade_scene_get_bounce_sampling(jade_scene* s, int* mode) {
   return JADE_OK;
 }
 
+// The direct sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_direct_sampling(jade_scene* s, int mode) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (mode != JADE_DIRECT_RAYS && mode != JADE_DIRECT_MIS) return jade_fail(JADE_ERR_INVALID, "unknown direct sampling (JADE_DIRECT_*)");
+  s->direct_sampling = mode;
+  return JADE_OK;
+}
+int jade_scene_get_direct_sampling(jade_scene* s, int* mode) {
+  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *mode = s->direct_sampling;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -2316,6 +2360,10 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
     return jade_fail(JADE_ERR_UNSUPPORTED, std::string("bounce sampling: JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling) does not run together with ") +
                                                (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
                                                " yet: those kernels are not built");
+  const bool mis = s->direct_sampling == JADE_DIRECT_MIS;
+  if (mis && !cosine)
+    return jade_fail(JADE_ERR_UNSUPPORTED, "direct sampling: JADE_DIRECT_MIS (jade_scene_set_direct_sampling) weighs the emitter rays against the cosine bounce "
+                                           "and needs JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling)");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
@@ -2386,6 +2434,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->dn_carried = jade_stats{};
   s->lights_on = lights_one;  // the scene's light sampling as it is now: the render keeps it, like its lens
   s->cosine_on = cosine;      // ... and its bounce sampling
+  s->mis_on = mis;            // ... and its direct sampling
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
@@ -2435,6 +2484,7 @@ struct PassRun {
   decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
   decltype(&k_shade_shutter) shade_kernel_shutter = nullptr;  // under a shutter: the kernel launched instead, with s->sh as its last argument
   decltype(&k_shade_lights) shade_kernel_lights = nullptr;    // JADE_LIGHTS_ONE or JADE_BOUNCE_COSINE: the kernel launched instead, with the emitters' alias table as its last argument
+  decltype(&k_shade_cos_mis) shade_kernel_mis = nullptr;      // JADE_DIRECT_MIS: the kernel launched instead, with the alias table and the per-triangle table {m, M} as its last arguments
   bool batching, tail_ok;
   uint32_t tail_max;                  // active records at or below which k_tail finishes the list
   uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
@@ -2506,7 +2556,11 @@ static int launch_arm(jade_scene* s, uint32_t target_spp, QueueCtl* ctl, size_t 
 static void launch_shade(const PassRun& r, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
                          const QueueCtl* prev, uint32_t stop_below) {
   jade_scene* s = r.s;
-  if (r.shade_kernel_lights)
+  if (r.shade_kernel_mis)
+    hipLaunchKernelGGL(r.shade_kernel_mis, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
+                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below,
+                       (const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
+  else if (r.shade_kernel_lights)
     hipLaunchKernelGGL(r.shade_kernel_lights, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
                        list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below,
                        (const uint4*)s->b_light_alias.as<uint4>());
@@ -2858,6 +2912,9 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   // cosine-weighted bounces (refused under a lens or a shutter likewise): its own kernels under either light sampling, with the same arguments
   if (s->cosine_on)
     r.shade_kernel_lights = s->lights_on ? (s->ps.env_sampling ? k_shade_cos_lights_envis : k_shade_cos_lights) : (s->ps.env_sampling ? k_shade_cos_envis : k_shade_cos);
+  // ... and with the emitters' two techniques weighed (jade_render_begin: under cosine bounces only): its own kernels, one more argument
+  if (s->mis_on)
+    r.shade_kernel_mis = s->lights_on ? (s->ps.env_sampling ? k_shade_cos_mis_lights_envis : k_shade_cos_mis_lights) : (s->ps.env_sampling ? k_shade_cos_mis_envis : k_shade_cos_mis);
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
   r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s) && !s->lights_on && !s->cosine_on;  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));

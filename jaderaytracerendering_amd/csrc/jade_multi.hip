@@ -138,6 +138,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->bounce_sampling != scenes[0]->bounce_sampling)
       return jade_fail(JADE_ERR_INVALID, "the scenes carry different bounce sampling modes (jade_scene_set_bounce_sampling): scene " + std::to_string(i) + " against scene 0");
+  // ... and with the same direct sampling (jade_scene_set_direct_sampling)
+  for (int i = 1; i < ndev; ++i)
+    if (scenes[i]->direct_sampling != scenes[0]->direct_sampling)
+      return jade_fail(JADE_ERR_INVALID, "the scenes carry different direct sampling modes (jade_scene_set_direct_sampling): scene " + std::to_string(i) + " against scene 0");
   // 1. every device renders its share (one host thread each) and resolves it into a device buffer
   std::vector<int> rcs(ndev, JADE_OK);
   std::vector<std::string> msgs(ndev);

@@ -200,7 +200,7 @@ struct jade_scene {
   Tunables tun;
   hipStream_t stream = nullptr;
   DevScene dev{};
-  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias, b_light_alias;
+  DevBuf b_nodes, b_nodes4, b_tverts, b_tris, b_emit, b_mapping, b_prefix, b_segs, b_env, b_guide, b_guide_obj, b_tnorm, b_mats, b_anyhit, b_env_alias, b_light_alias, b_mis;
   bool boxes_nested = true;   // every child's box lies inside its parent's (jade_scene_create): what the wide walk and the occluder cache need
   int n_emit = 0;
   int n_objects = 0;
@@ -214,6 +214,8 @@ struct jade_scene {
   bool lights_on = false;     // ... and what the render in progress took: JADE_LIGHTS_ONE (its records have min(n_emit, 1) + 2 slots)
   int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling: what the next jade_render_begin takes ...
   bool cosine_on = false;     // ... and what the render in progress took: JADE_BOUNCE_COSINE (the k_shade_cos* kernels; same records, same rays)
+  int direct_sampling = JADE_DIRECT_RAYS;  // jade_scene_set_direct_sampling: what the next jade_render_begin takes ...
+  bool mis_on = false;        // ... and what the render in progress took: JADE_DIRECT_MIS (the k_shade_cos_mis* kernels; cosine's records, rays and counters)
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;
@@ -278,6 +280,7 @@ struct ScenePrep {
   std::vector<DevMaterial> mats;
   std::vector<uint4> env_alias;
   std::vector<uint4> light_alias;                     // JADE_LIGHTS_ONE: the alias table over emit_indices (n_emit entries)
+  std::vector<float2> mis;                            // JADE_DIRECT_MIS: {m, M} per triangle (n_triangles entries)
   int n_internal = 0;
   size_t n_pairs = 0;
   bool missing_child = false;  // the reference's "child 0" under an internal node: the walk then needs its general form
@@ -301,6 +304,10 @@ static inline bool env_importance_fits(int32_t env_width, int32_t env_height) {
 // emission + a floor), made by env_alias_table's builder, and the emitter counts that mode takes: light_sample (jade_shade.h) forms the
 // slot from a 24-bit uniform, as env_sample does
 JADE_HIDDEN void light_alias_table(const jade_triangle* triangles, const int32_t* emit_indices, int32_t n_emit, std::vector<uint4>& light_alias);
+// ... and its per-triangle table for JADE_DIRECT_MIS (include/jade_bvh.h "The direct light, stated"): {m, M} of a weighted triangle, {0, 0} of
+// every other; light_alias is light_alias_table's (n_emit entries, or empty: M = 0)
+JADE_HIDDEN void mis_table(const jade_triangle* triangles, int32_t n_triangles, const int32_t* emit_indices, int32_t n_emit,
+                           const std::vector<uint4>& light_alias, std::vector<float2>& mis);
 static inline bool light_sampling_fits(int64_t n_emit) { return n_emit >= 0 && n_emit <= JADE_LIGHTS_ONE_MAX_ENTRIES; }
 
 // The two places where host code of one file needs a kernel of another (this tree is not built with -fgpu-rdc), both in jade_hip.hip:

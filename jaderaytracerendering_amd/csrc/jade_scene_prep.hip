@@ -382,6 +382,40 @@ void light_alias_table(const jade_triangle* triangles, const int32_t* emit_indic
   alias_table_of(wgt, total, light_alias);
 }
 
+// Multiple importance sampling of the emitters (jade_scene_set_direct_sampling = JADE_DIRECT_MIS; non-parity): per triangle h the number
+// of entries of emit_indices that name it, m, and the probability with which JADE_LIGHTS_ONE's table realises them, M - for a WEIGHTED
+// triangle (emits at or above the indirect-hit threshold, area and stored normal finite and positive: include/jade_bvh.h, "The direct
+// light, stated"); {0, 0} for every other.  The area is tri_size's statements in fp32, as in light_alias_table.  No HIP call.
+void mis_table(const jade_triangle* triangles, int32_t n_triangles, const int32_t* emit_indices, int32_t n_emit, const std::vector<uint4>& light_alias,
+               std::vector<float2>& mis) {
+  const size_t N = n_triangles > 0 ? (size_t)n_triangles : 0, nE = n_emit > 0 ? (size_t)n_emit : 0;
+  std::vector<uint32_t> count(N, 0u);
+  std::vector<double> prob(N, 0.0);
+  const bool have_q = nE > 0 && light_alias.size() == nE;
+  for (size_t i = 0; i < nE; ++i) {
+    const size_t h = (size_t)emit_indices[i];
+    count[h]++;
+    if (have_q) {
+      float q;
+      memcpy(&q, &light_alias[i].z, 4);
+      prob[h] += (double)q;
+    }
+  }
+  mis.assign(N, make_float2(0.0f, 0.0f));
+  for (size_t h = 0; h < N; ++h) {
+    if (count[h] == 0) continue;
+    const jade_triangle& t = triangles[h];
+    if (t.emissive[0] < 1.5e-4f && t.emissive[1] < 1.5e-4f && t.emissive[2] < 1.5e-4f) continue;  // nonemissive (jade_shade.h)
+    const jvec3 p1 = jv(t.p1[0], t.p1[1], t.p1[2]);
+    const jvec3 cp = jv_cross(jv_sub(jv(t.p2[0], t.p2[1], t.p2[2]), p1), jv_sub(jv(t.p3[0], t.p3[1], t.p3[2]), p1));
+    const float area = 0.5f * jade_sqrt(jv_dot(cp, cp));
+    const jvec3 ne = jv(t.norm[0], t.norm[1], t.norm[2]);
+    const float nne = jv_dot(ne, ne);
+    if (!(area > 0 && std::isfinite(area)) || !(nne > 0 && std::isfinite(nne))) continue;
+    mis[h] = make_float2((float)count[h], (float)(prob[h] / (double)nE));
+  }
+}
+
 // What jade_scene_create checks of the caller's descriptor before anything is derived from it: ranges, and a walk of the tree from the
 // root - the nodes the root does not reach are not read (include/jade_rt.h).  No HIP call.
 int validate_desc(const jade_scene_desc* d, int* depth_out) {
@@ -464,5 +498,6 @@ int prepare_scene(const jade_scene_desc& desc, int depth, const Tunables& tun, S
   materials(d, out->mats, out->tnorm);
   env_alias_table(d->env_width, d->env_height, d->env_rgb, out->env_alias);
   if (light_sampling_fits(d->n_emit)) light_alias_table(d->triangles, d->emit_indices, d->n_emit, out->light_alias);  // (a longer list renders with JADE_LIGHTS_ALL only)
+  mis_table(d->triangles, d->n_triangles, d->emit_indices, d->n_emit, out->light_alias, out->mis);
   return JADE_OK;
 }

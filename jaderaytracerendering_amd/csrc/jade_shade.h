@@ -199,6 +199,28 @@ static __device__ __forceinline__ float cosine_weight(jvec3 n, jvec3 rd) {
   return (nn > 0 && nn < jade_u2f(0x7f800000u)) ? 0.5f * jade_sqrt(nn) : jade_fabs(jv_dot(n, rd));
 }
 
+// Multiple importance sampling of the emitters (jade_scene_set_direct_sampling = JADE_DIRECT_MIS; NOT the reference's estimator), as
+// include/jade_bvh.h states it ("The direct light, stated"): the balance heuristic between a uniform point of emitter triangle h (density
+// PL = mu * pA per solid angle) and the cosine bounce (pB), from ONE vector l - vertex to a point of h - on both sides.  n: the vertex's
+// stored normal; ne, A: h's stored normal and tri_size; (m, mu): h's row of the table (mis_table, jade_scene_prep.hip; mu = m with all
+// lights, M with one).  *w_L: what an emitter term towards h is multiplied with; *g_B: the scalar factor of the bounce term,
+// T_B = Le f g_B / RR.  h not weighted (m not > 0), or a normal that gives the cosine draw no axis: w_L = 1, g_B = 0.
+static __device__ __forceinline__ void mis_terms(jvec3 n, jvec3 ne, float A, float m, float mu, jvec3 l, float* w_L, float* g_B) {
+  const float nn = jv_dot(n, n);
+  if (!(m > 0) || !(nn > 0 && nn < jade_u2f(0x7f800000u))) {
+    *w_L = 1.0f;
+    *g_B = 0.0f;
+    return;
+  }
+  const float ll = jv_dot(l, l), rl = jade_sqrt(ll), sne = jade_sqrt(jv_dot(ne, ne));
+  const float nl = jade_fabs(jv_dot(n, l));
+  const float pA = ll * rl * sne / (A * jade_fabs(jv_dot(ne, l)));
+  const float PL = mu * pA;
+  const float pB = nl / (rl * jade_sqrt(nn) * (float)JADE_PI_D);
+  *w_L = 1.0f / (1.0f + pB / PL);  // (PL = inf: 1; no inf / inf for l.l > 0)
+  *g_B = m * (nl / rl) * sne / (PL + pB);
+}
+
 static __device__ __forceinline__ jvec3 tri_point(const jade_triangle* t, float rx, float ry) {
   jvec3 p1 = V3(t->p1);
   return jv_add(jv_add(p1, jv_scale(jv_sub(V3(t->p2), p1), rx)), jv_scale(jv_sub(V3(t->p3), p1), ry));
@@ -709,8 +731,12 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // refraction loop issued its next ray.
 // LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight (bounce_branch)
 // COSINE: where a ray came from cosine_dir_rng, the reference's |dot(normal, direction)| is cosine_weight - four places, nothing else
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
-static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u) {
+// MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with COSINE only; compiled apart, k_shade_cos_mis*): at a diffuse or
+// SSS-diffuse vertex an emitter term towards a weighted triangle is multiplied by w_L, and an indirect ray that lands on one adds T_B
+// before the vertex's scale.  `mis`: the per-triangle table {m, M}.  Rays, draws, records and counters are COSINE's.
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>
+static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u,
+                              const float2* mis = nullptr) {
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
   const int nL = LIGHTS ? (nE > 0 ? 1 : 0) : nE;
@@ -738,6 +764,12 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
         w = jv_divs(jv_divs(w, dls), dls);
         w = jv_scale(w, tri_size(&T[emit_tri_idx]));
         if (LIGHTS) w = jv_scale(w, light_weight(lights, (uint32_t)nE, light));  // x 1 / (the probability the entry was drawn with)
+        if (MIS) {
+          const float2 e = mis[emit_tri_idx];
+          float w_L, g_B;
+          mis_terms(n, t_i.norm, tri_size(&T[emit_tri_idx]), e.x, LIGHTS ? e.y : e.x, ld, &w_L, &g_B);
+          w = jv_scale(w, w_L);
+        }
         l_dir = jv_add(l_dir, w);
       }
     }
@@ -748,6 +780,18 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       w = jv_scale(jv_scale(w, 2.0f), PI_F);
       if (ENVIS) w = jv_scale(w, __int_as_float(px.auxi()));  // x (1 / 2 pi) / pdf: the reference's weight is 1 / its own pdf
       l_dir = jv_add(l_dir, w);
+    }
+    if (MIS && (c.flags & STF_RR)) {  // the bounce term: the indirect ray found a weighted emitter
+      const int bh = px.hit(nL + 1);
+      if (bh >= 0) {
+        const float2 e = mis[bh];
+        if (e.x > 0) {
+          const ShadeTri t_b = shade_tri(S, bh);
+          float w_L, g_B;
+          mis_terms(n, t_b.norm, tri_size(&T[bh]), e.x, LIGHTS ? e.y : e.x, jv_sub(px.hpt(nL + 1), c.src), &w_L, &g_B);
+          l_dir = jv_add(l_dir, jv_divs(jv_scale(jv_mul(V3(t_b.m->emissive), f), g_B), RR_F));
+        }
+      }
     }
     l_dir = jv_scale(l_dir, sss ? (float)(k / JADE_SSS_RATE_D) : (float)k);
     *l_final = l_dir;

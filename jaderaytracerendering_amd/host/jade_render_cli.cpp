@@ -53,6 +53,8 @@ struct Api {
   int (*scene_set_light_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --bounce
   int (*scene_set_bounce_sampling)(jade_scene*, int) = nullptr;
+  // ... and only for --direct
+  int (*scene_set_direct_sampling)(jade_scene*, int) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -95,7 +97,7 @@ static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance] [--one-light]\n"
-          "                   [--bounce uniform|cosine]\n"
+          "                   [--bounce uniform|cosine] [--direct rays|mis]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -116,6 +118,9 @@ static void usage() {
           "  --bounce cosine: the environment and indirect rays of every diffuse and sub-surface vertex are drawn with density cos / pi about the\n"
           "                   normal instead of uniformly (HIP backend only; NOT the reference's samples; include/jade_bvh.h).  Same rays per\n"
           "                   sample, less noise under open sky; not together with --aperture or --shutter-*.  uniform is the default\n"
+          "  --direct mis: the emitter rays and the indirect ray of every diffuse vertex are weighed against each other (multiple importance\n"
+          "                sampling, balance heuristic), which bounds the bright samples next to a lamp (HIP backend only; NOT the reference's\n"
+          "                samples; include/jade_bvh.h).  Needs --bounce cosine and implies nothing.  rays is the default\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -157,6 +162,7 @@ int main(int argc, char** argv) {
   double aperture = 0.0, focus = 0.0, focus_px = 0, focus_py = 0;
   bool one_light = false;
   int bounce = -1;  // --bounce: JADE_BOUNCE_*, -1 = not given
+  int direct = -1;  // --direct: JADE_DIRECT_*, -1 = not given
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -199,6 +205,12 @@ int main(int argc, char** argv) {
       if (v == "uniform") bounce = JADE_BOUNCE_UNIFORM;
       else if (v == "cosine") bounce = JADE_BOUNCE_COSINE;
       else { fprintf(stderr, "--bounce takes uniform or cosine, not %s\n", v.c_str()); return 2; }
+    }
+    else if (a == "--direct") {
+      const std::string v = need("--direct");
+      if (v == "rays") direct = JADE_DIRECT_RAYS;
+      else if (v == "mis") direct = JADE_DIRECT_MIS;
+      else { fprintf(stderr, "--direct takes rays or mis, not %s\n", v.c_str()); return 2; }
     }
     else if (a == "--adaptive") { adaptive = number("--adaptive", need("--adaptive")); use_adaptive = true; }
     else if (a == "--min-spp") { const double v = number("--min-spp", need("--min-spp")); min_spp = v >= 0 && v <= (1 << 30) && v == (int)v ? (int)v : -1; }
@@ -372,6 +384,17 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (direct == JADE_DIRECT_MIS && bounce != JADE_BOUNCE_COSINE) {
+    fprintf(stderr, "--direct mis weighs the emitter rays against the cosine bounce: it needs --bounce cosine\n");
+    return 2;
+  }
+  if (direct >= 0) {
+    *(void**)(&api.scene_set_direct_sampling) = dlsym(api.h, "jade_scene_set_direct_sampling");
+    if (!api.scene_set_direct_sampling) {
+      fprintf(stderr, "--direct needs the HIP backend: %s has no jade_scene_set_direct_sampling\n", backend.c_str());
+      return 2;
+    }
+  }
   // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
   const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
   if (need_display) {
@@ -425,7 +448,9 @@ int main(int argc, char** argv) {
   }
   if (one_light && api.scene_set_light_sampling(dev, JADE_LIGHTS_ONE) != JADE_OK) { fprintf(stderr, "light sampling: %s\n", api.last_error()); return 1; }
   if (bounce >= 0 && api.scene_set_bounce_sampling(dev, bounce) != JADE_OK) { fprintf(stderr, "bounce sampling: %s\n", api.last_error()); return 1; }
-  const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "");
+  if (direct >= 0 && api.scene_set_direct_sampling(dev, direct) != JADE_OK) { fprintf(stderr, "direct sampling: %s\n", api.last_error()); return 1; }
+  const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
+                                    (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);

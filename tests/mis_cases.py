@@ -1,0 +1,205 @@
+"""The sample-for-sample cases of multiple importance sampling of the emitters (JADE_DIRECT_MIS): their scenes, the driver that holds a
+backend's 1-spp frames against tests/mis_spec.py's arm (test_jade_spec.compare's bar, unchanged: 1e-4 relative per channel with a floor
+of 1e-3, at most 2 % of the samples disagreeing, bssrdf-coplanar samples left out) and the `need` tables.  tests/test_gpu_mis.py
+compares on the device; tests/test_mis_cpu.py counts what the arm alone reaches, without a GPU."""
+import numpy as np
+
+import mis_spec
+import test_jade_spec as TJ
+from conftest import B, J
+from jaderaytracerendering_amd import _abi, host as H
+
+MAX_LEFT_OUT = 0.05
+BIG = dict(emissive=(6, 5, 4), brdf=(0.3, 0.3, 0.3))
+WALL = np.array([[1.7, -0.9, -1.2], [1.7, 1.5, -1.2], [1.7, 1.5, 1.8], [1.7, -0.9, 1.8]], np.float32)
+BACK = np.array([[-2.5, -0.9, 3.0], [2.5, -0.9, 3.0], [2.5, 2.5, 3.0], [-2.5, 2.5, 3.0]], np.float32)
+
+
+def big_lamp():
+    """The jade cube on the floor under a lamp quad of side 3.6 at y = 1.15, a hand's breadth over the cube's top corner, and beside a
+    second one standing at x = 1.7 (outside the camera's view of the cube) and a third standing behind the camera at z = 3: a large
+    share of the indirect rays of the cube's faces and of the floor ends on one of them.  emit_indices = their six triangles and the
+    first again."""
+    b = J.SceneBuilder()
+    b.add_mesh(TJ.CUBE_V, TJ.CUBE_I, H.material(**TJ.JADE), H.transform_matrix(rot_deg=(20, 30, 0)))
+    b.add_mesh(TJ.quad(1.15, 1.8, flip=True), TJ.QUAD_I, H.material(**BIG))
+    b.add_mesh(WALL, TJ.QUAD_I, H.material(**BIG))
+    b.add_mesh(BACK, TJ.QUAD_I, H.material(**BIG))
+    b.add_mesh(TJ.quad(-0.9, 3.0), TJ.QUAD_I, H.material(**TJ.FLOOR))
+    b.set_env_constant(0.5, 0.6, 0.8)
+    hs = b.build()
+    obj = hs.tri_i32()[:, 0]
+    lamp = np.flatnonzero((obj >= 1) & (obj <= 3))
+    assert len(lamp) == 6
+    hs.a["emit"] = np.array(list(lamp) + [lamp[0]], np.int32)
+    return hs
+
+
+def long_normals():
+    """two_lamps with the stored normals of the four lamp triangles times 1.7 and of every third other triangle times 2.5: the
+    reference's terms scale with both lengths, pA with the emitter's and pB with neither."""
+    hs = TJ.build("two_lamps")
+    t, obj = hs.tri_f32(), hs.tri_i32()[:, 0]
+    lamp = (obj == 1) | (obj == 2)
+    t[lamp, 10:13] *= np.float32(1.7)
+    others = np.flatnonzero(~lamp)
+    t[others[::3], 10:13] *= np.float32(2.5)
+    return hs
+
+
+CONTACT_LE = (12.0, 10.0, 8.0)
+CONTACT_W, CONTACT_H = 48, 40
+
+
+def contact():
+    """A diffuse floor (FLOOR's material, y = 0) with a lamp quad standing on it - x in [-0.5, 0.5], y in [0, 1], in the plane z = 0 - under a
+    black sky: the contact edge, where the emitter term of a floor vertex has no bound.  emit_indices = the lamp's two triangles."""
+    b = J.SceneBuilder()
+    b.add_mesh(TJ.quad(0.0, 3.0), TJ.QUAD_I, H.material(**TJ.FLOOR))
+    b.add_mesh(np.array([[-0.5, 0, 0], [0.5, 0, 0], [0.5, 1, 0], [-0.5, 1, 0]], np.float32), TJ.QUAD_I,
+               H.material(emissive=CONTACT_LE, brdf=(0.3, 0.3, 0.3)))
+    b.set_env_constant(0, 0, 0)
+    hs = b.build()
+    assert len(hs.a["emit"]) == 2 and (hs.tri_i32()[hs.a["emit"], 0] == 1).all()
+    return hs
+
+
+def contact_camera():
+    return H.camera_orbit(1.0, 40.0, 0.0)      # close over the edge: the lamp fills the upper half of the frame, the floor the lower
+
+
+def contact_floor_mask(width=CONTACT_W, height=CONTACT_H):
+    """[height, width] bool: the pixels of contact()'s frame every one of whose camera rays ends on the floor - the nine rays of the
+    jitters {0, 0.5, 1}^2 (jade_spec.sample's camera) meet y = 0 inside the floor and do not meet the lamp's rectangle, grown by 0.01,
+    before that.  Geometry alone; no render."""
+    eye, cam = contact_camera()
+    M = np.asarray(cam, np.float64).reshape(4, 4)
+    o = np.asarray(eye, np.float64)
+    ok = np.ones((height, width), bool)
+    ys, xs = np.mgrid[0:height, 0:width]
+    for u in (0.0, 0.5, 1.0):
+        for v in (0.0, 0.5, 1.0):
+            lx = (-1 + 2.0 / width * (xs + u - 0.5)) * (width / height)
+            ly = -1 + 2.0 / height * (ys + v - 0.5)
+            d = lx[..., None] * M[0, :3] + ly[..., None] * M[1, :3] - 1.5 * M[2, :3]
+            with np.errstate(all="ignore"):
+                tf = -o[1] / d[..., 1]
+                pf = o + d * tf[..., None]
+                floor = (tf > 0) & (np.abs(pf[..., 0]) < 3) & (np.abs(pf[..., 2]) < 3)
+                tl = -o[2] / d[..., 2]
+                pl = o + d * tl[..., None]
+                lamp = (tl > 0) & (np.abs(pl[..., 0]) < 0.51) & (pl[..., 1] > -0.01) & (pl[..., 1] < 1.01) & ~(tl > tf)
+            ok &= floor & ~lamp
+    return ok
+
+
+def build(kind, sky=False):
+    if kind == "contact":
+        return contact()
+    if kind == "big_lamp":
+        return big_lamp()
+    if kind == "long_normals":
+        return long_normals()
+    return TJ.build(kind, sky)
+
+
+def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_REFERENCE, light_sampling=_abi.LIGHTS_ALL, out=None, count_only=False):
+    """test_jade_spec.compare for JADE_DIRECT_MIS over JADE_BOUNCE_COSINE.  count_only: no backend - what the arm alone counts per tag."""
+    hs = build(kind, sky)
+    S = mis_spec.Scene(hs, env_sampling, light_sampling)
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    seen, bad, kept = {}, [], {}
+    n = skipped = 0
+    worst = 0.0
+
+    def run(sc):
+        nonlocal n, skipped, worst
+        for frame in frames:
+            if sc is not None:
+                p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2, env_sampling=env_sampling)
+                rgb, _, _ = sc.render(p, want_bgr8=False)
+                kept[frame] = rgb
+            for y in range(size):
+                for x in range(size):
+                    tr = []
+                    want = mis_spec.sample(S, x, y, size, size, eye, cam, frame, tr)
+                    if "bssrdf-coplanar" in tr:
+                        skipped += 1
+                        continue
+                    n += 1
+                    got = want if sc is None else rgb[y, x].astype(np.float64)
+                    if bool((np.abs(got - want) <= 1e-4 * np.maximum(np.abs(want), 1e-3)).all()):
+                        worst = max(worst, float((np.abs(got - want) / np.maximum(np.abs(want), 1e-3)).max()))
+                        for t in set(tr):
+                            seen[t] = seen.get(t, 0) + 1
+                    else:
+                        bad.append((frame, x, y, tr, got, want))
+
+    if count_only:
+        run(None)
+    else:
+        with backend.scene(hs) as sc:
+            sc.set_bounce_sampling(_abi.BOUNCE_COSINE)
+            sc.set_direct_sampling(_abi.DIRECT_MIS)
+            if light_sampling != _abi.LIGHTS_ALL:
+                sc.set_light_sampling(light_sampling)
+            run(sc)
+    print(f"compare mis {kind} sky={sky} env_sampling={env_sampling} light_sampling={light_sampling}: {n} compared, {len(bad)} disagree, "
+          f"{skipped} left out, worst relative error {worst:.3g}, seen {dict(sorted(seen.items()))}")
+    if out is not None:
+        out.update(frames=kept, worst=worst, seen=seen, bad=bad)
+    assert skipped <= MAX_LEFT_OUT * (n + skipped), f"{skipped} of {n + skipped} samples left out as bssrdf-coplanar"
+    assert len(bad) <= 0.02 * n, f"{len(bad)} of {n} samples disagree with the float64 spec, e.g. {bad[:3]}"
+    for tag, count in need.items():
+        assert seen.get(tag, 0) >= count, f"only {seen.get(tag, 0)} agreeing samples went through '{tag}' ({seen})"
+    return seen, len(bad), n, skipped
+
+
+# 12 x 12 frames at 1 spp.  `need`: half of what the arm alone counts for every tag on these samples (tests/test_mis_cpu.py holds the
+# tables to these counts and the frames to the 5 % that may be left out).
+IMP, ONE = _abi.ENV_IMPORTANCE, _abi.LIGHTS_ONE
+CASES = {
+    # the arm alone: 423 samples, 9 left out (2.1 %): 18 bssrdf, 251 cos-env, 227 cos-indirect, 221 diffuse, 64 mirror, 11 mis-bounce-lit,
+    # 4 mis-sss-bounce-lit, 3 mis-unweighted (the listed floor triangle), 211 mis-weighted, 142 sky, 40 sss            (k_shade_cos_mis)
+    "two_lamps": dict(kind="two_lamps", size=12, frames=(0, 1, 2),
+                      need={"bssrdf": 9, "cos-env": 125, "cos-indirect": 113, "diffuse": 110, "mirror": 32, "mis-bounce-lit": 5,
+                            "mis-sss-bounce-lit": 2, "mis-unweighted": 1, "mis-weighted": 105, "sky": 71, "sss": 20}),
+    # under one light (k_shade_cos_mis_lights; mu = M): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
+    # 219 diffuse, 116 diffuse-lit, 80 light-alias, 136 light-lit, 176 light-own, 116 light-shadowed, 15 light-side, 60 mirror,
+    # 6 mis-bounce-lit, 2 mis-sss-bounce-lit, 130 mis-weighted, 142 sky, 34 sss, 15 sss-lit
+    "two_lamps_one_light": dict(kind="two_lamps", light_sampling=ONE, size=12, frames=(0, 1, 2),
+                                need={"bssrdf": 6, "bssrdf-lit": 3, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "diffuse-lit": 58,
+                                      "light-alias": 40, "light-lit": 68, "light-own": 88, "light-shadowed": 58, "light-side": 7, "mirror": 30,
+                                      "mis-bounce-lit": 3, "mis-sss-bounce-lit": 1, "mis-weighted": 65, "sky": 71, "sss": 17, "sss-lit": 7}),
+    # both under JADE_ENV_IMPORTANCE with the textured sky (k_shade_cos_mis_envis): 423 samples, 9 left out (2.1 %): 14 bssrdf,
+    # 226 cos-indirect, 223 diffuse, 176 env-importance, 95 env-noenv, 64 mirror, 13 mis-bounce-lit, 4 mis-sss-bounce-lit, 1 mis-unweighted,
+    # 212 mis-weighted, 142 sky, 38 sss
+    "two_lamps_sky_importance": dict(kind="two_lamps", sky=True, env_sampling=IMP, size=12, frames=(0, 1, 2),
+                                     need={"bssrdf": 7, "cos-indirect": 113, "diffuse": 111, "env-importance": 88, "env-noenv": 47, "mirror": 32,
+                                           "mis-bounce-lit": 6, "mis-sss-bounce-lit": 2, "mis-weighted": 106, "sky": 71, "sss": 19}),
+    # (k_shade_cos_mis_lights_envis): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse, 118 diffuse-lit,
+    # 170 env-importance, 99 env-noenv, 87 light-alias, 138 light-lit, 180 light-own, 120 light-shadowed, 21 light-side, 71 mirror,
+    # 9 mis-bounce-lit, 5 mis-sss-bounce-lit, 131 mis-weighted, 142 sky, 45 sss, 18 sss-lit
+    "two_lamps_sky_importance_one_light": dict(kind="two_lamps", sky=True, env_sampling=IMP, light_sampling=ONE, size=12, frames=(0, 1, 2),
+                                               need={"bssrdf": 8, "bssrdf-lit": 5, "cos-indirect": 113, "diffuse": 110, "diffuse-lit": 59,
+                                                     "env-importance": 85, "env-noenv": 49, "light-alias": 43, "light-lit": 69, "light-own": 90,
+                                                     "light-shadowed": 60, "light-side": 10, "mirror": 35, "mis-bounce-lit": 4,
+                                                     "mis-sss-bounce-lit": 2, "mis-weighted": 65, "sky": 71, "sss": 22, "sss-lit": 9}),
+    # one dim lamp triangle listed, the other three lamp triangles emit and are NOT listed: an indirect ray that ends on one of them adds
+    # nothing (mis-bounce-unlisted).  418 samples, 14 left out (3.2 %): 15 bssrdf, 246 cos-env, 227 cos-indirect, 218 diffuse, 66 mirror,
+    # 2 mis-bounce-lit, 5 mis-bounce-unlisted, 1 mis-sss-bounce-lit, 109 mis-weighted, 142 sky, 41 sss
+    "one_entry": dict(kind="one_entry", size=12, frames=(0, 1, 2),
+                      need={"bssrdf": 7, "cos-env": 123, "cos-indirect": 113, "diffuse": 109, "mirror": 33, "mis-bounce-lit": 1,
+                            "mis-bounce-unlisted": 2, "mis-weighted": 54, "sky": 71, "sss": 20}),
+    # three large near lamps: 847 samples, 17 left out (2.0 %): 31 bssrdf, 463 cos-env, 420 cos-indirect, 410 diffuse, 131 mirror,
+    # 195 mis-bounce-lit, 32 mis-sss-bounce-lit, 439 mis-weighted, 135 sky, 74 sss
+    "big_lamp": dict(kind="big_lamp", size=12, frames=(0, 1, 2, 3, 4, 5),
+                     need={"bssrdf": 15, "cos-env": 231, "cos-indirect": 210, "diffuse": 205, "mirror": 65, "mis-bounce-lit": 97,
+                           "mis-sss-bounce-lit": 16, "mis-weighted": 219, "sky": 67, "sss": 37}),
+    # emitter normals times 1.7, every third other normal times 2.5: 422 samples, 10 left out (2.3 %): 17 bssrdf, 247 cos-env,
+    # 223 cos-indirect, 82 cos-nonunit, 218 diffuse, 63 mirror, 10 mis-bounce-lit, 4 mis-sss-bounce-lit, 3 mis-unweighted, 211 mis-weighted,
+    # 142 sky, 39 sss
+    "long_normals": dict(kind="long_normals", size=12, frames=(0, 1, 2),
+                         need={"bssrdf": 8, "cos-env": 123, "cos-indirect": 111, "cos-nonunit": 41, "diffuse": 109, "mirror": 31,
+                               "mis-bounce-lit": 5, "mis-sss-bounce-lit": 2, "mis-unweighted": 1, "mis-weighted": 105, "sky": 71, "sss": 19}),
+}

@@ -1,0 +1,281 @@
+"""Multiple importance sampling of the emitters without a GPU (include/jade_bvh.h, "The direct light, stated"): the per-triangle table
+of the module (jade_debug_mis_table_host: host code, no HIP call) against tests/mis_spec.py's, the two weights summing to one from the
+spec's two code paths, the estimator's expectation by quadrature - no sampling - against the unweighted emitter expectation, the arm
+with nothing to weigh against bounce_spec's double for double, and the `need` tables of tests/mis_cases.py."""
+import ctypes
+import math
+import os
+
+import numpy as np
+import pytest
+
+import bounce_spec
+import jade_spec
+import lights_spec
+import mis_cases as MC
+import mis_spec as spec
+import test_jade_spec as TJ
+from conftest import J, ROOT
+from jaderaytracerendering_amd import _abi, host as H
+
+F32 = np.float32
+DEBUG_LIB = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "libjade_hip_debug.so")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    return ctypes.CDLL(DEBUG_LIB)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. the table --
+
+def lists():
+    """{name: (tf [n, 28], emit)}: 0, 1, 2, 3 and 82 entries, and one list with every kind of entry the header tells apart."""
+    out = {"none": (lights_spec.triangles(5, 11), np.zeros(0, np.int32))}
+    for kind in ("one", "two", "three", "unequal82"):
+        out[kind] = lights_spec.emitter_list(kind)
+    tf = lights_spec.triangles(12, 12)
+    tf[:, 10:13] = np.float32([0.0, 1.0, 0.0])
+    tf[:9, 13:16] = np.float32([5, 4, 3])
+    tf[2, 13:16] = 0                       # a listed non-emitter
+    tf[3, 13:16] = 1e-4                    # a dim listed emitter: below the indirect-hit threshold
+    tf[4, 4:10] = tf[4, 1:4].tolist() * 2  # zero area
+    tf[5, 10:13] = 0                       # a zero normal
+    tf[6, 10:13] = np.float32([np.nan, 0, 1])
+    tf[7, 10:13] *= np.float32(1.7)        # a long normal is a normal
+    tf[8, 13:16] = np.float32([np.nan, 0, 0])  # a NaN channel fails `nonemissive`: weighted
+    # triangle 9 .. 11 do not emit; triangle 1 emits and is NOT listed; 0 is listed three times, 7 twice
+    tf[1, 13:16] = np.float32([9, 9, 9])
+    out["mixed"] = (tf, np.int32([0, 2, 3, 0, 4, 5, 6, 7, 8, 7, 0, 10]))
+    return out
+
+
+LISTS = lists()
+
+
+@pytest.mark.parametrize("name", sorted(LISTS))
+def test_the_modules_table_is_the_statements(lib, name):
+    tf, emit = LISTS[name]
+    light = lights_spec.table_of(lib, tf, emit) if len(emit) else None
+    m, M = spec.table(tf, emit, light)
+    got_m, got_M = spec.table_of(lib, tf, emit)
+    assert np.array_equal(got_m.astype(np.float64), m), (got_m, m)
+    assert np.array_equal(got_M, M.astype(F32)), (got_M, M)       # bit for bit: one rounding of a double both sides form alike
+    assert ((m > 0) == (M > 0)).all() or len(emit) == 0
+    w = spec.weighted(tf)
+    listed = np.isin(np.arange(len(tf)), emit)
+    assert ((m > 0) == (w & listed)).all()
+    if len(emit):
+        # M sums to the realised probability of the weighted entries
+        q = light["q_own"].astype(np.float64) / len(emit)
+        assert abs(M.sum() - q[w[emit]].sum()) <= 2.0 ** -23 * max(len(emit), 1)
+        assert m.sum() == w[emit].sum()
+    if name == "mixed":
+        assert list(m) == [3, 0, 0, 0, 0, 0, 0, 2, 1, 0, 0, 0]
+    if name == "none":
+        assert not m.any() and not M.any()
+
+
+# ------------------------------------------------------------------------------------------------------- 2. the weights sum to one --
+
+def test_the_two_code_paths_weights_sum_to_one():
+    """At random (vertex, direction, emitter): the emitter side's w_L (all mu entries' share) and the bounce side's share
+    w_B = g_B pB / (m |n.omega| sqrt(nne)), with pB formed HERE from unit vectors, sum to 1."""
+    rng = np.random.default_rng(313)
+    worst = 0.0
+    for _ in range(2000):
+        n32 = (rng.normal(size=3) * rng.choice([0.3, 1.0, 2.5])).astype(F32)
+        ne = rng.normal(size=3) * rng.choice([0.3, 1.0, 1.7])
+        A = float(rng.uniform(0.01, 5))
+        m = float(rng.integers(1, 4))
+        mu = m if rng.random() < 0.5 else float(F32(rng.uniform(1e-6, 1)))
+        l = rng.normal(size=3) * 2.0 ** rng.integers(-6, 7)
+        n = n32.astype(np.float64)
+        w_L = spec.w_emitter(n32, ne, A, m, mu, l)
+        g_B = spec.g_bounce(n32, ne, A, m, mu, l)
+        cos = abs(n @ l) / math.sqrt((n @ n) * (l @ l))
+        pB = cos / spec.PI32
+        w_B = g_B * pB / (m * cos * math.sqrt(n @ n) * math.sqrt(ne @ ne))
+        assert 0 <= w_L <= 1 and 0 <= w_B <= 1
+        worst = max(worst, abs(w_L + w_B - 1))
+    assert worst < 1e-12, worst
+
+
+def test_a_triangle_that_is_not_weighted_and_a_fallback_vertex_take_nothing():
+    ne, l = np.float64([0, -1, 0]), np.float64([0.3, 1.0, 0.2])
+    assert spec.w_emitter(F32([0, 1, 0]), ne, 1.0, 0.0, 0.0, l) == 1.0 and spec.g_bounce(F32([0, 1, 0]), ne, 1.0, 0.0, 0.0, l) == 0.0
+    for n32 in (F32([0, 0, 0]), F32([np.nan, 1, 0]), F32([np.inf, 0, 0]), F32([2.0 ** 70, 0, 0])):
+        assert spec.w_emitter(n32, ne, 1.0, 2.0, 2.0, l) == 1.0 and spec.g_bounce(n32, ne, 1.0, 2.0, 2.0, l) == 0.0
+    # dot(ne, l) = 0: PL = inf, w_L = 1, g_B = 0
+    assert spec.w_emitter(F32([0, 1, 0]), np.float64([1, 0, 0]), 1.0, 1.0, 1.0, np.float64([0, 1, 0])) == 1.0
+    assert spec.g_bounce(F32([0, 1, 0]), np.float64([1, 0, 0]), 1.0, 1.0, 1.0, np.float64([0, 1, 0])) == 0.0
+
+
+# ------------------------------------------------------------------------------------------------- 3. unbiasedness by quadrature --
+
+def lamp_over_floor(normal_scale=1.0):
+    """A jade-material floor quad (so that both f apply) under a lamp quad of side 1.2 at y = 0.7, nothing else: no occluder.
+    emit_indices = the lamp's two triangles and the first again.  The lamp's stored normals times 1.7."""
+    b = J.SceneBuilder()
+    b.add_mesh(TJ.quad(0.0, 2.0), TJ.QUAD_I, H.material(**TJ.JADE))
+    b.add_mesh(TJ.quad(0.7, 0.6, flip=True) + np.float32([0.3, 0, 0.2]), TJ.QUAD_I, H.material(**MC.BIG))
+    b.set_env_constant(0, 0, 0)
+    hs = b.build()
+    obj = hs.tri_i32()[:, 0]
+    lamp = np.flatnonzero(obj == 1)
+    hs.tri_f32()[lamp, 10:13] *= F32(1.7)
+    hs.tri_f32()[obj == 0, 10:13] *= F32(normal_scale)
+    hs.a["emit"] = np.array([lamp[0], lamp[1], lamp[0]], np.int32)
+    return hs
+
+
+def tri_points(S, e, K):
+    """The centroids of the K^2 congruent sub-triangles of triangle e: points [K^2, 3], each standing for area / K^2."""
+    p1, a, b = S.p1[e], S.p2[e] - S.p1[e], S.p3[e] - S.p1[e]
+    pts = []
+    for i in range(K):
+        for j in range(K - i):
+            pts.append(p1 + a * ((i + 1 / 3) / K) + b * ((j + 1 / 3) / K))
+            if j < K - i - 1:
+                pts.append(p1 + a * ((i + 2 / 3) / K) + b * ((j + 2 / 3) / K))
+    assert len(pts) == K * K
+    return np.array(pts)
+
+
+@pytest.mark.parametrize("one_light", [False, True], ids=["all-lights", "one-light"])
+@pytest.mark.parametrize("sss", [False, True], ids=["diffuse", "sss-diffuse"])
+def test_the_estimators_expectation_is_the_unweighted_emitter_expectation(sss, one_light):
+    """No sampling.  E_L: the expectation of the weighted emitter terms, over the entries' triangles (centroid rule on K^2 sub-triangles;
+    under one light entry i is drawn with q_own_i / nE and its term carries nE / q_own_i).  E_B: the expectation of T_B, which exists with
+    probability RR.  E_ref: the unweighted emitter expectation on the same points.
+    (a) E_B over the SAME points in area measure (d omega = |ne.l| / (|ne| |l|^3) dA, pB formed here from unit vectors): the identity
+        holds point by point, so the sums agree to rounding - 1e-10 relative.
+    (b) E_B over the hemisphere: the unit square of the cosine draw's two uniforms (bounce_spec.draw1 gives the direction, so pB du1 du2
+        is the draw's own measure), midpoint rule on N x N cells.  Its error is at most the sum over cells of cell area x the
+        integrand's oscillation in the cell, taken over the cell's corners and centre (the lamp's edge makes it first order): that sum is
+        the tolerance, computed below from the grid itself."""
+    hs = lamp_over_floor(normal_scale=2.5)
+    S = spec.Scene(hs, 0, 1 if one_light else 0)
+    floor = int(np.flatnonzero(hs.tri_i32()[:, 0] == 0)[0])
+    src = S.p1[floor] * 0.2 + S.p2[floor] * 0.45 + S.p3[floor] * 0.35
+    n, n32 = S.norm[floor], S.norm32[floor]
+    assert abs(math.sqrt(n @ n) - 2.5) < 1e-6
+    up = 1.0 if n[1] > 0 else -1.0        # the side the lamp is on: s of the cosine draw
+    f = (S.albedo[floor] if sss else S.brdf[floor]) * float(F32(1.0 / jade_spec.PI))
+    nE = len(S.emit)
+    K = 20
+    E_L, E_ref, E_B_area = np.zeros(3), np.zeros(3), np.zeros(3)
+    for i, e in enumerate(S.emit):
+        wt = nE / float(S.light_table["q_own"][i]) if one_light else 1.0
+        p_i = float(S.light_table["q_own"][i]) / nE if one_light else 1.0
+        for P in tri_points(S, e, K):
+            l = P - src
+            tr = []
+            E_L += p_i * spec.emitter_term(S, floor, src, n, f, e, l, wt, tr) / K ** 2
+            assert tr == ["mis-weighted"]
+            ll = l @ l
+            E_ref += S.emis[e] * f * abs((n @ l) * (S.norm[e] @ l)) / ll / ll * S.area(e) / K ** 2
+    for h in sorted(set(int(e) for e in S.emit)):
+        ne = S.norm[h]
+        for P in tri_points(S, h, K):
+            l = P - src
+            rl = math.sqrt(l @ l)
+            pB = abs(n @ l) / (rl * math.sqrt(n @ n)) / spec.PI32
+            domega = abs(ne @ l) / (math.sqrt(ne @ ne) * rl ** 3) * S.area(h) / K ** 2
+            E_B_area += jade_spec.RR * pB * domega * spec.bounce_term(S, floor, src, f, h, P, sss, [])
+    assert (E_B_area > 0.05 * E_ref).all() and (E_L > 0.05 * E_ref).all(), (E_L, E_B_area, E_ref)
+    rel = np.abs(E_L + E_B_area - E_ref) / E_ref
+    print(f"quadrature sss={sss} one_light={one_light}: E_L {E_L}, E_B {E_B_area}, E_ref {E_ref}, relative defect {rel.max():.3g}")
+    assert rel.max() < 1e-10
+    # (b)  vectorised: the directions are bounce_spec.draw's, the hit a Moeller-Trumbore test against the lamp's two triangles, T_B the
+    # header's formula once more; 600 cells are held to spec.bounce_term through S.hit, so the grid integrates the spec's own function
+    N = 256
+
+    def T(u1, u2):
+        u1, u2 = np.asarray(u1, F32).ravel(), np.asarray(u2, F32).ravel()
+        d, fb, _ = bounce_spec.draw(np.repeat(n32[None], len(u1), 0), np.full(len(u1), up, F32), u1, u2)
+        out = np.zeros(len(u1))
+        for h in sorted(set(int(e) for e in S.emit)):
+            e1, e2, ne = S.p2[h] - S.p1[h], S.p3[h] - S.p1[h], S.norm[h]
+            pv = np.cross(d, e2)
+            det = pv @ e1
+            with np.errstate(all="ignore"):
+                tv = src - S.p1[h]
+                a = (pv @ tv) / det
+                qv = np.cross(tv, e1)
+                b = (d * qv).sum(-1) / det
+                t = (qv @ e2) / det
+                hit = (a > 0) & (b > 0) & (a + b < 1) & (t > 0)
+                l = d * t[:, None]
+                ll = (l * l).sum(-1)
+                rl = np.sqrt(ll)
+                sne = math.sqrt(ne @ ne)
+                PL = S.mis_mu[h] * ll * rl * sne / (S.area(h) * np.abs(l @ ne))
+                pB = np.abs(l @ n) / (rl * math.sqrt(n @ n) * spec.PI32)
+                val = S.mis_m[h] * S.emis[h][1] * f[1] * (np.abs(l @ n) / rl) * sne / (PL + pB) / jade_spec.RR
+            out = np.where(hit, val, out)
+        return out
+
+    g = np.linspace(0, 1, N + 1)
+    c = (g[:-1] + g[1:]) / 2
+    corner = T(*np.meshgrid(g, g, indexing="ij")).reshape(N + 1, N + 1)
+    cu1, cu2 = np.meshgrid(c, c, indexing="ij")
+    centre = T(cu1, cu2).reshape(N, N)
+    pick = np.random.default_rng(5).integers(0, N, size=(600, 2))
+    lit = 0
+    for i, j in pick:
+        d, _, _ = bounce_spec.draw1(n32, up, F32(c[i]), F32(c[j]))
+        h, hp = S.hit(src, d, floor)
+        want = spec.bounce_term(S, floor, src, f, h, hp, sss, [])[1] if h >= 0 else 0.0
+        assert abs(centre[i, j] - want) <= 1e-9 * max(want, 1e-3), (i, j, centre[i, j], want)
+        lit += want > 0
+    assert lit > 20
+    stack = np.stack([corner[:-1, :-1], corner[1:, :-1], corner[:-1, 1:], corner[1:, 1:], centre])
+    tol = jade_spec.RR * (stack.max(0) - stack.min(0)).sum() / N ** 2
+    E_B_hemi = jade_spec.RR * centre.sum() / N ** 2
+    print(f"   hemisphere: E_B {E_B_hemi:.6g} against {E_B_area[1]:.6g}, defect {abs(E_B_hemi - E_B_area[1]) / E_B_area[1]:.3g}, "
+          f"tolerance {tol / E_B_area[1]:.3g} relative")
+    assert tol < 0.2 * E_B_area[1], "the grid resolves the integral: a factor of 2, pi or |n| in the measure would show"
+    assert abs(E_B_hemi - E_B_area[1]) <= tol
+
+
+# ----------------------------------------------------------------------------------------------------- 4. nothing to weigh --
+
+@pytest.mark.parametrize("kind", ["no_list", "dark_list"])
+def test_without_weighted_entries_the_arm_is_bounce_specs_double_for_double(kind):
+    hs = TJ.build(kind)
+    S = spec.Scene(hs)
+    Sb = bounce_spec.Scene(hs)
+    assert not S.mis_m.any()
+    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
+    n = 0
+    for y in range(12):
+        for x in range(12):
+            tr = []
+            a = spec.sample(S, x, y, 12, 12, eye, cam, 1, tr)
+            b = bounce_spec.sample(Sb, x, y, 12, 12, eye, cam, 1)
+            assert np.array_equal(a, b), (x, y, a, b)
+            assert not any(t in ("mis-weighted", "mis-bounce-lit", "mis-sss-bounce-lit") for t in tr)
+            n += "cos-indirect" in tr
+    assert n > 50
+
+
+# ------------------------------------------------------------------------------------------------------------ 5. the need tables --
+
+@pytest.mark.parametrize("case", sorted(MC.CASES))
+def test_the_scenes_reach_what_the_device_tests_demand(case):
+    """The arm alone on a case's samples: at most 5 % are left out as bssrdf-coplanar (compare asserts it), `need` demands half of what
+    the arm counts for every tag it meets at least twice, and the mis-* tags the case is there for are among them."""
+    c = MC.CASES[case]
+    out = {}
+    MC.compare(None, count_only=True, out=out, **c)
+    seen = out["seen"]
+    assert {k: v // 2 for k, v in seen.items() if v >= 2} == c["need"], {k: v // 2 for k, v in sorted(seen.items())}
+    if case == "one_entry":
+        assert {"mis-weighted", "mis-bounce-lit", "mis-bounce-unlisted"} <= set(c["need"])
+    else:
+        assert {"mis-weighted", "mis-bounce-lit", "mis-sss-bounce-lit"} <= set(c["need"])
+    if case == "big_lamp":
+        assert seen["mis-bounce-lit"] >= 36 and seen["mis-sss-bounce-lit"] >= 24
+    if case == "long_normals":
+        assert "cos-nonunit" in c["need"]
