@@ -649,6 +649,18 @@ int jade_debug_prepare_scene_host(const jade_scene_desc* d, int32_t wide_mode, c
 int64_t jade_debug_ray_record_cap_host(uint64_t slots, int32_t enabled, int64_t hook) { return (int64_t)ray_record_cap((size_t)slots, enabled != 0, hook); }
 uint32_t jade_debug_trace_chunk_host(uint32_t n_rays, uint64_t waves, uint32_t hook) { return trace_chunk_for(n_rays, waves, hook); }
 
+// What jade_render_begin makes of a render's settings (shade_mode_for, jade_runtime.h; tests/test_shade_modes_cpu.py): JADE_OK and the mode's
+// bits in *mode, or the refusal's code - returned, with its text in jade_last_error() - and *mode untouched.  No HIP call.
+int jade_debug_shade_mode_host(int32_t env_importance, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                               uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_importance != 0, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why)) return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
 // The rows jade_debug_exit_search runs: every obj_idx[i] names an object and every u[i] lies in [0, 1] (a NaN does not).  exit_search
 // forms its table cell from u x Gn: a row outside that range would read past the object's table - a wild read on a device, which no
 // assertion there could catch - so the rows are refused here, on the host, before anything is launched.  No HIP call.

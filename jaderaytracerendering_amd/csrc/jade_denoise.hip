@@ -382,10 +382,10 @@ static int dn_guides(jade_scene* s, int G) {
   uint32_t* mirrors = s->b_dn_mirrors.as<uint32_t>();
   const float inv_g = (float)(1.0 / (double)G);
   for (int smp = 0; smp < G && n_in; ++smp) {
-    if (s->sh_on)
+    if (shutter_on(s))
       hipLaunchKernelGGL(k_guide_camera_shutter, dim3(dn_grid(n_in)), dim3(JADE_DN_BLOCK), 0, s->stream, g, s->rc, s->ps.lens_k, s->b_tiles.as<int32_t>(),
                          s->b_dn_list.as<uint32_t>(), n_in, (uint32_t)smp, state, mirrors, s->sh);
-    else if (s->rc.lens_radius > 0.0f)
+    else if (lens_on(s))
       hipLaunchKernelGGL(k_guide_camera_lens, dim3(dn_grid(n_in)), dim3(JADE_DN_BLOCK), 0, s->stream, g, s->rc, s->ps.lens_k, s->b_tiles.as<int32_t>(),
                          s->b_dn_list.as<uint32_t>(), n_in, (uint32_t)smp, state, mirrors);
     else

@@ -20,6 +20,9 @@
 //   k_resolve       adds the partial sums; mean, ACES, gamma, BGR8 pack (PathTrace.cu:1457-1473)
 //   k_arm / k_shade_lean  list the records with work / shade light samples over all records: the schedules without the
 //                   fused pass (flushes, JADE_FUSED=0)
+//   k_shade_mode<M> / k_shade_lean_mode<M>  k_shade / k_shade_lean of a non-parity render mode M (ShadeMode, jade_runtime.h: environment
+//                   importance, lens, shutter, one-light, cosine bounces, MIS), one instantiation per built mode; k_shade, k_shade_binned
+//                   and k_shade_lean themselves are mode 0, the parity shading.  shade_launcher picks by the render's mode
 //
 // shade/trace alternate until a shade pass emits nothing (every path record has
 // finished its samples), or until so few are active that the step hands them to the
@@ -211,16 +214,16 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // the sky and pure mirrors: it hands every other record to the full kernel through `defer`
 // (either untouched, or parked at ST_VERTEX with its path state stored).  Same statements either
 // way: the lean paths are the shared helpers consume_mirror / begin_bounce_lean / bounce_mirror.
-// LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the k_shade*_lens kernels only)
+// LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the kernels of a mode with SM_LENS only)
 // SHUTTER: the camera ray leaves the pose of a time drawn within the exposure, through a lens or not (include/jade_bvh.h, "The shutter,
-// stated"; non-parity; the k_shade*_shutter kernels only, which pass their ShutterConst as H)
+// stated"; non-parity; the kernels of a mode with SM_SHUTTER only, which pass their ShutterConst as H)
 // LIGHTS: one emitter per sampling vertex, drawn from the table `lights` (include/jade_bvh.h, "The lights, stated"; non-parity; the
-// k_shade_lights* kernels only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
+// kernels of a mode with SM_LIGHTS only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
 // COSINE: the environment and indirect rays of a sampling vertex are drawn with pdf cos / pi about the normal (include/jade_bvh.h, "The bounce,
-// stated"; non-parity; the k_shade_cos* kernels only).  Nothing of it travels with the record.
+// stated"; non-parity; the kernels of a mode with SM_COSINE only).  Nothing of it travels with the record.
 // MIS: the emitter rays and the indirect ray weighed against each other (include/jade_bvh.h, "The direct light, stated"; non-parity; the
-// k_shade_cos_mis* kernels only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>  // ENVIS: environment rays by importance (non-parity; k_shade_envis only)
+// kernels of a mode with SM_MIS only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
                                                     const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr) {
@@ -545,6 +548,7 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
+// The flags are shade_record's: k_shade passes none, k_shade_mode<M> those of its mode (JADE_MODE_FLAGS).
 template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
@@ -577,106 +581,23 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(De
                                                uint32_t stop_below) {
   shade_kernel_body<false>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
 }
-// ... with jade_render_params.env_sampling = JADE_ENV_IMPORTANCE (non-parity): the one kernel that carries that code
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+// ... and every non-parity mode (ShadeMode, jade_runtime.h): one kernel per built mode M, instantiated where it is launched
+// (launch_full).  The trailing arguments X are those the mode needs, each the last: none for the pinhole and the lens; the shutter's
+// constants (ShutterConst, by value) under SM_SHUTTER; the alias table over the scene's emitter entries (`lights`; read under SM_LIGHTS
+// only) under SM_LIGHTS or SM_COSINE; that and the per-triangle table {m, M} (mis_table, jade_scene_prep.hip) under SM_MIS.
+// JADE_MODE_FLAGS: shade_record's / shade_kernel_body's template flags of mode M.
+#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0
+template <uint32_t M, class... X>
+__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below) {
-  shade_kernel_body<true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
-}
-// ... and under a thin lens (jade_scene_set_lens, non-parity): the kernels that carry the lens ray, with either environment sampling
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below) {
-  shade_kernel_body<false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_envis_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below) {
-  shade_kernel_body<true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
-}
-// ... and under a shutter (jade_scene_set_shutter, non-parity), with a lens or without: the shutter's constants are one more argument, the last
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, ShutterConst H) {
-  shade_kernel_body<false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &H);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_envis_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, ShutterConst H) {
-  shade_kernel_body<true, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &H);
-}
-// ... and with one emitter per vertex (jade_scene_set_light_sampling = JADE_LIGHTS_ONE, non-parity), under either environment sampling: the
-// two kernels that carry that code.  The alias table over the scene's emitter entries is one more argument, the last.
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<true, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-// ... and with cosine-weighted bounce sampling (jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE, non-parity), under either environment
-// sampling and either light sampling: the four kernels that carry that code.  All take k_shade_lights' arguments; `lights` is read by
-// the *_lights* two only.
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<false, false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<true, false, false, false, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights) {
-  shade_kernel_body<true, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights);
-}
-// ... and with multiple importance sampling of the emitters on top of the cosine bounce (jade_scene_set_direct_sampling = JADE_DIRECT_MIS,
-// non-parity): the four kernels that carry that code.  All take the k_shade_cos* arguments and the per-triangle table {m, M} (mis_table,
-// jade_scene_prep.hip) as one more, the last.
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
-  shade_kernel_body<false, false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
-  shade_kernel_body<true, false, false, false, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_lights(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
-  shade_kernel_body<false, false, false, true, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
-}
-__global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_cos_mis_lights_envis(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const uint4* lights, const float2* mis) {
-  shade_kernel_body<true, false, false, true, true, true>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis);
+                                               uint32_t stop_below, X... x) {
+  if constexpr ((M & SM_SHUTTER) != 0)  // x: the constants; the body takes H, lights, mis
+    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &x...);
+  else if constexpr (sizeof...(X) != 0)  // x: lights, or lights and mis
+    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, x...);
+  else
+    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -964,30 +885,19 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean(DevScene S, Path
   shade_record<true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
-// ... under a thin lens: the same kernel with the lens ray in its camera arm
-__global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_lens(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
+// ... under a thin lens (M = SM_LENS) or a shutter (M = SM_SHUTTER; X: its constants, the last argument): the same kernel with that ray in
+// its camera arm.  The other bits of a mode mean nothing to it: what they change, it hands over (launch_lean).
+template <uint32_t M, class... X>
+__global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                                       uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
-                                                                      QueueCtl* qc, DevCounters* ctr) {
+                                                                      QueueCtl* qc, DevCounters* ctr, X... x) {
   const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   ShadeCtx c;
   c.n_emit_rays = 0;
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<true, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
-  shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
-}
-// ... under a shutter: the same kernel with the shutter ray in its camera arm
-__global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_shutter(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
-                                                                         uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
-                                                                         QueueCtl* qc, DevCounters* ctr, ShutterConst H) {
-  const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-  ShadeCtx c;
-  c.n_emit_rays = 0;
-  c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
-  uint32_t st;
-  bool defer;
-  shade_record<true, false, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer, &H);
+  shade_record<true, false, (M & SM_LENS) != 0, (M & SM_SHUTTER) != 0>(S, P, R, tile_ids, target_spp, p, c, st, defer, &x...);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 
@@ -2348,22 +2258,14 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
   if (rp->env_sampling == JADE_ENV_IMPORTANCE && !env_importance_fits(s->dev.env_w, s->dev.env_h))
     return jade_fail(JADE_ERR_UNSUPPORTED, "env_sampling: JADE_ENV_IMPORTANCE takes environment maps of at most 2^24 texels (JADE_ENV_IMPORTANCE_MAX_TEXELS)");
-  const bool lights_one = s->light_sampling == JADE_LIGHTS_ONE;
-  if (lights_one && !light_sampling_fits(s->n_emit))
+  if (s->light_sampling == JADE_LIGHTS_ONE && !light_sampling_fits(s->n_emit))
     return jade_fail(JADE_ERR_UNSUPPORTED, "light sampling: JADE_LIGHTS_ONE takes at most 2^24 emitter entries (JADE_LIGHTS_ONE_MAX_ENTRIES)");
-  if (lights_one && (s->lens.aperture_radius > 0.0f || s->shutter_set))
-    return jade_fail(JADE_ERR_UNSUPPORTED, std::string("light sampling: JADE_LIGHTS_ONE (jade_scene_set_light_sampling) does not run together with ") +
-                                               (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
-                                               " yet: those kernels are not built");
-  const bool cosine = s->bounce_sampling == JADE_BOUNCE_COSINE;
-  if (cosine && (s->lens.aperture_radius > 0.0f || s->shutter_set))
-    return jade_fail(JADE_ERR_UNSUPPORTED, std::string("bounce sampling: JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling) does not run together with ") +
-                                               (s->lens.aperture_radius > 0.0f ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") +
-                                               " yet: those kernels are not built");
-  const bool mis = s->direct_sampling == JADE_DIRECT_MIS;
-  if (mis && !cosine)
-    return jade_fail(JADE_ERR_UNSUPPORTED, "direct sampling: JADE_DIRECT_MIS (jade_scene_set_direct_sampling) weighs the emitter rays against the cosine bounce "
-                                           "and needs JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling)");
+  // the scene's settings as they are now make the render's mode, if that mode is built (shade_mode_for, jade_runtime.h)
+  uint32_t mode = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(rp->env_sampling == JADE_ENV_IMPORTANCE, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
+                                    s->direct_sampling, &mode, &why))
+    return jade_fail(rc, why);
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
@@ -2371,7 +2273,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
     for (int x = 0; x < tx; ++x)
       if ((x + y) % rp->tile_nranks == rp->tile_rank) s->tile_ids.push_back(y * tx + x);
   // the record's layout: a shadow slot per emitter entry - or one for the entry drawn (JADE_LIGHTS_ONE) -, the environment ray's, the indirect ray's
-  const int nslots = (lights_one ? std::min(s->n_emit, 1) : s->n_emit) + 2;
+  const int nslots = ((mode & SM_LIGHTS) ? std::min(s->n_emit, 1) : s->n_emit) + 2;
   const int64_t npx64 = (int64_t)s->tile_ids.size() * 256;
   // Records per pixel: as many paths in flight as JADE_RECORD_MEMORY of the free device memory holds (the
   // partial sums come out of the same share), whatever the image share of this GPU: more records = fewer,
@@ -2432,9 +2334,9 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->tile_n.clear();
   s->adaptive_done = false;
   s->dn_carried = jade_stats{};
-  s->lights_on = lights_one;  // the scene's light sampling as it is now: the render keeps it, like its lens
-  s->cosine_on = cosine;      // ... and its bounce sampling
-  s->mis_on = mis;            // ... and its direct sampling
+  // ... its mode, and with it its shutter: the constants of the statement, one float subtraction each
+  s->mode = mode;
+  s->sh = (mode & SM_SHUTTER) ? shutter_const(rp->eye, rp->camera, s->shutter.eye_close, s->shutter.camera_close, s->shutter.t_open, s->shutter.t_close) : ShutterConst{};
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
@@ -2442,9 +2344,6 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   s->ps.env_sampling = rp->env_sampling == JADE_ENV_IMPORTANCE ? 1u : 0u;
   memcpy(s->ps.eye, rp->eye, sizeof s->ps.eye);
   s->ps.lens_k = lens_k;  // (setup_state wrote the record layout into s->ps)
-  // ... and its shutter: the constants of the statement, one float subtraction each
-  s->sh_on = s->shutter_set;
-  s->sh = s->sh_on ? shutter_const(rp->eye, rp->camera, s->shutter.eye_close, s->shutter.camera_close, s->shutter.t_open, s->shutter.t_close) : ShutterConst{};
   HIP_TRY(upload(s->b_tiles, s->tile_ids.data(), s->tile_ids.size(), s->stream));
   HIP_TRY(hipMemsetAsync(s->b_ctr.p, 0, sizeof(DevCounters) * JADE_CTR_SHARDS, s->stream));
   hipLaunchKernelGGL(k_init, dim3((unsigned)((npix64 + 255) / 256)), dim3(256), 0, s->stream, s->ps);
@@ -2476,15 +2375,61 @@ static hipError_t sum_counters(jade_scene* s, DevCounters* out) {
 
 // ---- run_passes: the schedule of one step / flush ----
 
+// The shade kernels of a mode as the passes launch them: `full` over a list (launch_shade), `lean` over all records, handing over to
+// heavy_out / qc->heavy (shade_pass).  One per built mode: shade_launcher.
+struct ShadeLaunch {
+  void (*full)(jade_scene* s, uint32_t target_spp, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
+               const QueueCtl* prev, uint32_t stop_below);
+  void (*lean)(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc);
+};
+// the kernel that runs mode M: its own, but the shutter kernels handle "with a lens" themselves (R.lens_radius)
+static constexpr uint32_t shade_kernel_mode(uint32_t M) { return (M & SM_SHUTTER) ? M & ~(uint32_t)SM_LENS : M; }
+// the trailing arguments the kernels of mode K take (k_shade_mode), formed from the scene and handed to f
+template <uint32_t K, class F>
+static void with_mode_args(const jade_scene* s, F&& f) {
+  if constexpr ((K & SM_MIS) != 0) f((const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
+  else if constexpr ((K & (SM_LIGHTS | SM_COSINE)) != 0) f((const uint4*)s->b_light_alias.as<uint4>());
+  else if constexpr ((K & SM_SHUTTER) != 0) f(s->sh);
+  else f();
+}
+template <uint32_t M>
+static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next,
+                        QueueCtl* ctl, const QueueCtl* prev, uint32_t stop_below) {
+  constexpr uint32_t K = shade_kernel_mode(M);
+  auto go = [&](auto kernel, auto... x) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), target_spp, list, n, n_dev,
+                       next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, x...);
+  };
+  // the parity mode: k_shade, or - JADE_SHADE_BINNED - with the records dealt by branch through LDS (k_shade_binned), the one mode with that form
+  if constexpr (K == 0) go(s->tun.shade_binned ? k_shade_binned : k_shade);
+  else with_mode_args<K>(s, [&](auto... x) { go(k_shade_mode<K, decltype(x)...>, x...); });
+}
+template <uint32_t M>
+static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER);  // (the camera arm is all of a mode the lean kernel carries)
+  auto go = [&](auto kernel, auto... x) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
+                       s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), x...);
+  };
+  if constexpr (K == 0) go(k_shade_lean);
+  else with_mode_args<K>(s, [&](auto... x) { go(k_shade_lean_mode<K, decltype(x)...>, x...); });
+}
+// The lookup: a row per mode of JADE_SHADE_MODES_BUILT (jade_runtime.h) - the list jade_render_begin accepts from - and no other.
+static const ShadeLaunch* shade_launcher(uint32_t mode) {
+  switch (mode) {
+#define JADE_X(m) case (m): { static const ShadeLaunch l{launch_full<(m)>, launch_lean<(m)>}; return &l; }
+    JADE_SHADE_MODES_BUILT(JADE_X)
+#undef JADE_X
+  }
+  return nullptr;
+}
+
 // The per-call state of run_passes.  Its pieces below each do one thing to it; every one queues its work on s->stream in the order written.
 struct PassRun {
   jade_scene* s;
   uint32_t target_spp;
   QueueCtl* qc;                       // s->b_ctl: entry 0 for passes the host follows, the ring for a batch
-  decltype(&k_shade) shade_kernel;    // k_shade, or k_shade_binned / k_shade_envis (run_passes)
-  decltype(&k_shade_shutter) shade_kernel_shutter = nullptr;  // under a shutter: the kernel launched instead, with s->sh as its last argument
-  decltype(&k_shade_lights) shade_kernel_lights = nullptr;    // JADE_LIGHTS_ONE or JADE_BOUNCE_COSINE: the kernel launched instead, with the emitters' alias table as its last argument
-  decltype(&k_shade_cos_mis) shade_kernel_mis = nullptr;      // JADE_DIRECT_MIS: the kernel launched instead, with the alias table and the per-triangle table {m, M} as its last arguments
+  const ShadeLaunch* shade;           // the shade kernels of the render's mode (shade_launcher)
   bool batching, tail_ok;
   uint32_t tail_max;                  // active records at or below which k_tail finishes the list
   uint32_t carry_below = 0;           // ... and below which the step leaves them to the next one (0: never)
@@ -2529,7 +2474,7 @@ void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, Queu
   // the render's LAYOUT, which under JADE_LIGHTS_ONE is not the length of the scene's list (the single-slot callers - the guide pass,
   // jade_trace_rays - ask about slot 0 alone, which reads the same against either count)
   DevScene S = s->dev;
-  if (s->lights_on) S.n_emit = std::min(s->n_emit, 1);
+  if (one_light_on(s)) S.n_emit = std::min(s->n_emit, 1);
   hipLaunchKernelGGL(wide ? k_trace_wide : k_trace, dim3((unsigned)(wide ? s->trace_blocks_wide : s->trace_blocks)), dim3(JADE_TRACE_BLOCK), 0, s->stream,
                      S, P, queue, qc, spill, ctr, trace_chunk(s, n_rays));
 }
@@ -2551,25 +2496,11 @@ static int launch_arm(jade_scene* s, uint32_t target_spp, QueueCtl* ctl, size_t 
   return JADE_OK;
 }
 
-// the chosen shade kernel over `list`: n entries, or - n_dev not null - as many as the device counted there; the records it leaves
+// the mode's shade kernel over `list`: n entries, or - n_dev not null - as many as the device counted there; the records it leaves
 // active go to `next` (nullable)
 static void launch_shade(const PassRun& r, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next, QueueCtl* ctl,
                          const QueueCtl* prev, uint32_t stop_below) {
-  jade_scene* s = r.s;
-  if (r.shade_kernel_mis)
-    hipLaunchKernelGGL(r.shade_kernel_mis, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
-                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below,
-                       (const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
-  else if (r.shade_kernel_lights)
-    hipLaunchKernelGGL(r.shade_kernel_lights, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
-                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below,
-                       (const uint4*)s->b_light_alias.as<uint4>());
-  else if (r.shade_kernel_shutter)
-    hipLaunchKernelGGL(r.shade_kernel_shutter, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp,
-                       list, n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, s->sh);
-  else
-    hipLaunchKernelGGL(r.shade_kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, list,
-                       n, n_dev, next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below);
+  r.shade->full(r.s, r.target_spp, blocks, list, n, n_dev, next, ctl, prev, stop_below);
 }
 
 // a finished k_trace launch, timed by the events (a, b)
@@ -2587,14 +2518,11 @@ static int account_pending_trace(PassRun& r) {
   return account_trace(r, r.ev(PassRun::TA), r.ev(PassRun::TB));
 }
 
-// A render under a thin lens (jade_scene_set_lens; taken by jade_render_begin) runs the lens kernels: k_shade_lean_lens + k_shade_lens /
-// k_shade_envis_lens + k_trace, the schedule JADE_FUSED=0 JADE_TAIL=0 gives the pinhole.  k_light, k_light_packet, k_tail and
+// A render under a thin lens (jade_scene_set_lens; taken by jade_render_begin) runs the lens kernels: k_shade_lean_mode<SM_LENS> +
+// k_shade_mode<SM_LENS | ...> + k_trace, the schedule JADE_FUSED=0 JADE_TAIL=0 gives the pinhole.  k_light, k_light_packet, k_tail and
 // k_shade_binned have no lens form, so JADE_FUSED, JADE_LIGHT_PACKET, JADE_TAIL and JADE_SHADE_BINNED have no effect there.
 // A render under a shutter (jade_scene_set_shutter) runs the same schedule with the shutter kernels, which handle "with a lens" and "without"
-// themselves.  What the schedule asks is own_origin: the camera ray has an origin of its own, stored per record.
-static bool lens_on(const jade_scene* s) { return s->rc.lens_radius > 0.0f; }
-static bool shutter_on(const jade_scene* s) { return s->sh_on; }
-static bool own_origin(const jade_scene* s) { return lens_on(s) || shutter_on(s); }
+// themselves.  What the schedule asks is own_origin (jade_runtime.h).
 static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s); }
 
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
@@ -2780,14 +2708,7 @@ static int shade_pass(PassRun& r, bool lean_mode) {
     r.cur = 0;
   } else if (lean_mode) {
     // b_active[1] carries the hand-over list; no active list is kept in this mode
-    if (shutter_on(s))
-      hipLaunchKernelGGL(k_shade_lean_shutter, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream,
-                         s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(), s->b_queue.as<uint32_t>(), qc,
-                         s->b_ctr.as<DevCounters>(), s->sh);
-    else
-      hipLaunchKernelGGL(lens_on(s) ? k_shade_lean_lens : k_shade_lean, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0,
-                         s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), r.target_spp, s->b_active[1].as<uint32_t>(),
-                         s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>());
+    r.shade->lean(s, r.target_spp, s->b_active[1].as<uint32_t>(), qc);
     if (log_passes) HIP_TRY(hipEventRecord(r.ev(PassRun::SM), s->stream));
     // only a record that was active can be handed over: n_active bounds the grid, the count stays on the device
     launch_shade(r, nb, s->b_active[1].as<uint32_t>(), 0u, &qc->heavy, nullptr, qc, nullptr, 0u);
@@ -2902,21 +2823,10 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   s->tail_pending = false;  // whatever an earlier step left is part of this call's work
   if (int rc = arm_step(r, from_spp)) return rc;
   r.carry_below = carry_threshold(s, may_carry, r.n_active);
-  // k_shade with the records dealt by branch through LDS (k_shade_binned), unless switched off - or the render draws its
-  // environment rays by importance: a bounce may then emit no ray at all and is folded in on the spot, which the binned form does not do
-  r.shade_kernel = s->ps.env_sampling ? k_shade_envis : s->tun.shade_binned ? k_shade_binned : k_shade;
-  if (lens_on(s)) r.shade_kernel = s->ps.env_sampling ? k_shade_envis_lens : k_shade_lens;
-  if (shutter_on(s)) r.shade_kernel_shutter = s->ps.env_sampling ? k_shade_envis_shutter : k_shade_shutter;
-  // one emitter per vertex (jade_render_begin refuses it under a lens or a shutter): its own kernels, JADE_SHADE_BINNED has no effect
-  if (s->lights_on) r.shade_kernel_lights = s->ps.env_sampling ? k_shade_lights_envis : k_shade_lights;
-  // cosine-weighted bounces (refused under a lens or a shutter likewise): its own kernels under either light sampling, with the same arguments
-  if (s->cosine_on)
-    r.shade_kernel_lights = s->lights_on ? (s->ps.env_sampling ? k_shade_cos_lights_envis : k_shade_cos_lights) : (s->ps.env_sampling ? k_shade_cos_envis : k_shade_cos);
-  // ... and with the emitters' two techniques weighed (jade_render_begin: under cosine bounces only): its own kernels, one more argument
-  if (s->mis_on)
-    r.shade_kernel_mis = s->lights_on ? (s->ps.env_sampling ? k_shade_cos_mis_lights_envis : k_shade_cos_mis_lights) : (s->ps.env_sampling ? k_shade_cos_mis_envis : k_shade_cos_mis);
+  r.shade = shade_launcher(s->mode);
+  if (!r.shade) return jade_fail(JADE_ERR_DEVICE, "no shade kernel for the render's mode (internal error: jade_render_begin accepts built modes only)");
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && !s->ps.env_sampling && !own_origin(s) && !s->lights_on && !s->cosine_on;  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && parity_shading(s);  // (k_tail shades with the parity code only)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
   r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);

@@ -130,18 +130,15 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->shutter_set != scenes[0]->shutter_set || memcmp(&scenes[i]->shutter, &scenes[0]->shutter, sizeof(jade_shutter_params)) != 0)
       return jade_fail(JADE_ERR_INVALID, "the scenes carry different shutters (jade_scene_set_shutter): scene " + std::to_string(i) + " against scene 0");
-  // ... and with the same light sampling (jade_scene_set_light_sampling)
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->light_sampling != scenes[0]->light_sampling)
-      return jade_fail(JADE_ERR_INVALID, "the scenes carry different light sampling modes (jade_scene_set_light_sampling): scene " + std::to_string(i) + " against scene 0");
-  // ... and with the same bounce sampling (jade_scene_set_bounce_sampling)
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->bounce_sampling != scenes[0]->bounce_sampling)
-      return jade_fail(JADE_ERR_INVALID, "the scenes carry different bounce sampling modes (jade_scene_set_bounce_sampling): scene " + std::to_string(i) + " against scene 0");
-  // ... and with the same direct sampling (jade_scene_set_direct_sampling)
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->direct_sampling != scenes[0]->direct_sampling)
-      return jade_fail(JADE_ERR_INVALID, "the scenes carry different direct sampling modes (jade_scene_set_direct_sampling): scene " + std::to_string(i) + " against scene 0");
+  // ... and with the same light, bounce and direct sampling
+  static const struct { int jade_scene::*mode; const char* setter; const char* noun; } kSampling[] = {
+      {&jade_scene::light_sampling, "jade_scene_set_light_sampling", "light"},
+      {&jade_scene::bounce_sampling, "jade_scene_set_bounce_sampling", "bounce"},
+      {&jade_scene::direct_sampling, "jade_scene_set_direct_sampling", "direct"}};
+  for (const auto& k : kSampling)
+    for (int i = 1; i < ndev; ++i)
+      if (scenes[i]->*k.mode != scenes[0]->*k.mode)
+        return jade_fail(JADE_ERR_INVALID, std::string("the scenes carry different ") + k.noun + " sampling modes (" + k.setter + "): scene " + std::to_string(i) + " against scene 0");
   // 1. every device renders its share (one host thread each) and resolves it into a device buffer
   std::vector<int> rcs(ndev, JADE_OK);
   std::vector<std::string> msgs(ndev);

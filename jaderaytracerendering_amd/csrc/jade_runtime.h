@@ -195,6 +195,54 @@ static inline uint32_t trace_chunk_for(uint32_t n_rays, uint64_t waves, uint32_t
   return (uint32_t)per * 64u;
 }
 
+// The mode of a render: which non-parity pieces its shade kernels carry, one bit each.  0 is the parity shading - the reference's
+// estimator through the pinhole, the only mode k_tail, k_shade_binned and the oracle know.
+enum ShadeMode : uint32_t {
+  SM_ENVIS = 1u,     // jade_render_params.env_sampling = JADE_ENV_IMPORTANCE
+  SM_LENS = 2u,      // jade_scene_set_lens with a radius > 0
+  SM_SHUTTER = 4u,   // jade_scene_set_shutter
+  SM_LIGHTS = 8u,    // jade_scene_set_light_sampling = JADE_LIGHTS_ONE
+  SM_COSINE = 16u,   // jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE
+  SM_MIS = 32u,      // jade_scene_set_direct_sampling = JADE_DIRECT_MIS
+};
+// THE list of the modes that are built, written once: X(m) for each, under either environment sampling.  shade_mode_built (so what
+// jade_render_begin accepts) and shade_launcher (jade_hip.hip: the kernel a render's passes launch) are both made from it, so a mode
+// cannot be accepted without a kernel or have a kernel that is never reached.  Adding a render mode: DESIGN.md 3.14.
+#define JADE_SHADE_MODES_BUILT(X) \
+  JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS)
+#define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS)
+static inline bool shade_mode_built(uint32_t mode) {
+#define JADE_X(m) if (mode == (m)) return true;
+  JADE_SHADE_MODES_BUILT(JADE_X)
+#undef JADE_X
+  return false;
+}
+// What jade_render_begin makes of the settings a render is asked with: JADE_OK and its mode, or the refusal's code and text.  A mode
+// is accepted if and only if it is in the list above; the texts say why the others are not, first reason first: one-light sampling's
+// own check, then the cosine bounce's, then what MIS needs.  Pure: no HIP call, no scene (tests/test_shade_modes_cpu.py).
+static inline int shade_mode_for(bool env_importance, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
+                                 std::string* why) {
+  const uint32_t m = (env_importance ? SM_ENVIS : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
+                     (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u);
+  if (shade_mode_built(m)) {
+    *mode = m;
+    return JADE_OK;
+  }
+  const std::string camera = std::string(lens ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") + " yet: those kernels are not built";
+  if ((m & SM_LIGHTS) && (m & (SM_LENS | SM_SHUTTER)))
+    *why = "light sampling: JADE_LIGHTS_ONE (jade_scene_set_light_sampling) does not run together with " + camera;
+  else if ((m & SM_COSINE) && (m & (SM_LENS | SM_SHUTTER)))
+    *why = "bounce sampling: JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling) does not run together with " + camera;
+  else if ((m & SM_MIS) && !(m & SM_COSINE))
+    *why = "direct sampling: JADE_DIRECT_MIS (jade_scene_set_direct_sampling) weighs the emitter rays against the cosine bounce "
+           "and needs JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling)";
+  else
+    *why = "this combination of render modes is not built";
+  return JADE_ERR_UNSUPPORTED;
+}
+
 struct jade_scene {
   int device = 0;
   Tunables tun;
@@ -205,17 +253,17 @@ struct jade_scene {
   int n_emit = 0;
   int n_objects = 0;
   int bvh_depth = 0;
-  jade_lens_params lens{};    // jade_scene_set_lens: what the next jade_render_begin takes (the render in progress keeps its own: rc.lens_radius, ps.lens_k)
-  jade_shutter_params shutter{};  // jade_scene_set_shutter, if shutter_set: what the next jade_render_begin takes ...
+  // what the next jade_render_begin takes (the setters' state; jade_render_multi compares it between scenes) ...
+  jade_lens_params lens{};    // jade_scene_set_lens
+  jade_shutter_params shutter{};  // jade_scene_set_shutter, if shutter_set
   bool shutter_set = false;
-  ShutterConst sh{};          // ... and what the render in progress took: the argument of the shutter kernels, if sh_on
-  bool sh_on = false;
-  int light_sampling = JADE_LIGHTS_ALL;  // jade_scene_set_light_sampling: what the next jade_render_begin takes ...
-  bool lights_on = false;     // ... and what the render in progress took: JADE_LIGHTS_ONE (its records have min(n_emit, 1) + 2 slots)
-  int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling: what the next jade_render_begin takes ...
-  bool cosine_on = false;     // ... and what the render in progress took: JADE_BOUNCE_COSINE (the k_shade_cos* kernels; same records, same rays)
-  int direct_sampling = JADE_DIRECT_RAYS;  // jade_scene_set_direct_sampling: what the next jade_render_begin takes ...
-  bool mis_on = false;        // ... and what the render in progress took: JADE_DIRECT_MIS (the k_shade_cos_mis* kernels; cosine's records, rays and counters)
+  int light_sampling = JADE_LIGHTS_ALL;       // jade_scene_set_light_sampling
+  int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling
+  int direct_sampling = JADE_DIRECT_RAYS;     // jade_scene_set_direct_sampling
+  // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
+  // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
+  uint32_t mode = 0;
+  ShutterConst sh{};
   bool sort_rays = false;     // the ray queue is ordered before every k_trace launch (Tunables.sort_mode; then passes are host-followed)
   // render state
   bool have_rp = false;
@@ -270,7 +318,15 @@ struct jade_scene {
     if (stream) (void)hipStreamDestroy(stream);
   }
 };
-
+// The render in progress, asked by what its mode means to the schedule:
+static inline bool lens_on(const jade_scene* s) { return (s->mode & SM_LENS) != 0; }
+static inline bool shutter_on(const jade_scene* s) { return (s->mode & SM_SHUTTER) != 0; }
+// ... the camera ray has an origin of its own, stored per record: no k_light / k_light_packet, which have no such form
+static inline bool own_origin(const jade_scene* s) { return lens_on(s) || shutter_on(s); }
+// ... one shadow slot per record, for the entry drawn, whatever the length of the scene's emitter list (k_trace's n_emit, the record layout)
+static inline bool one_light_on(const jade_scene* s) { return (s->mode & SM_LIGHTS) != 0; }
+// ... the parity shading, the only one k_tail and k_shade_binned carry: no bit at all
+static inline bool parity_shading(const jade_scene* s) { return s->mode == 0; }
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
 struct ScenePrep {

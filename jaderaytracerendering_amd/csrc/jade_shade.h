@@ -497,10 +497,10 @@ static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx
 // The branch itself: its draws, its rays (written through px), stage / flags / n_emit_rays.  Returns false if the path ended at
 // this vertex (*l_final holds the last l_dir).  `type` is uniform over the waves k_shade runs it for.
 // ENVIS: jade_render_params.env_sampling = JADE_ENV_IMPORTANCE (compiled apart: the parity kernels carry none of its code)
-// LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h; compiled apart likewise, k_shade_lights*): ONE entry of S.emit, drawn from `lights`, in
+// LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h; compiled apart likewise, modes with SM_LIGHTS): ONE entry of S.emit, drawn from `lights`, in
 // slot 0; nL = the shadow slots of the record's layout, so the environment ray sits in slot nL and the indirect ray in slot nL + 1.
 // *light = the entry drawn: it travels with the record (the fourth word of PathState.hdr, shade_record) to consume.
-// COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"; compiled apart likewise, k_shade_cos*): the environment ray - unless
+// COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"; compiled apart likewise, modes with SM_COSINE): the environment ray - unless
 // ENVIS draws it - and the indirect ray come from cosine_dir_rng in place of sphere_dir and its flip, on the same two draws.
 template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
 static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final,
@@ -731,7 +731,7 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // refraction loop issued its next ray.
 // LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight (bounce_branch)
 // COSINE: where a ray came from cosine_dir_rng, the reference's |dot(normal, direction)| is cosine_weight - four places, nothing else
-// MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with COSINE only; compiled apart, k_shade_cos_mis*): at a diffuse or
+// MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with COSINE only; compiled apart, modes with SM_MIS): at a diffuse or
 // SSS-diffuse vertex an emitter term towards a weighted triangle is multiplied by w_L, and an indirect ray that lands on one adds T_B
 // before the vertex's scale.  `mis`: the per-triangle table {m, M}.  Rays, draws, records and counters are COSINE's.
 template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>

@@ -104,12 +104,12 @@ CASES = {
     # 570 samples, 6 left out (1.0 %): 8 bssrdf, 326 cos-env, 297 cos-indirect, 308 diffuse, 54 mirror, 8 refract, 1 refract-open, 202 sky, 19 sss
     "patchwork": dict(kind="patchwork", size=12, frames=(0, 1, 2, 3),
                       need={"bssrdf": 4, "cos-env": 163, "cos-indirect": 148, "diffuse": 154, "mirror": 27, "refract": 4, "sky": 101, "sss": 9}),
-    # JADE_LIGHTS_ONE on top (k_shade_cos_lights): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
+    # JADE_LIGHTS_ONE on top (k_shade_mode<LIGHTS|COSINE>): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
     # 219 diffuse, 116 diffuse-lit, 80 light-alias, 136 light-lit, 176 light-own, 116 light-shadowed, 15 light-side, 60 mirror, 142 sky, 34 sss, 15 sss-lit
     "two_lamps_sky": dict(kind="two_lamps", sky=True, light_sampling=ONE, size=12, frames=(0, 1, 2),
                           need={"bssrdf": 6, "bssrdf-lit": 3, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "diffuse-lit": 58, "light-alias": 40,
                                 "light-lit": 68, "light-own": 88, "light-shadowed": 58, "light-side": 7, "mirror": 30, "sky": 71, "sss": 17, "sss-lit": 7}),
-    # ... and both (k_shade_cos_lights_envis): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse,
+    # ... and both (k_shade_mode<ENVIS|LIGHTS|COSINE>): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse,
     # 118 diffuse-lit, 170 env-importance, 99 env-noenv, 87 light-alias, 138 light-lit, 180 light-own, 120 light-shadowed, 21 light-side,
     # 71 mirror, 142 sky, 45 sss, 18 sss-lit
     "two_lamps_sky_importance": dict(kind="two_lamps", sky=True, env_sampling=IMP, light_sampling=ONE, size=12, frames=(0, 1, 2),

@@ -160,24 +160,24 @@ def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_
 IMP, ONE = _abi.ENV_IMPORTANCE, _abi.LIGHTS_ONE
 CASES = {
     # the arm alone: 423 samples, 9 left out (2.1 %): 18 bssrdf, 251 cos-env, 227 cos-indirect, 221 diffuse, 64 mirror, 11 mis-bounce-lit,
-    # 4 mis-sss-bounce-lit, 3 mis-unweighted (the listed floor triangle), 211 mis-weighted, 142 sky, 40 sss            (k_shade_cos_mis)
+    # 4 mis-sss-bounce-lit, 3 mis-unweighted (the listed floor triangle), 211 mis-weighted, 142 sky, 40 sss            (k_shade_mode<COSINE|MIS>)
     "two_lamps": dict(kind="two_lamps", size=12, frames=(0, 1, 2),
                       need={"bssrdf": 9, "cos-env": 125, "cos-indirect": 113, "diffuse": 110, "mirror": 32, "mis-bounce-lit": 5,
                             "mis-sss-bounce-lit": 2, "mis-unweighted": 1, "mis-weighted": 105, "sky": 71, "sss": 20}),
-    # under one light (k_shade_cos_mis_lights; mu = M): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
+    # under one light (k_shade_mode<LIGHTS|COSINE|MIS>; mu = M): 413 samples, 19 left out (4.4 %): 13 bssrdf, 7 bssrdf-lit, 241 cos-env, 211 cos-indirect,
     # 219 diffuse, 116 diffuse-lit, 80 light-alias, 136 light-lit, 176 light-own, 116 light-shadowed, 15 light-side, 60 mirror,
     # 6 mis-bounce-lit, 2 mis-sss-bounce-lit, 130 mis-weighted, 142 sky, 34 sss, 15 sss-lit
     "two_lamps_one_light": dict(kind="two_lamps", light_sampling=ONE, size=12, frames=(0, 1, 2),
                                 need={"bssrdf": 6, "bssrdf-lit": 3, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "diffuse-lit": 58,
                                       "light-alias": 40, "light-lit": 68, "light-own": 88, "light-shadowed": 58, "light-side": 7, "mirror": 30,
                                       "mis-bounce-lit": 3, "mis-sss-bounce-lit": 1, "mis-weighted": 65, "sky": 71, "sss": 17, "sss-lit": 7}),
-    # both under JADE_ENV_IMPORTANCE with the textured sky (k_shade_cos_mis_envis): 423 samples, 9 left out (2.1 %): 14 bssrdf,
+    # both under JADE_ENV_IMPORTANCE with the textured sky (k_shade_mode<ENVIS|COSINE|MIS>): 423 samples, 9 left out (2.1 %): 14 bssrdf,
     # 226 cos-indirect, 223 diffuse, 176 env-importance, 95 env-noenv, 64 mirror, 13 mis-bounce-lit, 4 mis-sss-bounce-lit, 1 mis-unweighted,
     # 212 mis-weighted, 142 sky, 38 sss
     "two_lamps_sky_importance": dict(kind="two_lamps", sky=True, env_sampling=IMP, size=12, frames=(0, 1, 2),
                                      need={"bssrdf": 7, "cos-indirect": 113, "diffuse": 111, "env-importance": 88, "env-noenv": 47, "mirror": 32,
                                            "mis-bounce-lit": 6, "mis-sss-bounce-lit": 2, "mis-weighted": 106, "sky": 71, "sss": 19}),
-    # (k_shade_cos_mis_lights_envis): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse, 118 diffuse-lit,
+    # (k_shade_mode<ENVIS|LIGHTS|COSINE|MIS>): 418 samples, 14 left out (3.2 %): 17 bssrdf, 11 bssrdf-lit, 226 cos-indirect, 221 diffuse, 118 diffuse-lit,
     # 170 env-importance, 99 env-noenv, 87 light-alias, 138 light-lit, 180 light-own, 120 light-shadowed, 21 light-side, 71 mirror,
     # 9 mis-bounce-lit, 5 mis-sss-bounce-lit, 131 mis-weighted, 142 sky, 45 sss, 18 sss-lit
     "two_lamps_sky_importance_one_light": dict(kind="two_lamps", sky=True, env_sampling=IMP, light_sampling=ONE, size=12, frames=(0, 1, 2),

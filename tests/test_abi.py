@@ -130,7 +130,7 @@ def test_product_library_exports_only_the_boundary():
     assert "jade_debug_scene_flags" in out and "jade_debug_scene_grids" in out
     for name in ("jade_debug_fpmath", "jade_debug_sample_hdr", "jade_debug_tone_pack", "jade_debug_tone_pack_host", "jade_debug_env_alias_host",
                  "jade_debug_env_sample", "jade_debug_env_sample_rng", "jade_debug_env_importance_fits", "jade_debug_guide_tables_host",
-                 "jade_debug_prepare_scene_host", "jade_debug_ray_record_cap_host", "jade_debug_trace_chunk_host",
+                 "jade_debug_prepare_scene_host", "jade_debug_ray_record_cap_host", "jade_debug_trace_chunk_host", "jade_debug_shade_mode_host",
                  "jade_debug_exit_search_rows", "jade_debug_exit_search"):  # jade_debug_units.hip
         assert name in out, name
     assert "jade_debug_ray_record_use" in out  # jade_hip.hip

@@ -330,7 +330,7 @@ def test_records_per_pixel_and_schedules_are_one_result(hip, cos_ref, monkeypatc
 
 @pytest.mark.parametrize("envs,lights", [(_abi.ENV_IMPORTANCE, _abi.LIGHTS_ALL), (_abi.ENV_REFERENCE, _abi.LIGHTS_ONE), (_abi.ENV_IMPORTANCE, _abi.LIGHTS_ONE)])
 def test_with_the_other_estimators_on_top(hip, cos_ref, envs, lights):
-    """k_shade_cos_envis, k_shade_cos_lights, k_shade_cos_lights_envis: repeatable, finite, another frame than the mode alone and than
+    """k_shade_mode<ENVIS|COSINE>, <LIGHTS|COSINE>, <ENVIS|LIGHTS|COSINE>: repeatable, finite, another frame than the mode alone and than
     the other estimator alone, the ray classes adding up."""
     p = params(env_sampling=envs)
     a = render(hip, p, COS, lights=lights)

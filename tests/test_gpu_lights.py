@@ -508,7 +508,7 @@ def one_light_frames(hip, case, kind=None):
 def test_the_render_is_the_float64_statement_sample_for_sample(hip, case):
     """two_lamps: two lamps of unequal power, a duplicate entry and a listed non-emitter (own and alias, the side test's `continue`, lit
     and shadowed, in the diffuse, SSS-diffuse and BSSRDF branch); ..._sky and ..._sky_importance: under the textured sky in both
-    env_sampling modes - k_shade_lights_envis, four light draws before four environment draws; one_entry: nE = 1, weight exactly 1, only the
+    env_sampling modes - k_shade_mode<ENVIS|LIGHTS>, four light draws before four environment draws; one_entry: nE = 1, weight exactly 1, only the
     four-for-two draw count differs from all lights; fan: 24 entries over 3.4 orders of magnitude, weights above 100, aliases
     frequent, a lit sample with a weight above 50 must agree; dark_list: only non-emitters listed - every term is zero and the draws
     still move everything behind them.

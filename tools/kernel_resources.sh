@@ -23,9 +23,14 @@ for line in sys.stdin:
 for k, v in rows.items():
     m = re.match(r"^_Z\d+(k_[a-z_0-9]+?)(?=\d|P|$)", k)
     t = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILb([01])EE", k)  # a kernel template over one bool: k_name<0> / k_name<1>
-    if not m and not t:
+    s = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILj(\d+)E", k)  # a kernel template over the ShadeMode mask (jade_runtime.h): k_shade_mode<COSINE|MIS>
+    if not m and not t and not s:
         continue
-    name = "%s<%s>" % (t.group(1), t.group(2)) if t else m.group(1)
+    bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS")
+    if s:
+        name = "%s<%s>" % (s.group(1), "|".join(b for i, b in enumerate(bits) if int(s.group(2)) >> i & 1) or "0")
+    else:
+        name = "%s<%s>" % (t.group(1), t.group(2)) if t else m.group(1)
     print("%-16s VGPR %3d AGPR %3d SGPR %3d scratch %4d B  LDS %6d B  occupancy %d" % (name, v.get("VGPRs", -1), v.get("AGPRs", 0), v.get("TotalSGPRs", v.get("SGPRs", -1)), v.get("ScratchSize [bytes/lane]", v.get("ScratchSize", 0)), v.get("LDS Size [bytes/block]", v.get("LDS Size", 0)), v.get("Occupancy [waves/SIMD]", v.get("Occupancy", -1))))
 '
 done
