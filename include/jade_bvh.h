@@ -166,7 +166,15 @@ int jade_render_error(jade_scene* scene, float error_floor, float* out_error);
  *     w_a = exp(-|a_p - a_q|_1 / sigma_albedo)
  *     w   = h(dx) h(dy) w_l w_n w_z w_a
  *   c'_p = sum w c_q / sum w          v'_p = sum w^2 v_q / (sum w)^2
- * iterations = 0 returns the input colour bit for bit. */
+ * iterations = 0 returns the input colour bit for bit.
+ * The normal: nhat = n / |n| for every finite non-zero n, whatever its length (a normal whose squared length leaves the float range
+ * is first scaled by a power of two); nhat = 0 for n = 0, which is what "the normal is 0" means in w_n.
+ * Unusable pixels: a pixel is unusable if a channel of its c, a or n is non-finite, or its z is non-finite, or its v is non-finite
+ * or negative.  This is decided once, from the inputs.  In every pass an unusable pixel keeps its c and v bit for bit, and it is no
+ * tap of any other pixel: neither in the 5x5 sums nor in the 3x3 blur of v, which is renormalised over the in-image usable taps.
+ * The centre tap of a usable pixel is usable, so no sum is empty.  So: finite inputs give a finite output; one non-finite pixel
+ * stays one pixel, whatever the number of passes; a variance that is NaN everywhere (what jade_render_guides gives for a count that
+ * cannot be estimated) returns the input colour bit for bit. */
 typedef struct jade_denoise_params {
   int32_t iterations;    /* a-trous passes, 0..8; pass i uses a step of 2^i pixels; 0 = identity */
   int32_t guide_spp;     /* camera samples averaged into the guides, 1..64 */

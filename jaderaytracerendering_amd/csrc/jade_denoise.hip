@@ -165,19 +165,32 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits(DevScene S, PathSt
 // ------------------------------------------------------------------------------------------------------------------ filter --
 
 // One pixel's filter record from its inputs; the two pack kernels call it, so the render's path and jade_denoise_image's are the
-// same bits.  nhat = n / |n|, or 0 for the zero normal (a miss in every guide sample).
+// same bits.  nhat = n / |n|, or 0 for the zero normal (a miss in every guide sample).  Where the float sum of squares is 0,
+// subnormal or infinite, n is first scaled by the power of two that brings its largest component into [1, 2) (exact; every other
+// normal takes the plain statements).  L.w = 1 marks an unusable pixel (jade_bvh.h: a non-finite input, a negative variance):
+// k_atrous copies it and never taps it.
 static __device__ __forceinline__ void dn_pack(float r, float g, float b, float v, float ax, float ay, float az, float nx, float ny, float nz,
                                                float z, float4* A, float4* N, float4* L, size_t o) {
+  const bool usable = isfinite(r) && isfinite(g) && isfinite(b) && isfinite(ax) && isfinite(ay) && isfinite(az) && isfinite(nx) && isfinite(ny) &&
+                      isfinite(nz) && isfinite(z) && isfinite(v) && v >= 0.0f;
   float hx = 0.0f, hy = 0.0f, hz = 0.0f;
-  if (nx != 0.0f || ny != 0.0f || nz != 0.0f) {
-    const float len = sqrtf(nx * nx + ny * ny + nz * nz);
+  if (usable && (nx != 0.0f || ny != 0.0f || nz != 0.0f)) {
+    float ss = nx * nx + ny * ny + nz * nz;
+    if (!(ss >= 1.17549435e-38f && ss <= 3.40282347e+38f)) {
+      const int e = -ilogbf(fmaxf(fabsf(nx), fmaxf(fabsf(ny), fabsf(nz))));
+      nx = ldexpf(nx, e);
+      ny = ldexpf(ny, e);
+      nz = ldexpf(nz, e);
+      ss = nx * nx + ny * ny + nz * nz;
+    }
+    const float len = sqrtf(ss);
     hx = nx / len;
     hy = ny / len;
     hz = nz / len;
   }
   A[o] = make_float4(r, g, b, v);
   N[o] = make_float4(hx, hy, hz, z);
-  L[o] = make_float4(ax, ay, az, 0.0f);
+  L[o] = make_float4(ax, ay, az, usable ? 0.0f : 1.0f);
 }
 
 // The render's owned tiles (compact layout: rgb as k_resolve writes it, variance, guide sums) -> image layout
@@ -210,7 +223,12 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_atrous(const float4* __restri
   const int x = blockIdx.x * 16 + (threadIdx.x & 15), y = blockIdx.y * 16 + (threadIdx.x >> 4);
   if (x >= W || y >= H) return;
   const size_t p = (size_t)y * W + x;
-  // g_p: 3x3 (1/4, 1/2, 1/4)^2 blur of the variance over the in-image neighbours, renormalised
+  const float4 ap = Ain[p], lp = L[p];
+  if (lp.w != 0.0f) {  // unusable: colour and variance as they came in, every pass
+    Aout[p] = ap;
+    return;
+  }
+  // g_p: 3x3 (1/4, 1/2, 1/4)^2 blur of the variance over the in-image usable neighbours, renormalised
   float gs = 0.0f, gw = 0.0f;
   for (int dy = -1; dy <= 1; ++dy) {
     const int yy = y + dy;
@@ -218,13 +236,14 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_atrous(const float4* __restri
     for (int dx = -1; dx <= 1; ++dx) {
       const int xx = x + dx;
       if (xx < 0 || xx >= W) continue;
+      if (L[(size_t)yy * W + xx].w != 0.0f) continue;
       const float w = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);
       gs += w * Ain[(size_t)yy * W + xx].w;
       gw += w;
     }
   }
   const float g = gs / gw;
-  const float4 ap = Ain[p], np = N[p], lp = L[p];
+  const float4 np = N[p];
   const float lum_p = 0.3f * ap.x + 0.6f * ap.y + 0.1f * ap.z;
   const float den_l = sg.l * sqrtf(g) + 1e-10f;
   const bool pz = np.x == 0.0f && np.y == 0.0f && np.z == 0.0f;
@@ -237,7 +256,9 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_atrous(const float4* __restri
       const int xx = x + s * dx;
       if (xx < 0 || xx >= W) continue;
       const size_t q = (size_t)yy * W + xx;
-      const float4 aq = Ain[q], nq = N[q], lq = L[q];
+      const float4 lq = L[q];
+      if (lq.w != 0.0f) continue;  // an unusable pixel is no tap (skipped, not weighted by 0: 0 * inf is NaN)
+      const float4 aq = Ain[q], nq = N[q];
       const bool qz = nq.x == 0.0f && nq.y == 0.0f && nq.z == 0.0f;
       float wn;
       if (pz || qz) {

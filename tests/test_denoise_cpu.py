@@ -11,7 +11,9 @@ import pytest
 from conftest import B, ORACLE_LIB, ROOT, config_scene
 from jaderaytracerendering_amd import _abi
 
-from denoise_ref import H5, denoise
+import denoise_cases as DC
+import guide_cases as GC
+from denoise_ref import H5, denoise, unit_normals, unusable
 
 NEW = ("jade_denoise_defaults", "jade_render_guides", "jade_render_denoise", "jade_denoise_image")
 CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
@@ -75,6 +77,236 @@ def test_zero_iterations_and_constant_colour():
     const = np.broadcast_to([0.2, 0.5, 0.9], (h, w, 3))
     out, _ = denoise(const, var, alb, nrm, dep, 4, 4.0, 128.0, 0.1, 0.1)
     np.testing.assert_allclose(out, const, rtol=1e-12)
+
+
+# ------------------------------------------------------------------------------- inputs on which the filter mixes, and mutants --
+
+MUTANTS = ("blur not renormalised", "centre variance", "min in w_z", "w in v'", "h(+2) = 1/8", "tap clamped", "w_n = 1 at one zero normal",
+           "step not applied to dy")
+
+
+def _statement(rgb, var, alb, nrm, dep, iterations, sl, sn, sz, sa, mut=None, cut=None):
+    """The filter of include/jade_bvh.h once more, in float64, by index arithmetic (not denoise_ref's shifts), with one line broken
+    (`mut`) or with the pixels of the mask `cut` taken out of every sum - they are told here, not found from the inputs."""
+    c, v, a, n, z = (np.array(x, np.float64) for x in (rgb, var, alb, nrm, dep))
+    h, w = v.shape
+    use = np.ones((h, w), bool) if cut is None else ~cut
+    h5 = H5.copy()
+    if mut == "h(+2) = 1/8":
+        h5[4] = 1 / 8
+    zero = np.all(n == 0, axis=-1)
+    nh = n / np.where(zero, 1.0, np.sqrt((n * n).sum(-1)))[..., None]
+    yy, xx = np.mgrid[0:h, 0:w]
+    c0, v0 = c.copy(), v.copy()
+    for i in range(iterations):
+        s = 1 << i
+        gs, gw = np.zeros((h, w)), np.zeros((h, w))
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                qy, qx = yy + dy, xx + dx
+                inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+                qy, qx = qy.clip(0, h - 1), qx.clip(0, w - 1)
+                ok = inside & use[qy, qx]
+                k = (0.5 if dy == 0 else 0.25) * (0.5 if dx == 0 else 0.25) * ok
+                gs += k * v[qy, qx]
+                gw += k
+        g = gs if mut == "blur not renormalised" else gs / np.where(gw == 0, 1.0, gw)
+        if mut == "centre variance":
+            g = v
+        lum = 0.3 * c[..., 0] + 0.6 * c[..., 1] + 0.1 * c[..., 2]
+        sw, sc, sv = np.zeros((h, w)), np.zeros((h, w, 3)), np.zeros((h, w))
+        for dy in range(-2, 3):
+            for dx in range(-2, 3):
+                qy, qx = yy + (dy if mut == "step not applied to dy" else s * dy), xx + s * dx
+                inside = (qy >= 0) & (qy < h) & (qx >= 0) & (qx < w)
+                qy, qx = qy.clip(0, h - 1), qx.clip(0, w - 1)
+                ok = (inside | (mut == "tap clamped")) & use[qy, qx]
+                wl = np.exp(-np.abs(lum - lum[qy, qx]) / (sl * np.sqrt(g) + 1e-10))
+                one = zero ^ zero[qy, qx]
+                wn = np.where(zero & zero[qy, qx], 1.0, np.where(one, 1.0 if mut == "w_n = 1 at one zero normal" else 0.0,
+                                                                 np.maximum((nh * nh[qy, qx]).sum(-1), 0.0) ** sn))
+                zz = np.minimum(z, z[qy, qx]) if mut == "min in w_z" else np.maximum(z, z[qy, qx])
+                wz = np.exp(-np.abs(z - z[qy, qx]) / (sz * zz + 1e-10))
+                wa = np.exp(-np.abs(a - a[qy, qx]).sum(-1) / sa)
+                k = h5[dx + 2] * h5[dy + 2] * wl * wn * wz * wa * ok
+                sw += k
+                sc += k[..., None] * c[qy, qx]
+                sv += (k if mut == "w in v'" else k * k) * v[qy, qx]
+        sw = np.where(use, sw, 1.0)
+        c, v = sc / sw[..., None], sv / (sw * sw)
+        c[~use], v[~use] = c0[~use], v0[~use]
+    return c, v
+
+
+@pytest.mark.parametrize("h,w", DC.SMOOTH_SIZES)
+def test_the_second_statement_agrees_with_the_first(h, w):
+    ins = DC.case(h, w)
+    for it in (1, 3, 8):
+        with np.errstate(all="ignore"):
+            got = _statement(*ins, it, *DC.SIGMAS)[0]
+        assert DC.worst(got, DC.want(ins, it)) <= 1e-12
+
+
+@pytest.mark.parametrize("h,w", [s for s in DC.SMOOTH_SIZES if min(s) >= 16])
+def test_the_filter_mixes_on_the_smooth_cases(h, w):
+    ins = DC.case(h, w)
+    rgb = ins[0].astype(np.float64)
+    for it in (1, 3, 8):
+        moved = np.abs(DC.want(ins, it) - rgb).max(-1) > 0.01 * np.maximum(np.abs(rgb).max(-1), 1e-3)
+        print(f"{DC.case_name(h, w)}, {it} passes: {moved.mean():.3f} of the pixels move by more than 1 %")
+        assert moved.mean() >= 0.9
+
+
+def test_float32_evaluation_is_close_per_pixel():
+    """E32 on the smooth cases is 1e-6 to 4e-6, and 3e-5 where one channel of one pixel of 48x64 is a sum that cancels to 0.03 from
+    terms of 0.6.  Held under 1e-4 so that the device's bound, 16 x E32, stays under the 2e-3 of the weakest one-line break."""
+    for h, w in DC.SMOOTH_SIZES:
+        for it in DC.ITERATIONS:
+            e = DC.e32(DC.case(h, w), it)
+            print(f"{DC.case_name(h, w)}, {it} passes: E32 {e:.2e}")
+            assert e <= 1e-4
+
+
+@pytest.mark.parametrize("mut", MUTANTS)
+def test_every_mutant_is_far_above_the_device_bound(mut):
+    """Each one-line break of the statement is more than 10 x the device's bound away, at its worst pixel, on some (case, passes)."""
+    best = (0.0, None)
+    for h, w in DC.SMOOTH_SIZES:
+        ins = DC.case(h, w)
+        for it in DC.ITERATIONS:
+            with np.errstate(all="ignore"):
+                got = _statement(*ins, it, *DC.SIGMAS, mut=mut)[0]
+            d = DC.worst(got, DC.want(ins, it)) if np.isfinite(got).all() else np.inf
+            r = d / max(DC.bound(ins, it), 1e-300)
+            if r > best[0]:
+                best = (r, f"{DC.case_name(h, w)}, {it} passes: distance {d:.2e}, bound {DC.bound(ins, it):.2e}")
+    print(f"{mut}: {best[1]} ({best[0]:.0f} x)")
+    assert best[0] > 10.0, best
+
+
+# ---------------------------------------------------------------------------------------------------------- unusable pixels --
+
+UNUSABLE = {"nan colour": ("rgb", np.nan), "+inf colour": ("rgb", np.inf), "-inf colour": ("rgb", -np.inf), "nan variance": ("var", np.nan),
+            "negative variance": ("var", -1.0)}
+
+
+def _spoil(ins, kind, y, x):
+    rgb, var, alb, nrm, dep = (a.copy() for a in ins)
+    what, value = UNUSABLE[kind]
+    if what == "rgb":
+        rgb[y, x, 1] = value
+    else:
+        var[y, x] = value
+    return rgb, var, alb, nrm, dep
+
+
+@pytest.mark.parametrize("kind", list(UNUSABLE))
+def test_one_unusable_pixel_stays_one_pixel(kind):
+    h, w, y, x = 23, 37, 11, 20
+    clean = DC.case(h, w)
+    ins = _spoil(clean, kind, y, x)
+    cut = np.zeros((h, w), bool)
+    cut[y, x] = True
+    for it in (1, 3, 8):
+        out, v = denoise(*ins, it, *DC.SIGMAS)
+        assert np.array_equal(out[y, x].view(np.uint64), ins[0][y, x].astype(np.float64).view(np.uint64))  # untouched, bit for bit
+        assert np.array_equal(v[y, x].view(np.uint64), np.float64(ins[1][y, x]).view(np.uint64))
+        assert np.isfinite(out[~cut]).all() and np.isfinite(v[~cut]).all()
+        with np.errstate(all="ignore"):
+            want, want_v = _statement(*clean, it, *DC.SIGMAS, cut=cut)  # the clean frame with that pixel told to be left out
+        assert DC.worst(out[~cut], want[~cut]) <= 1e-12 and DC.worst(v[~cut], want_v[~cut]) <= 1e-12
+        # ... and leaving it out is not nothing: the statement on the clean frame differs around it
+        assert DC.worst(out[~cut], DC.want(clean, it)[~cut]) > 1e-3
+
+
+def test_impulse_response_beside_an_unusable_pixel_is_the_renormalised_b3_kernel():
+    h = w = 21
+    rgb = np.zeros((h, w, 3))
+    rgb[10, 10] = 1.0
+    rgb[10, 11, 2] = np.nan
+    alb, nrm, dep = _flat(h, w)
+    var = np.full((h, w), 1e12)
+    out, _ = denoise(rgb, var, alb, nrm, dep, 1, 4.0, 128.0, 0.1, 0.1)
+    k = np.outer(H5, H5)
+    want = np.zeros((h, w))
+    for y in range(h):
+        for x in range(w):
+            at = lambda qy, qx: k[qy - y + 2, qx - x + 2] if abs(qy - y) <= 2 and abs(qx - x) <= 2 else 0.0  # noqa: E731
+            want[y, x] = at(10, 10) / (1.0 - at(10, 11))
+    ok = np.ones((h, w), bool)
+    ok[10, 11] = False
+    np.testing.assert_allclose(out[..., 0][ok], want[ok], atol=1e-6)
+    assert abs(want[10, 12] - (1 / 16 * 3 / 8) / (1 - 1 / 4 * 3 / 8)) < 1e-15  # the pixel right of it: its tap h(-2) h(0) over what is left
+    assert np.isnan(out[10, 11, 2]) and out[10, 11, 0] == 0.0
+
+
+def test_unusable_rule_consequences():
+    h, w = 16, 16
+    ins = DC.case(h, w)
+    rgb, var, alb, nrm, dep = ins
+    for it in (1, 3, 8):
+        assert np.isfinite(denoise(*ins, it, *DC.SIGMAS)[0]).all()  # finite in, finite out
+        nan_v = np.full_like(var, np.nan)
+        out, v = denoise(rgb, nan_v, alb, nrm, dep, it, *DC.SIGMAS)  # nothing usable: the input's bits
+        assert np.array_equal(out, rgb.astype(np.float64)) and np.isnan(v).all()
+        out32, _ = denoise(rgb, nan_v, alb, nrm, dep, it, *DC.SIGMAS, dtype=np.float32)
+        assert out32.dtype == np.float32 and np.array_equal(out32.view(np.uint32), rgb.view(np.uint32))
+    # every input decides: a non-finite albedo, normal or depth does what a non-finite colour does
+    for which in (2, 3, 4):
+        spoiled = [a.copy() for a in ins]
+        spoiled[which][5, 6] = np.inf
+        out, _ = denoise(*spoiled, 3, *DC.SIGMAS)
+        assert np.array_equal(out[5, 6], rgb[5, 6].astype(np.float64))
+        assert np.isfinite(out).all() and unusable(*spoiled).sum() == 1
+
+
+def test_normals_of_any_length_normalise():
+    n = np.array([[[1e-25, 0, 0], [1e20, 1e20, 0], [2.0 ** -149, 0, 0], [0, 0, 0], [3e-200, 4e-200, 0], [0, -1e300, 0]]])
+    zero = np.all(n == 0, axis=-1)
+    r = np.sqrt(0.5)
+    np.testing.assert_allclose(unit_normals(n, zero)[0], [[1, 0, 0], [r, r, 0], [1, 0, 0], [0, 0, 0], [0.6, 0.8, 0], [0, -1, 0]], rtol=1e-15)
+    n32 = n[:, :4].astype(np.float32)
+    np.testing.assert_allclose(unit_normals(n32, zero[:, :4])[0], [[1, 0, 0], [r, r, 0], [1, 0, 0], [0, 0, 0]], rtol=1e-7)
+    # in a frame: such a pixel filters as the unit normal does
+    ins = [a.copy() for a in DC.case(16, 16)]
+    ins[3][...] = [0, 0, 1]
+    want = denoise(*ins, 2, *DC.SIGMAS)[0]
+    ins[3][4:7, 4:7] = [0, 0, 2.0 ** -149]
+    ins[3][9, 9] = [0, 0, 1e-25]
+    ins[3][12, 3] = [0, 0, 1e20]
+    assert np.array_equal(denoise(*ins, 2, *DC.SIGMAS)[0], want)
+
+
+# ------------------------------------------------------------------------------------------------ the guide pass's scenes --
+
+@pytest.mark.parametrize("name", GC.SCENES)
+def test_crafted_guide_scenes_reach_their_vertices(name):
+    """By the spec alone: enough pixels of each crafted scene reach the vertex the scene was made for, and the spec's guide there is
+    what the header says of it."""
+    from test_gpu_denoise import _Geometry, _spec_guide
+    S, p = _Geometry(GC.scene(name)), GC.params()
+    got = GC.counts(S, p)
+    print(name, got)
+    for what, need in GC.NEED[name].items():
+        assert got.get(what, 0) >= need, (what, got)
+    for y in range(p.height):
+        for x in range(p.width):
+            seen = GC.classify(S, x, y, p, p.frame)
+            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            if "limit" in seen:
+                np.testing.assert_allclose(a, np.array([0.9, 0.8, 0.95]) ** 33, rtol=1e-6)  # (brdf as float32 holds it)
+                assert z > 33 * 2.0 and abs(abs(n[2]) - 1) < 1e-6
+            if "red" in seen:
+                np.testing.assert_allclose(a, [0.9, 0.5, 0.5], rtol=1e-6)
+            if "green" in seen:
+                np.testing.assert_allclose(a, [0.5, 0.9, 0.5], rtol=1e-6)
+            if "blue passed" in seen and "miss" not in seen and not seen & {"red", "green"}:
+                np.testing.assert_allclose(a, np.array([0.5, 0.5, 0.9]) * [0.6, 0.7, 0.8], rtol=1e-6)
+                assert z > 6.0  # 2 to the mirror, 4 back to the wall behind the camera
+            if "miss" in seen and name == "behind":
+                assert np.array_equal(a, np.ones(3)) and np.array_equal(n, np.zeros(3)) and z == 0.0
+            if "back face" in seen and name == "behind":
+                np.testing.assert_allclose(n, [0, 0, 1], atol=1e-6)  # facing the camera, whatever the winding says
 
 
 def test_hip_library_exports_the_entry_points():

@@ -1,0 +1,350 @@
+"""The denoiser's filter held pixel by pixel on the MI355X, its unusable pixels, and the guide pass on crafted scenes.
+
+tests/test_gpu_denoise.py compares whole images (relative L2 <= 1e-4) on inputs most of which the filter leaves as they are.  Here:
+
+  * every pixel and channel of jade_denoise_image on the smooth cases of tests/denoise_cases.py (on which the filter moves more than
+    90 % of the pixels) is within B max(|want|, 1e-3) of the float64 statement (tests/denoise_ref.py), B = 16 x E32 of that case, E32
+    being the same distance for the statement evaluated in float32 numpy.  Every one-line break of the statement that
+    tests/test_denoise_cpu.py lists is more than 10 B away.  Each test prints its worst error / E32;
+  * values at the ends of the float range, normals of any length, and unusable pixels (include/jade_bvh.h): one non-finite pixel
+    comes back bit for bit and spoils no other;
+  * where nothing is unusable the filter's output is the recording of tests/golden/denoise_frames.json, sha256 for sha256.  That was
+    recorded with the library as it stood BEFORE the unusable rule went in, twice, the two recordings equal.  To record:
+
+        python tests/test_gpu_denoise_exact.py record OUT.json     (on the MI355X; twice, and compare the two files)
+
+  * the guide pass on tests/guide_cases.py's scenes, against test_gpu_denoise.py's float64 spec."""
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from conftest import B, config_scene  # noqa: E402
+from jaderaytracerendering_amd import host as H  # noqa: E402
+
+import denoise_cases as DC  # noqa: E402
+import guide_cases as GC  # noqa: E402
+from denoise_ref import denoise, unusable  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "denoise_frames.json")
+GOLDEN_PASSES = (1, 3, 8)
+BASE = (23, 37)  # the case the variants are made from
+
+
+def _dp(hip, **kw):
+    d = hip.denoise_defaults()
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def _sigmas(d):
+    return (d.sigma_luminance, d.sigma_normal, d.sigma_depth, d.sigma_albedo)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _held(hip, label, ins, d, scale=1.0):
+    """jade_denoise_image on `ins` against the statement, pixel by pixel; returns the device's frame.  Pixels the statement leaves
+    non-finite (unusable ones) are the caller's to compare, by their bits."""
+    ins = tuple(np.ascontiguousarray(a, np.float32) for a in ins)
+    got = hip.denoise_image(*ins, params=d)
+    want = DC.want(ins, d.iterations, _sigmas(d))
+    ok = np.isfinite(want)
+    assert np.isfinite(got[ok]).all(), label
+    if scale == 1.0:
+        e32 = DC.e32(ins, d.iterations, _sigmas(d))
+    else:
+        with np.errstate(all="ignore"):
+            f32 = denoise(*ins, d.iterations, *_sigmas(d), dtype=np.float32)[0]
+        e32 = DC.worst(f32[ok].astype(np.float64) * scale, want[ok] * scale)
+    r = DC.ratio_map(got[ok].astype(np.float64) * scale, want[ok] * scale)
+    worst = float(r.max())
+    print(f"{label}: worst pixel {worst:.3e}, E32 {e32:.3e}, error / E32 = {worst / e32 if e32 else (0.0 if worst == 0 else np.inf):.2f}")
+    assert worst <= DC.BOUND_FACTOR * e32, f"{label}: {int((r > DC.BOUND_FACTOR * e32).sum())} values above 16 x E32"
+    return got
+
+
+# --------------------------------------------------------------------------------------------------------- the smooth cases --
+
+@pytest.mark.parametrize("iterations", DC.ITERATIONS)
+@pytest.mark.parametrize("h,w", DC.SMOOTH_SIZES)
+def test_every_pixel_of_the_smooth_cases(hip, h, w, iterations):
+    _held(hip, f"{DC.case_name(h, w)}, {iterations} passes", DC.case(h, w), _dp(hip, iterations=iterations))
+
+
+@pytest.mark.parametrize("sigma", [dict(sigma_normal=0.0), dict(sigma_normal=1024.0), dict(sigma_luminance=0.25), dict(sigma_depth=1e-3),
+                                   dict(sigma_albedo=10.0)], ids=lambda s: "%s=%g" % next(iter(s.items())))
+def test_every_pixel_under_other_sigmas(hip, sigma):
+    _held(hip, f"{DC.case_name(*BASE)}, {sigma}", DC.case(*BASE), _dp(hip, **sigma))
+
+
+def test_every_pixel_of_a_real_frame(hip):
+    hs, cfg = config_scene("C1")
+    p = B.params_from_config(cfg, spp=16)
+    p.width, p.height = 64, 48
+    with hip.scene(hs) as sc:
+        sc.begin(p)
+        sc.step(16)
+        g = sc.guides(4)
+        rgb, _ = sc.resolve(want_bgr8=False)
+    _held(hip, "C1 64x48, 16 spp", (rgb, g["variance"], g["albedo"], g["normal"], g["depth"]), _dp(hip))
+
+
+# ------------------------------------------------------------------------------------------------------------------ values --
+
+def _variant(kind):
+    rgb, var, alb, nrm, dep = (a.copy() for a in DC.case(*BASE))
+    scale = 1.0
+    if kind == "variance 0":
+        var[:] = 0.0
+    elif kind == "variance subnormal":
+        var[:] = (var * np.float32(1e-37)).astype(np.float32)  # 1e-41 .. 1e-38
+        assert (var[var > 0] < np.finfo(np.float32).tiny).all()
+    elif kind == "colour and variance x 1e30":
+        rgb, var, scale = rgb * np.float32(1e30), var * np.float32(1e30), 1e-30
+    elif kind == "colour and variance x 1e-30":
+        rgb, var, scale = rgb * np.float32(1e-30), var * np.float32(1e-30), 1e30
+    elif kind == "depth 0":
+        dep[:] = 0.0
+    elif kind == "depth x 1e30":
+        dep = dep * np.float32(1e30)
+    elif kind == "normals of any length":
+        unit = nrm / np.maximum(np.sqrt((nrm.astype(np.float64) ** 2).sum(-1)), 1e-30)[..., None]
+        nrm[5, 9] = unit[5, 9] * 1e-25          # the squared length underflows to 0
+        nrm[6, 20] = unit[6, 20] * 1e-21        # ... to a subnormal
+        nrm[15, 30] = unit[15, 30] * 1e20       # ... overflows
+        nrm[18, 4] = [1e20, 1e20, 0]
+        nrm[2, 30] = [1e-25, 0, 0]
+        nrm[12:15, 14:17] = [2.0 ** -149, 0, 0]  # the smallest float there is
+    else:
+        raise ValueError(kind)
+    return (rgb, var, alb, nrm, dep), scale
+
+
+@pytest.mark.parametrize("kind", ["variance 0", "variance subnormal", "colour and variance x 1e30", "colour and variance x 1e-30", "depth 0",
+                                  "depth x 1e30", "normals of any length"])
+def test_values_at_the_ends_of_the_range(hip, kind):
+    ins, scale = _variant(kind)
+    assert np.isfinite(np.concatenate([a.ravel() for a in ins])).all()
+    for it in (1, 3):
+        got = _held(hip, f"{kind}, {it} passes", ins, _dp(hip, iterations=it))
+        assert np.isfinite(got).all()
+        if scale != 1.0:  # ... and in units of the frame's own size, where the metric's floor of 1e-3 does not hide a pixel
+            _held(hip, f"{kind}, {it} passes, rescaled", ins, _dp(hip, iterations=it), scale=scale)
+
+
+# --------------------------------------------------------------------------------------------------------- unusable pixels --
+
+SPOIL = {"nan colour": (0, 1, np.nan), "+inf colour": (0, 0, np.inf), "-inf colour": (0, 2, -np.inf), "nan variance": (1, None, np.nan),
+         "negative variance": (1, None, -1.0), "inf albedo": (2, 1, np.inf), "nan normal": (3, 0, np.nan), "inf depth": (4, None, np.inf),
+         "-inf variance": (1, None, -np.inf), "nan depth": (4, None, np.nan)}
+
+
+def _spoil(ins, kind, y, x):
+    which, ch, value = SPOIL[kind]
+    if ch is None:
+        ins[which][y, x] = value
+    else:
+        ins[which][y, x, ch] = value
+
+
+def _unusable_held(hip, label, ins, bad, iterations):
+    d = _dp(hip, iterations=iterations)
+    got = _held(hip, label, ins, d)
+    assert np.array_equal(_bits(got[bad]), _bits(ins[0][bad])), f"{label}: an unusable pixel's colour changed"
+    assert np.isfinite(got[~bad]).all(), f"{label}: {int((~np.isfinite(got[~bad])).sum())} non-finite values in usable pixels"
+    again = hip.denoise_image(*ins, params=d)
+    assert np.array_equal(_bits(again), _bits(got)), f"{label}: two calls, different bits"
+    return got
+
+
+@pytest.mark.parametrize("iterations", [1, 3, 8])
+@pytest.mark.parametrize("kind", ["nan colour", "+inf colour", "-inf colour", "nan variance", "negative variance"])
+def test_one_unusable_pixel_stays_one_pixel(hip, kind, iterations):
+    ins = [a.copy() for a in DC.case(*BASE)]
+    bad = np.zeros(BASE, bool)
+    bad[11, 20] = True
+    _spoil(ins, kind, 11, 20)
+    _unusable_held(hip, f"{kind}, {iterations} passes", ins, bad, iterations)
+
+
+@pytest.mark.parametrize("iterations", [1, 3, 8])
+def test_one_unusable_pixel_in_every_block(hip, iterations):
+    h, w = 48, 64
+    ins = [a.copy() for a in DC.case(h, w)]
+    bad = np.zeros((h, w), bool)
+    kinds = list(SPOIL)
+    for k, (by, bx) in enumerate((by, bx) for by in range(h // 16) for bx in range(w // 16)):
+        y, x = 16 * by + (5 * k + 3) % 16, 16 * bx + (7 * k) % 16  # block corners and edges among them
+        _spoil(ins, kinds[k % len(kinds)], y, x)
+        bad[y, x] = True
+    assert bad.sum() == 12 and np.array_equal(unusable(*ins), bad)
+    _unusable_held(hip, f"one unusable pixel per block, {iterations} passes", ins, bad, iterations)
+
+
+@pytest.mark.parametrize("what", ["nan variance", "nan colour channel", "inf depth"])
+def test_a_frame_that_is_unusable_everywhere_comes_back_as_it_went_in(hip, what):
+    rgb, var, alb, nrm, dep = (a.copy() for a in DC.case(*BASE))
+    if what == "nan variance":  # what jade_render_guides hands out for a count that gives no variance
+        var[:] = np.nan
+    elif what == "nan colour channel":
+        rgb[..., 2] = np.nan
+    else:
+        dep[:] = np.inf
+    for it in (1, 3, 8):
+        got = hip.denoise_image(rgb, var, alb, nrm, dep, params=_dp(hip, iterations=it))
+        assert np.array_equal(_bits(got), _bits(rgb)), it
+
+
+# ---------------------------------------------------------------------------------------------------------- the render path --
+
+def _lamp_scene():
+    b = H.SceneBuilder()
+    try:
+        v = np.array([[-0.5, -0.4, -2], [0.5, -0.4, -2], [0.5, 0.4, -2], [-0.5, 0.4, -2]], np.float32)
+        b.add_mesh(v, GC.QUAD_I, H.material(emissive=(3e38, 3e38, 3e38), brdf=(0.5, 0.5, 0.5)))
+        b.set_env_sky(16, 8)
+        return b.build()
+    finally:
+        b.close()
+
+
+def test_a_lamp_that_resolves_to_inf_stays_within_its_pixels(hip):
+    p = B.make_params(40, 24, 16, (0.0, 0.0, 0.0), np.eye(4, dtype=np.float32).ravel(), frame=1)
+    d = _dp(hip)
+    with hip.scene(_lamp_scene()) as sc:
+        sc.begin(p)
+        sc.step(16)
+        rgb, bgr = sc.resolve()
+        den, den_bgr = sc.denoise(d)
+        g = sc.guides(d.guide_spp)
+    lamp = np.isinf(rgb).any(-1)
+    print(f"{int(lamp.sum())} lamp pixels of {lamp.size}; non-finite after the denoiser: {int((~np.isfinite(den).all(-1)).sum())}")
+    assert 20 <= lamp.sum() <= lamp.size // 2 and np.isfinite(rgb[~lamp]).all()
+    assert np.array_equal(_bits(den[lamp]), _bits(rgb[lamp]))
+    assert np.isfinite(den[~lamp]).all()
+    assert np.array_equal(den_bgr[lamp], bgr[lamp])
+    got = hip.denoise_image(rgb, g["variance"], g["albedo"], g["normal"], g["depth"], params=d)
+    assert np.array_equal(_bits(got), _bits(den))
+    assert not np.array_equal(_bits(den[~lamp]), _bits(rgb[~lamp]))  # (the rest of the frame is filtered)
+
+
+# ----------------------------------------------------------------------------------------- unchanged where nothing is unusable --
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a, np.float32).tobytes()).hexdigest()
+
+
+def _golden_image(hip, h, w, iterations):
+    return _sha(hip.denoise_image(*DC.case(h, w), params=_dp(hip, iterations=iterations)))
+
+
+def _golden_render(hip):
+    hs, cfg = config_scene("tinyjade")
+    p = B.params_from_config(cfg, spp=16)
+    p.width, p.height = 40, 24
+    with hip.scene(hs) as sc:
+        sc.begin(p)
+        sc.step(16)
+        rgb, bgr = sc.denoise(_dp(hip))
+    return {"rgb": _sha(rgb), "bgr8": hashlib.sha256(np.ascontiguousarray(bgr).tobytes()).hexdigest()}
+
+
+def _image_key(h, w, iterations):
+    return f"{DC.case_name(h, w)}, {iterations} passes"
+
+
+if __name__ == "__main__":
+    if len(sys.argv) == 3 and sys.argv[1] == "record":
+        be = B.hip()
+        rec = {"jade_denoise_image": {_image_key(h, w, it): _golden_image(be, h, w, it) for h, w in DC.SMOOTH_SIZES for it in GOLDEN_PASSES},
+               "jade_render_denoise": {"tinyjade 40x24, 16 spp": _golden_render(be)}}
+        with open(sys.argv[2], "w") as f:
+            json.dump(rec, f, indent=1, sort_keys=True)
+            f.write("\n")
+        print(f"recorded {len(rec['jade_denoise_image']) + 1} entries to {sys.argv[2]}")
+        sys.exit(0)
+    raise SystemExit(__doc__)
+
+
+with open(FIXTURE) as _f:
+    RECORDED = json.load(_f)
+
+
+def test_the_fixture_holds_every_case():
+    assert sorted(RECORDED["jade_denoise_image"]) == sorted(_image_key(h, w, it) for h, w in DC.SMOOTH_SIZES for it in GOLDEN_PASSES)
+    assert list(RECORDED["jade_render_denoise"]) == ["tinyjade 40x24, 16 spp"]
+    big = [_image_key(h, w, it) for h, w in DC.SMOOTH_SIZES if h * w > 1 for it in GOLDEN_PASSES]
+    assert len({RECORDED["jade_denoise_image"][k] for k in big}) == len(big)
+
+
+@pytest.mark.parametrize("iterations", GOLDEN_PASSES)
+@pytest.mark.parametrize("h,w", DC.SMOOTH_SIZES)
+def test_usable_frames_filter_to_the_recorded_bits(hip, h, w, iterations):
+    assert _golden_image(hip, h, w, iterations) == RECORDED["jade_denoise_image"][_image_key(h, w, iterations)]
+
+
+def test_render_denoise_gives_the_recorded_bits(hip):
+    assert _golden_render(hip) == RECORDED["jade_render_denoise"]["tinyjade 40x24, 16 spp"]
+
+
+# ---------------------------------------------------------------------------------------------------------- the guide pass --
+
+def _guides(hip, name, **kw):
+    p = GC.params(**kw)
+    with hip.scene(GC.scene(name)) as sc:
+        sc.begin(p)
+        sc.step(4)
+        return sc.guides(1)
+
+
+def _guides_agree(g, name):
+    from test_gpu_denoise import _Geometry, _spec_guide
+    S, p = _Geometry(GC.scene(name)), GC.params()
+    ok, by_kind = 0, {}
+    for y in range(p.height):
+        for x in range(p.width):
+            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            good = bool(np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6)
+                        and abs(g["depth"][y, x] - z) <= 1e-5 * max(1.0, abs(z)))
+            ok += good
+            for kind in GC.classify(S, x, y, p, p.frame):
+                by_kind[kind] = by_kind.get(kind, 0) + good
+    print(f"{name}: {ok} of {p.width * p.height} pixels agree with the spec; by vertex {by_kind}")
+    assert ok >= 0.99 * p.width * p.height, f"{ok} of {p.width * p.height} pixels agree with the spec"
+    for kind, need in GC.NEED[name].items():  # ... and those the scene was made for are among them
+        assert by_kind.get(kind, 0) >= need, (kind, by_kind)
+
+
+@pytest.mark.parametrize("name", GC.SCENES)
+def test_guides_match_the_spec_on_the_crafted_scenes(hip, name):
+    _guides_agree(_guides(hip, name), name)
+
+
+def test_guides_of_two_tile_shares_assemble_to_the_same(hip):
+    name = "mirrors"
+    whole = _guides(hip, name)
+    parts = {k: np.full_like(v, np.nan) for k, v in whole.items()}
+    owned_all = np.zeros((GC.HEIGHT, GC.WIDTH), bool)
+    for r in range(2):
+        gr = _guides(hip, name, tile_rank=r, tile_nranks=2)
+        owned = ~np.isnan(gr["depth"])
+        assert not (owned & owned_all).any()
+        owned_all |= owned
+        for k in parts:
+            parts[k][owned] = gr[k][owned]
+    assert owned_all.all()
+    for k in ("albedo", "normal", "depth"):
+        assert np.array_equal(_bits(parts[k]), _bits(whole[k])), k
+    _guides_agree(parts, name)
