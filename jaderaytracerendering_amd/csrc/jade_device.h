@@ -290,18 +290,52 @@ static __device__ __forceinline__ void st3(float* a, int npix, int p, jvec3 v) {
 }
 static __device__ __forceinline__ jvec3 V3(const float* p) { return jv(p[0], p[1], p[2]); }
 
-// The camera ray of sample `sidx` of pixel (x, y), PathTrace.cu:1428-1437: its direction (the origin is the eye).  *rng is left
-// after the two jitter draws.  The statements of k_shade's / k_light's camera ray; the denoiser's guide pass calls it
-// (jade_denoise.hip).  (The four copies in jade_hip.hip stay as they are: those kernels sit at their register limits.)
-static __device__ __forceinline__ jvec3 camera_ray_dir(const RenderConst& R, int x, int y, uint32_t sidx, uint32_t* rng) {
+// Wave primitives of the render kernels (jade_hip.hip, jade_light.h).
+// how many lanes of mask m sit below this one (v_mbcnt_lo + v_mbcnt_hi: two instructions, no per-lane mask kept in registers)
+static __device__ __forceinline__ uint32_t lanes_below(unsigned long long m) {
+  return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+}
+static __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, uint32_t* total) {
+  const int lane = threadIdx.x & 63;
+  uint32_t x = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    uint32_t y = __shfl_up(x, off, 64);
+    if (lane >= off) x += y;
+  }
+  *total = __shfl(x, 63, 64);
+  return x - v;
+}
+static __device__ __forceinline__ unsigned long long wave_sum_u32(uint32_t v) {
+  unsigned long long x = v;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_down(x, off, 64);
+  return x;  // valid in lane 0
+}
+
+// The film point of sample `sidx` of pixel (x, y), PathTrace.cu:1428-1435: the sample's stream is seeded, the two jitter draws taken
+// (*rng is left after them) and the offsets formed in double.  Every camera ray of the render
+// kernels (shade_record and k_shade_binned, jade_hip.hip) and of the denoiser's guide pass (camera_ray_* below; tests/test_gpu_denoise*.py,
+// test_gpu_lens.py and test_gpu_shutter.py hold it) begins here; the lens and the shutter use the offsets themselves.  The two first-pass
+// kernels keep copies of these statements (jade_light.h says why).
+static __device__ __forceinline__ void film_point(const RenderConst& R, int x, int y, uint32_t sidx, uint32_t* rng, float* left_offset, float* up_offset) {
   *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
   float fx = (float)x + jade_rand(rng);
   double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
-  float left_offset = (float)(lo * R.aspect);
+  *left_offset = (float)(lo * R.aspect);
   float fy = (float)y + jade_rand(rng);
-  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  *up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+}
+// ... and the pinhole direction through it, PathTrace.cu:1436-1437 (the origin is the eye)
+static __device__ __forceinline__ jvec3 pinhole_dir(const RenderConst& R, float left_offset, float up_offset) {
   jvec3 dir = jade_transform(jv(left_offset, up_offset, -1.5f), 0.0f, R.cam);
   return jv_normalize(dir);
+}
+// The two in a row: the camera ray of sample `sidx` of pixel (x, y) as the denoiser's guide pass asks for it (jade_denoise.hip).
+static __device__ __forceinline__ jvec3 camera_ray_dir(const RenderConst& R, int x, int y, uint32_t sidx, uint32_t* rng) {
+  float left_offset, up_offset;
+  film_point(R, x, y, sidx, rng, &left_offset, &up_offset);
+  return pinhole_dir(R, left_offset, up_offset);
 }
 
 // The thin-lens ray (include/jade_bvh.h, "The lens, stated"; non-parity) of the jitter (left_offset, up_offset) - camera_ray_dir's
@@ -319,15 +353,11 @@ static __host__ __device__ __forceinline__ void lens_ray(const float* cam, const
   const jvec3 l = jade_transform(jv(lx, ly, 0.0f), 0.0f, cam);
   *origin = jv(eye[0] + l.x, eye[1] + l.y, eye[2] + l.z);
 }
-// ... of sample `sidx` of pixel (x, y) under the lens (R.lens_radius, k): camera_ray_dir's seed and jitter draws, then u3, u4.  *rng is left
+// ... of sample `sidx` of pixel (x, y) under the lens (R.lens_radius, k): film_point's seed and jitter draws, then u3, u4.  *rng is left
 // after the four draws.  The statements of shade_record's lens arm (jade_hip.hip); the denoiser's guide pass calls it.
 static __device__ __forceinline__ jvec3 camera_ray_lens(const RenderConst& R, float k, int x, int y, uint32_t sidx, uint32_t* rng, jvec3* origin) {
-  *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
-  float fx = (float)x + jade_rand(rng);
-  double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
-  float left_offset = (float)(lo * R.aspect);
-  float fy = (float)y + jade_rand(rng);
-  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  float left_offset, up_offset;
+  film_point(R, x, y, sidx, rng, &left_offset, &up_offset);
   const float u3 = jade_rand(rng);
   const float u4 = jade_rand(rng);
   jvec3 dir;
@@ -371,17 +401,13 @@ static __host__ __device__ __forceinline__ void shutter_ray(const float* cam, co
     *origin = jv(eye_t[0], eye_t[1], eye_t[2]);
   }
 }
-// ... of sample `sidx` of pixel (x, y): camera_ray_dir's seed and jitter draws, u3 and u4 under a lens (R.lens_radius > 0, k as for
+// ... of sample `sidx` of pixel (x, y): film_point's seed and jitter draws, u3 and u4 under a lens (R.lens_radius > 0, k as for
 // camera_ray_lens), then ut.  *rng is left after the three or five draws.  The statements of shade_record's shutter arm (jade_hip.hip);
 // the denoiser's guide pass calls it.
 static __device__ __forceinline__ jvec3 camera_ray_shutter(const RenderConst& R, const ShutterConst& H, float k, int x, int y, uint32_t sidx, uint32_t* rng,
                                                            jvec3* origin) {
-  *rng = jade_rng_seed((uint32_t)x, (uint32_t)y, R.frame + sidx);
-  float fx = (float)x + jade_rand(rng);
-  double lo = -1.0 + R.two_over_w * ((double)fx - 0.5);
-  float left_offset = (float)(lo * R.aspect);
-  float fy = (float)y + jade_rand(rng);
-  float up_offset = (float)(-1.0 + R.two_over_h * ((double)fy - 0.5));
+  float left_offset, up_offset;
+  film_point(R, x, y, sidx, rng, &left_offset, &up_offset);
   float u3 = 0.0f, u4 = 0.0f;
   if (R.lens_radius > 0.0f) {
     u3 = jade_rand(rng);

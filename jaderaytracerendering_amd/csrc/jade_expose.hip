@@ -45,7 +45,7 @@ static __host__ __device__ __forceinline__ int meter_classify(float r, float g, 
   return bin < 0 ? 0 : bin > JADE_METER_BINS - 1 ? JADE_METER_BINS - 1 : bin;
 }
 
-// owned pixel p (tile p >> 8) lies inside the image (pixel_xy's statement, jade_hip.hip)
+// owned pixel p (tile p >> 8) lies inside the image (pixel_xy's statement, jade_shade.h)
 static __device__ __forceinline__ bool ex_in_image(const RenderConst& R, const int32_t* tile_ids, int p) {
   const int tid = tile_ids[p >> 8], l = p & 255;
   return (tid % R.tiles_x) * JADE_TILE_SIZE + (l & 15) < R.width && (tid / R.tiles_x) * JADE_TILE_SIZE + (l >> 4) < R.height;

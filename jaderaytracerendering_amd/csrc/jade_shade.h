@@ -364,6 +364,99 @@ struct ShadeCtx {
   uint32_t c_cls;  // rays emitted by call site, one byte each: env | indirect << 8 | mirror << 16 | refract << 24 (a record emits once per pass)
 };
 
+// ---- The record steps: how a sample begins, ends and parks.  One text each for shade_record and k_shade_binned (jade_hip.hip); the
+// first-pass kernels (jade_light.h) call vertex_from_primary and store_ctx and keep their own text of the other steps, statement for
+// statement these (their instructions answer any change of their text: see there).  The film point and the pinhole direction of a
+// camera ray are jade_device.h's film_point / pinhole_dir, which the denoiser's guide pass shares.
+
+// Record p has finished `done` samples: which sample comes next and for which owned pixel.
+struct NextSample {
+  uint32_t sidx;  // global sample index (jade_rt.h)
+  int pixel;      // owned-pixel index it belongs to
+};
+// (m, home) = (p / npx, p % npx): where record p sits; computed once per thread, an integer division each.
+// rpp and JADE_SAMPLE_LANES are powers of two, so everything else is shifts — and the 64-bit modulo of the
+// pixel rotation only runs when rotation is on (it is not, by default).  A record of a tile that adaptive sampling has stopped carries
+// the stop offset in `done` (PathState.hdr): its sidx is 2^31 above its last sample's, past any target.
+static __device__ __forceinline__ NextSample next_sample_mh(const PathState& P, uint32_t m, uint32_t home, uint32_t done) {
+  const uint32_t rpp_log2 = 31u - (uint32_t)__clz(P.rpp);
+  const uint32_t per_log2 = (31u - (uint32_t)__clz(JADE_SAMPLE_LANES)) - rpp_log2;  // samples per record per block = LANES / rpp
+  const uint32_t blk = done >> per_log2, n = done - (blk << per_log2);
+  NextSample r;
+  r.sidx = JADE_SAMPLE_LANES * blk + m + (n << rpp_log2);
+  r.pixel = P.stride == 0 ? (int)home
+                          : (int)(((unsigned long long)home + (unsigned long long)n * (uint32_t)P.stride) % (uint32_t)P.npx);
+  return r;
+}
+static __device__ __forceinline__ NextSample next_sample(const PathState& P, int p, uint32_t done) {
+  const uint32_t m = (uint32_t)p / (uint32_t)P.npx;
+  return next_sample_mh(P, m, (uint32_t)p - m * (uint32_t)P.npx, done);
+}
+static __device__ __forceinline__ bool pixel_xy_t(const RenderConst& R, int tid, int pixel, int* x, int* y) {
+  int l = pixel & 255;
+  *x = (tid % R.tiles_x) * JADE_TILE_SIZE + (l & 15);
+  *y = (tid / R.tiles_x) * JADE_TILE_SIZE + (l >> 4);
+  return *x < R.width && *y < R.height;
+}
+static __device__ __forceinline__ bool pixel_xy(const RenderConst& R, const int32_t* tile_ids, int pixel, int* x, int* y) {
+  return pixel_xy_t(R, tile_ids[pixel >> 8], pixel, x, y);
+}
+
+// The next live sample of the record (rec_m, home_pix; tid0: its home pixel's tile): samples of out-of-image pixels (edge tiles) are skipped,
+// `done` counted past them.  False: nothing is left for this record below target_spp.  Otherwise *sidx is the sample, (*x, *y) its pixel.
+static __device__ __forceinline__ bool next_live_sample(const PathState& P, const RenderConst& R, const int32_t* tile_ids, uint32_t target_spp,
+                                                        uint32_t rec_m, int home_pix, int tid0, uint32_t& done, uint32_t* sidx, int* x, int* y) {
+  NextSample ns = next_sample_mh(P, rec_m, (uint32_t)home_pix, done);
+  while (ns.sidx < target_spp && !pixel_xy_t(R, ns.pixel == home_pix ? tid0 : tile_ids[ns.pixel >> 8], ns.pixel, x, y)) {
+    done += 1;
+    ns = next_sample_mh(P, rec_m, (uint32_t)home_pix, done);
+  }
+  *sidx = ns.sidx;
+  return ns.sidx < target_spp;
+}
+// A sample of the record ended with `color`: final_result = final_result + color (PathTrace.cu:1454), into the partial sum of this
+// sample's (pixel, lane) - only this record touches it in this pass
+static __device__ __forceinline__ void add_sample(const PathState& P, uint32_t rec_m, int home_pix, uint32_t& done, ShadeCtx& c, const jvec3& color) {
+  const NextSample cs = next_sample_mh(P, rec_m, (uint32_t)home_pix, done);  // the sample that just ended
+  const size_t si = (size_t)(cs.sidx % JADE_SAMPLE_LANES) * (size_t)P.npx + (size_t)cs.pixel;
+  const size_t sn = (size_t)P.sum_lanes * (size_t)P.npx;
+  st3w(P.sum, sn, si, jv_add(ld3w(P.sum, sn, si), color));
+  done += 1;
+  c.c_samples += 1;
+}
+// The path context of record p, for a record on a path or parked at a vertex.  Stored and loaded by need (shade_record): before the first
+// path_push thr is 1 and acc 0, and a mirror ray in flight needs neither the vertex it left nor, at depth 0, a stored Le.
+// (aux and auxi - P.aux - are begin_bounce's and consume's: written through Px while the record was shaded)
+static __device__ __forceinline__ void store_ctx(const PathState& P, int p, const ShadeCtx& c) {
+  float4* cx = P.ctx + (size_t)p * 4;
+  cx[0] = make_float4(c.thr.x, c.thr.y, c.thr.z, __int_as_float(c.obj));
+  cx[1] = make_float4(c.acc.x, c.acc.y, c.acc.z, c.out.z);
+  cx[2] = make_float4(c.le.x, c.le.y, c.le.z, c.src.x);
+  cx[3] = make_float4(c.src.y, c.src.z, c.out.x, c.out.y);
+}
+// A camera ray with direction d met triangle `hit` at hp: the first vertex of a path
+static __device__ __forceinline__ void vertex_from_primary(const DevScene& S, ShadeCtx& c, int hit, const jvec3& hp, const jvec3& d) {
+  c.le = V3(shade_tri(S, hit).m->emissive);
+  c.thr = jv(1, 1, 1);
+  c.acc = jv(0, 0, 0);
+  c.depth = 0;
+  c.obj = hit;
+  c.src = hp;
+  c.out = jv_neg(d);
+}
+// The secondary rays a record emitted this pass (st: its stage after it), by hitBVH call site (jade_rt.h)
+static __device__ __forceinline__ void count_secondary(ShadeCtx& c, uint32_t st) {
+  if (st == ST_PRIMARY || !c.n_emit_rays) return;
+  if (st == ST_DIFFUSE || st == ST_BSSRDF) {
+    const uint32_t ind = (c.flags & STF_RR) ? 1u : 0u;
+    const uint32_t env = (c.flags & STF_NOENV) ? 0u : 1u;  // one environment ray always (env_sampling: unless its direction lay on the wrong side)
+    c.c_cls += env | (ind << 8);  // ... and the indirect ray if the roulette passed
+    c.c_shadow += (uint32_t)c.n_emit_rays - env - ind;
+  } else {
+    c.c_cls += st == ST_MIRROR ? (1u << 16) : (1u << 24);
+  }
+}
+
 // push (dir, rate) — forward form of stack_dir / stack_indir_rate.  Returns
 // true when the reference's `while (stack_offset < STACK_CAPACITY)` would stop.
 static __device__ __forceinline__ bool path_push(ShadeCtx& c, jvec3 dirv, jvec3 rate) {
