@@ -304,7 +304,8 @@ int jade_expose_image(int device_id, int32_t width, int32_t height, const float*
  * Rows (y) first, then columns (x).  Both operators keep a constant, and away from the borders both keep the sum of the frame: a
  * source pixel gives 1/2 per axis to the coarser level, and EXPAND gives it back.
  *
- * Weights: w_k = f^(k-1) / sum over j = 1..levels of f^(j-1), computed in double on the host and passed on as float.
+ * Weights: w_k = f^(k-1) / sum over j = 1..levels of f^(j-1), computed in double on the host and passed on as float; for f > 1
+ * every power is taken relative to the largest, f^(k-levels) over the sum of those (added in increasing k), so that none overflows.
  *
  * Accumulation, from the top down:
  *   A_levels = w_levels L_levels
