@@ -1,13 +1,12 @@
 """The sample-for-sample cases of cosine-weighted bounce sampling: their scenes, the driver that holds a backend's 1-spp frames against
-tests/bounce_spec.py's arm (test_jade_spec.compare's bar, unchanged: 1e-4 relative per channel with a floor of 1e-3, at most 2 % of the
+tests/bounce_spec.py's arm (spec_scenes.compare's bar, unchanged: 1e-4 relative per channel with a floor of 1e-3, at most 2 % of the
 samples disagreeing, bssrdf-coplanar samples left out) and the `need` tables.  tests/test_gpu_bounce.py compares on the device;
 tests/test_bounce_spec_cpu.py counts what the arm alone reaches, without a GPU."""
 import numpy as np
 
 import bounce_spec
-import test_jade_spec as TJ
-from conftest import B
-from jaderaytracerendering_amd import _abi, host as H
+import spec_scenes as SP
+from jaderaytracerendering_amd import _abi
 
 MAX_LEFT_OUT = 0.05
 
@@ -16,7 +15,7 @@ def bent_cube():
     """jade_cube with the stored normal of every third triangle scaled by 2.5 (cos-nonunit: the reference's weights scale with it, the
     mode's closed form takes sqrt(nn) / 2) and the normal of one floor triangle zeroed (cos-fallback: the reference's direction, no flip,
     a zero weight)."""
-    hs = TJ.build("jade_cube")
+    hs = SP.build("jade_cube")
     t = hs.tri_f32()
     t[::3, 10:13] *= np.float32(2.5)
     floor = np.flatnonzero(hs.tri_i32()[:, 0] == hs.tri_i32()[:, 0].max())
@@ -26,58 +25,13 @@ def bent_cube():
 
 
 def build(kind, sky=False):
-    return bent_cube() if kind == "bent_cube" else TJ.build(kind, sky)
+    return bent_cube() if kind == "bent_cube" else SP.build(kind, sky)
 
 
-def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_REFERENCE, light_sampling=_abi.LIGHTS_ALL, out=None, count_only=False):
-    """test_jade_spec.compare for JADE_BOUNCE_COSINE.  count_only: no backend - what the arm alone counts per tag and leaves out."""
-    hs = build(kind, sky)
-    S = bounce_spec.Scene(hs, env_sampling, light_sampling)
-    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
-    seen, bad, kept = {}, [], {}
-    n = skipped = 0
-    worst = 0.0
-
-    def run(sc):
-        nonlocal n, skipped, worst
-        for frame in frames:
-            if sc is not None:
-                p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2, env_sampling=env_sampling)
-                rgb, _, _ = sc.render(p, want_bgr8=False)
-                kept[frame] = rgb
-            for y in range(size):
-                for x in range(size):
-                    tr = []
-                    want = bounce_spec.sample(S, x, y, size, size, eye, cam, frame, tr)
-                    if "bssrdf-coplanar" in tr:
-                        skipped += 1
-                        continue
-                    n += 1
-                    got = want if sc is None else rgb[y, x].astype(np.float64)
-                    if bool((np.abs(got - want) <= 1e-4 * np.maximum(np.abs(want), 1e-3)).all()):
-                        worst = max(worst, float((np.abs(got - want) / np.maximum(np.abs(want), 1e-3)).max()))
-                        for t in set(tr):
-                            seen[t] = seen.get(t, 0) + 1
-                    else:
-                        bad.append((frame, x, y, tr, got, want))
-
-    if count_only:
-        run(None)
-    else:
-        with backend.scene(hs) as sc:
-            sc.set_bounce_sampling(_abi.BOUNCE_COSINE)
-            if light_sampling != _abi.LIGHTS_ALL:
-                sc.set_light_sampling(light_sampling)
-            run(sc)
-    print(f"compare cosine {kind} sky={sky} env_sampling={env_sampling} light_sampling={light_sampling}: {n} compared, {len(bad)} disagree, "
-          f"{skipped} left out, worst relative error {worst:.3g}, seen {dict(sorted(seen.items()))}")
-    if out is not None:
-        out.update(frames=kept, worst=worst, seen=seen, bad=bad)
-    assert skipped <= MAX_LEFT_OUT * (n + skipped), f"{skipped} of {n + skipped} samples left out as bssrdf-coplanar"
-    assert len(bad) <= 0.02 * n, f"{len(bad)} of {n} samples disagree with the float64 spec, e.g. {bad[:3]}"
-    for tag, count in need.items():
-        assert seen.get(tag, 0) >= count, f"only {seen.get(tag, 0)} agreeing samples went through '{tag}' ({seen})"
-    return seen, len(bad), n, skipped
+def compare(backend, kind, size, frames, need, **kw):
+    """spec_scenes.compare_arm for JADE_BOUNCE_COSINE."""
+    return SP.compare_arm(bounce_spec, "cosine ", [("set_bounce_sampling", _abi.BOUNCE_COSINE)], build, backend, kind, size, frames, need,
+                          max_left_out=MAX_LEFT_OUT, **kw)
 
 
 # 12 x 12 frames at 1 spp.  `need`: half of what the arm alone counts for every tag on these samples (the comment above each case;
@@ -89,7 +43,7 @@ CASES = {
                       need={"bssrdf": 6, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "mirror": 30, "sky": 76, "sss": 17}),
     # 432 samples, none left out: 239 cos-env, 211 cos-indirect, 239 diffuse, 191 sky
     "open_floor": dict(kind="open_floor", size=12, frames=(0, 1, 2), need={"cos-env": 119, "cos-indirect": 105, "diffuse": 119, "sky": 95}),
-    # under the textured sky (TJ.sky_map) the draws, so the counts, are the constant sky's
+    # under the textured sky (SP.sky_map) the draws, so the counts, are the constant sky's
     "jade_cube_sky": dict(kind="jade_cube", sky=True, size=12, frames=(0, 1, 2),
                           need={"bssrdf": 6, "cos-env": 120, "cos-indirect": 105, "diffuse": 109, "mirror": 30, "sky": 76, "sss": 17}),
     "open_floor_sky": dict(kind="open_floor", sky=True, size=12, frames=(0, 1, 2), need={"cos-env": 119, "cos-indirect": 105, "diffuse": 119, "sky": 95}),

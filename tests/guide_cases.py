@@ -71,7 +71,7 @@ def params(spp=4, **kw):
 
 
 def camera_ray(x, y, p, frame):
-    """The camera ray of sample `frame - p.frame` of pixel (x, y) in float64, as tests/test_gpu_denoise.py's _spec_guide makes it."""
+    """The camera ray of sample `frame - p.frame` of pixel (x, y) in float64, as spec_guide below makes it."""
     rng = jade_spec.wang_stream(x, y, frame)
     lx = (-1 + 2.0 / p.width * (x + next(rng) - 0.5)) * (p.width / p.height)
     ly = -1 + 2.0 / p.height * (y + next(rng) - 0.5)
@@ -115,3 +115,49 @@ def counts(S, p):
             for name in classify(S, x, y, p, p.frame):
                 out[name] = out.get(name, 0) + 1
     return out
+
+
+# ---- the float64 statement of the guide pass, on any scene (tests/test_gpu_denoise.py holds the device's guides to it) ----
+
+def spec_guide(S, x, y, p, frame):
+    """jade_bvh.h's guide sample in float64: (albedo, normal, depth)."""
+    rng = jade_spec.wang_stream(x, y, frame)
+    lx = (-1 + 2.0 / p.width * (x + next(rng) - 0.5)) * (p.width / p.height)
+    ly = -1 + 2.0 / p.height * (y + next(rng) - 0.5)
+    M = np.asarray(list(p.camera), np.float64).reshape(4, 4)
+    v = np.array([lx, ly, -1.5, 0.0])
+    d = np.array([sum(M[c][r] * v[c] for c in range(4)) for r in range(3)])
+    d = d / math.sqrt(d @ d)
+    o = np.asarray(list(p.eye), np.float64)
+    t, z, skip = np.ones(3), 0.0, -1
+    for k in range(33):  # JADE_MAX_FULL_REFLEX_TIME mirror vertices, then the final one
+        h, hp = S.hit(o, d, skip)
+        if h < 0:
+            return t, np.zeros(3), 0.0
+        dist = (hp - o) @ (d / math.sqrt(d @ d))
+        e = S.emis[h]
+        if S.reflex[h] == _abi.MIRROR and not (e[0] > 1.5e-4 or e[1] > 1.5e-4 or e[0] > 1.5e-4) and k < 32:
+            t = t * S.brdf[h]
+            z += dist
+            out = -d
+            n = S.norm[h]
+            d = n * (2 * (out @ n)) - out
+            o, skip = hp, h
+            continue
+        z += dist
+        n = S.norm[h]
+        return t * S.brdf[h], (-n if n @ d > 0 else n), z
+    raise AssertionError("mirror chain too long")
+
+
+class Geometry:
+    """What jade_spec.Scene.hit reads of a scene (the geometry alone: the guides never look at the environment)."""
+    hit = jade_spec.Scene.hit
+
+    def __init__(self, hs):
+        t = hs.a["triangles"]
+        f, i = t.view(np.float32).astype(np.float64), t.view(np.int32)
+        self.p1, self.p2, self.p3 = f[:, 1:4], f[:, 4:7], f[:, 7:10]
+        self.norm, self.emis, self.brdf = f[:, 10:13], f[:, 13:16], f[:, 16:19]
+        self.reflex = i[:, 19]
+        self.n = len(t)

@@ -1,12 +1,12 @@
 """The sample-for-sample cases of multiple importance sampling of the emitters (JADE_DIRECT_MIS): their scenes, the driver that holds a
-backend's 1-spp frames against tests/mis_spec.py's arm (test_jade_spec.compare's bar, unchanged: 1e-4 relative per channel with a floor
+backend's 1-spp frames against tests/mis_spec.py's arm (spec_scenes.compare's bar, unchanged: 1e-4 relative per channel with a floor
 of 1e-3, at most 2 % of the samples disagreeing, bssrdf-coplanar samples left out) and the `need` tables.  tests/test_gpu_mis.py
 compares on the device; tests/test_mis_cpu.py counts what the arm alone reaches, without a GPU."""
 import numpy as np
 
 import mis_spec
-import test_jade_spec as TJ
-from conftest import B, J
+import spec_scenes as SP
+from conftest import J
 from jaderaytracerendering_amd import _abi, host as H
 
 MAX_LEFT_OUT = 0.05
@@ -21,11 +21,11 @@ def big_lamp():
     share of the indirect rays of the cube's faces and of the floor ends on one of them.  emit_indices = their six triangles and the
     first again."""
     b = J.SceneBuilder()
-    b.add_mesh(TJ.CUBE_V, TJ.CUBE_I, H.material(**TJ.JADE), H.transform_matrix(rot_deg=(20, 30, 0)))
-    b.add_mesh(TJ.quad(1.15, 1.8, flip=True), TJ.QUAD_I, H.material(**BIG))
-    b.add_mesh(WALL, TJ.QUAD_I, H.material(**BIG))
-    b.add_mesh(BACK, TJ.QUAD_I, H.material(**BIG))
-    b.add_mesh(TJ.quad(-0.9, 3.0), TJ.QUAD_I, H.material(**TJ.FLOOR))
+    b.add_mesh(SP.CUBE_V, SP.CUBE_I, H.material(**SP.JADE), H.transform_matrix(rot_deg=(20, 30, 0)))
+    b.add_mesh(SP.quad(1.15, 1.8, flip=True), SP.QUAD_I, H.material(**BIG))
+    b.add_mesh(WALL, SP.QUAD_I, H.material(**BIG))
+    b.add_mesh(BACK, SP.QUAD_I, H.material(**BIG))
+    b.add_mesh(SP.quad(-0.9, 3.0), SP.QUAD_I, H.material(**SP.FLOOR))
     b.set_env_constant(0.5, 0.6, 0.8)
     hs = b.build()
     obj = hs.tri_i32()[:, 0]
@@ -38,7 +38,7 @@ def big_lamp():
 def long_normals():
     """two_lamps with the stored normals of the four lamp triangles times 1.7 and of every third other triangle times 2.5: the
     reference's terms scale with both lengths, pA with the emitter's and pB with neither."""
-    hs = TJ.build("two_lamps")
+    hs = SP.build("two_lamps")
     t, obj = hs.tri_f32(), hs.tri_i32()[:, 0]
     lamp = (obj == 1) | (obj == 2)
     t[lamp, 10:13] *= np.float32(1.7)
@@ -55,8 +55,8 @@ def contact():
     """A diffuse floor (FLOOR's material, y = 0) with a lamp quad standing on it - x in [-0.5, 0.5], y in [0, 1], in the plane z = 0 - under a
     black sky: the contact edge, where the emitter term of a floor vertex has no bound.  emit_indices = the lamp's two triangles."""
     b = J.SceneBuilder()
-    b.add_mesh(TJ.quad(0.0, 3.0), TJ.QUAD_I, H.material(**TJ.FLOOR))
-    b.add_mesh(np.array([[-0.5, 0, 0], [0.5, 0, 0], [0.5, 1, 0], [-0.5, 1, 0]], np.float32), TJ.QUAD_I,
+    b.add_mesh(SP.quad(0.0, 3.0), SP.QUAD_I, H.material(**SP.FLOOR))
+    b.add_mesh(np.array([[-0.5, 0, 0], [0.5, 0, 0], [0.5, 1, 0], [-0.5, 1, 0]], np.float32), SP.QUAD_I,
                H.material(emissive=CONTACT_LE, brdf=(0.3, 0.3, 0.3)))
     b.set_env_constant(0, 0, 0)
     hs = b.build()
@@ -100,59 +100,13 @@ def build(kind, sky=False):
         return big_lamp()
     if kind == "long_normals":
         return long_normals()
-    return TJ.build(kind, sky)
+    return SP.build(kind, sky)
 
 
-def compare(backend, kind, size, frames, need, sky=False, env_sampling=_abi.ENV_REFERENCE, light_sampling=_abi.LIGHTS_ALL, out=None, count_only=False):
-    """test_jade_spec.compare for JADE_DIRECT_MIS over JADE_BOUNCE_COSINE.  count_only: no backend - what the arm alone counts per tag."""
-    hs = build(kind, sky)
-    S = mis_spec.Scene(hs, env_sampling, light_sampling)
-    eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
-    seen, bad, kept = {}, [], {}
-    n = skipped = 0
-    worst = 0.0
-
-    def run(sc):
-        nonlocal n, skipped, worst
-        for frame in frames:
-            if sc is not None:
-                p = B.make_params(size, size, 1, eye, cam, frame=frame, threads=2, env_sampling=env_sampling)
-                rgb, _, _ = sc.render(p, want_bgr8=False)
-                kept[frame] = rgb
-            for y in range(size):
-                for x in range(size):
-                    tr = []
-                    want = mis_spec.sample(S, x, y, size, size, eye, cam, frame, tr)
-                    if "bssrdf-coplanar" in tr:
-                        skipped += 1
-                        continue
-                    n += 1
-                    got = want if sc is None else rgb[y, x].astype(np.float64)
-                    if bool((np.abs(got - want) <= 1e-4 * np.maximum(np.abs(want), 1e-3)).all()):
-                        worst = max(worst, float((np.abs(got - want) / np.maximum(np.abs(want), 1e-3)).max()))
-                        for t in set(tr):
-                            seen[t] = seen.get(t, 0) + 1
-                    else:
-                        bad.append((frame, x, y, tr, got, want))
-
-    if count_only:
-        run(None)
-    else:
-        with backend.scene(hs) as sc:
-            sc.set_bounce_sampling(_abi.BOUNCE_COSINE)
-            sc.set_direct_sampling(_abi.DIRECT_MIS)
-            if light_sampling != _abi.LIGHTS_ALL:
-                sc.set_light_sampling(light_sampling)
-            run(sc)
-    print(f"compare mis {kind} sky={sky} env_sampling={env_sampling} light_sampling={light_sampling}: {n} compared, {len(bad)} disagree, "
-          f"{skipped} left out, worst relative error {worst:.3g}, seen {dict(sorted(seen.items()))}")
-    if out is not None:
-        out.update(frames=kept, worst=worst, seen=seen, bad=bad)
-    assert skipped <= MAX_LEFT_OUT * (n + skipped), f"{skipped} of {n + skipped} samples left out as bssrdf-coplanar"
-    assert len(bad) <= 0.02 * n, f"{len(bad)} of {n} samples disagree with the float64 spec, e.g. {bad[:3]}"
-    for tag, count in need.items():
-        assert seen.get(tag, 0) >= count, f"only {seen.get(tag, 0)} agreeing samples went through '{tag}' ({seen})"
-    return seen, len(bad), n, skipped
+def compare(backend, kind, size, frames, need, **kw):
+    """spec_scenes.compare_arm for JADE_DIRECT_MIS over JADE_BOUNCE_COSINE."""
+    return SP.compare_arm(mis_spec, "mis ", [("set_bounce_sampling", _abi.BOUNCE_COSINE), ("set_direct_sampling", _abi.DIRECT_MIS)], build,
+                          backend, kind, size, frames, need, max_left_out=MAX_LEFT_OUT, **kw)
 
 
 # 12 x 12 frames at 1 spp.  `need`: half of what the arm alone counts for every tag on these samples (tests/test_mis_cpu.py holds the

@@ -21,7 +21,7 @@ FRAMES = {
     "tinyjade-11x11": ("tinyjade", 11, 11, 8, {"JADE_RECORDS_PER_PIXEL": "1"}),
     "C2-11x11": ("C2", 11, 11, 4, {"JADE_RECORDS_PER_PIXEL": "1"}),
 }
-LENS = (0.02, 0.45)  # tinyjade: the statuette sits 0.40 - 0.48 deep (tests/test_gpu_lens.py, SCHED_LENS)
+LENS = (0.02, 0.45)  # tinyjade: the statuette sits 0.40 - 0.48 deep (tests/render_helpers.py, SCHED_LENS)
 
 
 def frame(name):

@@ -11,7 +11,7 @@ import bounce_spec as spec
 import jade_spec
 from jade_spec import PI
 from jaderaytracerendering_amd import host as H
-from test_jade_spec import build
+from spec_scenes import build
 
 F32 = np.float32
 

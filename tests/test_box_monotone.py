@@ -11,19 +11,7 @@ import pytest
 
 from conftest import config_scene
 
-
-def _slab(aa, bb, o, d):
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        inv = (np.float32(1.0) / d).astype(np.float32)
-        f = ((bb - o) * inv).astype(np.float32)
-        n = ((aa - o) * inv).astype(np.float32)
-    tmax = np.where(f > n, f, n)
-    tmin = np.where(f < n, f, n)
-    lt = lambda a, b: np.where(a < b, a, b)  # noqa: E731  (std::min: a < b ? a : b)
-    gt = lambda a, b: np.where(a > b, a, b)  # noqa: E731
-    t1 = lt(tmax[:, 0], lt(tmax[:, 1], tmax[:, 2]))
-    t0 = gt(tmin[:, 0], gt(tmin[:, 1], tmin[:, 2]))
-    return np.where(t1 >= t0, np.where(t0 > 0, t0, t1), np.float32(-1))
+import ray_helpers as RH
 
 
 @pytest.mark.parametrize("name", ["tinyjade", "C1"])
@@ -54,7 +42,7 @@ def test_a_ray_that_meets_a_box_meets_its_parents(oracle, name):
     met_total = 0
     with oracle.scene(hs) as so:
         for r in range(n_rays):
-            met = _slab(aa, bb, o[r], d[r]) > 0
+            met = RH.slab(aa, bb, o[r], d[r]) > 0
             met[1] = True  # the root is entered without a test
             assert not (met[kids] & ~met[parent[kids]]).any(), f"ray {r}: a box is met whose parent's is not"
             # the restatement agrees with the oracle: V = 1 + 2 x (internal nodes entered) in a tree without missing children

@@ -283,8 +283,8 @@ def test_normals_of_any_length_normalise():
 def test_crafted_guide_scenes_reach_their_vertices(name):
     """By the spec alone: enough pixels of each crafted scene reach the vertex the scene was made for, and the spec's guide there is
     what the header says of it."""
-    from test_gpu_denoise import _Geometry, _spec_guide
-    S, p = _Geometry(GC.scene(name)), GC.params()
+    from guide_cases import Geometry, spec_guide
+    S, p = Geometry(GC.scene(name)), GC.params()
     got = GC.counts(S, p)
     print(name, got)
     for what, need in GC.NEED[name].items():
@@ -292,7 +292,7 @@ def test_crafted_guide_scenes_reach_their_vertices(name):
     for y in range(p.height):
         for x in range(p.width):
             seen = GC.classify(S, x, y, p, p.frame)
-            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            a, n, z = spec_guide(S, x, y, p, p.frame)
             if "limit" in seen:
                 np.testing.assert_allclose(a, np.array([0.9, 0.8, 0.95]) ** 33, rtol=1e-6)  # (brdf as float32 holds it)
                 assert z > 33 * 2.0 and abs(abs(n[2]) - 1) < 1e-6

@@ -1,26 +1,25 @@
 """Cosine-weighted bounce sampling on the device (include/jade_bvh.h, "The bounce, stated"; jade_scene_set_bounce_sampling): the draw
-against tests/bounce_spec.py within a derived bound, zero variance where the mathematics says so, the default mode and the seams every
-mode is held to, what it refuses, the render against bounce_spec's arm sample for sample (tests/bounce_cases.py), and the integral it
-estimates (Welch's t against the uniform mode, which is the parent's code)."""
+against tests/bounce_spec.py within a derived bound, zero variance where the mathematics says so, the default mode, the frame next to the
+uniform mode's and the other estimators on top, the render against bounce_spec's arm sample for sample (tests/bounce_cases.py), and the
+integral it estimates (Welch's t against the uniform mode, which is the parent's code).  The seams every mode is held to - twice, the
+walks, steps, tile shares, schedules, the refusals, jade_render_multi, the command line - are in tests/test_gpu_mode_seams.py (case
+"cosine" of tests/mode_seams.py)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import bounce_cases as BC
 import bounce_spec as spec
-import test_gpu_lens as GL
-import test_gpu_lights as LI
-import test_jade_spec as TJ
-from conftest import B, COUNTER_KEYS, ROOT, counters
+import jade_spec
+import spec_scenes as SP
+from conftest import B, counters
 from jaderaytracerendering_amd import _abi, host as H
+from lamp_scenes import HH, SPP, W, lamp_scene, params
+from render_helpers import all_counters, same_bits, welch_t
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
-all_counters, same_bits = GL.all_counters, GL.same_bits
 F32 = np.float32
 COS, UNI = _abi.BOUNCE_COSINE, _abi.BOUNCE_UNIFORM
 
@@ -139,7 +138,7 @@ def test_the_rng_entry_takes_two_wang_steps_and_gives_the_bodys_result(hip_debug
     body, _ = bounce_dir_device(hip_debug, np.concatenate([n, s[:, None], u1[:, None], u2[:, None]], 1))
     assert same_bits(d, body), "u1 first"
     # (jade_spec.wang_stream is the same generator: one seed's first two numbers)
-    g = TJ.jade_spec.wang_stream(3, 5, 9)
+    g = jade_spec.wang_stream(3, 5, 9)
     seed = np.uint32([((3 * 1973 + 5 * 9277 + 9 * 26699) | 1) & 0xffffffff])
     assert float((wang(seed).astype(F32) * F32(2.0 ** -32))[0]) == next(g)
 
@@ -153,7 +152,7 @@ def floor_scene(normal_scale=1.0):
     """One diffuse floor quad (FLOOR's material) under a constant sky, no emitter entries; its stored normals times normal_scale."""
     b = H.SceneBuilder()
     try:
-        b.add_mesh(TJ.quad(-0.9, 3.0), TJ.QUAD_I, H.material(**TJ.FLOOR))
+        b.add_mesh(SP.quad(-0.9, 3.0), SP.QUAD_I, H.material(**SP.FLOOR))
         b.set_env_constant(*SKY)
         hs = b.build()
     finally:
@@ -179,7 +178,7 @@ def test_an_open_floor_under_a_constant_sky_has_no_variance(hip):
         sc.set_bounce_sampling(COS)
         cos, _, st_c = sc.render(p, want_bgr8=False)
     sky = np.float32(SKY)
-    want = np.float64(TJ.FLOOR["brdf"]) * np.float64(SKY)
+    want = np.float64(SP.FLOOR["brdf"]) * np.float64(SKY)
     # (the lookup interpolates the constant map: a sky pixel is the sky within a few fp32 roundings; no floor sample can be - its three
     # channels carry three different brdf factors)
     is_sky = (np.abs(uni.astype(np.float64) / sky - 1) < 1e-6).all(-1)
@@ -204,7 +203,7 @@ def test_a_normal_of_length_two_and_a_half_carries_the_weight_of_its_length(hip)
     with hip.scene(floor_scene(2.5)) as sc:
         sc.set_bounce_sampling(COS)
         cos, _, st = sc.render(p, want_bgr8=False)
-    want = 2.5 * np.float64(TJ.FLOOR["brdf"]) * np.float64(SKY)
+    want = 2.5 * np.float64(SP.FLOOR["brdf"]) * np.float64(SKY)
     is_sky = (np.abs(cos.astype(np.float64) / np.float32(SKY) - 1) < 1e-6).all(-1)
     assert (~is_sky).sum() == st.shaded_hits > 500
     rel = np.abs(cos[~is_sky].astype(np.float64) / want - 1).max()
@@ -212,10 +211,7 @@ def test_a_normal_of_length_two_and_a_half_carries_the_weight_of_its_length(hip)
     assert rel < 1e-5
 
 
-# ---------------------------------------------------------------------------------------------------------- 3. defaults and seams --
-W, HH, SPP = LI.W, LI.HH, LI.SPP
-params, lamp_scene = LI.params, LI.lamp_scene
-NOT_WALK = [k for k in COUNTER_KEYS if k not in ("nodes_visited", "tris_tested")]
+# ---------------------------------------------------------------------------------------------------------- 3. the default and the frame --
 
 
 def render(hip, p, mode=COS, name="lamp", lights=_abi.LIGHTS_ALL):
@@ -234,11 +230,6 @@ def cos_ref(hip):
 def uni_ref(hip):
     with hip.scene(lamp_scene("lamp")) as sc:
         return sc.render(params())
-
-
-def _is_ref(out, ref, what=""):
-    assert same_bits(out[0], ref[0]) and np.array_equal(out[1], ref[1]), what
-    assert {k: getattr(out[2], k) for k in NOT_WALK} == {k: getattr(ref[2], k) for k in NOT_WALK}, what
 
 
 def test_the_default_mode_is_todays_render_after_a_round_trip(hip, uni_ref):
@@ -263,69 +254,6 @@ def test_the_frame_is_finite_lit_and_not_the_uniform_modes(cos_ref, uni_ref):
     assert st.rays_primary == uni_ref[2].rays_primary
     assert st.rays_secondary == st.rays_shadow + st.rays_env + st.rays_indirect + st.rays_mirror + st.rays_refract
     assert min(st.rays_shadow, st.rays_env, st.rays_indirect, st.rays_mirror) > 0
-
-
-def test_the_same_bits_twice(hip, cos_ref):
-    out = render(hip, params())
-    _is_ref(out, cos_ref)
-    assert counters(out[2]) == counters(cos_ref[2])
-
-
-@pytest.mark.parametrize("walk", [_abi.WALK_REFERENCE, _abi.WALK_EARLY_EXIT, _abi.WALK_EARLY_EXIT_CACHED])
-def test_the_same_bits_under_the_three_walks(hip, cos_ref, walk):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        for _ in range(2 if walk == _abi.WALK_EARLY_EXIT_CACHED else 1):
-            _is_ref(sc.render(params(walk=walk)), cos_ref, walk)
-
-
-def test_steps_equal_one_call(hip, cos_ref):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.begin(params())
-        st = _abi.Stats()
-        for _ in range(3):
-            sc.step(2, st)
-        sc.set_bounce_sampling(UNI)  # a render in progress keeps the mode it began with
-        sc.flush(st)
-        rgb, bgr = sc.resolve()
-    _is_ref((rgb, bgr, st), cos_ref, "3 steps of 2 + flush")
-    assert counters(st) == counters(cos_ref[2])
-
-
-def test_two_tile_shares_assemble_to_the_frame(hip, cos_ref):
-    acc, acc_b = np.zeros_like(cos_ref[0]), np.zeros_like(cos_ref[1])
-    tot = {k: 0 for k in counters(cos_ref[2])}
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        for r in range(2):
-            part, part_b, st = sc.render(params(tile_rank=r, tile_nranks=2))
-            assert not ((acc != 0) & (part != 0)).any()
-            acc += part
-            acc_b += part_b
-            for k, v in counters(st).items():
-                tot[k] += v
-    assert same_bits(acc, cos_ref[0]) and np.array_equal(acc_b, cos_ref[1])
-    assert tot == counters(cos_ref[2])
-
-
-SCHEDULES = [
-    dict(JADE_RECORDS_PER_PIXEL="1"), dict(JADE_FUSED="0"), dict(JADE_SORT="1", JADE_SORT_MIN="64"),
-    dict(JADE_SHADE_BINNED="1", JADE_TAIL="1"),  # switches of kernels this mode does not run: no effect
-]
-
-
-@pytest.mark.parametrize("env", SCHEDULES, ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
-def test_records_per_pixel_and_schedules_are_one_result(hip, cos_ref, monkeypatch, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.begin(params())
-        rpp = sc.query(_abi.Q_RECORDS_PER_PIXEL)
-        out = sc.render(params(walk=_abi.WALK_EARLY_EXIT))
-    assert rpp == (1 if "JADE_RECORDS_PER_PIXEL" in env else 8)
-    _is_ref(out, cos_ref, env)
 
 
 @pytest.mark.parametrize("envs,lights", [(_abi.ENV_IMPORTANCE, _abi.LIGHTS_ALL), (_abi.ENV_REFERENCE, _abi.LIGHTS_ONE), (_abi.ENV_IMPORTANCE, _abi.LIGHTS_ONE)])
@@ -357,91 +285,21 @@ def test_adaptive_sampling_the_denoiser_exposure_and_glare_run_on_top(hip):
         assert np.isfinite(gl).all() and gl.max() > 0
 
 
-# ------------------------------------------------------------------------------------------------------------------ 4. the refusals --
-
-def test_the_oracle_has_no_such_entry_point(oracle):
-    with oracle.scene(lamp_scene("lamp1")) as so:
-        with pytest.raises(B.JadeError) as ei:
-            so.set_bounce_sampling(COS)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
-        with pytest.raises(B.JadeError):
-            so.bounce_sampling
-
-
-def test_an_unknown_mode_is_invalid_and_leaves_the_mode(hip):
-    with hip.scene(lamp_scene("lamp1")) as sc:
-        sc.set_bounce_sampling(COS)
-        for bad in (2, -1, 255):
-            with pytest.raises(B.JadeError) as ei:
-                sc.set_bounce_sampling(bad)
-            assert ei.value.code == _abi.JADE_ERR_INVALID
-            assert sc.bounce_sampling == COS
-
-
-def test_a_lens_or_a_shutter_is_refused_by_name(hip, cos_ref):
-    p = params()
-    eye, cam = np.array(p.eye[:], np.float32), np.array(p.camera[:], np.float32)
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.set_lens(0.05, 4.0)
-        with pytest.raises(B.JadeError) as ei:
-            sc.begin(p)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_BOUNCE_COSINE" in str(ei.value) and "lens" in str(ei.value)
-        sc.set_lens(0.0)
-        sc.set_shutter(eye, cam)
-        with pytest.raises(B.JadeError) as ei:
-            sc.render(p)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_BOUNCE_COSINE" in str(ei.value) and "shutter" in str(ei.value)
-        sc.set_shutter(None)
-        _is_ref(sc.render(p), cos_ref, "the refusals left the handle usable")
-        sc.set_bounce_sampling(UNI)
-        sc.set_lens(0.05, 4.0)
-        assert np.isfinite(sc.render(p)[0]).all()
-
-
-def test_render_multi_refuses_scenes_of_different_modes(hip, cos_ref):
-    p = params()
-    hs = lamp_scene("lamp")
-    with hip.scene(hs) as s0, hip.scene(hs) as s1:
-        s0.set_bounce_sampling(COS)
-        with pytest.raises(B.JadeError) as ei:
-            B.render_multi(hip, [s0, s1], p)
-        assert ei.value.code == _abi.JADE_ERR_INVALID and "bounce sampling" in str(ei.value)
-        s1.set_bounce_sampling(COS)
-        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
-    assert same_bits(rgb, cos_ref[0]) and np.array_equal(bgr, cos_ref[1])
-
-
-def test_the_command_line(tmp_path):
-    out = tmp_path / "cos.ppm"
-    base = [CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4"]
-    r = subprocess.run(base + ["--bounce", "cosine", "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    start = [ln for ln in r.stdout.splitlines() if ln.startswith("Start...")]
-    assert len(start) == 1 and start[0].endswith("on hip-gfx950, cosine-weighted bounces") and out.exists()
-    r = subprocess.run(base + ["--bounce", "cosine", "--backend", os.path.join(ROOT, "oracle", "libjade_oracle.so"), "--out", str(out)],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "--bounce needs the HIP backend" in r.stderr
-    r = subprocess.run(base + ["--bounce", "sideways", "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "uniform or cosine" in r.stderr
-
-
-# ------------------------------------------------------------------------ 5. the render against the float64 statement, sample for sample --
+# ------------------------------------------------------------------------ 4. the render against the float64 statement, sample for sample --
 
 @pytest.mark.parametrize("case", sorted(BC.CASES))
 def test_the_render_is_the_statement_sample_for_sample(hip, case):
     BC.compare(hip, **BC.CASES[case])
 
 
-# ------------------------------------------------------------------------------------------------------------ 6. the same integral --
+# ------------------------------------------------------------------------------------------------------------ 5. the same integral --
 WELCH_K = 8
 WELCH_SPP = 4      # the smallest power of two at which both scaled groups are told apart (the table in the test's docstring)
 WELCH_LIMIT = 4.5
-welch_t = LI.welch_t
 
 
 def welch_totals(hip, spp):
-    """Per mode, the WELCH_K totals of radiance over the pixels that do not look into a lamp (test_gpu_lights.welch_totals' mask: every
+    """Per mode, the WELCH_K totals of radiance over the pixels that do not look into a lamp (tests/test_gpu_lights.py's mask: every
     channel below 4 in an all-lights frame of other samples), frames of independent samples (frame = 1000 k), both modes from the same seeds."""
     with hip.scene(lamp_scene("lamp")) as sc:
         mask = (sc.render(params(spp=64, frame=500000))[0] < 4).all(-1)

@@ -14,9 +14,8 @@ import pytest
 from conftest import (B, assert_cached_walk_equals_reference_walk, assert_early_exit_equals_reference_walk, config_scene, counters,
                       rel_l2)
 from jaderaytracerendering_amd import _abi
-from test_gpu_early_exit import INF, _trace_limit
-from test_gpu_packet import _oracle_per_ray, _packet_rays
 
+import ray_helpers as RH
 import walk_ref as W
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +29,7 @@ def _reference(oracle, name):
     if name not in _want:
         hs, (o, d, skip), _ = W.deep_tree(name)
         with oracle.scene(hs) as so:
-            _want[name] = _oracle_per_ray(so, o, d, skip), so.trace_rays(*_source_rays(hs))[:3]
+            _want[name] = RH.oracle_per_ray(so, o, d, skip), so.trace_rays(*_source_rays(hs))[:3]
     return _want[name]
 
 
@@ -46,57 +45,12 @@ def _source_rays(hs):
     return o, d, src
 
 
-def _nan_limit(n):
-    limit = np.full(n, np.float32(np.nan))
-    limit.view(np.int32)[:] = -1  # the marker of a ray whose nearest hit is wanted
-    return limit
-
-
-def _flags(hip, sc):
-    return hip.lib.jade_debug_scene_flags(sc._h)
-
-
 def _grids(hip, sc):
     fn = hip.lib.jade_debug_scene_grids  # libjade_hip_debug.so only (not part of jade_rt.h)
     fn.restype, fn.argtypes = C.c_int, [C.c_void_p, C.c_void_p]
     out = np.zeros(4, np.int32)
     hip.check(fn(sc._h, out.ctypes.data))
     return [int(x) for x in out]  # trace_blocks, trace_blocks_wide, light_blocks, packet_blocks
-
-
-def _same_bits(got, want, where=None):
-    i, t, p = got[:3]
-    wi, wt, wp = want[:3]
-    m = np.ones(len(wi), bool) if where is None else where
-    assert np.array_equal(i[m], wi[m]), "triangle index"
-    assert np.array_equal(t[m].view(np.uint32), wt[m].view(np.uint32)), "distance"
-    hit = m & (wi >= 0)
-    assert np.array_equal(p[hit].view(np.uint32), wp[hit].view(np.uint32)), "hit point"
-
-
-def _limits(rng, hitm, t0):
-    """A limit per ray: NaN (the nearest hit is wanted), INF (any recorded hit), a distance at or below / at or beyond the nearest hit."""
-    n = len(t0)
-    limit = _nan_limit(n)
-    kind = rng.integers(0, 4, n)
-    limit[kind == 1] = INF
-    near = np.where(hitm, t0, 1.0).astype(np.float32)
-    limit[kind == 2] = (near * rng.uniform(0.5, 1.0, n).astype(np.float32))[kind == 2]
-    limit[kind == 3] = (near * rng.uniform(1.0, 3.0, n).astype(np.float32))[kind == 3]
-    return limit
-
-
-def _assert_answers(got, want, limit, skip):
-    """k_trace with a limit per ray: the reference's answer wherever its nearest hit is not nearer than the limit (a NaN: never),
-    otherwise SOME recorded hit nearer than the limit and not nearer than the reference's."""
-    i1, t1, p1 = got[:3]
-    i0, t0, p0 = want[:3]
-    hitm = i0 >= 0
-    ends = hitm & (t0 < limit)
-    _same_bits(got, want, ~ends)
-    assert (i1[ends] >= 0).all() and (t1[ends] < limit[ends]).all() and (t1[ends] >= t0[ends]).all()
-    assert (i1[ends] != skip[ends]).all()
-    return ends
 
 
 @pytest.mark.parametrize("name,wide", [(n, w) for n in W.TREES for w in ("0", "1")])  # shallow to deep
@@ -114,43 +68,43 @@ def test_raw_rays_are_the_oracles_at_every_depth(oracle, hip_debug, name, wide, 
     with hip.scene(hs) as sh:
         # ---- the reference's walk: binary units, every leaf met
         got = sh.trace_rays(o, d, skip)
-        _same_bits(got, want)
+        RH.same_answers(got, want)
         assert got[3].nodes_visited == int(want[3].sum()) and got[3].tris_tested == int(want[4].sum())
         hitm = want[0] >= 0
         assert hitm.sum() >= 300 and (~hitm).sum() >= 10
         # ---- the packet form: one scalar stack of JADE_PACKET_MAX_DEPTH + 1 entries per wave
         if hs.bvh_depth <= W.PACKET_MAX_DEPTH:
-            pk = _packet_rays(hip, sh, o, d, skip)
+            pk = RH.packet_rays(hip, sh, o, d, skip)
             assert not (pk[0] == -3).any(), "no two leaves tie on these trees: no packet is given up"
-            _same_bits(pk, want)
+            RH.same_answers(pk, want)
             assert np.array_equal(pk[3].astype(np.int64), want[3]), "node records per ray"
             assert np.array_equal(pk[4].astype(np.int64), want[4]), "triangle tests per ray"
         else:
             with pytest.raises(B.JadeError) as ei:
-                _packet_rays(hip, sh, o, d, skip)
+                RH.packet_rays(hip, sh, o, d, skip)
             assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
         # ---- k_trace / k_trace_wide with a limit per ray: all NaN (the whole walk, whatever its units), all INF, a mixture
-        nan = _trace_limit(hip, sh, o, d, skip, _nan_limit(n))
-        _same_bits(nan, want)
+        nan = RH.trace_limit(hip, sh, o, d, skip, RH.nan_limit(n))
+        RH.same_answers(nan, want)
         assert nan[3].tris_tested == int(want[4].sum())  # (no tie on these trees: no ray is walked twice)
-        if not _flags(hip, sh) & 2:
+        if not RH.flags(hip, sh) & 2:
             assert nan[3].nodes_visited == int(want[3].sum())
-        for limit in (np.full(n, INF), _limits(rng, hitm, want[1])):
-            got = _trace_limit(hip, sh, o, d, skip, limit)
-            ends = _assert_answers(got, want, limit, skip)
+        for limit in (np.full(n, RH.INF), RH.limits(rng, hitm, want[1])):
+            got = RH.trace_limit(hip, sh, o, d, skip, limit)
+            ends = RH.assert_answers(got, want, limit, skip)
             assert ends.sum() >= 100
             assert got[3].tris_tested < int(want[4].sum())
         # ---- the occluder cache: queries that leave triangles, three times on this handle
         so_, sd_, ssrc = _source_rays(hs)
-        limit = _limits(rng, want_src[0] >= 0, want_src[1])
+        limit = RH.limits(rng, want_src[0] >= 0, want_src[1])
         answered = []
         for rnd in range(3):
-            got = _trace_limit(hip, sh, so_, sd_, ssrc, limit, cached=True)
-            ends = _assert_answers(got, want_src, limit, ssrc)
+            got = RH.trace_limit(hip, sh, so_, sd_, ssrc, limit, cached=True)
+            ends = RH.assert_answers(got, want_src, limit, ssrc)
             answered.append(int(got[3].rays_cached))
             assert answered[-1] <= ends.sum()  # the cache only ever answers "yes" queries
         assert ends.sum() >= 60
-        if _flags(hip, sh) & 4:
+        if RH.flags(hip, sh) & 4:
             assert answered[0] <= answered[-1] and answered[-1] > 0, answered  # warm rounds start from what the cold one learnt
         else:
             assert answered == [0, 0, 0]
@@ -165,7 +119,7 @@ def test_gates_at_their_thresholds(hip_debug, monkeypatch):
     for name in W.TREES:
         hs = W.deep_tree(name)[0]
         with hip.scene(hs) as sh:
-            flags, g = _flags(hip, sh), _grids(hip, sh)
+            flags, g = RH.flags(hip, sh), _grids(hip, sh)
         assert flags & 1, name
         assert flags == want.get(name, 7), name
         assert (g[3] > 0) == (hs.bvh_depth <= W.PACKET_MAX_DEPTH), (name, g)
@@ -228,7 +182,7 @@ def test_frames_over_a_spine(oracle, hip_debug, depth, wide, monkeypatch):
     q = type(p).from_buffer_copy(p)
     q.walk = _abi.WALK_EARLY_EXIT
     with hip.scene(hs) as sh:
-        flags, g = _flags(hip, sh), _grids(hip, sh)
+        flags, g = RH.flags(hip, sh), _grids(hip, sh)
         ref = sh.render(p)
         early = sh.render(q)
         assert_cached_walk_equals_reference_walk(sh, p, ref)
@@ -246,7 +200,7 @@ def test_guides_over_the_deepest_spine_match_the_spec(hip):
     hold (walk_ref's rule b on the very ray the spec draws: the guide pass goes through the spill area for them) and on as many
     others.  The float64 brute force costs 50 ms a pixel, hence a choice of 64 pixels of the 48 x 40."""
     import jade_spec
-    from test_gpu_denoise import _Geometry, _spec_guide
+    from guide_cases import Geometry, spec_guide
     hs0, cfg = config_scene("tinyjade")
     hs = W.spine_to_depth(hs0, 127)
     w, h = 48, 40
@@ -268,10 +222,10 @@ def test_guides_over_the_deepest_spine_match_the_spec(hip):
         sc.begin(p)
         sc.step(4)
         g = sc.guides(1)
-    S = _Geometry(hs)
+    S = Geometry(hs)
     ok = 0
     for x, y in deep + rest:
-        a, n, z = _spec_guide(S, x, y, p, p.frame)
+        a, n, z = spec_guide(S, x, y, p, p.frame)
         good = (np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6)
                 and abs(g["depth"][y, x] - z) <= 1e-5 * max(1.0, abs(z)))
         ok += bool(good)

@@ -4,7 +4,6 @@ The filter against tests/denoise_ref.py, its exact properties, the guides agains
 brute-force hit, the variance against numpy on per-sample values, the consistency of the entry points with each other and with the
 render, the quality gain against a disjoint reference, and the error codes."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
@@ -12,9 +11,10 @@ import pytest
 from conftest import B, counters, config_scene, rel_l2
 from jaderaytracerendering_amd import _abi
 
-import jade_spec
 from adaptive_ref import lane_sums
 from denoise_ref import denoise, pixel_variance
+from guide_cases import Geometry, spec_guide
+from render_helpers import with_params
 
 pytestmark = pytest.mark.gpu
 
@@ -27,13 +27,6 @@ def _params(name, spp, width=None, height=None, **kw):
     if width:
         p.width, p.height = width, height
     return hs, p
-
-
-def _with(p, **kw):
-    q = type(p).from_buffer_copy(p)
-    for k, v in kw.items():
-        setattr(q, k, v)
-    return q
 
 
 def _dp(hip, **kw):
@@ -127,54 +120,10 @@ def test_constant_colour_stays_constant(hip):
 
 # ------------------------------------------------------------------------------------------------------------- guides --
 
-def _spec_guide(S, x, y, p, frame):
-    """jade_bvh.h's guide sample in float64: (albedo, normal, depth)."""
-    rng = jade_spec.wang_stream(x, y, frame)
-    lx = (-1 + 2.0 / p.width * (x + next(rng) - 0.5)) * (p.width / p.height)
-    ly = -1 + 2.0 / p.height * (y + next(rng) - 0.5)
-    M = np.asarray(list(p.camera), np.float64).reshape(4, 4)
-    v = np.array([lx, ly, -1.5, 0.0])
-    d = np.array([sum(M[c][r] * v[c] for c in range(4)) for r in range(3)])
-    d = d / math.sqrt(d @ d)
-    o = np.asarray(list(p.eye), np.float64)
-    t, z, skip = np.ones(3), 0.0, -1
-    for k in range(33):  # JADE_MAX_FULL_REFLEX_TIME mirror vertices, then the final one
-        h, hp = S.hit(o, d, skip)
-        if h < 0:
-            return t, np.zeros(3), 0.0
-        dist = (hp - o) @ (d / math.sqrt(d @ d))
-        e = S.emis[h]
-        if S.reflex[h] == _abi.MIRROR and not (e[0] > 1.5e-4 or e[1] > 1.5e-4 or e[0] > 1.5e-4) and k < 32:
-            t = t * S.brdf[h]
-            z += dist
-            out = -d
-            n = S.norm[h]
-            d = n * (2 * (out @ n)) - out
-            o, skip = hp, h
-            continue
-        z += dist
-        n = S.norm[h]
-        return t * S.brdf[h], (-n if n @ d > 0 else n), z
-    raise AssertionError("mirror chain too long")
-
-
-class _Geometry:
-    """What jade_spec.Scene.hit reads of a scene (the geometry alone: the guides never look at the environment)."""
-    hit = jade_spec.Scene.hit
-
-    def __init__(self, hs):
-        t = hs.a["triangles"]
-        f, i = t.view(np.float32).astype(np.float64), t.view(np.int32)
-        self.p1, self.p2, self.p3 = f[:, 1:4], f[:, 4:7], f[:, 7:10]
-        self.norm, self.emis, self.brdf = f[:, 10:13], f[:, 13:16], f[:, 16:19]
-        self.reflex = i[:, 19]
-        self.n = len(t)
-
-
 @pytest.mark.parametrize("name,w,h", [("tinyjade", 24, 16), ("C1", 12, 10)])
 def test_guides_match_the_spec(hip, name, w, h):
     hs, p = _params(name, 4, w, h)
-    S = _Geometry(hs)
+    S = Geometry(hs)
     with hip.scene(hs) as sc:
         sc.begin(p)
         sc.step(4)
@@ -182,7 +131,7 @@ def test_guides_match_the_spec(hip, name, w, h):
     ok = 0
     for y in range(h):
         for x in range(w):
-            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            a, n, z = spec_guide(S, x, y, p, p.frame)
             good = (np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6)
                     and abs(g["depth"][y, x] - z) <= 1e-5 * max(1.0, abs(z)))
             ok += bool(good)
@@ -197,7 +146,7 @@ def test_guides_average_their_samples_in_order(hip):
         g4 = sc.guides(4)
         ones = []
         for s in range(4):
-            sc.begin(_with(p, frame=7 + s))
+            sc.begin(with_params(p, frame=7 + s))
             sc.step(4)
             ones.append(sc.guides(1))
     for k in ("albedo", "normal", "depth"):
@@ -211,7 +160,7 @@ def test_guides_average_their_samples_in_order(hip):
 # ----------------------------------------------------------------------------------------------------------- variance --
 
 def _samples(sc, p, n):
-    return np.stack([sc.render(_with(p, spp=1, frame=s), want_bgr8=False)[0] for s in range(n)])
+    return np.stack([sc.render(with_params(p, spp=1, frame=s), want_bgr8=False)[0] for s in range(n)])
 
 
 @pytest.mark.parametrize("n", [2, 16, 2048])
@@ -219,7 +168,7 @@ def test_variance_matches_numpy(hip, n):
     hs, p = _params("tinyjade", n, 16, 16) if n > 16 else _params("tinyjade", n, 37, 21)
     with hip.scene(hs) as sc:
         x = _samples(sc, p, n)
-        sc.begin(_with(p, spp=n))
+        sc.begin(with_params(p, spp=n))
         sc.step(n)
         got = sc.guides(1)["variance"]
     want = pixel_variance(lane_sums(x), n)
@@ -264,7 +213,7 @@ def test_two_rank_guides_assembled_equal_the_one_rank_denoise(hip):
     rgb = np.zeros((p.height, p.width, 3), np.float32)
     g = {k: np.zeros_like(v) for k, v in {"albedo": rgb, "normal": rgb, "depth": rgb[..., 0], "variance": rgb[..., 0]}.items()}
     for r in range(2):
-        q = _with(p, tile_rank=r, tile_nranks=2)
+        q = with_params(p, tile_rank=r, tile_nranks=2)
         with hip.scene(hs) as sc:
             sc.begin(q)
             sc.step(16)
@@ -318,7 +267,7 @@ def test_result_does_not_depend_on_records_per_pixel(hip):
     out, rpp = [], []
     for msb in (0, 1 << 21):
         with hip.scene(hs) as sc:
-            sc.begin(_with(p, max_state_bytes=msb))
+            sc.begin(with_params(p, max_state_bytes=msb))
             rpp.append(sc.query(_abi.Q_RECORDS_PER_PIXEL))
             sc.step(16)
             out.append(sc.denoise()[0])
@@ -338,7 +287,7 @@ def _rel_mse(x, r):
 def test_denoised_frame_halves_the_error(hip, name, w, h, spp):
     hs, p = _params(name, spp, w, h, walk=_abi.WALK_EARLY_EXIT)
     with hip.scene(hs) as sc:
-        ref, _, _ = sc.render(_with(p, spp=4096, frame=1 << 20), want_bgr8=False)
+        ref, _, _ = sc.render(with_params(p, spp=4096, frame=1 << 20), want_bgr8=False)
         sc.begin(p)
         sc.step(spp)
         noisy, _ = sc.resolve(want_bgr8=False)
@@ -377,7 +326,7 @@ def test_error_codes(hip):
         with pytest.raises(B.JadeError) as e:
             sc.guides(0)
         assert e.value.code == _abi.JADE_ERR_INVALID
-        sc.begin(_with(p, tile_nranks=2))
+        sc.begin(with_params(p, tile_nranks=2))
         sc.step(4)
         with pytest.raises(B.JadeError) as e:
             sc.denoise()

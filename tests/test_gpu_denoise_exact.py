@@ -13,7 +13,7 @@ tests/test_gpu_denoise.py compares whole images (relative L2 <= 1e-4) on inputs 
 
         python tests/test_gpu_denoise_exact.py record OUT.json     (on the MI355X; twice, and compare the two files)
 
-  * the guide pass on tests/guide_cases.py's scenes, against test_gpu_denoise.py's float64 spec."""
+  * the guide pass on tests/guide_cases.py's scenes, against guide_cases.spec_guide, the float64 spec."""
 import hashlib
 import json
 import os
@@ -310,12 +310,12 @@ def _guides(hip, name, **kw):
 
 
 def _guides_agree(g, name):
-    from test_gpu_denoise import _Geometry, _spec_guide
-    S, p = _Geometry(GC.scene(name)), GC.params()
+    from guide_cases import Geometry, spec_guide
+    S, p = Geometry(GC.scene(name)), GC.params()
     ok, by_kind = 0, {}
     for y in range(p.height):
         for x in range(p.width):
-            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            a, n, z = spec_guide(S, x, y, p, p.frame)
             good = bool(np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6)
                         and abs(g["depth"][y, x] - z) <= 1e-5 * max(1.0, abs(z)))
             ok += good

@@ -17,8 +17,9 @@ import pytest
 from conftest import B, J, assert_cached_walk_equals_reference_walk, assert_early_exit_equals_reference_walk, config_scene, counters, rel_l2, WALK_KEYS
 from jaderaytracerendering_amd import _abi
 
+import ray_helpers as RH
+
 pytestmark = pytest.mark.gpu
-INF = np.float32(2147483647.0)
 
 
 def _shadow_limit(hip, sc, o, d, tri):
@@ -28,18 +29,6 @@ def _shadow_limit(hip, sc, o, d, tri):
     out = np.zeros(len(o), np.float32)
     hip.check(fn(sc._h, len(o), o.ctypes.data, d.ctypes.data, tri.ctypes.data, out.ctypes.data))
     return out
-
-
-def _trace_limit(hip, sc, o, d, skip, limit, cached=False):
-    fn = hip.lib.jade_debug_trace_rays_cached if cached else hip.lib.jade_debug_trace_rays_limit  # libjade_hip_debug.so only (not part of jade_rt.h)
-    fn.restype = C.c_int
-    fn.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
-    n = len(o)
-    hit, dist, pt = np.zeros(n, np.int32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
-    st = _abi.Stats()
-    hip.check(fn(sc._h, n, o.ctypes.data, d.ctypes.data, skip.ctypes.data, limit.ctypes.data, hit.ctypes.data, dist.ctypes.data,
-                 pt.ctypes.data, C.byref(st)))
-    return hit, dist, pt, st
 
 
 def _aimed_rays(hs, n, seed):
@@ -80,8 +69,8 @@ def test_shadow_limit_is_the_walks_own_distance(oracle, hip_debug, name):
     seen = i_o == tri
     assert seen.sum() > 2000
     assert np.array_equal(lim[seen].view(np.uint32), t_o[seen].view(np.uint32))
-    assert (lim > 0).all() and (lim <= INF).all() and not np.isnan(lim).any()
-    assert (lim == INF).sum() > 100  # rays that miss their target (the zeroed component)
+    assert (lim > 0).all() and (lim <= RH.INF).all() and not np.isnan(lim).any()
+    assert (lim == RH.INF).sum() > 100  # rays that miss their target (the zeroed component)
     # a nearest hit nearer than the limit is never the target (the limit is the target's own distance)
     assert not (seen & (t_o < lim)).any()
 
@@ -105,11 +94,11 @@ def test_walk_with_a_limit_per_ray(oracle, hip_debug, name, wide, monkeypatch):
         limit = np.full(n, np.float32(np.nan))
         limit.view(np.int32)[:] = -1  # the marker of a ray whose nearest hit is wanted
         kind = rng.integers(0, 4, n)
-        limit[kind == 1] = INF
+        limit[kind == 1] = RH.INF
         near = np.where(hitm, t0, 1.0).astype(np.float32)
         limit[kind == 2] = (near * rng.uniform(0.5, 1.0, n).astype(np.float32))[kind == 2]  # at or below the nearest hit: never reached
         limit[kind == 3] = (near * rng.uniform(1.0, 3.0, n).astype(np.float32))[kind == 3]  # at or beyond it
-        i1, t1, p1, st1 = _trace_limit(hip, sh, o, d, skip, limit)
+        i1, t1, p1, st1 = RH.trace_limit(hip, sh, o, d, skip, limit)
     ends = hitm & (t0 < limit)  # (False for a NaN limit)
     assert ends.sum() > 5000 and (~ends & hitm).sum() > 3000
     same = ~ends
@@ -219,7 +208,7 @@ def test_wide_walk_ties_are_walked_again_in_the_references_order(oracle, hip_deb
     never.view(np.int32)[:] = -1  # the nearest hit is wanted: the reference's answer, whatever the form of the walk
     with oracle.scene(hs) as so, hip.scene(hs) as sh:
         i_o, t_o, p_o, _ = so.trace_rays(o, d, skip)
-        i_w, t_w, p_w, _ = _trace_limit(hip, sh, o, d, skip, never)
+        i_w, t_w, p_w, _ = RH.trace_limit(hip, sh, o, d, skip, never)
     hitm = i_o >= 0
     assert hitm.sum() > 1000
     assert np.array_equal(t_o.view(np.uint32), t_w.view(np.uint32))
@@ -279,7 +268,7 @@ def test_cached_walk_answers_every_query_as_the_whole_walk_does(oracle, hip_debu
         limit = np.full(n, np.float32(np.nan))
         limit.view(np.int32)[:] = -1
         kind = rng.integers(0, 4, n)
-        limit[kind == 1] = INF
+        limit[kind == 1] = RH.INF
         near = np.where(hitm, t0, 1.0).astype(np.float32)
         limit[kind == 2] = (near * rng.uniform(0.5, 1.0, n).astype(np.float32))[kind == 2]
         limit[kind == 3] = (near * rng.uniform(1.0, 3.0, n).astype(np.float32))[kind == 3]
@@ -287,7 +276,7 @@ def test_cached_walk_answers_every_query_as_the_whole_walk_does(oracle, hip_debu
         same = ~ends
         answered = []
         for rnd in range(5):
-            i1, t1, p1, st1 = _trace_limit(hip, sh, o, d, skip, limit, cached=True)
+            i1, t1, p1, st1 = RH.trace_limit(hip, sh, o, d, skip, limit, cached=True)
             assert np.array_equal(i1[same], i0[same]) and np.array_equal(t1[same].view(np.uint32), t0[same].view(np.uint32)), rnd
             assert np.array_equal(p1[same & hitm].view(np.uint32), p0[same & hitm].view(np.uint32)), rnd
             assert (i1[ends] >= 0).all() and (t1[ends] < limit[ends]).all() and (t1[ends] >= t0[ends]).all(), rnd

@@ -1,7 +1,8 @@
 """The thin-lens camera on the device (include/jade_bvh.h, "The lens, stated"; jade_scene_set_lens): the lens ray against its host
-build, the null lens against a handle that never heard of one, the render sample for sample against tests/lens_spec.py, the
-schedules, tile partitions and steps among themselves, hard geometric bounds on the circle of confusion, and the entry points that
-begin a render or read one - adaptive sampling, the guides and the denoiser, jade_render_multi, the command line."""
+build, the null lens against a handle that never heard of one, the render sample for sample against tests/lens_spec.py, hard geometric
+bounds on the circle of confusion, and the entry points that begin a render or read one - adaptive sampling, the guides and the
+denoiser, the command line.  The seams every mode is held to - twice, the walks, steps, tile shares, schedules, jade_render_multi - are
+in tests/test_gpu_mode_seams.py (case "lens" of tests/mode_seams.py)."""
 import ctypes
 import os
 import subprocess
@@ -9,33 +10,16 @@ import subprocess
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import jade_spec
 import lens_spec
-import test_jade_spec as TJ
-import test_lens_cpu as TL
-from adaptive_ref import tile_errors
-from conftest import B, J, ROOT, config_scene, counters, tile_mask
+import mode_seams as MS
+from conftest import B, config_scene
 from jaderaytracerendering_amd import _abi, host as H
+from render_helpers import CLI, SCHED_LENS, all_counters, read_pfm, same_bits
+from spec_scenes import build
 
 pytestmark = pytest.mark.gpu
-
-CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
-INT_FIELDS = [n for n, t in _abi.Stats._fields_ if t is ctypes.c_uint64]  # every counter of jade_stats (the rest are times)
-
-
-def all_counters(st):
-    return {k: getattr(st, k) for k in INT_FIELDS}
-
-
-def same_bits(a, b):
-    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
-
-
-def _with(p, **kw):
-    q = type(p).from_buffer_copy(p)
-    for k, v in kw.items():
-        setattr(q, k, v)
-    return q
 
 
 # ------------------------------------------------------------------------------------------------- 1. the lens ray, device = host --
@@ -46,7 +30,7 @@ def test_lens_ray_device_equals_host_build_bit_for_bit(hip_debug):
         fn.restype = ctypes.c_int
     lib.jade_debug_lens_ray_host.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     lib.jade_debug_lens_ray.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    rows = TL.lens_rows()
+    rows = CC.lens_rows()
     host = np.zeros((len(rows), 6), np.float32)
     dev = np.full((len(rows), 6), np.nan, np.float32)
     hip_debug.check(lib.jade_debug_lens_ray_host(len(rows), rows.ctypes.data, host.ctypes.data))
@@ -66,17 +50,13 @@ def test_lens_ray_device_equals_host_build_bit_for_bit(hip_debug):
     state = np.zeros(n, np.uint32)
     hip_debug.check(lib.jade_debug_lens_ray_rng(0, n, W, H_, frame, eye.ctypes.data, cam.ctypes.data, A, f, xs.ctypes.data, ys.ctypes.data,
                                                 sidx.ctypes.data, out.ctypes.data, state.ctypes.data))
-    rows2 = np.zeros((n, TL.LENS_ROW), np.float32)
+    rows2 = np.zeros((n, CC.LENS_ROW), np.float32)
     want_state = np.zeros(n, np.uint32)
     for i in range(n):
         s = ((int(xs[i]) * 1973 + int(ys[i]) * 9277 + (frame + int(sidx[i])) * 26699) | 1) & 0xffffffff
         u = []
         for _ in range(4):  # jade_wang, include/jade_fpmath.h
-            s = ((s ^ 61) ^ (s >> 16)) & 0xffffffff
-            s = (s * 9) & 0xffffffff
-            s = s ^ (s >> 4)
-            s = (s * 0x27d4eb2d) & 0xffffffff
-            s = s ^ (s >> 15)
+            s = CC.wang(s)
             u.append(np.float32(s) * np.float32(2.0 ** -32))
         want_state[i] = s
         rows2[i] = np.concatenate([[xs[i], ys[i], W, H_], eye, cam, [A, f], u, [0, 0, 0]]).astype(np.float32)
@@ -89,9 +69,7 @@ def test_lens_ray_device_equals_host_build_bit_for_bit(hip_debug):
 # -------------------------------------------------------------------------------------------- 2. no lens is today's render --
 
 def test_null_or_zero_lens_is_the_pinhole_render_in_every_bit_and_counter(hip):
-    hs, cfg = config_scene("tinyjade")
-    p = B.params_from_config(cfg, spp=24)
-    p.width, p.height = 40, 36
+    hs, p, _ = CC.tinyjade(24, 40, 36)
     with hip.scene(hs) as sc:
         ref = sc.render(p)
         assert sc.lens() == (0.0, 0.0)
@@ -144,12 +122,12 @@ SPEC_CASES = {
 
 @pytest.mark.parametrize("case", sorted(SPEC_CASES))
 def test_render_matches_the_float64_statement_sample_for_sample(hip, case):
-    """test_jade_spec.compare's settings (size 12, frames 0-2, spp 1) and rule - a sample agrees when every channel is within
+    """spec_scenes.compare's settings (size 12, frames 0-2, spp 1) and rule - a sample agrees when every channel is within
     1e-4 max(|want|, 1e-3); at most 2 % may disagree (a cap: a decision fp32 and float64 take differently, such as a ray grazing an
     edge, which a lens ray may do where the pinhole ray does not).  Disagreeing samples on the MI355X at the time of writing: DESIGN.md 3.9."""
     c = SPEC_CASES[case]
     kind = case.split("-")[0]
-    hs = TJ.build(kind, c["sky"])
+    hs = build(kind, c["sky"])
     S = jade_spec.Scene(hs, c["env_sampling"])
     eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
     size = 12
@@ -180,108 +158,20 @@ def test_render_matches_the_float64_statement_sample_for_sample(hip, case):
         assert seen.get(branch, 0) >= count, f"only {seen.get(branch, 0)} agreeing samples went through '{branch}' ({seen})"
 
 
-# ------------------------------------------------------------------------------------------ 4. schedules under a lens: one result --
+# ------------------------------------------------------------------------------------------ the schedule matrix's earlier ids --
 
-SCHED_LENS = (0.02, 0.45)  # tinyjade: the statuette sits 0.40 - 0.48 deep, the room's walls up to 1.2
-
-
-def _sched_params():
-    hs, cfg = config_scene("tinyjade")
-    p = B.params_from_config(cfg, spp=64)
-    p.width, p.height = 40, 24  # partial tiles; 960 x 64 records: more than one 512-thread block, a last wave partly filled
-    return hs, p
+@pytest.mark.parametrize("env", MS.COMMON_SCHEDULES[:5] + MS.CAMERA_SCHEDULES, ids=MS.schedule_id)
+def test_schedules_under_a_lens_are_one_result(hip, monkeypatch, env):
+    """Kept for its ids, which cannot all be retired in one change: tests/test_gpu_mode_seams.py runs this check for every case and environment."""
+    MS.check_schedule(hip, MS.BY_NAME["lens"], MS.reference(hip, MS.BY_NAME["lens"]), env, monkeypatch.setenv)
 
 
-@pytest.fixture(scope="module")
-def sched_ref(hip):
-    hs, p = _sched_params()
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        rgb, bgr, st = sc.render(p)
-    return rgb, bgr, st
-
-
-def _assert_is_ref(out, ref, what):
-    rgb, bgr, st = out
-    assert same_bits(rgb, ref[0]) and np.array_equal(bgr, ref[1]), what
-    assert counters(st) == counters(ref[2]), what
-    assert st.rays_inline == 0 and st.tail_launches == 0 and st.rays_tail == 0 and st.rays_primary == st.samples, what
-
-
-def test_lens_render_counts(sched_ref):
-    rgb, bgr, st = sched_ref
-    assert st.samples == 40 * 24 * 64 and st.rays_primary == st.samples
-    assert st.rays_inline == 0 and st.tail_launches == 0 and st.rays_tail == 0
-    assert np.isfinite(rgb).all() and rgb.max() > 0
-
-
-def test_steps_and_flush_equal_one_call_under_a_lens(hip, sched_ref):
-    hs, p = _sched_params()
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        sc.begin(p)
-        st = _abi.Stats()
-        for _ in range(4):
-            sc.step(16, st)
-        sc.flush(st)
-        rgb, bgr = sc.resolve()
-    _assert_is_ref((rgb, bgr, st), sched_ref, "4 steps of 16 + flush")
-
-
-def test_tile_partition_assembles_to_the_full_frame_under_a_lens(hip, sched_ref):
-    hs, p = _sched_params()
-    acc, acc_b = np.zeros_like(sched_ref[0]), np.zeros_like(sched_ref[1])
-    tot = {k: 0 for k in counters(sched_ref[2])}
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        for r in range(3):
-            part, part_b, st = sc.render(_with(p, tile_rank=r, tile_nranks=3))
-            assert not ((acc != 0) & (part != 0)).any()
-            assert st.rays_inline == 0 and st.tail_launches == 0
-            acc += part
-            acc_b += part_b
-            for k, v in counters(st).items():
-                tot[k] += v
-    assert same_bits(acc, sched_ref[0]) and np.array_equal(acc_b, sched_ref[1])
-    assert tot == counters(sched_ref[2])
-
-
-SCHEDULES = [
-    dict(JADE_BATCH="0"), dict(JADE_BATCH="1"), dict(JADE_SHADE_SPLIT="0"), dict(JADE_SHADE_SPLIT="1"), dict(JADE_RAY_RECORDS="0"),
-    dict(JADE_RAY_RECORDS="1"), dict(JADE_SORT="1", JADE_SORT_MIN="64"), dict(JADE_SORT="1", JADE_SORT_MIN="64", JADE_SORT_KEYS_KERNEL="1"),
-    dict(JADE_RECORDS_PER_PIXEL="1"), dict(JADE_RECORDS_PER_PIXEL="64"), dict(JADE_SHADE_SPLIT="0", JADE_BATCH="0", JADE_RAY_RECORDS="0"),
-    # switches of kernels that have no lens form: no effect under a lens
-    dict(JADE_FUSED="0"), dict(JADE_FUSED="1"), dict(JADE_LIGHT_PACKET="0"), dict(JADE_LIGHT_PACKET="1"), dict(JADE_TAIL="0"), dict(JADE_TAIL="1"),
-    dict(JADE_SHADE_BINNED="0"), dict(JADE_SHADE_BINNED="1"), dict(JADE_FUSED="0", JADE_TAIL="0", JADE_SHADE_BINNED="1", JADE_LIGHT_PACKET="0"),
-]
-
-
-@pytest.mark.parametrize("env", SCHEDULES, ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
-def test_schedules_under_a_lens_are_one_result(hip, sched_ref, monkeypatch, env):
-    hs, p = _sched_params()
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        out = sc.render(p)
-        early = sc.render(_with(p, walk=_abi.WALK_EARLY_EXIT))
-    _assert_is_ref(out, sched_ref, env)
-    assert same_bits(early[0], sched_ref[0]) and np.array_equal(early[1], sched_ref[1]), "early exits change no bit under a lens either"
-
-
-# ------------------------------------------------------------------------------------------------------------ 5. nothing in view --
+# ------------------------------------------------------------------------------------------------------------ 4. nothing in view --
 
 def test_with_nothing_in_view_the_lens_frame_is_the_pinhole_frame(hip):
-    """The geometry is behind the camera and the sky one constant.  The constant lies ABOVE the lookup's clamp at 10
-    (PathTrace.cu:694-702): the bilinear lookup of a constant map returns it only up to an ulp that depends on the direction (four
-    weights that add up to 1 +- 2^-24), and the clamp makes (10, 10, 10) of every such value - so that every sample of both frames is
-    the same constant bit for bit, whatever its ray."""
-    b = H.SceneBuilder()
-    b.add_mesh(np.array([[-1, -1, 4], [-1, 1, 4], [1, 1, 4], [1, -1, 4]], np.float32), TL.QUAD_I, H.material(emissive=(5, 5, 5), brdf=(0.3, 0.3, 0.3)))
-    b.add_mesh(np.array([[-1, -1, 3], [1, -1, 3], [1, 1, 3], [-1, 1, 3]], np.float32), TL.QUAD_I, H.material(brdf=(0.6, 0.5, 0.4)))
-    b.set_env_constant(20.0, 30.0, 40.0)
-    p = B.make_params(40, 24, 8, (0, 0, 0), TL.IDENTITY_CAM)
-    with hip.scene(b.build()) as sc:
+    """camera_cases.nothing_in_view: every sample of both frames is the same constant bit for bit, whatever its ray."""
+    p = B.make_params(40, 24, 8, (0, 0, 0), CC.IDENTITY_CAM)
+    with hip.scene(CC.nothing_in_view()) as sc:
         pin = sc.render(p)
         sc.set_lens(0.3, 2.0)
         lens = sc.render(p)
@@ -290,15 +180,7 @@ def test_with_nothing_in_view_the_lens_frame_is_the_pinhole_frame(hip):
     assert lens[2].samples == pin[2].samples == 40 * 24 * 8 and lens[2].rays_secondary == 0 and lens[2].rays_inline == 0
 
 
-# ------------------------------------------------------------------------------------------- 6. the circle of confusion, on the device --
-
-def _emitter_on_the_axis(z, half=0.01):
-    b = H.SceneBuilder()
-    b.add_mesh(np.array([[-half, -half, -z], [half, -half, -z], [half, half, -z], [-half, half, -z]], np.float32), TL.QUAD_I,
-               H.material(emissive=(5, 5, 5), brdf=(0.3, 0.3, 0.3)))
-    b.set_env_constant(0.0, 0.0, 0.0)
-    return b.build()
-
+# ------------------------------------------------------------------------------------------- 5. the circle of confusion, on the device --
 
 def test_circle_of_confusion_on_the_device(hip):
     """A 0.02-wide emitter across the axis of the identity camera under a black sky, 64 x 64, 256 spp: a pixel is lit iff a sample of
@@ -307,11 +189,11 @@ def test_circle_of_confusion_on_the_device(hip):
     pixel's centre is within R_px + sqrt(2) hw + 0.71 of (32, 32) - within R_px + hw + 1 as long as hw <= 0.7 pixels, as here
     (hw = 0.48 / z pixels).  Hard bounds of the geometry, not statistics."""
     W, A, f, half = 64, 0.5, 2.0, 0.01
-    p = B.make_params(W, W, 256, (0, 0, 0), TL.IDENTITY_CAM)
+    p = B.make_params(W, W, 256, (0, 0, 0), CC.IDENTITY_CAM)
     yy, xx = np.mgrid[0:W, 0:W]
     dist = np.sqrt((xx - 32.0) ** 2 + (yy - 32.0) ** 2)
     for z in (f, 2 * f, f / 2):
-        with hip.scene(_emitter_on_the_axis(z, half)) as sc:
+        with hip.scene(CC.emitter_on_the_axis(z, half)) as sc:
             pin = sc.render(p, want_bgr8=False)[0].sum(-1) > 0
             sc.set_lens(A, f)
             rgb, _, st = sc.render(p, want_bgr8=False)
@@ -332,34 +214,16 @@ def test_circle_of_confusion_on_the_device(hip):
             assert lit.sum() > 4 * pin.sum()
 
 
-# --------------------------------------------------------------------------------------------------------------------- 7. adaptive --
+# --------------------------------------------------------------------------------------------------------------------- 6. adaptive --
 
 def test_adaptive_tiles_equal_uniform_lens_renders(hip):
-    hs, cfg = config_scene("tinyjade")
-    p = B.params_from_config(cfg, spp=16)
-    p.width, p.height = 64, 48
-    floor = 0.01
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        sc.begin(_with(p, spp=2))
-        sc.step(2)
-        e = np.sort(tile_errors(sc.error_map(floor), 4, 3).ravel())
-        e = e[np.isfinite(e)]
-        rel = next(float(0.5 * (e[i] + e[i + 1])) for i in range(len(e) // 2, len(e) - 1) if e[i + 1] > e[i] * (1 + 1e-3))
-        rgb, bgr, tspp, st = sc.render_adaptive(p, 2, rel, floor)
-        ks = sorted(set(tspp.ravel().tolist()))
-        assert len(ks) >= 2 and st.rays_inline == 0, ks
-        for k in ks:
-            r_u, b_u, _ = sc.render(_with(p, spp=int(k)))
-            m = tile_mask(p.width, p.height, np.flatnonzero(tspp.ravel() == k))
-            assert same_bits(rgb[m], r_u[m]) and np.array_equal(bgr[m], b_u[m]), k
-    assert st.samples == int(tspp.sum()) * 256
+    CC.check_adaptive_tiles_equal_uniform_renders(hip, lambda sc: sc.set_lens(*SCHED_LENS))
 
 
-# ---------------------------------------------------------------------------------------------------------------------- 8. guides --
+# ---------------------------------------------------------------------------------------------------------------------- 7. guides --
 
 def test_guides_follow_the_lens(hip):
-    hs = TJ.build("open_floor")
+    hs = build("open_floor")
     S = jade_spec.Scene(hs)
     eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
     size, frame = 12, 1
@@ -391,47 +255,10 @@ def test_guides_follow_the_lens(hip):
 
 
 def test_denoise_under_a_lens_is_denoise_image_on_its_own_inputs(hip):
-    hs, cfg = config_scene("tinyjade")
-    p = B.params_from_config(cfg, spp=16)
-    p.width, p.height = 40, 24
-    d = hip.denoise_defaults()
-    with hip.scene(hs) as sc:
-        sc.set_lens(*SCHED_LENS)
-        sc.begin(p)
-        sc.step(16)
-        r1, b1 = sc.denoise(d)
-        g = sc.guides(d.guide_spp)
-        rgb, _ = sc.resolve(want_bgr8=False)
-    got = hip.denoise_image(rgb, g["variance"], g["albedo"], g["normal"], g["depth"], params=d)
-    assert same_bits(got, r1) and np.isfinite(r1).all()
+    CC.check_denoise_is_denoise_image_on_its_own_inputs(hip, lambda sc: sc.set_lens(*SCHED_LENS))
 
 
-# ---------------------------------------------------------------------------------------------------------------- 9. render_multi --
-
-def test_render_multi_under_equal_lenses_and_its_refusal_of_unequal_ones(hip, sched_ref):
-    hs, p = _sched_params()
-    with hip.scene(hs) as s0, hip.scene(hs) as s1:
-        s0.set_lens(*SCHED_LENS)
-        s1.set_lens(*SCHED_LENS)
-        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
-        assert same_bits(rgb, sched_ref[0]) and np.array_equal(bgr, sched_ref[1])
-        assert counters(st) == counters(sched_ref[2]) and st.rays_inline == 0
-        for other in ((SCHED_LENS[0], 0.5), (0.03, SCHED_LENS[1]), None):
-            s1.set_lens(*other) if other else s1.set_lens(None)
-            with pytest.raises(B.JadeError) as ei:
-                B.render_multi(hip, [s0, s1], p)
-            assert ei.value.code == _abi.JADE_ERR_INVALID
-
-
-# ------------------------------------------------------------------------------------------------------------------------- 10. CLI --
-
-def _read_pfm(path):
-    with open(path, "rb") as f:
-        assert f.readline().strip() == b"PF"
-        w, h = (int(v) for v in f.readline().split())
-        assert float(f.readline()) < 0  # little-endian
-        return np.frombuffer(f.read(), "<f4").reshape(h, w, 3)
-
+# ------------------------------------------------------------------------------------------------------------------------- 8. CLI --
 
 def test_cli_aperture_with_autofocus_writes_the_python_frame(hip, tmp_path):
     size, spp, px, py = 32, 8, 16, 15  # the `tiny` configuration: geometry in the middle, the sky around it
@@ -447,7 +274,7 @@ def test_cli_aperture_with_autofocus_writes_the_python_frame(hip, tmp_path):
         rgb, _, _ = sc.render(p, want_bgr8=False)
         pin, _, _ = (sc.set_lens(None), sc.render(p, want_bgr8=False))[1]
     assert f"focus: pixel ({px}, {py}) is {f:.9g} away" in r.stdout, r.stdout
-    assert same_bits(_read_pfm(tmp_path / "lens.pfm"), rgb) and not same_bits(rgb, pin)
+    assert same_bits(read_pfm(tmp_path / "lens.pfm"), rgb) and not same_bits(rgb, pin)
     # the other flags keep working on top
     r = subprocess.run(common + ["--focus", "13.5", "--adaptive", "0.5", "--min-spp", "2", "--denoise", "--glare", "0.1", "--exposure", "auto", "--out", "all.ppm"],
                        capture_output=True, text=True, timeout=300, cwd=tmp_path)

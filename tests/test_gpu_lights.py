@@ -1,85 +1,21 @@
 """One-light sampling on the device (include/jade_bvh.h, "The lights, stated"; jade_scene_set_light_sampling): the draw against
-tests/lights_spec.py bit for bit, the two anchors (no emitter entry: JADE_LIGHTS_ALL's render; the default mode: today's), the
-invariants every mode is held to, the work and the memory the mode is for, the integral it estimates, what it refuses, and (section 8)
-the render against tests/jade_spec.py's one-light arm, sample for sample: how the shading kernels USE a draw."""
-import os
-import subprocess
-
+tests/lights_spec.py bit for bit, the two anchors (no emitter entry: JADE_LIGHTS_ALL's render; the default mode: today's), what the frame
+and its counters are next to all lights', the work and the memory the mode is for, the integral it estimates, and (section 7) the render
+against tests/jade_spec.py's one-light arm, sample for sample: how the shading kernels USE a draw.  The seams every mode is held to -
+twice, the walks, steps, tile shares, schedules, the refusals, jade_render_multi, the command line - are in
+tests/test_gpu_mode_seams.py (case "one-light" of tests/mode_seams.py)."""
 import numpy as np
 import pytest
 
 import lights_spec as spec
-import test_gpu_lens as GL
-from conftest import B, ROOT, counters
+import mode_seams as MS
+import spec_scenes as SP
+from conftest import B, counters
 from jaderaytracerendering_amd import _abi, host as H
-from jaderaytracerendering_amd.host import HostScene
+from lamp_scenes import HH, SPP, W, lamp_scene, params
+from render_helpers import all_counters, same_bits, welch_t
 
 pytestmark = pytest.mark.gpu
-
-CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
-all_counters, same_bits, _with = GL.all_counters, GL.same_bits, GL._with
-W, HH, SPP = 48, 40, 6
-QUAD_I = np.int32([[0, 1, 2], [0, 2, 3]])
-
-
-# ------------------------------------------------------------------------------------------------------------------ the scenes --
-
-def _jade():
-    return H.material(brdf=(0.3, 0.4, 0.5), reflex_mode=_abi.MIRROR, refract_mode=_abi.SUB_SURFACE, refract_rate=(0.3, 0.4, 0.5),
-                      refract_albedo=(0.3, 0.5, 0.7), refract_index=2.66)
-
-
-def _build(freq):
-    """A diffuse slab, a diffuse ball, a small SUB_SURFACE box (so the diffuse, the SSS-diffuse and the BSSRDF branch all sample the
-    emitters), a geodesic lamp of 20 freq^2 triangles and two quad lights of unequal power, under a 16 x 8 sky."""
-    b = H.SceneBuilder()
-    try:
-        T = H.transform_matrix
-        b.add_proc("box", 0, H.material(brdf=(0.6, 0.5, 0.4)), T(trans=(0, -1.1, 0), scale=(7, 0.2, 7)))
-        b.add_proc("geodesic", 2, H.material(brdf=(0.5, 0.6, 0.5)), T(trans=(-1.1, -0.45, 0.2), scale=(0.5,) * 3))
-        b.add_proc("box", 0, _jade(), T(rot_deg=(0, 35, 0), trans=(0.55, -0.7, 0.9), scale=(0.6,) * 3))
-        b.add_proc("geodesic", freq, H.material(emissive=(30, 27, 22), brdf=(0.3,) * 3), T(trans=(0.3, 1.3, 0.4), scale=(0.25,) * 3))
-        big = np.float32([[-2.6, 0.2, -1.8], [-1.4, 0.2, -1.8], [-1.4, 1.4, -1.8], [-2.6, 1.4, -1.8]])
-        b.add_mesh(big, QUAD_I, H.material(emissive=(9, 12, 15), brdf=(0.3,) * 3))
-        small = np.float32([[1.8, -0.6, 1.6], [2.1, -0.6, 1.3], [2.1, -0.3, 1.3], [1.8, -0.3, 1.6]])
-        b.add_mesh(small, QUAD_I, H.material(emissive=(40, 10, 4), brdf=(0.3,) * 3))
-        b.set_env_sky(16, 8)
-        return b.build()
-    finally:
-        b.close()
-
-
-_scenes = {}
-
-
-def lamp_scene(name="lamp"):
-    """"lamp": the 80-triangle lamp and the two quads, 84 entries.  "lamp82" / "lamp3" / "lamp1": the same triangles with 82 (the lamp
-    and one triangle of each quad), 3 and 1 of them listed - an emissive triangle need not be listed (it is then found by hitting it
-    only).  "none": none listed.  "big": the lamp at frequency 64, 81 920 + 4 entries."""
-    if name not in _scenes:
-        if name == "lamp":
-            hs = _build(2)
-            assert len(hs.a["emit"]) == 84
-        elif name == "big":
-            hs = _build(64)
-            assert len(hs.a["emit"]) == 81924
-        else:
-            base = lamp_scene("lamp")
-            hs = HostScene({k: np.array(v, copy=True) for k, v in base.a.items()}, base.bvh_depth)
-            e = base.a["emit"]
-            tf = base.tri_f32()
-            lamp = [i for i in e if tf[i, 13] == 30]
-            quads = [i for i in e if tf[i, 13] != 30]
-            assert len(lamp) == 80 and len(quads) == 4
-            pick = {"lamp82": lamp + [quads[0], quads[2]], "lamp3": [lamp[7], quads[0], quads[3]], "lamp1": [quads[1]], "none": []}[name]
-            hs.a["emit"] = np.int32(pick)
-        _scenes[name] = hs
-    return _scenes[name]
-
-
-def params(spp=SPP, w=W, h=HH, **kw):
-    eye, cam = H.camera_orbit(5.0, 20.0, 30.0)
-    return B.make_params(w, h, spp, eye, cam, **kw)
 
 
 def render(hip, name, p, mode):
@@ -181,12 +117,7 @@ def test_the_default_mode_is_todays_render_after_a_round_trip(hip, all_ref):
     assert fresh[2].rays_inline > 0, "the fused first pass runs"
 
 
-# ------------------------------------------------------------------------------------------------------------- 3. the invariants --
-
-def _is_ref(out, ref, what=""):
-    assert same_bits(out[0], ref[0]) and np.array_equal(out[1], ref[1]), what
-    assert counters(out[2]) == counters(ref[2]), what
-
+# ------------------------------------------------------------------------------------------------------------- 3. the frame --
 
 def test_the_frame_is_finite_lit_and_not_all_lights(one_ref, all_ref):
     rgb, bgr, st = one_ref
@@ -197,73 +128,10 @@ def test_the_frame_is_finite_lit_and_not_all_lights(one_ref, all_ref):
     assert st.rays_primary == all_ref[2].rays_primary
 
 
-def test_the_same_bits_twice(hip, one_ref):
-    _is_ref(render(hip, "lamp", params(), _abi.LIGHTS_ONE), one_ref)
-
-
-@pytest.mark.parametrize("walk", [_abi.WALK_REFERENCE, _abi.WALK_EARLY_EXIT, _abi.WALK_EARLY_EXIT_CACHED])
-def test_the_same_bits_under_the_three_walks(hip, one_ref, walk):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        for _ in range(2 if walk == _abi.WALK_EARLY_EXIT_CACHED else 1):  # (the second time with what the first left in the cache)
-            rgb, bgr, st = sc.render(params(walk=walk))
-            assert same_bits(rgb, one_ref[0]) and np.array_equal(bgr, one_ref[1])
-            c, r = counters(st), counters(one_ref[2])
-            assert {k: v for k, v in c.items() if k not in ("nodes_visited", "tris_tested")} == {k: v for k, v in r.items() if k not in ("nodes_visited", "tris_tested")}
-
-
-def test_steps_equal_one_call(hip, one_ref):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        sc.begin(params())
-        st = _abi.Stats()
-        for _ in range(3):
-            sc.step(2, st)
-        sc.set_light_sampling(_abi.LIGHTS_ALL)  # a render in progress keeps the mode it began with
-        sc.flush(st)
-        rgb, bgr = sc.resolve()
-    _is_ref((rgb, bgr, st), one_ref, "3 steps of 2 + flush")
-
-
-def test_two_tile_shares_assemble_to_the_frame(hip, one_ref):
-    acc, acc_b = np.zeros_like(one_ref[0]), np.zeros_like(one_ref[1])
-    tot = {k: 0 for k in counters(one_ref[2])}
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        for r in range(2):
-            part, part_b, st = sc.render(params(tile_rank=r, tile_nranks=2))
-            assert not ((acc != 0) & (part != 0)).any()
-            acc += part
-            acc_b += part_b
-            for k, v in counters(st).items():
-                tot[k] += v
-    assert same_bits(acc, one_ref[0]) and np.array_equal(acc_b, one_ref[1])
-    assert tot == counters(one_ref[2])
-
-
-SCHEDULES = [
-    dict(JADE_RECORDS_PER_PIXEL="1"), dict(JADE_FUSED="0"), dict(JADE_SHADE_SPLIT="0", JADE_BATCH="0", JADE_RAY_RECORDS="0"),
-    dict(JADE_SORT="1", JADE_SORT_MIN="64"), dict(JADE_SORT="1", JADE_SORT_MIN="64", JADE_SORT_KEYS_KERNEL="1"),
-    # switches of kernels this mode does not run: no effect
-    dict(JADE_SHADE_BINNED="1", JADE_TAIL="1"), dict(JADE_TAIL="0", JADE_LIGHT_PACKET="0"),
-]
-
-
-@pytest.mark.parametrize("env", SCHEDULES, ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("env", MS.COMMON_SCHEDULES, ids=MS.schedule_id)
 def test_records_per_pixel_and_schedules_are_one_result(hip, one_ref, monkeypatch, env):
-    """JADE_RECORDS_PER_PIXEL=1 against the default (6 spp: 8 records per pixel), and the schedules that change how a ray's kind is
-    read off its slot number (ordered queues, with the keys from either kernel)."""
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        sc.begin(params())
-        rpp = sc.query(_abi.Q_RECORDS_PER_PIXEL)
-        out = sc.render(params(walk=_abi.WALK_EARLY_EXIT))
-    assert rpp == (1 if "JADE_RECORDS_PER_PIXEL" in env else 8)
-    assert same_bits(out[0], one_ref[0]) and np.array_equal(out[1], one_ref[1]), env
-    c, r = counters(out[2]), counters(one_ref[2])
-    assert {k: v for k, v in c.items() if k not in ("nodes_visited", "tris_tested")} == {k: v for k, v in r.items() if k not in ("nodes_visited", "tris_tested")}
+    """Kept for its ids, which cannot all be retired in one change: tests/test_gpu_mode_seams.py runs this check for every case and environment."""
+    MS.check_schedule(hip, MS.BY_NAME["one-light"], one_ref, env, monkeypatch.setenv)
 
 
 def test_secondary_rays_are_the_sum_of_their_five_parts(one_ref):
@@ -367,11 +235,6 @@ WELCH_SPP = 8      # the smallest power of two at which the scaled group is told
 WELCH_LIMIT = 4.5
 
 
-def welch_t(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float((a.mean() - b.mean()) / np.sqrt(a.var(ddof=1) / len(a) + b.var(ddof=1) / len(b)))
-
-
 def welch_totals(hip, spp):
     """Per mode, the WELCH_K totals of radiance over the lit pixels: frames of independent samples (frame = 1000 k), both modes from the
     same seeds.  Lit pixels: those that do not look straight into a lamp - every channel below 4, the weakest lamp channel - in an
@@ -404,91 +267,21 @@ def test_both_modes_estimate_the_same_integral(hip):
     assert abs(t_up) > WELCH_LIMIT and abs(t_down) > WELCH_LIMIT
 
 
-# -------------------------------------------------------------------------------------------------------------- 7. the refusals --
-
-def test_the_oracle_has_no_such_entry_point(oracle):
-    with oracle.scene(lamp_scene("lamp1")) as so:
-        with pytest.raises(B.JadeError) as ei:
-            so.set_light_sampling(_abi.LIGHTS_ONE)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
-        with pytest.raises(B.JadeError):
-            so.light_sampling
-
-
-def test_an_unknown_mode_is_invalid_and_leaves_the_mode(hip):
-    with hip.scene(lamp_scene("lamp1")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        for bad in (2, -1, 255):
-            with pytest.raises(B.JadeError) as ei:
-                sc.set_light_sampling(bad)
-            assert ei.value.code == _abi.JADE_ERR_INVALID
-            assert sc.light_sampling == _abi.LIGHTS_ONE
-
-
-def test_a_lens_or_a_shutter_is_refused_by_name(hip, one_ref):
-    p = params()
-    eye, cam = np.array(p.eye[:], np.float32), np.array(p.camera[:], np.float32)
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_light_sampling(_abi.LIGHTS_ONE)
-        sc.set_lens(0.05, 4.0)
-        with pytest.raises(B.JadeError) as ei:
-            sc.begin(p)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_LIGHTS_ONE" in str(ei.value) and "lens" in str(ei.value)
-        sc.set_lens(0.0)
-        sc.set_shutter(eye, cam)
-        with pytest.raises(B.JadeError) as ei:
-            sc.render(p)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_LIGHTS_ONE" in str(ei.value) and "shutter" in str(ei.value)
-        sc.set_shutter(None)
-        _is_ref(sc.render(p), one_ref, "the refusals left the handle usable")
-        # ... and with all lights both still render
-        sc.set_light_sampling(_abi.LIGHTS_ALL)
-        sc.set_lens(0.05, 4.0)
-        assert np.isfinite(sc.render(p)[0]).all()
-
-
-def test_render_multi_refuses_scenes_of_different_modes(hip, one_ref):
-    p = params()
-    hs = lamp_scene("lamp")
-    with hip.scene(hs) as s0, hip.scene(hs) as s1:
-        s0.set_light_sampling(_abi.LIGHTS_ONE)
-        with pytest.raises(B.JadeError) as ei:
-            B.render_multi(hip, [s0, s1], p)
-        assert ei.value.code == _abi.JADE_ERR_INVALID and "light sampling" in str(ei.value)
-        s1.set_light_sampling(_abi.LIGHTS_ONE)
-        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
-    assert same_bits(rgb, one_ref[0]) and np.array_equal(bgr, one_ref[1])
-
-
-def test_the_command_line(tmp_path):
-    out = tmp_path / "one.ppm"
-    r = subprocess.run([CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4", "--one-light", "--out", str(out)],
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    start = [ln for ln in r.stdout.splitlines() if ln.startswith("Start...")]
-    assert len(start) == 1 and start[0].endswith("on hip-gfx950, one light per vertex") and out.exists()
-    r = subprocess.run([CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4", "--one-light", "--backend",
-                        os.path.join(ROOT, "oracle", "libjade_oracle.so"), "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "--one-light needs the HIP backend" in r.stderr
-
-
-# ------------------------------------------------------------------------ 8. the render against the float64 statement, sample for sample --
+# ------------------------------------------------------------------------ 7. the render against the float64 statement, sample for sample --
 # How bounce_branch<.., LIGHTS> and consume<.., LIGHTS> USE a draw: jade_spec's one-light arm (include/jade_bvh.h's text in float64; checked
-# without a GPU in tests/test_lights_spec_cpu.py) against 12 x 12 frames at 1 spp, by test_jade_spec.compare and its bar, unchanged: a
+# without a GPU in tests/test_lights_spec_cpu.py) against 12 x 12 frames at 1 spp, by spec_scenes.compare and its bar, unchanged: a
 # sample agrees when every channel is within 1e-4 relative (floor 1e-3), at most 2 % may disagree, bssrdf-coplanar samples are left out
 # (here: at most 5 % of a case).
-
-import test_jade_spec as TJ  # noqa: E402
 
 _checked = {}
 
 
 def checked(hip, case):
-    """compare() of one case of TJ.LIGHT_CASES, once per session: (seen, bad, n, skipped, {"frames", "worst"})."""
+    """compare() of one case of SP.LIGHT_CASES, once per session: (seen, bad, n, skipped, {"frames", "worst"})."""
     if case not in _checked:
-        c = TJ.LIGHT_CASES[case]
+        c = SP.LIGHT_CASES[case]
         out = {}
-        r = TJ.compare(hip, c["kind"], c["size"], c["frames"], c["need"], sky=c.get("sky", False), env_sampling=c.get("env_sampling", _abi.ENV_REFERENCE),
+        r = SP.compare(hip, c["kind"], c["size"], c["frames"], c["need"], sky=c.get("sky", False), env_sampling=c.get("env_sampling", _abi.ENV_REFERENCE),
                        light_sampling=_abi.LIGHTS_ONE, max_left_out=0.05, out=out)
         _checked[case] = r + (out,)
     return _checked[case]
@@ -496,15 +289,15 @@ def checked(hip, case):
 
 def one_light_frames(hip, case, kind=None):
     """The frames of a case as compare renders them, from a scene handle of its own (kind: another emitter list of the same geometry)."""
-    c = TJ.LIGHT_CASES[case]
+    c = SP.LIGHT_CASES[case]
     eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
-    with hip.scene(TJ.build(kind or c["kind"], c.get("sky", False))) as sc:
+    with hip.scene(SP.build(kind or c["kind"], c.get("sky", False))) as sc:
         sc.set_light_sampling(_abi.LIGHTS_ONE)
         return {f: sc.render(B.make_params(c["size"], c["size"], 1, eye, cam, frame=f, threads=2, env_sampling=c.get("env_sampling", _abi.ENV_REFERENCE)),
                              want_bgr8=False)[0] for f in c["frames"]}
 
 
-@pytest.mark.parametrize("case", sorted(TJ.LIGHT_CASES))
+@pytest.mark.parametrize("case", sorted(SP.LIGHT_CASES))
 def test_the_render_is_the_float64_statement_sample_for_sample(hip, case):
     """two_lamps: two lamps of unequal power, a duplicate entry and a listed non-emitter (own and alias, the side test's `continue`, lit
     and shadowed, in the diffuse, SSS-diffuse and BSSRDF branch); ..._sky and ..._sky_importance: under the textured sky in both
@@ -517,7 +310,7 @@ def test_the_render_is_the_float64_statement_sample_for_sample(hip, case):
     two_lamps 560 / 0 / 16, 3.1e-6; two_lamps_sky 422 / 0 / 10, 4.6e-6; two_lamps_sky_importance 421 / 0 / 11, 7.7e-6; one_entry 422 / 0 / 10,
     3.1e-6; fan 560 / 0 / 16, 1.7e-5; dark_list 422 / 0 / 10, 1.7e-5 (the bar is 1e-4; the all-lights cases' worst is 5e-6)."""
     seen, bad, n, skipped, out = checked(hip, case)
-    assert n + skipped == len(TJ.LIGHT_CASES[case]["frames"]) * 144
+    assert n + skipped == len(SP.LIGHT_CASES[case]["frames"]) * 144
     assert out["worst"] <= 1e-4
 
 
@@ -530,10 +323,10 @@ def test_a_dark_list_still_moves_the_draws(hip):
         assert not same_bits(rgb, bare[f])
 
 
-@pytest.mark.parametrize("env", [SCHEDULES[1], SCHEDULES[3], SCHEDULES[0]], ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
+@pytest.mark.parametrize("env", [dict(JADE_FUSED="0"), dict(JADE_SORT="1", JADE_SORT_MIN="64"), dict(JADE_RECORDS_PER_PIXEL="1")], ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
 def test_the_checked_frames_are_the_same_bits_under_other_schedules(hip, monkeypatch, env):
     """The unfused first pass, ordered queues and one record per pixel give the very arrays that were compared with the statement: the
-    schedule matrix of section 3 hangs on a frame that has been checked."""
+    schedule matrix of tests/test_gpu_mode_seams.py hangs on a frame that has been checked."""
     _, _, _, _, out = checked(hip, "two_lamps")
     for k, v in env.items():
         monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)

@@ -1,28 +1,26 @@
 """Multiple importance sampling of the emitters on the device (include/jade_bvh.h, "The direct light, stated";
 jade_scene_set_direct_sampling): the weight function against tests/mis_spec.py within a derived bound, the anchors that are cosine's
-render bit for bit, counters that are cosine's while the frames differ, the seams every mode is held to, the bound the mode exists for
-next to a lamp's contact edge, the render against mis_spec's arm sample for sample (tests/mis_cases.py), the integral it estimates
-(Welch's t against the cosine mode, which is the parent's code) and what it refuses."""
+render bit for bit, counters that are cosine's while the frames differ, the bound the mode exists for next to a lamp's contact edge, the
+render against mis_spec's arm sample for sample (tests/mis_cases.py) and the integral it estimates (Welch's t against the cosine mode,
+which is the parent's code).  The seams every mode is held to - twice, the walks, steps, tile shares, schedules, the refusals,
+jade_render_multi, the command line - are in tests/test_gpu_mode_seams.py (case "MIS" of tests/mode_seams.py)."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import mis_cases as MC
 import mis_spec as spec
-import test_gpu_lens as GL
-import test_gpu_lights as LI
-import test_jade_spec as TJ
-from conftest import B, ROOT, counters
+import mode_seams as MS
+import spec_scenes as SP
+from conftest import B, counters
 from jaderaytracerendering_amd import _abi
+from lamp_scenes import lamp_scene, params
+from render_helpers import all_counters, same_bits, welch_t
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
-all_counters, same_bits = GL.all_counters, GL.same_bits
 F32 = np.float32
 COS, UNI = _abi.BOUNCE_COSINE, _abi.BOUNCE_UNIFORM
 MIS, RAYS = _abi.DIRECT_MIS, _abi.DIRECT_RAYS
@@ -124,9 +122,6 @@ def test_device_terms_are_the_statement_within_the_derived_bound(hip_debug):
 
 
 # ---------------------------------------------------------------------------------------------------- 2. anchors, bit for bit --
-W, HH, SPP = LI.W, LI.HH, LI.SPP
-params, lamp_scene = LI.params, LI.lamp_scene
-
 
 def render(hip, p, direct=MIS, name="lamp", lights=ALL, hs=None):
     with hip.scene(hs if hs is not None else lamp_scene(name)) as sc:
@@ -176,7 +171,7 @@ def test_the_default_mode_is_todays_render_after_a_round_trip(hip):
     assert ref[2].rays_inline > 0 and ref[2].tail_launches > 0, "the parent's schedule: fused first pass and tail kernel"
 
 
-# ------------------------------------------------------------------------------------- 3. counters are cosine's; seams --
+# ------------------------------------------------------------------------------------- 3. counters are cosine's --
 
 @pytest.fixture(scope="module")
 def mis_ref(hip):
@@ -204,56 +199,10 @@ def test_the_other_three_kernels_keep_cosines_counters_too(hip, lights, envs):
     _same(render(hip, p, MIS, lights=lights), a, "twice")
 
 
-def test_the_same_bits_twice(hip, mis_ref):
-    _same(render(hip, params()), mis_ref)
-
-
-@pytest.mark.parametrize("walk", [_abi.WALK_REFERENCE, _abi.WALK_EARLY_EXIT, _abi.WALK_EARLY_EXIT_CACHED])
-def test_the_same_bits_under_the_three_walks(hip, mis_ref, walk):
-    out = render(hip, params(walk=walk))
-    assert same_bits(out[0], mis_ref[0]) and np.array_equal(out[1], mis_ref[1]), walk
-
-
-def test_steps_equal_one_call(hip, mis_ref):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.set_direct_sampling(MIS)
-        sc.begin(params())
-        st = _abi.Stats()
-        for _ in range(3):
-            sc.step(2, st)
-        sc.set_direct_sampling(RAYS)  # a render in progress keeps the mode it began with
-        sc.flush(st)
-        rgb, bgr = sc.resolve()
-    assert same_bits(rgb, mis_ref[0]) and np.array_equal(bgr, mis_ref[1])
-    assert counters(st) == counters(mis_ref[2])
-
-
-def test_two_tile_shares_assemble_to_the_frame(hip, mis_ref):
-    acc, acc_b = np.zeros_like(mis_ref[0]), np.zeros_like(mis_ref[1])
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.set_direct_sampling(MIS)
-        for r in range(2):
-            part, part_b, _ = sc.render(params(tile_rank=r, tile_nranks=2))
-            assert not ((acc != 0) & (part != 0)).any()
-            acc += part
-            acc_b += part_b
-    assert same_bits(acc, mis_ref[0]) and np.array_equal(acc_b, mis_ref[1])
-
-
-@pytest.mark.parametrize("env", [dict(JADE_RECORDS_PER_PIXEL="1"), dict(JADE_FUSED="0")], ids=["RECORDS_PER_PIXEL=1", "FUSED=0"])
+@pytest.mark.parametrize("env", MS.COMMON_SCHEDULES[:2], ids=MS.schedule_id)
 def test_records_per_pixel_and_the_unfused_first_pass_are_one_result(hip, mis_ref, monkeypatch, env):
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_bounce_sampling(COS)
-        sc.set_direct_sampling(MIS)
-        sc.begin(params())
-        rpp = sc.query(_abi.Q_RECORDS_PER_PIXEL)
-        out = sc.render(params())
-    assert rpp == (1 if "JADE_RECORDS_PER_PIXEL" in env else 8)
-    assert same_bits(out[0], mis_ref[0]) and np.array_equal(out[1], mis_ref[1]), env
+    """Kept for its ids, which cannot all be retired in one change: tests/test_gpu_mode_seams.py runs this check for every case and environment."""
+    MS.check_schedule(hip, MS.BY_NAME["MIS"], mis_ref, env, monkeypatch.setenv)
 
 
 def test_adaptive_sampling_the_denoiser_and_environment_importance_run_on_top(hip):
@@ -267,21 +216,6 @@ def test_adaptive_sampling_the_denoiser_and_environment_importance_run_on_top(hi
         assert np.isfinite(dn).all() and dn.max() > 0
 
 
-def test_render_multi_with_equal_modes_gives_the_one_scene_frame_and_refuses_unequal_ones(hip, mis_ref):
-    p = params()
-    hs = lamp_scene("lamp")
-    with hip.scene(hs) as s0, hip.scene(hs) as s1:
-        for s in (s0, s1):
-            s.set_bounce_sampling(COS)
-        s0.set_direct_sampling(MIS)
-        with pytest.raises(B.JadeError) as ei:
-            B.render_multi(hip, [s0, s1], p)
-        assert ei.value.code == _abi.JADE_ERR_INVALID and "direct sampling" in str(ei.value)
-        s1.set_direct_sampling(MIS)
-        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
-    assert same_bits(rgb, mis_ref[0]) and np.array_equal(bgr, mis_ref[1])
-
-
 # ------------------------------------------------------------------------------------------------------------------ 4. the bound --
 CONTACT_SEEDS = (0, 1, 2, 3, 4)   # chosen on the CPU with the two specs: cosine's largest floor sample is 4.4, 1.4, 11.2, 0.9, 2.0 x the bound
 
@@ -291,7 +225,7 @@ def contact_bound():
     lamp's two triangles, each listed once: mu = 1 - of at most pi f Le |n| |ne| each, and a bounce term of at most pi f Le |n| |ne| m / RR:
     V = pi f Le (2 + 1 / 0.9).  A path's vertices add up with the indirect rate f (|n| / 2) / RR per vertex (the cosine mode's closed
     form), a geometric series: V / (1 - r).  1e-5 on top for fp32 rounding."""
-    f = np.float64(TJ.FLOOR["brdf"]) * float(F32(1.0 / spec.PI))
+    f = np.float64(SP.FLOOR["brdf"]) * float(F32(1.0 / spec.PI))
     V = math.pi * f * np.float64(MC.CONTACT_LE) * (2 + 1 / 0.9)
     r = f * 0.5 / 0.9
     return V / (1 - r) * (1 + 1e-5)
@@ -332,7 +266,6 @@ def test_the_render_is_the_statement_sample_for_sample(hip, case):
 WELCH_K = 8
 WELCH_LIMIT = 4.5
 WELCH_SPP = {"lamp": 8, "contact": 8}   # the smallest power of two at which both scaled groups are told apart (the test's docstring)
-welch_t = LI.welch_t
 
 
 def welch_setup(scene):
@@ -381,52 +314,3 @@ def test_both_modes_estimate_the_same_integral(hip, scene):
     t, t_up, t_down = welch_line(hip, scene, WELCH_SPP[scene])
     assert abs(t) < WELCH_LIMIT
     assert abs(t_up) > WELCH_LIMIT and abs(t_down) > WELCH_LIMIT
-
-
-# ------------------------------------------------------------------------------------------------------------------ 7. the refusals --
-
-def test_without_cosine_bounces_the_mode_is_refused_by_name(hip, mis_ref):
-    with hip.scene(lamp_scene("lamp")) as sc:
-        sc.set_direct_sampling(MIS)
-        with pytest.raises(B.JadeError) as ei:
-            sc.begin(params())
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_DIRECT_MIS" in str(ei.value) and "JADE_BOUNCE_COSINE" in str(ei.value)
-        sc.set_bounce_sampling(COS)
-        out = sc.render(params())
-        assert same_bits(out[0], mis_ref[0]), "the refusal left the handle usable"
-        sc.set_lens(0.05, 4.0)
-        with pytest.raises(B.JadeError) as ei:
-            sc.begin(params())
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED and "JADE_BOUNCE_COSINE" in str(ei.value) and "lens" in str(ei.value), "cosine's own check"
-
-
-def test_an_unknown_mode_is_invalid_and_leaves_the_mode(hip):
-    with hip.scene(lamp_scene("lamp1")) as sc:
-        sc.set_direct_sampling(MIS)
-        for bad in (2, -1, 255):
-            with pytest.raises(B.JadeError) as ei:
-                sc.set_direct_sampling(bad)
-            assert ei.value.code == _abi.JADE_ERR_INVALID
-            assert sc.direct_sampling == MIS
-
-
-def test_the_oracle_has_no_such_entry_point(oracle):
-    with oracle.scene(lamp_scene("lamp1")) as so:
-        with pytest.raises(B.JadeError) as ei:
-            so.set_direct_sampling(MIS)
-        assert ei.value.code == _abi.JADE_ERR_UNSUPPORTED
-        with pytest.raises(B.JadeError):
-            so.direct_sampling
-
-
-def test_the_command_line(tmp_path):
-    out = tmp_path / "mis.ppm"
-    base = [CLI, "--config", "tiny", "--width", "48", "--height", "40", "--spp", "4"]
-    r = subprocess.run(base + ["--bounce", "cosine", "--direct", "mis", "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr
-    start = [ln for ln in r.stdout.splitlines() if ln.startswith("Start...")]
-    assert len(start) == 1 and start[0].endswith("cosine-weighted bounces, emitters by multiple importance sampling") and out.exists()
-    r = subprocess.run(base + ["--direct", "mis", "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "--direct mis" in r.stderr and "--bounce cosine" in r.stderr
-    r = subprocess.run(base + ["--direct", "sideways", "--out", str(out)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 2 and "rays or mis" in r.stderr

@@ -18,7 +18,7 @@ import pytest
 import queue_hooks as Q
 from conftest import WALK_KEYS, COUNTER_KEYS
 from jaderaytracerendering_amd import _abi
-from test_gpu_parity import TOL, _assert_parity
+from render_helpers import TOL, assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -82,7 +82,7 @@ def test_caps_under_the_default_schedule(hip_debug, refs, oracle_frames, name):
         else:
             _crossed(out, (name, cap))
         if cap == 100:  # the oracle's frame, at the parity bar of tests/test_gpu_parity.py
-            err = _assert_parity(oracle_frames[name], out[:3], TOL)
+            err = assert_parity(oracle_frames[name], out[:3], TOL)
             print(f"{name} cap 100 against the oracle: relative L2 {err:.3g}")
     # about half the longest queue: halve c from the total until some queue is longer than c - the longest then lies in (c, 2c]
     c = total

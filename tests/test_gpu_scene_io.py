@@ -12,7 +12,7 @@ import pytest
 from conftest import ORACLE_LIB, ROOT, rel_l2
 from jaderaytracerendering_amd import host as H
 from jaderaytracerendering_amd.backend import HIP_LIB
-from test_host_pipeline import _write_hdr
+from render_helpers import write_hdr
 
 pytestmark = pytest.mark.gpu
 EXE = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
@@ -76,7 +76,7 @@ def test_render_args_obj_hdr_scene_hip_vs_oracle(tmp_path):
     env = np.broadcast_to(np.float32([0.9, 1.1, 1.6]) * (1.2 - yy), (hh, ww, 3)).copy()
     env[4:8, 20:26] = [40.0, 36.0, 30.0]
     hdr = os.path.join(d, "background.hdr")
-    _write_hdr(hdr, env, rle=True)
+    write_hdr(hdr, env, rle=True)
 
     size, spp = (96, 64), 6
     st_o, _ = _run(ORACLE_LIB, args, hdr, os.path.join(d, "o.pfm"), size, spp)

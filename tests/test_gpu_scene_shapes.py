@@ -63,11 +63,11 @@ def test_variant_is_the_same_bits_under_every_schedule_and_walk(hip, monkeypatch
 def test_guides_of_the_patchwork_match_the_spec(hip):
     """jade_render_guides reads the material through the de-duplicated table (mats + tnorm.w): with five materials per object the
     albedo, the mirror decision and the normal must still be the hit triangle's own (test_gpu_denoise.py's float64 statement and bars)."""
-    from test_gpu_denoise import _Geometry, _spec_guide
+    from guide_cases import Geometry, spec_guide
     hs = SS.scene("patchwork")
     p = SS.params()
     p.spp, p.width, p.height = 4, 16, 12  # (the float64 statement takes 20 ms a pixel)
-    S = _Geometry(hs)
+    S = Geometry(hs)
     with hip.scene(hs) as sc:
         sc.begin(p)
         sc.step(4)
@@ -75,6 +75,6 @@ def test_guides_of_the_patchwork_match_the_spec(hip):
     ok = 0
     for y in range(p.height):
         for x in range(p.width):
-            a, n, z = _spec_guide(S, x, y, p, p.frame)
+            a, n, z = spec_guide(S, x, y, p, p.frame)
             ok += bool(np.allclose(g["albedo"][y, x], a, rtol=0, atol=1e-6) and np.allclose(g["normal"][y, x], n, rtol=0, atol=1e-6))
     assert ok >= 0.99 * p.width * p.height, f"{ok} of {p.width * p.height} pixels agree with the spec"

@@ -2,7 +2,7 @@
 
 The 18 modes are {reference, importance} environment sampling x {pinhole, lens, shutter, shutter+lens, one-light, cosine, cosine+one-light,
 MIS, MIS+one-light} (include/jade_bvh.h; tests/test_shade_modes_cpu.py states which combinations are built and which are refused).  Each is
-rendered through the public ABI on test_jade_spec's two_lamps scene under the textured sky - a jade cube (mirror and sub-surface), two
+rendered through the public ABI on spec_scenes' two_lamps scene under the textured sky - a jade cube (mirror and sub-surface), two
 lamps, a diffuse floor - at 32 x 32, 4 spp, under the default schedule, under JADE_FUSED=0 (the lean kernel and the split hand-over run)
 and under JADE_SHADE_SPLIT=0 (the full kernel alone over the list).  The switches are read once per process, so every schedule renders in
 a fresh child process: three children per session, each rendering all 18 modes on one scene handle.
@@ -75,11 +75,11 @@ def child():
     """Renders every mode under this process's schedule; one JSON object on the last line of stdout."""
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import test_jade_spec as TJ
+    import spec_scenes as SP
     from jaderaytracerendering_amd import _abi, backend as B, host as H
 
     hip = B.hip()
-    hs = TJ.build("two_lamps", sky=True)
+    hs = SP.build("two_lamps", sky=True)
     eye, cam = H.camera_orbit(2.8, 20.0, 10.0)
     out = {}
     with hip.scene(hs) as sc:

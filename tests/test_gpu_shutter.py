@@ -1,7 +1,8 @@
 """The camera shutter on the device (include/jade_bvh.h, "The shutter, stated"; jade_scene_set_shutter): the shutter ray against its
-host build, no shutter against a handle that never heard of one, the render sample for sample against tests/shutter_spec.py, the
-schedules, tile partitions and steps among themselves, hard geometric bounds on the streak of a truck, and the entry points that
-begin a render or read one - adaptive sampling, the guides and the denoiser, jade_render_multi, the command line."""
+host build, no shutter against a handle that never heard of one, the render sample for sample against tests/shutter_spec.py, hard
+geometric bounds on the streak of a truck, and the entry points that begin a render or read one - adaptive sampling, the guides and the
+denoiser, the command line.  The seams every mode is held to - twice, the walks, steps, tile shares, schedules, jade_render_multi - are
+in tests/test_gpu_mode_seams.py (cases "shutter" and "shutter+lens" of tests/mode_seams.py)."""
 import ctypes
 import os
 import subprocess
@@ -9,30 +10,19 @@ import subprocess
 import numpy as np
 import pytest
 
+import camera_cases as CC
 import jade_spec
+import mode_seams as MS
 import shutter_spec
-import test_gpu_lens as GL
-import test_jade_spec as TJ
-import test_shutter_cpu as TS
-from adaptive_ref import tile_errors
-from conftest import B, ROOT, config_scene, counters, tile_mask
+from conftest import B, config_scene
 from jaderaytracerendering_amd import _abi, host as H
+from render_helpers import CLI, SCHED_LENS, all_counters, read_pfm, same_bits
+from spec_scenes import build
 
 pytestmark = pytest.mark.gpu
 
-CLI = os.path.join(ROOT, "jaderaytracerendering_amd", "lib", "jade_render")
-all_counters, same_bits, _with = GL.all_counters, GL.same_bits, GL._with
-
 
 # ---------------------------------------------------------------------------------------------- 1. the shutter ray, device = host --
-
-def _wang(s):
-    s = ((s ^ 61) ^ (s >> 16)) & 0xffffffff
-    s = (s * 9) & 0xffffffff
-    s = s ^ (s >> 4)
-    s = (s * 0x27d4eb2d) & 0xffffffff
-    return s ^ (s >> 15)
-
 
 def test_shutter_ray_device_equals_host_build_bit_for_bit(hip_debug):
     lib = hip_debug.lib
@@ -40,7 +30,7 @@ def test_shutter_ray_device_equals_host_build_bit_for_bit(hip_debug):
         fn.restype = ctypes.c_int
     lib.jade_debug_shutter_ray_host.argtypes = [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
     lib.jade_debug_shutter_ray.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
-    rows = TS.shutter_rows()
+    rows = CC.shutter_rows()
     host = np.zeros((len(rows), 6), np.float32)
     dev = np.full((len(rows), 6), np.nan, np.float32)
     hip_debug.check(lib.jade_debug_shutter_ray_host(len(rows), rows.ctypes.data, host.ctypes.data))
@@ -52,7 +42,7 @@ def test_shutter_ray_device_equals_host_build_bit_for_bit(hip_debug):
     lib.jade_debug_shutter_ray_rng.argtypes = [ctypes.c_int, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_float, ctypes.c_float, ctypes.POINTER(_abi.ShutterParams)] + [ctypes.c_void_p] * 5
     W, H_, frame = 40, 24, 7
-    eye, cam, (eye_c, cam_c, _, _) = TS.spec_poses()
+    eye, cam, (eye_c, cam_c, _, _) = CC.spec_poses()
     t0, t1 = 0.25, 0.75
     sh = _abi.ShutterParams(_abi.f3(*eye_c.tolist()), (ctypes.c_float * 16)(*cam_c.tolist()), t0, t1)
     ys, xs = (v.ravel().astype(np.int32) for v in np.mgrid[0:H_, 0:W])
@@ -63,13 +53,13 @@ def test_shutter_ray_device_equals_host_build_bit_for_bit(hip_debug):
         state = np.zeros(n, np.uint32)
         hip_debug.check(lib.jade_debug_shutter_ray_rng(0, n, W, H_, frame, eye.ctypes.data, cam.ctypes.data, A, f, ctypes.byref(sh), xs.ctypes.data,
                                                        ys.ctypes.data, sidx.ctypes.data, out.ctypes.data, state.ctypes.data))
-        rows2 = np.zeros((n, TS.SHUTTER_ROW), np.float32)
+        rows2 = np.zeros((n, CC.SHUTTER_ROW), np.float32)
         want_state = np.zeros(n, np.uint32)
         for i in range(n):
             s = ((int(xs[i]) * 1973 + int(ys[i]) * 9277 + (frame + int(sidx[i])) * 26699) | 1) & 0xffffffff
             u = []
             for _ in range(5 if A > 0 else 3):  # jade_wang, include/jade_fpmath.h
-                s = _wang(s)
+                s = CC.wang(s)
                 u.append(np.float32(s) * np.float32(2.0 ** -32))
             want_state[i] = s
             u1, u2, u3, u4, ut = u if A > 0 else (u[0], u[1], 0.0, 0.0, u[2])
@@ -82,19 +72,9 @@ def test_shutter_ray_device_equals_host_build_bit_for_bit(hip_debug):
 
 # -------------------------------------------------------------------------------------------- 2. no shutter is today's render --
 
-def _tinyjade(spp, w=40, h=24):
-    hs, cfg = config_scene("tinyjade")
-    p = B.params_from_config(cfg, spp=spp)
-    p.width, p.height = w, h
-    eye, cam = np.array(p.eye[:], np.float32), np.array(p.camera[:], np.float32)
-    # the statuette is about 0.45 away: a turntable step of 3 degrees about the orbit's centre and a small truck
-    close = H.camera_move(eye, cam, truck=(0.004, -0.002, 0.0), orbit_deg=3.0, pivot=(0.26, -1.28, 0.0))
-    return hs, p, close
-
-
 def test_no_shutter_is_the_render_of_a_handle_that_never_had_one_in_every_bit_and_counter(hip):
-    hs, p, close = _tinyjade(24)
-    lens = GL.SCHED_LENS
+    hs, p, close = CC.tinyjade(24)
+    lens = SCHED_LENS
     with hip.scene(hs) as sc:
         ref_pin = sc.render(p)
         assert sc.shutter() is None
@@ -146,29 +126,29 @@ def test_no_shutter_is_the_render_of_a_handle_that_never_had_one_in_every_bit_an
 
 # ----------------------------------------------------------------------------------- 3. sample for sample against the statement --
 
-@pytest.mark.parametrize("case", sorted(TS.SPEC_CASES))
+@pytest.mark.parametrize("case", sorted(CC.SPEC_CASES))
 def test_render_matches_the_float64_statement_sample_for_sample(hip, case):
     """tests/test_gpu_lens.py's settings (size 12, frames 0-2, spp 1) and rule - a sample agrees when every channel is within
     1e-4 max(|want|, 1e-3); at most 2 % may disagree (a cap: a decision fp32 and float64 take differently, such as a ray grazing an
     edge); bssrdf-coplanar samples are left out as there.  Per branch, at least half of what the statement alone counts
     (tests/test_shutter_cpu.py, SPEC_COUNTS) must be among the agreeing samples.  Disagreeing samples on the MI355X at the time of
     writing: DESIGN.md 3.10."""
-    kind, sky, env_sampling, lens = TS.SPEC_CASES[case]
-    hs = TJ.build(kind, sky)
-    eye, cam, shutter = TS.spec_poses()
-    size = TS.SPEC_SIZE
+    kind, sky, env_sampling, lens = CC.SPEC_CASES[case]
+    hs = build(kind, sky)
+    eye, cam, shutter = CC.spec_poses()
+    size = CC.SPEC_SIZE
     frames = {}
     with hip.scene(hs) as sc:
         if lens:
             sc.set_lens(*lens)
         sc.set_shutter(*shutter)
-        for frame in TS.SPEC_FRAMES:
+        for frame in CC.SPEC_FRAMES:
             p = B.make_params(size, size, 1, eye, cam, frame=frame, env_sampling=env_sampling)
             rgb, _, st = sc.render(p, want_bgr8=False)
             assert st.rays_primary == st.samples == size * size and st.rays_inline == 0 and st.tail_launches == 0
             frames[frame] = rgb
     seen, bad, n, skipped = {}, [], 0, 0
-    for frame, x, y, want, tr in TS.spec_samples(case):
+    for frame, x, y, want, tr in CC.spec_samples(case):
         got = frames[frame][y, x].astype(np.float64)
         if "bssrdf-coplanar" in tr:
             skipped += 1
@@ -181,97 +161,35 @@ def test_render_matches_the_float64_statement_sample_for_sample(hip, case):
             bad.append((frame, x, y, tr, got, want))
     print(f"shutter spec {case}: {len(bad)} of {n} samples disagree ({skipped} left out), agreeing by branch {dict(sorted(seen.items()))}")
     assert len(bad) <= 0.02 * n, f"{len(bad)} of {n} samples disagree with the float64 statement, e.g. {bad[:3]}"
-    for branch, count in TS.SPEC_COUNTS[case].items():
+    for branch, count in CC.SPEC_COUNTS[case].items():
         if branch != "left-out":
             assert seen.get(branch, 0) >= count // 2, f"only {seen.get(branch, 0)} agreeing samples went through '{branch}' ({seen})"
 
 
-# --------------------------------------------------------------------------------------- 4. schedules under a shutter: one result --
+# ------------------------------------------------------------------------------- 4. the frames differ from the pinhole's and each other --
 
-SCHED_MODES = {"shutter": None, "shutter+lens": GL.SCHED_LENS}
-
-
-def _prepare(sc, mode, close):
-    if SCHED_MODES[mode]:
-        sc.set_lens(*SCHED_MODES[mode])
-    sc.set_shutter(*close)
-
-
-@pytest.fixture(scope="module")
-def sched_refs(hip):
-    hs, p, close = _tinyjade(64)  # 40 x 24: partial tiles; 960 x 64 records: more than one 512-thread block, a last wave partly filled
-    refs = {}
-    for mode in SCHED_MODES:
-        with hip.scene(hs) as sc:
-            _prepare(sc, mode, close)
-            refs[mode] = sc.render(p)
-    return refs
-
-
-def _assert_is_ref(out, ref, what):
-    rgb, bgr, st = out
-    assert same_bits(rgb, ref[0]) and np.array_equal(bgr, ref[1]), what
-    assert counters(st) == counters(ref[2]), what
-    assert st.rays_inline == 0 and st.tail_launches == 0 and st.rays_tail == 0 and st.rays_primary == st.samples, what
-
-
-def test_shutter_render_counts(hip, sched_refs):
-    hs, p, close = _tinyjade(64)
+def test_shutter_render_counts(hip):
+    hs, p, close = CC.tinyjade(64)
+    frames = {}
     with hip.scene(hs) as sc:
         pin = sc.render(p)
-    for mode, (rgb, bgr, st) in sched_refs.items():
+        sc.set_shutter(*close)
+        frames["shutter"] = sc.render(p)
+        sc.set_lens(*SCHED_LENS)
+        frames["shutter+lens"] = sc.render(p)
+    for mode, (rgb, bgr, st) in frames.items():
         assert st.samples == 40 * 24 * 64 and st.rays_primary == st.samples, mode
         assert st.rays_inline == 0 and st.tail_launches == 0 and st.rays_tail == 0, mode
         assert np.isfinite(rgb).all() and rgb.max() > 0 and not same_bits(rgb, pin[0]), mode
-    assert not same_bits(sched_refs["shutter"][0], sched_refs["shutter+lens"][0])
+    assert not same_bits(frames["shutter"][0], frames["shutter+lens"][0])
 
 
-@pytest.mark.parametrize("mode", sorted(SCHED_MODES))
-def test_steps_and_flush_equal_one_call_under_a_shutter(hip, sched_refs, mode):
-    hs, p, close = _tinyjade(64)
-    with hip.scene(hs) as sc:
-        _prepare(sc, mode, close)
-        sc.begin(p)
-        st = _abi.Stats()
-        for _ in range(4):
-            sc.step(16, st)
-        sc.flush(st)
-        rgb, bgr = sc.resolve()
-    _assert_is_ref((rgb, bgr, st), sched_refs[mode], "4 steps of 16 + flush")
-
-
-@pytest.mark.parametrize("mode", sorted(SCHED_MODES))
-def test_tile_partition_assembles_to_the_full_frame_under_a_shutter(hip, sched_refs, mode):
-    hs, p, close = _tinyjade(64)
-    ref = sched_refs[mode]
-    acc, acc_b = np.zeros_like(ref[0]), np.zeros_like(ref[1])
-    tot = {k: 0 for k in counters(ref[2])}
-    with hip.scene(hs) as sc:
-        _prepare(sc, mode, close)
-        for r in range(3):
-            part, part_b, st = sc.render(_with(p, tile_rank=r, tile_nranks=3))
-            assert not ((acc != 0) & (part != 0)).any()
-            assert st.rays_inline == 0 and st.tail_launches == 0
-            acc += part
-            acc_b += part_b
-            for k, v in counters(st).items():
-                tot[k] += v
-    assert same_bits(acc, ref[0]) and np.array_equal(acc_b, ref[1])
-    assert tot == counters(ref[2])
-
-
-@pytest.mark.parametrize("env", GL.SCHEDULES, ids=lambda e: ",".join(f"{k[5:]}={v}" for k, v in e.items()))
-def test_schedules_under_a_shutter_are_one_result(hip, sched_refs, monkeypatch, env):
-    hs, p, close = _tinyjade(64)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)  # (read once, at jade_scene_create)
-    for mode in sorted(SCHED_MODES):
-        with hip.scene(hs) as sc:
-            _prepare(sc, mode, close)
-            out = sc.render(p)
-            early = sc.render(_with(p, walk=_abi.WALK_EARLY_EXIT))
-        _assert_is_ref(out, sched_refs[mode], (mode, env))
-        assert same_bits(early[0], sched_refs[mode][0]) and np.array_equal(early[1], sched_refs[mode][1]), "early exits change no bit under a shutter either"
+@pytest.mark.parametrize("env", MS.COMMON_SCHEDULES[:5] + MS.CAMERA_SCHEDULES, ids=MS.schedule_id)
+def test_schedules_under_a_shutter_are_one_result(hip, monkeypatch, env):
+    """Kept for its ids, which cannot all be retired in one change: tests/test_gpu_mode_seams.py runs this check for every case and environment."""
+    cases = [MS.BY_NAME["shutter"], MS.BY_NAME["shutter+lens"]]
+    for case, ref in zip(cases, [MS.reference(hip, c) for c in cases]):  # (the references before any environment is set)
+        MS.check_schedule(hip, case, ref, env, monkeypatch.setenv)
 
 
 # -------------------------------------------------------------------------------------------------------------- 5. the streak --
@@ -304,17 +222,17 @@ def test_the_streak_of_a_truck_on_the_device(hip):
     hw = half * 1.5 / z * W / 2
     assert s == 12.0 and hw <= 0.7
     eye = np.zeros(3, np.float32)
-    eye_c, cam_c = H.camera_move(eye, TS.IDENTITY_CAM, truck=(D, 0.0, 0.0))
-    assert np.array_equal(eye_c, [D, 0, 0]) and np.array_equal(cam_c[:12], TS.IDENTITY_CAM[:12])
-    eye_m, cam_m = H.camera_move(eye, TS.IDENTITY_CAM, truck=(D / 2, 0.0, 0.0))
-    p = B.make_params(W, W, spp, eye, TS.IDENTITY_CAM)
+    eye_c, cam_c = H.camera_move(eye, CC.IDENTITY_CAM, truck=(D, 0.0, 0.0))
+    assert np.array_equal(eye_c, [D, 0, 0]) and np.array_equal(cam_c[:12], CC.IDENTITY_CAM[:12])
+    eye_m, cam_m = H.camera_move(eye, CC.IDENTITY_CAM, truck=(D / 2, 0.0, 0.0))
+    p = B.make_params(W, W, spp, eye, CC.IDENTITY_CAM)
 
     def lit_of(sc, params):
         rgb, _, st = sc.render(params, want_bgr8=False)
         assert st.rays_primary == st.samples == W * W * spp
         return rgb.sum(-1) > 0
 
-    with hip.scene(GL._emitter_on_the_axis(z, half)) as sc:
+    with hip.scene(CC.emitter_on_the_axis(z, half)) as sc:
         static = lit_of(sc, p)
         static_mid = lit_of(sc, B.make_params(W, W, spp, eye_m, cam_m))
         sc.set_shutter(eye_c, cam_c)
@@ -341,19 +259,15 @@ def test_the_streak_of_a_truck_on_the_device(hip):
 
 @pytest.mark.parametrize("lens", [None, (0.3, 2.0)])
 def test_with_nothing_in_view_the_shutter_frame_is_the_pinhole_frame(hip, lens):
-    """As tests/test_gpu_lens.py argues: the geometry is behind the camera at both ends of the move and the sky one constant ABOVE the
-    lookup's clamp at 10, so that every sample of both frames is (10, 10, 10) bit for bit, whatever its ray."""
-    b = H.SceneBuilder()
-    b.add_mesh(np.array([[-1, -1, 4], [-1, 1, 4], [1, 1, 4], [1, -1, 4]], np.float32), TS.QUAD_I, H.material(emissive=(5, 5, 5), brdf=(0.3, 0.3, 0.3)))
-    b.add_mesh(np.array([[-1, -1, 3], [1, -1, 3], [1, 1, 3], [-1, 1, 3]], np.float32), TS.QUAD_I, H.material(brdf=(0.6, 0.5, 0.4)))
-    b.set_env_constant(20.0, 30.0, 40.0)
+    """camera_cases.nothing_in_view: the geometry is behind the camera at both ends of the move, so that every sample of both frames is
+    (10, 10, 10) bit for bit, whatever its ray."""
     eye = np.zeros(3, np.float32)
-    p = B.make_params(40, 24, 8, eye, TS.IDENTITY_CAM)
-    with hip.scene(b.build()) as sc:
+    p = B.make_params(40, 24, 8, eye, CC.IDENTITY_CAM)
+    with hip.scene(CC.nothing_in_view()) as sc:
         pin = sc.render(p)
         if lens:
             sc.set_lens(*lens)
-        sc.set_shutter(*H.camera_move(eye, TS.IDENTITY_CAM, truck=(0.3, 0.1, 0.0), orbit_deg=5.0))
+        sc.set_shutter(*H.camera_move(eye, CC.IDENTITY_CAM, truck=(0.3, 0.1, 0.0), orbit_deg=5.0))
         blur = sc.render(p)
     assert (pin[0] == 10.0).all()
     assert same_bits(blur[0], pin[0]) and np.array_equal(blur[1], pin[1])
@@ -363,30 +277,14 @@ def test_with_nothing_in_view_the_shutter_frame_is_the_pinhole_frame(hip, lens):
 # ----------------------------------------------------------------------------------------------------------- 7. on top of the mode --
 
 def test_adaptive_tiles_equal_uniform_shutter_renders(hip):
-    hs, p, close = _tinyjade(16, 64, 48)
-    floor = 0.01
-    with hip.scene(hs) as sc:
-        sc.set_shutter(*close)
-        sc.begin(_with(p, spp=2))
-        sc.step(2)
-        e = np.sort(tile_errors(sc.error_map(floor), 4, 3).ravel())
-        e = e[np.isfinite(e)]
-        rel = next(float(0.5 * (e[i] + e[i + 1])) for i in range(len(e) // 2, len(e) - 1) if e[i + 1] > e[i] * (1 + 1e-3))
-        rgb, bgr, tspp, st = sc.render_adaptive(p, 2, rel, floor)
-        ks = sorted(set(tspp.ravel().tolist()))
-        assert len(ks) >= 2 and st.rays_inline == 0, ks
-        for k in ks:
-            r_u, b_u, _ = sc.render(_with(p, spp=int(k)))
-            m = tile_mask(p.width, p.height, np.flatnonzero(tspp.ravel() == k))
-            assert same_bits(rgb[m], r_u[m]) and np.array_equal(bgr[m], b_u[m]), k
-    assert st.samples == int(tspp.sum()) * 256
+    CC.check_adaptive_tiles_equal_uniform_renders(hip, lambda sc: sc.set_shutter(*CC.tinyjade(16)[2]))
 
 
-@pytest.mark.parametrize("lens", [None, TS.SPEC_LENS])
+@pytest.mark.parametrize("lens", [None, CC.SPEC_LENS])
 def test_guides_follow_the_shutter(hip, lens):
-    hs = TJ.build("open_floor")
+    hs = build("open_floor")
     S = jade_spec.Scene(hs)
-    eye, cam, shutter = TS.spec_poses()
+    eye, cam, shutter = CC.spec_poses()
     A, f = lens if lens else (0.0, 0.0)
     size, frame = 12, 1
     p = B.make_params(size, size, 2, eye, cam, frame=frame)
@@ -421,37 +319,7 @@ def test_guides_follow_the_shutter(hip, lens):
 
 
 def test_denoise_under_a_shutter_is_denoise_image_on_its_own_inputs(hip):
-    hs, p, close = _tinyjade(16)
-    d = hip.denoise_defaults()
-    with hip.scene(hs) as sc:
-        sc.set_shutter(*close)
-        sc.begin(p)
-        sc.step(16)
-        r1, b1 = sc.denoise(d)
-        g = sc.guides(d.guide_spp)
-        rgb, _ = sc.resolve(want_bgr8=False)
-    got = hip.denoise_image(rgb, g["variance"], g["albedo"], g["normal"], g["depth"], params=d)
-    assert same_bits(got, r1) and np.isfinite(r1).all()
-
-
-def test_render_multi_under_equal_shutters_and_its_refusal_of_unequal_ones(hip, sched_refs):
-    hs, p, close = _tinyjade(64)
-    ref = sched_refs["shutter"]
-    other_eye = close[0].copy()
-    other_eye[0] = np.nextafter(other_eye[0], np.float32(10))
-    with hip.scene(hs) as s0, hip.scene(hs) as s1:
-        s0.set_shutter(*close)
-        s1.set_shutter(*close)
-        rgb, bgr, st = B.render_multi(hip, [s0, s1], p)
-        assert same_bits(rgb, ref[0]) and np.array_equal(bgr, ref[1])
-        assert counters(st) == counters(ref[2]) and st.rays_inline == 0
-        for other in ((other_eye, close[1]), (close[0], close[1], 0.0, 0.5), None):
-            s1.set_shutter(*other) if other else s1.set_shutter(None)
-            with pytest.raises(B.JadeError) as ei:
-                B.render_multi(hip, [s0, s1], p)
-            assert ei.value.code == _abi.JADE_ERR_INVALID
-        s0.set_shutter(None)  # none on either: the pinhole frame, accepted
-        B.render_multi(hip, [s0, s1], p)
+    CC.check_denoise_is_denoise_image_on_its_own_inputs(hip, lambda sc: sc.set_shutter(*CC.tinyjade(16)[2]))
 
 
 def test_cli_shutter_orbit_writes_the_python_frame(hip, tmp_path):
@@ -470,7 +338,7 @@ def test_cli_shutter_orbit_writes_the_python_frame(hip, tmp_path):
         sc.set_shutter(None)
         pin, _, _ = sc.render(p, want_bgr8=False)
     assert f"shutter: closes at eye ({eye_c[0]:.9g}, {eye_c[1]:.9g}, {eye_c[2]:.9g}), exposure 0.25 .. 1 of the move" in r.stdout, r.stdout
-    assert same_bits(GL._read_pfm(tmp_path / "blur.pfm"), rgb) and not same_bits(rgb, pin)
+    assert same_bits(read_pfm(tmp_path / "blur.pfm"), rgb) and not same_bits(rgb, pin)
     # the other flags keep working on top, the lens among them
     r = subprocess.run(common + ["--shutter-orbit", "2", "--aperture", "0.1", "--focus", "13.5", "--adaptive", "0.5", "--min-spp", "2", "--denoise", "--glare", "0.1",
                                  "--exposure", "auto", "--out", "all.ppm"], capture_output=True, text=True, timeout=300, cwd=tmp_path)

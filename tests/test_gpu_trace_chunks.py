@@ -11,9 +11,8 @@ import pytest
 
 import queue_hooks as Q
 from conftest import config_scene
-from test_gpu_early_exit import _trace_limit
-from test_gpu_packet import _oracle_per_ray, _rays
-from test_gpu_parity import TOL, _assert_parity
+import ray_helpers as RH
+from render_helpers import TOL, assert_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -44,9 +43,9 @@ def _oracle_rays(oracle, name):
     answer for each, its own node records and triangle tests included: once per scene."""
     if name not in _want:
         hs, _ = config_scene(name)
-        o, d, skip = _rays(hs, (N_MAX + 63) // 64, 11)
+        o, d, skip = RH.rays(hs, (N_MAX + 63) // 64, 11)
         with oracle.scene(hs) as so:
-            _want[name] = (o, d, skip) + _oracle_per_ray(so, o, d, skip)
+            _want[name] = (o, d, skip) + RH.oracle_per_ray(so, o, d, skip)
     return _want[name]
 
 
@@ -69,7 +68,7 @@ def test_raw_rays_at_every_chunk_match_the_oracle_ray_by_ray(oracle, hip_debug, 
     base = {}  # the chunk-64 answers under a limit of INF, for every ray count of every chunk
     with Q.environment(_chunk(64)), hip_debug.scene(hs) as sc:
         for n in sorted({n for chunk in CHUNKS for n in _counts(chunk)}):
-            base[n] = _trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], inf_limits[:n])
+            base[n] = RH.trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], inf_limits[:n])
     for chunk in CHUNKS:
         with Q.environment(_chunk(chunk)), hip_debug.scene(hs) as sc:
             for n in _counts(chunk):
@@ -77,12 +76,12 @@ def test_raw_rays_at_every_chunk_match_the_oracle_ray_by_ray(oracle, hip_debug, 
                 _assert_rays(sc.trace_rays(o[:n], d[:n], skip[:n]), want, n, what)
                 # ... and through jade_debug_trace_rays_limit.  A NaN limit never ends a walk: the reference's answer and work, again.
                 nan = np.full(n, np.nan, np.float32)
-                _assert_rays(_trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], nan), want, n, what + ("NaN limits",))
+                _assert_rays(RH.trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], nan), want, n, what + ("NaN limits",))
                 # A limit of INF ends a walk at ANY recorded hit - which one depends on the other rays of the wave (jade_hip.hip,
                 # jade_debug_trace_rays_limit), and so on the chunk.  What does not: the same rays miss, with the same bits; a ray that hits
                 # reports a triangle at a distance not nearer than its nearest hit; and wherever the triangle is the chunk-64 run's, so
                 # are distance and point.
-                i1, t1, p1, _ = _trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], inf_limits[:n])
+                i1, t1, p1, _ = RH.trace_limit(hip_debug, sc, o[:n], d[:n], skip[:n], inf_limits[:n])
                 i0, t0, p0, _ = base[n]
                 miss = want[0][:n] < 0
                 assert np.array_equal(i1 < 0, miss) and np.array_equal(i0 < 0, miss), what
@@ -116,10 +115,10 @@ def test_the_chunk_64_frame_is_the_oracles(oracle, hip_debug, chunk64):
     hs, p, _ = Q.frame("tinyjade")
     with oracle.scene(hs) as so:
         want = so.render(p)
-    err = _assert_parity(want, chunk64[:3], TOL)
+    err = assert_parity(want, chunk64[:3], TOL)
     print(f"tinyjade, chunk 64, against the oracle: relative L2 {err:.3g}")
     big = Q.render(hip_debug, "tinyjade", {**TAIL0, **_chunk(512)})
-    _assert_parity(want, big[:3], TOL)
+    assert_parity(want, big[:3], TOL)
 
 
 @pytest.mark.parametrize("chunk", CHUNKS)

@@ -11,9 +11,7 @@ import pytest
 from conftest import (B, assert_cached_walk_equals_reference_walk, assert_early_exit_equals_reference_walk, config_scene, counters,
                       rel_l2)
 from jaderaytracerendering_amd import _abi
-from test_gpu_deep_trees import _assert_answers, _flags, _limits, _nan_limit, _same_bits
-from test_gpu_early_exit import INF, _trace_limit
-from test_gpu_packet import _packet_rays
+import ray_helpers as RH
 
 import prep_ref as P
 import scene_shapes as SS
@@ -48,41 +46,41 @@ def test_raw_rays_are_the_oracles_on_every_shape(oracle, hip_debug, name, wide, 
     rng = np.random.default_rng(3)
     flags_want, general, p = _expected_flags(hip, hs, int(wide))
     with hip.scene(hs) as sc:
-        flags = _flags(hip, sc)
+        flags = RH.flags(hip, sc)
         assert flags == flags_want, (flags, flags_want)
         if p.n_internal > 1:
             assert (flags & 6 == 0) == general, "neither wide records nor a cache exactly where the walk is the general one"
         if sh.same_as_base:
             with hip.scene(TS.base_scene(sh.base)) as sb:
-                assert flags == _flags(hip, sb)
+                assert flags == RH.flags(hip, sb)
         # ---- the reference's walk
         got = sc.trace_rays(o, d, skip)
-        _same_bits(got, want)
+        RH.same_answers(got, want)
         assert got[3].nodes_visited == int(want[3].sum()) and got[3].tris_tested == int(want[4].sum())
         hitm = want[0] >= 0
         # ---- the packet form
-        pk = _packet_rays(hip, sc, o, d, skip)
+        pk = RH.packet_rays(hip, sc, o, d, skip)
         given_up = pk[0] == -3
         # (a packet in which two leaves tie for some ray's best distance is given up, test_gpu_packet.py: a triangle in two leaves, and in
         # the 148-triangle base the boxes that stand ON the floor - a ray through a contact face)
         assert (~given_up).sum() >= (64 if sh.group == "cover" else n // 2), int(given_up.sum())  # (packets 0-31 go anywhere: no contact face in most)
         assert (given_up.reshape(-1, 64).all(1) == given_up.reshape(-1, 64).any(1)).all(), "a packet is given up as a whole"
-        _same_bits(pk, want, ~given_up)
+        RH.same_answers(pk, want, ~given_up)
         assert np.array_equal(pk[3].astype(np.int64)[~given_up], want[3][~given_up]), "node records per ray"
         assert np.array_equal(pk[4].astype(np.int64)[~given_up], want[4][~given_up]), "triangle tests per ray"
         # ---- k_trace / k_trace_wide with a limit per ray: none (the whole walk), any hit, a mixture
-        _same_bits(_trace_limit(hip, sc, o, d, skip, _nan_limit(n)), want)
-        ends = _assert_answers(_trace_limit(hip, sc, o, d, skip, np.full(n, INF)), want, np.full(n, INF), skip)
+        RH.same_answers(RH.trace_limit(hip, sc, o, d, skip, RH.nan_limit(n)), want)
+        ends = RH.assert_answers(RH.trace_limit(hip, sc, o, d, skip, np.full(n, RH.INF)), want, np.full(n, RH.INF), skip)
         assert sh.empty or ends.sum() >= 100  # (every ray the oracle finds a hit for)
-        limit = _limits(rng, hitm, want[1])
-        ends = _assert_answers(_trace_limit(hip, sc, o, d, skip, limit), want, limit, skip)
+        limit = RH.limits(rng, hitm, want[1])
+        ends = RH.assert_answers(RH.trace_limit(hip, sc, o, d, skip, limit), want, limit, skip)
         assert sh.empty or ends.any()
         # ---- the occluder cache: the rays that leave triangles are its queries; three rounds on this handle
-        limit = _limits(rng, hitm, want[1])
+        limit = RH.limits(rng, hitm, want[1])
         answered = []
         for _ in range(3):
-            got = _trace_limit(hip, sc, o, d, skip, limit, cached=True)
-            ends = _assert_answers(got, want, limit, skip)
+            got = RH.trace_limit(hip, sc, o, d, skip, limit, cached=True)
+            ends = RH.assert_answers(got, want, limit, skip)
             answered.append(int(got[3].rays_cached))
             assert answered[-1] <= ends.sum()
         if not flags & 4:

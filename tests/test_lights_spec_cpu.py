@@ -2,7 +2,7 @@
 include/jade_bvh.h, "The lights, stated") checked without a GPU against things that do not share its code - there is no oracle for this
 mode: with no entry it is the all-lights arm; with one entry it is the all-lights arm on a stream thinned by two uniforms per vertex;
 at a fixed vertex its expectation over the slot and the own / alias outcome is the all-lights arm's sum, within the header's rounding
-bounds; and the scenes tests/test_gpu_lights.py section 8 compares on the device reach, by the arm alone, what its `need` tables
+bounds; and the scenes tests/test_gpu_lights.py section 7 compares on the device reach, by the arm alone, what its `need` tables
 demand.  The table is the module's own, made on the host (libjade_hip_debug.so's jade_debug_light_table_host: no HIP call)."""
 import copy
 import functools
@@ -12,7 +12,7 @@ import pytest
 
 import jade_spec
 import lights_spec as spec
-import test_jade_spec as TJ
+import spec_scenes as SP
 from jaderaytracerendering_amd import _abi, host as H
 
 SIZE = 12
@@ -33,7 +33,7 @@ def frame_of(S, frame, traces=None):
 # ------------------------------------------------------------------------------------------------------- nE = 0 and nE = 1 --
 
 def test_without_entries_the_arm_is_the_all_lights_arm():
-    hs = TJ.build("no_list")
+    hs = SP.build("no_list")
     ta, to = [], []
     a = frame_of(jade_spec.Scene(hs), 0, ta)
     o = frame_of(jade_spec.Scene(hs, light_sampling=_abi.LIGHTS_ONE), 0, to)
@@ -46,7 +46,7 @@ def test_with_one_entry_the_arm_is_the_all_lights_arm_on_a_thinned_stream(monkey
     the all-lights sample of a stream without u1 and u2.  The all-lights arm pulls an entry's pair through jade_spec.light_uniforms;
     here that drops two uniforms, takes the next two and folds them in fp32 as the header's draw does (Scene.point's own fold, on the
     float64 sum of an already folded pair, then changes nothing): every channel of every sample of two frames is the same double."""
-    hs = TJ.build("one_entry")
+    hs = SP.build("one_entry")
     one = jade_spec.Scene(hs, light_sampling=_abi.LIGHTS_ONE)
     t = one.light_table
     assert len(t) == 1 and (t["accept"][0], t["alias"][0], t["q_own"][0], t["q_alias"][0]) == (1, 0, 1, 1)
@@ -120,7 +120,7 @@ def test_the_arm_is_unbiased_at_a_vertex(branch):
     plus the float64 rounding of at most 2 nE additions and a dozen multiplications per term, 64 nE 2^-53 sum_i |t_i|.  The bound
     is about 1e-5 relative for the floor triangle's entry and 2e-7 for the lamps'; a weight read from the slot and not the entry, or
     a missing weight, is off by tens of percent."""
-    hs = TJ.build("two_lamps")
+    hs = SP.build("two_lamps")
     args = vertices_of(hs)[branch]
     fn = jade_spec.direct_bssrdf if branch == "bssrdf" else jade_spec.direct_diffuse
     S_all, S_one = jade_spec.Scene(hs), jade_spec.Scene(hs, light_sampling=_abi.LIGHTS_ONE)
@@ -165,8 +165,8 @@ def test_the_arm_is_unbiased_at_a_vertex(branch):
 def arm_counts(case):
     """(tag -> number of compared samples whose trace has it, compared, left out) of the arm alone on the frames of a case, counted
     as compare() counts: a sample tagged bssrdf-coplanar is left out."""
-    c = TJ.LIGHT_CASES[case]
-    S = jade_spec.Scene(TJ.build(c["kind"], c.get("sky", False)), c.get("env_sampling", _abi.ENV_REFERENCE), _abi.LIGHTS_ONE)
+    c = SP.LIGHT_CASES[case]
+    S = jade_spec.Scene(SP.build(c["kind"], c.get("sky", False)), c.get("env_sampling", _abi.ENV_REFERENCE), _abi.LIGHTS_ONE)
     seen, n, skipped = {}, 0, 0
     for frame in c["frames"]:
         for y in range(c["size"]):
@@ -182,14 +182,14 @@ def arm_counts(case):
     return seen, n, skipped
 
 
-@pytest.mark.parametrize("case", sorted(TJ.LIGHT_CASES))
+@pytest.mark.parametrize("case", sorted(SP.LIGHT_CASES))
 def test_the_scenes_reach_what_the_device_tests_demand(case):
     """Every `need` is half of what the arm alone counts (the table's comment carries the counts), and at most 5 % of a case's samples
     are left out."""
-    c = TJ.LIGHT_CASES[case]
+    c = SP.LIGHT_CASES[case]
     seen, n, skipped = arm_counts(case)
     print(case, n, skipped, dict(sorted(seen.items())))
-    assert c["size"] == SIZE and 3 <= len(c["frames"]) <= 4 and TJ.build(c["kind"]).n_triangles <= 40
+    assert c["size"] == SIZE and 3 <= len(c["frames"]) <= 4 and SP.build(c["kind"]).n_triangles <= 40
     assert skipped <= 0.05 * (n + skipped)
     assert {t: seen.get(t, 0) // 2 for t in c["need"]} == c["need"]
     assert min(c["need"].values()) >= 1
@@ -207,7 +207,7 @@ def test_one_entry_never_takes_an_alias_and_the_dark_list_never_finds_light():
 
 
 def test_the_fan_has_weights_of_a_hundred_and_takes_aliases_often():
-    hs = TJ.build("fan")
+    hs = SP.build("fan")
     e = hs.tri_f32()[hs.a["emit"], 13]
     assert len(e) >= 24 and e.max() / e.min() >= 1e3
     table = jade_spec.Scene(hs, light_sampling=_abi.LIGHTS_ONE).light_table

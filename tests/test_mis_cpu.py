@@ -14,7 +14,7 @@ import jade_spec
 import lights_spec
 import mis_cases as MC
 import mis_spec as spec
-import test_jade_spec as TJ
+import spec_scenes as SP
 from conftest import J, ROOT
 from jaderaytracerendering_amd import _abi, host as H
 
@@ -117,8 +117,8 @@ def lamp_over_floor(normal_scale=1.0):
     """A jade-material floor quad (so that both f apply) under a lamp quad of side 1.2 at y = 0.7, nothing else: no occluder.
     emit_indices = the lamp's two triangles and the first again.  The lamp's stored normals times 1.7."""
     b = J.SceneBuilder()
-    b.add_mesh(TJ.quad(0.0, 2.0), TJ.QUAD_I, H.material(**TJ.JADE))
-    b.add_mesh(TJ.quad(0.7, 0.6, flip=True) + np.float32([0.3, 0, 0.2]), TJ.QUAD_I, H.material(**MC.BIG))
+    b.add_mesh(SP.quad(0.0, 2.0), SP.QUAD_I, H.material(**SP.JADE))
+    b.add_mesh(SP.quad(0.7, 0.6, flip=True) + np.float32([0.3, 0, 0.2]), SP.QUAD_I, H.material(**MC.BIG))
     b.set_env_constant(0, 0, 0)
     hs = b.build()
     obj = hs.tri_i32()[:, 0]
@@ -243,7 +243,7 @@ def test_the_estimators_expectation_is_the_unweighted_emitter_expectation(sss, o
 
 @pytest.mark.parametrize("kind", ["no_list", "dark_list"])
 def test_without_weighted_entries_the_arm_is_bounce_specs_double_for_double(kind):
-    hs = TJ.build(kind)
+    hs = SP.build(kind)
     S = spec.Scene(hs)
     Sb = bounce_spec.Scene(hs)
     assert not S.mis_m.any()

@@ -11,8 +11,7 @@ import pytest
 
 from conftest import B, J, config_scene
 from jaderaytracerendering_amd import _abi
-from test_box_monotone import _slab
-from test_gpu_packet import _oracle_per_ray, _rays
+import ray_helpers as RH
 
 import walk_ref as W
 
@@ -43,10 +42,10 @@ def _scene_and_rays(name):
         return W.deep_tree(name)
     if name.startswith("spine"):
         hs = W.spine_to_depth(config_scene("tinyjade")[0], int(name[5:]))
-        rays = _rays(hs, 10, 11)
+        rays = RH.rays(hs, 10, 11)
     else:
         hs = config_scene(name)[0]
-        rays = _rays(hs, 42, 11)  # test_gpu_packet.py's batch
+        rays = RH.rays(hs, 42, 11)  # test_gpu_packet.py's batch
     return hs, rays, W.walk_batch(hs, *rays)
 
 
@@ -54,7 +53,7 @@ def _scene_and_rays(name):
 def test_model_reads_what_the_oracle_reads(oracle, name):
     hs, (o, d, skip), res = _scene_and_rays(name)
     with oracle.scene(hs) as so:
-        want = _oracle_per_ray(so, o, d, skip)
+        want = RH.oracle_per_ray(so, o, d, skip)
         deferred = _deferred(oracle, so, o, d, skip)
     assert np.array_equal(_col(res, "V"), want[3]), "node records per ray"
     assert np.array_equal(_col(res, "T"), want[4]), "triangle tests per ray"
@@ -78,7 +77,7 @@ def test_slab_is_the_monotone_tests_slab_where_no_nan_occurs():
         finite = np.isfinite(np.float32(1) / d).all(1)
     assert finite.sum() > 300 and (~finite).sum() >= 40
     for i in np.nonzero(finite)[0]:
-        assert np.array_equal(W.slab(T.aa, T.bb, o[i], d[i]), _slab(T.aa, T.bb, o[i], d[i]))
+        assert np.array_equal(W.slab(T.aa, T.bb, o[i], d[i]), RH.slab(T.aa, T.bb, o[i], d[i]))
 
 
 @pytest.mark.parametrize("D,height", [(9, 7), (10, 8), (11, 9), (12, 10), (63, 61), (64, 62), (82, 80), (83, 81), (124, 122), (125, 123),
@@ -142,7 +141,7 @@ def test_heights_of_the_suite_before_the_deep_trees():
     got = {}
     for name, packets in (("tiny", 42), ("tinyjade", 42), ("C2", 24)):
         hs, _ = config_scene(name)
-        res = W.walk_batch(hs, *_rays(hs, packets, 11))
+        res = W.walk_batch(hs, *RH.rays(hs, packets, 11))
         got[name] = tuple(int(_col(res, k).max()) for k in ("ha", "hb", "hc"))
     assert got == {"tiny": (6, 5, 8), "tinyjade": (8, 7, 8), "C2": (9, 9, 10)}, got
 

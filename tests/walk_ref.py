@@ -16,7 +16,7 @@ Stacked along z, not x: the reference's barycentric solve takes the x / y compon
 so a triangle in a plane x = const met head-on divides 0 by 0 and is never reported - by the oracle and by the kernels alike.
 
 Model.  walk(tree, o, d, skip) restates in float32 numpy what decides the SHAPE of a walk - near child first by d1 < d2, a box
-entered iff the slab value is > 0 (slab below: test_box_monotone._slab with the oracle's NaN rules), no pruning - and returns per ray the node records read (V), the
+entered iff the slab value is > 0 (slab below: ray_helpers.slab with the oracle's NaN rules), no pruning - and returns per ray the node records read (V), the
 triangle tests (T), the leaves in the order met, and the high-water mark of the stack under three rules:
   ha       the reference's rule (oracle: stack[128]): the far child is deferred whenever both are met.  The figure is the number of
            entries waiting while the top one is followed - what jade_oracle_stack_histogram counts; the array holds one more
@@ -281,7 +281,7 @@ def comb_rays(hs, seed=3):
 # ------------------------------------------------------------------------------------------------------------- model --
 
 def slab(aa, bb, o, d):
-    """hitAABB (PathTrace.cu:758-771) in float32 for the boxes aa, bb [N, 3] and one ray: test_box_monotone._slab, whose reductions
+    """hitAABB (PathTrace.cu:758-771) in float32 for the boxes aa, bb [N, 3] and one ray: ray_helpers.slab, whose reductions
     are written for rays without a NaN, with the reductions as the oracle and the kernels have them - tmax / tmin by the reference's
     ternaries (a NaN goes to the second operand), then fminf / fmaxf, which DROP a NaN operand (jade_fpmath.h) - so that the model
     also follows the rays that take the NaN-faithful unit.  The same values wherever no NaN occurs (test_walk_ref_cpu.py)."""

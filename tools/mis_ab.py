@@ -2,7 +2,7 @@
 
 usage: python tools/mis_ab.py [--out profiles/mis_ab.json] [--scenes C2,C3,contact,lamp] [--repeats 3] [--step-spp 64] [--converged-spp 2048] [--frames 6]
            C2 and C3 at their own sizes, the contact scene (tests/mis_cases.py: a lamp quad standing on a floor) and the 84-entry lamp
-           scene (tests/test_gpu_lights.py) at 192 x 160; the two modes alternating in ONE scene handle, JADE_BOUNCE_COSINE set throughout:
+           scene (tests/lamp_scenes.py) at 192 x 160; the two modes alternating in ONE scene handle, JADE_BOUNCE_COSINE set throughout:
              time     C2 and C3: one step of --step-spp samples plus flush, --repeats times per mode after a warm-up each: device time
                       per sample from jade_stats.  The rays are the same rays, so level is expected; the runs are written down.
              noise    relMSE at EQUAL samples per pixel, 16 / 64 / 256, --frames independent frames per mode and count, against the mean
@@ -40,9 +40,9 @@ def scene_of(name):
             hs = mis_cases.contact()
             eye, cam = mis_cases.contact_camera()
         else:
-            import test_gpu_lights
+            import lamp_scenes
             from jaderaytracerendering_amd import host as H
-            hs = test_gpu_lights.lamp_scene("lamp")
+            hs = lamp_scenes.lamp_scene("lamp")
             eye, cam = H.camera_orbit(5.0, 20.0, 30.0)
         return hs, (lambda spp, frame=0: B.make_params(SMALL_W, SMALL_H, spp, eye, cam, frame=frame, walk=_abi.WALK_EARLY_EXIT)), False
     hs, cfg = J.build_config(name)
