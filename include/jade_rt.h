@@ -282,6 +282,40 @@ typedef struct jade_render_params {
  * with JADE_ENV_REFERENCE only (jade_scene_create accepts it). */
 #define JADE_ENV_IMPORTANCE 1
 #define JADE_ENV_IMPORTANCE_MAX_TEXELS 16777216 /* 2^24 */
+/* JADE_ENV_MIXTURE, completely (tests/env_mixture_spec.py is this text in float64): a third value of env_sampling - a value of an
+ * existing field, so the ABI version stays.  JADE_ENV_IMPORTANCE draws from the map alone and knows nothing of which way the surface
+ * faces: under a bright sky at least half the draws of a surface that looks sideways, and almost all of one that looks down, lie on
+ * the wrong side and carry nothing.  This mode is the one-sample mixture of that draw and the render's own bounce sampling, weighed
+ * by the balance heuristic: no extra ray, no extra record word, one more uniform and one 16-B gather.
+ *
+ * At every vertex where the reference draws its environment direction (diffuse, SSS-diffuse, BSSRDF) the sample draws FIVE uniforms
+ * u0..u4, in this order, where JADE_ENV_IMPORTANCE draws four.  All five are always drawn, so every later draw of the sample is where
+ * it would be whichever technique was picked.  n, side: the normal and the side term of the reference's flip at that vertex (diffuse
+ * and SSS-diffuse: the vertex's normal, dot(out, n); BSSRDF: n_exit, dot(exit - entry, n_exit)).
+ *
+ *   u0 < 0.5 (in fp32) - the sky technique.  Slot, own / alias, texel t, q, theta, phi, st and the direction w are exactly
+ *     JADE_ENV_IMPORTANCE's from (u1, u2, u3, u4);  s = st.  A direction on the wrong side follows that mode's rule unchanged -
+ *     dot(w, n) * side < 0: no ray, not counted in rays_env, nothing added for the environment at this vertex.
+ *   otherwise - the hemisphere technique.  w is the direction the render's bounce sampling draws from (u1, u2), as it stands:
+ *     JADE_BOUNCE_UNIFORM gives the reference's statements (PathTrace.cu:968-971) and its flip, JADE_BOUNCE_COSINE the draw of "The
+ *     bounce, stated" (jade_bvh.h), fallback included.  u3 and u4 are drawn and not used.  It is never on the wrong side.
+ *         s = sqrt(wx^2 + wz^2);     t = the texel of w:  (u, v) = SampleSphericalMap's coordinates of w (sampleHdr's statements,
+ *         PathTrace.cu:686-692, a NaN counting as 0),  i = min((uint32)fl(u * W), W - 1),  j = min((uint32)fl(v * H), H - 1)  - a
+ *         negative product counts as 0 -,  t = j * W + i;     q = q_own of entry t of the table (= fl(q_t)).
+ *   The weight.  m stands where JADE_ENV_IMPORTANCE has ratio - the reference's term, 2 PI included, is multiplied by it where the
+ *     ray meets nothing.  With P = fl(PI):
+ *         uniform hemisphere:   m = (2 P s) / (q + P s)
+ *         cosine hemisphere:    m = (2 P s) / (q + 2 P s c),     c = |dot(n, w)| / sqrt(dot(n, n))
+ *     and a vertex whose normal gives the cosine draw no axis (dot(n, n) is 0, infinite or NaN) uses the uniform form; its term is 0
+ *     or not finite in every mode.  m = (1 / 2 pi) / (p_sky / 2 + p_hemi / 2) with p_sky = q / (2 pi^2 s) and p_hemi = 1 / 2 pi or
+ *     c / pi on the surface's side, 0 off it.  Hence 0 <= m <= 2 in the uniform form and m c <= 1 in the cosine form; q > 0, so no
+ *     denominator vanishes; at a pole m = 0.  The second moment of the mixture is at most twice that of either technique alone.
+ *
+ * Nothing else of the sample changes.  Non-parity: the oracle refuses it (JADE_ERR_UNSUPPORTED).  Maps above
+ * JADE_ENV_IMPORTANCE_MAX_TEXELS are refused with it as with JADE_ENV_IMPORTANCE.  0 and 1 stay today's render in every kernel, bit
+ * and counter; every other value of env_sampling stays JADE_ERR_INVALID.  It is not the default anywhere.  The device forms s, c and
+ * m in fp32; DESIGN.md 3.16 derives how far m may then lie from this statement. */
+#define JADE_ENV_MIXTURE 2
 #define JADE_WALK_REFERENCE 0
 #define JADE_WALK_EARLY_EXIT 1
 /* JADE_WALK_EARLY_EXIT plus an occluder cache (ABI 7).  The reference tests a leaf's triangles iff the ray meets the leaf's box

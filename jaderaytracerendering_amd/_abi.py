@@ -15,7 +15,7 @@ TILE_SIZE = 16
 TONEMAP_ACES, TONEMAP_REINHARD = 0, 1
 Q_RECORDS_PER_PIXEL, Q_STATE_BYTES, Q_SUM_LANES = 0, 1, 2
 WALK_REFERENCE, WALK_EARLY_EXIT, WALK_EARLY_EXIT_CACHED = 0, 1, 2
-ENV_REFERENCE, ENV_IMPORTANCE = 0, 1
+ENV_REFERENCE, ENV_IMPORTANCE, ENV_MIXTURE = 0, 1, 2
 LIGHTS_ALL, LIGHTS_ONE = 0, 1  # include/jade_bvh.h, jade_scene_set_light_sampling
 BOUNCE_UNIFORM, BOUNCE_COSINE = 0, 1  # include/jade_bvh.h, jade_scene_set_bounce_sampling
 DIRECT_RAYS, DIRECT_MIS = 0, 1  # include/jade_bvh.h, jade_scene_set_direct_sampling

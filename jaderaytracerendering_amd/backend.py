@@ -30,7 +30,7 @@ def make_params(width, height, spp, eye, camera, frame=0, tile_rank=0, tile_nran
     p.tile_rank, p.tile_nranks = int(tile_rank), int(tile_nranks)
     p.device_id, p.threads = int(device_id), int(threads)
     p.walk = int(walk)  # jade_rt.h, JADE_WALK_*: 0 = the reference's walk (V / T equal the oracle's), 1 = early exits, 2 = + occluder cache
-    p.env_sampling = int(env_sampling)  # JADE_ENV_*: 0 = the reference's estimator; 1 = environment rays by importance (non-parity)
+    p.env_sampling = int(env_sampling)  # JADE_ENV_*: 0 = the reference's estimator; 1 = environment rays by importance, 2 = importance mixed with the hemisphere draw (non-parity)
     return p
 
 

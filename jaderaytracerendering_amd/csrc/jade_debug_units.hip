@@ -1,6 +1,6 @@
 // jade_debug_units.hip — test-only entry points that run the shared numeric pieces on the device one by one: every routine of
 // include/jade_fpmath.h, the environment lookup (sample_hdr, jade_shade.h), the environment importance draw (env_sample, jade_shade.h,
-// and its table, env_alias_table, jade_scene_prep.hip; the one-light draw, light_sample, and its table, light_alias_table; the cosine bounce draw, cosine_dir_with; the weights of JADE_DIRECT_MIS, mis_terms, and its table, mis_table), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
+// and its table, env_alias_table, jade_scene_prep.hip; the environment mixture's draw over the same table, env_mix_sample_with and env_texel_of, tests/test_gpu_env_mixture.py; the one-light draw, light_sample, and its table, light_alias_table; the cosine bounce draw, cosine_dir_with; the weights of JADE_DIRECT_MIS, mis_terms, and its table, mis_table), the tone curve (tone_pack_bgr8, jade_device.h) the thin-lens ray (lens_ray,
 // jade_device.h; tests/test_lens_cpu.py, tests/test_gpu_lens.py) and the BSSRDF branch's exit-triangle search (exit_search, jade_shade.h, and
 // its tables, guide_tables, jade_scene_prep.hip; tests/test_area_search_cpu.py, tests/test_gpu_area_search.py).
 // NOT part of jade_rt.h and NOT in libjade_hip.so: only a -DJADE_DEBUG_EXPORTS=1 build (libjade_hip_debug.so) has them
@@ -164,6 +164,32 @@ __global__ void k_debug_env_sample_rng(DevScene S, int n, uint32_t* rng, float* 
   uint32_t state = rng[i];
   put3(dir, i, env_sample(S, &state, ratio + i));
   rng[i] = state;
+}
+
+// env_mix_sample_with's body (jade_shade.h; include/jade_rt.h, JADE_ENV_MIXTURE) on row i = (u0..u4, n[3], side, bounce technique), MIX_ROW
+// floats: the direction, m and the info word (EMI_*) ...
+#define MIX_ROW 10
+#define MIX_ROW_RNG 5
+__global__ void k_debug_env_mix_sample(DevScene S, int n, const float* rows, float* dir, float* m, uint32_t* info) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + MIX_ROW * (size_t)i;
+  const jvec3 nrm = jv(r[5], r[6], r[7]);
+  put3(dir, i, r[9] != 0.0f ? env_mix_sample_at<true>(S, r, nrm, r[8], m + i, info + i) : env_mix_sample_at<false>(S, r, nrm, r[8], m + i, info + i));
+}
+// ... and the wrapper the shading kernel calls, on row i = (n[3], side, bounce technique) from RNG state rng[i]; the state it leaves is written back
+__global__ void k_debug_env_mix_sample_rng(DevScene S, int n, const float* rows, uint32_t* rng, float* dir, float* m, uint32_t* info) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + MIX_ROW_RNG * (size_t)i;
+  const jvec3 nrm = jv(r[0], r[1], r[2]);
+  uint32_t state = rng[i];
+  put3(dir, i, r[4] != 0.0f ? env_mix_sample<true>(S, &state, nrm, r[3], m + i, info + i) : env_mix_sample<false>(S, &state, nrm, r[3], m + i, info + i));
+  rng[i] = state;
+}
+__global__ void k_debug_env_texel_of(DevScene S, int n, const float* d, uint32_t* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = env_texel_of(S, V3(d + 3 * i));
 }
 
 // cosine_dir_with's body (jade_shade.h; include/jade_bvh.h "The bounce, stated") on row i = (n[3], s, u1, u2): the direction and whether
@@ -385,6 +411,90 @@ int jade_debug_env_sample_rng(jade_scene* s, int32_t n, const uint32_t* rng_in, 
   HIP_TRY(hipMemcpyAsync(rng_out, bs.p, N * 4, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(out_dir, bd.p, N * 12, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipMemcpyAsync(out_ratio, br.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// The rows jade_debug_env_mix_sample (width = MIX_ROW: u0..u4, n[3], side, technique) and jade_debug_env_mix_sample_rng (width = MIX_ROW_RNG:
+// n[3], side, technique) run: every uniform lies in [0, 1] (a NaN does not) - the slot is formed from u1 x N - and the technique is
+// JADE_BOUNCE_UNIFORM or JADE_BOUNCE_COSINE as a float.  The normal and the side may hold anything: no index is formed from them (the
+// texel of a direction is clamped into the map, env_texel_of).  Checked on the host before anything is launched.  No HIP call.
+int jade_debug_env_mix_rows(int32_t n, int32_t width, const float* rows) {
+  if (!rows) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (width != MIX_ROW && width != MIX_ROW_RNG) return jade_fail(JADE_ERR_INVALID, "row width is neither the draw's nor the RNG entry's");
+  if (n <= 0 || n > kDebugMaxRows / width) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  for (int32_t i = 0; i < n; ++i) {
+    const float* r = rows + (size_t)width * i;
+    for (int k = 0; width == MIX_ROW && k < 5; ++k)
+      if (!(r[k] >= 0.0f && r[k] <= 1.0f)) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": a uniform outside [0, 1]");
+    const float t = r[width - 1];
+    if (!(t == (float)JADE_BOUNCE_UNIFORM || t == (float)JADE_BOUNCE_COSINE)) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": unknown bounce technique");
+  }
+  return JADE_OK;
+}
+
+// (out_dir[i], out_m[i], out_info[i]) = env_mix_sample_with's body on rows[i] = (u0..u4, n[3], side, technique): the draw of JADE_ENV_MIXTURE.
+// out_info: the texel in bits 0..23, bit 29 = a sky draw on the wrong side, bit 30 = the hemisphere technique, bit 31 = own (sky draws).
+int jade_debug_env_mix_sample(jade_scene* s, int32_t n, const float* rows, float* out_dir, float* out_m, uint32_t* out_info) {
+  if (!s || !out_dir || !out_m || !out_info) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (int rc = jade_debug_env_mix_rows(n, MIX_ROW, rows)) return rc;
+  if (int rc = env_sample_scene_ok(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bu, bd, br, bt;
+  HIP_TRY(upload(bu, rows, MIX_ROW * N, s->stream));
+  HIP_TRY(bd.alloc(N * 12));
+  HIP_TRY(br.alloc(N * 4));
+  HIP_TRY(bt.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_env_mix_sample, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bu.as<float>(), bd.as<float>(),
+                     br.as<float>(), bt.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_dir, bd.p, N * 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_m, br.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_info, bt.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// ... and the wrapper the shading kernel calls, on rows[i] = (n[3], side, technique) from the RNG states rng_in[i]: rng_out[i] is the state after.
+int jade_debug_env_mix_sample_rng(jade_scene* s, int32_t n, const float* rows, const uint32_t* rng_in, uint32_t* rng_out, float* out_dir, float* out_m,
+                                  uint32_t* out_info) {
+  if (!s || !rng_in || !rng_out || !out_dir || !out_m || !out_info) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (int rc = jade_debug_env_mix_rows(n, MIX_ROW_RNG, rows)) return rc;
+  if (int rc = env_sample_scene_ok(s)) return rc;
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bu, bs, bd, br, bt;
+  HIP_TRY(upload(bu, rows, MIX_ROW_RNG * N, s->stream));
+  HIP_TRY(upload(bs, rng_in, N, s->stream));
+  HIP_TRY(bd.alloc(N * 12));
+  HIP_TRY(br.alloc(N * 4));
+  HIP_TRY(bt.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_env_mix_sample_rng, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bu.as<float>(), bs.as<uint32_t>(),
+                     bd.as<float>(), br.as<float>(), bt.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(rng_out, bs.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_dir, bd.p, N * 12, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_m, br.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_info, bt.p, N * 4, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// out_texel[i] = env_texel_of(scene, dirs[i]) (jade_shade.h): the texel the mixture looks q up in for a hemisphere direction.  Any
+// direction may be asked - the answer is clamped into the map - so the rows' check is the scene's: it has a map.
+int jade_debug_env_texel_of(jade_scene* s, int32_t n, const float* dirs, uint32_t* out_texel) {
+  if (!s || !dirs || !out_texel) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / 3) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (!s->dev.env || s->dev.env_w <= 0 || s->dev.env_h <= 0) return jade_fail(JADE_ERR_INVALID, "the scene has no environment map");
+  HIP_TRY(hipSetDevice(s->device));
+  const size_t N = (size_t)n;
+  DevBuf bd, bo;
+  HIP_TRY(upload(bd, dirs, 3 * N, s->stream));
+  HIP_TRY(bo.alloc(N * 4));
+  hipLaunchKernelGGL(k_debug_env_texel_of, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, s->dev, n, bd.as<float>(), bo.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_texel, bo.p, N * 4, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }
@@ -656,7 +766,20 @@ int jade_debug_shade_mode_host(int32_t env_importance, int32_t lens, int32_t shu
   if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
   uint32_t m = 0;
   std::string why;
-  if (const int rc = shade_mode_for(env_importance != 0, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why)) return jade_fail(rc, why);
+  if (const int rc = shade_mode_for(env_importance != 0 ? JADE_ENV_IMPORTANCE : JADE_ENV_REFERENCE, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why)) return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
+// ... and with the value of jade_render_params.env_sampling (JADE_ENV_*; any other value is JADE_ERR_INVALID, as jade_render_begin answers it).
+int jade_debug_shade_mode_env_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                   uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why)) return jade_fail(rc, why);
   *mode = m;
   return JADE_OK;
 }

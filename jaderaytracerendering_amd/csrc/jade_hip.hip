@@ -22,7 +22,7 @@
 //   k_arm / k_shade_lean  list the records with work / shade light samples over all records: the schedules without the
 //                   fused pass (flushes, JADE_FUSED=0)
 //   k_shade_mode<M> / k_shade_lean_mode<M>  k_shade / k_shade_lean of a non-parity render mode M (ShadeMode, jade_runtime.h: environment
-//                   importance, lens, shutter, one-light, cosine bounces, MIS), one instantiation per built mode; k_shade, k_shade_binned
+//                   importance or the environment mixture, lens, shutter, one-light, cosine bounces, MIS), one instantiation per built mode; k_shade, k_shade_binned
 //                   and k_shade_lean themselves are mode 0, the parity shading.  shade_launcher picks by the render's mode
 //
 // shade/trace alternate until a shade pass emits nothing (every path record has
@@ -171,7 +171,9 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // stated"; non-parity; the kernels of a mode with SM_COSINE only).  Nothing of it travels with the record.
 // MIS: the emitter rays and the indirect ray weighed against each other (include/jade_bvh.h, "The direct light, stated"; non-parity; the
 // kernels of a mode with SM_MIS only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
+// ENVMIX: the environment ray by the one-sample mixture of ENVIS's draw and the bounce sampling's (include/jade_rt.h, JADE_ENV_MIXTURE; non-parity;
+// the kernels of a mode with SM_ENVMIX only, with ENVIS).  begin_bounce alone knows it: m travels where ENVIS's ratio does.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
                                                     const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr) {
@@ -275,7 +277,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           defer = true;
           break;
         }
-        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS, COSINE>(S, px, c, &l_final, lights, &light)) {
+        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS, COSINE, ENVMIX>(S, px, c, &l_final, lights, &light)) {
           st = c.stage;
           if (!ENVIS || c.n_emit_rays != 0) break;
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
@@ -457,7 +459,7 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
 // The flags are shade_record's: k_shade passes none, k_shade_mode<M> those of its mode (JADE_MODE_FLAGS).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
@@ -480,7 +482,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis);
+  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS, ENVMIX>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -494,7 +496,7 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(De
 // constants (ShutterConst, by value) under SM_SHUTTER; the alias table over the scene's emitter entries (`lights`; read under SM_LIGHTS
 // only) under SM_LIGHTS or SM_COSINE; that and the per-triangle table {m, M} (mis_table, jade_scene_prep.hip) under SM_MIS.
 // JADE_MODE_FLAGS: shade_record's / shade_kernel_body's template flags of mode M.
-#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0
+#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0, ((M) & SM_ENVMIX) != 0
 template <uint32_t M, class... X>
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
@@ -1513,15 +1515,16 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
     return jade_fail(JADE_ERR_INVALID, "bad image size or tile partition");
   if (rp->walk != JADE_WALK_REFERENCE && rp->walk != JADE_WALK_EARLY_EXIT && rp->walk != JADE_WALK_EARLY_EXIT_CACHED)
     return jade_fail(JADE_ERR_INVALID, "unknown walk (JADE_WALK_*)");
-  if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE) return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
-  if (rp->env_sampling == JADE_ENV_IMPORTANCE && !env_importance_fits(s->dev.env_w, s->dev.env_h))
+  if (rp->env_sampling != JADE_ENV_REFERENCE && rp->env_sampling != JADE_ENV_IMPORTANCE && rp->env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (rp->env_sampling != JADE_ENV_REFERENCE && !env_importance_fits(s->dev.env_w, s->dev.env_h))  // (the mixture draws from the same table)
     return jade_fail(JADE_ERR_UNSUPPORTED, "env_sampling: JADE_ENV_IMPORTANCE takes environment maps of at most 2^24 texels (JADE_ENV_IMPORTANCE_MAX_TEXELS)");
   if (s->light_sampling == JADE_LIGHTS_ONE && !light_sampling_fits(s->n_emit))
     return jade_fail(JADE_ERR_UNSUPPORTED, "light sampling: JADE_LIGHTS_ONE takes at most 2^24 emitter entries (JADE_LIGHTS_ONE_MAX_ENTRIES)");
   // the scene's settings as they are now make the render's mode, if that mode is built (shade_mode_for, jade_runtime.h)
   uint32_t mode = 0;
   std::string why;
-  if (const int rc = shade_mode_for(rp->env_sampling == JADE_ENV_IMPORTANCE, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
+  if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
                                     s->direct_sampling, &mode, &why))
     return jade_fail(rc, why);
   HIP_TRY(hipSetDevice(s->device));
@@ -1599,7 +1602,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
   s->ps.early_exit = rp->walk == JADE_WALK_EARLY_EXIT_CACHED ? 2u : rp->walk == JADE_WALK_EARLY_EXIT ? 1u : 0u;
-  s->ps.env_sampling = rp->env_sampling == JADE_ENV_IMPORTANCE ? 1u : 0u;
+  s->ps.env_sampling = rp->env_sampling != JADE_ENV_REFERENCE ? 1u : 0u;  // (either mode may leave a bounce without a ray: shade_record)
   memcpy(s->ps.eye, rp->eye, sizeof s->ps.eye);
   s->ps.lens_k = lens_k;  // (setup_state wrote the record layout into s->ps)
   HIP_TRY(upload(s->b_tiles, s->tile_ids.data(), s->tile_ids.size(), s->stream));

@@ -204,15 +204,16 @@ enum ShadeMode : uint32_t {
   SM_LIGHTS = 8u,    // jade_scene_set_light_sampling = JADE_LIGHTS_ONE
   SM_COSINE = 16u,   // jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE
   SM_MIS = 32u,      // jade_scene_set_direct_sampling = JADE_DIRECT_MIS
+  SM_ENVMIX = 64u,   // jade_render_params.env_sampling = JADE_ENV_MIXTURE: raised together with SM_ENVIS, whose record steps it shares
 };
-// THE list of the modes that are built, written once: X(m) for each, under either environment sampling.  shade_mode_built (so what
+// THE list of the modes that are built, written once: X(m) for each, under each of the three environment samplings.  shade_mode_built (so what
 // jade_render_begin accepts) and shade_launcher (jade_hip.hip: the kernel a render's passes launch) are both made from it, so a mode
 // cannot be accepted without a kernel or have a kernel that is never reached.  Adding a render mode: DESIGN.md 3.14.
 #define JADE_SHADE_MODES_BUILT(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS)
-#define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS)
+#define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS) X((m) | SM_ENVIS | SM_ENVMIX)
 static inline bool shade_mode_built(uint32_t mode) {
 #define JADE_X(m) if (mode == (m)) return true;
   JADE_SHADE_MODES_BUILT(JADE_X)
@@ -222,9 +223,10 @@ static inline bool shade_mode_built(uint32_t mode) {
 // What jade_render_begin makes of the settings a render is asked with: JADE_OK and its mode, or the refusal's code and text.  A mode
 // is accepted if and only if it is in the list above; the texts say why the others are not, first reason first: one-light sampling's
 // own check, then the cosine bounce's, then what MIS needs.  Pure: no HIP call, no scene (tests/test_shade_modes_cpu.py).
-static inline int shade_mode_for(bool env_importance, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
+// env_sampling: JADE_ENV_* (a value jade_render_begin has checked); the mixture is refused exactly where importance is, in the same words.
+static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
                                  std::string* why) {
-  const uint32_t m = (env_importance ? SM_ENVIS : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
+  const uint32_t m = (env_sampling == JADE_ENV_IMPORTANCE ? SM_ENVIS : env_sampling == JADE_ENV_MIXTURE ? SM_ENVIS | SM_ENVMIX : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
                      (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u);
   if (shade_mode_built(m)) {
     *mode = m;

@@ -24,9 +24,8 @@ static __device__ __forceinline__ int mirror_index(int i, int n) {
   return m;
 }
 
-// sampleHdr / SampleSphericalMap, PathTrace.cu:686-702; software bilinear with
-// mirror addressing in place of tex2D (gfx950 has no sampler path).
-static __device__ jvec3 sample_hdr(const DevScene& S, jvec3 v) {
+// SampleSphericalMap's coordinates of direction v (PathTrace.cu:686-692), NaN rule included: the statements sample_hdr and env_texel_of share
+static __device__ __forceinline__ void env_uv_of(jvec3 v, float* u_out, float* v_out) {
   jvec3 nv = jv_normalize(v);
   float ux = jade_atan2f(nv.z, nv.x);
   float uy = jade_asinf(nv.y);
@@ -39,9 +38,18 @@ static __device__ jvec3 sample_hdr(const DevScene& S, jvec3 v) {
   ux = (float)((double)ux + 0.5);
   uy = (float)((double)uy + 0.5);
   uy = (float)(1.0 - (double)uy);
-  const int W = S.env_w, H = S.env_h;
   if (jade_isnan(ux)) ux = 0.0f;
   if (jade_isnan(uy)) uy = 0.0f;
+  *u_out = ux;
+  *v_out = uy;
+}
+
+// sampleHdr / SampleSphericalMap, PathTrace.cu:686-702; software bilinear with
+// mirror addressing in place of tex2D (gfx950 has no sampler path).
+static __device__ jvec3 sample_hdr(const DevScene& S, jvec3 v) {
+  float ux, uy;
+  env_uv_of(v, &ux, &uy);
+  const int W = S.env_w, H = S.env_h;
   float x = ux * (float)W - 0.5f;
   float y = uy * (float)H - 0.5f;
   float xf = jade_floorf(x), yf = jade_floorf(y);
@@ -64,13 +72,33 @@ static __device__ jvec3 sample_hdr(const DevScene& S, jvec3 v) {
   return c;
 }
 
-static __device__ __forceinline__ jvec3 sphere_dir(uint32_t* rng) {  // PathTrace.cu:968-971
-  float cosine_theta = (float)(2.0 * ((double)jade_rand(rng) - 0.5));
+// The texel of the map direction v lies in (JADE_ENV_MIXTURE, include/jade_rt.h): column min((uint32)fl(u W), W - 1), row
+// min((uint32)fl(v H), H - 1) of env_uv_of's coordinates - a negative product or a NaN converts to 0 - so the answer is below W * H
+// whatever v holds.
+static __device__ __forceinline__ uint32_t env_texel_of(const DevScene& S, jvec3 v) {
+  float ux, uy;
+  env_uv_of(v, &ux, &uy);
+  const uint32_t W = (uint32_t)S.env_w, H = (uint32_t)S.env_h;
+  const float fx = ux * (float)W, fy = uy * (float)H;
+  uint32_t i = fx > 0.0f ? (uint32_t)fx : 0u;  // (a NaN compares false)
+  uint32_t j = fy > 0.0f ? (uint32_t)fy : 0u;
+  i = i < W - 1u ? i : W - 1u;
+  j = j < H - 1u ? j : H - 1u;
+  return j * W + i;
+}
+
+// PathTrace.cu:968-971 on two uniforms from `next`, cosine first
+template <class NextUniform>
+static __device__ __forceinline__ jvec3 sphere_dir_with(NextUniform next) {
+  float cosine_theta = (float)(2.0 * ((double)next() - 0.5));
   float sine_theta = jade_sqrt(1.0f - cosine_theta * cosine_theta);
-  float fai_value = (float)(2.0 * JADE_PI_D * (double)jade_rand(rng));
+  float fai_value = (float)(2.0 * JADE_PI_D * (double)next());
   float sn, cs;
   jade_sincosf(fai_value, &sn, &cs);
   return jv(sine_theta * cs, sine_theta * sn, cosine_theta);
+}
+static __device__ __forceinline__ jvec3 sphere_dir(uint32_t* rng) {  // ... with two successive jade_rand draws
+  return sphere_dir_with([rng]() { return jade_rand(rng); });
 }
 
 // Environment importance sampling (jade_render_params.env_sampling = JADE_ENV_IMPORTANCE; NOT the reference's estimator), as
@@ -80,8 +108,10 @@ static __device__ __forceinline__ jvec3 sphere_dir(uint32_t* rng) {  // PathTrac
 // The body takes its uniforms from `next` where it needs them - u1 (the slot), u2 (own / alias), u3, u4 (the point) - so that the
 // shading kernel's code is what it was with jade_rand written in those four places, and a test can feed the four numbers
 // (jade_debug_units.hip).  *texel: the texel drawn, bit 31 = own (tests only; a caller that passes a dead variable pays nothing for it).
+// env_sample_core_with: the draw up to the direction, with what a weight is formed from - *st_out = st, *q_out = the chosen texel's q -
+// so that JADE_ENV_MIXTURE's sky technique (env_mix_sample_with) is these very statements.
 template <class NextUniform>
-static __device__ __forceinline__ jvec3 env_sample_with(const DevScene& S, NextUniform next, float* ratio, uint32_t* texel) {
+static __device__ __forceinline__ jvec3 env_sample_core_with(const DevScene& S, NextUniform next, float* st_out, float* q_out, uint32_t* texel) {
   const uint32_t W = (uint32_t)S.env_w, N = W * (uint32_t)S.env_h;  // N <= 2^24: jade_render_begin refuses the mode otherwise
   uint32_t idx = (uint32_t)(next() * (float)N);
   idx = idx < N ? idx : N - 1u;
@@ -99,9 +129,17 @@ static __device__ __forceinline__ jvec3 env_sample_with(const DevScene& S, NextU
   jade_sincosf(theta, &st, &ct);
   jade_sincosf(phi, &sp, &cp);
   st = st > 0.0f ? st : 0.0f;  // a weight is never negative, whatever a sine rounds to at theta = fl(PI) (u4 = 1 in the bottom row; jade_sincosf: +1.5e-7)
+  *st_out = st;
+  *q_out = pdf_n;
+  return jv(st * cp, ct, st * sp);
+}
+template <class NextUniform>
+static __device__ __forceinline__ jvec3 env_sample_with(const DevScene& S, NextUniform next, float* ratio, uint32_t* texel) {
+  float st, pdf_n;
+  const jvec3 d = env_sample_core_with(S, next, &st, &pdf_n, texel);
   // pdf(direction) = pdf_n / (2 pi^2 sin theta); against 1 / (2 pi): ratio = pi sin theta / pdf_n
   *ratio = (float)JADE_PI_D * st / pdf_n;
-  return jv(st * cp, ct, st * sp);
+  return d;
 }
 // ... with four successive jade_rand draws: what bounce_branch calls
 static __device__ __forceinline__ jvec3 env_sample(const DevScene& S, uint32_t* rng, float* ratio) {
@@ -197,6 +235,61 @@ static __device__ __forceinline__ jvec3 cosine_dir_at(const float* u2, jvec3 n, 
 static __device__ __forceinline__ float cosine_weight(jvec3 n, jvec3 rd) {
   const float nn = jv_dot(n, n);
   return (nn > 0 && nn < jade_u2f(0x7f800000u)) ? 0.5f * jade_sqrt(nn) : jade_fabs(jv_dot(n, rd));
+}
+
+// The environment mixture (jade_render_params.env_sampling = JADE_ENV_MIXTURE; NOT the reference's estimator), as include/jade_rt.h states
+// it draw by draw: five uniforms from `next` - u0 picks the technique, u1..u4 are env_sample_with's four (the sky technique, u0 < 0.5) or
+// the bounce sampling's two and two that are drawn and dropped (the hemisphere technique: cosine_dir_with under COSINE, sphere_dir's
+// statements and the reference's flip otherwise).  n, side: the normal and the number whose sign is the surface's side, as cosine_dir_with
+// takes them - the kernels pass the product term of the reference's flip.  *m = (1 / 2 pi) / (the mixture's density), what the
+// reference's weight is multiplied with: it stands where JADE_ENV_IMPORTANCE has ratio.  *info (EMI_*): the texel of the direction, the
+// technique, own / alias of a sky draw, and whether a sky draw lay on the wrong side - the caller traces no ray then.  A hemisphere
+// direction is never tested again: it is on the surface's side by construction, whatever its dot product with n rounds to.
+// One 16-B gather either way (the slot's entry, or the entry of the direction's texel: q_own of entry t is fl(q_t)).
+enum : uint32_t { EMI_TEXEL = 0x00ffffffu, EMI_WRONG = 1u << 29, EMI_HEMI = 1u << 30, EMI_OWN = 1u << 31 };
+template <bool COSINE, class NextUniform>
+static __device__ __forceinline__ jvec3 env_mix_sample_with(const DevScene& S, NextUniform next, jvec3 n, float side, float* m, uint32_t* info) {
+  const float u0 = next();
+  const float nn = jv_dot(n, n);
+  const bool axis = COSINE && nn > 0 && nn < jade_u2f(0x7f800000u);  // cosine_dir_with's predicate: otherwise the uniform form of m
+  jvec3 w;
+  float s, q;
+  uint32_t word;
+  if (u0 < 0.5f) {
+    w = env_sample_core_with(S, next, &s, &q, &word);  // (bit 31 of the texel word is EMI_OWN)
+    if (jv_dot(w, n) * side < 0) word |= EMI_WRONG;
+  } else {
+    if (COSINE) {
+      bool fallback;
+      w = cosine_dir_with(next, n, side, &fallback);
+    } else {
+      w = sphere_dir_with(next);
+      if (jv_dot(w, n) * side < 0) w = jv_neg(w);
+    }
+    (void)next();  // u3, u4: drawn, so that every later draw of the sample is where the sky technique leaves it
+    (void)next();
+    s = jade_sqrt(w.x * w.x + w.z * w.z);
+    const uint32_t t = env_texel_of(S, w);
+    q = jade_u2f(S.env_alias[t].z);
+    word = t | EMI_HEMI;
+  }
+  // m = (1 / 2 pi) / (p_sky / 2 + p_hemi / 2), p_sky = q / (2 pi^2 s), p_hemi = 1 / 2 pi or c / pi
+  const float ps = (float)JADE_PI_D * s;
+  const float c = jade_fabs(jv_dot(n, w)) / jade_sqrt(nn);
+  *m = (2.0f * ps) / (axis ? q + (2.0f * ps) * c : q + ps);
+  *info = word;
+  return w;
+}
+// ... with five successive jade_rand draws: what bounce_branch calls
+template <bool COSINE>
+static __device__ __forceinline__ jvec3 env_mix_sample(const DevScene& S, uint32_t* rng, jvec3 n, float side, float* m, uint32_t* info) {
+  return env_mix_sample_with<COSINE>(S, [rng]() { return jade_rand(rng); }, n, side, m, info);
+}
+// ... and with five given numbers
+template <bool COSINE>
+static __device__ __forceinline__ jvec3 env_mix_sample_at(const DevScene& S, const float* u5, jvec3 n, float side, float* m, uint32_t* info) {
+  int k = 0;
+  return env_mix_sample_with<COSINE>(S, [u5, &k]() { return u5[k++]; }, n, side, m, info);
 }
 
 // Multiple importance sampling of the emitters (jade_scene_set_direct_sampling = JADE_DIRECT_MIS; NOT the reference's estimator), as
@@ -595,7 +688,9 @@ static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx
 // *light = the entry drawn: it travels with the record (the fourth word of PathState.hdr, shade_record) to consume.
 // COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"; compiled apart likewise, modes with SM_COSINE): the environment ray - unless
 // ENVIS draws it - and the indirect ray come from cosine_dir_rng in place of sphere_dir and its flip, on the same two draws.
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
+// ENVMIX: JADE_ENV_MIXTURE (include/jade_rt.h; with ENVIS only, compiled apart likewise, modes with SM_ENVMIX): where ENVIS calls env_sample
+// this calls env_mix_sample - five draws, the sky technique or the bounce sampling's own direction - and m travels where ratio does.
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool ENVMIX = false>
 static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final,
                                                      const uint4* lights = nullptr, uint32_t* light = nullptr) {
   const jade_triangle* T = S.tris;  // vertices only
@@ -664,8 +759,9 @@ static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S
       uint32_t noenv = 0;
       if (ENVIS) {  // (non-parity mode: by importance; a direction on the wrong side contributes nothing and is not traced)
         float ratio;
-        const jvec3 ray_direction = env_sample(S, &c.rng, &ratio);
-        if (jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) {
+        uint32_t mix = 0;
+        const jvec3 ray_direction = ENVMIX ? env_mix_sample<COSINE>(S, &c.rng, t_norm, jv_dot(inner_direction, t_norm), &ratio, &mix) : env_sample(S, &c.rng, &ratio);
+        if (ENVMIX ? (mix & EMI_WRONG) != 0 : jv_dot(ray_direction, t_norm) * jv_dot(inner_direction, t_norm) < 0) {
           px.set_hit(nL, -2);
           noenv = STF_NOENV;
         } else {
@@ -753,8 +849,9 @@ diffuse_like:
     }
     if (ENVIS) {  // (non-parity mode, as in the BSSRDF branch)
       float ratio;
-      const jvec3 ray_direction = env_sample(S, &c.rng, &ratio);
-      if (jv_dot(ray_direction, n) * side < 0) {
+      uint32_t mix = 0;
+      const jvec3 ray_direction = ENVMIX ? env_mix_sample<COSINE>(S, &c.rng, n, side, &ratio, &mix) : env_sample(S, &c.rng, &ratio);
+      if (ENVMIX ? (mix & EMI_WRONG) != 0 : jv_dot(ray_direction, n) * side < 0) {
         px.set_hit(nL, -2);
         c.flags |= STF_NOENV;
       } else {
@@ -787,12 +884,12 @@ diffuse_like:
 
 // Sample the bounce at the current vertex and emit its rays.  Returns false
 // if the path ended at this vertex (l_final holds the last l_dir).
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false>
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool ENVMIX = false>
 static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr,
                                     uint32_t* light = nullptr) {
   const int type = bounce_classify(S, c, l_final);
   if (type == BT_END) return false;
-  return bounce_branch<ENVIS, LIGHTS, COSINE>(type, S, px, c, l_final, lights, light);
+  return bounce_branch<ENVIS, LIGHTS, COSINE, ENVMIX>(type, S, px, c, l_final, lights, light);
 }
 
 // Outcome of folding the pending rays' results into the path.

@@ -96,7 +96,7 @@ static bool write_pfm1(const std::string& path, const float* v, int width, int h
 static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
-          "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance] [--one-light]\n"
+          "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
           "                   [--bounce uniform|cosine] [--direct rays|mis]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
@@ -138,6 +138,8 @@ static void usage() {
           "                  two >= 2 (default 16); --error-floor F > 0 (default 0.01) is added to the mean in the error's denominator\n"
           "  --env-importance: environment-visibility rays drawn by the sky's luminance instead of uniformly (NOT the reference's samples: the\n"
           "                    same image with less noise under a sky with a sun; the oracle backend refuses it)\n"
+          "  --env-mixture: each such ray drawn either by the sky's luminance or as the bounce sampling draws it, half and half, weighed by the\n"
+          "                 balance heuristic (JADE_ENV_MIXTURE; NOT the reference's samples; excludes --env-importance; the oracle backend refuses it)\n"
           "  --reference-walk: every hitBVH query walks what the reference walks (nodes_visited / tris_tested equal the oracle's);\n"
           "                    default: shadow / environment-visibility walks end at the hit that settles them - the same image, bit for bit\n"
           "  NAME: tiny, tinyjade, C1, C2, C3, C4, C5 (SURVEY.md section 8d); C3G = C3 with a DIR_REFRACT glass statue\n");
@@ -147,7 +149,7 @@ int main(int argc, char** argv) {
   std::string config, args_file, out = "RenderResultHip.bmp", backend, env;
   int width = 0, height = 0, spp = 0, device = 0;
   bool reference_walk = false;
-  bool env_importance = false;
+  bool env_importance = false, env_mixture = false;
   double adaptive = 0.0, error_floor = 0.01;
   int min_spp = 16;
   bool use_adaptive = false;
@@ -199,6 +201,7 @@ int main(int argc, char** argv) {
     else if (a == "--device") device = atoi(need("--device"));
     else if (a == "--reference-walk") reference_walk = true;
     else if (a == "--env-importance") env_importance = true;
+    else if (a == "--env-mixture") env_mixture = true;
     else if (a == "--one-light") one_light = true;
     else if (a == "--bounce") {
       const std::string v = need("--bounce");
@@ -253,6 +256,7 @@ int main(int argc, char** argv) {
     else { usage(); return 2; }
   }
   // bad values end here, before a scene is built or a backend loaded
+  if (env_importance && env_mixture) { fprintf(stderr, "--env-importance and --env-mixture exclude each other: give one of them\n"); return 2; }
   if (use_adaptive && !(adaptive > 0.0)) { fprintf(stderr, "--adaptive must be > 0\n"); return 2; }
   if (min_spp < 2 || (min_spp & (min_spp - 1)) != 0) { fprintf(stderr, "--min-spp must be a power of two >= 2\n"); return 2; }
   if (!(error_floor > 0.0)) { fprintf(stderr, "--error-floor must be > 0\n"); return 2; }
@@ -418,7 +422,7 @@ int main(int argc, char** argv) {
   rp.tile_nranks = 1;
   rp.device_id = device;
   rp.walk = reference_walk ? JADE_WALK_REFERENCE : JADE_WALK_EARLY_EXIT;
-  rp.env_sampling = env_importance ? JADE_ENV_IMPORTANCE : JADE_ENV_REFERENCE;  // (non-parity: another estimator of the same image; HIP backend only)
+  rp.env_sampling = env_mixture ? JADE_ENV_MIXTURE : env_importance ? JADE_ENV_IMPORTANCE : JADE_ENV_REFERENCE;  // (non-parity: another estimator of the same image; HIP backend only)
   if (use_aperture) {
     jade_lens_params lens;
     lens.aperture_radius = (float)aperture;
@@ -450,7 +454,8 @@ int main(int argc, char** argv) {
   if (bounce >= 0 && api.scene_set_bounce_sampling(dev, bounce) != JADE_OK) { fprintf(stderr, "bounce sampling: %s\n", api.last_error()); return 1; }
   if (direct >= 0 && api.scene_set_direct_sampling(dev, direct) != JADE_OK) { fprintf(stderr, "direct sampling: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
-                                    (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "");
+                                    (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
