@@ -635,6 +635,84 @@ int jade_scene_get_bounce_sampling(jade_scene* scene, int* mode);
 int jade_scene_set_direct_sampling(jade_scene* scene, int mode);
 int jade_scene_get_direct_sampling(jade_scene* scene, int* mode);
 
+/* ---- Light passes ----
+ *
+ * A render can keep, beside its frame, the same radiance split into JADE_PASS_COUNT passes by the statement that produced each addend:
+ * emission, background, sky light and lamp light, each direct and indirect, per kind of vertex - what an offline renderer calls render
+ * passes or light AOVs, and what says where a frame's bright samples come from.  jade_scene_set_passes(scene, 1) is a property of the
+ * scene handle, read by the next jade_render_begin; a render in progress keeps what it began with.  With passes off (the default) a
+ * render is today's in every kernel, bit and counter.  With passes on the FRAME is unchanged in every bit, and so is every integer
+ * counter of jade_stats, against the same render under the list schedule (below); jade_render_passes returns the split.
+ *
+ * ---- The passes, stated ----
+ * tests/passes_spec.py is this text in float64.  A finished sample's colour is le + acc + thr * l_final, where acc is the sum over the
+ * pushed vertices of thr_at_that_vertex * l_dir (jade_rt.h; PathTrace.cu:1410-1413 unwinds the same sum).  Every addend belongs to
+ * exactly one pass, decided by the statement that formed it:
+ *
+ *   JADE_PASS_BACKGROUND (0)    sampleHdr(d) of a camera ray that hit nothing
+ *   JADE_PASS_EMISSION (1)      le, the emission of the camera ray's triangle; and thr * emissive where the head of the bounce loop ends a
+ *                               path on an emitter (PathTrace.cu:916-920, and the mirror branch's emissive statement).  The reference
+ *                               counts a directly seen emitter twice: both addends land here.
+ *   JADE_PASS_SPECULAR_SKY (2)  thr * l_final of a mirror ray that hit nothing (:1383-1398) and of a refraction's exit ray that hit
+ *                               nothing (:1239-1257): the sky at the end of a mirror or glass chain
+ *   3 + 4 kind + 2 source + depth (3 .. 14)   the parts of a sampling vertex's l_dir:
+ *       kind    0 diffuse (:1266-1364), 1 SSS-diffuse (:931-1028), 2 BSSRDF (:1029-1178)
+ *       source  0 the emitters: the shadow-ray loop's terms and, under JADE_DIRECT_MIS, the bounce term T_B; 1 the sky: the environment
+ *               ray's term, with its JADE_ENV_IMPORTANCE ratio or JADE_ENV_MIXTURE m
+ *       depth   0 if nothing has been pushed when the vertex is folded (the path's push count is 0): the camera ray's own vertex;
+ *               otherwise 1 - a mirror or a refraction pushes too, so a vertex seen through either is a later one
+ *
+ * A part is thr * (scale * sum_of_that_source), all in fp32: the source's terms are added in the order l_dir adds them, scale is the
+ * branch's own (k, k / 0.5 at an SSS-diffuse vertex, k / (1 - 0.5) at a BSSRDF vertex, the constants l_dir is multiplied with), thr the
+ * throughput before that vertex's push.  l_dir, acc and thr themselves are formed by the unchanged statements.  A part that is 0 in all
+ * three channels is not added.
+ *
+ * Two quirks of the reference are followed, not repaired:
+ *   "surface is not close" (:1231): the refraction loop returns 0 and the sample's colour is le alone.  The parts the sample has
+ *   gathered are dropped; only le goes to JADE_PASS_EMISSION.
+ *   The 128th push: the path ends with le + acc + thr_new * l_final, where l_final is the l_dir just pushed - that vertex is counted
+ *   again with the new throughput.  The second addend is split exactly as the first.
+ *
+ * Per record the parts of a sample are added in the order they are formed, then le; a finished sample's sums are added to the
+ * record's totals in the order its samples end; jade_render_passes adds a pixel's records in ascending order and multiplies with the
+ * factor jade_render_resolve uses for that pixel (1 / samples, or its tile's after jade_render_adaptive).  No atomics: the same bits
+ * every time, under every step split, tile partition and schedule switch; across JADE_RECORDS_PER_PIXEL only the order of the last sum
+ * differs.  For every pixel the sum over the passes equals the frame up to fp32 summation order.
+ *
+ * The schedule is the one a lens runs: no fused first pass, no k_tail, JADE_SHADE_BINNED ignored (those kernels book nothing).  A
+ * record carries 424 bytes more, which jade_render_begin counts when it chooses the records per pixel and when it answers
+ * JADE_ERR_NOMEM.  jade_render_query's JADE_Q_STATE_BYTES counts them.  The jade_render_begin of a render that keeps no passes frees
+ * that memory before it measures what is free; the render in progress ends there, also where that jade_render_begin then fails.
+ *
+ * jade_render_begin refuses passes together with a lens, a shutter or JADE_LIGHTS_ONE with JADE_ERR_UNSUPPORTED (those kernels are
+ * not built yet), after the other modes' own refusals, and together with JADE_PIXEL_ROTATE.  jade_render_multi refuses a handle that
+ * has passes on with JADE_ERR_UNSUPPORTED: each rank renders its share and calls jade_render_passes.
+ * jade_render_passes: out is JADE_PASS_COUNT x height x width x 3 floats, pass by pass, each laid out and treated for tile shares
+ * exactly as jade_render_resolve's out_rgb; callable wherever jade_render_resolve is, with the same meaning (the samples finished so
+ * far; carried paths are flushed).  JADE_ERR_INVALID, naming the setter, if the render in progress keeps no passes.
+ * jade_pass_name: "background", "emission", "specular_sky", then "<diffuse|sss|bssrdf>_<emitter|sky>_<first|later>"; null out of range. */
+#define JADE_PASS_COUNT 15
+#define JADE_PASS_BACKGROUND 0
+#define JADE_PASS_EMISSION 1
+#define JADE_PASS_SPECULAR_SKY 2
+#define JADE_PASS_DIFFUSE_EMITTER_FIRST 3
+#define JADE_PASS_DIFFUSE_EMITTER_LATER 4
+#define JADE_PASS_DIFFUSE_SKY_FIRST 5
+#define JADE_PASS_DIFFUSE_SKY_LATER 6
+#define JADE_PASS_SSS_EMITTER_FIRST 7
+#define JADE_PASS_SSS_EMITTER_LATER 8
+#define JADE_PASS_SSS_SKY_FIRST 9
+#define JADE_PASS_SSS_SKY_LATER 10
+#define JADE_PASS_BSSRDF_EMITTER_FIRST 11
+#define JADE_PASS_BSSRDF_EMITTER_LATER 12
+#define JADE_PASS_BSSRDF_SKY_FIRST 13
+#define JADE_PASS_BSSRDF_SKY_LATER 14
+
+int jade_scene_set_passes(jade_scene* scene, int on);
+int jade_scene_get_passes(jade_scene* scene, int* on);
+const char* jade_pass_name(int pass);
+int jade_render_passes(jade_scene* scene, float* out);
+
 #ifdef __cplusplus
 }
 #endif

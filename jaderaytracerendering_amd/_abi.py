@@ -19,6 +19,9 @@ ENV_REFERENCE, ENV_IMPORTANCE, ENV_MIXTURE = 0, 1, 2
 LIGHTS_ALL, LIGHTS_ONE = 0, 1  # include/jade_bvh.h, jade_scene_set_light_sampling
 BOUNCE_UNIFORM, BOUNCE_COSINE = 0, 1  # include/jade_bvh.h, jade_scene_set_bounce_sampling
 DIRECT_RAYS, DIRECT_MIS = 0, 1  # include/jade_bvh.h, jade_scene_set_direct_sampling
+PASS_COUNT = 15  # include/jade_bvh.h, jade_render_passes; jade_pass_name gives these
+PASS_NAMES = ("background", "emission", "specular_sky") + tuple(
+    f"{kind}_{source}_{depth}" for kind in ("diffuse", "sss", "bssrdf") for source in ("emitter", "sky") for depth in ("first", "later"))
 EXPOSURE_MANUAL, EXPOSURE_AUTO = 0, 1
 METER_BINS = 512
 
@@ -215,6 +218,11 @@ BVH_SYMBOLS = {
     # the direct sampling of a scene handle (scene, mode) / (scene, out)
     "jade_scene_set_direct_sampling": (C.c_int, [C.c_void_p, C.c_int]),
     "jade_scene_get_direct_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # the passes of a scene handle (scene, on) / (scene, out); a pass's name; the render's passes (scene, out: PASS_COUNT x H x W x 3 floats)
+    "jade_scene_set_passes": (C.c_int, [C.c_void_p, C.c_int]),
+    "jade_scene_get_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "jade_pass_name": (C.c_char_p, [C.c_int]),
+    "jade_render_passes": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 HOST_SYMBOLS = {

@@ -462,6 +462,31 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(mode)))
         return mode.value
 
+    def set_passes(self, on):
+        """jade_scene_set_passes: the next render this handle begins keeps, beside its frame, the same radiance split into the
+        _abi.PASS_COUNT light passes (HIP module only; include/jade_bvh.h, "The passes, stated").  The frame does not change in any bit."""
+        fn = self._hip_only("jade_scene_set_passes")
+        self.backend.check(fn(self._h, 1 if on else 0))
+
+    @property
+    def passes_enabled(self):
+        """jade_scene_get_passes: whether the next render of this handle keeps passes."""
+        fn = self._hip_only("jade_scene_get_passes")
+        on = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def passes(self):
+        """jade_render_passes: the passes of the render in progress over the samples finished so far, a dict from jade_pass_name's names
+        (_abi.PASS_NAMES, in index order) to float32 [H, W, 3] arrays laid out as resolve's rgb; tiles this rank does not own are 0."""
+        fn = self._hip_only("jade_render_passes")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        name = self._hip_only("jade_pass_name")
+        out = np.zeros((_abi.PASS_COUNT, self._params.height, self._params.width, 3), np.float32)
+        self.backend.check(fn(self._h, out.ctypes.data))
+        return {name(i).decode(): out[i] for i in range(_abi.PASS_COUNT)}
+
     def focus_distance(self, params, px, py):
         """jadeh_focus_distance: the depth along the camera's axis of what the centre of pixel (px, py) of the frame `params` shows
         (row 0 = the bottom row) - the focus_distance that puts it in focus.  Traced with this backend's jade_trace_rays; a pixel that

@@ -784,6 +784,19 @@ int jade_debug_shade_mode_env_host(int32_t env_sampling, int32_t lens, int32_t s
   return JADE_OK;
 }
 
+// ... and with jade_scene_set_passes' value (tests/test_passes_cpu.py).
+int jade_debug_shade_mode_passes_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                      int32_t passes, uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0)) return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
 // The rows jade_debug_exit_search runs: every obj_idx[i] names an object and every u[i] lies in [0, 1] (a NaN does not).  exit_search
 // forms its table cell from u x Gn: a row outside that range would read past the object's table - a wild read on a device, which no
 // assertion there could catch - so the rows are refused here, on the host, before anything is launched.  No HIP call.

@@ -173,10 +173,13 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // kernels of a mode with SM_MIS only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
 // ENVMIX: the environment ray by the one-sample mixture of ENVIS's draw and the bounce sampling's (include/jade_rt.h, JADE_ENV_MIXTURE; non-parity;
 // the kernels of a mode with SM_ENVMIX only, with ENVIS).  begin_bounce alone knows it: m travels where ENVIS's ratio does.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
+// PASSES: every addend of a sample's colour is booked in its pass as well (include/jade_bvh.h, "The passes, stated"; the kernels of a mode with
+// SM_PASSES only), in the planes *L (jade_shade.h, PassPlanes).  The colour itself is formed by the statements it always was.
+template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false, bool PASSES = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
-                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr) {
+                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr,
+                                                    const PassPlanes* L = nullptr) {
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -238,6 +241,12 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     }
     uint32_t done = done0;
     uint32_t light = LIGHTS ? hdr0.w : 0u;  // JADE_LIGHTS_ONE: the emitter entry the bounce in flight drew
+    uint32_t pmask = 0u;  // PASSES: the passes the sample in flight has touched
+    PassParts parts;
+    if (PASSES) {
+      pmask = L->mask[p];
+      parts.cls = -1;
+    }
     jvec3 l_final;
     bool finished = false;  // a sample ended: colour in `color`
     jvec3 color = jv(0, 0, 0);
@@ -248,13 +257,15 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
       jvec3 d = dir0;
       if (h < 0) {
         color = sample_hdr(S, d);  // PathTrace.cu:1443-1445
+        if (PASSES) pass_add(*L, p, pmask, PASS_BACKGROUND, color);
         finished = true;
       } else {
         vertex_from_primary(S, c, h, px.hpt(0), d);
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror(S, px, c, &l_final) : consume<ENVIS, LIGHTS, COSINE, MIS>(S, px, c, &l_final, lights, light, mis);
+      int r = LEAN ? consume_mirror<Px, PASSES>(S, px, c, &l_final, &parts) : consume<ENVIS, LIGHTS, COSINE, MIS, PASSES>(S, px, c, &l_final, lights, light, mis, &parts);
+      if (PASSES) pass_fold(*L, p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
       } else if (r == CONSUME_EMITTED) {
@@ -268,6 +279,10 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     // (b) advance until this record has rays in flight or no samples left
     for (;;) {
       if (finished) {
+        if (PASSES) {  // c.le of the sample's camera vertex (0 for a camera ray that met nothing), then the sample's parts to the totals
+          pass_add(*L, p, pmask, PASS_EMISSION, c.le);
+          pass_commit(*L, p, pmask);
+        }
         add_sample(P, rec_m, home_pix, done, c, color);
         finished = false;
         st = ST_IDLE;
@@ -283,7 +298,8 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
           // emitter, the roulette ended the path) has all its results already - nothing is visible: folded in right here (with the
           // reference's sampling there is always the environment ray)
-          const int r = consume<ENVIS, LIGHTS, COSINE, MIS>(S, px, c, &l_final, lights, light, mis);
+          const int r = consume<ENVIS, LIGHTS, COSINE, MIS, PASSES>(S, px, c, &l_final, lights, light, mis, &parts);
+          if (PASSES) pass_fold(*L, p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
           if (r == CONSUME_VERTEX) {
             st = ST_VERTEX;
             continue;
@@ -293,6 +309,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           continue;
         }
         color = jv_add(c.le, jv_add(c.acc, jv_mul(c.thr, l_final)));
+        if (PASSES) pass_add(*L, p, pmask, PASS_EMISSION, jv_mul(c.thr, l_final));  // the path ended on an emitter (or with 0: the mirror's roulette)
         finished = true;
         continue;
       }
@@ -340,6 +357,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     count_secondary(c, st);
     P.hdr[p] = make_uint4(c.rng, done, st | (c.depth << 8) | (c.flags << 16), light);
     if ((st >= ST_DIFFUSE && st <= ST_REFRACT_EXIT) || st == ST_VERTEX) store_ctx(P, p, c);
+    if (PASSES) L->mask[p] = pmask;
   }
   st_out = st;
 }
@@ -459,12 +477,12 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
 // The flags are shade_record's: k_shade passes none, k_shade_mode<M> those of its mode (JADE_MODE_FLAGS).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false>
+template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false, bool PASSES = false>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below, const ShutterConst* H = nullptr, const uint4* lights = nullptr,
-                                               const float2* mis = nullptr) {
+                                               const float2* mis = nullptr, const PassPlanes* L = nullptr) {
   const uint32_t n = n_dev ? *n_dev : n_host;
   // A pass of a batch (prev = the pass before it, on the device): nothing to do once the paths have ended (that pass
   // emitted no ray) or once fewer than stop_below records are active - the point where the host would hand the rest to
@@ -482,7 +500,7 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS, ENVMIX>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis);
+  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS, ENVMIX, PASSES>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis, L);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
@@ -495,14 +513,24 @@ __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(De
 // (launch_full).  The trailing arguments X are those the mode needs, each the last: none for the pinhole and the lens; the shutter's
 // constants (ShutterConst, by value) under SM_SHUTTER; the alias table over the scene's emitter entries (`lights`; read under SM_LIGHTS
 // only) under SM_LIGHTS or SM_COSINE; that and the per-triangle table {m, M} (mis_table, jade_scene_prep.hip) under SM_MIS.
+// Under SM_PASSES the planes (PassPlanes, by value) come FIRST of X, ahead of what the rest of the mode takes (shade_passes_body).
 // JADE_MODE_FLAGS: shade_record's / shade_kernel_body's template flags of mode M.
-#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0, ((M) & SM_ENVMIX) != 0
+#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0, ((M) & SM_ENVMIX) != 0, ((M) & SM_PASSES) != 0
+template <uint32_t M>
+static __device__ __forceinline__ void shade_passes_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
+                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
+                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
+                                               uint32_t stop_below, const PassPlanes& L, const uint4* lights = nullptr, const float2* mis = nullptr) {
+  shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis, &L);
+}
 template <uint32_t M, class... X>
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below, X... x) {
-  if constexpr ((M & SM_SHUTTER) != 0)  // x: the constants; the body takes H, lights, mis
+  if constexpr ((M & SM_PASSES) != 0)  // x: the planes, then lights, or lights and mis
+    shade_passes_body<M>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, x...);
+  else if constexpr ((M & SM_SHUTTER) != 0)  // x: the constants; the body takes H, lights, mis
     shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &x...);
   else if constexpr (sizeof...(X) != 0)  // x: lights, or lights and mis
     shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, x...);
@@ -759,7 +787,8 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean(DevScene S, Path
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 // ... under a thin lens (M = SM_LENS) or a shutter (M = SM_SHUTTER; X: its constants, the last argument): the same kernel with that ray in
-// its camera arm.  The other bits of a mode mean nothing to it: what they change, it hands over (launch_lean).
+// its camera arm; or keeping passes (M = SM_PASSES; X: the planes): it finishes background, emission and mirror-sky samples, so it books
+// them.  The other bits of a mode mean nothing to it: what they change, it hands over (launch_lean).
 template <uint32_t M, class... X>
 __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                                       uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
@@ -770,7 +799,10 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_mode(DevScene S,
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<true, false, (M & SM_LENS) != 0, (M & SM_SHUTTER) != 0>(S, P, R, tile_ids, target_spp, p, c, st, defer, &x...);
+  if constexpr ((M & SM_PASSES) != 0)  // x: the planes
+    shade_record<true, false, false, false, false, false, false, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer, nullptr, nullptr, nullptr, &x...);
+  else
+    shade_record<true, false, (M & SM_LENS) != 0, (M & SM_SHUTTER) != 0>(S, P, R, tile_ids, target_spp, p, c, st, defer, &x...);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 
@@ -1432,6 +1464,18 @@ int jade_scene_get_direct_sampling(jade_scene* s, int* mode) {
   return JADE_OK;
 }
 
+// The passes of the scene handle (include/jade_bvh.h): read by the next jade_render_begin.
+int jade_scene_set_passes(jade_scene* s, int on) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  s->passes = on != 0;
+  return JADE_OK;
+}
+int jade_scene_get_passes(jade_scene* s, int* on) {
+  if (!s || !on) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *on = s->passes ? 1 : 0;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -1525,8 +1569,10 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why))
+                                    s->direct_sampling, &mode, &why, s->passes))
     return jade_fail(rc, why);
+  if ((mode & SM_PASSES) && s->tun.pixel_rotate)
+    return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
   HIP_TRY(hipSetDevice(s->device));
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
@@ -1539,16 +1585,26 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   // Records per pixel: as many paths in flight as JADE_RECORD_MEMORY of the free device memory holds (the
   // partial sums come out of the same share), whatever the image share of this GPU: more records = fewer,
   // wider passes.  288 GB is what makes 530 M paths (112 GB) for a full 1080p frame affordable.
-  const double bytes_per_record = 4.0 * (34 + 5 * nslots) + (s->tun.ray_records ? 6.0 * nslots : 0.0);  // PathState (a float4 per slot, one hit point per record) + queue entry + two list entries + 48-B ray records for an eighth of the slots
+  const double bytes_per_record = 4.0 * (34 + 5 * nslots) + (s->tun.ray_records ? 6.0 * nslots : 0.0) +
+                                  ((mode & SM_PASSES) ? 28.0 * PASS_COUNT + 4.0 : 0.0);  // (passes: a float4 and three floats per pass, one word; jade_shade.h PassPlanes)
+  // PathState (a float4 per slot, one hit point per record) + queue entry + two list entries + 48-B ray records for an eighth of the slots
   // partial sums per pixel: one lane per sample up to JADE_SAMPLE_LANES, never more than the render was announced with
   // (rounded up to a power of two): a 1-spp 4K frame is 100 MB of sums, not 102 GB
   int sum_lanes = JADE_SAMPLE_LANES;
   if (rp->spp > 0)
     for (sum_lanes = 1; sum_lanes < rp->spp && sum_lanes < JADE_SAMPLE_LANES;) sum_lanes <<= 1;
   const double sums_bytes = 12.0 * sum_lanes * (double)npx64;
+  // A render that keeps no passes gives the planes and images of an earlier one back before the memory is measured: they are up to
+  // 424 B per record of that render, and a handle must not hold them for life.  The earlier render ends here - its shade kernels
+  // would write to them - so a begin that fails below leaves no render in progress, as one that fails in setup_state does.
+  if (!(mode & SM_PASSES) && (s->b_pass_cur.p || s->b_pass_tot.p || s->b_pass_mask.p || s->b_pass_out.p)) {
+    s->have_rp = false;
+    passes_release(s);
+  }
   size_t mem_free = 0, mem_total = 0;
   HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-  mem_free += s->b_state.bytes + s->b_sum.bytes + s->b_queue.bytes + s->b_rayq.bytes + s->b_active[0].bytes + s->b_active[1].bytes;  // ours to reuse
+  mem_free += s->b_state.bytes + s->b_sum.bytes + s->b_queue.bytes + s->b_rayq.bytes + s->b_active[0].bytes + s->b_active[1].bytes +
+              s->b_pass_cur.bytes + s->b_pass_tot.bytes + s->b_pass_mask.bytes;  // ours to reuse
   // the caller's bound (jade_render_params.max_state_bytes) replaces the default share of the free memory
   double state_budget = JADE_RECORD_MEMORY * (double)mem_free;
   if (rp->max_state_bytes) state_budget = std::min((double)rp->max_state_bytes, 0.95 * (double)mem_free);
@@ -1601,6 +1657,8 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   if (npix64 == 0) { s->ps.npix = 0; s->ps.npx = 0; s->have_rp = true; return JADE_OK; }
   int rc = setup_state(s, (int)npx64, rpp, nslots, sum_lanes);
   if (rc) return rc;
+  if (mode & SM_PASSES)
+    if ((rc = passes_setup(s, (size_t)npix64))) return rc;
   s->ps.early_exit = rp->walk == JADE_WALK_EARLY_EXIT_CACHED ? 2u : rp->walk == JADE_WALK_EARLY_EXIT ? 1u : 0u;
   s->ps.env_sampling = rp->env_sampling != JADE_ENV_REFERENCE ? 1u : 0u;  // (either mode may leave a bounce without a ray: shade_record)
   memcpy(s->ps.eye, rp->eye, sizeof s->ps.eye);
@@ -1646,9 +1704,13 @@ struct ShadeLaunch {
 // the kernel that runs mode M: its own, but the shutter kernels handle "with a lens" themselves (R.lens_radius)
 static constexpr uint32_t shade_kernel_mode(uint32_t M) { return (M & SM_SHUTTER) ? M & ~(uint32_t)SM_LENS : M; }
 // the trailing arguments the kernels of mode K take (k_shade_mode), formed from the scene and handed to f
+static PassPlanes pass_planes(const jade_scene* s) {
+  return PassPlanes{s->b_pass_cur.as<float4>(), s->b_pass_tot.as<float>(), s->b_pass_mask.as<uint32_t>(), (uint32_t)s->ps.npix};
+}
 template <uint32_t K, class F>
 static void with_mode_args(const jade_scene* s, F&& f) {
-  if constexpr ((K & SM_MIS) != 0) f((const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
+  if constexpr ((K & SM_PASSES) != 0) with_mode_args<K & ~(uint32_t)SM_PASSES>(s, [&](auto... x) { f(pass_planes(s), x...); });  // the planes first
+  else if constexpr ((K & SM_MIS) != 0) f((const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
   else if constexpr ((K & (SM_LIGHTS | SM_COSINE)) != 0) f((const uint4*)s->b_light_alias.as<uint4>());
   else if constexpr ((K & SM_SHUTTER) != 0) f(s->sh);
   else f();
@@ -1667,7 +1729,7 @@ static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, con
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
-  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER);  // (the camera arm is all of a mode the lean kernel carries)
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES);  // (the camera arm and the passes are all of a mode the lean kernel carries)
   auto go = [&](auto kernel, auto... x) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
                        s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), x...);
@@ -1784,7 +1846,8 @@ static int account_pending_trace(PassRun& r) {
 // k_shade_binned have no lens form, so JADE_FUSED, JADE_LIGHT_PACKET, JADE_TAIL and JADE_SHADE_BINNED have no effect there.
 // A render under a shutter (jade_scene_set_shutter) runs the same schedule with the shutter kernels, which handle "with a lens" and "without"
 // themselves.  What the schedule asks is own_origin (jade_runtime.h).
-static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s); }
+// A render that keeps passes (jade_scene_set_passes) runs that schedule as well: k_light and k_light_packet book nothing.
+static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s) && !passes_on(s); }
 
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
 // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.
@@ -2087,7 +2150,7 @@ static int run_passes(jade_scene* s, int64_t from_spp, uint32_t target_spp, bool
   r.shade = shade_launcher(s->mode);
   if (!r.shade) return jade_fail(JADE_ERR_DEVICE, "no shade kernel for the render's mode (internal error: jade_render_begin accepts built modes only)");
   r.batching = s->tun.batching && !s->sort_rays;  // (rocPRIM wants the queue's length on the host)
-  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && parity_shading(s);  // (k_tail shades with the parity code only)
+  r.tail_ok = s->tun.tail && s->tun.tail_max > 0 && parity_shading(s) && !passes_on(s);  // (k_tail shades with the parity code only, and books no pass)
   r.tail_max = std::min<uint32_t>(s->tun.tail_max, (uint32_t)(s->b_queue.bytes / 4 / (size_t)std::max(s->ps.nslots, 1)));
   // (k_tail is launched with one thread per record and is handed the stack spill area, which is sized for k_trace's grid: setup_state)
   r.tail_max = std::min<uint32_t>(r.tail_max, (uint32_t)s->trace_blocks * JADE_TRACE_BLOCK);
@@ -2206,7 +2269,7 @@ int jade_render_query(jade_scene* s, int what, int64_t* value) {
     case JADE_Q_RECORDS_PER_PIXEL: *value = s->ps.npix ? s->ps.rpp : 0; return JADE_OK;
     case JADE_Q_STATE_BYTES:
       *value = s->ps.npix ? (int64_t)(s->b_state.bytes + s->b_sum.bytes + s->b_queue.bytes + s->b_rayq.bytes + s->b_active[0].bytes + s->b_active[1].bytes +
-                                      s->b_wavecnt.bytes + s->b_spill.bytes + s->b_sortkey.bytes + s->b_sortkey2.bytes + s->b_sortpos.bytes + s->b_sortq.bytes + s->b_sorttmp.bytes)
+                                      s->b_wavecnt.bytes + s->b_spill.bytes + s->b_pass_cur.bytes + s->b_pass_tot.bytes + s->b_pass_mask.bytes + s->b_sortkey.bytes + s->b_sortkey2.bytes + s->b_sortpos.bytes + s->b_sortq.bytes + s->b_sorttmp.bytes)
                           : 0;
       return JADE_OK;
     case JADE_Q_SUM_LANES: *value = s->ps.npix ? s->ps.sum_lanes : 0; return JADE_OK;

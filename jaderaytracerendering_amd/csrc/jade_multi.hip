@@ -139,6 +139,11 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
     for (int i = 1; i < ndev; ++i)
       if (scenes[i]->*k.mode != scenes[0]->*k.mode)
         return jade_fail(JADE_ERR_INVALID, std::string("the scenes carry different ") + k.noun + " sampling modes (" + k.setter + "): scene " + std::to_string(i) + " against scene 0");
+  // ... and none keeps passes: only the frame is gathered here (each rank renders its share and calls jade_render_passes)
+  for (int i = 0; i < ndev; ++i)
+    if (scenes[i]->passes)
+      return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) are on for scene " + std::to_string(i) +
+                                                 ": jade_render_multi gathers the frame only - render each share with jade_render_begin / jade_render_step and call jade_render_passes per rank");
   // 1. every device renders its share (one host thread each) and resolves it into a device buffer
   std::vector<int> rcs(ndev, JADE_OK);
   std::vector<std::string> msgs(ndev);

@@ -74,6 +74,11 @@ struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
   ~DevBuf() { if (p) (void)hipFree(p); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+  }
   hipError_t alloc(size_t n) {
     if (p) { (void)hipFree(p); p = nullptr; }
     bytes = 0;
@@ -205,6 +210,7 @@ enum ShadeMode : uint32_t {
   SM_COSINE = 16u,   // jade_scene_set_bounce_sampling = JADE_BOUNCE_COSINE
   SM_MIS = 32u,      // jade_scene_set_direct_sampling = JADE_DIRECT_MIS
   SM_ENVMIX = 64u,   // jade_render_params.env_sampling = JADE_ENV_MIXTURE: raised together with SM_ENVIS, whose record steps it shares
+  SM_PASSES = 128u,  // jade_scene_set_passes: the frame's radiance kept split into the light passes as well (include/jade_bvh.h, "The passes, stated")
 };
 // THE list of the modes that are built, written once: X(m) for each, under each of the three environment samplings.  shade_mode_built (so what
 // jade_render_begin accepts) and shade_launcher (jade_hip.hip: the kernel a render's passes launch) are both made from it, so a mode
@@ -212,7 +218,8 @@ enum ShadeMode : uint32_t {
 #define JADE_SHADE_MODES_BUILT(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
-  JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS)
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS)
 #define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS) X((m) | SM_ENVIS | SM_ENVMIX)
 static inline bool shade_mode_built(uint32_t mode) {
 #define JADE_X(m) if (mode == (m)) return true;
@@ -224,10 +231,12 @@ static inline bool shade_mode_built(uint32_t mode) {
 // is accepted if and only if it is in the list above; the texts say why the others are not, first reason first: one-light sampling's
 // own check, then the cosine bounce's, then what MIS needs.  Pure: no HIP call, no scene (tests/test_shade_modes_cpu.py).
 // env_sampling: JADE_ENV_* (a value jade_render_begin has checked); the mixture is refused exactly where importance is, in the same words.
+// passes: jade_scene_set_passes.  Their kernels are built for the pinhole with all lights; a refusal of theirs comes after the others', which
+// keep their texts whether passes are on or not.
 static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
-                                 std::string* why) {
+                                 std::string* why, bool passes = false) {
   const uint32_t m = (env_sampling == JADE_ENV_IMPORTANCE ? SM_ENVIS : env_sampling == JADE_ENV_MIXTURE ? SM_ENVIS | SM_ENVMIX : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
-                     (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u);
+                     (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u) | (passes ? SM_PASSES : 0u);
   if (shade_mode_built(m)) {
     *mode = m;
     return JADE_OK;
@@ -240,6 +249,10 @@ static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int 
   else if ((m & SM_MIS) && !(m & SM_COSINE))
     *why = "direct sampling: JADE_DIRECT_MIS (jade_scene_set_direct_sampling) weighs the emitter rays against the cosine bounce "
            "and needs JADE_BOUNCE_COSINE (jade_scene_set_bounce_sampling)";
+  else if ((m & SM_PASSES) && (m & (SM_LENS | SM_SHUTTER)))
+    *why = "passes (jade_scene_set_passes) do not run together with " + camera;
+  else if ((m & SM_PASSES) && (m & SM_LIGHTS))
+    *why = "passes (jade_scene_set_passes) do not run together with light sampling JADE_LIGHTS_ONE (jade_scene_set_light_sampling) yet: those kernels are not built";
   else
     *why = "this combination of render modes is not built";
   return JADE_ERR_UNSUPPORTED;
@@ -262,6 +275,7 @@ struct jade_scene {
   int light_sampling = JADE_LIGHTS_ALL;       // jade_scene_set_light_sampling
   int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling
   int direct_sampling = JADE_DIRECT_RAYS;     // jade_scene_set_direct_sampling
+  bool passes = false;                        // jade_scene_set_passes
   // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
   // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
   uint32_t mode = 0;
@@ -316,6 +330,9 @@ struct jade_scene {
   // glare (jade_glare.hip), allocated on first use and kept: the frame in image layout (glared in place), its bytes, and every level
   // of the pyramid in one allocation
   DevBuf b_gl_rgb, b_gl_bgr, b_gl_pyr;
+  // passes (jade_shade.h PassPlanes, jade_passes.hip): the planes of a render with SM_PASSES - cleared by its jade_render_begin - and the
+  // 15 resolved images in the compact tile layout, allocated on first use and kept
+  DevBuf b_pass_cur, b_pass_tot, b_pass_mask, b_pass_out;
   ~jade_scene() {
     if (stream) (void)hipStreamDestroy(stream);
   }
@@ -329,6 +346,8 @@ static inline bool own_origin(const jade_scene* s) { return lens_on(s) || shutte
 static inline bool one_light_on(const jade_scene* s) { return (s->mode & SM_LIGHTS) != 0; }
 // ... the parity shading, the only one k_tail and k_shade_binned carry: no bit at all
 static inline bool parity_shading(const jade_scene* s) { return s->mode == 0; }
+// ... the passes are kept: the list schedule a lens runs - k_light, k_light_packet, k_tail and k_shade_binned have no such form
+static inline bool passes_on(const jade_scene* s) { return (s->mode & SM_PASSES) != 0; }
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
 struct ScenePrep {
@@ -373,6 +392,10 @@ static inline bool light_sampling_fits(int64_t n_emit) { return n_emit >= 0 && n
 // sizes them from the queue's length on the device - and k_resolve over the owned pixels.  The caller asks hipGetLastError.
 JADE_HIDDEN void launch_trace(jade_scene* s, const PathState& P, const uint32_t* queue, QueueCtl* qc, uint32_t* spill, DevCounters* ctr, uint32_t n_rays);
 JADE_HIDDEN int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr, hipStream_t stream);
+// ... and the planes of a render that keeps passes (jade_passes.hip): allocated and cleared by jade_render_begin for npix records
+JADE_HIDDEN int passes_setup(jade_scene* s, size_t npix);
+// ... and given back by the jade_render_begin of a render that keeps none, with the resolved images
+JADE_HIDDEN void passes_release(jade_scene* s);
 
 // What the glare (jade_glare.hip) takes from exposure (jade_expose.hip) rather than copying it: the check of display parameters, the
 // grow-only allocation, flush + k_resolve into b_out_rgb (compact tiles), the meter of n pixels at dev_rgb (tile_ids: compact tiles of

@@ -457,6 +457,76 @@ struct ShadeCtx {
   uint32_t c_cls;  // rays emitted by call site, one byte each: env | indirect << 8 | mirror << 16 | refract << 24 (a record emits once per pass)
 };
 
+// ---- The passes (include/jade_bvh.h, "The passes, stated"; the kernels of a mode with SM_PASSES only, jade_runtime.h): beside its frame a
+// render keeps every addend of a sample's colour in the pass of the statement that formed it.  Nothing of it rides in ShadeCtx or
+// PathState - no other kernel's arguments or registers move: the planes come as an argument of their own, and consume hands the parts
+// of a sampling vertex's l_dir to shade_record through PassParts.
+//   cur[pass][p]  float4   the parts of record p's sample in flight (.w unused); meaningful only where bit `pass` of mask[p] is set, so
+//                          that dropping a sample's parts (CONSUME_ZERO) and starting the next one is mask[p] = 0 and touches no plane
+//   tot[pass][p]  3 floats the finished samples of record p: += cur when a sample ends, in the order the samples end
+//   mask[p]                the passes record p's sample in flight has touched
+// [pass][p]: a wave's neighbouring records touch neighbouring addresses.  Only record p touches its entries: no race, no atomics, the
+// same bits every time.  k_passes_resolve (jade_passes.hip) adds a pixel's records in ascending order.
+enum { PASS_BACKGROUND = 0, PASS_EMISSION = 1, PASS_SPECULAR_SKY = 2, PASS_SAMPLED = 3, PASS_COUNT = 15 };
+struct PassPlanes {
+  float4* cur;
+  float* tot;
+  uint32_t* mask;
+  uint32_t npix;
+};
+// What consume / consume_mirror tell shade_record about the vertex they folded: cls < 0 - nothing to book (l_final is 0);
+// PASS_EMISSION / PASS_SPECULAR_SKY - *l_final is that pass's (e holds it); otherwise 3 + 4 kind + depth, the vertex's emitter pass, its sky
+// pass two above: e and s are the two parts of l_dir, each with the branch's scale, thr0 the throughput before the vertex's push.
+struct PassParts {
+  jvec3 e, s, thr0;
+  int cls;
+  bool pushed;
+};
+static __device__ __forceinline__ void pass_add(const PassPlanes& L, int p, uint32_t& mask, int pass, jvec3 v) {
+  if (!(v.x != 0 || v.y != 0 || v.z != 0)) return;  // adding 0 changes no sum (a NaN is not 0: it is booked)
+  float4* c = L.cur + ((size_t)pass * L.npix + (size_t)p);
+  if ((mask >> pass) & 1u) {
+    const float4 o = *c;
+    v = jv_add(jv(o.x, o.y, o.z), v);
+  }
+  *c = make_float4(v.x, v.y, v.z, 0.0f);
+  mask |= 1u << pass;
+}
+// the sample of record p ended: its parts go to the record's totals
+static __device__ __forceinline__ void pass_commit(const PassPlanes& L, int p, uint32_t& mask) {
+  for (uint32_t m = mask; m; m &= m - 1u) {
+    const size_t i = (size_t)(__ffs(m) - 1) * L.npix + (size_t)p;
+    const float4 v = L.cur[i];
+    float* t = L.tot + 3 * i;
+    t[0] += v.x;
+    t[1] += v.y;
+    t[2] += v.z;
+  }
+  mask = 0u;
+}
+// consume's / consume_mirror's outcome r (CONSUME_*, below) and parts, booked: a pushed vertex with the throughput before the push; the
+// last l_dir of a path that ended with the throughput it ends with - after a 128th push the same vertex again (the reference's double
+// count); CONSUME_ZERO drops what the sample has gathered.
+static __device__ __forceinline__ void pass_fold(const PassPlanes& L, int p, uint32_t& mask, const PassParts& pp, jvec3 thr, bool ended, bool zero) {
+  if (zero) {
+    mask = 0u;
+    return;
+  }
+  if (pp.cls < 0) return;
+  if (pp.cls < PASS_SAMPLED) {
+    if (ended) pass_add(L, p, mask, pp.cls, jv_mul(thr, pp.e));
+    return;
+  }
+  if (pp.pushed) {
+    pass_add(L, p, mask, pp.cls, jv_mul(pp.thr0, pp.e));
+    pass_add(L, p, mask, pp.cls + 2, jv_mul(pp.thr0, pp.s));
+  }
+  if (ended) {
+    pass_add(L, p, mask, pp.cls, jv_mul(thr, pp.e));
+    pass_add(L, p, mask, pp.cls + 2, jv_mul(thr, pp.s));
+  }
+}
+
 // ---- The record steps: how a sample begins, ends and parks.  One text each for shade_record and k_shade_binned (jade_hip.hip); the
 // first-pass kernels (jade_light.h) call vertex_from_primary and store_ctx and keep their own text of the other steps, statement for
 // statement these (their instructions answer any change of their text: see there).  The film point and the pinhole direction of a
@@ -896,8 +966,9 @@ static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c
 enum { CONSUME_VERTEX = 0, CONSUME_END = 1, CONSUME_ZERO = 2, CONSUME_EMITTED = 3 };
 
 // Result of the mirror ray (PathTrace.cu:1383-1398).  Shared by both shading kernels.
-template <class PX>
-static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX& px, ShadeCtx& c, jvec3* l_final) {
+// PASSES: *pp says which pass *l_final belongs to (the sky at the end of a mirror chain), or that there is nothing to book
+template <class PX, bool PASSES = false>
+static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX& px, ShadeCtx& c, jvec3* l_final, PassParts* pp = nullptr) {
   const DevMaterial* ot = shade_tri(S, c.obj).m;
   const int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
   const jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
@@ -909,9 +980,14 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
     c.src = px.hpt(0);
     c.obj = nh;
     *l_final = jv(0, 0, 0);
+    if (PASSES) pp->cls = -1;
     return path_push(c, jv(0, 0, 0), jv_scale(obj_hit_fr, kk)) ? CONSUME_END : CONSUME_VERTEX;
   }
   *l_final = jv_scale(jv_mul(sample_hdr(S, refl), obj_hit_fr), kk);
+  if (PASSES) {
+    pp->cls = PASS_SPECULAR_SKY;
+    pp->e = *l_final;
+  }
   return CONSUME_END;
 }
 
@@ -924,9 +1000,11 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with COSINE only; compiled apart, modes with SM_MIS): at a diffuse or
 // SSS-diffuse vertex an emitter term towards a weighted triangle is multiplied by w_L, and an indirect ray that lands on one adds T_B
 // before the vertex's scale.  `mis`: the per-triangle table {m, M}.  Rays, draws, records and counters are COSINE's.
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false>
+// PASSES: include/jade_bvh.h, "The passes, stated" (compiled apart, modes with SM_PASSES): beside l_dir - formed by the statements it always was -
+// the emitter terms (the loop's and T_B) and the sky term are summed apart and leave in *pp with the branch's scale (PassParts, above).
+template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool PASSES = false>
 static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u,
-                              const float2* mis = nullptr) {
+                              const float2* mis = nullptr, PassParts* pp = nullptr) {
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
   const int nL = LIGHTS ? (nE > 0 ? 1 : 0) : nE;
@@ -938,6 +1016,12 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
   const int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
   const jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
   jvec3 l_dir = jv(0, 0, 0);
+  jvec3 part_e = jv(0, 0, 0), part_s = jv(0, 0, 0);  // PASSES only
+  if (PASSES) {
+    pp->cls = -1;
+    pp->pushed = false;
+    pp->thr0 = c.thr;
+  }
 
   if (c.stage == ST_DIFFUSE) {
     const bool sss = (c.flags & STF_SSS) != 0;
@@ -961,6 +1045,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
           w = jv_scale(w, w_L);
         }
         l_dir = jv_add(l_dir, w);
+        if (PASSES) part_e = jv_add(part_e, w);
       }
     }
     if (ENVIS ? px.hit(nL) == -1 : px.hit(nL) < 0) {  // (-1: traced and nothing hit; -2: no environment ray this bounce - env_sampling only)
@@ -970,6 +1055,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       w = jv_scale(jv_scale(w, 2.0f), PI_F);
       if (ENVIS) w = jv_scale(w, __int_as_float(px.auxi()));  // x (1 / 2 pi) / pdf: the reference's weight is 1 / its own pdf
       l_dir = jv_add(l_dir, w);
+      if (PASSES) part_s = w;
     }
     if (MIS && (c.flags & STF_RR)) {  // the bounce term: the indirect ray found a weighted emitter
       const int bh = px.hit(nL + 1);
@@ -979,12 +1065,19 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
           const ShadeTri t_b = shade_tri(S, bh);
           float w_L, g_B;
           mis_terms(n, t_b.norm, tri_size(&T[bh]), e.x, LIGHTS ? e.y : e.x, jv_sub(px.hpt(nL + 1), c.src), &w_L, &g_B);
-          l_dir = jv_add(l_dir, jv_divs(jv_scale(jv_mul(V3(t_b.m->emissive), f), g_B), RR_F));
+          const jvec3 t_B = jv_divs(jv_scale(jv_mul(V3(t_b.m->emissive), f), g_B), RR_F);
+          l_dir = jv_add(l_dir, t_B);
+          if (PASSES) part_e = jv_add(part_e, t_B);
         }
       }
     }
     l_dir = jv_scale(l_dir, sss ? (float)(k / JADE_SSS_RATE_D) : (float)k);
     *l_final = l_dir;
+    if (PASSES) {
+      pp->cls = PASS_SAMPLED + (sss ? 4 : 0) + (c.depth != 0 ? 1 : 0);
+      pp->e = jv_scale(part_e, sss ? (float)(k / JADE_SSS_RATE_D) : (float)k);
+      pp->s = jv_scale(part_s, sss ? (float)(k / JADE_SSS_RATE_D) : (float)k);
+    }
     if (!(c.flags & STF_RR)) return CONSUME_END;
     int nh = px.hit(nL + 1);
     if (nh >= 0 && nonemissive(shade_tri(S, nh).m)) {
@@ -994,6 +1087,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       c.src = px.hpt(nL + 1);
       c.out = rd;
       c.obj = nh;
+      if (PASSES) pp->pushed = true;
       return path_push(c, l_dir, rate) ? CONSUME_END : CONSUME_VERTEX;
     }
     return CONSUME_END;
@@ -1025,6 +1119,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
         w = jv_scale(w, area_total);
         if (LIGHTS) w = jv_scale(w, light_weight(lights, (uint32_t)nE, light));
         l_dir = jv_add(l_dir, w);
+        if (PASSES) part_e = jv_add(part_e, w);
       }
     }
     if (ENVIS ? px.hit(nL) == -1 : px.hit(nL) < 0) {
@@ -1034,9 +1129,15 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       w = jv_scale(jv_scale(w, COSINE && !ENVIS ? cosine_weight(t_norm, rd) : jade_fabs(jv_dot(t_norm, rd))), 2.0f);
       if (ENVIS) w = jv_scale(w, __int_as_float(px.auxi()));
       l_dir = jv_add(l_dir, w);
+      if (PASSES) part_s = w;
     }
     l_dir = jv_scale(l_dir, (float)(k / (1 - JADE_SSS_RATE_D)));
     *l_final = l_dir;
+    if (PASSES) {
+      pp->cls = PASS_SAMPLED + 8 + (c.depth != 0 ? 1 : 0);
+      pp->e = jv_scale(part_e, (float)(k / (1 - JADE_SSS_RATE_D)));
+      pp->s = jv_scale(part_s, (float)(k / (1 - JADE_SSS_RATE_D)));
+    }
     if (!(c.flags & STF_RR)) return CONSUME_END;
     int nh = px.hit(nL + 1);
     if (nh >= 0 && nonemissive(shade_tri(S, nh).m)) {
@@ -1050,12 +1151,13 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       c.src = px.hpt(nL + 1);
       c.out = rd;
       c.obj = nh;
+      if (PASSES) pp->pushed = true;
       return path_push(c, l_dir, rate) ? CONSUME_END : CONSUME_VERTEX;
     }
     return CONSUME_END;
   }
 
-  if (c.stage == ST_MIRROR) return consume_mirror(S, px, c, l_final);
+  if (c.stage == ST_MIRROR) return consume_mirror<Px, PASSES>(S, px, c, l_final, pp);
 
   if (c.stage == ST_REFRACT_LOOP) {
     // one iteration of the for loop at PathTrace.cu:1201-1234
@@ -1118,6 +1220,10 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
       return path_push(c, jv(0, 0, 0), jv_scale(l_indir_rate, kk)) ? CONSUME_END : CONSUME_VERTEX;
     }
     *l_final = jv_scale(jv_mul(sample_hdr(S, refract_ray), l_indir_rate), kk);
+    if (PASSES) {  // the sky at the end of a glass chain
+      pp->cls = PASS_SPECULAR_SKY;
+      pp->e = *l_final;
+    }
     return CONSUME_END;
   }
 }

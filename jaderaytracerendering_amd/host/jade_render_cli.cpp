@@ -55,6 +55,10 @@ struct Api {
   int (*scene_set_bounce_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --direct
   int (*scene_set_direct_sampling)(jade_scene*, int) = nullptr;
+  // ... and only for --passes
+  int (*scene_set_passes)(jade_scene*, int) = nullptr;
+  int (*render_passes)(jade_scene*, float*) = nullptr;
+  const char* (*pass_name)(int) = nullptr;
 };
 
 static bool load_api(const std::string& path, Api& a, bool adaptive) {
@@ -97,7 +101,7 @@ static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
-          "                   [--bounce uniform|cosine] [--direct rays|mis]\n"
+          "                   [--bounce uniform|cosine] [--direct rays|mis] [--passes PREFIX]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -131,6 +135,9 @@ static void usage() {
           "                    counts of the positive, zero, negative and non-finite pixels and the smallest / largest positive luminance\n"
           "                    (HIP backend only).  With --denoise and / or --glare both read the denoised / glared frame\n"
           "  --denoise: write the frame filtered by the edge-aware denoiser (HIP backend only; include/jade_bvh.h, default parameters)\n"
+          "  --passes PREFIX: keep the frame's radiance split into the 15 light passes as well and write them as PREFIX.<name>.pfm (background,\n"
+          "                   emission, specular_sky, diffuse_emitter_first, ... bssrdf_sky_later; HIP backend only; the frame itself is unchanged;\n"
+          "                   not with --aperture, --shutter or --one-light)\n"
           "  --guides PREFIX: write the denoiser's inputs as PREFIX_albedo.pfm, PREFIX_normal.pfm, PREFIX_depth.pfm, PREFIX_variance.pfm\n"
           "                   (HIP backend only; 4 guide samples)\n"
           "  --adaptive REL: adaptive sampling (HIP backend only): each 16x16 tile stops at the first of N, 2N, 4N, ... samples at which\n"
@@ -165,6 +172,7 @@ int main(int argc, char** argv) {
   bool one_light = false;
   int bounce = -1;  // --bounce: JADE_BOUNCE_*, -1 = not given
   int direct = -1;  // --direct: JADE_DIRECT_*, -1 = not given
+  std::string passes;  // --passes PREFIX
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -209,6 +217,7 @@ int main(int argc, char** argv) {
       else if (v == "cosine") bounce = JADE_BOUNCE_COSINE;
       else { fprintf(stderr, "--bounce takes uniform or cosine, not %s\n", v.c_str()); return 2; }
     }
+    else if (a == "--passes") passes = need("--passes");
     else if (a == "--direct") {
       const std::string v = need("--direct");
       if (v == "rays") direct = JADE_DIRECT_RAYS;
@@ -399,6 +408,15 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (!passes.empty()) {
+    *(void**)(&api.scene_set_passes) = dlsym(api.h, "jade_scene_set_passes");
+    *(void**)(&api.render_passes) = dlsym(api.h, "jade_render_passes");
+    *(void**)(&api.pass_name) = dlsym(api.h, "jade_pass_name");
+    if (!api.scene_set_passes || !api.render_passes || !api.pass_name) {
+      fprintf(stderr, "--passes needs the HIP backend: %s has no jade_scene_set_passes\n", backend.c_str());
+      return 2;
+    }
+  }
   // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
   const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
   if (need_display) {
@@ -453,9 +471,10 @@ int main(int argc, char** argv) {
   if (one_light && api.scene_set_light_sampling(dev, JADE_LIGHTS_ONE) != JADE_OK) { fprintf(stderr, "light sampling: %s\n", api.last_error()); return 1; }
   if (bounce >= 0 && api.scene_set_bounce_sampling(dev, bounce) != JADE_OK) { fprintf(stderr, "bounce sampling: %s\n", api.last_error()); return 1; }
   if (direct >= 0 && api.scene_set_direct_sampling(dev, direct) != JADE_OK) { fprintf(stderr, "direct sampling: %s\n", api.last_error()); return 1; }
+  if (!passes.empty() && api.scene_set_passes(dev, 1) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
                                     (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
-                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "");
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (!passes.empty() ? ", light passes kept" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
@@ -472,6 +491,16 @@ int main(int argc, char** argv) {
   } else {
     printf("Start... %dx%d, %d spp on %s%s\n", rp.width, rp.height, rp.spp, api.backend_name(), lights_note);
     if (api.render(dev, &rp, rgb.data(), bgr.data(), &st) != JADE_OK) { fprintf(stderr, "render: %s\n", api.last_error()); return 1; }
+  }
+  if (!passes.empty()) {
+    const size_t np = (size_t)rp.width * rp.height;
+    std::vector<float> pv((size_t)JADE_PASS_COUNT * 3 * np);
+    if (api.render_passes(dev, pv.data()) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
+    for (int i = 0; i < JADE_PASS_COUNT; ++i) {
+      const std::string path = passes + "." + api.pass_name(i) + ".pfm";
+      if (!write_pfm(path, pv.data() + (size_t)i * 3 * np, rp.width, rp.height)) { fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+      printf("wrote %s\n", path.c_str());
+    }
   }
   if (!guides.empty()) {
     const size_t np = (size_t)rp.width * rp.height;

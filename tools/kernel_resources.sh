@@ -5,7 +5,7 @@ set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose jade_glare; do
+for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose jade_glare jade_passes; do
 /opt/rocm/bin/hipcc "$@" -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -mfma -I"$R/include" -I"$R/jaderaytracerendering_amd/csrc" \
   -c "$R/jaderaytracerendering_amd/csrc/$f.hip" -o "$T/x.o" -Rpass-analysis=kernel-resource-usage 2>&1 |
@@ -26,7 +26,7 @@ for k, v in rows.items():
     s = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILj(\d+)E", k)  # a kernel template over the ShadeMode mask (jade_runtime.h): k_shade_mode<COSINE|MIS>
     if not m and not t and not s:
         continue
-    bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS", "ENVMIX")
+    bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS", "ENVMIX", "PASSES")
     if s:
         name = "%s<%s>" % (s.group(1), "|".join(b for i, b in enumerate(bits) if int(s.group(2)) >> i & 1) or "0")
     else:
