@@ -22,8 +22,8 @@
 //   k_arm / k_shade_lean  list the records with work / shade light samples over all records: the schedules without the
 //                   fused pass (flushes, JADE_FUSED=0)
 //   k_shade_mode<M> / k_shade_lean_mode<M>  k_shade / k_shade_lean of a non-parity render mode M (ShadeMode, jade_runtime.h: environment
-//                   importance or the environment mixture, lens, shutter, one-light, cosine bounces, MIS), one instantiation per built mode; k_shade, k_shade_binned
-//                   and k_shade_lean themselves are mode 0, the parity shading.  shade_launcher picks by the render's mode
+//                   importance or the environment mixture, lens, shutter, one-light, cosine bounces, MIS, passes), one instantiation per built mode; k_shade,
+//                   k_shade_binned and k_shade_lean themselves are mode 0, the parity shading.  shade_launcher picks by the render's mode
 //
 // shade/trace alternate until a shade pass emits nothing (every path record has
 // finished its samples), or until so few are active that the step hands them to the
@@ -158,28 +158,26 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 #ifndef JADE_SHADE_WAVES
 #define JADE_SHADE_WAVES 6 /* k_shade: 75 VGPRs, no spill (7 would spill 16 B).  +4 % over 5 when it runs alone, +-0 behind k_shade_lean */
 #endif
-// One record's shade pass (see the file header).  LEAN = the kernel that only knows camera rays,
-// the sky and pure mirrors: it hands every other record to the full kernel through `defer`
-// (either untouched, or parked at ST_VERTEX with its path state stored).  Same statements either
-// way: the lean paths are the shared helpers consume_mirror / begin_bounce_lean / bounce_mirror.
-// LENS: the camera ray leaves a point of a thin lens (include/jade_bvh.h, "The lens, stated"; non-parity; the kernels of a mode with SM_LENS only)
-// SHUTTER: the camera ray leaves the pose of a time drawn within the exposure, through a lens or not (include/jade_bvh.h, "The shutter,
-// stated"; non-parity; the kernels of a mode with SM_SHUTTER only, which pass their ShutterConst as H)
-// LIGHTS: one emitter per sampling vertex, drawn from the table `lights` (include/jade_bvh.h, "The lights, stated"; non-parity; the
-// kernels of a mode with SM_LIGHTS only).  The entry drawn travels in the fourth word of the record's header, which this function reads and writes anyway.
-// COSINE: the environment and indirect rays of a sampling vertex are drawn with pdf cos / pi about the normal (include/jade_bvh.h, "The bounce,
-// stated"; non-parity; the kernels of a mode with SM_COSINE only).  Nothing of it travels with the record.
-// MIS: the emitter rays and the indirect ray weighed against each other (include/jade_bvh.h, "The direct light, stated"; non-parity; the
-// kernels of a mode with SM_MIS only, with COSINE), from the per-triangle table `mis`.  consume alone reads it.
-// ENVMIX: the environment ray by the one-sample mixture of ENVIS's draw and the bounce sampling's (include/jade_rt.h, JADE_ENV_MIXTURE; non-parity;
-// the kernels of a mode with SM_ENVMIX only, with ENVIS).  begin_bounce alone knows it: m travels where ENVIS's ratio does.
-// PASSES: every addend of a sample's colour is booked in its pass as well (include/jade_bvh.h, "The passes, stated"; the kernels of a mode with
-// SM_PASSES only), in the planes *L (jade_shade.h, PassPlanes).  The colour itself is formed by the statements it always was.
-template <bool LEAN, bool ENVIS = false, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false, bool PASSES = false>  // ENVIS: environment rays by importance (non-parity; the kernels of a mode with SM_ENVIS only)
+// One record's shade pass (see the file header).  LEAN = the kernel that only knows camera rays, the sky and pure mirrors: it hands every other
+// record to the full kernel through `defer` (either untouched, or parked at ST_VERTEX with its path state stored).  Same statements either way: the
+// lean paths are the shared helpers consume_mirror / begin_bounce_lean / bounce_mirror.
+// M: the render's mode (ShadeMode, jade_runtime.h; 0: the parity shading), read by bit through sm; every bit is non-parity, its code in the
+// kernels of a mode that carries it only.  A: what those kernels take for it (ShadeArgs<M>, jade_shade.h).  "stated": include/jade_bvh.h.
+// SM_ENVIS: environment rays by importance.  SM_LENS: the camera ray leaves a point of a thin lens ("The lens, stated")
+// SM_SHUTTER: the camera ray leaves the pose of a time drawn within the exposure, through a lens or not, by the constants *A.H() ("The shutter, stated")
+// SM_LIGHTS: one emitter per sampling vertex, drawn from the table A.lights() ("The lights, stated").  The entry drawn travels in the fourth
+// word of the record's header, which this function reads and writes anyway.
+// SM_COSINE: the environment and indirect rays of a sampling vertex are drawn with pdf cos / pi about the normal ("The bounce, stated").  Nothing of it travels with the record.
+// SM_MIS: the emitter rays and the indirect ray weighed against each other ("The direct light, stated"; with SM_COSINE), from the per-triangle table A.mis().  consume alone reads it.
+// SM_ENVMIX: the environment ray by the one-sample mixture of SM_ENVIS's draw and the bounce sampling's (include/jade_rt.h, JADE_ENV_MIXTURE;
+// with SM_ENVIS).  begin_bounce alone knows it: m travels where SM_ENVIS's ratio does.
+// SM_PASSES: every addend of a sample's colour is booked in its pass as well ("The passes, stated"), in the planes *A.L() (jade_shade.h,
+// PassPlanes).  The colour itself is formed by the statements it always was.
+template <bool LEAN, uint32_t M = 0>
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
-                                                    const ShutterConst* H = nullptr, const uint4* lights = nullptr, const float2* mis = nullptr,
-                                                    const PassPlanes* L = nullptr) {
+                                                    const ShadeArgs<M>& A = SHADE_ARGS_NONE) {
+  constexpr bool ENVIS = sm(M, SM_ENVIS), LENS = sm(M, SM_LENS), SHUTTER = sm(M, SM_SHUTTER), LIGHTS = sm(M, SM_LIGHTS), PASSES = sm(M, SM_PASSES);
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -244,7 +242,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     uint32_t pmask = 0u;  // PASSES: the passes the sample in flight has touched
     PassParts parts;
     if (PASSES) {
-      pmask = L->mask[p];
+      pmask = A.L()->mask[p];
       parts.cls = -1;
     }
     jvec3 l_final;
@@ -257,15 +255,15 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
       jvec3 d = dir0;
       if (h < 0) {
         color = sample_hdr(S, d);  // PathTrace.cu:1443-1445
-        if (PASSES) pass_add(*L, p, pmask, PASS_BACKGROUND, color);
+        if (PASSES) pass_add(*A.L(), p, pmask, PASS_BACKGROUND, color);
         finished = true;
       } else {
         vertex_from_primary(S, c, h, px.hpt(0), d);
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror<Px, PASSES>(S, px, c, &l_final, &parts) : consume<ENVIS, LIGHTS, COSINE, MIS, PASSES>(S, px, c, &l_final, lights, light, mis, &parts);
-      if (PASSES) pass_fold(*L, p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
+      int r = LEAN ? consume_mirror<Px, M>(S, px, c, &l_final, &parts) : consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
+      if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
       } else if (r == CONSUME_EMITTED) {
@@ -280,8 +278,8 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     for (;;) {
       if (finished) {
         if (PASSES) {  // c.le of the sample's camera vertex (0 for a camera ray that met nothing), then the sample's parts to the totals
-          pass_add(*L, p, pmask, PASS_EMISSION, c.le);
-          pass_commit(*L, p, pmask);
+          pass_add(*A.L(), p, pmask, PASS_EMISSION, c.le);
+          pass_commit(*A.L(), p, pmask);
         }
         add_sample(P, rec_m, home_pix, done, c, color);
         finished = false;
@@ -292,14 +290,14 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           defer = true;
           break;
         }
-        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<ENVIS, LIGHTS, COSINE, ENVMIX>(S, px, c, &l_final, lights, &light)) {
+        if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<M>(S, px, c, &l_final, A.lights(), &light)) {
           st = c.stage;
           if (!ENVIS || c.n_emit_rays != 0) break;
           // env_sampling only: a bounce that emitted NO ray (the drawn sky direction lay on the wrong side, no shadow ray faced its
           // emitter, the roulette ended the path) has all its results already - nothing is visible: folded in right here (with the
           // reference's sampling there is always the environment ray)
-          const int r = consume<ENVIS, LIGHTS, COSINE, MIS, PASSES>(S, px, c, &l_final, lights, light, mis, &parts);
-          if (PASSES) pass_fold(*L, p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
+          const int r = consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
+          if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
           if (r == CONSUME_VERTEX) {
             st = ST_VERTEX;
             continue;
@@ -309,7 +307,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           continue;
         }
         color = jv_add(c.le, jv_add(c.acc, jv_mul(c.thr, l_final)));
-        if (PASSES) pass_add(*L, p, pmask, PASS_EMISSION, jv_mul(c.thr, l_final));  // the path ended on an emitter (or with 0: the mirror's roulette)
+        if (PASSES) pass_add(*A.L(), p, pmask, PASS_EMISSION, jv_mul(c.thr, l_final));  // the path ended on an emitter (or with 0: the mirror's roulette)
         finished = true;
         continue;
       }
@@ -331,7 +329,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           }
           const float ut = jade_rand(&c.rng);
           jvec3 org;
-          shutter_ray(R.cam, R.eye, *H, R.lens_radius, P.lens_k, left_offset, up_offset, u3, u4, ut, &org, &dir);
+          shutter_ray(R.cam, R.eye, *A.H(), R.lens_radius, P.lens_k, left_offset, up_offset, u3, u4, ut, &org, &dir);
           px.set_origin(org, -1);
         } else if (LENS) {
           // two more draws before any draw of the path, and an origin of the ray's own: stored with "no source triangle" (-1), which
@@ -357,7 +355,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     count_secondary(c, st);
     P.hdr[p] = make_uint4(c.rng, done, st | (c.depth << 8) | (c.flags << 16), light);
     if ((st >= ST_DIFFUSE && st <= ST_REFRACT_EXIT) || st == ST_VERTEX) store_ctx(P, p, c);
-    if (PASSES) L->mask[p] = pmask;
+    if (PASSES) A.L()->mask[p] = pmask;
   }
   st_out = st;
 }
@@ -476,13 +474,12 @@ static __device__ __forceinline__ void shade_tail(const PathState& P, int p, uin
 
 // The full shade kernel: one thread per entry of `list` (the active list, or — after k_shade_lean —
 // the records that kernel handed over, whose count lives on the device: n_dev).  75 VGPRs, 6 waves/SIMD (JADE_SHADE_WAVES).
-// The flags are shade_record's: k_shade passes none, k_shade_mode<M> those of its mode (JADE_MODE_FLAGS).
-template <bool ENVIS, bool LENS = false, bool SHUTTER = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool ENVMIX = false, bool PASSES = false>
+// M and A are shade_record's: k_shade is mode 0 and passes nothing, k_shade_mode<M> its mode and the argument it was launched with.
+template <uint32_t M = 0>
 static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const ShutterConst* H = nullptr, const uint4* lights = nullptr,
-                                               const float2* mis = nullptr, const PassPlanes* L = nullptr) {
+                                               uint32_t stop_below, const ShadeArgs<M>& A = SHADE_ARGS_NONE) {
   const uint32_t n = n_dev ? *n_dev : n_host;
   // A pass of a batch (prev = the pass before it, on the device): nothing to do once the paths have ended (that pass
   // emitted no ray) or once fewer than stop_below records are active - the point where the host would hand the rest to
@@ -500,42 +497,26 @@ static __device__ __forceinline__ void shade_kernel_body(const DevScene& S, cons
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  shade_record<false, ENVIS, LENS, SHUTTER, LIGHTS, COSINE, MIS, ENVMIX, PASSES>(S, P, R, tile_ids, target_spp, p, c, st, defer, H, lights, mis, L);
+  shade_record<false, M>(S, P, R, tile_ids, target_spp, p, c, st, defer, A);
   shade_tail<false, JADE_SHADE_NW>(P, p, st, c, false, active_out, nullptr, queue, qc, ctr);
 }
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
                                                uint32_t stop_below) {
-  shade_kernel_body<false>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
+  shade_kernel_body(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
 }
-// ... and every non-parity mode (ShadeMode, jade_runtime.h): one kernel per built mode M, instantiated where it is launched
-// (launch_full).  The trailing arguments X are those the mode needs, each the last: none for the pinhole and the lens; the shutter's
-// constants (ShutterConst, by value) under SM_SHUTTER; the alias table over the scene's emitter entries (`lights`; read under SM_LIGHTS
-// only) under SM_LIGHTS or SM_COSINE; that and the per-triangle table {m, M} (mis_table, jade_scene_prep.hip) under SM_MIS.
-// Under SM_PASSES the planes (PassPlanes, by value) come FIRST of X, ahead of what the rest of the mode takes (shade_passes_body).
-// JADE_MODE_FLAGS: shade_record's / shade_kernel_body's template flags of mode M.
-#define JADE_MODE_FLAGS(M) ((M) & SM_ENVIS) != 0, ((M) & SM_LENS) != 0, ((M) & SM_SHUTTER) != 0, ((M) & SM_LIGHTS) != 0, ((M) & SM_COSINE) != 0, ((M) & SM_MIS) != 0, ((M) & SM_ENVMIX) != 0, ((M) & SM_PASSES) != 0
-template <uint32_t M>
-static __device__ __forceinline__ void shade_passes_body(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
-                                               uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
-                                               uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, const PassPlanes& L, const uint4* lights = nullptr, const float2* mis = nullptr) {
-  shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, lights, mis, &L);
-}
-template <uint32_t M, class... X>
+// ... and every non-parity mode (ShadeMode): one kernel per built mode M, instantiated where it is launched (launch_full).  k_shade's arguments, then what
+// mode M takes beyond them in one piece, T = ShadeArgs<M> (jade_shade.h; mode_args fills it) - but under SM_MIS its members apart, T = (ArgPlanes,) ArgLights,
+// ArgMis: a struct of two pointers reaches a kernel by reference and is loaded in the first block, which costs COSINE|MIS(|PASSES) exec masks kept in VGPR lanes.
+template <uint32_t M, class... T>
 __global__ __launch_bounds__(JADE_SHADE_BLOCK, JADE_SHADE_WAVES) void k_shade_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                uint32_t target_spp, const uint32_t* list, uint32_t n_host, const uint32_t* n_dev,
                                                uint32_t* active_out, uint32_t* queue, QueueCtl* qc, DevCounters* ctr, const QueueCtl* prev,
-                                               uint32_t stop_below, X... x) {
-  if constexpr ((M & SM_PASSES) != 0)  // x: the planes, then lights, or lights and mis
-    shade_passes_body<M>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, x...);
-  else if constexpr ((M & SM_SHUTTER) != 0)  // x: the constants; the body takes H, lights, mis
-    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, &x...);
-  else if constexpr (sizeof...(X) != 0)  // x: lights, or lights and mis
-    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, nullptr, x...);
-  else
-    shade_kernel_body<JADE_MODE_FLAGS(M)>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below);
+                                               uint32_t stop_below, T... a) {
+  ShadeArgs<M> A;
+  ((static_cast<T&>(A) = a), ...);
+  shade_kernel_body<M>(S, P, R, tile_ids, target_spp, list, n_host, n_dev, active_out, queue, qc, ctr, prev, stop_below, A);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -786,23 +767,20 @@ __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean(DevScene S, Path
   shade_record<true>(S, P, R, tile_ids, target_spp, p, c, st, defer);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
-// ... under a thin lens (M = SM_LENS) or a shutter (M = SM_SHUTTER; X: its constants, the last argument): the same kernel with that ray in
-// its camera arm; or keeping passes (M = SM_PASSES; X: the planes): it finishes background, emission and mirror-sky samples, so it books
-// them.  The other bits of a mode mean nothing to it: what they change, it hands over (launch_lean).
-template <uint32_t M, class... X>
+// ... under a thin lens (M = SM_LENS) or a shutter (M = SM_SHUTTER): the same kernel with that ray in its camera arm; or keeping passes
+// (M = SM_PASSES): it finishes background, emission and mirror-sky samples, so it books them.  A: the constants, the planes (ShadeArgs<M>).
+// The other bits of a mode mean nothing to it: what they change, it hands over (launch_lean).
+template <uint32_t M>
 __global__ __launch_bounds__(JADE_LEAN_BLOCK) void k_shade_lean_mode(DevScene S, PathState P, RenderConst R, const int32_t* tile_ids,
                                                                       uint32_t target_spp, uint32_t* heavy_out, uint32_t* queue,
-                                                                      QueueCtl* qc, DevCounters* ctr, X... x) {
+                                                                      QueueCtl* qc, DevCounters* ctr, ShadeArgs<M> A) {
   const int p = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   ShadeCtx c;
   c.n_emit_rays = 0;
   c.c_primary = c.c_shadow = c.c_shaded = c.c_samples = c.c_cls = 0;
   uint32_t st;
   bool defer;
-  if constexpr ((M & SM_PASSES) != 0)  // x: the planes
-    shade_record<true, false, false, false, false, false, false, false, true>(S, P, R, tile_ids, target_spp, p, c, st, defer, nullptr, nullptr, nullptr, &x...);
-  else
-    shade_record<true, false, (M & SM_LENS) != 0, (M & SM_SHUTTER) != 0>(S, P, R, tile_ids, target_spp, p, c, st, defer, &x...);
+  shade_record<true, M>(S, P, R, tile_ids, target_spp, p, c, st, defer, A);
   shade_tail<true, JADE_LEAN_BLOCK / 64>(P, p, st, c, defer, nullptr, heavy_out, queue, qc, ctr);
 }
 
@@ -1703,39 +1681,39 @@ struct ShadeLaunch {
 };
 // the kernel that runs mode M: its own, but the shutter kernels handle "with a lens" themselves (R.lens_radius)
 static constexpr uint32_t shade_kernel_mode(uint32_t M) { return (M & SM_SHUTTER) ? M & ~(uint32_t)SM_LENS : M; }
-// the trailing arguments the kernels of mode K take (k_shade_mode), formed from the scene and handed to f
-static PassPlanes pass_planes(const jade_scene* s) {
-  return PassPlanes{s->b_pass_cur.as<float4>(), s->b_pass_tot.as<float>(), s->b_pass_mask.as<uint32_t>(), (uint32_t)s->ps.npix};
-}
-template <uint32_t K, class F>
-static void with_mode_args(const jade_scene* s, F&& f) {
-  if constexpr ((K & SM_PASSES) != 0) with_mode_args<K & ~(uint32_t)SM_PASSES>(s, [&](auto... x) { f(pass_planes(s), x...); });  // the planes first
-  else if constexpr ((K & SM_MIS) != 0) f((const uint4*)s->b_light_alias.as<uint4>(), (const float2*)s->b_mis.as<float2>());
-  else if constexpr ((K & (SM_LIGHTS | SM_COSINE)) != 0) f((const uint4*)s->b_light_alias.as<uint4>());
-  else if constexpr ((K & SM_SHUTTER) != 0) f(s->sh);
-  else f();
+// the argument the kernels of mode K take beyond the parity kernels' (ShadeArgs, jade_shade.h), filled from the scene: a line per member
+template <uint32_t K>
+static ShadeArgs<K> mode_args(const jade_scene* s) {
+  ShadeArgs<K> a{};
+  if constexpr (sm(K, SM_PASSES)) a.planes = PassPlanes{s->b_pass_cur.as<float4>(), s->b_pass_tot.as<float>(), s->b_pass_mask.as<uint32_t>(), (uint32_t)s->ps.npix};
+  if constexpr (sm(K, SM_SHUTTER)) a.shutter = s->sh;
+  if constexpr ((K & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0) a.light_table = s->b_light_alias.as<uint4>();
+  if constexpr (sm(K, SM_MIS)) a.mis_table = s->b_mis.as<float2>();
+  return a;
 }
 template <uint32_t M>
 static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, const uint32_t* list, uint32_t n, const uint32_t* n_dev, uint32_t* next,
                         QueueCtl* ctl, const QueueCtl* prev, uint32_t stop_below) {
   constexpr uint32_t K = shade_kernel_mode(M);
-  auto go = [&](auto kernel, auto... x) {
+  auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(JADE_SHADE_BLOCK), 0, s->stream, s->dev, s->ps, s->rc, s->b_tiles.as<int32_t>(), target_spp, list, n, n_dev,
-                       next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, x...);
+                       next, s->b_queue.as<uint32_t>(), ctl, s->b_ctr.as<DevCounters>(), prev, stop_below, a...);
   };
   // the parity mode: k_shade, or - JADE_SHADE_BINNED - with the records dealt by branch through LDS (k_shade_binned), the one mode with that form
   if constexpr (K == 0) go(s->tun.shade_binned ? k_shade_binned : k_shade);
-  else with_mode_args<K>(s, [&](auto... x) { go(k_shade_mode<K, decltype(x)...>, x...); });
+  else if constexpr (!sm(K, SM_MIS)) go(k_shade_mode<K, ShadeArgs<K>>, mode_args<K>(s));
+  else if constexpr (const ShadeArgs<K> a = mode_args<K>(s); sm(K, SM_PASSES)) go(k_shade_mode<K, ArgPlanes, ArgLights, ArgMis>, (ArgPlanes)a, (ArgLights)a, (ArgMis)a);
+  else go(k_shade_mode<K, ArgLights, ArgMis>, (ArgLights)a, (ArgMis)a);  // SM_MIS: the bundle's members apart (k_shade_mode)
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
   constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES);  // (the camera arm and the passes are all of a mode the lean kernel carries)
-  auto go = [&](auto kernel, auto... x) {
+  auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
-                       s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), x...);
+                       s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), a...);
   };
   if constexpr (K == 0) go(k_shade_lean);
-  else with_mode_args<K>(s, [&](auto... x) { go(k_shade_lean_mode<K, decltype(x)...>, x...); });
+  else go(k_shade_lean_mode<K>, mode_args<K>(s));
 }
 // The lookup: a row per mode of JADE_SHADE_MODES_BUILT (jade_runtime.h) - the list jade_render_begin accepts from - and no other.
 static const ShadeLaunch* shade_launcher(uint32_t mode) {

@@ -212,6 +212,9 @@ enum ShadeMode : uint32_t {
   SM_ENVMIX = 64u,   // jade_render_params.env_sampling = JADE_ENV_MIXTURE: raised together with SM_ENVIS, whose record steps it shares
   SM_PASSES = 128u,  // jade_scene_set_passes: the frame's radiance kept split into the light passes as well (include/jade_bvh.h, "The passes, stated")
 };
+// How the device code reads a mode: whether mask M carries bit b.  The shade kernels and every function they are made of (jade_shade.h,
+// jade_hip.hip) are templates over the one mask and ask by name - sm(M, SM_COSINE) - so no flag has a position to be wrong in.
+static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 0; }
 // THE list of the modes that are built, written once: X(m) for each, under each of the three environment samplings.  shade_mode_built (so what
 // jade_render_begin accepts) and shade_launcher (jade_hip.hip: the kernel a render's passes launch) are both made from it, so a mode
 // cannot be accepted without a kernel or have a kernel that is never reached.  Adding a render mode: DESIGN.md 3.14.

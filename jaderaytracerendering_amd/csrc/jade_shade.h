@@ -15,7 +15,9 @@
 // is accumulated forward here (acc += thr * dir; thr *= rate), which differs
 // from the unwind only by fp32 rounding of the radiance (never of a decision).
 #pragma once
+#include <type_traits>
 #include "jade_device.h"
+#include "jade_runtime.h"  // ShadeMode and sm: the functions below that differ by render mode are templates over the mode's mask
 
 static __device__ __forceinline__ int mirror_index(int i, int n) {
   int m = i % (2 * n);
@@ -474,6 +476,22 @@ struct PassPlanes {
   uint32_t* mask;
   uint32_t npix;
 };
+// What the kernels of mode M take beyond the parity kernels' arguments, in one piece: a by-value kernel argument, the last (k_shade_mode, which says why SM_MIS is
+// the exception; k_shade_lean_mode; mode_args, jade_hip.hip).  A member is there only in the modes that take it - in the others its base is the empty one, which takes
+// no space and whose accessor answers nullptr, so shade_record is one text - in this order: the pass planes under SM_PASSES; the shutter's constants under SM_SHUTTER; the
+// alias table over the scene's emitter entries under SM_LIGHTS, SM_COSINE or SM_MIS (read under SM_LIGHTS only); the per-triangle table {m, M} under SM_MIS.
+struct ArgPlanes { PassPlanes planes; __device__ const PassPlanes* L() const { return &planes; } };
+struct NoPlanes { __device__ const PassPlanes* L() const { return nullptr; } };
+struct ArgShutter { ShutterConst shutter; __device__ const ShutterConst* H() const { return &shutter; } };
+struct NoShutter { __device__ const ShutterConst* H() const { return nullptr; } };
+struct ArgLights { const uint4* light_table; __device__ const uint4* lights() const { return light_table; } };
+struct NoLights { __device__ const uint4* lights() const { return nullptr; } };
+struct ArgMis { const float2* mis_table; __device__ const float2* mis() const { return mis_table; } };
+struct NoMis { __device__ const float2* mis() const { return nullptr; } };
+template <uint32_t M>
+struct ShadeArgs : std::conditional_t<sm(M, SM_PASSES), ArgPlanes, NoPlanes>, std::conditional_t<sm(M, SM_SHUTTER), ArgShutter, NoShutter>,
+                   std::conditional_t<(M & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0, ArgLights, NoLights>, std::conditional_t<sm(M, SM_MIS), ArgMis, NoMis> {};
+static __device__ const ShadeArgs<0> SHADE_ARGS_NONE{};  // what mode 0 passes, by name: with a temporary on the caller's stack k_shade_lean and k_tail come out in another order
 // What consume / consume_mirror tell shade_record about the vertex they folded: cls < 0 - nothing to book (l_final is 0);
 // PASS_EMISSION / PASS_SPECULAR_SKY - *l_final is that pass's (e holds it); otherwise 3 + 4 kind + depth, the vertex's emitter pass, its sky
 // pass two above: e and s are the two parts of l_dir, each with the branch's scale, thr0 the throughput before the vertex's push.
@@ -752,17 +770,18 @@ static __device__ __forceinline__ int exit_search(const DevScene& S, int obj_idx
 
 // The branch itself: its draws, its rays (written through px), stage / flags / n_emit_rays.  Returns false if the path ended at
 // this vertex (*l_final holds the last l_dir).  `type` is uniform over the waves k_shade runs it for.
-// ENVIS: jade_render_params.env_sampling = JADE_ENV_IMPORTANCE (compiled apart: the parity kernels carry none of its code)
-// LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h; compiled apart likewise, modes with SM_LIGHTS): ONE entry of S.emit, drawn from `lights`, in
-// slot 0; nL = the shadow slots of the record's layout, so the environment ray sits in slot nL and the indirect ray in slot nL + 1.
-// *light = the entry drawn: it travels with the record (the fourth word of PathState.hdr, shade_record) to consume.
-// COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"; compiled apart likewise, modes with SM_COSINE): the environment ray - unless
-// ENVIS draws it - and the indirect ray come from cosine_dir_rng in place of sphere_dir and its flip, on the same two draws.
-// ENVMIX: JADE_ENV_MIXTURE (include/jade_rt.h; with ENVIS only, compiled apart likewise, modes with SM_ENVMIX): where ENVIS calls env_sample
-// this calls env_mix_sample - five draws, the sky technique or the bounce sampling's own direction - and m travels where ratio does.
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool ENVMIX = false>
+// M: the render's mode (ShadeMode, jade_runtime.h); each bit's code is compiled apart: the parity kernels (M = 0) carry none.  SM_ENVIS: JADE_ENV_IMPORTANCE (include/jade_rt.h)
+// SM_LIGHTS: JADE_LIGHTS_ONE (include/jade_bvh.h): ONE entry of S.emit, drawn from `lights`, in slot 0; nL = the shadow slots of the
+// record's layout, so the environment ray sits in slot nL and the indirect ray in slot nL + 1.  *light = the entry drawn: it travels with
+// the record (the fourth word of PathState.hdr, shade_record) to consume.
+// SM_COSINE: JADE_BOUNCE_COSINE (include/jade_bvh.h, "The bounce, stated"): the environment ray - unless SM_ENVIS draws it - and the
+// indirect ray come from cosine_dir_rng in place of sphere_dir and its flip, on the same two draws.
+// SM_ENVMIX: JADE_ENV_MIXTURE (include/jade_rt.h; with SM_ENVIS only): where SM_ENVIS calls env_sample this calls env_mix_sample - five
+// draws, the sky technique or the bounce sampling's own direction - and m travels where ratio does.
+template <uint32_t M = 0>
 static __device__ __forceinline__ bool bounce_branch(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final,
                                                      const uint4* lights = nullptr, uint32_t* light = nullptr) {
+  constexpr bool ENVIS = sm(M, SM_ENVIS), LIGHTS = sm(M, SM_LIGHTS), COSINE = sm(M, SM_COSINE), ENVMIX = sm(M, SM_ENVMIX);
   const jade_triangle* T = S.tris;  // vertices only
   const ShadeTri ots = shade_tri(S, c.obj);
   const DevMaterial* ot = ots.m;
@@ -954,21 +973,22 @@ diffuse_like:
 
 // Sample the bounce at the current vertex and emit its rays.  Returns false
 // if the path ended at this vertex (l_final holds the last l_dir).
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool ENVMIX = false>
+template <uint32_t M = 0>
 static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr,
                                     uint32_t* light = nullptr) {
   const int type = bounce_classify(S, c, l_final);
   if (type == BT_END) return false;
-  return bounce_branch<ENVIS, LIGHTS, COSINE, ENVMIX>(type, S, px, c, l_final, lights, light);
+  return bounce_branch<M>(type, S, px, c, l_final, lights, light);
 }
 
 // Outcome of folding the pending rays' results into the path.
 enum { CONSUME_VERTEX = 0, CONSUME_END = 1, CONSUME_ZERO = 2, CONSUME_EMITTED = 3 };
 
 // Result of the mirror ray (PathTrace.cu:1383-1398).  Shared by both shading kernels.
-// PASSES: *pp says which pass *l_final belongs to (the sky at the end of a mirror chain), or that there is nothing to book
-template <class PX, bool PASSES = false>
+// M: the render's mode; SM_PASSES: *pp says which pass *l_final belongs to (the sky at the end of a mirror chain), or that there is nothing to book
+template <class PX, uint32_t M = 0>
 static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX& px, ShadeCtx& c, jvec3* l_final, PassParts* pp = nullptr) {
+  constexpr bool PASSES = sm(M, SM_PASSES);
   const DevMaterial* ot = shade_tri(S, c.obj).m;
   const int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
   const jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
@@ -995,16 +1015,17 @@ static __device__ __forceinline__ int consume_mirror(const DevScene& S, const PX
 // moved to a new vertex (c.obj/src/out updated); CONSUME_END: it ended with
 // *l_final; CONSUME_ZERO: pathTracing returned 0 (:1231); CONSUME_EMITTED: the
 // refraction loop issued its next ray.
-// LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight (bounce_branch)
-// COSINE: where a ray came from cosine_dir_rng, the reference's |dot(normal, direction)| is cosine_weight - four places, nothing else
-// MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with COSINE only; compiled apart, modes with SM_MIS): at a diffuse or
-// SSS-diffuse vertex an emitter term towards a weighted triangle is multiplied by w_L, and an indirect ray that lands on one adds T_B
-// before the vertex's scale.  `mis`: the per-triangle table {m, M}.  Rays, draws, records and counters are COSINE's.
-// PASSES: include/jade_bvh.h, "The passes, stated" (compiled apart, modes with SM_PASSES): beside l_dir - formed by the statements it always was -
-// the emitter terms (the loop's and T_B) and the sky term are summed apart and leave in *pp with the branch's scale (PassParts, above).
-template <bool ENVIS = false, bool LIGHTS = false, bool COSINE = false, bool MIS = false, bool PASSES = false>
+// M: the render's mode, as bounce_branch reads it.  SM_LIGHTS: slot 0 holds the shadow ray towards entry `light`, whose term is multiplied by light_weight
+// SM_COSINE: where a ray came from cosine_dir_rng, the reference's |dot(normal, direction)| is cosine_weight - four places, nothing else
+// SM_MIS: JADE_DIRECT_MIS (include/jade_bvh.h, "The direct light, stated"; with SM_COSINE only): at a diffuse or SSS-diffuse vertex an
+// emitter term towards a weighted triangle is multiplied by w_L, and an indirect ray that lands on one adds T_B before the vertex's
+// scale.  `mis`: the per-triangle table {m, M}.  Rays, draws, records and counters are SM_COSINE's.
+// SM_PASSES: include/jade_bvh.h, "The passes, stated": beside l_dir - formed by the statements it always was - the emitter terms (the
+// loop's and T_B) and the sky term are summed apart and leave in *pp with the branch's scale (PassParts, above).
+template <uint32_t M = 0>
 static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights = nullptr, uint32_t light = 0u,
                               const float2* mis = nullptr, PassParts* pp = nullptr) {
+  constexpr bool ENVIS = sm(M, SM_ENVIS), LIGHTS = sm(M, SM_LIGHTS), COSINE = sm(M, SM_COSINE), MIS = sm(M, SM_MIS), PASSES = sm(M, SM_PASSES);
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
   const int nL = LIGHTS ? (nE > 0 ? 1 : 0) : nE;
@@ -1157,7 +1178,7 @@ static __device__ int consume(const DevScene& S, const Px& px, ShadeCtx& c, jvec
     return CONSUME_END;
   }
 
-  if (c.stage == ST_MIRROR) return consume_mirror<Px, PASSES>(S, px, c, l_final, pp);
+  if (c.stage == ST_MIRROR) return consume_mirror<Px, M>(S, px, c, l_final, pp);
 
   if (c.stage == ST_REFRACT_LOOP) {
     // one iteration of the for loop at PathTrace.cu:1201-1234

@@ -268,7 +268,7 @@ def test_both_modes_estimate_the_same_integral(hip):
 
 
 # ------------------------------------------------------------------------ 7. the render against the float64 statement, sample for sample --
-# How bounce_branch<.., LIGHTS> and consume<.., LIGHTS> USE a draw: jade_spec's one-light arm (include/jade_bvh.h's text in float64; checked
+# How bounce_branch and consume USE a draw under SM_LIGHTS: jade_spec's one-light arm (include/jade_bvh.h's text in float64; checked
 # without a GPU in tests/test_lights_spec_cpu.py) against 12 x 12 frames at 1 spp, by spec_scenes.compare and its bar, unchanged: a
 # sample agrees when every channel is within 1e-4 relative (floor 1e-3), at most 2 % may disagree, bssrdf-coplanar samples are left out
 # (here: at most 5 % of a case).
