@@ -713,6 +713,67 @@ int jade_scene_get_passes(jade_scene* scene, int* on);
 const char* jade_pass_name(int pass);
 int jade_render_passes(jade_scene* scene, float* out);
 
+/* ---- Branch sampling ----
+ *
+ * Non-parity.  At a vertex the reference tosses coins: select_reflex_refract < 0.5 takes a material's refraction arm (glass, or the jade's
+ * sub-surface arms) and weighs it 1 / 0.5, a second select < JADE_SSS_RATE_D takes the SSS-diffuse arm of a JADE_SUB_SURFACE material,
+ * and the mirror's roulette goes on with probability JADE_RR_RATE.  A branch taken with probability q and weighted 1 / q whose value is T
+ * adds T^2 q (1 - q) of per-sample variance from the coin alone.  Every pixel draws its samples with known indices 0 .. spp - 1, so under
+ * JADE_BRANCH_STRATIFIED the coins of a path's first two vertices are shared out among a pixel's samples instead of tossed: exactly half
+ * of any aligned 2^k samples take each arm, and of those the stated share goes on.  The probabilities, the weights and every other
+ * statement are unchanged, each sample's number is uniform, so the estimator is unbiased; it costs no ray, no record word and no draw.
+ * jade_scene_set_branch_sampling is a property of the scene handle, read by the next jade_render_begin; a render in progress keeps the
+ * mode it began with.  JADE_BRANCH_RANDOM (0, the default) is today's render in every kernel, bit and counter.  An unknown value is
+ * JADE_ERR_INVALID.
+ *
+ * ---- The branch draws, stated ----
+ * tests/branch_spec.py is this text in numpy.  All integers are uint32_t and arithmetic wraps.
+ *
+ * The two sequences.  A(i) is the bit reversal of i (van der Corput in base 2 as 32-bit fixed point; __brev on the device).  B(i) is
+ * Sobol's second dimension: r = 0; v = 0x80000000; then for every bit of i, lowest first: if (i & 1) r ^= v; i >>= 1; v ^= v >> 1; B = r.
+ * Together they are a (0, 2)-sequence in base 2: every aligned block of 2^k indices puts one point into each elementary interval of
+ * area 2^-k, and a digital shift (an XOR of each dimension with a constant) keeps that.
+ *
+ * The shift of a pixel's render.  D(x, y, frame, d): s = jade_rng_seed(x, y, frame) ^ (d == 0 ? 0x68E31DA4u : 0xB5297A4Du); jade_wang is
+ * applied to s twice, and D is the second result.  frame is jade_render_params.frame, NOT frame + sidx.
+ *
+ * The stratified number of sample sidx of pixel (x, y) at a vertex of depth d - the path's push count when the vertex is shaded, 0 at
+ * the camera ray's vertex -, for d < 2:
+ *   U = (d == 0 ? A(sidx) : B(sidx)) ^ D(x, y, frame, d)
+ * Vertices of depth 2 and more use the stream's draws.  su(W) = (float)W * 2.3283064365386963e-10f, jade_rand's own conversion.
+ *
+ * What U replaces, at a vertex of depth 0 or 1:
+ *   the first select_reflex_refract is su(U);
+ *   on a material with refract_mode != JADE_NO_REFRACT that one bit is spent, and every later decision at that vertex uses V = U << 1:
+ *     the second select of a JADE_SUB_SURFACE material, su(V) < (float)JADE_SSS_RATE_D, and the mirror branch's rr_result = su(V);
+ *   on a material without a refraction arm the select decides nothing, and the mirror branch's rr_result = su(U).
+ * Every comparison stays the float comparison it is.  The jade_rand calls stay where they are and their values are discarded, so every
+ * other draw of the path keeps its position in the sample's stream.  Nothing else is stratified: the diffuse branches' roulette for the
+ * indirect ray, the refraction loop's reflex_refract_select, the area draw, all directions and the film jitter are the stream's.
+ *
+ * A dimension is used at most once per path: a vertex is shaded only as the camera ray's (depth 0) or after the fold of a bounce's rays
+ * moved the path on, and every such move is a push, which counts the depth up; so no two vertices of a path share a depth, and the one
+ * vertex of depth 0 and the one of depth 1 read different dimensions.  (Two vertices sharing a number would bias the estimator.)
+ *
+ * The schedule is the one a lens runs: no fused first pass, no k_tail, JADE_SHADE_BINNED ignored.  Rays per kind, path lengths and the
+ * record layout are the random mode's in distribution; no counter is the same number.  Results do not depend on steps, tile partitions,
+ * the walk or the records per pixel.  The denoiser, exposure, glare and passes (under the reference estimator) run on top unchanged.
+ *
+ * JADE_PIXEL_ROTATE stays legal: a record's samples then move between pixels, each pixel's numbers are still uniform and the render
+ * unbiased, but a pixel no longer sees an aligned run of indices, so the stratification is no longer guaranteed.
+ * jade_render_adaptive runs on top, and a stopped tile is that tile of the uniform stratified render at its count.  Its error estimate
+ * assumes independent samples; a pixel's stratified samples are negatively correlated, so under this mode the estimate is an
+ * over-estimate of the error and tiles stop later than they could.  A limitation, not a defect.
+ *
+ * jade_render_begin refuses JADE_BRANCH_STRATIFIED with JADE_ERR_UNSUPPORTED together with a lens, a shutter or JADE_LIGHTS_ONE, and
+ * together with passes under anything but the reference estimator (those kernels are not built yet), after the other modes' own
+ * refusals.  The oracle backend knows the parity estimator only and has no such entry.  jade_render_multi compares the setting between
+ * its scenes as it compares the others. */
+#define JADE_BRANCH_RANDOM 0
+#define JADE_BRANCH_STRATIFIED 1
+int jade_scene_set_branch_sampling(jade_scene* scene, int mode);
+int jade_scene_get_branch_sampling(jade_scene* scene, int* mode);
+
 #ifdef __cplusplus
 }
 #endif

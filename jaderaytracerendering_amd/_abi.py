@@ -19,6 +19,7 @@ ENV_REFERENCE, ENV_IMPORTANCE, ENV_MIXTURE = 0, 1, 2
 LIGHTS_ALL, LIGHTS_ONE = 0, 1  # include/jade_bvh.h, jade_scene_set_light_sampling
 BOUNCE_UNIFORM, BOUNCE_COSINE = 0, 1  # include/jade_bvh.h, jade_scene_set_bounce_sampling
 DIRECT_RAYS, DIRECT_MIS = 0, 1  # include/jade_bvh.h, jade_scene_set_direct_sampling
+BRANCH_RANDOM, BRANCH_STRATIFIED = 0, 1  # include/jade_bvh.h, jade_scene_set_branch_sampling
 PASS_COUNT = 15  # include/jade_bvh.h, jade_render_passes; jade_pass_name gives these
 PASS_NAMES = ("background", "emission", "specular_sky") + tuple(
     f"{kind}_{source}_{depth}" for kind in ("diffuse", "sss", "bssrdf") for source in ("emitter", "sky") for depth in ("first", "later"))
@@ -223,6 +224,9 @@ BVH_SYMBOLS = {
     "jade_scene_get_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "jade_pass_name": (C.c_char_p, [C.c_int]),
     "jade_render_passes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # the branch sampling of a scene handle (scene, mode) / (scene, out)
+    "jade_scene_set_branch_sampling": (C.c_int, [C.c_void_p, C.c_int]),
+    "jade_scene_get_branch_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {

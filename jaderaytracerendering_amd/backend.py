@@ -462,6 +462,22 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(mode)))
         return mode.value
 
+    def set_branch_sampling(self, mode):
+        """jade_scene_set_branch_sampling: _abi.BRANCH_RANDOM (the default: every vertex tosses its coins - mirror or refraction arm, SSS or
+        BSSRDF, the mirror's roulette - from the sample's stream, as the reference does) or _abi.BRANCH_STRATIFIED (at a path's first two
+        vertices a pixel's samples share the arms out; HIP module only; non-parity: include/jade_bvh.h, "The branch draws, stated").  Taken by
+        the next render this handle begins.  JadeError(JADE_ERR_INVALID) leaves the previous mode in place."""
+        fn = self._hip_only("jade_scene_set_branch_sampling")
+        self.backend.check(fn(self._h, int(mode)))
+
+    @property
+    def branch_sampling(self):
+        """jade_scene_get_branch_sampling: the mode the next render of this handle takes."""
+        fn = self._hip_only("jade_scene_get_branch_sampling")
+        mode = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(mode)))
+        return mode.value
+
     def set_passes(self, on):
         """jade_scene_set_passes: the next render this handle begins keeps, beside its frame, the same radiance split into the
         _abi.PASS_COUNT light passes (HIP module only; include/jade_bvh.h, "The passes, stated").  The frame does not change in any bit."""

@@ -312,6 +312,19 @@ __global__ void k_debug_shutter_ray_rng(RenderConst R, ShutterConst H, float len
   rng_out[i] = rng;
 }
 
+// row i: the stratified number U (branch_number, jade_shade.h) of sample rows[5 i + 3] of pixel (rows[5 i], rows[5 i + 1]) in a render with
+// frame rows[5 i + 2], at a vertex of depth rows[5 i + 4] (0 or 1)
+#define BRANCH_ROW 5
+static __host__ __device__ __forceinline__ uint32_t debug_branch_row(const uint32_t* row) {
+  RenderConst R{};
+  R.frame = row[2];
+  return branch_number(R, (int)row[0], (int)row[1], row[3], row[4]);
+}
+__global__ void k_debug_branch_number(int n, const uint32_t* rows, uint32_t* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) out[i] = debug_branch_row(rows + (size_t)BRANCH_ROW * i);
+}
+
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
 
 static hipError_t upload0(DevBuf& b, const void* src, size_t elems) {  // on the null stream: these entry points have no scene
@@ -794,6 +807,49 @@ int jade_debug_shade_mode_passes_host(int32_t env_sampling, int32_t lens, int32_
   std::string why;
   if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0)) return jade_fail(rc, why);
   *mode = m;
+  return JADE_OK;
+}
+
+// ... and with jade_scene_set_branch_sampling's value (JADE_BRANCH_*; any other is JADE_ERR_INVALID, as the setter answers it; tests/test_branch_cpu.py).
+int jade_debug_shade_mode_branch_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                      int32_t passes, int32_t branch_sampling, uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (branch_sampling != JADE_BRANCH_RANDOM && branch_sampling != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0,
+                                    branch_sampling == JADE_BRANCH_STRATIFIED))
+    return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
+// The stratified number of the branch draws (branch_number, jade_shade.h; include/jade_bvh.h "The branch draws, stated") on n rows of
+// BRANCH_ROW uint32 (x, y, frame, sidx, depth; depth 0 or 1): out[i] = U.  The HOST build of the function, no HIP call (tests/test_branch_cpu.py).
+int jade_debug_branch_number_host(int32_t n, const uint32_t* rows, uint32_t* out) {
+  if (n < 0 || !rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  for (int32_t i = 0; i < n; ++i) {
+    if (rows[(size_t)BRANCH_ROW * i + 4] > 1u) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": depth is 0 or 1");
+    out[i] = debug_branch_row(rows + (size_t)BRANCH_ROW * i);
+  }
+  return JADE_OK;
+}
+// ... and the same rows on the device (tests/test_gpu_branch.py).
+int jade_debug_branch_number(int device_id, int32_t n, const uint32_t* rows, uint32_t* out) {
+  if (!rows || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / BRANCH_ROW) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  for (int32_t i = 0; i < n; ++i)
+    if (rows[(size_t)BRANCH_ROW * i + 4] > 1u) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": depth is 0 or 1");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  DevBuf bi, bo;
+  HIP_TRY(upload0(bi, rows, BRANCH_ROW * N));
+  HIP_TRY(bo.alloc(4 * N));
+  hipLaunchKernelGGL(k_debug_branch_number, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bi.as<uint32_t>(), bo.as<uint32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out, bo.p, 4 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 

@@ -173,11 +173,13 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // with SM_ENVIS).  begin_bounce alone knows it: m travels where SM_ENVIS's ratio does.
 // SM_PASSES: every addend of a sample's colour is booked in its pass as well ("The passes, stated"), in the planes *A.L() (jade_shade.h,
 // PassPlanes).  The colour itself is formed by the statements it always was.
+// SM_BRANCH: the draws that choose the arm at a vertex of depth 0 or 1 are read off the sample's stratified number U ("The branch draws, stated";
+// branch_number, jade_shade.h), formed here from the record's `done` and home pixel.  Nothing of it travels with the record.
 template <bool LEAN, uint32_t M = 0>
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
                                                     const ShadeArgs<M>& A = SHADE_ARGS_NONE) {
-  constexpr bool ENVIS = sm(M, SM_ENVIS), LENS = sm(M, SM_LENS), SHUTTER = sm(M, SM_SHUTTER), LIGHTS = sm(M, SM_LIGHTS), PASSES = sm(M, SM_PASSES);
+  constexpr bool ENVIS = sm(M, SM_ENVIS), LENS = sm(M, SM_LENS), SHUTTER = sm(M, SM_SHUTTER), LIGHTS = sm(M, SM_LIGHTS), PASSES = sm(M, SM_PASSES), BRANCH = sm(M, SM_BRANCH);
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -290,6 +292,30 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
           defer = true;
           break;
         }
+        // A mode with SM_BRANCH: the statement below and what follows it, with the vertex's stratified number - U of the sample in flight, which the
+        // record's `done` names.  A second text, since a flag or a helper woven into the one below moves the registers of every other kernel.
+        if constexpr (BRANCH) {
+          uint32_t bu = 0u;
+          if (c.depth < 2u) {
+            const NextSample cs = next_sample_mh(P, rec_m, (uint32_t)home_pix, done);
+            int bx, by;
+            (void)pixel_xy_t(R, cs.pixel == home_pix ? tid0 : tile_ids[cs.pixel >> 8], cs.pixel, &bx, &by);
+            bu = branch_number(R, bx, by, cs.sidx, c.depth);
+          }
+          if (LEAN ? begin_bounce_lean_branch(S, px, c, &l_final, bu) : begin_bounce_branch<M>(S, px, c, &l_final, A.lights(), &light, bu)) {
+            st = c.stage;
+            if (!ENVIS || c.n_emit_rays != 0) break;
+            const int r = consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
+            if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
+            if (r == CONSUME_VERTEX) {
+              st = ST_VERTEX;
+              continue;
+            }
+            color = r == CONSUME_END ? jv_add(c.le, jv_add(c.acc, jv_mul(c.thr, l_final))) : c.le;
+            finished = true;
+            continue;
+          }
+        } else
         if (LEAN ? begin_bounce_lean(S, px, c, &l_final) : begin_bounce<M>(S, px, c, &l_final, A.lights(), &light)) {
           st = c.stage;
           if (!ENVIS || c.n_emit_rays != 0) break;
@@ -1454,6 +1480,19 @@ int jade_scene_get_passes(jade_scene* s, int* on) {
   return JADE_OK;
 }
 
+// The branch sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
+int jade_scene_set_branch_sampling(jade_scene* s, int mode) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (mode != JADE_BRANCH_RANDOM && mode != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
+  s->branch_sampling = mode;
+  return JADE_OK;
+}
+int jade_scene_get_branch_sampling(jade_scene* s, int* mode) {
+  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *mode = s->branch_sampling;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -1547,7 +1586,7 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why, s->passes))
+                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED))
     return jade_fail(rc, why);
   if ((mode & SM_PASSES) && s->tun.pixel_rotate)
     return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
@@ -1707,7 +1746,7 @@ static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, con
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
-  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES);  // (the camera arm and the passes are all of a mode the lean kernel carries)
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH);  // (the camera arm, the passes and the mirror's shared-out roulette are all of a mode the lean kernel carries)
   auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
                        s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), a...);
@@ -1825,7 +1864,9 @@ static int account_pending_trace(PassRun& r) {
 // A render under a shutter (jade_scene_set_shutter) runs the same schedule with the shutter kernels, which handle "with a lens" and "without"
 // themselves.  What the schedule asks is own_origin (jade_runtime.h).
 // A render that keeps passes (jade_scene_set_passes) runs that schedule as well: k_light and k_light_packet book nothing.
-static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s) && !passes_on(s); }
+// A render with the branch draws shared out (jade_scene_set_branch_sampling) runs it too: k_light and k_light_packet shade the camera vertex with the
+// stream's draws.
+static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s) && !passes_on(s) && !branch_on(s); }
 
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
 // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.

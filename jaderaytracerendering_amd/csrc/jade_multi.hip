@@ -130,11 +130,12 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->shutter_set != scenes[0]->shutter_set || memcmp(&scenes[i]->shutter, &scenes[0]->shutter, sizeof(jade_shutter_params)) != 0)
       return jade_fail(JADE_ERR_INVALID, "the scenes carry different shutters (jade_scene_set_shutter): scene " + std::to_string(i) + " against scene 0");
-  // ... and with the same light, bounce and direct sampling
+  // ... and with the same light, bounce, direct and branch sampling
   static const struct { int jade_scene::*mode; const char* setter; const char* noun; } kSampling[] = {
       {&jade_scene::light_sampling, "jade_scene_set_light_sampling", "light"},
       {&jade_scene::bounce_sampling, "jade_scene_set_bounce_sampling", "bounce"},
-      {&jade_scene::direct_sampling, "jade_scene_set_direct_sampling", "direct"}};
+      {&jade_scene::direct_sampling, "jade_scene_set_direct_sampling", "direct"},
+      {&jade_scene::branch_sampling, "jade_scene_set_branch_sampling", "branch"}};
   for (const auto& k : kSampling)
     for (int i = 1; i < ndev; ++i)
       if (scenes[i]->*k.mode != scenes[0]->*k.mode)

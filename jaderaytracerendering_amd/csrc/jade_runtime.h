@@ -211,6 +211,7 @@ enum ShadeMode : uint32_t {
   SM_MIS = 32u,      // jade_scene_set_direct_sampling = JADE_DIRECT_MIS
   SM_ENVMIX = 64u,   // jade_render_params.env_sampling = JADE_ENV_MIXTURE: raised together with SM_ENVIS, whose record steps it shares
   SM_PASSES = 128u,  // jade_scene_set_passes: the frame's radiance kept split into the light passes as well (include/jade_bvh.h, "The passes, stated")
+  SM_BRANCH = 256u,  // jade_scene_set_branch_sampling = JADE_BRANCH_STRATIFIED: the branch draws of a path's first two vertices shared out (include/jade_bvh.h, "The branch draws, stated")
 };
 // How the device code reads a mode: whether mask M carries bit b.  The shade kernels and every function they are made of (jade_shade.h,
 // jade_hip.hip) are templates over the one mask and ask by name - sm(M, SM_COSINE) - so no flag has a position to be wrong in.
@@ -222,7 +223,11 @@ static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 
   JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS) \
-  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS)
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS) JADE_SHADE_MODES_BRANCH(X)
+// ... its rows under SM_BRANCH: the pinhole with all lights - the reference estimator, the cosine bounce, MIS - and the passes on the reference estimator
+#define JADE_SHADE_MODES_BRANCH(X) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE | SM_MIS) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_PASSES)
 #define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS) X((m) | SM_ENVIS | SM_ENVMIX)
 static inline bool shade_mode_built(uint32_t mode) {
 #define JADE_X(m) if (mode == (m)) return true;
@@ -236,10 +241,13 @@ static inline bool shade_mode_built(uint32_t mode) {
 // env_sampling: JADE_ENV_* (a value jade_render_begin has checked); the mixture is refused exactly where importance is, in the same words.
 // passes: jade_scene_set_passes.  Their kernels are built for the pinhole with all lights; a refusal of theirs comes after the others', which
 // keep their texts whether passes are on or not.
+// branch: jade_scene_set_branch_sampling = JADE_BRANCH_STRATIFIED.  Its kernels are built for the pinhole with all lights as well, and for the passes on
+// the reference estimator; its refusals come last, after everybody else's, whose texts stay.
 static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
-                                 std::string* why, bool passes = false) {
+                                 std::string* why, bool passes = false, bool branch = false) {
   const uint32_t m = (env_sampling == JADE_ENV_IMPORTANCE ? SM_ENVIS : env_sampling == JADE_ENV_MIXTURE ? SM_ENVIS | SM_ENVMIX : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
-                     (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u) | (passes ? SM_PASSES : 0u);
+                     (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u) | (passes ? SM_PASSES : 0u) |
+                     (branch ? SM_BRANCH : 0u);
   if (shade_mode_built(m)) {
     *mode = m;
     return JADE_OK;
@@ -256,6 +264,14 @@ static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int 
     *why = "passes (jade_scene_set_passes) do not run together with " + camera;
   else if ((m & SM_PASSES) && (m & SM_LIGHTS))
     *why = "passes (jade_scene_set_passes) do not run together with light sampling JADE_LIGHTS_ONE (jade_scene_set_light_sampling) yet: those kernels are not built";
+  else if ((m & SM_BRANCH) && (m & (SM_LENS | SM_SHUTTER)))
+    *why = "branch sampling: JADE_BRANCH_STRATIFIED (jade_scene_set_branch_sampling) does not run together with " + camera;
+  else if ((m & SM_BRANCH) && (m & SM_LIGHTS))
+    *why = "branch sampling: JADE_BRANCH_STRATIFIED (jade_scene_set_branch_sampling) does not run together with light sampling JADE_LIGHTS_ONE "
+           "(jade_scene_set_light_sampling) yet: those kernels are not built";
+  else if ((m & SM_BRANCH) && (m & SM_PASSES))
+    *why = "branch sampling: JADE_BRANCH_STRATIFIED (jade_scene_set_branch_sampling) keeps passes (jade_scene_set_passes) under the reference estimator only "
+           "(JADE_BOUNCE_UNIFORM, JADE_DIRECT_RAYS) yet: those kernels are not built";
   else
     *why = "this combination of render modes is not built";
   return JADE_ERR_UNSUPPORTED;
@@ -279,6 +295,7 @@ struct jade_scene {
   int bounce_sampling = JADE_BOUNCE_UNIFORM;  // jade_scene_set_bounce_sampling
   int direct_sampling = JADE_DIRECT_RAYS;     // jade_scene_set_direct_sampling
   bool passes = false;                        // jade_scene_set_passes
+  int branch_sampling = JADE_BRANCH_RANDOM;   // jade_scene_set_branch_sampling
   // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
   // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
   uint32_t mode = 0;
@@ -351,6 +368,8 @@ static inline bool one_light_on(const jade_scene* s) { return (s->mode & SM_LIGH
 static inline bool parity_shading(const jade_scene* s) { return s->mode == 0; }
 // ... the passes are kept: the list schedule a lens runs - k_light, k_light_packet, k_tail and k_shade_binned have no such form
 static inline bool passes_on(const jade_scene* s) { return (s->mode & SM_PASSES) != 0; }
+// ... the branch draws are shared out: the list schedule again - k_light and k_light_packet shade a camera vertex's mirror with the stream's draw
+static inline bool branch_on(const jade_scene* s) { return (s->mode & SM_BRANCH) != 0; }
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
 struct ScenePrep {

@@ -981,6 +981,119 @@ static __device__ bool begin_bounce(const DevScene& S, const Px& px, ShadeCtx& c
   return bounce_branch<M>(type, S, px, c, l_final, lights, light);
 }
 
+// ---- The branch draws (include/jade_bvh.h, "The branch draws, stated"; the kernels of a mode with SM_BRANCH only, jade_runtime.h): at a
+// vertex of depth 0 or 1 the draws that choose the arm - the select, the SSS select, the mirror's roulette - are read off one stratified
+// number U of the sample instead of the stream, whose draws are made all the same and dropped.  Nothing of it rides in ShadeCtx or
+// PathState: shade_record forms U from the record's `done` where it shades such a vertex.  The head of the bounce and its mirror arm
+// stand here a second time, with U: the functions above are every other kernel's, k_light's and k_tail's among them, and one more
+// argument or template parameter on them moves those kernels' registers (profiles/branch_kernel_resources.txt).
+// A: the bit reversal (van der Corput, base 2); B: Sobol's second dimension; D: the pixel's shift for dimension d.  Host and device.
+static __host__ __device__ __forceinline__ uint32_t branch_A(uint32_t i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __brev(i);
+#else
+  i = (i >> 16) | (i << 16);
+  i = ((i & 0xff00ff00u) >> 8) | ((i & 0x00ff00ffu) << 8);
+  i = ((i & 0xf0f0f0f0u) >> 4) | ((i & 0x0f0f0f0fu) << 4);
+  i = ((i & 0xccccccccu) >> 2) | ((i & 0x33333333u) << 2);
+  return ((i & 0xaaaaaaaau) >> 1) | ((i & 0x55555555u) << 1);
+#endif
+}
+static __host__ __device__ __forceinline__ uint32_t branch_B(uint32_t i) {
+  uint32_t r = 0u;
+  for (uint32_t v = 0x80000000u; i; i >>= 1, v ^= v >> 1)
+    if (i & 1u) r ^= v;
+  return r;
+}
+static __host__ __device__ __forceinline__ uint32_t branch_D(uint32_t x, uint32_t y, uint32_t frame, uint32_t d) {
+  uint32_t s = jade_rng_seed(x, y, frame) ^ (d == 0u ? 0x68E31DA4u : 0xB5297A4Du);
+  (void)jade_wang(&s);
+  return jade_wang(&s);
+}
+// U of sample sidx of pixel (x, y) at a vertex of depth 0 or 1 (R.frame: the render's, not the sample's)
+static __host__ __device__ __forceinline__ uint32_t branch_number(const RenderConst& R, int x, int y, uint32_t sidx, uint32_t depth) {
+  return (depth == 0u ? branch_A(sidx) : branch_B(sidx)) ^ branch_D((uint32_t)x, (uint32_t)y, R.frame, depth);
+}
+// su: jade_rand's own conversion
+static __host__ __device__ __forceinline__ float branch_su(uint32_t w) { return (float)w * 2.3283064365386963e-10f; }
+
+// bounce_mirror with the roulette's number: u is U - or U << 1 on a material with a refraction arm, whose select spent a bit - at a
+// vertex of depth < 2 (strat), the stream's draw otherwise; the stream's draw is made either way
+template <class PX>
+static __device__ __forceinline__ bool bounce_mirror_branch(PX& px, ShadeCtx& c, const DevMaterial* ot, jvec3 obj_emissive, jvec3 n, jvec3* l_final,
+                                                            bool strat, uint32_t u) {
+  const float RR_F = (float)JADE_RR_RATE_D;
+  jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
+  int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
+  if (obj_emissive.x > 1.5e-4f || obj_emissive.y > 1.5e-4f || obj_emissive.x > 1.5e-4f) {
+    *l_final = jv_scale(jv_mul(obj_emissive, obj_hit_fr), (float)k);
+    return false;
+  }
+  float rr_result = jade_rand(&c.rng);
+  if (strat) rr_result = branch_su(k == 2 ? u << 1 : u);
+  if (!(rr_result < RR_F)) return false;
+  jvec3 refl = jv_sub(jv_scale(n, 2 * jv_dot(c.out, n)), c.out);
+  px.set_origin(c.src, c.obj);
+  px.set_dir(0, refl);
+  px.set_hit(0, -1);
+  c.n_emit_rays++;
+  c.stage = ST_MIRROR;
+  c.flags = 0;
+  return true;
+}
+// begin_bounce_lean with U
+template <class PX>
+static __device__ bool begin_bounce_lean_branch(const DevScene& S, PX& px, ShadeCtx& c, jvec3* l_final, uint32_t u) {
+  const ShadeTri ots = shade_tri(S, c.obj);
+  const DevMaterial* ot = ots.m;
+  c.c_shaded += 1;
+  jvec3 obj_emissive = V3(ot->emissive);
+  if (obj_emissive.x > 1.4e-5f || obj_emissive.y > 1.4e-5f || obj_emissive.z > 1.4e-5f) {
+    *l_final = obj_emissive;
+    return false;
+  }
+  *l_final = jv(0, 0, 0);
+  (void)jade_rand(&c.rng);  // select_reflex_refract: made and dropped
+  return bounce_mirror_branch(px, c, ot, obj_emissive, ots.norm, l_final, c.depth < 2u, u);
+}
+// begin_bounce with U: bounce_classify's statements with the two selects read off U and U << 1 at a vertex of depth < 2, then the mirror
+// arm above or - every other arm draws from the stream alone - bounce_branch as it is
+template <uint32_t M>
+static __device__ bool begin_bounce_branch(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const uint4* lights, uint32_t* light, uint32_t u) {
+  const ShadeTri ots = shade_tri(S, c.obj);
+  const DevMaterial* ot = ots.m;
+  c.c_shaded += 1;
+  jvec3 obj_emissive = V3(ot->emissive);
+  if (obj_emissive.x > 1.4e-5f || obj_emissive.y > 1.4e-5f || obj_emissive.z > 1.4e-5f) {
+    *l_final = obj_emissive;  // PathTrace.cu:916-920
+    return false;
+  }
+  *l_final = jv(0, 0, 0);
+  const bool strat = c.depth < 2u;
+  int type = BT_MIRROR;
+  float select_reflex_refract = jade_rand(&c.rng);
+  if (strat) select_reflex_refract = branch_su(u);
+  if (select_reflex_refract < 0.5f && ot->refract_mode != JADE_NO_REFRACT) {
+    type = BT_REFRACT;
+    if (ot->refract_mode == JADE_SUB_SURFACE) {
+      select_reflex_refract = jade_rand(&c.rng);
+      if (strat) select_reflex_refract = branch_su(u << 1);
+      type = BT_BSSRDF;
+      if (select_reflex_refract < (float)JADE_SSS_RATE_D) {
+        c.stage = ST_DIFFUSE;
+        c.flags = STF_SSS;
+        type = BT_DIFFUSE;
+      }
+    }
+  } else if (ot->reflex_mode == JADE_DIFFUSE) {
+    c.stage = ST_DIFFUSE;
+    c.flags = 0;
+    type = BT_DIFFUSE;
+  }
+  if (type == BT_MIRROR) return bounce_mirror_branch(px, c, ot, obj_emissive, ots.norm, l_final, strat, u);
+  return bounce_branch<M>(type, S, px, c, l_final, lights, light);
+}
+
 // Outcome of folding the pending rays' results into the path.
 enum { CONSUME_VERTEX = 0, CONSUME_END = 1, CONSUME_ZERO = 2, CONSUME_EMITTED = 3 };
 

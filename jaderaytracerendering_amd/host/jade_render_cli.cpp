@@ -55,6 +55,8 @@ struct Api {
   int (*scene_set_bounce_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --direct
   int (*scene_set_direct_sampling)(jade_scene*, int) = nullptr;
+  // ... and only for --branch
+  int (*scene_set_branch_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --passes
   int (*scene_set_passes)(jade_scene*, int) = nullptr;
   int (*render_passes)(jade_scene*, float*) = nullptr;
@@ -101,7 +103,7 @@ static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
-          "                   [--bounce uniform|cosine] [--direct rays|mis] [--passes PREFIX]\n"
+          "                   [--bounce uniform|cosine] [--direct rays|mis] [--branch random|stratified] [--passes PREFIX]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -125,6 +127,10 @@ static void usage() {
           "  --direct mis: the emitter rays and the indirect ray of every diffuse vertex are weighed against each other (multiple importance\n"
           "                sampling, balance heuristic), which bounds the bright samples next to a lamp (HIP backend only; NOT the reference's\n"
           "                samples; include/jade_bvh.h).  Needs --bounce cosine and implies nothing.  rays is the default\n"
+          "  --branch stratified: at a path's first two vertices a pixel's samples share out the coins that choose the arm - mirror or sub-surface,\n"
+          "                       SSS or BSSRDF, the mirror's roulette - instead of tossing them (HIP backend only; NOT the reference's samples;\n"
+          "                       include/jade_bvh.h).  Same rays per sample on average; not together with --aperture, --shutter-* or --one-light.\n"
+          "                       random is the default\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -172,6 +178,7 @@ int main(int argc, char** argv) {
   bool one_light = false;
   int bounce = -1;  // --bounce: JADE_BOUNCE_*, -1 = not given
   int direct = -1;  // --direct: JADE_DIRECT_*, -1 = not given
+  int branch = -1;  // --branch: JADE_BRANCH_*, -1 = not given
   std::string passes;  // --passes PREFIX
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
@@ -216,6 +223,12 @@ int main(int argc, char** argv) {
       if (v == "uniform") bounce = JADE_BOUNCE_UNIFORM;
       else if (v == "cosine") bounce = JADE_BOUNCE_COSINE;
       else { fprintf(stderr, "--bounce takes uniform or cosine, not %s\n", v.c_str()); return 2; }
+    }
+    else if (a == "--branch") {
+      const std::string v = need("--branch");
+      if (v == "random") branch = JADE_BRANCH_RANDOM;
+      else if (v == "stratified") branch = JADE_BRANCH_STRATIFIED;
+      else { fprintf(stderr, "--branch takes random or stratified, not %s\n", v.c_str()); return 2; }
     }
     else if (a == "--passes") passes = need("--passes");
     else if (a == "--direct") {
@@ -408,6 +421,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (branch >= 0) {
+    *(void**)(&api.scene_set_branch_sampling) = dlsym(api.h, "jade_scene_set_branch_sampling");
+    if (!api.scene_set_branch_sampling) {
+      fprintf(stderr, "--branch needs the HIP backend: %s has no jade_scene_set_branch_sampling\n", backend.c_str());
+      return 2;
+    }
+  }
   if (!passes.empty()) {
     *(void**)(&api.scene_set_passes) = dlsym(api.h, "jade_scene_set_passes");
     *(void**)(&api.render_passes) = dlsym(api.h, "jade_render_passes");
@@ -471,10 +491,11 @@ int main(int argc, char** argv) {
   if (one_light && api.scene_set_light_sampling(dev, JADE_LIGHTS_ONE) != JADE_OK) { fprintf(stderr, "light sampling: %s\n", api.last_error()); return 1; }
   if (bounce >= 0 && api.scene_set_bounce_sampling(dev, bounce) != JADE_OK) { fprintf(stderr, "bounce sampling: %s\n", api.last_error()); return 1; }
   if (direct >= 0 && api.scene_set_direct_sampling(dev, direct) != JADE_OK) { fprintf(stderr, "direct sampling: %s\n", api.last_error()); return 1; }
+  if (branch >= 0 && api.scene_set_branch_sampling(dev, branch) != JADE_OK) { fprintf(stderr, "branch sampling: %s\n", api.last_error()); return 1; }
   if (!passes.empty() && api.scene_set_passes(dev, 1) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
                                     (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
-                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (!passes.empty() ? ", light passes kept" : "");
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (!passes.empty() ? ", light passes kept" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);
