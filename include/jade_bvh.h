@@ -774,6 +774,69 @@ int jade_render_passes(jade_scene* scene, float* out);
 int jade_scene_set_branch_sampling(jade_scene* scene, int mode);
 int jade_scene_get_branch_sampling(jade_scene* scene, int* mode);
 
+/* ---- Smooth shading: vertex normals interpolated at every path vertex ----
+ *
+ * Non-parity.  Every triangle carries one flat normal (jade_triangle.norm), and the reference shades with nothing else, so a curved
+ * object shows its facets in the mirror arm, in the Fresnel factors, in every hemisphere and in the denoiser's normal guide.
+ * jade_scene_set_vertex_normals gives the handle three normals per triangle - 9 floats, corners in the order p1 p2 p3, triangles in the
+ * scene description's order; NULL clears - and every vertex a path is shaded at then uses the normal interpolated at its point.  The table
+ * is a property of the handle, taken by the next jade_render_begin like the lens; a render in progress keeps the table it began with.  A
+ * count that is not the scene's is JADE_ERR_INVALID.  Entries that are not finite are not refused: they fall back as stated below.
+ * jade_scene_get_vertex_normals: *set = 1 if a table is set.  A triangle whose three normals are bitwise its norm is FLAT; a table that
+ * is flat everywhere, like no table, is today's render in every kernel, bit and counter.
+ *
+ * ---- The shading normal, stated ----
+ * tests/smooth_spec.py is this text in float64.  fl() rounds to fp32; dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)).
+ *
+ * The record of a triangle with corners p1 p2 p3, corner normals n1 n2 n3 and stored flat normal g (of any length), made when the table
+ * is set: in double, from the fp32 corners, e1 = p2 - p1, e2 = p3 - p1, N = e1 x e2, NN = N.N; the triangle is FLAT as said above, else
+ * DEGENERATE if !(NN > 0 && NN < inf), else it keeps d2 = fl((e2 x N) / NN) and d3 = fl((N x e1) / NN) per component - the dual basis, so
+ * that with w = p - p1 the barycentrics are b2 = ((w x e2).N) / NN = w.d2 and b3 = ((e1 x w).N) / NN = w.d3, b1 = 1 - b2 - b3 - and
+ * m2 = n2 - n1, m3 = n3 - n1, one fp32 subtraction per component.
+ *
+ * normal(triangle, p, r), the ONE function every use goes through - the BSSRDF exit point too, although its barycentrics are known:
+ *   FLAT or DEGENERATE: g.
+ *   w = p - p1;  b2 = dot(w, d2);  b3 = dot(w, d3);  s = fma(b3, m3, fma(b2, m2, n1)) per component   ( = b1 n1 + b2 n2 + b3 n3 )
+ *   There is no clamp: a point a rounding outside the triangle extrapolates.
+ *   ss = dot(s, s);  if !(ss > 0 && ss < inf): g  (the predicate of "The bounce, stated").   ns = s / sqrt(ss), the division per component.
+ *   The side rule: a = dot(ns, r), b = dot(g, r); unless (a > 0 && b > 0) || (a < 0 && b < 0): g, for everything at this vertex - a viewer
+ *   never sees the back of a shading normal.  The product (ns.r)(g.r) <= 0 of the rule is never formed, so it cannot underflow.
+ *   Otherwise n = ns.
+ * r is `out` at a vertex a ray arrived at (a camera ray's, a mirror's, an indirect ray's, a glass chain's), inner_direction = exit point -
+ * entry vertex at a BSSRDF exit, and the reversed incoming direction at a hit of the refraction loop.
+ *
+ * Directions the normal FORMS.  same(d, r): dot(d, g) and dot(r, g) are both > 0 or both < 0; other(d, r): one > 0, the other < 0.
+ *   mirror: refl = n * (2 dot(out, n)) - out; unless same(refl, out) it is formed again with g in place of n.
+ *   refraction entry: gen_refract_ray(-out, n, 1 / index) and the Fresnel factor of |dot(n, out)|; unless other(ray, out) both are formed
+ *     again with g.
+ *   refraction loop, with hn = normal(hit triangle, hit point, -ray): gen_refract_ray(ray, hn, index), the Fresnel factor of |dot(new ray,
+ *     hn)|, and - on total reflection or where the iteration's draw says reflect - the reflection about hn; unless the direction the
+ *     iteration leaves with is same(d, -ray) when reflected and other(d, -ray) when refracted, all of it - total reflection's decision
+ *     included - is formed again with the flat normal, on the same draw.
+ *   So no ray starts into the wrong side of its own triangle.
+ * Directions that are DRAWN, at diffuse, SSS-diffuse and BSSRDF vertices, under both bounce samplings and the three environment samplings:
+ *   every side test, flip, axis and cosine the statements make against the vertex's normal - n at a diffuse or SSS-diffuse vertex, t_norm =
+ *   normal(exit triangle, exit point, inner_direction) at a BSSRDF exit, the entry's Fresnel factor with n - is made against this normal.
+ *   A direction that passes is tested against g with the same expression - dot(d, g) * dot(out, g) < 0 at a diffuse vertex,
+ *   dot(d, g) * dot(inner, g) < 0 for the BSSRDF environment ray and > 0 for its indirect ray - and one that fails there is not traced
+ *   and contributes nothing: an emitter ray as the reference's `continue`, the environment ray as a direction on the wrong side under
+ *   JADE_ENV_IMPORTANCE (the mixture's hemisphere technique included), the indirect ray as a roulette that failed.  The reference tests no
+ *   side for the BSSRDF branch's emitter rays, so none is tested against g.  All draws are made before these tests: a sample's stream
+ *   positions are those of the flat render of the same decisions.  Rays that are not traced are not counted in jade_stats.
+ * What stays g: an emitter's own normal in an emitter term - the measure of its area.
+ * The denoiser's guide pass follows its mirror chain with the mirror statement above and its normal guide is the shading normal, turned
+ * towards the viewer as the flat one is.
+ * Known: the cull against g darkens a coarse mesh at grazing light (the shadow terminator); nothing softens it.
+ *
+ * The schedule is the one a lens runs: no fused first pass, no k_tail, JADE_SHADE_BINNED ignored.  Results do not depend on steps, tile
+ * partitions, the walk or the records per pixel.  Adaptive sampling, the guides and the denoiser, exposure and glare run on top.
+ * jade_render_begin takes a table that is not flat everywhere with the three environment samplings, with JADE_BOUNCE_COSINE and with a
+ * lens (not both), and refuses it with JADE_ERR_UNSUPPORTED together with a shutter, JADE_LIGHTS_ONE, JADE_DIRECT_MIS, passes or
+ * JADE_BRANCH_STRATIFIED (those kernels are not built yet), after the other modes' own refusals.  jade_render_multi: every scene's handle
+ * carries such a table or none does, else JADE_ERR_INVALID.  The oracle backend has no such entry. */
+int jade_scene_set_vertex_normals(jade_scene* scene, const float* normals, int32_t n_triangles);
+int jade_scene_get_vertex_normals(jade_scene* scene, int* set);
+
 #ifdef __cplusplus
 }
 #endif

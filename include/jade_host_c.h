@@ -59,6 +59,14 @@ int jadeh_builder_add_proc(jadeh_builder* b, const char* kind, int param, unsign
                            const jadeh_material* mat, const float* trans16, int normalize);
 int jadeh_write_proc_obj(const char* kind, int param, unsigned seed, const char* path);
 
+/* Smooth shading (include/jade_bvh.h, jade_scene_set_vertex_normals).  jadeh_builder_set_smoothing: the meshes added from now on get
+ * vertex normals - a corner's is the angle-weighted sum of the flat normals of the mesh's triangles that share its vertex index and lie
+ * within crease_deg of the corner's triangle, formed after the mesh's transform; <= 0 (the default): flat.  OBJ `vn` lines are not read.
+ * jadeh_vertex_normals: the same function on a caller's mesh, 9 floats per triangle into out9.  jadeh_scene_vertex_normals: the built
+ * scene's table in BVH order (*out; owned by s) and its triangle count, or 0 and NULL if no mesh was smoothed. */
+int jadeh_builder_set_smoothing(jadeh_builder* b, float crease_deg);
+int jadeh_vertex_normals(const float* verts, int nv, const int* idx, int nt, float crease_deg, float* out9);
+int jadeh_scene_vertex_normals(const jadeh_scene* s, const float** out);
 int jadeh_builder_set_env_constant(jadeh_builder* b, float r, float g, float bl);
 int jadeh_builder_set_env_sky(jadeh_builder* b, int w, int h);
 int jadeh_builder_set_env_data(jadeh_builder* b, int w, int h, const float* rgb);

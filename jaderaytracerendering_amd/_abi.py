@@ -227,6 +227,9 @@ BVH_SYMBOLS = {
     # the branch sampling of a scene handle (scene, mode) / (scene, out)
     "jade_scene_set_branch_sampling": (C.c_int, [C.c_void_p, C.c_int]),
     "jade_scene_get_branch_sampling": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # the vertex normals of a scene handle (scene, 9 floats per triangle or null, n_triangles) / (scene, out: 1 if a table is set)
+    "jade_scene_set_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "jade_scene_get_vertex_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {
@@ -240,6 +243,9 @@ HOST_SYMBOLS = {
     "jadeh_builder_add_proc": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.c_uint, C.POINTER(Material), C.c_void_p,
                                          C.c_int]),
     "jadeh_write_proc_obj": (C.c_int, [C.c_char_p, C.c_int, C.c_uint, C.c_char_p]),
+    "jadeh_builder_set_smoothing": (C.c_int, [C.c_void_p, C.c_float]),
+    "jadeh_vertex_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "jadeh_scene_vertex_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "jadeh_builder_set_env_constant": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float]),
     "jadeh_builder_set_env_sky": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jadeh_builder_set_env_data": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -229,6 +229,12 @@ class Scene:
         desc = host_scene.desc()
         backend.check(backend.lib.jade_scene_create(C.byref(desc), device_id, C.byref(self._h)))
         self._params = None
+        if getattr(host_scene, "vertex_normals", None) is not None:  # a host scene without a table behaves as it always did
+            try:
+                self.set_vertex_normals(host_scene.vertex_normals)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -477,6 +483,27 @@ class Scene:
         mode = C.c_int(-1)
         self.backend.check(fn(self._h, C.byref(mode)))
         return mode.value
+
+    def set_vertex_normals(self, normals):
+        """jade_scene_set_vertex_normals: float32 [n_triangles, 3, 3] (or anything of 9 n_triangles floats) - a normal per corner, corners in
+        the order p1 p2 p3, triangles in the scene's order - or None to clear.  The next render this handle begins interpolates them at
+        every path vertex (HIP module only; include/jade_bvh.h, "The shading normal, stated"); a table that is flat everywhere is today's
+        render bit for bit."""
+        fn = self._hip_only("jade_scene_set_vertex_normals")
+        if normals is None:
+            self.backend.check(fn(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(normals, np.float32)
+        if a.size % 9:
+            raise JadeError(_abi.JADE_ERR_INVALID, "vertex normals: 9 floats per triangle")
+        self.backend.check(fn(self._h, a.ctypes.data, a.size // 9))
+
+    def vertex_normals_set(self):
+        """jade_scene_get_vertex_normals: whether the handle carries a table."""
+        fn = self._hip_only("jade_scene_get_vertex_normals")
+        on = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(on)))
+        return bool(on.value)
 
     def set_passes(self, on):
         """jade_scene_set_passes: the next render this handle begins keeps, beside its frame, the same radiance split into the

@@ -12,6 +12,7 @@
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // jade_shade.h's non-inline statics this file does not call
 #include "jade_shade.h"
+#include "jade_smooth.h"
 #pragma clang diagnostic pop
 
 #if JADE_DEBUG_EXPORTS
@@ -323,6 +324,17 @@ static __host__ __device__ __forceinline__ uint32_t debug_branch_row(const uint3
 __global__ void k_debug_branch_number(int n, const uint32_t* rows, uint32_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = debug_branch_row(rows + (size_t)BRANCH_ROW * i);
+}
+
+// the shading normal of row i (jade_debug_shading_normal, below): the record of row i is entry i of `table`
+enum { SMOOTH_ROW = 27 };
+__global__ void k_debug_shading_normal(int n, const float4* table, const float* rows, float* out_n, int32_t* out_rule) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rows + (size_t)SMOOTH_ROW * i;
+  int32_t rule;
+  put3(out_n, i, shading_normal_rule(table, i, V3(r + 18), V3(r + 21), V3(r + 24), &rule));
+  out_rule[i] = rule;
 }
 
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
@@ -823,6 +835,47 @@ int jade_debug_shade_mode_branch_host(int32_t env_sampling, int32_t lens, int32_
                                     branch_sampling == JADE_BRANCH_STRATIFIED))
     return jade_fail(rc, why);
   *mode = m;
+  return JADE_OK;
+}
+
+// ... and with whether the handle carries vertex normals that are not flat everywhere (jade_scene_set_vertex_normals; tests/test_smooth_modes_cpu.py).
+int jade_debug_shade_mode_smooth_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                      int32_t passes, int32_t branch_sampling, int32_t smooth, uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (branch_sampling != JADE_BRANCH_RANDOM && branch_sampling != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0,
+                                    branch_sampling == JADE_BRANCH_STRATIFIED, smooth != 0))
+    return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
+// The shading normal (shading_normal_rule, jade_smooth.h; include/jade_bvh.h "The shading normal, stated") on n rows of SMOOTH_ROW floats:
+// p1, p2, p3, n1, n2, n3, g, p, r (27).  Each row's record is made by smooth_record, as jade_scene_set_vertex_normals makes it;
+// out_n[i] = the normal the vertex uses, out_rule[i] = which rule gave it (SMOOTH_RULE_*; tests/test_gpu_smooth.py).
+int jade_debug_shading_normal(int device_id, int32_t n, const float* rows, float* out_n, int32_t* out_rule) {
+  if (!rows || !out_n || !out_rule) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / SMOOTH_ROW) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  HIP_TRY(hipSetDevice(device_id));
+  const size_t N = (size_t)n;
+  std::vector<float4> rec(N * JADE_SMOOTH_REC);
+  for (size_t i = 0; i < N; ++i) {
+    const float* r = rows + SMOOTH_ROW * i;
+    smooth_record(r, r + 3, r + 6, r + 9, r + 18, &rec[i * JADE_SMOOTH_REC]);
+  }
+  DevBuf bt, bi, bn, br;
+  HIP_TRY(upload0(bt, rec.data(), 4 * rec.size()));  // (upload0 counts 4-byte elements: a record is JADE_SMOOTH_REC float4)
+  HIP_TRY(upload0(bi, rows, SMOOTH_ROW * N));
+  HIP_TRY(bn.alloc(12 * N));
+  HIP_TRY(br.alloc(4 * N));
+  hipLaunchKernelGGL(k_debug_shading_normal, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, n, bt.as<float4>(), bi.as<float>(), bn.as<float>(), br.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(out_n, bn.p, 12 * N, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_rule, br.p, 4 * N, hipMemcpyDeviceToHost));
   return JADE_OK;
 }
 

@@ -58,6 +58,7 @@
 
 #include "jade_runtime.h"
 #include "jade_shade.h"
+#include "jade_smooth_shade.h"
 #include "jade_trace.h"
 #include "jade_light.h"
 
@@ -175,11 +176,13 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // PassPlanes).  The colour itself is formed by the statements it always was.
 // SM_BRANCH: the draws that choose the arm at a vertex of depth 0 or 1 are read off the sample's stratified number U ("The branch draws, stated";
 // branch_number, jade_shade.h), formed here from the record's `done` and home pixel.  Nothing of it travels with the record.
+// SM_SMOOTH: the normal of every vertex shaded is the triangle's vertex normals interpolated at the vertex ("The shading normal, stated"), from the records
+// A.smooth() (jade_smooth_shade.h), where the bounce and the fold stand a second time with it.  Nothing of it travels with the record.
 template <bool LEAN, uint32_t M = 0>
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
                                                     const ShadeArgs<M>& A = SHADE_ARGS_NONE) {
-  constexpr bool ENVIS = sm(M, SM_ENVIS), LENS = sm(M, SM_LENS), SHUTTER = sm(M, SM_SHUTTER), LIGHTS = sm(M, SM_LIGHTS), PASSES = sm(M, SM_PASSES), BRANCH = sm(M, SM_BRANCH);
+  constexpr bool ENVIS = sm(M, SM_ENVIS), LENS = sm(M, SM_LENS), SHUTTER = sm(M, SM_SHUTTER), LIGHTS = sm(M, SM_LIGHTS), PASSES = sm(M, SM_PASSES), BRANCH = sm(M, SM_BRANCH), SMOOTH = sm(M, SM_SMOOTH);
   const int npix = P.npix;
   uint32_t st = ST_INVALID;
   defer = false;
@@ -264,7 +267,9 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
         st = ST_VERTEX;
       }
     } else if (on_path) {
-      int r = LEAN ? consume_mirror<Px, M>(S, px, c, &l_final, &parts) : consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
+      int r;
+      if constexpr (SMOOTH && !LEAN) r = consume_smooth<M>(S, px, c, &l_final, A.smooth());
+      else r = LEAN ? consume_mirror<Px, M>(S, px, c, &l_final, &parts) : consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
       if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
       if (r == CONSUME_VERTEX) {
         st = ST_VERTEX;
@@ -307,6 +312,21 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
             if (!ENVIS || c.n_emit_rays != 0) break;
             const int r = consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
             if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
+            if (r == CONSUME_VERTEX) {
+              st = ST_VERTEX;
+              continue;
+            }
+            color = r == CONSUME_END ? jv_add(c.le, jv_add(c.acc, jv_mul(c.thr, l_final))) : c.le;
+            finished = true;
+            continue;
+          }
+        } else if constexpr (SMOOTH) {
+          // A mode with SM_SMOOTH: the same step with the shading normal (jade_smooth_shade.h).  A bounce may emit no ray under any environment sampling -
+          // every drawn direction can fail against the flat normal - and then has all its results already, as under SM_ENVIS below.
+          if (LEAN ? begin_bounce_lean_smooth(S, px, c, &l_final, A.smooth()) : begin_bounce_smooth<M>(S, px, c, &l_final, A.smooth())) {
+            st = c.stage;
+            if (LEAN || c.n_emit_rays != 0) break;  // (the lean kernel's mirror always emits its ray)
+            const int r = consume_smooth<M>(S, px, c, &l_final, A.smooth());
             if (r == CONSUME_VERTEX) {
               st = ST_VERTEX;
               continue;
@@ -1493,6 +1513,42 @@ int jade_scene_get_branch_sampling(jade_scene* s, int* mode) {
   return JADE_OK;
 }
 
+// The vertex normals of the scene handle (include/jade_bvh.h, "The shading normal, stated"): the table's records (jade_smooth.h) are made here,
+// from the triangles as the handle holds them, and uploaded by the next jade_render_begin - a render in progress keeps the table it began with.
+int jade_scene_set_vertex_normals(jade_scene* s, const float* normals, int32_t n_triangles) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (!normals) {
+    s->smooth_rec.clear();
+    s->smooth_rec.shrink_to_fit();
+    s->smooth_any = false;
+    s->smooth_uploaded = false;
+    return JADE_OK;
+  }
+  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "vertex normals: the triangle count is not the scene's");
+  HIP_TRY(hipSetDevice(s->device));
+  std::vector<jade_triangle> tris((size_t)n_triangles);
+  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  std::vector<float4> rec(tris.size() * JADE_SMOOTH_REC);
+  bool any = false;
+  for (size_t i = 0; i < tris.size(); ++i) {
+    const jade_triangle& t = tris[i];
+    smooth_record(t.p1, t.p2, t.p3, normals + 9 * i, t.norm, &rec[i * JADE_SMOOTH_REC]);
+    uint32_t flag;
+    memcpy(&flag, &rec[i * JADE_SMOOTH_REC].w, 4);
+    any = any || flag != SMOOTH_FLAT;
+  }
+  s->smooth_rec.swap(rec);
+  s->smooth_any = any;
+  s->smooth_uploaded = false;
+  return JADE_OK;
+}
+int jade_scene_get_vertex_normals(jade_scene* s, int* set) {
+  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *set = s->smooth_rec.empty() ? 0 : 1;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -1586,11 +1642,16 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED))
+                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any))
     return jade_fail(rc, why);
   if ((mode & SM_PASSES) && s->tun.pixel_rotate)
     return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
   HIP_TRY(hipSetDevice(s->device));
+  if ((mode & SM_SMOOTH) && !s->smooth_uploaded) {  // the handle's table as it is now: the render keeps it whatever the setter is told before the next begin
+    s->have_rp = false;  // (the earlier render's kernels would read the buffer that is given back here)
+    HIP_TRY(upload(s->b_smooth, s->smooth_rec.data(), s->smooth_rec.size(), s->stream));
+    s->smooth_uploaded = true;
+  }
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
   for (int y = 0; y < ty; ++y)
@@ -1728,6 +1789,7 @@ static ShadeArgs<K> mode_args(const jade_scene* s) {
   if constexpr (sm(K, SM_SHUTTER)) a.shutter = s->sh;
   if constexpr ((K & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0) a.light_table = s->b_light_alias.as<uint4>();
   if constexpr (sm(K, SM_MIS)) a.mis_table = s->b_mis.as<float2>();
+  if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = s->b_smooth.as<float4>();
   return a;
 }
 template <uint32_t M>
@@ -1746,7 +1808,7 @@ static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, con
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
-  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH);  // (the camera arm, the passes and the mirror's shared-out roulette are all of a mode the lean kernel carries)
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH | SM_SMOOTH);  // (the camera arm, the passes, the mirror's shared-out roulette and its shading normal are all of a mode the lean kernel carries)
   auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
                        s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), a...);
@@ -1866,7 +1928,8 @@ static int account_pending_trace(PassRun& r) {
 // A render that keeps passes (jade_scene_set_passes) runs that schedule as well: k_light and k_light_packet book nothing.
 // A render with the branch draws shared out (jade_scene_set_branch_sampling) runs it too: k_light and k_light_packet shade the camera vertex with the
 // stream's draws.
-static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s) && !passes_on(s) && !branch_on(s); }
+// A smooth render (jade_scene_set_vertex_normals) runs it as well: k_light and k_light_packet shade the camera vertex's mirror with the flat normal.
+static bool fused_first_pass(const jade_scene* s) { return s->tun.fused && !own_origin(s) && !passes_on(s) && !branch_on(s) && !smooth_on(s); }
 
 // The records with work in this call: all of them when the step gives every record a sample (k_light then walks the
 // records itself); otherwise - a flush, a step of fewer samples than records per pixel - k_arm lists and counts them.

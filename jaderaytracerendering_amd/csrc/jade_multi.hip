@@ -140,6 +140,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
     for (int i = 1; i < ndev; ++i)
       if (scenes[i]->*k.mode != scenes[0]->*k.mode)
         return jade_fail(JADE_ERR_INVALID, std::string("the scenes carry different ") + k.noun + " sampling modes (" + k.setter + "): scene " + std::to_string(i) + " against scene 0");
+  // ... and either every scene shades smooth (jade_scene_set_vertex_normals, a table that is not flat everywhere) or none does
+  for (int i = 1; i < ndev; ++i)
+    if (scenes[i]->smooth_any != scenes[0]->smooth_any)
+      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry vertex normals (jade_scene_set_vertex_normals): scene " + std::to_string(i) + " against scene 0");
   // ... and none keeps passes: only the frame is gathered here (each rank renders its share and calls jade_render_passes)
   for (int i = 0; i < ndev; ++i)
     if (scenes[i]->passes)

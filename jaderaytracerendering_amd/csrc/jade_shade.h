@@ -479,7 +479,8 @@ struct PassPlanes {
 // What the kernels of mode M take beyond the parity kernels' arguments, in one piece: a by-value kernel argument, the last (k_shade_mode, which says why SM_MIS is
 // the exception; k_shade_lean_mode; mode_args, jade_hip.hip).  A member is there only in the modes that take it - in the others its base is the empty one, which takes
 // no space and whose accessor answers nullptr, so shade_record is one text - in this order: the pass planes under SM_PASSES; the shutter's constants under SM_SHUTTER; the
-// alias table over the scene's emitter entries under SM_LIGHTS, SM_COSINE or SM_MIS (read under SM_LIGHTS only); the per-triangle table {m, M} under SM_MIS.
+// alias table over the scene's emitter entries under SM_LIGHTS, SM_COSINE or SM_MIS (read under SM_LIGHTS only); the per-triangle table {m, M} under SM_MIS; the
+// vertex-normal records under SM_SMOOTH.
 struct ArgPlanes { PassPlanes planes; __device__ const PassPlanes* L() const { return &planes; } };
 struct NoPlanes { __device__ const PassPlanes* L() const { return nullptr; } };
 struct ArgShutter { ShutterConst shutter; __device__ const ShutterConst* H() const { return &shutter; } };
@@ -488,9 +489,12 @@ struct ArgLights { const uint4* light_table; __device__ const uint4* lights() co
 struct NoLights { __device__ const uint4* lights() const { return nullptr; } };
 struct ArgMis { const float2* mis_table; __device__ const float2* mis() const { return mis_table; } };
 struct NoMis { __device__ const float2* mis() const { return nullptr; } };
+struct ArgSmooth { const float4* smooth_table; __device__ const float4* smooth() const { return smooth_table; } };  // SM_SMOOTH: the vertex-normal records (jade_smooth.h)
+struct NoSmooth { __device__ const float4* smooth() const { return nullptr; } };
 template <uint32_t M>
 struct ShadeArgs : std::conditional_t<sm(M, SM_PASSES), ArgPlanes, NoPlanes>, std::conditional_t<sm(M, SM_SHUTTER), ArgShutter, NoShutter>,
-                   std::conditional_t<(M & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0, ArgLights, NoLights>, std::conditional_t<sm(M, SM_MIS), ArgMis, NoMis> {};
+                   std::conditional_t<(M & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0, ArgLights, NoLights>, std::conditional_t<sm(M, SM_MIS), ArgMis, NoMis>,
+                   std::conditional_t<sm(M, SM_SMOOTH), ArgSmooth, NoSmooth> {};
 static __device__ const ShadeArgs<0> SHADE_ARGS_NONE{};  // what mode 0 passes, by name: with a temporary on the caller's stack k_shade_lean and k_tail come out in another order
 // What consume / consume_mirror tell shade_record about the vertex they folded: cls < 0 - nothing to book (l_final is 0);
 // PASS_EMISSION / PASS_SPECULAR_SKY - *l_final is that pass's (e holds it); otherwise 3 + 4 kind + depth, the vertex's emitter pass, its sky

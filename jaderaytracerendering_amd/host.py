@@ -83,14 +83,28 @@ def camera_move(eye, cam, truck=None, orbit_deg=0.0, pivot=None):
     return eye_out, cam_out
 
 
-class HostScene:
-    """Flattened scene: the arrays that cross the jade_rt.h boundary."""
+def vertex_normals(vertices, indices, crease_deg):
+    """jadeh_vertex_normals: float32 [n_triangles, 3, 3], a normal per corner of every triangle of the mesh (vertices [nv, 3], indices
+    [nt, 3]) - the angle-weighted sum of the flat normals of the triangles that share the corner's vertex index and lie within
+    crease_deg of the corner's triangle.  crease_deg <= 0: the flat normal thrice, bitwise.  What Scene.set_vertex_normals takes, for a
+    mesh whose triangles are the scene's in this order."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    i = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    out = np.zeros((len(i), 3, 3), np.float32)
+    _check(host_lib().jadeh_vertex_normals(v.ctypes.data, len(v), i.ctypes.data, len(i), float(crease_deg), out.ctypes.data))
+    return out
 
-    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0):
+
+class HostScene:
+    """Flattened scene: the arrays that cross the jade_rt.h boundary, and - optional, beside them - vertex_normals: float32
+    [n_triangles, 3, 3] in the triangles' order, which Backend.scene() puts on the handle (Scene.set_vertex_normals), or None."""
+
+    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0, vertex_normals=None):
         # arrays: dict of numpy arrays (owned copies)
         self.a = arrays
         self.bvh_depth = bvh_depth
         self.build_seconds = build_seconds
+        self.vertex_normals = vertex_normals
 
     ARRAY_KEYS = ("triangles", "nodes", "emit", "mapping", "prefix", "segs", "env")
 
@@ -115,14 +129,20 @@ class HostScene:
             "segs": grab(d.obj_segs, d.n_objects * 2, np.int32).reshape(-1, 2),
             "env": grab(d.env_rgb, d.env_width * d.env_height * 3, np.float32).reshape(d.env_height, d.env_width, 3),
         }
-        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle))
+        vn, p = None, C.c_void_p()
+        n = lib.jadeh_scene_vertex_normals(handle, C.byref(p))
+        if n:
+            vn = np.frombuffer((C.c_char * (n * 36)).from_address(p.value), dtype=np.float32).copy().reshape(n, 3, 3)
+        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle), vn)
 
     @classmethod
     def from_npz(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS})
+            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS}, vertex_normals=z["vertex_normals"].copy() if "vertex_normals" in z.files else None)
 
     def save_npz(self, path, **extra):
+        if self.vertex_normals is not None:
+            extra = dict(extra, vertex_normals=self.vertex_normals)
         np.savez_compressed(path, **self.a, **extra)
 
     @property
@@ -207,6 +227,11 @@ class SceneBuilder:
         t = self._t(trans)
         _check(self._lib.jadeh_builder_add_proc(self._h, kind.encode(), int(param), int(seed), C.byref(mat),
                                                 t.ctypes.data, int(normalize)))
+
+    def set_smoothing(self, crease_deg):
+        """jadeh_builder_set_smoothing: the meshes added from now on get vertex normals (vertex_normals() after the mesh's transform;
+        <= 0: flat again).  The built HostScene then carries `vertex_normals`."""
+        _check(self._lib.jadeh_builder_set_smoothing(self._h, float(crease_deg)))
 
     def set_env_constant(self, r, g, b):
         _check(self._lib.jadeh_builder_set_env_constant(self._h, r, g, b))

@@ -97,6 +97,25 @@ int jadeh_write_proc_obj(const char* kind, int param, unsigned seed, const char*
   return write_obj(path, m) ? 0 : fail(std::string("cannot write ") + path);
 }
 
+int jadeh_builder_set_smoothing(jadeh_builder* b, float crease_deg) {
+  if (!b) return fail("null builder");
+  if (!(crease_deg == crease_deg)) return fail("set_smoothing: the angle is not a number");
+  b->b.set_smoothing(crease_deg);
+  return 0;
+}
+int jadeh_vertex_normals(const float* verts, int nv, const int* idx, int nt, float crease_deg, float* out9) {
+  if (!verts || !idx || !out9 || nv < 0 || nt < 0) return fail("vertex_normals: bad arguments");
+  Mesh m;
+  m.vertices.resize((size_t)nv);
+  for (int i = 0; i < nv; ++i) m.vertices[i] = jv(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]);
+  for (int i = 0; i < 3 * nt; ++i) {
+    if (idx[i] < 0 || idx[i] >= nv) return fail("vertex_normals: index out of range");
+    m.indices.push_back(idx[i]);
+  }
+  const std::vector<float> vn = vertex_normals(m, crease_deg);
+  if (!vn.empty()) memcpy(out9, vn.data(), vn.size() * sizeof(float));
+  return 0;
+}
 int jadeh_builder_set_env_constant(jadeh_builder* b, float r, float g, float bl) {
   if (!b) return fail("null builder");
   b->b.set_env(make_env_constant(r, g, bl));
@@ -193,6 +212,11 @@ jadeh_scene* jadeh_builder_build_with_bvh(jadeh_builder* b, const int32_t* order
 void jadeh_scene_free(jadeh_scene* s) { delete s; }
 void jadeh_scene_desc(const jadeh_scene* s, jade_scene_desc* out) {
   if (s && out) *out = s->s.desc();
+}
+int jadeh_scene_vertex_normals(const jadeh_scene* s, const float** out) {
+  if (!s) return 0;
+  if (out) *out = s->s.vertex_normals.empty() ? nullptr : s->s.vertex_normals.data();
+  return (int)(s->s.vertex_normals.size() / 9);
 }
 int jadeh_scene_bvh_depth(const jadeh_scene* s) { return s ? s->s.bvh_depth : 0; }
 double jadeh_scene_build_seconds(const jadeh_scene* s) { return s ? s->s.build_seconds : 0; }

@@ -53,6 +53,13 @@ Mesh make_geodesic(int freq);        // unit sphere, 20*freq^2 triangles, shared
 // seeded multi-octave field.  style 0 = upright statue, 1 = elongated "dragon".
 Mesh make_statue(int freq, uint32_t seed, int style);
 void append(Mesh& dst, const Mesh& src);
+// Vertex normals for smooth shading (include/jade_bvh.h, jade_scene_set_vertex_normals): 9 floats per triangle, corners in the order of its
+// indices.  A corner's normal is the sum, over the mesh's triangles that share its vertex INDEX and whose flat normal is within
+// crease_deg of this triangle's, of those flat normals, each weighted by its triangle's interior angle at the vertex; formed in double
+// from the fp32 flat normals (add_mesh's own statement), normalised, rounded once.  crease_deg <= 0, or a corner nothing but its own
+// triangle contributes to, or one whose contributors all have this triangle's flat normal (component by component, -0 = 0), or a sum without a direction: the
+// flat normal, bitwise.
+std::vector<float> vertex_normals(const Mesh& mesh, float crease_deg);
 
 // -- scene builder (host triangles, pre-BVH) -------------------------------
 struct HostTriangle {  // == Triangle, PathTrace.cu:305-311
@@ -77,6 +84,7 @@ struct BuiltScene {
   std::vector<int32_t> mapping;          // original -> sorted
   std::vector<float> prefix;             // original order
   std::vector<jade_obj_seg> segs;
+  std::vector<float> vertex_normals;     // 9 per triangle, BVH order: what jade_scene_set_vertex_normals takes; empty if no mesh was smoothed
   EnvMap env;
   int bvh_depth = 0;
   double build_seconds = 0;
@@ -90,6 +98,9 @@ class SceneBuilder {
   // 4x4 transform, flat normals, one object segment.
   void add_mesh(const Mesh& mesh, const Material& mat, const Mat4& trans, bool normalize);
   void set_env(EnvMap env) { env_ = std::move(env); }
+  // The smoothing angle of the meshes added from now on (degrees; <= 0: flat, the default): add_mesh forms their vertex normals with
+  // vertex_normals(), after the mesh's transform.  load_obj reads no `vn` lines: normals come from the geometry alone.
+  void set_smoothing(float crease_deg) { smooth_deg_ = crease_deg; }
   int triangle_count() const { return (int)tris_.size(); }
   // Area prefix sums (PathTrace.cu:1539-1546), SAH BVH with leaf size 8
   // (:1557-1565), encode (:1570-1612).
@@ -104,6 +115,8 @@ class SceneBuilder {
   void finish(std::vector<HostTriangle>& sorted, BuiltScene& out) const;
   std::vector<HostTriangle> tris_;
   std::vector<jade_obj_seg> segs_;
+  std::vector<float> vnorm_;  // 9 per triangle of tris_, original order; empty until a mesh is smoothed
+  float smooth_deg_ = 0.0f;
   EnvMap env_;
 };
 

@@ -57,6 +57,8 @@ struct Api {
   int (*scene_set_direct_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --branch
   int (*scene_set_branch_sampling)(jade_scene*, int) = nullptr;
+  // ... and only for --smooth
+  int (*scene_set_vertex_normals)(jade_scene*, const float*, int32_t) = nullptr;
   // ... and only for --passes
   int (*scene_set_passes)(jade_scene*, int) = nullptr;
   int (*render_passes)(jade_scene*, float*) = nullptr;
@@ -103,7 +105,7 @@ static void usage() {
   fprintf(stderr,
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
-          "                   [--bounce uniform|cosine] [--direct rays|mis] [--branch random|stratified] [--passes PREFIX]\n"
+          "                   [--bounce uniform|cosine] [--direct rays|mis] [--branch random|stratified] [--passes PREFIX] [--smooth [DEG]]\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -131,6 +133,10 @@ static void usage() {
           "                       SSS or BSSRDF, the mirror's roulette - instead of tossing them (HIP backend only; NOT the reference's samples;\n"
           "                       include/jade_bvh.h).  Same rays per sample on average; not together with --aperture, --shutter-* or --one-light.\n"
           "                       random is the default\n"
+          "  --smooth [DEG]: vertex normals for every object - at each corner the angle-weighted mean of the flat normals of the triangles that\n"
+          "                       share its vertex and lie within DEG degrees (default 60) of its triangle - interpolated at every path vertex\n"
+          "                       (HIP backend only; NOT the reference's image; include/jade_bvh.h).  OBJ vn lines are not read.  Not together\n"
+          "                       with --shutter-*, --one-light, --direct mis, --passes or --branch stratified\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -180,6 +186,7 @@ int main(int argc, char** argv) {
   int direct = -1;  // --direct: JADE_DIRECT_*, -1 = not given
   int branch = -1;  // --branch: JADE_BRANCH_*, -1 = not given
   std::string passes;  // --passes PREFIX
+  double smooth_deg = 0.0;  // --smooth [DEG]: the objects' smoothing angle, 0 = not given
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -231,6 +238,18 @@ int main(int argc, char** argv) {
       else { fprintf(stderr, "--branch takes random or stratified, not %s\n", v.c_str()); return 2; }
     }
     else if (a == "--passes") passes = need("--passes");
+    else if (a == "--smooth") {  // the angle is optional: taken if the next argument is a number
+      smooth_deg = 60.0;
+      if (i + 1 < argc) {
+        char* end = nullptr;
+        const double v = strtod(argv[i + 1], &end);
+        if (end != argv[i + 1] && *end == 0) {
+          ++i;
+          if (!std::isfinite(v) || !(v > 0.0 && v <= 180.0)) { fprintf(stderr, "--smooth takes an angle in (0, 180] degrees, not %s\n", argv[i]); return 2; }
+          smooth_deg = v;
+        }
+      }
+    }
     else if (a == "--direct") {
       const std::string v = need("--direct");
       if (v == "rays") direct = JADE_DIRECT_RAYS;
@@ -319,6 +338,7 @@ int main(int argc, char** argv) {
   }
 
   SceneBuilder builder;
+  builder.set_smoothing((float)smooth_deg);  // (0: flat) - every object of the configuration or of render_args
   Config cfg;
   std::string err;
   if (!config.empty()) {
@@ -428,6 +448,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (smooth_deg > 0.0) {
+    *(void**)(&api.scene_set_vertex_normals) = dlsym(api.h, "jade_scene_set_vertex_normals");
+    if (!api.scene_set_vertex_normals) {
+      fprintf(stderr, "--smooth needs the HIP backend: %s has no jade_scene_set_vertex_normals\n", backend.c_str());
+      return 2;
+    }
+  }
   if (!passes.empty()) {
     *(void**)(&api.scene_set_passes) = dlsym(api.h, "jade_scene_set_passes");
     *(void**)(&api.render_passes) = dlsym(api.h, "jade_render_passes");
@@ -492,10 +519,15 @@ int main(int argc, char** argv) {
   if (bounce >= 0 && api.scene_set_bounce_sampling(dev, bounce) != JADE_OK) { fprintf(stderr, "bounce sampling: %s\n", api.last_error()); return 1; }
   if (direct >= 0 && api.scene_set_direct_sampling(dev, direct) != JADE_OK) { fprintf(stderr, "direct sampling: %s\n", api.last_error()); return 1; }
   if (branch >= 0 && api.scene_set_branch_sampling(dev, branch) != JADE_OK) { fprintf(stderr, "branch sampling: %s\n", api.last_error()); return 1; }
+  if (smooth_deg > 0.0 && !scene.vertex_normals.empty() &&
+      api.scene_set_vertex_normals(dev, scene.vertex_normals.data(), (int32_t)(scene.vertex_normals.size() / 9)) != JADE_OK) {
+    fprintf(stderr, "vertex normals: %s\n", api.last_error());
+    return 1;
+  }
   if (!passes.empty() && api.scene_set_passes(dev, 1) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
                                     (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
-                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (!passes.empty() ? ", light passes kept" : "");
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (smooth_deg > 0.0 ? ", smooth shading" : "") + (!passes.empty() ? ", light passes kept" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);

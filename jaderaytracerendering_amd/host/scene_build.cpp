@@ -228,6 +228,53 @@ Mesh make_statue(int freq, uint32_t seed, int style) {
   return m;
 }
 
+// ------------------------------------------------------- vertex normals ----
+
+std::vector<float> vertex_normals(const Mesh& mesh, float crease_deg) {
+  const size_t nt = mesh.indices.size() / 3, nv = mesh.vertices.size();
+  std::vector<jvec3> flat(nt);
+  std::vector<double> angle(3 * nt, 0.0);
+  std::vector<std::vector<uint32_t>> users(nv);  // corners (3 * triangle + k) by vertex index
+  for (size_t i = 0; i < nt; ++i) {
+    const jvec3 p[3] = {mesh.vertices[mesh.indices[3 * i]], mesh.vertices[mesh.indices[3 * i + 1]], mesh.vertices[mesh.indices[3 * i + 2]]};
+    flat[i] = jv_normalize(jv_cross(jv_sub(p[1], p[0]), jv_sub(p[2], p[0])));
+    for (int k = 0; k < 3; ++k) {
+      const jvec3 &o = p[k], &a = p[(k + 1) % 3], &b = p[(k + 2) % 3];
+      const double u[3] = {(double)a.x - o.x, (double)a.y - o.y, (double)a.z - o.z}, v[3] = {(double)b.x - o.x, (double)b.y - o.y, (double)b.z - o.z};
+      const double c[3] = {u[1] * v[2] - u[2] * v[1], u[2] * v[0] - u[0] * v[2], u[0] * v[1] - u[1] * v[0]};
+      angle[3 * i + k] = std::atan2(std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), u[0] * v[0] + u[1] * v[1] + u[2] * v[2]);
+      users[mesh.indices[3 * i + k]].push_back((uint32_t)(3 * i + k));
+    }
+  }
+  const double cos_crease = std::cos((double)crease_deg * 3.14159265358979323846 / 180.0);
+  std::vector<float> out(9 * nt);
+  for (size_t i = 0; i < nt; ++i) {
+    const double fi[3] = {flat[i].x, flat[i].y, flat[i].z};
+    for (int k = 0; k < 3; ++k) {
+      double s[3] = {0, 0, 0};
+      size_t others = 0;
+      bool same = true;  // every contributor's flat normal equals this triangle's, component by component: that normal is the answer, bitwise
+      if (crease_deg > 0.0f)
+        for (const uint32_t c : users[mesh.indices[3 * i + k]]) {
+          const size_t j = c / 3;
+          const double fj[3] = {flat[j].x, flat[j].y, flat[j].z};
+          if (j != i && !(fi[0] * fj[0] + fi[1] * fj[1] + fi[2] * fj[2] >= cos_crease)) continue;
+          others += j != i;
+          same = same && flat[j].x == flat[i].x && flat[j].y == flat[i].y && flat[j].z == flat[i].z;
+          for (int x = 0; x < 3; ++x) s[x] += angle[c] * fj[x];
+        }
+      const double len = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+      float* o = &out[9 * i + 3 * k];
+      if (others == 0 || same || !(len > 0.0 && len < (double)INFINITY)) {
+        o[0] = flat[i].x; o[1] = flat[i].y; o[2] = flat[i].z;
+      } else {
+        for (int x = 0; x < 3; ++x) o[x] = (float)(s[x] / len);
+      }
+    }
+  }
+  return out;
+}
+
 // -------------------------------------------------------------- builder ----
 
 static float host_tri_area(const HostTriangle& t) {  // size(), PathTrace.cu:459-465
@@ -274,6 +321,24 @@ void SceneBuilder::add_mesh(const Mesh& mesh, const Material& mat, const Mat4& t
     t.p3 = vertices[mesh.indices[3 * i + 2]];
     t.norm = jv_normalize(jv_cross(jv_sub(t.p2, t.p1), jv_sub(t.p3, t.p1)));
     t.material = mat;
+  }
+  // vertex normals, after the transform: this mesh's if it is smoothed, and the flat normal thrice for every triangle that is not once any is
+  if (smooth_deg_ > 0.0f || !vnorm_.empty()) {
+    const size_t have = vnorm_.size() / 9;
+    vnorm_.resize(9 * tris_.size());
+    for (size_t i = have; i < tris_.size(); ++i)
+      for (int k = 0; k < 3; ++k) {
+        vnorm_[9 * i + 3 * k] = tris_[i].norm.x;
+        vnorm_[9 * i + 3 * k + 1] = tris_[i].norm.y;
+        vnorm_[9 * i + 3 * k + 2] = tris_[i].norm.z;
+      }
+    if (smooth_deg_ > 0.0f) {
+      Mesh moved;
+      moved.vertices = vertices;
+      moved.indices = mesh.indices;
+      const std::vector<float> vn = vertex_normals(moved, smooth_deg_);
+      std::copy(vn.begin(), vn.begin() + 9 * (size_t)ntri, vnorm_.begin() + 9 * (size_t)offset);
+    }
   }
 }
 
@@ -477,6 +542,11 @@ void SceneBuilder::finish(std::vector<HostTriangle>& tris, BuiltScene& out) cons
     out.mapping[t.index] = (int32_t)i;
     const Material& m = t.material;
     if (m.emissive[0] > 1.5e-4f || m.emissive[1] > 1.5e-4f || m.emissive[2] > 1.5e-4f) out.emit.push_back((int32_t)i);
+  }
+  out.vertex_normals.clear();
+  if (!vnorm_.empty()) {  // the triangles' own, carried through whatever order `tris` is in
+    out.vertex_normals.resize(9 * n);
+    for (size_t i = 0; i < n; ++i) std::copy(vnorm_.begin() + 9 * (size_t)tris[i].index, vnorm_.begin() + 9 * (size_t)tris[i].index + 9, out.vertex_normals.begin() + 9 * i);
   }
   out.env = env_.width > 0 ? env_ : make_env_constant(0, 0, 0);
 }
