@@ -837,6 +837,69 @@ int jade_scene_get_branch_sampling(jade_scene* scene, int* mode);
 int jade_scene_set_vertex_normals(jade_scene* scene, const float* normals, int32_t n_triangles);
 int jade_scene_get_vertex_normals(jade_scene* scene, int* set);
 
+/* ---- Albedo textures: UVs per triangle, images filtered at every path vertex ----
+ *
+ * Non-parity.  Every triangle has one brdf and one refract_albedo (jade_material), so a colour cannot vary over a surface.
+ * jade_scene_set_textures gives the handle n_images images, six floats of UV per triangle - (u, v) of the corners p1 p2 p3, triangles in
+ * the scene description's order - and one image number per triangle, -1 for a triangle without an image.  An image is width x height
+ * texels of linear RGB, interleaved, row 0 at v = 0, texel (i, j) covering u in [i / W, (i + 1) / W).  The texels are copied: the caller's
+ * arrays may go after the call.  n_images = 0 or a NULL array clears.  The table is a property of the handle, taken by the next
+ * jade_render_begin like the lens and the vertex normals; a render in progress keeps the table it began with.
+ * JADE_ERR_INVALID, with a message that names the offender, and the handle's table left as it was: an n_triangles that is not the scene's,
+ * an image_of outside [-1, n_images), a width or height outside 1 .. 16384, more than 65 536 images, a texel that is not finite.  UVs that
+ * are not finite are NOT refused (the statement says what they give), and texels are otherwise used as given: negative values and values
+ * above 1 pass through.  jade_scene_get_textures: *set = 1 if a table is set.  A table in which no triangle names an image, like no table,
+ * is today's render in every kernel, bit and counter.
+ *
+ * ---- The surface colour, stated ----
+ * tests/texture_spec.py is this text: the lookup in float64, the fetch in emulated fp32 as well.  fl() rounds to fp32; fma(a, b, c) is
+ * a * b + c rounded once; dot(a, b) = fma(a.z, b.z, fma(a.y, b.y, a.x * b.x)), as in "The shading normal, stated".
+ *
+ * The record of a triangle with corners p1 p2 p3 and corner UVs uv1 uv2 uv3, made when the table is set: d2 and d3 exactly as the smooth
+ * record's - in double, from the fp32 corners, e1 = p2 - p1, e2 = p3 - p1, N = e1 x e2, NN = N.N, d2 = fl((e2 x N) / NN), d3 = fl((N x e1)
+ * / NN) per component - except that a triangle whose NN is not in (0, inf) keeps d2 = d3 = 0, so that every one of its points has uv1;
+ * du2 = uv2 - uv1 and du3 = uv3 - uv1, one fp32 subtraction per component.
+ *
+ * uv(triangle, p):  w = p - p1;  b2 = dot(w, d2);  b3 = dot(w, d3);  u = fma(b3, du3.x, fma(b2, du2.x, uv1.x));  v the same with .y.
+ *   There is no clamp: a point a rounding outside its triangle extrapolates.
+ *
+ * colour(image, u, v), each line one fp32 operation, W and H the image's size, t(i, j) texel i of row j:
+ *   If u or v is NaN or infinite the colour is (1, 1, 1) and nothing below is formed.
+ *   u' = u - floor(u)                  in [0, 1]: 1 itself where u is a small negative number
+ *   x  = fma(u', fl(W), -0.5f)         texel centres at the integers
+ *   xf = floor(x);  fx = x - xf;  i0 = (int)xf  in [-1, W - 1];  i1 = i0 + 1
+ *   an i0 of -1 becomes W - 1, an i1 of W becomes 0                                    (the image repeats)
+ *   v, H, y, yf, fy, j0, j1 the same.  Then per channel:
+ *   top = fma(fx, t(i1, j0) - t(i0, j0), t(i0, j0));  bottom = fma(fx, t(i1, j1) - t(i0, j1), t(i0, j1));  c = fma(fy, bottom - top, top)
+ *   So every index is in range for every float input, a constant image returns its constant exactly (every difference is 0), a texel
+ *   centre returns its texel exactly where x and y are formed exactly (a power-of-two size), and c has period 1 in u and in v.
+ *
+ * The surface colour c(triangle, p) is (1, 1, 1) for a triangle without an image - it costs the first 16 bytes of its record - and
+ * colour(its image, uv(triangle, p)) otherwise.  The material at a vertex: brdf_eff = fl(brdf * c) and albedo_eff = fl(refract_albedo * c)
+ * per channel, formed first; every statement that reads brdf or refract_albedo of the vertex's triangle reads these instead, with p the
+ * vertex's point: the mirror's emissive term, its rate and its sky term, the f of a diffuse or SSS-diffuse vertex and its indirect rate.
+ * NOT touched: emissive and its two thresholds, refract_rate, refract_index, the modes, the emitter table and its power, and every draw.
+ * A texture multiplies radiance: it changes no ray, no draw and no jade_stats counter.  An image of ones is the untextured render bit for
+ * bit, a constant image the render with fl(brdf * c) and fl(refract_albedo * c) written into the materials.
+ * The denoiser's guide pass multiplies its throughput and its albedo guide by brdf_eff, at every vertex of its mirror chain.
+ *
+ * A textured render runs the kernels and the schedule of a smooth render (above), with the handle's vertex normals or, where it carries
+ * none, the flat ones: no fused first pass, no k_tail.  Results do not depend on steps, tile partitions, the walk or the records per pixel.
+ * Adaptive sampling, the guides and the denoiser, exposure and glare run on top.  jade_render_begin takes a table that names an image with
+ * the three environment samplings, with JADE_BOUNCE_COSINE and with a lens (not both), with vertex normals and without, and refuses it
+ * with JADE_ERR_UNSUPPORTED together with a shutter, JADE_LIGHTS_ONE, JADE_DIRECT_MIS, passes or JADE_BRANCH_STRATIFIED, after the other
+ * modes' own refusals and in smooth shading's words.  jade_render_multi: every scene's handle carries such a table or none does, else
+ * JADE_ERR_INVALID.  The oracle backend has no such entry.
+ * Not here: mip maps or any filtering by footprint (a minified image aliases, and the samples of a pixel average it); textures on
+ * emissive, refract_rate or the normal. */
+typedef struct jade_texture_image {
+  int32_t width, height;
+  const float* rgb; /* width * height * 3 floats */
+} jade_texture_image;
+int jade_scene_set_textures(jade_scene* scene, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of,
+                            int32_t n_triangles);
+int jade_scene_get_textures(jade_scene* scene, int* set);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,35 @@ int jadeh_write_proc_obj(const char* kind, int param, unsigned seed, const char*
 int jadeh_builder_set_smoothing(jadeh_builder* b, float crease_deg);
 int jadeh_vertex_normals(const float* verts, int nv, const int* idx, int nt, float crease_deg, float* out9);
 int jadeh_scene_vertex_normals(const jadeh_scene* s, const float** out);
+
+/* Albedo textures (include/jade_bvh.h, jade_scene_set_textures).  A jadeh_texture is an image of linear RGB, row 0 at v = 0 (the top of
+ * an image file): jadeh_texture_load reads a P6 file of 8 bits per channel (sRGB decoded in double, rounded once) or a PF file (linear;
+ * its rows, stored bottom to top, are flipped) by the file's own magic; jadeh_texture_checker makes size x size texels in squares x
+ * squares squares of colours a and b; jadeh_texture_data copies a caller's width x height x 3 floats.  NULL on failure.
+ * jadeh_builder_set_texture: the meshes added from now on carry the image (NULL: none, the default), with their own UVs - a quad's, those
+ * jadeh_builder_add_mesh_uv or an OBJ's `vt` lines give - or, where they have none, those of `projection`: 0 1 2 planar along x y z,
+ * 3 spherical (jadeh_project_uvs: the same function on a caller's mesh, 6 floats per triangle into out6).  While a texture is set,
+ * jadeh_builder_add_obj reads its file with the `v` / `vt` / `f a/b[/c]` reader; without one it reads as it always did.
+ * jadeh_load_obj_textured: that reader by itself - counts first (NULL arrays), then the arrays: verts 3 per vertex, idx 3 per triangle,
+ * uv6 6 per triangle (*has_uv = 0 and zeros if the file has no `vt` line).
+ * jadeh_scene_textures: the built scene's table in BVH order - *uv 6 floats and *image_of one number per triangle (owned by s) - and
+ * the number of images, 0 if no mesh was textured; jadeh_scene_texture: image k of it (*rgb owned by s). */
+typedef struct jadeh_texture jadeh_texture;
+jadeh_texture* jadeh_texture_load(const char* path);
+jadeh_texture* jadeh_texture_checker(int size, int squares, const float a[3], const float b[3]);
+jadeh_texture* jadeh_texture_data(int width, int height, const float* rgb);
+void jadeh_texture_free(jadeh_texture* t);
+int jadeh_texture_get(const jadeh_texture* t, int* width, int* height, const float** rgb);
+int jadeh_builder_set_texture(jadeh_builder* b, const jadeh_texture* t, int projection);
+/* ... and the texture of the object'th mesh to be added (0-based, in the order of the add calls, a configuration's included), whatever
+ * jadeh_builder_set_texture says when it arrives: one object of a configuration the caller does not build itself. */
+int jadeh_builder_set_object_texture(jadeh_builder* b, int object, const jadeh_texture* t, int projection);
+int jadeh_builder_add_mesh_uv(jadeh_builder* b, const float* verts, int nv, const int* idx, int nt, const float* uv6, const jadeh_material* mat,
+                              const float* trans16, int normalize);
+int jadeh_project_uvs(const float* verts, int nv, const int* idx, int nt, int projection, float* out6);
+int jadeh_load_obj_textured(const char* path, int* nv, int* nt, int* has_uv, float* verts, int* idx, float* uv6);
+int jadeh_scene_textures(const jadeh_scene* s, const float** uv, const int32_t** image_of);
+int jadeh_scene_texture(const jadeh_scene* s, int k, int* width, int* height, const float** rgb);
 int jadeh_builder_set_env_constant(jadeh_builder* b, float r, float g, float bl);
 int jadeh_builder_set_env_sky(jadeh_builder* b, int w, int h);
 int jadeh_builder_set_env_data(jadeh_builder* b, int w, int h, const float* rgb);

@@ -136,6 +136,10 @@ class ShutterParams(C.Structure):  # == jade_shutter_params, include/jade_bvh.h
     _fields_ = [("eye_close", f3), ("camera_close", C.c_float * 16), ("t_open", C.c_float), ("t_close", C.c_float)]
 
 
+class TextureImage(C.Structure):  # == jade_texture_image, include/jade_bvh.h
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgb", C.POINTER(C.c_float))]
+
+
 class Material(C.Structure):  # == Material, PathTrace.cu:293-301
     _fields_ = [
         ("emissive", f3), ("brdf", f3),
@@ -230,6 +234,9 @@ BVH_SYMBOLS = {
     # the vertex normals of a scene handle (scene, 9 floats per triangle or null, n_triangles) / (scene, out: 1 if a table is set)
     "jade_scene_set_vertex_normals": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "jade_scene_get_vertex_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # the textures of a scene handle (scene, n_images, images, 6 floats of uv per triangle, an image number per triangle, n_triangles) / (scene, out: 1 if set)
+    "jade_scene_set_textures": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(TextureImage), C.c_void_p, C.c_void_p, C.c_int32]),
+    "jade_scene_get_textures": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {
@@ -246,6 +253,19 @@ HOST_SYMBOLS = {
     "jadeh_builder_set_smoothing": (C.c_int, [C.c_void_p, C.c_float]),
     "jadeh_vertex_normals": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "jadeh_scene_vertex_normals": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    # textures: images (load / checker / data -> handle), the builder's current texture, UVs, the built scene's table
+    "jadeh_texture_load": (C.c_void_p, [C.c_char_p]),
+    "jadeh_texture_checker": (C.c_void_p, [C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "jadeh_texture_data": (C.c_void_p, [C.c_int, C.c_int, C.c_void_p]),
+    "jadeh_texture_free": (None, [C.c_void_p]),
+    "jadeh_texture_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    "jadeh_builder_set_texture": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "jadeh_builder_set_object_texture": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "jadeh_builder_add_mesh_uv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Material), C.c_void_p, C.c_int]),
+    "jadeh_project_uvs": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "jadeh_load_obj_textured": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "jadeh_scene_textures": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "jadeh_scene_texture": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "jadeh_builder_set_env_constant": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float]),
     "jadeh_builder_set_env_sky": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jadeh_builder_set_env_data": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

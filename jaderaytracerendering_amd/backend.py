@@ -235,6 +235,12 @@ class Scene:
             except Exception:
                 self.close()
                 raise
+        if getattr(host_scene, "textures", None) is not None:  # ... and the same for its textures: (images, uv, image_of)
+            try:
+                self.set_textures(*host_scene.textures)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -501,6 +507,35 @@ class Scene:
     def vertex_normals_set(self):
         """jade_scene_get_vertex_normals: whether the handle carries a table."""
         fn = self._hip_only("jade_scene_get_vertex_normals")
+        on = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_textures(self, images, uv=None, image_of=None):
+        """jade_scene_set_textures: images - a list of float32 [height, width, 3] arrays of linear RGB, row 0 at v = 0; uv - float32
+        [n_triangles, 3, 2], the (u, v) of the corners p1 p2 p3, triangles in the scene's order; image_of - int32 [n_triangles], each
+        triangle's image or -1 for none.  None (or no images) clears.  The next render this handle begins multiplies the image, filtered
+        at every path vertex, into the triangle's brdf and refract_albedo (HIP module only; include/jade_bvh.h, "The surface colour,
+        stated"); a table in which no triangle names an image is today's render bit for bit."""
+        fn = self._hip_only("jade_scene_set_textures")
+        if images is None or len(images) == 0:
+            self.backend.check(fn(self._h, 0, None, None, None, 0))
+            return
+        imgs = [np.ascontiguousarray(im, np.float32) for im in images]
+        for k, im in enumerate(imgs):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise JadeError(_abi.JADE_ERR_INVALID, f"textures: image {k} is not [height, width, 3]")
+        arr = (_abi.TextureImage * len(imgs))(*[_abi.TextureImage(im.shape[1], im.shape[0], C.cast(im.ctypes.data, C.POINTER(C.c_float))) for im in imgs])
+        u = np.ascontiguousarray(uv, np.float32)
+        io = np.ascontiguousarray(image_of, np.int32).reshape(-1)
+        if u.size != 6 * io.size:
+            raise JadeError(_abi.JADE_ERR_INVALID, "textures: 6 floats of uv and one image number per triangle")
+        self.backend.check(fn(self._h, len(imgs), arr, u.ctypes.data, io.ctypes.data, io.size))
+
+    @property
+    def textures(self):
+        """jade_scene_get_textures: whether the handle carries a texture table."""
+        fn = self._hip_only("jade_scene_get_textures")
         on = C.c_int(-1)
         self.backend.check(fn(self._h, C.byref(on)))
         return bool(on.value)

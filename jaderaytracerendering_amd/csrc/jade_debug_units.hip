@@ -337,6 +337,21 @@ __global__ void k_debug_shading_normal(int n, const float4* table, const float* 
   out_rule[i] = rule;
 }
 
+// the texture pieces (jade_texture.h) on row i: uv(tri[i], p[i]); colour(image[i], uv[i]); the surface colour c(tri[i], p[i]).  The host checks every index.
+__global__ void k_debug_surface_uv(int n, const float4* rec, const int32_t* tri, const float* p, float* out_uv) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  surface_uv(rec, tri[i], V3(p + (size_t)3 * i), out_uv + (size_t)2 * i, out_uv + (size_t)2 * i + 1);
+}
+__global__ void k_debug_texture_fetch(int n, const float4* texels, const uint4* images, const int32_t* image, const float* uv, float* out_rgb) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) put3(out_rgb, i, texture_fetch(texels, images, image[i], uv[(size_t)2 * i], uv[(size_t)2 * i + 1]));
+}
+__global__ void k_debug_surface_colour(int n, TexTables T, const int32_t* tri, const float* p, float* out_rgb) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) put3(out_rgb, i, surface_colour(T, tri[i], V3(p + (size_t)3 * i)));
+}
+
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
 
 static hipError_t upload0(DevBuf& b, const void* src, size_t elems) {  // on the null stream: these entry points have no scene
@@ -876,6 +891,89 @@ int jade_debug_shading_normal(int device_id, int32_t n, const float* rows, float
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(out_n, bn.p, 12 * N, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_rule, br.p, 4 * N, hipMemcpyDeviceToHost));
+  return JADE_OK;
+}
+
+// ... and with whether the handle carries textures in which a triangle names an image (jade_scene_set_textures; tests/test_texture_modes_cpu.py).
+int jade_debug_shade_mode_textures_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                        int32_t passes, int32_t branch_sampling, int32_t smooth, int32_t textures, uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (branch_sampling != JADE_BRANCH_RANDOM && branch_sampling != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0,
+                                    branch_sampling == JADE_BRANCH_STRATIFIED, smooth != 0, textures != 0))
+    return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
+// The pieces of "The surface colour, stated" (include/jade_bvh.h; jade_texture.h) on n rows, with the table the handle carries as
+// jade_scene_set_textures left it (no render is begun; tests/test_gpu_texture.py):
+//   jade_debug_surface_uv:      out_uv[i] = uv(tri[i], points[i])
+//   jade_debug_texture_fetch:   out_rgb[i] = colour(image[i], uv[i])
+//   jade_debug_surface_colour:  out_rgb[i] = c(tri[i], points[i]), (1, 1, 1) for a triangle without an image
+struct DebugTextures {
+  DevBuf rec, texels, images;
+  TexTables T{};
+};
+static int debug_textures(jade_scene* s, int32_t n, const int32_t* index, int32_t index_lo, size_t index_n, DebugTextures* d) {
+  if (n <= 0 || n > kDebugMaxRows / 4) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (s->tex_rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no textures (jade_scene_set_textures)");
+  for (int32_t i = 0; i < n; ++i)
+    if (index[i] < index_lo || (size_t)index[i] >= index_n) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": index out of range");
+  HIP_TRY(hipSetDevice(s->device));
+  HIP_TRY(upload(d->rec, s->tex_rec.data(), s->tex_rec.size(), s->stream));
+  HIP_TRY(upload(d->texels, s->tex_texels.data(), s->tex_texels.size(), s->stream));
+  HIP_TRY(upload(d->images, s->tex_images.data(), s->tex_images.size(), s->stream));
+  d->T = TexTables{nullptr, d->rec.as<float4>(), d->texels.as<float4>(), d->images.as<uint4>()};
+  return JADE_OK;
+}
+int jade_debug_surface_uv(jade_scene* s, int32_t n, const int32_t* tri, const float* points, float* out_uv) {
+  if (!s || !tri || !points || !out_uv) return jade_fail(JADE_ERR_INVALID, "null argument");
+  DebugTextures d;
+  if (const int rc = debug_textures(s, n, tri, 0, s->tex_rec.size() / JADE_TEX_REC, &d)) return rc;
+  const size_t N = (size_t)n;
+  DevBuf bt, bp, bo;
+  HIP_TRY(upload(bt, tri, N, s->stream));
+  HIP_TRY(upload(bp, points, 3 * N, s->stream));
+  HIP_TRY(bo.alloc(8 * N));
+  hipLaunchKernelGGL(k_debug_surface_uv, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d.T.rec, bt.as<int32_t>(), bp.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_uv, bo.p, 8 * N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+int jade_debug_texture_fetch(jade_scene* s, int32_t n, const int32_t* image, const float* uv, float* out_rgb) {
+  if (!s || !image || !uv || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
+  DebugTextures d;
+  if (const int rc = debug_textures(s, n, image, 0, s->tex_images.size(), &d)) return rc;
+  const size_t N = (size_t)n;
+  DevBuf bi, bu, bo;
+  HIP_TRY(upload(bi, image, N, s->stream));
+  HIP_TRY(upload(bu, uv, 2 * N, s->stream));
+  HIP_TRY(bo.alloc(12 * N));
+  hipLaunchKernelGGL(k_debug_texture_fetch, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d.T.texels, d.T.images, bi.as<int32_t>(), bu.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_rgb, bo.p, 12 * N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+int jade_debug_surface_colour(jade_scene* s, int32_t n, const int32_t* tri, const float* points, float* out_rgb) {
+  if (!s || !tri || !points || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
+  DebugTextures d;
+  if (const int rc = debug_textures(s, n, tri, 0, s->tex_rec.size() / JADE_TEX_REC, &d)) return rc;
+  const size_t N = (size_t)n;
+  DevBuf bt, bp, bo;
+  HIP_TRY(upload(bt, tri, N, s->stream));
+  HIP_TRY(upload(bp, points, 3 * N, s->stream));
+  HIP_TRY(bo.alloc(12 * N));
+  hipLaunchKernelGGL(k_debug_surface_colour, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d.T, bt.as<int32_t>(), bp.as<float>(), bo.as<float>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_rgb, bo.p, 12 * N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }
 

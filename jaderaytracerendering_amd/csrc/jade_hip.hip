@@ -178,6 +178,8 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // branch_number, jade_shade.h), formed here from the record's `done` and home pixel.  Nothing of it travels with the record.
 // SM_SMOOTH: the normal of every vertex shaded is the triangle's vertex normals interpolated at the vertex ("The shading normal, stated"), from the records
 // A.smooth() (jade_smooth_shade.h), where the bounce and the fold stand a second time with it.  Nothing of it travels with the record.
+// SM_TEX (with SM_SMOOTH): A.smooth() carries the texture tables as well (jade_texture.h) and the same family multiplies the surface colour at (c.obj, c.src)
+// into every brdf and refract_albedo it reads ("The surface colour, stated"); the lean kernel's mirror fold is consume_mirror_textured.
 template <bool LEAN, uint32_t M = 0>
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
@@ -269,6 +271,7 @@ static __device__ __forceinline__ void shade_record(const DevScene& S, const Pat
     } else if (on_path) {
       int r;
       if constexpr (SMOOTH && !LEAN) r = consume_smooth<M>(S, px, c, &l_final, A.smooth());
+      else if constexpr (sm(M, SM_TEX)) r = consume_mirror_textured(S, px, c, &l_final, A.smooth());
       else r = LEAN ? consume_mirror<Px, M>(S, px, c, &l_final, &parts) : consume<M>(S, px, c, &l_final, A.lights(), light, A.mis(), &parts);
       if (PASSES) pass_fold(*A.L(), p, pmask, parts, c.thr, r == CONSUME_END, r == CONSUME_ZERO);
       if (r == CONSUME_VERTEX) {
@@ -1549,6 +1552,71 @@ int jade_scene_get_vertex_normals(jade_scene* s, int* set) {
   return JADE_OK;
 }
 
+// The textures of the scene handle (include/jade_bvh.h, "The surface colour, stated"): the records and the texel buffer (jade_texture.h) are made
+// here, from the triangles as the handle holds them, and uploaded by the next jade_render_begin - a render in progress keeps the table it began
+// with.  Everything is checked before anything of the handle changes: a refused call leaves the table that was there.
+int jade_scene_set_textures(jade_scene* s, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of, int32_t n_triangles) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n_images == 0 || !images || !uv || !image_of) {
+    for (auto* v : {&s->tex_rec, &s->tex_texels}) {
+      v->clear();
+      v->shrink_to_fit();
+    }
+    s->tex_images.clear();
+    s->tex_any = false;
+    s->tex_uploaded = false;
+    return JADE_OK;
+  }
+  if (n_images < 0 || n_images > JADE_TEX_MAX_IMAGES)
+    return jade_fail(JADE_ERR_INVALID, "textures: " + std::to_string(n_images) + " images (at most " + std::to_string(JADE_TEX_MAX_IMAGES) + ")");
+  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "textures: the triangle count " + std::to_string(n_triangles) + " is not the scene's");
+  std::vector<uint4> heads((size_t)n_images);
+  size_t total = 0;
+  for (int32_t k = 0; k < n_images; ++k) {
+    const jade_texture_image& im = images[k];
+    if (im.width < 1 || im.width > JADE_TEX_MAX_SIZE || im.height < 1 || im.height > JADE_TEX_MAX_SIZE)
+      return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " is " + std::to_string(im.width) + " x " + std::to_string(im.height) +
+                                             " (a width and a height of 1 .. " + std::to_string(JADE_TEX_MAX_SIZE) + ")");
+    if (!im.rgb) return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " has no texels");
+    heads[k] = make_uint4((uint32_t)(total & 0xffffffffu), (uint32_t)(total >> 32), (uint32_t)im.width, (uint32_t)im.height);
+    total += (size_t)im.width * (size_t)im.height;
+  }
+  bool any = false;
+  for (int32_t t = 0; t < n_triangles; ++t) {
+    if (image_of[t] < -1 || image_of[t] >= n_images)
+      return jade_fail(JADE_ERR_INVALID, "textures: image_of[" + std::to_string(t) + "] = " + std::to_string(image_of[t]) + " is outside -1 .. " + std::to_string(n_images - 1));
+    any = any || image_of[t] >= 0;
+  }
+  std::vector<float4> texels(total);
+  for (int32_t k = 0; k < n_images; ++k) {
+    const size_t first = ((size_t)heads[k].y << 32) | heads[k].x, n = (size_t)heads[k].z * heads[k].w;
+    const float* rgb = images[k].rgb;
+    for (size_t i = 0; i < n; ++i) {
+      if (!std::isfinite(rgb[3 * i]) || !std::isfinite(rgb[3 * i + 1]) || !std::isfinite(rgb[3 * i + 2]))
+        return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " has a texel that is not finite at (" + std::to_string(i % heads[k].z) + ", " +
+                                               std::to_string(i / heads[k].z) + ")");
+      texels[first + i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
+    }
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  std::vector<jade_triangle> tris((size_t)n_triangles);
+  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  std::vector<float4> rec(tris.size() * JADE_TEX_REC);
+  for (size_t i = 0; i < tris.size(); ++i) texture_record(tris[i].p1, tris[i].p2, tris[i].p3, uv + 6 * i, image_of[i], &rec[i * JADE_TEX_REC]);
+  s->tex_rec.swap(rec);
+  s->tex_texels.swap(texels);
+  s->tex_images.swap(heads);
+  s->tex_any = any;
+  s->tex_uploaded = false;
+  return JADE_OK;
+}
+int jade_scene_get_textures(jade_scene* s, int* set) {
+  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *set = s->tex_rec.empty() ? 0 : 1;
+  return JADE_OK;
+}
+
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -1642,16 +1710,29 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any))
+                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any, s->tex_any))
     return jade_fail(rc, why);
   if ((mode & SM_PASSES) && s->tun.pixel_rotate)
     return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
   HIP_TRY(hipSetDevice(s->device));
-  if ((mode & SM_SMOOTH) && !s->smooth_uploaded) {  // the handle's table as it is now: the render keeps it whatever the setter is told before the next begin
+  if ((mode & SM_TEX) && !s->tex_uploaded) {  // the same rule for the textures
+    s->have_rp = false;
+    HIP_TRY(upload(s->b_tex_rec, s->tex_rec.data(), s->tex_rec.size(), s->stream));
+    HIP_TRY(upload(s->b_tex_texels, s->tex_texels.data(), s->tex_texels.size(), s->stream));
+    HIP_TRY(upload(s->b_tex_images, s->tex_images.data(), s->tex_images.size(), s->stream));
+    if (!s->b_tex_flat.p) {
+      const size_t bytes = sizeof(float4) * JADE_SMOOTH_REC * (size_t)s->dev.n_tris;
+      HIP_TRY(s->b_tex_flat.alloc(bytes));
+      HIP_TRY(hipMemsetAsync(s->b_tex_flat.p, 0, bytes, s->stream));
+    }
+    s->tex_uploaded = true;
+  }
+  if ((mode & SM_SMOOTH) && s->smooth_any && !s->smooth_uploaded) {  // the handle's table as it is now: the render keeps it whatever the setter is told before the next begin
     s->have_rp = false;  // (the earlier render's kernels would read the buffer that is given back here)
     HIP_TRY(upload(s->b_smooth, s->smooth_rec.data(), s->smooth_rec.size(), s->stream));
     s->smooth_uploaded = true;
   }
+  if (mode & SM_TEX) s->tex_normals = (s->smooth_any ? s->b_smooth : s->b_tex_flat).as<float4>();  // the handle's vertex normals, or the all-flat table where it carries none
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
   for (int y = 0; y < ty; ++y)
@@ -1789,7 +1870,9 @@ static ShadeArgs<K> mode_args(const jade_scene* s) {
   if constexpr (sm(K, SM_SHUTTER)) a.shutter = s->sh;
   if constexpr ((K & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0) a.light_table = s->b_light_alias.as<uint4>();
   if constexpr (sm(K, SM_MIS)) a.mis_table = s->b_mis.as<float2>();
-  if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = s->b_smooth.as<float4>();
+  if constexpr (sm(K, SM_TEX))
+    a.tex_tables = texture_tables(s);
+  else if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = s->b_smooth.as<float4>();
   return a;
 }
 template <uint32_t M>
@@ -1808,7 +1891,7 @@ static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, con
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
-  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH | SM_SMOOTH);  // (the camera arm, the passes, the mirror's shared-out roulette and its shading normal are all of a mode the lean kernel carries)
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH | SM_SMOOTH | SM_TEX);  // (the camera arm, the passes, the mirror's shared-out roulette, its shading normal and its colour are all of a mode the lean kernel carries)
   auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
                        s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), a...);

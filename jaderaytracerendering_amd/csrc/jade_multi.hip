@@ -144,6 +144,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->smooth_any != scenes[0]->smooth_any)
       return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry vertex normals (jade_scene_set_vertex_normals): scene " + std::to_string(i) + " against scene 0");
+  // ... and the same for textures (jade_scene_set_textures, a table in which a triangle names an image)
+  for (int i = 1; i < ndev; ++i)
+    if (scenes[i]->tex_any != scenes[0]->tex_any)
+      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry textures (jade_scene_set_textures): scene " + std::to_string(i) + " against scene 0");
   // ... and none keeps passes: only the frame is gathered here (each rank renders its share and calls jade_render_passes)
   for (int i = 0; i < ndev; ++i)
     if (scenes[i]->passes)

@@ -11,6 +11,7 @@
 
 #include "jade_bvh.h"
 #include "jade_device.h"
+#include "jade_texture.h"
 
 #define JADE_HIDDEN __attribute__((visibility("hidden")))
 
@@ -213,6 +214,7 @@ enum ShadeMode : uint32_t {
   SM_PASSES = 128u,  // jade_scene_set_passes: the frame's radiance kept split into the light passes as well (include/jade_bvh.h, "The passes, stated")
   SM_BRANCH = 256u,  // jade_scene_set_branch_sampling = JADE_BRANCH_STRATIFIED: the branch draws of a path's first two vertices shared out (include/jade_bvh.h, "The branch draws, stated")
   SM_SMOOTH = 512u,  // jade_scene_set_vertex_normals with at least one triangle that is not flat: the vertex normals interpolated at every path vertex (include/jade_bvh.h, "The shading normal, stated")
+  SM_TEX = 1024u,    // jade_scene_set_textures with at least one triangle that names an image: the image filtered at every path vertex (include/jade_bvh.h, "The surface colour, stated").  Raised together with SM_SMOOTH, whose family it runs
 };
 // How the device code reads a mode: whether mask M carries bit b.  The shade kernels and every function they are made of (jade_shade.h,
 // jade_hip.hip) are templates over the one mask and ask by name - sm(M, SM_COSINE) - so no flag has a position to be wrong in.
@@ -224,7 +226,7 @@ static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 
   JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS) \
-  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS) JADE_SHADE_MODES_BRANCH(X) JADE_SHADE_MODES_SMOOTH(X)
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS) JADE_SHADE_MODES_BRANCH(X) JADE_SHADE_MODES_SMOOTH(X) JADE_SHADE_MODES_TEX(X)
 // ... its rows under SM_BRANCH: the pinhole with all lights - the reference estimator, the cosine bounce, MIS - and the passes on the reference estimator
 #define JADE_SHADE_MODES_BRANCH(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE | SM_MIS) \
@@ -232,6 +234,9 @@ static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 
 // ... and under SM_SMOOTH: the reference estimator, the cosine bounce, the lens - all lights, no shutter, no MIS, no passes, the stream's branch draws
 #define JADE_SHADE_MODES_SMOOTH(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_SMOOTH) JADE_SHADE_MODE_BOTH_ENV(X, SM_SMOOTH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_SMOOTH | SM_LENS)
+// ... and the same three rows with textures: a textured render runs the smooth family whether the handle carries vertex normals or not
+#define JADE_SHADE_MODES_TEX(X) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH) JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH | SM_LENS)
 #define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS) X((m) | SM_ENVIS | SM_ENVMIX)
 static inline bool shade_mode_built(uint32_t mode) {
 #define JADE_X(m) if (mode == (m)) return true;
@@ -249,33 +254,34 @@ static inline bool shade_mode_built(uint32_t mode) {
 // the reference estimator; its refusals come last, after everybody else's, whose texts stay.
 // smooth: jade_scene_set_vertex_normals with a table that is not flat everywhere.  Its kernels are built for the reference estimator and the cosine
 // bounce through the pinhole and for the reference estimator through a lens; its refusals come after all of the above, whose texts stay.
+// textures: jade_scene_set_textures with a table in which a triangle names an image.  They run the smooth family (SM_SMOOTH is raised with SM_TEX,
+// whether the handle carries vertex normals or not) and are refused where it is, in its words.
 static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
-                                 std::string* why, bool passes = false, bool branch = false, bool smooth = false) {
+                                 std::string* why, bool passes = false, bool branch = false, bool smooth = false, bool textures = false) {
   const uint32_t m = (env_sampling == JADE_ENV_IMPORTANCE ? SM_ENVIS : env_sampling == JADE_ENV_MIXTURE ? SM_ENVIS | SM_ENVMIX : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
                      (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u) | (passes ? SM_PASSES : 0u) |
-                     (branch ? SM_BRANCH : 0u) | (smooth ? SM_SMOOTH : 0u);
+                     (branch ? SM_BRANCH : 0u) | (smooth || textures ? SM_SMOOTH : 0u) | (textures ? SM_TEX : 0u);
   if (shade_mode_built(m)) {
     *mode = m;
     return JADE_OK;
   }
-  // smooth shading's own refusals: only where the same settings without the table are accepted - otherwise the refusal a caller reads is the one
-  // they would read without it, in the same words
-  if ((m & SM_SMOOTH) && shade_mode_built(m & ~(uint32_t)SM_SMOOTH)) {
+  // smooth shading's and the textures' own refusals: only where the same settings without the table are accepted - otherwise the refusal a caller
+  // reads is the one they would read without it, in the same words.  With both tables on the handle the words are smooth shading's.
+  if ((m & SM_SMOOTH) && shade_mode_built(m & ~(uint32_t)(SM_SMOOTH | SM_TEX))) {
+    const std::string who = smooth ? "smooth shading (jade_scene_set_vertex_normals) does not run " : "textures (jade_scene_set_textures) do not run ";
+    const char* built = " yet: those kernels are not built";
     if (m & SM_SHUTTER)
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run together with a shutter (jade_scene_set_shutter) yet: those kernels are not built";
+      *why = who + "together with a shutter (jade_scene_set_shutter)" + built;
     else if (m & SM_LIGHTS)
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run together with light sampling JADE_LIGHTS_ONE (jade_scene_set_light_sampling) yet: "
-             "those kernels are not built";
+      *why = who + "together with light sampling JADE_LIGHTS_ONE (jade_scene_set_light_sampling)" + built;
     else if (m & SM_MIS)
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run together with direct sampling JADE_DIRECT_MIS (jade_scene_set_direct_sampling) yet: "
-             "those kernels are not built";
+      *why = who + "together with direct sampling JADE_DIRECT_MIS (jade_scene_set_direct_sampling)" + built;
     else if (m & SM_PASSES)
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run together with passes (jade_scene_set_passes) yet: those kernels are not built";
+      *why = who + "together with passes (jade_scene_set_passes)" + built;
     else if (m & SM_BRANCH)
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run together with branch sampling JADE_BRANCH_STRATIFIED (jade_scene_set_branch_sampling) yet: "
-             "those kernels are not built";
+      *why = who + "together with branch sampling JADE_BRANCH_STRATIFIED (jade_scene_set_branch_sampling)" + built;
     else
-      *why = "smooth shading (jade_scene_set_vertex_normals) does not run with this combination of render modes yet: those kernels are not built";
+      *why = who + "with this combination of render modes" + built;
     return JADE_ERR_UNSUPPORTED;
   }
   const std::string camera = std::string(lens ? "a lens (jade_scene_set_lens)" : "a shutter (jade_scene_set_shutter)") + " yet: those kernels are not built";
@@ -327,6 +333,14 @@ struct jade_scene {
   std::vector<float4> smooth_rec;
   bool smooth_any = false, smooth_uploaded = false;
   DevBuf b_smooth;
+  // jade_scene_set_textures: the records and the images as jade_texture.h lays them out (empty: none set), whether any triangle names an image, and
+  // whether the device buffers hold them already (the next jade_render_begin uploads them once).  b_tex_flat: the all-flat vertex-normal table a
+  // textured render reads where the handle carries none (zeros: SMOOTH_FLAT)
+  std::vector<float4> tex_rec, tex_texels;
+  std::vector<uint4> tex_images;
+  bool tex_any = false, tex_uploaded = false;
+  DevBuf b_tex_rec, b_tex_texels, b_tex_images, b_tex_flat;
+  const float4* tex_normals = nullptr;  // ... and the vertex-normal table the textured render in progress began with: b_smooth or b_tex_flat
   // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
   // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
   uint32_t mode = 0;
@@ -403,6 +417,12 @@ static inline bool passes_on(const jade_scene* s) { return (s->mode & SM_PASSES)
 static inline bool branch_on(const jade_scene* s) { return (s->mode & SM_BRANCH) != 0; }
 // ... the vertex normals are interpolated: the list schedule once more - k_light, k_light_packet and k_tail shade with the flat normal
 static inline bool smooth_on(const jade_scene* s) { return (s->mode & SM_SMOOTH) != 0; }
+// ... the textures are read: a smooth render (smooth_on is true as well) whose kernels take the texture tables beside the vertex normals
+static inline bool textures_on(const jade_scene* s) { return (s->mode & SM_TEX) != 0; }
+// ... and what its kernels take (jade_texture.h): the tables as jade_render_begin left them
+static inline TexTables texture_tables(const jade_scene* s) {
+  return TexTables{s->tex_normals, s->b_tex_rec.as<float4>(), s->b_tex_texels.as<float4>(), s->b_tex_images.as<uint4>()};
+}
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
 struct ScenePrep {

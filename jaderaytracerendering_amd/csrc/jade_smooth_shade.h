@@ -2,18 +2,23 @@
 // stated"): bounce_branch, bounce_mirror, begin_bounce_lean and consume (jade_shade.h) are every other kernel's, k_light's and k_tail's among
 // them, and an argument more on them moves those kernels' registers.  The texts below carry the bits a smooth mode is built with (SM_ENVIS,
 // SM_ENVMIX, SM_COSINE) and no other; shade_record (jade_hip.hip) calls them in the kernels of a mode with SM_SMOOTH.
+// A textured mode (SM_TEX, raised with SM_SMOOTH; jade_texture.h; "The surface colour, stated") runs these texts too: `table` is then a TexTables -
+// the vertex normals together with the texture tables - in place of the `const float4*`, and the four places that read the vertex's brdf or
+// refract_albedo read them times the surface colour at the vertex, each under `if constexpr (has_textures<ST>)`: in the other modes no instruction moves.
 #pragma once
 #include "jade_shade.h"
 #include "jade_smooth.h"
+#include "jade_texture.h"
 
 // bounce_mirror with the vertex's shading normal n; g: its flat normal.  A reflected direction that does not leave on the side of g that
 // `out` is on is formed again with g.
-template <class PX>
-static __device__ __forceinline__ bool bounce_mirror_smooth(PX& px, ShadeCtx& c, const DevMaterial* ot, jvec3 obj_emissive, jvec3 n, jvec3 g, jvec3* l_final) {
+template <class PX, class ST = const float4*>
+static __device__ __forceinline__ bool bounce_mirror_smooth(PX& px, ShadeCtx& c, const DevMaterial* ot, jvec3 obj_emissive, jvec3 n, jvec3 g, jvec3* l_final, ST table = ST()) {
   const float RR_F = (float)JADE_RR_RATE_D;
   jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
   int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
   if (obj_emissive.x > 1.5e-4f || obj_emissive.y > 1.5e-4f || obj_emissive.x > 1.5e-4f) {
+    if constexpr (has_textures<ST>) obj_hit_fr = jv_scale(textured(table, c.obj, c.src, V3(ot->brdf)), (float)(1.0 / JADE_PI_D));  // (the one term of this step that reads the brdf)
     *l_final = jv_scale(jv_mul(obj_emissive, obj_hit_fr), (float)k);
     return false;
   }
@@ -30,8 +35,8 @@ static __device__ __forceinline__ bool bounce_mirror_smooth(PX& px, ShadeCtx& c,
   return true;
 }
 // begin_bounce_lean with the shading normal
-template <class PX>
-static __device__ bool begin_bounce_lean_smooth(const DevScene& S, PX& px, ShadeCtx& c, jvec3* l_final, const float4* table) {
+template <class PX, class ST>
+static __device__ bool begin_bounce_lean_smooth(const DevScene& S, PX& px, ShadeCtx& c, jvec3* l_final, ST table) {
   const ShadeTri ots = shade_tri(S, c.obj);
   const DevMaterial* ot = ots.m;
   c.c_shaded += 1;
@@ -42,7 +47,7 @@ static __device__ bool begin_bounce_lean_smooth(const DevScene& S, PX& px, Shade
   }
   *l_final = jv(0, 0, 0);
   (void)jade_rand(&c.rng);  // select_reflex_refract: drawn for every material, decides nothing for a pure mirror
-  return bounce_mirror_smooth(px, c, ot, obj_emissive, shading_normal(table, c.obj, ots.norm, c.src, c.out), ots.norm, l_final);
+  return bounce_mirror_smooth(px, c, ot, obj_emissive, shading_normal(table, c.obj, ots.norm, c.src, c.out), ots.norm, l_final, table);
 }
 
 // bounce_branch with the shading normal: n at (c.obj, c.src) for c.out, t_norm at the BSSRDF exit for inner_direction.  Every side test, flip
@@ -50,8 +55,8 @@ static __device__ bool begin_bounce_lean_smooth(const DevScene& S, PX& px, Shade
 // is not traced: an emitter ray as the reference's `continue`, the environment ray as STF_NOENV, the indirect ray as a roulette that
 // failed.  All draws are the flat render's, in its order.  The refraction entry's direction and Fresnel factor are formed again with the
 // flat normal where the direction does not cross the triangle.
-template <uint32_t M>
-static __device__ __forceinline__ bool bounce_branch_smooth(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const float4* table) {
+template <uint32_t M, class ST>
+static __device__ __forceinline__ bool bounce_branch_smooth(int type, const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, ST table) {
   constexpr bool ENVIS = sm(M, SM_ENVIS), COSINE = sm(M, SM_COSINE), ENVMIX = sm(M, SM_ENVMIX);
   const jade_triangle* T = S.tris;  // vertices only
   const ShadeTri ots = shade_tri(S, c.obj);
@@ -63,7 +68,7 @@ static __device__ __forceinline__ bool bounce_branch_smooth(int type, const DevS
   const jvec3 n = shading_normal(table, c.obj, g, c.src, c.out);
   *l_final = jv(0, 0, 0);
   if (type == BT_DIFFUSE) goto diffuse_like;
-  if (type == BT_MIRROR) return bounce_mirror_smooth(px, c, ot, V3(ot->emissive), n, g, l_final);
+  if (type == BT_MIRROR) return bounce_mirror_smooth(px, c, ot, V3(ot->emissive), n, g, l_final, table);
   if (type == BT_BSSRDF) {
     {
       int middle = S.mapping[exit_search(S, ot->obj_idx, jade_rand(&c.rng))];
@@ -240,8 +245,8 @@ diffuse_like:
     return true;
   }
 }
-template <uint32_t M>
-static __device__ bool begin_bounce_smooth(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const float4* table) {
+template <uint32_t M, class ST>
+static __device__ bool begin_bounce_smooth(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, ST table) {
   const int type = bounce_classify(S, c, l_final);
   if (type == BT_END) return false;
   return bounce_branch_smooth<M>(type, S, px, c, l_final, table);
@@ -250,8 +255,31 @@ static __device__ bool begin_bounce_smooth(const DevScene& S, const Px& px, Shad
 // consume with the shading normal: the vertex's again from (c.obj, c.src, c.out), the BSSRDF exit's from (the record's source triangle, its
 // origin, origin - c.src), a refraction hit's from (the triangle hit, the hit point, the reversed ray).  Nothing travels with the record.
 // An environment slot may hold "no ray" (-2) whatever the environment sampling is.  An emitter's own normal stays its flat one.
-template <uint32_t M>
-static __device__ int consume_smooth(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, const float4* table) {
+// consume_mirror (jade_shade.h) for a textured mode: its text again, with the vertex's brdf_eff - the colour at the vertex the mirror ray
+// left from, read before the path moves on.  No passes in these modes.
+template <class PX>
+static __device__ __forceinline__ int consume_mirror_textured(const DevScene& S, const PX& px, ShadeCtx& c, jvec3* l_final, const TexTables& table) {
+  const DevMaterial* ot = shade_tri(S, c.obj).m;
+  const int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
+  const jvec3 obj_hit_fr = jv_scale(textured(table, c.obj, px.origin(), V3(ot->brdf)), (float)(1.0 / JADE_PI_D));  // (the ray's origin IS the vertex's point - bounce_mirror_smooth stored c.src there - and a record in ST_MIRROR does not keep c.src)
+  float kk = (float)(k / (JADE_RR_RATE_D / JADE_PI_D));
+  jvec3 refl = px.dir(0);
+  int nh = px.hit(0);
+  if (nh >= 0) {
+    c.out = jv_neg(refl);
+    c.src = px.hpt(0);
+    c.obj = nh;
+    *l_final = jv(0, 0, 0);
+    return path_push(c, jv(0, 0, 0), jv_scale(obj_hit_fr, kk)) ? CONSUME_END : CONSUME_VERTEX;
+  }
+  *l_final = jv_scale(jv_mul(sample_hdr(S, refl), obj_hit_fr), kk);
+  return CONSUME_END;
+}
+
+// A textured mode (ST = TexTables, jade_texture.h): the ST_DIFFUSE fold's brdf and refract_albedo are the vertex's brdf_eff and albedo_eff,
+// and the mirror's fold is consume_mirror_textured.  The other stages read neither.
+template <uint32_t M, class ST>
+static __device__ int consume_smooth(const DevScene& S, const Px& px, ShadeCtx& c, jvec3* l_final, ST table) {
   constexpr bool ENVIS = sm(M, SM_ENVIS), COSINE = sm(M, SM_COSINE);
   const jade_triangle* T = S.tris;  // vertices only
   const int nE = S.n_emit;
@@ -261,13 +289,16 @@ static __device__ int consume_smooth(const DevScene& S, const Px& px, ShadeCtx& 
   const ShadeTri ots = shade_tri(S, c.obj);
   const DevMaterial* ot = ots.m;
   const int k = ot->refract_mode != JADE_NO_REFRACT ? 2 : 1;
-  const jvec3 obj_hit_fr = jv_scale(V3(ot->brdf), (float)(1.0 / JADE_PI_D));
+  jvec3 colour = jv(1.0f, 1.0f, 1.0f);  // (read by a textured mode alone)
+  if constexpr (has_textures<ST>)
+    if (c.stage == ST_DIFFUSE) colour = surface_colour(table, c.obj, c.src);
+  const jvec3 obj_hit_fr = jv_scale(tinted<ST>(V3(ot->brdf), colour), (float)(1.0 / JADE_PI_D));
   jvec3 l_dir = jv(0, 0, 0);
 
   if (c.stage == ST_DIFFUSE) {
     const jvec3 n = shading_normal(table, c.obj, ots.norm, c.src, c.out);
     const bool sss = (c.flags & STF_SSS) != 0;
-    const jvec3 f = sss ? jv_scale(V3(ot->refract_albedo), (float)(1.0 / JADE_PI_D)) : obj_hit_fr;
+    const jvec3 f = sss ? jv_scale(tinted<ST>(V3(ot->refract_albedo), colour), (float)(1.0 / JADE_PI_D)) : obj_hit_fr;
     for (int i = 0; i < nL; ++i) {
       int h = px.hit(i);
       int emit_tri_idx = S.emit[i];
@@ -362,7 +393,10 @@ static __device__ int consume_smooth(const DevScene& S, const Px& px, ShadeCtx& 
     return CONSUME_END;
   }
 
-  if (c.stage == ST_MIRROR) return consume_mirror<Px, 0>(S, px, c, l_final, nullptr);  // (no normal in it)
+  if (c.stage == ST_MIRROR) {  // (no normal in it)
+    if constexpr (has_textures<ST>) return consume_mirror_textured(S, px, c, l_final, table);
+    else return consume_mirror<Px, 0>(S, px, c, l_final, nullptr);
+  }
 
   if (c.stage == ST_REFRACT_LOOP) {
     const float triangle_miu = ot->refract_index;

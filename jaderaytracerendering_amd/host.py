@@ -95,16 +95,67 @@ def vertex_normals(vertices, indices, crease_deg):
     return out
 
 
+UV_PLANAR_X, UV_PLANAR_Y, UV_PLANAR_Z, UV_SPHERICAL = 0, 1, 2, 3
+
+
+def _texture_array(handle):
+    """The image of a jadeh_texture handle as float32 [height, width, 3] (a copy); the handle is freed."""
+    lib = host_lib()
+    if not handle:
+        raise RuntimeError(lib.jadeh_last_error().decode())
+    try:
+        w, h, p = C.c_int(), C.c_int(), C.c_void_p()
+        _check(lib.jadeh_texture_get(handle, C.byref(w), C.byref(h), C.byref(p)))
+        return np.frombuffer((C.c_char * (12 * w.value * h.value)).from_address(p.value), dtype=np.float32).copy().reshape(h.value, w.value, 3)
+    finally:
+        lib.jadeh_texture_free(handle)
+
+
+def load_texture(path):
+    """jadeh_texture_load: a P6 file (8 bits, sRGB decoded to linear) or a PF file (linear) as float32 [height, width, 3], row 0 the top
+    of the image - what Scene.set_textures and SceneBuilder.set_texture take."""
+    return _texture_array(host_lib().jadeh_texture_load(os.fsencode(path)))
+
+
+def texture_checker(size, squares, a=(0.9, 0.9, 0.9), b=(0.1, 0.1, 0.1)):
+    """jadeh_texture_checker: size x size texels in squares x squares squares of colours a and b."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return _texture_array(host_lib().jadeh_texture_checker(int(size), int(squares), a.ctypes.data, b.ctypes.data))
+
+
+def project_uvs(vertices, indices, projection=UV_SPHERICAL):
+    """jadeh_project_uvs: float32 [n_triangles, 3, 2] for a mesh without UVs - UV_PLANAR_X / _Y / _Z: the two other coordinates over the
+    mesh's bounding box; UV_SPHERICAL: longitude and latitude about the box's centre, the seam mended per triangle."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    i = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    out = np.zeros((len(i), 3, 2), np.float32)
+    _check(host_lib().jadeh_project_uvs(v.ctypes.data, len(v), i.ctypes.data, len(i), int(projection), out.ctypes.data))
+    return out
+
+
+def load_obj_textured(path):
+    """jadeh_load_obj_textured: (vertices [nv, 3], indices [nt, 3], uvs [nt, 3, 2] or None) of an OBJ file with `v`, `vt` and `f a/b[/c]` lines."""
+    lib = host_lib()
+    nv, nt, has = C.c_int(), C.c_int(), C.c_int()
+    _check(lib.jadeh_load_obj_textured(os.fsencode(path), C.byref(nv), C.byref(nt), C.byref(has), None, None, None))
+    v, i, uv = np.zeros((nv.value, 3), np.float32), np.zeros((nt.value, 3), np.int32), np.zeros((nt.value, 3, 2), np.float32)
+    _check(lib.jadeh_load_obj_textured(os.fsencode(path), C.byref(nv), C.byref(nt), C.byref(has), v.ctypes.data, i.ctypes.data, uv.ctypes.data))
+    return v, i, (uv if has.value else None)
+
+
 class HostScene:
     """Flattened scene: the arrays that cross the jade_rt.h boundary, and - optional, beside them - vertex_normals: float32
-    [n_triangles, 3, 3] in the triangles' order, which Backend.scene() puts on the handle (Scene.set_vertex_normals), or None."""
+    [n_triangles, 3, 3] in the triangles' order, which Backend.scene() puts on the handle (Scene.set_vertex_normals), or None; and
+    textures: (images - a list of float32 [height, width, 3], uv - float32 [n_triangles, 3, 2], image_of - int32 [n_triangles]) in the
+    triangles' order, which Backend.scene() puts on the handle as well (Scene.set_textures), or None."""
 
-    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0, vertex_normals=None):
+    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0, vertex_normals=None, textures=None):
         # arrays: dict of numpy arrays (owned copies)
         self.a = arrays
         self.bvh_depth = bvh_depth
         self.build_seconds = build_seconds
         self.vertex_normals = vertex_normals
+        self.textures = textures
 
     ARRAY_KEYS = ("triangles", "nodes", "emit", "mapping", "prefix", "segs", "env")
 
@@ -133,16 +184,35 @@ class HostScene:
         n = lib.jadeh_scene_vertex_normals(handle, C.byref(p))
         if n:
             vn = np.frombuffer((C.c_char * (n * 36)).from_address(p.value), dtype=np.float32).copy().reshape(n, 3, 3)
-        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle), vn)
+        tex, pu, pi = None, C.c_void_p(), C.c_void_p()
+        n_images = lib.jadeh_scene_textures(handle, C.byref(pu), C.byref(pi))
+        if n_images:
+            nt = d.n_triangles
+            images = []
+            for k in range(n_images):
+                w, h, p = C.c_int(), C.c_int(), C.c_void_p()
+                _check(lib.jadeh_scene_texture(handle, k, C.byref(w), C.byref(h), C.byref(p)))
+                images.append(np.frombuffer((C.c_char * (12 * w.value * h.value)).from_address(p.value), dtype=np.float32).copy().reshape(h.value, w.value, 3))
+            tex = (images, np.frombuffer((C.c_char * (24 * nt)).from_address(pu.value), dtype=np.float32).copy().reshape(nt, 3, 2),
+                   np.frombuffer((C.c_char * (4 * nt)).from_address(pi.value), dtype=np.int32).copy())
+        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle), vn, tex)
 
     @classmethod
     def from_npz(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS}, vertex_normals=z["vertex_normals"].copy() if "vertex_normals" in z.files else None)
+            tex = None
+            if "texture_uv" in z.files:
+                n = sum(1 for k in z.files if k.startswith("texture_image_") and k != "texture_image_of")
+                tex = ([z[f"texture_image_{k}"].copy() for k in range(n)], z["texture_uv"].copy(), z["texture_image_of"].copy())
+            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS}, vertex_normals=z["vertex_normals"].copy() if "vertex_normals" in z.files else None, textures=tex)
 
     def save_npz(self, path, **extra):
         if self.vertex_normals is not None:
             extra = dict(extra, vertex_normals=self.vertex_normals)
+        if self.textures is not None:
+            images, uv, image_of = self.textures
+            extra = dict(extra, texture_uv=np.asarray(uv, np.float32), texture_image_of=np.asarray(image_of, np.int32),
+                         **{f"texture_image_{k}": np.asarray(im, np.float32) for k, im in enumerate(images)})
         np.savez_compressed(path, **self.a, **extra)
 
     @property
@@ -212,10 +282,18 @@ class SceneBuilder:
             trans = transform_matrix()
         return np.ascontiguousarray(trans, np.float32)
 
-    def add_mesh(self, vertices, indices, mat, trans=None, normalize=False):
+    def add_mesh(self, vertices, indices, mat, trans=None, normalize=False, uvs=None):
+        """uvs: float32 [n_triangles, 3, 2], the mesh's own texture coordinates (used while a texture is set: set_texture)."""
         v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         i = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
         t = self._t(trans)
+        if uvs is not None:
+            u = np.ascontiguousarray(uvs, np.float32)
+            if u.size != 6 * len(i):
+                raise ValueError("add_mesh: 6 floats of uv per triangle")
+            _check(self._lib.jadeh_builder_add_mesh_uv(self._h, v.ctypes.data, len(v), i.ctypes.data, len(i), u.ctypes.data, C.byref(mat),
+                                                       t.ctypes.data, int(normalize)))
+            return
         _check(self._lib.jadeh_builder_add_mesh(self._h, v.ctypes.data, len(v), i.ctypes.data, len(i), C.byref(mat),
                                                 t.ctypes.data, int(normalize)))
 
@@ -232,6 +310,32 @@ class SceneBuilder:
         """jadeh_builder_set_smoothing: the meshes added from now on get vertex normals (vertex_normals() after the mesh's transform;
         <= 0: flat again).  The built HostScene then carries `vertex_normals`."""
         _check(self._lib.jadeh_builder_set_smoothing(self._h, float(crease_deg)))
+
+    def set_texture(self, image, projection=UV_SPHERICAL):
+        """jadeh_builder_set_texture: the meshes added from now on carry `image` (float32 [height, width, 3], linear, row 0 at v = 0; None:
+        no image again) with their own UVs - add_mesh's uvs, a "quad"'s, an OBJ's `vt` lines - or, where they have none, those of
+        `projection` (UV_*).  The built HostScene then carries `textures`."""
+        if image is None:
+            _check(self._lib.jadeh_builder_set_texture(self._h, None, int(projection)))
+            return
+        self._with_texture(image, lambda t: self._lib.jadeh_builder_set_texture(self._h, t, int(projection)))
+
+    def set_object_texture(self, obj, image, projection=UV_SPHERICAL):
+        """jadeh_builder_set_object_texture: the obj'th object to be added (0-based; the objects of config() count) carries `image`,
+        whatever set_texture says when it arrives - what jade_render --texture OBJ=IMAGE does."""
+        self._with_texture(image, lambda t: self._lib.jadeh_builder_set_object_texture(self._h, int(obj), t, int(projection)))
+
+    def _with_texture(self, image, call):
+        im = np.ascontiguousarray(image, np.float32)
+        if im.ndim != 3 or im.shape[2] != 3:
+            raise ValueError("an image is [height, width, 3]")
+        t = self._lib.jadeh_texture_data(im.shape[1], im.shape[0], im.ctypes.data)
+        if not t:
+            raise RuntimeError(self._lib.jadeh_last_error().decode())
+        try:
+            _check(call(t))
+        finally:
+            self._lib.jadeh_texture_free(t)
 
     def set_env_constant(self, r, g, b):
         _check(self._lib.jadeh_builder_set_env_constant(self._h, r, g, b))

@@ -1,6 +1,8 @@
 // host_capi.cpp — C entry points over the host scene pipeline, for the CLI,
 // the Python bindings (ctypes) and the tests.  Declared in jade_host_c.h.
+#include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <string>
 
@@ -20,6 +22,9 @@ struct jadeh_builder {
 };
 struct jadeh_scene {
   BuiltScene s;
+};
+struct jadeh_texture {
+  Texture t;
 };
 
 static Material to_mat(const jadeh_material* m) {
@@ -61,11 +66,30 @@ int jadeh_builder_add_mesh(jadeh_builder* b, const float* verts, int nv, const i
   return 0;
 }
 
+static bool mesh_from(const float* verts, int nv, const int* idx, int nt, Mesh& m) {
+  m.vertices.resize((size_t)nv);
+  for (int i = 0; i < nv; ++i) m.vertices[i] = jv(verts[3 * i], verts[3 * i + 1], verts[3 * i + 2]);
+  m.indices.assign(idx, idx + 3 * (size_t)nt);
+  for (int i : m.indices)
+    if (i < 0 || i >= nv) return false;
+  return true;
+}
+
+int jadeh_builder_add_mesh_uv(jadeh_builder* b, const float* verts, int nv, const int* idx, int nt, const float* uv6, const jadeh_material* mat,
+                              const float* trans16, int normalize) {
+  if (!b || !verts || !idx || !uv6 || nv <= 0 || nt <= 0) return fail("add_mesh_uv: bad arguments");
+  Mesh m;
+  if (!mesh_from(verts, nv, idx, nt, m)) return fail("add_mesh_uv: index out of range");
+  m.uvs.assign(uv6, uv6 + 6 * (size_t)nt);
+  b->b.add_mesh(m, to_mat(mat), to_mat4(trans16), normalize != 0);
+  return 0;
+}
+
 int jadeh_builder_add_obj(jadeh_builder* b, const char* path, const jadeh_material* mat, const float* trans16, int normalize) {
   if (!b || !path) return fail("add_obj: bad arguments");
   Mesh m;
   std::string err;
-  if (!load_obj(path, m, err)) return fail(err);
+  if (!(b->b.texture_set() ? load_obj_textured(path, m, err) : load_obj(path, m, err))) return fail(err);
   b->b.add_mesh(m, to_mat(mat), to_mat4(trans16), normalize != 0);
   return 0;
 }
@@ -114,6 +138,87 @@ int jadeh_vertex_normals(const float* verts, int nv, const int* idx, int nt, flo
   }
   const std::vector<float> vn = vertex_normals(m, crease_deg);
   if (!vn.empty()) memcpy(out9, vn.data(), vn.size() * sizeof(float));
+  return 0;
+}
+static jadeh_texture* texture_fail(const std::string& m) {
+  fail(m);
+  return nullptr;
+}
+jadeh_texture* jadeh_texture_load(const char* path) {
+  if (!path) return texture_fail("texture_load: bad arguments");
+  FILE* f = fopen(path, "rb");
+  if (!f) return texture_fail(std::string("File ") + path + " open failed.");
+  char magic[2] = {0, 0};
+  const size_t got = fread(magic, 1, 2, f);
+  fclose(f);
+  jadeh_texture* t = new jadeh_texture();
+  std::string err;
+  const bool pfm = got == 2 && magic[0] == 'P' && magic[1] == 'F';
+  if (!(pfm ? load_pfm(path, t->t, err) : load_ppm(path, t->t, err))) {
+    delete t;
+    return texture_fail(err);
+  }
+  return t;
+}
+jadeh_texture* jadeh_texture_checker(int size, int squares, const float a[3], const float b[3]) {
+  if (!a || !b || size < 1 || size > 16384 || squares < 1) return texture_fail("texture_checker: bad arguments");
+  jadeh_texture* t = new jadeh_texture();
+  t->t = make_texture_checker(size, squares, a, b);
+  return t;
+}
+jadeh_texture* jadeh_texture_data(int width, int height, const float* rgb) {
+  if (!rgb || width < 1 || width > 16384 || height < 1 || height > 16384) return texture_fail("texture_data: bad arguments");
+  jadeh_texture* t = new jadeh_texture();
+  t->t.width = width;
+  t->t.height = height;
+  t->t.rgb.assign(rgb, rgb + (size_t)3 * width * height);
+  return t;
+}
+void jadeh_texture_free(jadeh_texture* t) { delete t; }
+int jadeh_texture_get(const jadeh_texture* t, int* width, int* height, const float** rgb) {
+  if (!t || !width || !height || !rgb) return fail("texture_get: bad arguments");
+  *width = t->t.width;
+  *height = t->t.height;
+  *rgb = t->t.rgb.data();
+  return 0;
+}
+int jadeh_builder_set_texture(jadeh_builder* b, const jadeh_texture* t, int projection) {
+  if (!b) return fail("null builder");
+  if (projection < 0 || projection > 3) return fail("set_texture: projection is 0 1 2 (planar along x y z) or 3 (spherical)");
+  b->b.set_texture(t ? &t->t : nullptr, (UvProjection)projection);
+  return 0;
+}
+int jadeh_builder_set_object_texture(jadeh_builder* b, int object, const jadeh_texture* t, int projection) {
+  if (!b || !t || object < 0) return fail("set_object_texture: bad arguments");
+  if (projection < 0 || projection > 3) return fail("set_object_texture: projection is 0 1 2 (planar along x y z) or 3 (spherical)");
+  b->b.set_object_texture(object, t->t, (UvProjection)projection);
+  return 0;
+}
+int jadeh_project_uvs(const float* verts, int nv, const int* idx, int nt, int projection, float* out6) {
+  if (!verts || !idx || !out6 || nv < 0 || nt < 0 || projection < 0 || projection > 3) return fail("project_uvs: bad arguments");
+  Mesh m;
+  if (!mesh_from(verts, nv, idx, nt, m)) return fail("project_uvs: index out of range");
+  const std::vector<float> uv = projection == 3 ? spherical_uvs(m) : planar_uvs(m, projection);
+  if (!uv.empty()) memcpy(out6, uv.data(), uv.size() * sizeof(float));
+  return 0;
+}
+int jadeh_load_obj_textured(const char* path, int* nv, int* nt, int* has_uv, float* verts, int* idx, float* uv6) {
+  if (!path || !nv || !nt || !has_uv) return fail("load_obj_textured: bad arguments");
+  Mesh m;
+  std::string err;
+  if (!load_obj_textured(path, m, err)) return fail(err);
+  *nv = (int)m.vertices.size();
+  *nt = (int)(m.indices.size() / 3);
+  *has_uv = m.uvs.empty() ? 0 : 1;
+  if (verts)
+    for (size_t i = 0; i < m.vertices.size(); ++i) {
+      verts[3 * i] = m.vertices[i].x;
+      verts[3 * i + 1] = m.vertices[i].y;
+      verts[3 * i + 2] = m.vertices[i].z;
+    }
+  if (idx) std::copy(m.indices.begin(), m.indices.end(), idx);
+  if (uv6)
+    for (size_t i = 0; i < m.indices.size() * 2; ++i) uv6[i] = m.uvs.empty() ? 0.0f : m.uvs[i];
   return 0;
 }
 int jadeh_builder_set_env_constant(jadeh_builder* b, float r, float g, float bl) {
@@ -217,6 +322,19 @@ int jadeh_scene_vertex_normals(const jadeh_scene* s, const float** out) {
   if (!s) return 0;
   if (out) *out = s->s.vertex_normals.empty() ? nullptr : s->s.vertex_normals.data();
   return (int)(s->s.vertex_normals.size() / 9);
+}
+int jadeh_scene_textures(const jadeh_scene* s, const float** uv, const int32_t** image_of) {
+  if (!s) return 0;
+  if (uv) *uv = s->s.uv.empty() ? nullptr : s->s.uv.data();
+  if (image_of) *image_of = s->s.image_of.empty() ? nullptr : s->s.image_of.data();
+  return (int)s->s.textures.size();
+}
+int jadeh_scene_texture(const jadeh_scene* s, int k, int* width, int* height, const float** rgb) {
+  if (!s || !width || !height || !rgb || k < 0 || k >= (int)s->s.textures.size()) return fail("scene_texture: bad arguments");
+  *width = s->s.textures[k].width;
+  *height = s->s.textures[k].height;
+  *rgb = s->s.textures[k].rgb.data();
+  return 0;
 }
 int jadeh_scene_bvh_depth(const jadeh_scene* s) { return s ? s->s.bvh_depth : 0; }
 double jadeh_scene_build_seconds(const jadeh_scene* s) { return s ? s->s.build_seconds : 0; }

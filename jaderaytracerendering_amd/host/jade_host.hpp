@@ -8,6 +8,7 @@
 // PathTrace.cpp:343-359, 684-687, 883-918 without sharing their code.
 #pragma once
 #include <cstdint>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -39,12 +40,17 @@ Mat4 transform_matrix(const float rot_deg[3], const float trans[3], const float 
 struct Mesh {
   std::vector<jvec3> vertices;
   std::vector<int> indices;  // 3 per triangle, 0-based
+  std::vector<float> uvs;    // optional: 6 per triangle - (u, v) of its three corners, in the order of its indices; empty: the mesh has none
 };
 
 // -- mesh sources -----------------------------------------------------------
 // readObj's parser (PathTrace.cu:378-408): '#' lines skipped, '/' -> ' ',
 // "v x y z", "f a b c" (first three integers only).
 bool load_obj(const std::string& path, Mesh& out, std::string& err);
+// An OBJ file with texture coordinates: "v x y z", "vt u v" and "f a/b[/c] ..." (the first three corners only; a corner without a `vt`
+// index, or with one out of range, gets (0, 0)).  out.uvs is filled when the file has a `vt` line.  load_obj above - the reference's
+// parser, with its way of reading a '/' - stays what every existing caller uses.
+bool load_obj_textured(const std::string& path, Mesh& out, std::string& err);
 bool write_obj(const std::string& path, const Mesh& mesh);
 Mesh make_quad(jvec3 a, jvec3 b, jvec3 c, jvec3 d);
 Mesh make_box();                     // unit cube centred at 0, 12 triangles
@@ -60,6 +66,28 @@ void append(Mesh& dst, const Mesh& src);
 // triangle contributes to, or one whose contributors all have this triangle's flat normal (component by component, -0 = 0), or a sum without a direction: the
 // flat normal, bitwise.
 std::vector<float> vertex_normals(const Mesh& mesh, float crease_deg);
+
+// -- albedo textures (include/jade_bvh.h, jade_scene_set_textures) -----------
+// UVs for a mesh that has none, 6 floats per triangle, formed in double from the mesh's own (untransformed) vertices and rounded once.
+// planar_uvs: the two coordinates other than `axis` (0 x, 1 y, 2 z; in cyclic order: y z, z x, x y), each mapped from the mesh's bounding
+// box to [0, 1] (an extent of 0: 0).  spherical_uvs: about the centre of the bounding box, u = 0.5 + atan2(z, x) / 2 pi, v = 0.5 -
+// asin(y / r) / pi (v = 0 at the top, where the image's row 0 is); a triangle that crosses the seam u = 0 | 1 has 1 added to its corners
+// below 0.5 - the image repeats - and a corner at a pole takes the mean u of the other two.
+std::vector<float> planar_uvs(const Mesh& mesh, int axis);
+std::vector<float> spherical_uvs(const Mesh& mesh);
+enum UvProjection { UV_PLANAR_X = 0, UV_PLANAR_Y = 1, UV_PLANAR_Z = 2, UV_SPHERICAL = 3 };
+
+struct Texture {
+  int width = 0, height = 0;
+  std::vector<float> rgb;  // linear, interleaved, row 0 at v = 0 (the top of an image file)
+};
+// P6, 8 bits per channel: sRGB decoded in double - c / 12.92 up to 0.04045, ((c + 0.055) / 1.055)^2.4 above, c = byte / 255 - and rounded once.
+bool load_ppm(const std::string& path, Texture& out, std::string& err);
+// PF: linear values as stored - the sign of the header's scale gives the byte order, its magnitude is ignored; the file's rows run bottom
+// to top and are flipped, so that row 0 is the top.
+bool load_pfm(const std::string& path, Texture& out, std::string& err);
+// size x size texels in squares x squares squares of colours a and b, (0, 0) being a
+Texture make_texture_checker(int size, int squares, const float a[3], const float b[3]);
 
 // -- scene builder (host triangles, pre-BVH) -------------------------------
 struct HostTriangle {  // == Triangle, PathTrace.cu:305-311
@@ -85,6 +113,10 @@ struct BuiltScene {
   std::vector<float> prefix;             // original order
   std::vector<jade_obj_seg> segs;
   std::vector<float> vertex_normals;     // 9 per triangle, BVH order: what jade_scene_set_vertex_normals takes; empty if no mesh was smoothed
+  // what jade_scene_set_textures takes, BVH order: 6 floats of UV and an image number (-1: none) per triangle, and the images; empty if no mesh was textured
+  std::vector<float> uv;
+  std::vector<int32_t> image_of;
+  std::vector<Texture> textures;
   EnvMap env;
   int bvh_depth = 0;
   double build_seconds = 0;
@@ -101,6 +133,15 @@ class SceneBuilder {
   // The smoothing angle of the meshes added from now on (degrees; <= 0: flat, the default): add_mesh forms their vertex normals with
   // vertex_normals(), after the mesh's transform.  load_obj reads no `vn` lines: normals come from the geometry alone.
   void set_smoothing(float crease_deg) { smooth_deg_ = crease_deg; }
+  // The texture of the meshes added from now on (nullptr: none, the default): add_mesh gives their triangles the image and the mesh's own
+  // UVs or, where it has none, those of `fallback` - formed from the mesh as given, before normalize and the transform.
+  void set_texture(const Texture* texture, UvProjection fallback = UV_SPHERICAL);
+  bool texture_set() const { return texture_ >= 0; }
+  // ... and the texture of the object'th mesh to be added (0-based, in the order of the add_mesh calls), whatever set_texture says when it
+  // arrives: how a caller textures one object of a configuration it does not build itself (jade_render --texture).
+  void set_object_texture(int object, const Texture& texture, UvProjection fallback = UV_SPHERICAL);
+  bool object_texture_set(int object) const { return object_texture_.count(object) != 0; }
+  int object_count() const { return (int)segs_.size(); }
   int triangle_count() const { return (int)tris_.size(); }
   // Area prefix sums (PathTrace.cu:1539-1546), SAH BVH with leaf size 8
   // (:1557-1565), encode (:1570-1612).
@@ -117,6 +158,12 @@ class SceneBuilder {
   std::vector<jade_obj_seg> segs_;
   std::vector<float> vnorm_;  // 9 per triangle of tris_, original order; empty until a mesh is smoothed
   float smooth_deg_ = 0.0f;
+  std::vector<float> uv_;          // 6 per triangle of tris_, original order; empty until a mesh is textured
+  std::vector<int32_t> image_of_;  // ... and its image, -1 for none
+  std::vector<Texture> textures_;
+  int texture_ = -1;               // set_texture: the image of the meshes to come
+  UvProjection fallback_ = UV_SPHERICAL;
+  std::map<int, std::pair<int, UvProjection>> object_texture_;  // set_object_texture: object -> (its image in textures_, its fallback)
   EnvMap env_;
 };
 

@@ -59,6 +59,8 @@ struct Api {
   int (*scene_set_branch_sampling)(jade_scene*, int) = nullptr;
   // ... and only for --smooth
   int (*scene_set_vertex_normals)(jade_scene*, const float*, int32_t) = nullptr;
+  // ... and only for --texture
+  int (*scene_set_textures)(jade_scene*, int32_t, const jade_texture_image*, const float*, const int32_t*, int32_t) = nullptr;
   // ... and only for --passes
   int (*scene_set_passes)(jade_scene*, int) = nullptr;
   int (*render_passes)(jade_scene*, float*) = nullptr;
@@ -106,6 +108,7 @@ static void usage() {
           "usage: jade_render (--config NAME | --args render_args.txt) [--width W --height H] [--spp N]\n"
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
           "                   [--bounce uniform|cosine] [--direct rays|mis] [--branch random|stratified] [--passes PREFIX] [--smooth [DEG]]\n"
+          "                   [--texture K=checker[:SIZE[:SQUARES]]|FILE[@PROJECTION]]...\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -137,6 +140,12 @@ static void usage() {
           "                       share its vertex and lie within DEG degrees (default 60) of its triangle - interpolated at every path vertex\n"
           "                       (HIP backend only; NOT the reference's image; include/jade_bvh.h).  OBJ vn lines are not read.  Not together\n"
           "                       with --shutter-*, --one-light, --direct mis, --passes or --branch stratified\n"
+          "  --texture K=IMAGE[@PROJECTION]: an albedo texture on object K of the scene (0-based, in the order the configuration or the\n"
+          "                       arguments file adds its objects), multiplied into its brdf and refract_albedo at every path vertex (HIP backend\n"
+          "                       only; NOT the reference's image; include/jade_bvh.h).  IMAGE is a .ppm file (P6, 8 bits, sRGB), a .pfm file\n"
+          "                       (linear) or checker[:SIZE[:SQUARES]] (default 256 texels a side in 8 x 8 squares).  The object's own UVs are used\n"
+          "                       where it has them (a quad's; an OBJ file's vt lines); otherwise PROJECTION: spherical (the default), planar-x,\n"
+          "                       planar-y or planar-z.  May be given once per object.  Not together with what --smooth is not together with\n"
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
@@ -187,6 +196,8 @@ int main(int argc, char** argv) {
   int branch = -1;  // --branch: JADE_BRANCH_*, -1 = not given
   std::string passes;  // --passes PREFIX
   double smooth_deg = 0.0;  // --smooth [DEG]: the objects' smoothing angle, 0 = not given
+  struct TextureFlag { int object; std::string image; UvProjection projection; };
+  std::vector<TextureFlag> texture_flags;  // --texture K=IMAGE[@PROJECTION]
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -238,6 +249,28 @@ int main(int argc, char** argv) {
       else { fprintf(stderr, "--branch takes random or stratified, not %s\n", v.c_str()); return 2; }
     }
     else if (a == "--passes") passes = need("--passes");
+    else if (a == "--texture") {
+      const std::string v = need("--texture");
+      const size_t eq = v.find('='), at = v.rfind('@');
+      char* end = nullptr;
+      const long k = strtol(v.c_str(), &end, 10);
+      if (eq == std::string::npos || eq == 0 || end != v.c_str() + eq || k < 0 || k > 1000000 || eq + 1 >= (at == std::string::npos ? v.size() : at)) {
+        fprintf(stderr, "--texture takes K=IMAGE[@PROJECTION] with K an object number from 0, not %s\n", v.c_str());
+        return 2;
+      }
+      UvProjection proj = UV_SPHERICAL;
+      if (at != std::string::npos) {
+        const std::string pn = v.substr(at + 1);
+        if (pn == "spherical") proj = UV_SPHERICAL;
+        else if (pn == "planar-x") proj = UV_PLANAR_X;
+        else if (pn == "planar-y") proj = UV_PLANAR_Y;
+        else if (pn == "planar-z") proj = UV_PLANAR_Z;
+        else { fprintf(stderr, "--texture: the projection is spherical, planar-x, planar-y or planar-z, not %s\n", pn.c_str()); return 2; }
+      }
+      for (const TextureFlag& t : texture_flags)
+        if (t.object == (int)k) { fprintf(stderr, "--texture: object %ld is given twice\n", k); return 2; }
+      texture_flags.push_back({(int)k, v.substr(eq + 1, (at == std::string::npos ? v.size() : at) - eq - 1), proj});
+    }
     else if (a == "--smooth") {  // the angle is optional: taken if the next argument is a number
       smooth_deg = 60.0;
       if (i + 1 < argc) {
@@ -341,6 +374,22 @@ int main(int argc, char** argv) {
   builder.set_smoothing((float)smooth_deg);  // (0: flat) - every object of the configuration or of render_args
   Config cfg;
   std::string err;
+  for (const TextureFlag& t : texture_flags) {
+    Texture tex;
+    if (t.image.compare(0, 7, "checker") == 0 && (t.image.size() == 7 || t.image[7] == ':')) {
+      int size = 256, squares = 8;
+      if (t.image.size() > 7 && (sscanf(t.image.c_str() + 8, "%d:%d", &size, &squares) < 1 || size < 1 || size > 16384 || squares < 1 || squares > size)) {
+        fprintf(stderr, "--texture: checker[:SIZE[:SQUARES]] takes 1 .. 16384 texels a side and at most as many squares, not %s\n", t.image.c_str());
+        return 2;
+      }
+      const float light[3] = {0.9f, 0.9f, 0.9f}, dark[3] = {0.15f, 0.15f, 0.15f};
+      tex = make_texture_checker(size, squares, light, dark);
+    } else if (!(t.image.size() > 4 && t.image.compare(t.image.size() - 4, 4, ".pfm") == 0 ? load_pfm(t.image, tex, err) : load_ppm(t.image, tex, err))) {
+      fprintf(stderr, "--texture: %s\n", err.c_str());
+      return 1;
+    }
+    builder.set_object_texture(t.object, tex, t.projection);
+  }
   if (!config.empty()) {
     if (!make_config(config, builder, cfg, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
   } else {
@@ -352,7 +401,8 @@ int main(int argc, char** argv) {
     for (const RenderArgsObject& o : ra.objects) {
       Mesh m;
       std::string f = (!o.file.empty() && o.file[0] == '/') ? o.file : dir + o.file;
-      if (!load_obj(f, m, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+      // (a textured object is read with its vt lines; every other one as the reference reads it)
+      if (!(builder.object_texture_set(builder.object_count()) ? load_obj_textured(f, m, err) : load_obj(f, m, err))) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
       builder.add_mesh(m, o.material, o.trans, o.normalize);
     }
     memcpy(cfg.eye, ra.eye, sizeof cfg.eye);
@@ -361,6 +411,11 @@ int main(int argc, char** argv) {
     cfg.spp = 64;
     if (env.empty()) env = "sky";
   }
+  for (const TextureFlag& t : texture_flags)
+    if (t.object >= builder.object_count()) {
+      fprintf(stderr, "--texture: the scene has objects 0 .. %d, not %d\n", builder.object_count() - 1, t.object);
+      return 2;
+    }
   if (env == "sky") builder.set_env(make_env_sky(1024, 512));
   else if (!env.empty()) {
     EnvMap e;
@@ -455,6 +510,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (!texture_flags.empty()) {
+    *(void**)(&api.scene_set_textures) = dlsym(api.h, "jade_scene_set_textures");
+    if (!api.scene_set_textures) {
+      fprintf(stderr, "--texture needs the HIP backend: %s has no jade_scene_set_textures\n", backend.c_str());
+      return 2;
+    }
+  }
   if (!passes.empty()) {
     *(void**)(&api.scene_set_passes) = dlsym(api.h, "jade_scene_set_passes");
     *(void**)(&api.render_passes) = dlsym(api.h, "jade_render_passes");
@@ -524,10 +586,18 @@ int main(int argc, char** argv) {
     fprintf(stderr, "vertex normals: %s\n", api.last_error());
     return 1;
   }
+  if (!scene.textures.empty()) {
+    std::vector<jade_texture_image> images;
+    for (const Texture& t : scene.textures) images.push_back({t.width, t.height, t.rgb.data()});
+    if (api.scene_set_textures(dev, (int32_t)images.size(), images.data(), scene.uv.data(), scene.image_of.data(), (int32_t)scene.image_of.size()) != JADE_OK) {
+      fprintf(stderr, "textures: %s\n", api.last_error());
+      return 1;
+    }
+  }
   if (!passes.empty() && api.scene_set_passes(dev, 1) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
                                     (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
-                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (smooth_deg > 0.0 ? ", smooth shading" : "") + (!passes.empty() ? ", light passes kept" : "");
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (smooth_deg > 0.0 ? ", smooth shading" : "") + (!texture_flags.empty() ? ", textures" : "") + (!passes.empty() ? ", light passes kept" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);

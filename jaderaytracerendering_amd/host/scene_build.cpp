@@ -87,6 +87,59 @@ bool load_obj(const std::string& path, Mesh& out, std::string& err) {
   return true;
 }
 
+bool load_obj_textured(const std::string& path, Mesh& out, std::string& err) {
+  std::ifstream fin(path);
+  if (!fin.is_open()) {
+    err = "File " + path + " open failed.";
+    return false;
+  }
+  std::vector<float> vt;        // 2 per `vt` line
+  std::vector<int> corner_vt;   // per corner: 0-based `vt` index, -1 for none
+  std::string line;
+  while (std::getline(fin, line)) {
+    if (!line.empty() && line[0] == '#') continue;
+    std::istringstream sin(line);
+    std::string type;
+    sin >> type;
+    if (type == "v") {
+      float x = 0, y = 0, z = 0;
+      sin >> x >> y >> z;
+      out.vertices.push_back(jv(x, y, z));
+    } else if (type == "vt") {
+      float u = 0, v = 0;
+      sin >> u >> v;
+      vt.push_back(u);
+      vt.push_back(v);
+    } else if (type == "f") {
+      for (int k = 0; k < 3; ++k) {  // a/b/c, a//c, a/b or a: the first three corners
+        std::string corner;
+        sin >> corner;
+        int a = 0, b = 0;
+        const size_t s1 = corner.find('/');
+        a = atoi(corner.substr(0, s1).c_str());
+        if (s1 != std::string::npos) b = atoi(corner.substr(s1 + 1, corner.find('/', s1 + 1) - s1 - 1).c_str());
+        out.indices.push_back(a - 1);
+        corner_vt.push_back(b - 1);
+      }
+    }
+  }
+  for (int idx : out.indices)
+    if (idx < 0 || idx >= (int)out.vertices.size()) {
+      err = "File " + path + ": face index out of range";
+      return false;
+    }
+  out.uvs.clear();
+  if (!vt.empty()) {
+    out.uvs.assign(2 * corner_vt.size(), 0.0f);
+    for (size_t c = 0; c < corner_vt.size(); ++c)
+      if (corner_vt[c] >= 0 && (size_t)corner_vt[c] < vt.size() / 2) {
+        out.uvs[2 * c] = vt[2 * (size_t)corner_vt[c]];
+        out.uvs[2 * c + 1] = vt[2 * (size_t)corner_vt[c] + 1];
+      }
+  }
+  return true;
+}
+
 bool write_obj(const std::string& path, const Mesh& mesh) {
   FILE* f = fopen(path.c_str(), "w");
   if (!f) return false;
@@ -102,6 +155,7 @@ Mesh make_quad(jvec3 a, jvec3 b, jvec3 c, jvec3 d) {
   Mesh m;
   m.vertices = {a, b, c, d};
   m.indices = {0, 1, 2, 0, 2, 3};
+  m.uvs = {0, 0, 1, 0, 1, 1, 0, 0, 1, 1, 0, 1};  // a b c d at (0, 0) (1, 0) (1, 1) (0, 1)
   return m;
 }
 
@@ -119,7 +173,99 @@ Mesh make_box() {
 void append(Mesh& dst, const Mesh& src) {
   int base = (int)dst.vertices.size();
   dst.vertices.insert(dst.vertices.end(), src.vertices.begin(), src.vertices.end());
+  const bool keep_uvs = !src.uvs.empty() && (dst.indices.empty() || !dst.uvs.empty());  // UVs survive only where every triangle has them
   for (int i : src.indices) dst.indices.push_back(base + i);
+  if (keep_uvs) dst.uvs.insert(dst.uvs.end(), src.uvs.begin(), src.uvs.end());
+  else dst.uvs.clear();
+}
+
+// ------------------------------------------------------------------ UVs ----
+
+static void mesh_bounds(const Mesh& mesh, double lo[3], double hi[3]) {
+  for (int k = 0; k < 3; ++k) lo[k] = hi[k] = 0.0;
+  bool first = true;
+  for (const jvec3& v : mesh.vertices) {
+    const double c[3] = {v.x, v.y, v.z};
+    for (int k = 0; k < 3; ++k) {
+      if (first || c[k] < lo[k]) lo[k] = c[k];
+      if (first || c[k] > hi[k]) hi[k] = c[k];
+    }
+    first = false;
+  }
+}
+
+std::vector<float> planar_uvs(const Mesh& mesh, int axis) {
+  double lo[3], hi[3];
+  mesh_bounds(mesh, lo, hi);
+  const int a = (axis + 1) % 3, b = (axis + 2) % 3;
+  std::vector<float> uv(2 * mesh.indices.size());
+  for (size_t c = 0; c < mesh.indices.size(); ++c) {
+    const jvec3& v = mesh.vertices[mesh.indices[c]];
+    const double p[3] = {v.x, v.y, v.z};
+    uv[2 * c] = hi[a] > lo[a] ? (float)((p[a] - lo[a]) / (hi[a] - lo[a])) : 0.0f;
+    uv[2 * c + 1] = hi[b] > lo[b] ? (float)((p[b] - lo[b]) / (hi[b] - lo[b])) : 0.0f;
+  }
+  return uv;
+}
+
+std::vector<float> spherical_uvs(const Mesh& mesh) {
+  double lo[3], hi[3];
+  mesh_bounds(mesh, lo, hi);
+  const double centre[3] = {(lo[0] + hi[0]) / 2, (lo[1] + hi[1]) / 2, (lo[2] + hi[2]) / 2};
+  std::vector<float> uv(2 * mesh.indices.size());
+  for (size_t t = 0; t + 2 < mesh.indices.size(); t += 3) {
+    double u[3], v[3];
+    bool pole[3];
+    for (int k = 0; k < 3; ++k) {
+      const jvec3& p = mesh.vertices[mesh.indices[t + k]];
+      const double x = p.x - centre[0], y = p.y - centre[1], z = p.z - centre[2];
+      const double r = std::sqrt(x * x + y * y + z * z);
+      pole[k] = !(x * x + z * z > 0.0);
+      u[k] = pole[k] ? 0.0 : 0.5 + std::atan2(z, x) / (2.0 * JADE_PI_D);
+      v[k] = r > 0.0 ? std::max(0.0, std::min(1.0, 0.5 - std::asin(std::max(-1.0, std::min(1.0, y / r))) / JADE_PI_D)) : 0.5;
+    }
+    double umin = 2.0, umax = -1.0;
+    for (int k = 0; k < 3; ++k)
+      if (!pole[k]) {
+        umin = std::min(umin, u[k]);
+        umax = std::max(umax, u[k]);
+      }
+    if (umax - umin > 0.5)  // the triangle crosses the seam
+      for (int k = 0; k < 3; ++k)
+        if (!pole[k] && u[k] < 0.5) u[k] += 1.0;
+    for (int k = 0; k < 3; ++k)
+      if (pole[k]) {
+        double sum = 0.0;
+        int n = 0;
+        for (int j = 0; j < 3; ++j)
+          if (!pole[j]) {
+            sum += u[j];
+            ++n;
+          }
+        u[k] = n ? sum / n : 0.0;
+      }
+    for (int k = 0; k < 3; ++k) {
+      uv[2 * (t + k)] = (float)u[k];
+      uv[2 * (t + k) + 1] = (float)v[k];
+    }
+  }
+  return uv;
+}
+
+void SceneBuilder::set_texture(const Texture* texture, UvProjection fallback) {
+  fallback_ = fallback;
+  if (!texture || texture->width <= 0 || texture->height <= 0) {
+    texture_ = -1;
+    return;
+  }
+  textures_.push_back(*texture);
+  texture_ = (int)textures_.size() - 1;
+}
+
+void SceneBuilder::set_object_texture(int object, const Texture& texture, UvProjection fallback) {
+  if (texture.width <= 0 || texture.height <= 0) return;
+  textures_.push_back(texture);
+  object_texture_[object] = std::make_pair((int)textures_.size() - 1, fallback);
 }
 
 namespace {
@@ -340,6 +486,25 @@ void SceneBuilder::add_mesh(const Mesh& mesh, const Material& mat, const Mat4& t
       std::copy(vn.begin(), vn.begin() + 9 * (size_t)ntri, vnorm_.begin() + 9 * (size_t)offset);
     }
   }
+  // textures: this mesh's image and UVs if one is set, and "no image" for every triangle that has none once any has
+  int texture = texture_;
+  UvProjection fallback = fallback_;
+  if (const auto own = object_texture_.find(obj_idx); own != object_texture_.end()) {
+    texture = own->second.first;
+    fallback = own->second.second;
+  }
+  if (texture >= 0 || !image_of_.empty()) {
+    uv_.resize(6 * tris_.size(), 0.0f);
+    image_of_.resize(tris_.size(), -1);
+    if (texture >= 0) {
+      const std::vector<float> made = mesh.uvs.size() == 6 * (size_t)ntri ? std::vector<float>()
+                                      : fallback == UV_SPHERICAL      ? spherical_uvs(mesh)
+                                                                      : planar_uvs(mesh, (int)fallback);
+      const std::vector<float>& uv = made.empty() ? mesh.uvs : made;
+      std::copy(uv.begin(), uv.begin() + 6 * (size_t)ntri, uv_.begin() + 6 * (size_t)offset);
+      std::fill(image_of_.begin() + offset, image_of_.end(), texture);
+    }
+  }
 }
 
 // ------------------------------------------------------------------ BVH ----
@@ -547,6 +712,18 @@ void SceneBuilder::finish(std::vector<HostTriangle>& tris, BuiltScene& out) cons
   if (!vnorm_.empty()) {  // the triangles' own, carried through whatever order `tris` is in
     out.vertex_normals.resize(9 * n);
     for (size_t i = 0; i < n; ++i) std::copy(vnorm_.begin() + 9 * (size_t)tris[i].index, vnorm_.begin() + 9 * (size_t)tris[i].index + 9, out.vertex_normals.begin() + 9 * i);
+  }
+  out.uv.clear();
+  out.image_of.clear();
+  out.textures.clear();
+  if (!image_of_.empty()) {  // ... and their UVs and images, the same way
+    out.uv.resize(6 * n);
+    out.image_of.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      std::copy(uv_.begin() + 6 * (size_t)tris[i].index, uv_.begin() + 6 * (size_t)tris[i].index + 6, out.uv.begin() + 6 * i);
+      out.image_of[i] = image_of_[(size_t)tris[i].index];
+    }
+    out.textures = textures_;
   }
   out.env = env_.width > 0 ? env_ : make_env_constant(0, 0, 0);
 }

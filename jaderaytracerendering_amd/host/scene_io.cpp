@@ -254,6 +254,113 @@ bool write_pfm(const std::string& path, const float* rgb, int width, int height)
   return ok;
 }
 
+// --------------------------------------------------------------- textures ----
+
+// The next whitespace-separated token of a PNM / PFM header ('#' starts a comment that runs to the end of the line); exactly one
+// whitespace character is consumed after it, as the formats say of the last header token.
+static bool pnm_token(FILE* f, std::string& out) {
+  out.clear();
+  int c = fgetc(f);
+  for (;;) {
+    while (c == ' ' || c == '\t' || c == '\n' || c == '\r') c = fgetc(f);
+    if (c != '#') break;
+    while (c != '\n' && c != EOF) c = fgetc(f);
+  }
+  while (c != EOF && c != ' ' && c != '\t' && c != '\n' && c != '\r') {
+    out.push_back((char)c);
+    c = fgetc(f);
+  }
+  return !out.empty();
+}
+
+static bool texture_size_ok(int w, int h) { return w >= 1 && w <= 16384 && h >= 1 && h <= 16384; }
+
+bool load_ppm(const std::string& path, Texture& out, std::string& err) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    err = "File " + path + " open failed.";
+    return false;
+  }
+  std::string magic, sw, sh, smax;
+  const bool head = pnm_token(f, magic) && pnm_token(f, sw) && pnm_token(f, sh) && pnm_token(f, smax);
+  const int w = head ? atoi(sw.c_str()) : 0, h = head ? atoi(sh.c_str()) : 0;
+  if (!head || magic != "P6" || atoi(smax.c_str()) != 255 || !texture_size_ok(w, h)) {
+    fclose(f);
+    err = "File " + path + ": not a P6 image of 8 bits per channel, 1 .. 16384 texels a side";
+    return false;
+  }
+  std::vector<uint8_t> bytes((size_t)3 * w * h);
+  const bool ok = fread(bytes.data(), 1, bytes.size(), f) == bytes.size();
+  fclose(f);
+  if (!ok) {
+    err = "File " + path + ": truncated";
+    return false;
+  }
+  float decode[256];
+  for (int i = 0; i < 256; ++i) {
+    const double c = i / 255.0;
+    decode[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
+  }
+  out.width = w;
+  out.height = h;
+  out.rgb.resize(bytes.size());
+  for (size_t i = 0; i < bytes.size(); ++i) out.rgb[i] = decode[bytes[i]];
+  return true;
+}
+
+bool load_pfm(const std::string& path, Texture& out, std::string& err) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    err = "File " + path + " open failed.";
+    return false;
+  }
+  std::string magic, sw, sh, sscale;
+  const bool head = pnm_token(f, magic) && pnm_token(f, sw) && pnm_token(f, sh) && pnm_token(f, sscale);
+  const int w = head ? atoi(sw.c_str()) : 0, h = head ? atoi(sh.c_str()) : 0;
+  const double scale = head ? atof(sscale.c_str()) : 0.0;
+  if (!head || magic != "PF" || scale == 0.0 || !texture_size_ok(w, h)) {
+    fclose(f);
+    err = "File " + path + ": not a PF image, 1 .. 16384 texels a side";
+    return false;
+  }
+  std::vector<uint8_t> bytes((size_t)12 * w * h);
+  const bool ok = fread(bytes.data(), 1, bytes.size(), f) == bytes.size();
+  fclose(f);
+  if (!ok) {
+    err = "File " + path + ": truncated";
+    return false;
+  }
+  const bool little = scale < 0.0;
+  out.width = w;
+  out.height = h;
+  out.rgb.resize((size_t)3 * w * h);
+  for (int y = 0; y < h; ++y)  // the file's first row is the bottom one
+    for (int i = 0; i < 3 * w; ++i) {
+      const uint8_t* b = &bytes[4 * ((size_t)(h - 1 - y) * 3 * w + i)];
+      const uint32_t u = little ? (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24
+                                : (uint32_t)b[3] | (uint32_t)b[2] << 8 | (uint32_t)b[1] << 16 | (uint32_t)b[0] << 24;
+      float v;
+      memcpy(&v, &u, 4);
+      out.rgb[(size_t)y * 3 * w + i] = v;
+    }
+  return true;
+}
+
+Texture make_texture_checker(int size, int squares, const float a[3], const float b[3]) {
+  Texture t;
+  if (size < 1) size = 1;
+  if (squares < 1) squares = 1;
+  t.width = t.height = size;
+  t.rgb.resize((size_t)3 * size * size);
+  for (int y = 0; y < size; ++y)
+    for (int x = 0; x < size; ++x) {
+      const int cell = (int)((int64_t)x * squares / size) + (int)((int64_t)y * squares / size);
+      const float* c = (cell & 1) ? b : a;
+      for (int k = 0; k < 3; ++k) t.rgb[3 * ((size_t)y * size + x) + k] = c[k];
+    }
+  return t;
+}
+
 // ---------------------------------------------------- built-in configurations ----
 
 static Material jade_material() {  // PathTrace.cpp:981-989
