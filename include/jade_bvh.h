@@ -900,6 +900,65 @@ int jade_scene_set_textures(jade_scene* scene, int32_t n_images, const jade_text
                             int32_t n_triangles);
 int jade_scene_get_textures(jade_scene* scene, int* set);
 
+/* ---- Normal maps: tangent-space images bend the shading normal at every path vertex ----
+ *
+ * Non-parity.  Vertex normals give a surface a normal that varies over a triangle and textures a colour that does; relief - the grain of a
+ * carved statue, the joints of a tiled floor - still takes triangles, and those are what k_trace pays for.  jade_scene_set_normal_maps
+ * gives the handle n_images images of tangent-space vectors (x, y, z) per texel, ALREADY DECODED (the 2c - 1 of an 8-bit file is the host
+ * loader's: load_normal_map), in the layout and within the size limits of jade_scene_set_textures; six floats of UV and an image number
+ * per triangle, the map's OWN - independent of the albedo table's; -1 for a triangle without a map - and a strength, finite and >= 0,
+ * that scales x and y.  n_images = 0 or a NULL array clears.  The table is a property of the handle, taken by the next jade_render_begin
+ * like the vertex normals and the textures; a render in progress keeps the table - and the strength - it began with.
+ * JADE_ERR_INVALID, with a message that names the offender, and the handle's table left as it was: an n_triangles that is not the scene's,
+ * an image_of outside [-1, n_images), a width or height outside 1 .. 16384, more than 65 536 images, a texel that is not finite, a strength
+ * that is not finite or is negative.  UVs that are not finite are NOT refused (the statement says what they give).  Texels are not
+ * normalised and need not be: the statement normalises what it forms.  jade_scene_get_normal_maps: *set = 1 if a table is set.  A table
+ * that maps no triangle, like no table, is today's render in every kernel, bit and counter.
+ *
+ * ---- The mapped normal, stated ----
+ * tests/normal_map_spec.py is this text in float64, the per-vertex arithmetic in emulated fp32 as well.  fl(), fma() and dot() as in "The
+ * surface colour, stated"; normal(triangle, p, r), ns, g and the side rule as in "The shading normal, stated"; uv() and colour() as in
+ * "The surface colour, stated".
+ *
+ * The record of a triangle, made when the table is set.  Its UV part is the texture record's, statement for statement, from the map's UVs:
+ * d2, d3, uv1, du2, du3.  Then, in double from the fp32 corners and the record's fp32 du2 and du3:
+ *   det = du2.x * du3.y - du3.x * du2.y
+ *   T = (e1 * du3.y - e2 * du2.y) / det        B = (e2 * du2.x - e1 * du3.x) / det
+ * each divided by its length and rounded to fp32 once per component.  They are dP/du and dP/dv: constant over the triangle, NOT made
+ * orthogonal to each other or to any normal, NOT interpolated - a sheared UV layout shears the relief with it, as it shears the image.
+ * The triangle is UNMAPPED, and stored with image -1, if it names no image, if NN is not in (0, inf), if det is zero or not finite, or
+ * if the length of T or of B is not in (0, inf).
+ *
+ * normal'(triangle, p, r) stands for normal(triangle, p, r) at EVERY use, when a map table is set:
+ *   1. An unmapped triangle: normal(triangle, p, r).  It costs the first 16 bytes of its record, then what normal() costs.
+ *   2. (u, v) = uv(triangle, p) with the map's record.  If u or v is NaN or infinite: as unmapped.
+ *   3. m = colour(the map's image, u, v) by the fetch statement, operation for operation.
+ *   4. mx = fl(strength * m.x);  my = fl(strength * m.y);  mz = m.z.
+ *   5. If mx == 0 && my == 0, or any of mx my mz is NaN: as unmapped, and nothing below is formed.  So a texel (0, 0, z) - whatever z,
+ *      negative included - and a strength of 0 give today's normal bit for bit.
+ *   6. The base nb: the ns of normal(triangle, p, r) BEFORE its side rule; where the triangle is FLAT or the sum rule fails,
+ *      g / sqrt(dot(g, g)), the division per component; and if dot(g, g) is not in (0, inf): as unmapped.
+ *   7. t = fma(mz, nb, fma(my, B, fl(mx * T))) per component;  tt = dot(t, t);  if !(tt > 0 && tt < inf): as unmapped;  nm = t / sqrt(tt).
+ *   8. The side rule, as a cascade: a = dot(nm, r), b = dot(g, r); if (a > 0 && b > 0) || (a < 0 && b < 0) the result is nm.  Otherwise
+ *      it is normal(triangle, p, r) - ns under its own side rule, and then g.
+ * Everything "The shading normal, stated" says after the normal stays, word for word, with normal' for normal: directions the normal forms
+ * are formed again with g unless they leave on the right side; drawn directions are made against normal' and culled against g; all draws
+ * come before the tests, so a sample's stream positions are the flat render's; an emitter's own normal stays g; the guide pass follows its
+ * mirror chain with normal' and its normal guide is normal', turned towards the viewer.  A map changes rays through these rules only.
+ * The codes jade_smooth.h's SMOOTH_RULE_* gain: MAPPED (nm), MAP_ZERO (step 5), MAP_SUM (steps 6 and 7), MAP_SIDE_NS (step 8 gave ns).
+ *
+ * A mapped render runs the kernels and the schedule of a textured render (above) - with the handle's textures or, where it names no
+ * image, a table that names none; with its vertex normals or the flat ones: no fused first pass, no k_tail.  jade_render_begin takes a
+ * table that maps a triangle with the three environment samplings, with JADE_BOUNCE_COSINE and with a lens (not both), and refuses it with
+ * JADE_ERR_UNSUPPORTED together with a shutter, JADE_LIGHTS_ONE, JADE_DIRECT_MIS, passes or JADE_BRANCH_STRATIFIED, after the other
+ * modes' own refusals, in the words of smooth shading or of textures where the handle carries those and in its own name otherwise.
+ * jade_render_multi: every scene's handle carries such a table or none does, else JADE_ERR_INVALID.  The oracle backend has no such entry.
+ * Not here: mip maps or any filtering by footprint; interpolated or orthogonalised tangents; displacement - the surface a ray hits is
+ * the triangle's, and only its normal bends. */
+int jade_scene_set_normal_maps(jade_scene* scene, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of,
+                               int32_t n_triangles, float strength);
+int jade_scene_get_normal_maps(jade_scene* scene, int* set);
+
 #ifdef __cplusplus
 }
 #endif

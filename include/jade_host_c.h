@@ -96,6 +96,21 @@ int jadeh_project_uvs(const float* verts, int nv, const int* idx, int nt, int pr
 int jadeh_load_obj_textured(const char* path, int* nv, int* nt, int* has_uv, float* verts, int* idx, float* uv6);
 int jadeh_scene_textures(const jadeh_scene* s, const float** uv, const int32_t** image_of);
 int jadeh_scene_texture(const jadeh_scene* s, int k, int* width, int* height, const float** rgb);
+
+/* Normal maps (include/jade_bvh.h, jade_scene_set_normal_maps).  A map is a jadeh_texture of tangent-space vectors (x, y, z), decoded:
+ * jadeh_normal_map_load reads a P6 file LINEARLY - no sRGB decode - as 2 c - 1 per channel, or a PF file as given;
+ * jadeh_height_to_normal_map makes the map of the surface z = scale * height(u, v) from width x height heights (row 0 at v = 0) by
+ * central differences, the image repeating at its borders: (0 - scale dh/du, 0 - scale dh/dv, 1), not normalised - a constant height
+ * gives (0, 0, 1) exactly.  NULL on failure; freed with jadeh_texture_free, read with jadeh_texture_get.
+ * jadeh_builder_set_normal_map / jadeh_builder_set_object_normal_map: as the two texture setters, with the map's own UVs - the mesh's
+ * or the projection's - independent of the albedo texture; the table has one strength (finite, >= 0), the last one given.
+ * jadeh_scene_normal_maps / jadeh_scene_normal_map: the built scene's table in BVH order, as jadeh_scene_textures / jadeh_scene_texture. */
+jadeh_texture* jadeh_normal_map_load(const char* path);
+jadeh_texture* jadeh_height_to_normal_map(int width, int height, const float* heights, float scale);
+int jadeh_builder_set_normal_map(jadeh_builder* b, const jadeh_texture* t, int projection, float strength);
+int jadeh_builder_set_object_normal_map(jadeh_builder* b, int object, const jadeh_texture* t, int projection, float strength);
+int jadeh_scene_normal_maps(const jadeh_scene* s, const float** uv, const int32_t** image_of, float* strength);
+int jadeh_scene_normal_map(const jadeh_scene* s, int k, int* width, int* height, const float** xyz);
 int jadeh_builder_set_env_constant(jadeh_builder* b, float r, float g, float bl);
 int jadeh_builder_set_env_sky(jadeh_builder* b, int w, int h);
 int jadeh_builder_set_env_data(jadeh_builder* b, int w, int h, const float* rgb);

@@ -237,6 +237,9 @@ BVH_SYMBOLS = {
     # the textures of a scene handle (scene, n_images, images, 6 floats of uv per triangle, an image number per triangle, n_triangles) / (scene, out: 1 if set)
     "jade_scene_set_textures": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(TextureImage), C.c_void_p, C.c_void_p, C.c_int32]),
     "jade_scene_get_textures": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    # the normal maps of a scene handle: as the textures, the map's own uv and image numbers, and a strength / (scene, out: 1 if set)
+    "jade_scene_set_normal_maps": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(TextureImage), C.c_void_p, C.c_void_p, C.c_int32, C.c_float]),
+    "jade_scene_get_normal_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
 }
 
 HOST_SYMBOLS = {
@@ -266,6 +269,13 @@ HOST_SYMBOLS = {
     "jadeh_load_obj_textured": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]),
     "jadeh_scene_textures": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "jadeh_scene_texture": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
+    # normal maps: images (load / heights -> handle), the builder's current map and an object's, the built scene's table
+    "jadeh_normal_map_load": (C.c_void_p, [C.c_char_p]),
+    "jadeh_height_to_normal_map": (C.c_void_p, [C.c_int, C.c_int, C.c_void_p, C.c_float]),
+    "jadeh_builder_set_normal_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_float]),
+    "jadeh_builder_set_object_normal_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float]),
+    "jadeh_scene_normal_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_float)]),
+    "jadeh_scene_normal_map": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "jadeh_builder_set_env_constant": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float]),
     "jadeh_builder_set_env_sky": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "jadeh_builder_set_env_data": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

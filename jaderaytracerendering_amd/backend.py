@@ -241,6 +241,12 @@ class Scene:
             except Exception:
                 self.close()
                 raise
+        if getattr(host_scene, "normal_maps", None) is not None:  # ... and its normal maps: (images, uv, image_of, strength)
+            try:
+                self.set_normal_maps(*host_scene.normal_maps)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -536,6 +542,35 @@ class Scene:
     def textures(self):
         """jade_scene_get_textures: whether the handle carries a texture table."""
         fn = self._hip_only("jade_scene_get_textures")
+        on = C.c_int(-1)
+        self.backend.check(fn(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_normal_maps(self, images, uv=None, image_of=None, strength=1.0):
+        """jade_scene_set_normal_maps: images - a list of float32 [height, width, 3] arrays of tangent-space vectors (x, y, z), already
+        decoded (host.load_normal_map, host.height_to_normal_map), row 0 at v = 0; uv - float32 [n_triangles, 3, 2] and image_of - int32
+        [n_triangles], the map's own, -1 for a triangle without a map; strength - finite and >= 0, scales x and y.  None (or no images)
+        clears.  The next render this handle begins bends the shading normal of every path vertex on a mapped triangle (HIP module only;
+        include/jade_bvh.h, "The mapped normal, stated"); a table that maps no triangle is today's render bit for bit."""
+        fn = self._hip_only("jade_scene_set_normal_maps")
+        if images is None or len(images) == 0:
+            self.backend.check(fn(self._h, 0, None, None, None, 0, 1.0))
+            return
+        imgs = [np.ascontiguousarray(im, np.float32) for im in images]
+        for k, im in enumerate(imgs):
+            if im.ndim != 3 or im.shape[2] != 3:
+                raise JadeError(_abi.JADE_ERR_INVALID, f"normal maps: image {k} is not [height, width, 3]")
+        arr = (_abi.TextureImage * len(imgs))(*[_abi.TextureImage(im.shape[1], im.shape[0], C.cast(im.ctypes.data, C.POINTER(C.c_float))) for im in imgs])
+        u = np.ascontiguousarray(uv, np.float32)
+        io = np.ascontiguousarray(image_of, np.int32).reshape(-1)
+        if u.size != 6 * io.size:
+            raise JadeError(_abi.JADE_ERR_INVALID, "normal maps: 6 floats of uv and one image number per triangle")
+        self.backend.check(fn(self._h, len(imgs), arr, u.ctypes.data, io.ctypes.data, io.size, float(strength)))
+
+    @property
+    def normal_maps(self):
+        """jade_scene_get_normal_maps: whether the handle carries a normal-map table."""
+        fn = self._hip_only("jade_scene_get_normal_maps")
         on = C.c_int(-1)
         self.backend.check(fn(self._h, C.byref(on)))
         return bool(on.value)

@@ -13,6 +13,7 @@
 #pragma clang diagnostic ignored "-Wunneeded-internal-declaration"  // jade_shade.h's non-inline statics this file does not call
 #include "jade_shade.h"
 #include "jade_smooth.h"
+#include "jade_normal_map.h"
 #pragma clang diagnostic pop
 
 #if JADE_DEBUG_EXPORTS
@@ -350,6 +351,16 @@ __global__ void k_debug_texture_fetch(int n, const float4* texels, const uint4* 
 __global__ void k_debug_surface_colour(int n, TexTables T, const int32_t* tri, const float* p, float* out_rgb) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) put3(out_rgb, i, surface_colour(T, tri[i], V3(p + (size_t)3 * i)));
+}
+
+// the mapped normal of row i (jade_debug_mapped_normal, below): normal'(tri[i], p[i], r[i]) with the triangle's stored flat normal.  The host checks every index.
+__global__ void k_debug_mapped_normal(int n, MapTables T, const float4* tnorm, const int32_t* tri, const float* p, const float* r, float* out_n, int32_t* out_rule) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 tn = tnorm[tri[i]];
+  int32_t rule = -1;
+  put3(out_n, i, mapped_normal_rule(T, tri[i], jv(tn.x, tn.y, tn.z), V3(p + (size_t)3 * i), V3(r + (size_t)3 * i), &rule));
+  out_rule[i] = rule;
 }
 
 static const int32_t kDebugMaxRows = 1 << 22;  // rows per call: every index above stays far below 2^31
@@ -973,6 +984,59 @@ int jade_debug_surface_colour(jade_scene* s, int32_t n, const int32_t* tri, cons
   hipLaunchKernelGGL(k_debug_surface_colour, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, d.T, bt.as<int32_t>(), bp.as<float>(), bo.as<float>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(out_rgb, bo.p, 12 * N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  return JADE_OK;
+}
+
+// ... and with whether the handle carries normal maps in which a triangle is mapped (jade_scene_set_normal_maps; tests/test_normal_map_modes_cpu.py):
+// the full rule.
+int jade_debug_shade_mode_normal_maps_host(int32_t env_sampling, int32_t lens, int32_t shutter, int32_t light_sampling, int32_t bounce_sampling, int32_t direct_sampling,
+                                           int32_t passes, int32_t branch_sampling, int32_t smooth, int32_t textures, int32_t normal_maps, uint32_t* mode) {
+  if (!mode) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (env_sampling != JADE_ENV_REFERENCE && env_sampling != JADE_ENV_IMPORTANCE && env_sampling != JADE_ENV_MIXTURE)
+    return jade_fail(JADE_ERR_INVALID, "unknown env_sampling (JADE_ENV_*)");
+  if (branch_sampling != JADE_BRANCH_RANDOM && branch_sampling != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
+  uint32_t m = 0;
+  std::string why;
+  if (const int rc = shade_mode_for(env_sampling, lens != 0, shutter != 0, light_sampling, bounce_sampling, direct_sampling, &m, &why, passes != 0,
+                                    branch_sampling == JADE_BRANCH_STRATIFIED, smooth != 0, textures != 0, normal_maps != 0))
+    return jade_fail(rc, why);
+  *mode = m;
+  return JADE_OK;
+}
+
+// The mapped normal (mapped_normal_rule, jade_normal_map.h; include/jade_bvh.h "The mapped normal, stated") on n rows, with the tables the handle
+// carries as jade_scene_set_normal_maps and jade_scene_set_vertex_normals left them, joined as jade_render_begin joins them (no render is begun;
+// tests/test_gpu_normal_map.py): out_n[i] = normal'(tri[i], points[i], refs[i]), out_rule[i] = the SMOOTH_RULE_* that gave it.
+int jade_debug_mapped_normal(jade_scene* s, int32_t n, const int32_t* tri, const float* points, const float* refs, float* out_n, int32_t* out_rule) {
+  if (!s || !tri || !points || !refs || !out_n || !out_rule) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n <= 0 || n > kDebugMaxRows / 4) return jade_fail(JADE_ERR_INVALID, "row count out of range");
+  if (s->nmap_rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no normal maps (jade_scene_set_normal_maps)");
+  const size_t n_tris = s->nmap_rec.size() / JADE_NMAP_REC;
+  for (int32_t i = 0; i < n; ++i)
+    if (tri[i] < 0 || (size_t)tri[i] >= n_tris) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": index out of range");
+  HIP_TRY(hipSetDevice(s->device));
+  const bool smooth = !s->smooth_rec.empty();
+  std::vector<float4> rec(s->nmap_rec), flat;
+  for (size_t i = 0; i < n_tris; ++i) normal_map_join(&rec[i * JADE_NMAP_REC], smooth ? &s->smooth_rec[i * JADE_SMOOTH_REC] : nullptr);
+  if (!smooth) flat.assign(n_tris * JADE_SMOOTH_REC, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  DevBuf brec, btex, bimg, bsm, bt, bp, br, bn, bo;
+  HIP_TRY(upload(brec, rec.data(), rec.size(), s->stream));
+  HIP_TRY(upload(btex, s->nmap_texels.data(), s->nmap_texels.size(), s->stream));
+  HIP_TRY(upload(bimg, s->nmap_images.data(), s->nmap_images.size(), s->stream));
+  HIP_TRY(upload(bsm, smooth ? s->smooth_rec.data() : flat.data(), n_tris * JADE_SMOOTH_REC, s->stream));
+  const size_t N = (size_t)n;
+  HIP_TRY(upload(bt, tri, N, s->stream));
+  HIP_TRY(upload(bp, points, 3 * N, s->stream));
+  HIP_TRY(upload(br, refs, 3 * N, s->stream));
+  HIP_TRY(bn.alloc(12 * N));
+  HIP_TRY(bo.alloc(4 * N));
+  const MapTables T{TexTables{bsm.as<float4>(), nullptr, nullptr, nullptr}, brec.as<float4>(), btex.as<float4>(), bimg.as<uint4>(), s->nmap_strength};
+  hipLaunchKernelGGL(k_debug_mapped_normal, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, T, s->b_tnorm.as<float4>(), bt.as<int32_t>(), bp.as<float>(),
+                     br.as<float>(), bn.as<float>(), bo.as<int32_t>());
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_n, bn.p, 12 * N, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipMemcpyAsync(out_rule, bo.p, 4 * N, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(hipStreamSynchronize(s->stream));
   return JADE_OK;
 }

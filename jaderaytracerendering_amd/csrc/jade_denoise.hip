@@ -22,6 +22,7 @@
 #include <cstring>
 
 #include "jade_lanes.h"
+#include "jade_normal_map.h"
 #include "jade_runtime.h"
 #include "jade_smooth.h"
 #include "jade_texture.h"
@@ -225,6 +226,62 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_smooth(DevScene S,
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_textured(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
                                                                        uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
                                                                        uint32_t* next_queue, uint32_t* next_count, TexTables table) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= *count) return;
+  const int p = (int)queue[i];
+  const float4 sl = G.slot[p];
+  const jvec3 d = jv(sl.x, sl.y, sl.z);
+  const int h = __float_as_int(sl.w);
+  float4 st = state[p];
+  jvec3 t = jv(st.x, st.y, st.z);
+  float z = st.w;
+  jvec3 a, n;
+  if (h < 0) {
+    a = t;
+    n = jv(0.0f, 0.0f, 0.0f);
+    z = 0.0f;
+  } else {
+    const float4 hp = G.hitp[p];
+    const float4 tn = S.tnorm[h];
+    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
+    const jvec3 flat = jv(tn.x, tn.y, tn.z);
+    const jvec3 o = jv_neg(d);
+    const jvec3 norm = shading_normal(table, h, flat, jv(hp.x, hp.y, hp.z), o);
+    const jvec3 brdf = jv_mul(V3(m->brdf), surface_colour(table, h, jv(hp.x, hp.y, hp.z)));
+    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
+    const uint32_t k = mirrors[p];
+    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
+      t = jv_mul(t, brdf);
+      z = z + hp.w;
+      jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);
+      if (!same_side(refl, o, flat)) refl = jv_sub(jv_scale(flat, 2 * jv_dot(o, flat)), o);
+      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
+      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
+      state[p] = make_float4(t.x, t.y, t.z, z);
+      mirrors[p] = k + 1u;
+      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
+      return;
+    }
+    z = z + hp.w;
+    a = jv_mul(t, brdf);
+    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
+  }
+  float4 s0 = acc_az[p], s1 = acc_n[p];
+  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
+  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
+  if (last) {
+    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
+    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
+  }
+  acc_az[p] = s0;
+  acc_n[p] = s1;
+}
+
+// ... in a mapped render (SM_NMAP; include/jade_bvh.h, "The mapped normal, stated"): k_guide_hits_textured with the mapped normal of the hit - in the
+// mirror chain and in the normal guide; `table` carries the map's tables beside the textured render's.  A fourth text, for the same reason.
+__global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_mapped(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
+                                                                     uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
+                                                                     uint32_t* next_queue, uint32_t* next_count, MapTables table) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= *count) return;
   const int p = (int)queue[i];
@@ -538,7 +595,11 @@ static int dn_guides(jade_scene* s, int G) {
       HIP_TRY(hipGetLastError());
       HIP_TRY(hipMemsetAsync(qc + (cur ^ 1), 0, sizeof(QueueCtl), s->stream));
       uint32_t* next_queue = s->b_dn_q[qi].as<uint32_t>();
-      if (textures_on(s))
+      if (normal_maps_on(s))
+        hipLaunchKernelGGL(k_guide_hits_mapped, dim3(dn_grid(count)), dim3(JADE_DN_BLOCK), 0, s->stream, s->dev, g, queue, &qc[cur].count, state, mirrors,
+                           s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count,
+                           map_tables(s));
+      else if (textures_on(s))
         hipLaunchKernelGGL(k_guide_hits_textured, dim3(dn_grid(count)), dim3(JADE_DN_BLOCK), 0, s->stream, s->dev, g, queue, &qc[cur].count, state, mirrors,
                            s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count,
                            texture_tables(s));

@@ -180,6 +180,8 @@ __global__ __launch_bounds__(JADE_ARM_BLOCK) void k_arm(PathState P, uint32_t ta
 // A.smooth() (jade_smooth_shade.h), where the bounce and the fold stand a second time with it.  Nothing of it travels with the record.
 // SM_TEX (with SM_SMOOTH): A.smooth() carries the texture tables as well (jade_texture.h) and the same family multiplies the surface colour at (c.obj, c.src)
 // into every brdf and refract_albedo it reads ("The surface colour, stated"); the lean kernel's mirror fold is consume_mirror_textured.
+// SM_NMAP (with SM_TEX | SM_SMOOTH): A.smooth() carries the normal map's tables as well (jade_normal_map.h) and the family's one call for the normal
+// resolves to the mapped normal ("The mapped normal, stated").
 template <bool LEAN, uint32_t M = 0>
 static __device__ __forceinline__ void shade_record(const DevScene& S, const PathState& P, const RenderConst& R, const int32_t* tile_ids,
                                                     uint32_t target_spp, const int p, ShadeCtx& c, uint32_t& st_out, bool& defer,
@@ -1525,6 +1527,7 @@ int jade_scene_set_vertex_normals(jade_scene* s, const float* normals, int32_t n
     s->smooth_rec.shrink_to_fit();
     s->smooth_any = false;
     s->smooth_uploaded = false;
+    s->nmap_uploaded = false;  // (a normal map's records carry the vertex normals: jade_normal_map.h)
     return JADE_OK;
   }
   if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "vertex normals: the triangle count is not the scene's");
@@ -1544,6 +1547,7 @@ int jade_scene_set_vertex_normals(jade_scene* s, const float* normals, int32_t n
   s->smooth_rec.swap(rec);
   s->smooth_any = any;
   s->smooth_uploaded = false;
+  s->nmap_uploaded = false;
   return JADE_OK;
 }
 int jade_scene_get_vertex_normals(jade_scene* s, int* set) {
@@ -1614,6 +1618,78 @@ int jade_scene_set_textures(jade_scene* s, int32_t n_images, const jade_texture_
 int jade_scene_get_textures(jade_scene* s, int* set) {
   if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
   *set = s->tex_rec.empty() ? 0 : 1;
+  return JADE_OK;
+}
+
+// The normal maps of the scene handle (include/jade_bvh.h, "The mapped normal, stated"): the records and the texel buffer (jade_normal_map.h) are
+// made here as the textures' are, checked in the same order and refused in the same way; the vertex normals a mapped vertex bends are joined to the
+// records by the next jade_render_begin, which uploads them.
+int jade_scene_set_normal_maps(jade_scene* s, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of, int32_t n_triangles,
+                               float strength) {
+  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
+  if (n_images == 0 || !images || !uv || !image_of) {
+    for (auto* v : {&s->nmap_rec, &s->nmap_texels}) {
+      v->clear();
+      v->shrink_to_fit();
+    }
+    s->nmap_images.clear();
+    s->nmap_any = false;
+    s->nmap_uploaded = false;
+    return JADE_OK;
+  }
+  if (!(strength >= 0.0f && strength < INFINITY))
+    return jade_fail(JADE_ERR_INVALID, "normal maps: the strength " + std::to_string(strength) + " is not finite and >= 0");
+  if (n_images < 0 || n_images > JADE_TEX_MAX_IMAGES)
+    return jade_fail(JADE_ERR_INVALID, "normal maps: " + std::to_string(n_images) + " images (at most " + std::to_string(JADE_TEX_MAX_IMAGES) + ")");
+  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "normal maps: the triangle count " + std::to_string(n_triangles) + " is not the scene's");
+  std::vector<uint4> heads((size_t)n_images);
+  size_t total = 0;
+  for (int32_t k = 0; k < n_images; ++k) {
+    const jade_texture_image& im = images[k];
+    if (im.width < 1 || im.width > JADE_TEX_MAX_SIZE || im.height < 1 || im.height > JADE_TEX_MAX_SIZE)
+      return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " is " + std::to_string(im.width) + " x " + std::to_string(im.height) +
+                                             " (a width and a height of 1 .. " + std::to_string(JADE_TEX_MAX_SIZE) + ")");
+    if (!im.rgb) return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " has no texels");
+    heads[k] = make_uint4((uint32_t)(total & 0xffffffffu), (uint32_t)(total >> 32), (uint32_t)im.width, (uint32_t)im.height);
+    total += (size_t)im.width * (size_t)im.height;
+  }
+  for (int32_t t = 0; t < n_triangles; ++t)
+    if (image_of[t] < -1 || image_of[t] >= n_images)
+      return jade_fail(JADE_ERR_INVALID, "normal maps: image_of[" + std::to_string(t) + "] = " + std::to_string(image_of[t]) + " is outside -1 .. " + std::to_string(n_images - 1));
+  std::vector<float4> texels(total);
+  for (int32_t k = 0; k < n_images; ++k) {
+    const size_t first = ((size_t)heads[k].y << 32) | heads[k].x, n = (size_t)heads[k].z * heads[k].w;
+    const float* xyz = images[k].rgb;
+    for (size_t i = 0; i < n; ++i) {
+      if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !std::isfinite(xyz[3 * i + 2]))
+        return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " has a texel that is not finite at (" + std::to_string(i % heads[k].z) + ", " +
+                                               std::to_string(i / heads[k].z) + ")");
+      texels[first + i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
+    }
+  }
+  HIP_TRY(hipSetDevice(s->device));
+  std::vector<jade_triangle> tris((size_t)n_triangles);
+  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(hipStreamSynchronize(s->stream));
+  std::vector<float4> rec(tris.size() * JADE_NMAP_REC);
+  bool any = false;
+  for (size_t i = 0; i < tris.size(); ++i) {
+    normal_map_record(tris[i].p1, tris[i].p2, tris[i].p3, uv + 6 * i, image_of[i], &rec[i * JADE_NMAP_REC]);
+    int32_t stored;
+    memcpy(&stored, &rec[i * JADE_NMAP_REC].w, 4);
+    any = any || stored >= 0;  // (a triangle whose frame cannot be formed is stored unmapped)
+  }
+  s->nmap_rec.swap(rec);
+  s->nmap_texels.swap(texels);
+  s->nmap_images.swap(heads);
+  s->nmap_strength = strength;
+  s->nmap_any = any;
+  s->nmap_uploaded = false;
+  return JADE_OK;
+}
+int jade_scene_get_normal_maps(jade_scene* s, int* set) {
+  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
+  *set = s->nmap_rec.empty() ? 0 : 1;
   return JADE_OK;
 }
 
@@ -1710,23 +1786,43 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any, s->tex_any))
+                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any, s->tex_any,
+                                    s->nmap_any))
     return jade_fail(rc, why);
   if ((mode & SM_PASSES) && s->tun.pixel_rotate)
     return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
   HIP_TRY(hipSetDevice(s->device));
-  if ((mode & SM_TEX) && !s->tex_uploaded) {  // the same rule for the textures
+  if ((mode & SM_TEX) && s->tex_any && !s->tex_uploaded) {  // the same rule for the textures
     s->have_rp = false;
     HIP_TRY(upload(s->b_tex_rec, s->tex_rec.data(), s->tex_rec.size(), s->stream));
     HIP_TRY(upload(s->b_tex_texels, s->tex_texels.data(), s->tex_texels.size(), s->stream));
     HIP_TRY(upload(s->b_tex_images, s->tex_images.data(), s->tex_images.size(), s->stream));
-    if (!s->b_tex_flat.p) {
-      const size_t bytes = sizeof(float4) * JADE_SMOOTH_REC * (size_t)s->dev.n_tris;
-      HIP_TRY(s->b_tex_flat.alloc(bytes));
-      HIP_TRY(hipMemsetAsync(s->b_tex_flat.p, 0, bytes, s->stream));
-    }
     s->tex_uploaded = true;
   }
+  if ((mode & SM_TEX) && !s->b_tex_flat.p) {
+    const size_t bytes = sizeof(float4) * JADE_SMOOTH_REC * (size_t)s->dev.n_tris;
+    HIP_TRY(s->b_tex_flat.alloc(bytes));
+    HIP_TRY(hipMemsetAsync(s->b_tex_flat.p, 0, bytes, s->stream));
+  }
+  if (mode & SM_TEX) s->tex_none = !s->tex_any;
+  if ((mode & SM_NMAP) && s->tex_none && !s->b_tex_none.p) {  // a mapped render of a handle that names no image: texture records that say so (image -1, the 16 bytes such a vertex reads)
+    const int32_t no_image = -1;
+    float w;
+    memcpy(&w, &no_image, 4);
+    const std::vector<float4> none((size_t)s->dev.n_tris * JADE_TEX_REC, make_float4(0.0f, 0.0f, 0.0f, w));
+    HIP_TRY(upload(s->b_tex_none, none.data(), none.size(), s->stream));
+  }
+  if ((mode & SM_NMAP) && !s->nmap_uploaded) {  // ... and for the normal maps, whose records carry the vertex normals the handle has now (normal_map_join)
+    s->have_rp = false;
+    std::vector<float4> rec(s->nmap_rec);
+    const size_t n = rec.size() / JADE_NMAP_REC;
+    for (size_t i = 0; i < n; ++i) normal_map_join(&rec[i * JADE_NMAP_REC], s->smooth_any ? &s->smooth_rec[i * JADE_SMOOTH_REC] : nullptr);
+    HIP_TRY(upload(s->b_nmap_rec, rec.data(), rec.size(), s->stream));
+    HIP_TRY(upload(s->b_nmap_texels, s->nmap_texels.data(), s->nmap_texels.size(), s->stream));
+    HIP_TRY(upload(s->b_nmap_images, s->nmap_images.data(), s->nmap_images.size(), s->stream));
+    s->nmap_uploaded = true;
+  }
+  if (mode & SM_NMAP) s->nmap_strength_on = s->nmap_strength;
   if ((mode & SM_SMOOTH) && s->smooth_any && !s->smooth_uploaded) {  // the handle's table as it is now: the render keeps it whatever the setter is told before the next begin
     s->have_rp = false;  // (the earlier render's kernels would read the buffer that is given back here)
     HIP_TRY(upload(s->b_smooth, s->smooth_rec.data(), s->smooth_rec.size(), s->stream));
@@ -1870,7 +1966,9 @@ static ShadeArgs<K> mode_args(const jade_scene* s) {
   if constexpr (sm(K, SM_SHUTTER)) a.shutter = s->sh;
   if constexpr ((K & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0) a.light_table = s->b_light_alias.as<uint4>();
   if constexpr (sm(K, SM_MIS)) a.mis_table = s->b_mis.as<float2>();
-  if constexpr (sm(K, SM_TEX))
+  if constexpr (sm(K, SM_NMAP))
+    a.map_tables = map_tables(s);
+  else if constexpr (sm(K, SM_TEX))
     a.tex_tables = texture_tables(s);
   else if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = s->b_smooth.as<float4>();
   return a;
@@ -1891,7 +1989,7 @@ static void launch_full(jade_scene* s, uint32_t target_spp, unsigned blocks, con
 }
 template <uint32_t M>
 static void launch_lean(jade_scene* s, uint32_t target_spp, uint32_t* heavy_out, QueueCtl* qc) {
-  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH | SM_SMOOTH | SM_TEX);  // (the camera arm, the passes, the mirror's shared-out roulette, its shading normal and its colour are all of a mode the lean kernel carries)
+  constexpr uint32_t K = shade_kernel_mode(M) & (SM_LENS | SM_SHUTTER | SM_PASSES | SM_BRANCH | SM_SMOOTH | SM_TEX | SM_NMAP);  // (the camera arm, the passes, the mirror's shared-out roulette, its shading normal - mapped or not - and its colour are all of a mode the lean kernel carries)
   auto go = [&](auto kernel, auto... a) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)((s->ps.npix + JADE_LEAN_BLOCK - 1) / JADE_LEAN_BLOCK)), dim3(JADE_LEAN_BLOCK), 0, s->stream, s->dev, s->ps, s->rc,
                        s->b_tiles.as<int32_t>(), target_spp, heavy_out, s->b_queue.as<uint32_t>(), qc, s->b_ctr.as<DevCounters>(), a...);

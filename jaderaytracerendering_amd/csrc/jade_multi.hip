@@ -148,6 +148,10 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
   for (int i = 1; i < ndev; ++i)
     if (scenes[i]->tex_any != scenes[0]->tex_any)
       return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry textures (jade_scene_set_textures): scene " + std::to_string(i) + " against scene 0");
+  // ... and for normal maps (jade_scene_set_normal_maps, a table in which a triangle is mapped)
+  for (int i = 1; i < ndev; ++i)
+    if (scenes[i]->nmap_any != scenes[0]->nmap_any)
+      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry normal maps (jade_scene_set_normal_maps): scene " + std::to_string(i) + " against scene 0");
   // ... and none keeps passes: only the frame is gathered here (each rank renders its share and calls jade_render_passes)
   for (int i = 0; i < ndev; ++i)
     if (scenes[i]->passes)

@@ -11,6 +11,7 @@
 
 #include "jade_bvh.h"
 #include "jade_device.h"
+#include "jade_normal_map.h"
 #include "jade_texture.h"
 
 #define JADE_HIDDEN __attribute__((visibility("hidden")))
@@ -215,6 +216,7 @@ enum ShadeMode : uint32_t {
   SM_BRANCH = 256u,  // jade_scene_set_branch_sampling = JADE_BRANCH_STRATIFIED: the branch draws of a path's first two vertices shared out (include/jade_bvh.h, "The branch draws, stated")
   SM_SMOOTH = 512u,  // jade_scene_set_vertex_normals with at least one triangle that is not flat: the vertex normals interpolated at every path vertex (include/jade_bvh.h, "The shading normal, stated")
   SM_TEX = 1024u,    // jade_scene_set_textures with at least one triangle that names an image: the image filtered at every path vertex (include/jade_bvh.h, "The surface colour, stated").  Raised together with SM_SMOOTH, whose family it runs
+  SM_NMAP = 2048u,   // jade_scene_set_normal_maps with at least one mapped triangle: the tangent-space image bends the shading normal at every path vertex (include/jade_bvh.h, "The mapped normal, stated").  Raised together with SM_TEX | SM_SMOOTH, whose family it runs
 };
 // How the device code reads a mode: whether mask M carries bit b.  The shade kernels and every function they are made of (jade_shade.h,
 // jade_hip.hip) are templates over the one mask and ask by name - sm(M, SM_COSINE) - so no flag has a position to be wrong in.
@@ -226,7 +228,7 @@ static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 
   JADE_SHADE_MODE_BOTH_ENV(X, 0u) JADE_SHADE_MODE_BOTH_ENV(X, SM_LENS) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER) JADE_SHADE_MODE_BOTH_ENV(X, SM_SHUTTER | SM_LENS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_LIGHTS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_LIGHTS) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS) JADE_SHADE_MODE_BOTH_ENV(X, SM_COSINE | SM_MIS | SM_LIGHTS) \
-  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS) JADE_SHADE_MODES_BRANCH(X) JADE_SHADE_MODES_SMOOTH(X) JADE_SHADE_MODES_TEX(X)
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_PASSES | SM_COSINE | SM_MIS) JADE_SHADE_MODES_BRANCH(X) JADE_SHADE_MODES_SMOOTH(X) JADE_SHADE_MODES_TEX(X) JADE_SHADE_MODES_NMAP(X)
 // ... its rows under SM_BRANCH: the pinhole with all lights - the reference estimator, the cosine bounce, MIS - and the passes on the reference estimator
 #define JADE_SHADE_MODES_BRANCH(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_BRANCH | SM_COSINE | SM_MIS) \
@@ -237,6 +239,9 @@ static constexpr bool sm(uint32_t M, ShadeMode b) { return (M & (uint32_t)b) != 
 // ... and the same three rows with textures: a textured render runs the smooth family whether the handle carries vertex normals or not
 #define JADE_SHADE_MODES_TEX(X) \
   JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH) JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_TEX | SM_SMOOTH | SM_LENS)
+// ... and once more with normal maps: a mapped render runs the textured family whether the handle carries textures or not
+#define JADE_SHADE_MODES_NMAP(X) \
+  JADE_SHADE_MODE_BOTH_ENV(X, SM_NMAP | SM_TEX | SM_SMOOTH) JADE_SHADE_MODE_BOTH_ENV(X, SM_NMAP | SM_TEX | SM_SMOOTH | SM_COSINE) JADE_SHADE_MODE_BOTH_ENV(X, SM_NMAP | SM_TEX | SM_SMOOTH | SM_LENS)
 #define JADE_SHADE_MODE_BOTH_ENV(X, m) X((m)) X((m) | SM_ENVIS) X((m) | SM_ENVIS | SM_ENVMIX)
 static inline bool shade_mode_built(uint32_t mode) {
 #define JADE_X(m) if (mode == (m)) return true;
@@ -256,19 +261,23 @@ static inline bool shade_mode_built(uint32_t mode) {
 // bounce through the pinhole and for the reference estimator through a lens; its refusals come after all of the above, whose texts stay.
 // textures: jade_scene_set_textures with a table in which a triangle names an image.  They run the smooth family (SM_SMOOTH is raised with SM_TEX,
 // whether the handle carries vertex normals or not) and are refused where it is, in its words.
+// normal_maps: jade_scene_set_normal_maps with a table in which a triangle is mapped.  They run the textured family (SM_TEX | SM_SMOOTH are raised
+// with SM_NMAP, whatever else the handle carries) and are refused where textures are, in the same words - their own name where neither other table is set.
 static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int light_sampling, int bounce_sampling, int direct_sampling, uint32_t* mode,
-                                 std::string* why, bool passes = false, bool branch = false, bool smooth = false, bool textures = false) {
+                                 std::string* why, bool passes = false, bool branch = false, bool smooth = false, bool textures = false, bool normal_maps = false) {
   const uint32_t m = (env_sampling == JADE_ENV_IMPORTANCE ? SM_ENVIS : env_sampling == JADE_ENV_MIXTURE ? SM_ENVIS | SM_ENVMIX : 0u) | (lens ? SM_LENS : 0u) | (shutter ? SM_SHUTTER : 0u) | (light_sampling == JADE_LIGHTS_ONE ? SM_LIGHTS : 0u) |
                      (bounce_sampling == JADE_BOUNCE_COSINE ? SM_COSINE : 0u) | (direct_sampling == JADE_DIRECT_MIS ? SM_MIS : 0u) | (passes ? SM_PASSES : 0u) |
-                     (branch ? SM_BRANCH : 0u) | (smooth || textures ? SM_SMOOTH : 0u) | (textures ? SM_TEX : 0u);
+                     (branch ? SM_BRANCH : 0u) | (smooth || textures || normal_maps ? SM_SMOOTH : 0u) | (textures || normal_maps ? SM_TEX : 0u) | (normal_maps ? SM_NMAP : 0u);
   if (shade_mode_built(m)) {
     *mode = m;
     return JADE_OK;
   }
   // smooth shading's and the textures' own refusals: only where the same settings without the table are accepted - otherwise the refusal a caller
   // reads is the one they would read without it, in the same words.  With both tables on the handle the words are smooth shading's.
-  if ((m & SM_SMOOTH) && shade_mode_built(m & ~(uint32_t)(SM_SMOOTH | SM_TEX))) {
-    const std::string who = smooth ? "smooth shading (jade_scene_set_vertex_normals) does not run " : "textures (jade_scene_set_textures) do not run ";
+  if ((m & SM_SMOOTH) && shade_mode_built(m & ~(uint32_t)(SM_SMOOTH | SM_TEX | SM_NMAP))) {
+    const std::string who = smooth     ? "smooth shading (jade_scene_set_vertex_normals) does not run "
+                            : textures ? "textures (jade_scene_set_textures) do not run "
+                                       : "normal maps (jade_scene_set_normal_maps) do not run ";
     const char* built = " yet: those kernels are not built";
     if (m & SM_SHUTTER)
       *why = who + "together with a shutter (jade_scene_set_shutter)" + built;
@@ -341,6 +350,14 @@ struct jade_scene {
   bool tex_any = false, tex_uploaded = false;
   DevBuf b_tex_rec, b_tex_texels, b_tex_images, b_tex_flat;
   const float4* tex_normals = nullptr;  // ... and the vertex-normal table the textured render in progress began with: b_smooth or b_tex_flat
+  // jade_scene_set_normal_maps: the records (without their smooth part) and the images as jade_normal_map.h lays them out (empty: none set), the
+  // strength, whether any triangle is mapped, and whether b_nmap_rec holds the records joined with the vertex normals the handle has now.
+  // b_tex_none: the texture records of a mapped render whose handle names no image (every triangle -1); tex_none: the render in progress reads it
+  std::vector<float4> nmap_rec, nmap_texels;
+  std::vector<uint4> nmap_images;
+  float nmap_strength = 1.0f, nmap_strength_on = 1.0f;  // (the setter's; the render in progress's)
+  bool nmap_any = false, nmap_uploaded = false, tex_none = false;
+  DevBuf b_nmap_rec, b_nmap_texels, b_nmap_images, b_tex_none;
   // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
   // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
   uint32_t mode = 0;
@@ -421,7 +438,12 @@ static inline bool smooth_on(const jade_scene* s) { return (s->mode & SM_SMOOTH)
 static inline bool textures_on(const jade_scene* s) { return (s->mode & SM_TEX) != 0; }
 // ... and what its kernels take (jade_texture.h): the tables as jade_render_begin left them
 static inline TexTables texture_tables(const jade_scene* s) {
-  return TexTables{s->tex_normals, s->b_tex_rec.as<float4>(), s->b_tex_texels.as<float4>(), s->b_tex_images.as<uint4>()};
+  return TexTables{s->tex_normals, (s->tex_none ? s->b_tex_none : s->b_tex_rec).as<float4>(), s->b_tex_texels.as<float4>(), s->b_tex_images.as<uint4>()};
+}
+// ... the normal maps are read: a textured render (textures_on is true as well) whose kernels take the map's tables beside the others
+static inline bool normal_maps_on(const jade_scene* s) { return (s->mode & SM_NMAP) != 0; }
+static inline MapTables map_tables(const jade_scene* s) {
+  return MapTables{texture_tables(s), s->b_nmap_rec.as<float4>(), s->b_nmap_texels.as<float4>(), s->b_nmap_images.as<uint4>(), s->nmap_strength_on};
 }
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.

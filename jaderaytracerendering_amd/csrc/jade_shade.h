@@ -19,6 +19,7 @@
 #include "jade_device.h"
 #include "jade_runtime.h"  // ShadeMode and sm: the functions below that differ by render mode are templates over the mode's mask
 #include "jade_texture.h"  // TexTables: what a textured mode's argument bundle carries
+#include "jade_normal_map.h"  // MapTables: ... and a mapped mode's
 
 static __device__ __forceinline__ int mirror_index(int i, int n) {
   int m = i % (2 * n);
@@ -481,7 +482,8 @@ struct PassPlanes {
 // the exception; k_shade_lean_mode; mode_args, jade_hip.hip).  A member is there only in the modes that take it - in the others its base is the empty one, which takes
 // no space and whose accessor answers nullptr, so shade_record is one text - in this order: the pass planes under SM_PASSES; the shutter's constants under SM_SHUTTER; the
 // alias table over the scene's emitter entries under SM_LIGHTS, SM_COSINE or SM_MIS (read under SM_LIGHTS only); the per-triangle table {m, M} under SM_MIS; the
-// vertex-normal records under SM_SMOOTH - and under SM_TEX, which is raised with it, those together with the texture tables.
+// vertex-normal records under SM_SMOOTH - and under SM_TEX, which is raised with it, those together with the texture tables; under SM_NMAP, raised
+// with both, all of those together with the normal map's.
 struct ArgPlanes { PassPlanes planes; __device__ const PassPlanes* L() const { return &planes; } };
 struct NoPlanes { __device__ const PassPlanes* L() const { return nullptr; } };
 struct ArgShutter { ShutterConst shutter; __device__ const ShutterConst* H() const { return &shutter; } };
@@ -493,10 +495,11 @@ struct NoMis { __device__ const float2* mis() const { return nullptr; } };
 struct ArgSmooth { const float4* smooth_table; __device__ const float4* smooth() const { return smooth_table; } };  // SM_SMOOTH: the vertex-normal records (jade_smooth.h)
 struct NoSmooth { __device__ const float4* smooth() const { return nullptr; } };
 struct ArgTextures { TexTables tex_tables; __device__ const TexTables& smooth() const { return tex_tables; } };  // SM_TEX: the smooth family's table, with the textures (jade_texture.h)
+struct ArgNormalMaps { MapTables map_tables; __device__ const MapTables& smooth() const { return map_tables; } };  // SM_NMAP: the textured family's tables, with the normal map (jade_normal_map.h)
 template <uint32_t M>
 struct ShadeArgs : std::conditional_t<sm(M, SM_PASSES), ArgPlanes, NoPlanes>, std::conditional_t<sm(M, SM_SHUTTER), ArgShutter, NoShutter>,
                    std::conditional_t<(M & (SM_LIGHTS | SM_COSINE | SM_MIS)) != 0, ArgLights, NoLights>, std::conditional_t<sm(M, SM_MIS), ArgMis, NoMis>,
-                   std::conditional_t<sm(M, SM_TEX), ArgTextures, std::conditional_t<sm(M, SM_SMOOTH), ArgSmooth, NoSmooth>> {};
+                   std::conditional_t<sm(M, SM_NMAP), ArgNormalMaps, std::conditional_t<sm(M, SM_TEX), ArgTextures, std::conditional_t<sm(M, SM_SMOOTH), ArgSmooth, NoSmooth>>> {};
 static __device__ const ShadeArgs<0> SHADE_ARGS_NONE{};  // what mode 0 passes, by name: with a temporary on the caller's stack k_shade_lean and k_tail come out in another order
 // What consume / consume_mirror tell shade_record about the vertex they folded: cls < 0 - nothing to book (l_final is 0);
 // PASS_EMISSION / PASS_SPECULAR_SKY - *l_final is that pass's (e holds it); otherwise 3 + 4 kind + depth, the vertex's emitter pass, its sky

@@ -5,10 +5,13 @@
 // A textured mode (SM_TEX, raised with SM_SMOOTH; jade_texture.h; "The surface colour, stated") runs these texts too: `table` is then a TexTables -
 // the vertex normals together with the texture tables - in place of the `const float4*`, and the four places that read the vertex's brdf or
 // refract_albedo read them times the surface colour at the vertex, each under `if constexpr (has_textures<ST>)`: in the other modes no instruction moves.
+// A mapped mode (SM_NMAP, raised with both; jade_normal_map.h; "The mapped normal, stated") runs them a third way: `table` is a MapTables, which
+// has_textures holds for, and every shading_normal(table, ...) below resolves to that header's overload - the mapped normal.  No other text changes.
 #pragma once
 #include "jade_shade.h"
 #include "jade_smooth.h"
 #include "jade_texture.h"
+#include "jade_normal_map.h"
 
 // bounce_mirror with the vertex's shading normal n; g: its flat normal.  A reflected direction that does not leave on the side of g that
 // `out` is on is formed again with g.

@@ -31,7 +31,7 @@ struct TexTables {
   __device__ operator const float4*() const { return smooth; }
 };
 template <class ST>
-static constexpr bool has_textures = std::is_same<ST, TexTables>::value;
+static constexpr bool has_textures = std::is_base_of<TexTables, ST>::value;  // (TexTables itself, or the tables of a mapped mode that carry it: jade_normal_map.h)
 
 // The record of one triangle, as the header states it: the dual basis in double from the fp32 corners, each component rounded once (the
 // smooth record's); du2 and du3 one fp32 subtraction per component.  uv6: the corners' (u, v) in the order p1 p2 p3.  Host only.

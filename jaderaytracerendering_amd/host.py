@@ -123,6 +123,21 @@ def texture_checker(size, squares, a=(0.9, 0.9, 0.9), b=(0.1, 0.1, 0.1)):
     return _texture_array(host_lib().jadeh_texture_checker(int(size), int(squares), a.ctypes.data, b.ctypes.data))
 
 
+def load_normal_map(path):
+    """jadeh_normal_map_load: a P6 file read linearly - no sRGB decode - as 2 c - 1 per channel, or a PF file as given, as float32 [height,
+    width, 3] tangent-space vectors, row 0 the top of the image - what Scene.set_normal_maps and SceneBuilder.set_normal_map take."""
+    return _texture_array(host_lib().jadeh_normal_map_load(os.fsencode(path)))
+
+
+def height_to_normal_map(height, scale=1.0):
+    """jadeh_height_to_normal_map: float32 [H, W] heights (row 0 at v = 0) -> the map [H, W, 3] of the surface z = scale * height(u, v):
+    central differences, repeating at the borders, (-scale dh/du, -scale dh/dv, 1) unnormalised; a constant height gives (0, 0, 1) exactly."""
+    h = np.ascontiguousarray(height, np.float32)
+    if h.ndim != 2:
+        raise ValueError("heights are [height, width]")
+    return _texture_array(host_lib().jadeh_height_to_normal_map(h.shape[1], h.shape[0], h.ctypes.data, float(scale)))
+
+
 def project_uvs(vertices, indices, projection=UV_SPHERICAL):
     """jadeh_project_uvs: float32 [n_triangles, 3, 2] for a mesh without UVs - UV_PLANAR_X / _Y / _Z: the two other coordinates over the
     mesh's bounding box; UV_SPHERICAL: longitude and latitude about the box's centre, the seam mended per triangle."""
@@ -147,15 +162,17 @@ class HostScene:
     """Flattened scene: the arrays that cross the jade_rt.h boundary, and - optional, beside them - vertex_normals: float32
     [n_triangles, 3, 3] in the triangles' order, which Backend.scene() puts on the handle (Scene.set_vertex_normals), or None; and
     textures: (images - a list of float32 [height, width, 3], uv - float32 [n_triangles, 3, 2], image_of - int32 [n_triangles]) in the
-    triangles' order, which Backend.scene() puts on the handle as well (Scene.set_textures), or None."""
+    triangles' order, which Backend.scene() puts on the handle as well (Scene.set_textures), or None; and normal_maps: (images, uv,
+    image_of, strength) the same way (Scene.set_normal_maps), or None."""
 
-    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0, vertex_normals=None, textures=None):
+    def __init__(self, arrays, bvh_depth=None, build_seconds=0.0, vertex_normals=None, textures=None, normal_maps=None):
         # arrays: dict of numpy arrays (owned copies)
         self.a = arrays
         self.bvh_depth = bvh_depth
         self.build_seconds = build_seconds
         self.vertex_normals = vertex_normals
         self.textures = textures
+        self.normal_maps = normal_maps
 
     ARRAY_KEYS = ("triangles", "nodes", "emit", "mapping", "prefix", "segs", "env")
 
@@ -195,7 +212,18 @@ class HostScene:
                 images.append(np.frombuffer((C.c_char * (12 * w.value * h.value)).from_address(p.value), dtype=np.float32).copy().reshape(h.value, w.value, 3))
             tex = (images, np.frombuffer((C.c_char * (24 * nt)).from_address(pu.value), dtype=np.float32).copy().reshape(nt, 3, 2),
                    np.frombuffer((C.c_char * (4 * nt)).from_address(pi.value), dtype=np.int32).copy())
-        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle), vn, tex)
+        maps, pu, pi, strength = None, C.c_void_p(), C.c_void_p(), C.c_float(1.0)
+        n_maps = lib.jadeh_scene_normal_maps(handle, C.byref(pu), C.byref(pi), C.byref(strength))
+        if n_maps:
+            nt = d.n_triangles
+            images = []
+            for k in range(n_maps):
+                w, h, p = C.c_int(), C.c_int(), C.c_void_p()
+                _check(lib.jadeh_scene_normal_map(handle, k, C.byref(w), C.byref(h), C.byref(p)))
+                images.append(np.frombuffer((C.c_char * (12 * w.value * h.value)).from_address(p.value), dtype=np.float32).copy().reshape(h.value, w.value, 3))
+            maps = (images, np.frombuffer((C.c_char * (24 * nt)).from_address(pu.value), dtype=np.float32).copy().reshape(nt, 3, 2),
+                    np.frombuffer((C.c_char * (4 * nt)).from_address(pi.value), dtype=np.int32).copy(), float(strength.value))
+        return cls(arrays, lib.jadeh_scene_bvh_depth(handle), lib.jadeh_scene_build_seconds(handle), vn, tex, maps)
 
     @classmethod
     def from_npz(cls, path):
@@ -204,7 +232,12 @@ class HostScene:
             if "texture_uv" in z.files:
                 n = sum(1 for k in z.files if k.startswith("texture_image_") and k != "texture_image_of")
                 tex = ([z[f"texture_image_{k}"].copy() for k in range(n)], z["texture_uv"].copy(), z["texture_image_of"].copy())
-            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS}, vertex_normals=z["vertex_normals"].copy() if "vertex_normals" in z.files else None, textures=tex)
+            maps = None
+            if "normal_map_uv" in z.files:
+                n = sum(1 for k in z.files if k.startswith("normal_map_image_") and k != "normal_map_image_of")
+                maps = ([z[f"normal_map_image_{k}"].copy() for k in range(n)], z["normal_map_uv"].copy(), z["normal_map_image_of"].copy(), float(z["normal_map_strength"]))
+            return cls({k: z[k].copy() for k in cls.ARRAY_KEYS}, vertex_normals=z["vertex_normals"].copy() if "vertex_normals" in z.files else None, textures=tex,
+                       normal_maps=maps)
 
     def save_npz(self, path, **extra):
         if self.vertex_normals is not None:
@@ -213,6 +246,10 @@ class HostScene:
             images, uv, image_of = self.textures
             extra = dict(extra, texture_uv=np.asarray(uv, np.float32), texture_image_of=np.asarray(image_of, np.int32),
                          **{f"texture_image_{k}": np.asarray(im, np.float32) for k, im in enumerate(images)})
+        if self.normal_maps is not None:
+            images, uv, image_of, strength = self.normal_maps
+            extra = dict(extra, normal_map_uv=np.asarray(uv, np.float32), normal_map_image_of=np.asarray(image_of, np.int32), normal_map_strength=np.float32(strength),
+                         **{f"normal_map_image_{k}": np.asarray(im, np.float32) for k, im in enumerate(images)})
         np.savez_compressed(path, **self.a, **extra)
 
     @property
@@ -324,6 +361,20 @@ class SceneBuilder:
         """jadeh_builder_set_object_texture: the obj'th object to be added (0-based; the objects of config() count) carries `image`,
         whatever set_texture says when it arrives - what jade_render --texture OBJ=IMAGE does."""
         self._with_texture(image, lambda t: self._lib.jadeh_builder_set_object_texture(self._h, int(obj), t, int(projection)))
+
+    def set_normal_map(self, image, projection=UV_SPHERICAL, strength=1.0):
+        """jadeh_builder_set_normal_map: the meshes added from now on carry the normal map `image` (float32 [height, width, 3] tangent-space
+        vectors; None: no map again) with their own UVs or those of `projection`, as set_texture; one strength for the scene, the last
+        given.  The built HostScene then carries `normal_maps`."""
+        if image is None:
+            _check(self._lib.jadeh_builder_set_normal_map(self._h, None, int(projection), float(strength)))
+            return
+        self._with_texture(image, lambda t: self._lib.jadeh_builder_set_normal_map(self._h, t, int(projection), float(strength)))
+
+    def set_object_normal_map(self, obj, image, projection=UV_SPHERICAL, strength=1.0):
+        """jadeh_builder_set_object_normal_map: the obj'th object to be added carries the normal map `image` - what jade_render
+        --normal-map OBJ=FILE does."""
+        self._with_texture(image, lambda t: self._lib.jadeh_builder_set_object_normal_map(self._h, int(obj), t, int(projection), float(strength)))
 
     def _with_texture(self, image, call):
         im = np.ascontiguousarray(image, np.float32)

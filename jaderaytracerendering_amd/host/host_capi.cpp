@@ -89,7 +89,9 @@ int jadeh_builder_add_obj(jadeh_builder* b, const char* path, const jadeh_materi
   if (!b || !path) return fail("add_obj: bad arguments");
   Mesh m;
   std::string err;
-  if (!(b->b.texture_set() ? load_obj_textured(path, m, err) : load_obj(path, m, err))) return fail(err);
+  // (the vt lines are read where something will use them: a texture that is set, or a normal map - the builder's or this object's own)
+  const bool wants_uvs = b->b.texture_set() || b->b.normal_map_set() || b->b.object_normal_map_set(b->b.object_count());
+  if (!(wants_uvs ? load_obj_textured(path, m, err) : load_obj(path, m, err))) return fail(err);
   b->b.add_mesh(m, to_mat(mat), to_mat4(trans16), normalize != 0);
   return 0;
 }
@@ -192,6 +194,37 @@ int jadeh_builder_set_object_texture(jadeh_builder* b, int object, const jadeh_t
   if (!b || !t || object < 0) return fail("set_object_texture: bad arguments");
   if (projection < 0 || projection > 3) return fail("set_object_texture: projection is 0 1 2 (planar along x y z) or 3 (spherical)");
   b->b.set_object_texture(object, t->t, (UvProjection)projection);
+  return 0;
+}
+jadeh_texture* jadeh_normal_map_load(const char* path) {
+  if (!path) return texture_fail("normal_map_load: bad arguments");
+  jadeh_texture* t = new jadeh_texture();
+  std::string err;
+  if (!load_normal_map(path, t->t, err)) {
+    delete t;
+    return texture_fail(err);
+  }
+  return t;
+}
+jadeh_texture* jadeh_height_to_normal_map(int width, int height, const float* heights, float scale) {
+  if (!heights || width < 1 || width > 16384 || height < 1 || height > 16384 || !std::isfinite(scale)) return texture_fail("height_to_normal_map: bad arguments");
+  jadeh_texture* t = new jadeh_texture();
+  t->t = height_to_normal_map(heights, width, height, scale);
+  return t;
+}
+static bool strength_ok(float s) { return s >= 0.0f && std::isfinite(s); }
+int jadeh_builder_set_normal_map(jadeh_builder* b, const jadeh_texture* t, int projection, float strength) {
+  if (!b) return fail("null builder");
+  if (projection < 0 || projection > 3) return fail("set_normal_map: projection is 0 1 2 (planar along x y z) or 3 (spherical)");
+  if (!strength_ok(strength)) return fail("set_normal_map: the strength is finite and >= 0");
+  b->b.set_normal_map(t ? &t->t : nullptr, (UvProjection)projection, strength);
+  return 0;
+}
+int jadeh_builder_set_object_normal_map(jadeh_builder* b, int object, const jadeh_texture* t, int projection, float strength) {
+  if (!b || !t || object < 0) return fail("set_object_normal_map: bad arguments");
+  if (projection < 0 || projection > 3) return fail("set_object_normal_map: projection is 0 1 2 (planar along x y z) or 3 (spherical)");
+  if (!strength_ok(strength)) return fail("set_object_normal_map: the strength is finite and >= 0");
+  b->b.set_object_normal_map(object, t->t, (UvProjection)projection, strength);
   return 0;
 }
 int jadeh_project_uvs(const float* verts, int nv, const int* idx, int nt, int projection, float* out6) {
@@ -334,6 +367,20 @@ int jadeh_scene_texture(const jadeh_scene* s, int k, int* width, int* height, co
   *width = s->s.textures[k].width;
   *height = s->s.textures[k].height;
   *rgb = s->s.textures[k].rgb.data();
+  return 0;
+}
+int jadeh_scene_normal_maps(const jadeh_scene* s, const float** uv, const int32_t** image_of, float* strength) {
+  if (!s) return 0;
+  if (uv) *uv = s->s.map_uv.empty() ? nullptr : s->s.map_uv.data();
+  if (image_of) *image_of = s->s.map_image_of.empty() ? nullptr : s->s.map_image_of.data();
+  if (strength) *strength = s->s.map_strength;
+  return (int)s->s.normal_maps.size();
+}
+int jadeh_scene_normal_map(const jadeh_scene* s, int k, int* width, int* height, const float** xyz) {
+  if (!s || !width || !height || !xyz || k < 0 || k >= (int)s->s.normal_maps.size()) return fail("scene_normal_map: bad arguments");
+  *width = s->s.normal_maps[k].width;
+  *height = s->s.normal_maps[k].height;
+  *xyz = s->s.normal_maps[k].rgb.data();
   return 0;
 }
 int jadeh_scene_bvh_depth(const jadeh_scene* s) { return s ? s->s.bvh_depth : 0; }

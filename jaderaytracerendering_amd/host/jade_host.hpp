@@ -89,6 +89,15 @@ bool load_pfm(const std::string& path, Texture& out, std::string& err);
 // size x size texels in squares x squares squares of colours a and b, (0, 0) being a
 Texture make_texture_checker(int size, int squares, const float a[3], const float b[3]);
 
+// -- normal maps (include/jade_bvh.h, jade_scene_set_normal_maps) -------------
+// A map is a Texture of tangent-space vectors (x, y, z), decoded.  load_normal_map: a P6 file read LINEARLY - no sRGB decode - and then
+// 2 c - 1 per channel, c = byte / 255, in double and rounded once; a PF file as given (load_pfm).
+bool load_normal_map(const std::string& path, Texture& out, std::string& err);
+// width x height heights (row 0 at v = 0) -> the map of the surface z = scale * height(u, v): central differences in u and v over the
+// neighbouring texels, the image repeating at its borders - dh/du = (h(i + 1, j) - h(i - 1, j)) * (W / 2), dh/dv the same with H - in
+// fp32, and the UNNORMALISED vector (0 - scale * dh/du, 0 - scale * dh/dv, 1): a constant height gives (0, 0, 1) exactly.
+Texture height_to_normal_map(const float* height, int width, int height_texels, float scale);
+
 // -- scene builder (host triangles, pre-BVH) -------------------------------
 struct HostTriangle {  // == Triangle, PathTrace.cu:305-311
   int index;
@@ -117,6 +126,11 @@ struct BuiltScene {
   std::vector<float> uv;
   std::vector<int32_t> image_of;
   std::vector<Texture> textures;
+  // ... and what jade_scene_set_normal_maps takes, the same way: the map's own UVs and image numbers, its images and the strength
+  std::vector<float> map_uv;
+  std::vector<int32_t> map_image_of;
+  std::vector<Texture> normal_maps;
+  float map_strength = 1.0f;
   EnvMap env;
   int bvh_depth = 0;
   double build_seconds = 0;
@@ -141,6 +155,12 @@ class SceneBuilder {
   // arrives: how a caller textures one object of a configuration it does not build itself (jade_render --texture).
   void set_object_texture(int object, const Texture& texture, UvProjection fallback = UV_SPHERICAL);
   bool object_texture_set(int object) const { return object_texture_.count(object) != 0; }
+  // The normal map of the meshes added from now on, and of the object'th mesh to be added: as set_texture and set_object_texture, with
+  // the mesh's own UVs or those of `fallback`, independent of the albedo texture's.  The table has ONE strength: the last one given.
+  void set_normal_map(const Texture* map, UvProjection fallback = UV_SPHERICAL, float strength = 1.0f);
+  void set_object_normal_map(int object, const Texture& map, UvProjection fallback = UV_SPHERICAL, float strength = 1.0f);
+  bool normal_map_set() const { return map_ >= 0; }
+  bool object_normal_map_set(int object) const { return object_map_.count(object) != 0; }
   int object_count() const { return (int)segs_.size(); }
   int triangle_count() const { return (int)tris_.size(); }
   // Area prefix sums (PathTrace.cu:1539-1546), SAH BVH with leaf size 8
@@ -164,6 +184,13 @@ class SceneBuilder {
   int texture_ = -1;               // set_texture: the image of the meshes to come
   UvProjection fallback_ = UV_SPHERICAL;
   std::map<int, std::pair<int, UvProjection>> object_texture_;  // set_object_texture: object -> (its image in textures_, its fallback)
+  std::vector<float> map_uv_;          // the normal maps, member for member as the textures above
+  std::vector<int32_t> map_image_of_;
+  std::vector<Texture> maps_;
+  int map_ = -1;
+  UvProjection map_fallback_ = UV_SPHERICAL;
+  std::map<int, std::pair<int, UvProjection>> object_map_;
+  float map_strength_ = 1.0f;
   EnvMap env_;
 };
 

@@ -61,6 +61,8 @@ struct Api {
   int (*scene_set_vertex_normals)(jade_scene*, const float*, int32_t) = nullptr;
   // ... and only for --texture
   int (*scene_set_textures)(jade_scene*, int32_t, const jade_texture_image*, const float*, const int32_t*, int32_t) = nullptr;
+  // ... and only for --normal-map
+  int (*scene_set_normal_maps)(jade_scene*, int32_t, const jade_texture_image*, const float*, const int32_t*, int32_t, float) = nullptr;
   // ... and only for --passes
   int (*scene_set_passes)(jade_scene*, int) = nullptr;
   int (*render_passes)(jade_scene*, float*) = nullptr;
@@ -109,6 +111,7 @@ static void usage() {
           "                   [--out file.bmp|.ppm|.pfm] [--env sky|file.hdr] [--backend lib.so] [--device N] [--reference-walk] [--env-importance | --env-mixture] [--one-light]\n"
           "                   [--bounce uniform|cosine] [--direct rays|mis] [--branch random|stratified] [--passes PREFIX] [--smooth [DEG]]\n"
           "                   [--texture K=checker[:SIZE[:SQUARES]]|FILE[@PROJECTION]]...\n"
+          "                   [--normal-map K=FILE|bumps[:SIZE[:N]][@PROJECTION][:STRENGTH]]...\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
@@ -198,6 +201,8 @@ int main(int argc, char** argv) {
   double smooth_deg = 0.0;  // --smooth [DEG]: the objects' smoothing angle, 0 = not given
   struct TextureFlag { int object; std::string image; UvProjection projection; };
   std::vector<TextureFlag> texture_flags;  // --texture K=IMAGE[@PROJECTION]
+  struct MapFlag { int object; std::string image; UvProjection projection; float strength; };
+  std::vector<MapFlag> map_flags;          // --normal-map K=FILE|bumps[:SIZE[:N]][@PROJECTION][:STRENGTH]
   bool have_truck = false, have_orbit = false, have_pivot = false, have_interval = false;
   double truck[3] = {0, 0, 0}, orbit_deg = 0.0, pivot[3] = {0, 0, 0}, interval[2] = {0.0, 1.0};
   auto number = [](const char* flag, const char* v) {
@@ -270,6 +275,57 @@ int main(int argc, char** argv) {
       for (const TextureFlag& t : texture_flags)
         if (t.object == (int)k) { fprintf(stderr, "--texture: object %ld is given twice\n", k); return 2; }
       texture_flags.push_back({(int)k, v.substr(eq + 1, (at == std::string::npos ? v.size() : at) - eq - 1), proj});
+    }
+    else if (a == "--normal-map") {
+      // K=IMAGE[@PROJECTION][:STRENGTH]: a tangent-space normal map on object K - a P6 file (read linearly, 2 c - 1) or a PF file, or
+      // bumps[:SIZE[:N]], a lattice of N x N bumps on SIZE x SIZE texels.  Without @PROJECTION a strength follows the image as :STRENGTH
+      // (after bumps: as its third number).
+      const std::string v = need("--normal-map");
+      const size_t eq = v.find('='), at = v.rfind('@');
+      char* end = nullptr;
+      const long k = strtol(v.c_str(), &end, 10);
+      if (eq == std::string::npos || eq == 0 || end != v.c_str() + eq || k < 0 || k > 1000000 || eq + 1 >= (at == std::string::npos ? v.size() : at)) {
+        fprintf(stderr, "--normal-map takes K=IMAGE[@PROJECTION][:STRENGTH] with K an object number from 0, not %s\n", v.c_str());
+        return 2;
+      }
+      std::string image = v.substr(eq + 1, (at == std::string::npos ? v.size() : at) - eq - 1), tail;
+      UvProjection proj = UV_SPHERICAL;
+      if (at != std::string::npos) {
+        std::string pn = v.substr(at + 1);
+        const size_t colon = pn.find(':');
+        if (colon != std::string::npos) {
+          tail = pn.substr(colon + 1);
+          pn = pn.substr(0, colon);
+        }
+        if (pn == "spherical") proj = UV_SPHERICAL;
+        else if (pn == "planar-x") proj = UV_PLANAR_X;
+        else if (pn == "planar-y") proj = UV_PLANAR_Y;
+        else if (pn == "planar-z") proj = UV_PLANAR_Z;
+        else { fprintf(stderr, "--normal-map: the projection is spherical, planar-x, planar-y or planar-z, not %s\n", pn.c_str()); return 2; }
+      } else {
+        const bool bumps = image.compare(0, 5, "bumps") == 0 && (image.size() == 5 || image[5] == ':');
+        size_t colons = 0, last = std::string::npos;
+        for (size_t c = 0; c < image.size(); ++c)
+          if (image[c] == ':') { ++colons; last = c; }
+        if (last != std::string::npos && (bumps ? colons == 3 : true)) {
+          char* e2 = nullptr;
+          (void)strtod(image.c_str() + last + 1, &e2);
+          if (e2 != image.c_str() + last + 1 && *e2 == 0) {
+            tail = image.substr(last + 1);
+            image = image.substr(0, last);
+          }
+        }
+      }
+      float strength = 1.0f;
+      if (!tail.empty()) {
+        char* e3 = nullptr;
+        const double s = strtod(tail.c_str(), &e3);
+        if (e3 == tail.c_str() || *e3 != 0 || !(s >= 0.0) || !std::isfinite(s)) { fprintf(stderr, "--normal-map: the strength is a number >= 0, not %s\n", tail.c_str()); return 2; }
+        strength = (float)s;
+      }
+      for (const MapFlag& t : map_flags)
+        if (t.object == (int)k) { fprintf(stderr, "--normal-map: object %ld is given twice\n", k); return 2; }
+      map_flags.push_back({(int)k, image, proj, strength});
     }
     else if (a == "--smooth") {  // the angle is optional: taken if the next argument is a number
       smooth_deg = 60.0;
@@ -390,6 +446,26 @@ int main(int argc, char** argv) {
     }
     builder.set_object_texture(t.object, tex, t.projection);
   }
+  for (const MapFlag& t : map_flags) {
+    Texture map;
+    if (t.image.compare(0, 5, "bumps") == 0 && (t.image.size() == 5 || t.image[5] == ':')) {
+      int size = 256, n = 8;
+      if (t.image.size() > 5 && (sscanf(t.image.c_str() + 6, "%d:%d", &size, &n) < 1 || size < 1 || size > 16384 || n < 1 || 2 * n > size)) {
+        fprintf(stderr, "--normal-map: bumps[:SIZE[:N]] takes 1 .. 16384 texels a side and at most half as many bumps, not %s\n", t.image.c_str());
+        return 2;
+      }
+      // a lattice of n x n bumps: height = (0.08 / n) sin(2 pi n u) sin(2 pi n v), so that the steepest slope is 0.5 whatever n is
+      std::vector<float> height((size_t)size * size);
+      for (int y = 0; y < size; ++y)
+        for (int x = 0; x < size; ++x)
+          height[(size_t)y * size + x] = (float)(0.08 / n * std::sin(2.0 * M_PI * n * (x + 0.5) / size) * std::sin(2.0 * M_PI * n * (y + 0.5) / size));
+      map = height_to_normal_map(height.data(), size, size, 1.0f);
+    } else if (!load_normal_map(t.image, map, err)) {
+      fprintf(stderr, "--normal-map: %s\n", err.c_str());
+      return 1;
+    }
+    builder.set_object_normal_map(t.object, map, t.projection, t.strength);
+  }
   if (!config.empty()) {
     if (!make_config(config, builder, cfg, err)) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
   } else {
@@ -402,7 +478,7 @@ int main(int argc, char** argv) {
       Mesh m;
       std::string f = (!o.file.empty() && o.file[0] == '/') ? o.file : dir + o.file;
       // (a textured object is read with its vt lines; every other one as the reference reads it)
-      if (!(builder.object_texture_set(builder.object_count()) ? load_obj_textured(f, m, err) : load_obj(f, m, err))) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
+      if (!(builder.object_texture_set(builder.object_count()) || builder.object_normal_map_set(builder.object_count()) ? load_obj_textured(f, m, err) : load_obj(f, m, err))) { fprintf(stderr, "%s\n", err.c_str()); return 1; }
       builder.add_mesh(m, o.material, o.trans, o.normalize);
     }
     memcpy(cfg.eye, ra.eye, sizeof cfg.eye);
@@ -414,6 +490,11 @@ int main(int argc, char** argv) {
   for (const TextureFlag& t : texture_flags)
     if (t.object >= builder.object_count()) {
       fprintf(stderr, "--texture: the scene has objects 0 .. %d, not %d\n", builder.object_count() - 1, t.object);
+      return 2;
+    }
+  for (const MapFlag& t : map_flags)
+    if (t.object >= builder.object_count()) {
+      fprintf(stderr, "--normal-map: the scene has objects 0 .. %d, not %d\n", builder.object_count() - 1, t.object);
       return 2;
     }
   if (env == "sky") builder.set_env(make_env_sky(1024, 512));
@@ -517,6 +598,13 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (!map_flags.empty()) {
+    *(void**)(&api.scene_set_normal_maps) = dlsym(api.h, "jade_scene_set_normal_maps");
+    if (!api.scene_set_normal_maps) {
+      fprintf(stderr, "--normal-map needs the HIP backend: %s has no jade_scene_set_normal_maps\n", backend.c_str());
+      return 2;
+    }
+  }
   if (!passes.empty()) {
     *(void**)(&api.scene_set_passes) = dlsym(api.h, "jade_scene_set_passes");
     *(void**)(&api.render_passes) = dlsym(api.h, "jade_render_passes");
@@ -594,10 +682,18 @@ int main(int argc, char** argv) {
       return 1;
     }
   }
+  if (!scene.normal_maps.empty()) {
+    std::vector<jade_texture_image> images;
+    for (const Texture& t : scene.normal_maps) images.push_back({t.width, t.height, t.rgb.data()});
+    if (api.scene_set_normal_maps(dev, (int32_t)images.size(), images.data(), scene.map_uv.data(), scene.map_image_of.data(), (int32_t)scene.map_image_of.size(), scene.map_strength) != JADE_OK) {
+      fprintf(stderr, "normal maps: %s\n", api.last_error());
+      return 1;
+    }
+  }
   if (!passes.empty() && api.scene_set_passes(dev, 1) != JADE_OK) { fprintf(stderr, "passes: %s\n", api.last_error()); return 1; }
   const std::string lights_note_s = std::string(one_light ? ", one light per vertex" : "") + (bounce == JADE_BOUNCE_COSINE ? ", cosine-weighted bounces" : "") +
                                     (direct == JADE_DIRECT_MIS ? ", emitters by multiple importance sampling" : "") +
-                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (smooth_deg > 0.0 ? ", smooth shading" : "") + (!texture_flags.empty() ? ", textures" : "") + (!passes.empty() ? ", light passes kept" : "");
+                                    (env_mixture ? ", sky importance mixed with the hemisphere draw" : "") + (branch == JADE_BRANCH_STRATIFIED ? ", branch draws shared out" : "") + (smooth_deg > 0.0 ? ", smooth shading" : "") + (!texture_flags.empty() ? ", textures" : "") + (!map_flags.empty() ? ", normal maps" : "") + (!passes.empty() ? ", light passes kept" : "");
   const char* lights_note = lights_note_s.c_str();
   std::vector<float> rgb((size_t)3 * rp.width * rp.height);
   std::vector<uint8_t> bgr((size_t)3 * rp.width * rp.height);

@@ -262,6 +262,24 @@ void SceneBuilder::set_texture(const Texture* texture, UvProjection fallback) {
   texture_ = (int)textures_.size() - 1;
 }
 
+void SceneBuilder::set_normal_map(const Texture* map, UvProjection fallback, float strength) {
+  map_fallback_ = fallback;
+  if (!map || map->width <= 0 || map->height <= 0) {
+    map_ = -1;
+    return;
+  }
+  maps_.push_back(*map);
+  map_ = (int)maps_.size() - 1;
+  map_strength_ = strength;
+}
+
+void SceneBuilder::set_object_normal_map(int object, const Texture& map, UvProjection fallback, float strength) {
+  if (map.width <= 0 || map.height <= 0) return;
+  maps_.push_back(map);
+  object_map_[object] = std::make_pair((int)maps_.size() - 1, fallback);
+  map_strength_ = strength;
+}
+
 void SceneBuilder::set_object_texture(int object, const Texture& texture, UvProjection fallback) {
   if (texture.width <= 0 || texture.height <= 0) return;
   textures_.push_back(texture);
@@ -505,6 +523,25 @@ void SceneBuilder::add_mesh(const Mesh& mesh, const Material& mat, const Mat4& t
       std::fill(image_of_.begin() + offset, image_of_.end(), texture);
     }
   }
+  // normal maps: the same rule with the map's own members
+  int map = map_;
+  UvProjection map_fallback = map_fallback_;
+  if (const auto own = object_map_.find(obj_idx); own != object_map_.end()) {
+    map = own->second.first;
+    map_fallback = own->second.second;
+  }
+  if (map >= 0 || !map_image_of_.empty()) {
+    map_uv_.resize(6 * tris_.size(), 0.0f);
+    map_image_of_.resize(tris_.size(), -1);
+    if (map >= 0) {
+      const std::vector<float> made = mesh.uvs.size() == 6 * (size_t)ntri ? std::vector<float>()
+                                      : map_fallback == UV_SPHERICAL  ? spherical_uvs(mesh)
+                                                                      : planar_uvs(mesh, (int)map_fallback);
+      const std::vector<float>& uv = made.empty() ? mesh.uvs : made;
+      std::copy(uv.begin(), uv.begin() + 6 * (size_t)ntri, map_uv_.begin() + 6 * (size_t)offset);
+      std::fill(map_image_of_.begin() + offset, map_image_of_.end(), map);
+    }
+  }
 }
 
 // ------------------------------------------------------------------ BVH ----
@@ -724,6 +761,19 @@ void SceneBuilder::finish(std::vector<HostTriangle>& tris, BuiltScene& out) cons
       out.image_of[i] = image_of_[(size_t)tris[i].index];
     }
     out.textures = textures_;
+  }
+  out.map_uv.clear();
+  out.map_image_of.clear();
+  out.normal_maps.clear();
+  out.map_strength = map_strength_;
+  if (!map_image_of_.empty()) {  // ... and the normal maps' own
+    out.map_uv.resize(6 * n);
+    out.map_image_of.resize(n);
+    for (size_t i = 0; i < n; ++i) {
+      std::copy(map_uv_.begin() + 6 * (size_t)tris[i].index, map_uv_.begin() + 6 * (size_t)tris[i].index + 6, out.map_uv.begin() + 6 * i);
+      out.map_image_of[i] = map_image_of_[(size_t)tris[i].index];
+    }
+    out.normal_maps = maps_;
   }
   out.env = env_.width > 0 ? env_ : make_env_constant(0, 0, 0);
 }

@@ -275,7 +275,7 @@ static bool pnm_token(FILE* f, std::string& out) {
 
 static bool texture_size_ok(int w, int h) { return w >= 1 && w <= 16384 && h >= 1 && h <= 16384; }
 
-bool load_ppm(const std::string& path, Texture& out, std::string& err) {
+static bool load_ppm_decoded(const std::string& path, Texture& out, std::string& err, const float decode[256]) {
   FILE* f = fopen(path.c_str(), "rb");
   if (!f) {
     err = "File " + path + " open failed.";
@@ -296,16 +296,20 @@ bool load_ppm(const std::string& path, Texture& out, std::string& err) {
     err = "File " + path + ": truncated";
     return false;
   }
-  float decode[256];
-  for (int i = 0; i < 256; ++i) {
-    const double c = i / 255.0;
-    decode[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
-  }
   out.width = w;
   out.height = h;
   out.rgb.resize(bytes.size());
   for (size_t i = 0; i < bytes.size(); ++i) out.rgb[i] = decode[bytes[i]];
   return true;
+}
+
+bool load_ppm(const std::string& path, Texture& out, std::string& err) {
+  float decode[256];
+  for (int i = 0; i < 256; ++i) {
+    const double c = i / 255.0;
+    decode[i] = (float)(c <= 0.04045 ? c / 12.92 : std::pow((c + 0.055) / 1.055, 2.4));
+  }
+  return load_ppm_decoded(path, out, err, decode);
 }
 
 bool load_pfm(const std::string& path, Texture& out, std::string& err) {
@@ -344,6 +348,41 @@ bool load_pfm(const std::string& path, Texture& out, std::string& err) {
       out.rgb[(size_t)y * 3 * w + i] = v;
     }
   return true;
+}
+
+bool load_normal_map(const std::string& path, Texture& out, std::string& err) {
+  FILE* f = fopen(path.c_str(), "rb");
+  if (!f) {
+    err = "File " + path + " open failed.";
+    return false;
+  }
+  char magic[2] = {0, 0};
+  const size_t got = fread(magic, 1, 2, f);
+  fclose(f);
+  if (got == 2 && magic[0] == 'P' && magic[1] == 'F') return load_pfm(path, out, err);
+  float decode[256];
+  for (int i = 0; i < 256; ++i) decode[i] = (float)(2.0 * (i / 255.0) - 1.0);  // linear: a normal map's bytes are vectors, not colours
+  return load_ppm_decoded(path, out, err, decode);
+}
+
+Texture height_to_normal_map(const float* height, int width, int height_texels, float scale) {
+  Texture t;
+  const int W = width < 1 ? 1 : width, H = height_texels < 1 ? 1 : height_texels;
+  t.width = W;
+  t.height = H;
+  t.rgb.resize((size_t)3 * W * H);
+  const float half_w = 0.5f * (float)W, half_h = 0.5f * (float)H;
+  for (int j = 0; j < H; ++j)
+    for (int i = 0; i < W; ++i) {
+      const int il = i == 0 ? W - 1 : i - 1, ir = i == W - 1 ? 0 : i + 1, jl = j == 0 ? H - 1 : j - 1, jr = j == H - 1 ? 0 : j + 1;
+      const float du = (height[(size_t)j * W + ir] - height[(size_t)j * W + il]) * half_w;
+      const float dv = (height[(size_t)jr * W + i] - height[(size_t)jl * W + i]) * half_h;
+      float* out = &t.rgb[3 * ((size_t)j * W + i)];
+      out[0] = 0.0f - scale * du;
+      out[1] = 0.0f - scale * dv;
+      out[2] = 1.0f;
+    }
+  return t;
 }
 
 Texture make_texture_checker(int size, int squares, const float a[3], const float b[3]) {

@@ -26,7 +26,7 @@ for k, v in rows.items():
     s = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILj(\d+)E", k)  # a kernel template over the ShadeMode mask (jade_runtime.h): k_shade_mode<COSINE|MIS>
     if not m and not t and not s:
         continue
-    bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS", "ENVMIX", "PASSES", "BRANCH", "SMOOTH", "TEX")
+    bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS", "ENVMIX", "PASSES", "BRANCH", "SMOOTH", "TEX", "NMAP")
     if s:
         name = "%s<%s>" % (s.group(1), "|".join(b for i, b in enumerate(bits) if int(s.group(2)) >> i & 1) or "0")
     else:
