@@ -86,6 +86,10 @@ asan-check:
 	gcc -std=gnu11 -ffp-contract=off -mfma $(SAN) -DJADE_ORACLE_PROBE -I$(ROOT)/include -o $(ROOT)/tests/_build/asan/oracle_shapes \
 	  $(ROOT)/tests/native/oracle_shapes_main.c $(ROOT)/oracle/jade_oracle.c -lpthread -lm
 	ASAN_OPTIONS=detect_leaks=1 $(ROOT)/tests/_build/asan/prep_shapes $(ROOT)/tests/_build/tree_shapes
+	# the image-set check of the texture and normal-map setters (jade_surface.hip: host code, no HIP call), stand-alone
+	$(HIPCC) --offload-host-only -x hip -std=c++17 -O1 -g $(FPFLAGS) -fsanitize=address,undefined -fno-omit-frame-pointer -I$(ROOT)/include -I$(PKG)/csrc \
+	  -o $(ROOT)/tests/_build/asan/image_set $(ROOT)/tests/native/image_set_main.cpp $(PKG)/csrc/jade_surface.hip -ldl
+	ASAN_OPTIONS=detect_leaks=1 $(ROOT)/tests/_build/asan/image_set
 	ASAN_OPTIONS=detect_leaks=1 $(ROOT)/tests/_build/asan/oracle_shapes $(ROOT)/tests/_build/tree_shapes
 	@echo "asan-check: clean"
 

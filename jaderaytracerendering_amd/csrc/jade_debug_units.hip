@@ -932,20 +932,20 @@ struct DebugTextures {
 };
 static int debug_textures(jade_scene* s, int32_t n, const int32_t* index, int32_t index_lo, size_t index_n, DebugTextures* d) {
   if (n <= 0 || n > kDebugMaxRows / 4) return jade_fail(JADE_ERR_INVALID, "row count out of range");
-  if (s->tex_rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no textures (jade_scene_set_textures)");
+  if (s->surf.set.textures.rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no textures (jade_scene_set_textures)");
   for (int32_t i = 0; i < n; ++i)
     if (index[i] < index_lo || (size_t)index[i] >= index_n) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": index out of range");
   HIP_TRY(hipSetDevice(s->device));
-  HIP_TRY(upload(d->rec, s->tex_rec.data(), s->tex_rec.size(), s->stream));
-  HIP_TRY(upload(d->texels, s->tex_texels.data(), s->tex_texels.size(), s->stream));
-  HIP_TRY(upload(d->images, s->tex_images.data(), s->tex_images.size(), s->stream));
+  HIP_TRY(upload(d->rec, s->surf.set.textures.rec.data(), s->surf.set.textures.rec.size(), s->stream));
+  HIP_TRY(upload(d->texels, s->surf.set.textures.texels.data(), s->surf.set.textures.texels.size(), s->stream));
+  HIP_TRY(upload(d->images, s->surf.set.textures.images.data(), s->surf.set.textures.images.size(), s->stream));
   d->T = TexTables{nullptr, d->rec.as<float4>(), d->texels.as<float4>(), d->images.as<uint4>()};
   return JADE_OK;
 }
 int jade_debug_surface_uv(jade_scene* s, int32_t n, const int32_t* tri, const float* points, float* out_uv) {
   if (!s || !tri || !points || !out_uv) return jade_fail(JADE_ERR_INVALID, "null argument");
   DebugTextures d;
-  if (const int rc = debug_textures(s, n, tri, 0, s->tex_rec.size() / JADE_TEX_REC, &d)) return rc;
+  if (const int rc = debug_textures(s, n, tri, 0, s->surf.set.textures.rec.size() / JADE_TEX_REC, &d)) return rc;
   const size_t N = (size_t)n;
   DevBuf bt, bp, bo;
   HIP_TRY(upload(bt, tri, N, s->stream));
@@ -960,7 +960,7 @@ int jade_debug_surface_uv(jade_scene* s, int32_t n, const int32_t* tri, const fl
 int jade_debug_texture_fetch(jade_scene* s, int32_t n, const int32_t* image, const float* uv, float* out_rgb) {
   if (!s || !image || !uv || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
   DebugTextures d;
-  if (const int rc = debug_textures(s, n, image, 0, s->tex_images.size(), &d)) return rc;
+  if (const int rc = debug_textures(s, n, image, 0, s->surf.set.textures.images.size(), &d)) return rc;
   const size_t N = (size_t)n;
   DevBuf bi, bu, bo;
   HIP_TRY(upload(bi, image, N, s->stream));
@@ -975,7 +975,7 @@ int jade_debug_texture_fetch(jade_scene* s, int32_t n, const int32_t* image, con
 int jade_debug_surface_colour(jade_scene* s, int32_t n, const int32_t* tri, const float* points, float* out_rgb) {
   if (!s || !tri || !points || !out_rgb) return jade_fail(JADE_ERR_INVALID, "null argument");
   DebugTextures d;
-  if (const int rc = debug_textures(s, n, tri, 0, s->tex_rec.size() / JADE_TEX_REC, &d)) return rc;
+  if (const int rc = debug_textures(s, n, tri, 0, s->surf.set.textures.rec.size() / JADE_TEX_REC, &d)) return rc;
   const size_t N = (size_t)n;
   DevBuf bt, bp, bo;
   HIP_TRY(upload(bt, tri, N, s->stream));
@@ -1006,32 +1006,32 @@ int jade_debug_shade_mode_normal_maps_host(int32_t env_sampling, int32_t lens, i
 }
 
 // The mapped normal (mapped_normal_rule, jade_normal_map.h; include/jade_bvh.h "The mapped normal, stated") on n rows, with the tables the handle
-// carries as jade_scene_set_normal_maps and jade_scene_set_vertex_normals left them, joined as jade_render_begin joins them (no render is begun;
+// carries as jade_scene_set_normal_maps and jade_scene_set_vertex_normals left them, joined as jade_render_begin joins them (surface_join_maps; no render is begun;
 // tests/test_gpu_normal_map.py): out_n[i] = normal'(tri[i], points[i], refs[i]), out_rule[i] = the SMOOTH_RULE_* that gave it.
 int jade_debug_mapped_normal(jade_scene* s, int32_t n, const int32_t* tri, const float* points, const float* refs, float* out_n, int32_t* out_rule) {
   if (!s || !tri || !points || !refs || !out_n || !out_rule) return jade_fail(JADE_ERR_INVALID, "null argument");
   if (n <= 0 || n > kDebugMaxRows / 4) return jade_fail(JADE_ERR_INVALID, "row count out of range");
-  if (s->nmap_rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no normal maps (jade_scene_set_normal_maps)");
-  const size_t n_tris = s->nmap_rec.size() / JADE_NMAP_REC;
+  const auto& set = s->surf.set;
+  if (set.maps.rec.empty()) return jade_fail(JADE_ERR_INVALID, "the scene carries no normal maps (jade_scene_set_normal_maps)");
+  const size_t n_tris = set.maps.rec.size() / JADE_NMAP_REC;
   for (int32_t i = 0; i < n; ++i)
     if (tri[i] < 0 || (size_t)tri[i] >= n_tris) return jade_fail(JADE_ERR_INVALID, "row " + std::to_string(i) + ": index out of range");
   HIP_TRY(hipSetDevice(s->device));
-  const bool smooth = !s->smooth_rec.empty();
-  std::vector<float4> rec(s->nmap_rec), flat;
-  for (size_t i = 0; i < n_tris; ++i) normal_map_join(&rec[i * JADE_NMAP_REC], smooth ? &s->smooth_rec[i * JADE_SMOOTH_REC] : nullptr);
-  if (!smooth) flat.assign(n_tris * JADE_SMOOTH_REC, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+  const std::vector<float4> rec = surface_join_maps(s->surf);
+  std::vector<float4> flat;
+  if (set.normals.empty()) flat.assign(n_tris * JADE_SMOOTH_REC, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
   DevBuf brec, btex, bimg, bsm, bt, bp, br, bn, bo;
   HIP_TRY(upload(brec, rec.data(), rec.size(), s->stream));
-  HIP_TRY(upload(btex, s->nmap_texels.data(), s->nmap_texels.size(), s->stream));
-  HIP_TRY(upload(bimg, s->nmap_images.data(), s->nmap_images.size(), s->stream));
-  HIP_TRY(upload(bsm, smooth ? s->smooth_rec.data() : flat.data(), n_tris * JADE_SMOOTH_REC, s->stream));
+  HIP_TRY(upload(btex, set.maps.texels.data(), set.maps.texels.size(), s->stream));
+  HIP_TRY(upload(bimg, set.maps.images.data(), set.maps.images.size(), s->stream));
+  HIP_TRY(upload(bsm, set.normals.empty() ? flat.data() : set.normals.data(), n_tris * JADE_SMOOTH_REC, s->stream));
   const size_t N = (size_t)n;
   HIP_TRY(upload(bt, tri, N, s->stream));
   HIP_TRY(upload(bp, points, 3 * N, s->stream));
   HIP_TRY(upload(br, refs, 3 * N, s->stream));
   HIP_TRY(bn.alloc(12 * N));
   HIP_TRY(bo.alloc(4 * N));
-  const MapTables T{TexTables{bsm.as<float4>(), nullptr, nullptr, nullptr}, brec.as<float4>(), btex.as<float4>(), bimg.as<uint4>(), s->nmap_strength};
+  const MapTables T{TexTables{bsm.as<float4>(), nullptr, nullptr, nullptr}, brec.as<float4>(), btex.as<float4>(), bimg.as<uint4>(), set.strength};
   hipLaunchKernelGGL(k_debug_mapped_normal, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s->stream, n, T, s->b_tnorm.as<float4>(), bt.as<int32_t>(), bp.as<float>(),
                      br.as<float>(), bn.as<float>(), bo.as<int32_t>());
   HIP_TRY(hipGetLastError());

@@ -61,276 +61,138 @@ __global__ __launch_bounds__(JADE_ERR_BLOCK) void k_pixel_variance(PathState P, 
 // -------------------------------------------------------------------------------------------------------------- guide pass --
 
 // G: the throw-away PathState (one record and one slot per owned pixel: orgs, slot, hitp).  Sample sidx of every listed pixel.
-// state[p] = {throughput, depth so far}, mirrors[p] = mirror vertices passed.
-__global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera(PathState G, RenderConst R, const int32_t* tile_ids, const uint32_t* list, uint32_t n,
-                                                                uint32_t sidx, float4* state, uint32_t* mirrors) {
+// state[p] = {throughput, depth so far}, mirrors[p] = mirror vertices passed.  One text for the three cameras; the kernels below name them.
+// (One text per family is safe here: the library is built with -ffp-contract=off, so the same statements in the same order give the same
+// bits whatever the form they are compiled in, and tests/test_gpu_guide_tables_exact.py pins the guides' bits under every table.)
+enum GuideCamera { GUIDE_PINHOLE, GUIDE_LENS, GUIDE_SHUTTER };
+template <GuideCamera CAM>
+static __device__ __forceinline__ void guide_camera_body(PathState G, const RenderConst& R, float lens_k, const ShutterConst& H, const int32_t* tile_ids,
+                                                         const uint32_t* list, uint32_t n, uint32_t sidx, float4* state, uint32_t* mirrors) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int p = (int)list[i];
   int x, y;
   (void)dn_pixel_xy(R, tile_ids, p, &x, &y);  // (the list holds in-image pixels only)
   uint32_t rng;
-  const jvec3 dir = camera_ray_dir(R, x, y, sidx, &rng);
-  G.orgs[p] = make_float4(R.eye[0], R.eye[1], R.eye[2], __int_as_float(JADE_SKIP_CAMERA));  // (k_trace takes a camera ray's origin from P.eye)
-  G.slot[p] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));                          // -1: the nearest hit is wanted
+  jvec3 dir;
+  if constexpr (CAM == GUIDE_PINHOLE) {
+    dir = camera_ray_dir(R, x, y, sidx, &rng);
+    G.orgs[p] = make_float4(R.eye[0], R.eye[1], R.eye[2], __int_as_float(JADE_SKIP_CAMERA));  // (k_trace takes a camera ray's origin from P.eye)
+  } else {
+    // the sample's own origin, stored with "no source triangle" (-1) as jade_trace_rays' rays are, so k_trace reads it instead of P.eye
+    jvec3 org;
+    if constexpr (CAM == GUIDE_LENS) dir = camera_ray_lens(R, lens_k, x, y, sidx, &rng, &org);
+    else dir = camera_ray_shutter(R, H, lens_k, x, y, sidx, &rng, &org);
+    G.orgs[p] = make_float4(org.x, org.y, org.z, __int_as_float(-1));
+  }
+  G.slot[p] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));  // -1: the nearest hit is wanted
   state[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
   mirrors[p] = 0u;
 }
-// ... in a render under a thin lens (lens_k = PathState.lens_k of that render): the guides follow the lens (include/jade_bvh.h) - the
-// sample's own origin, stored with "no source triangle" (-1) as jade_trace_rays' rays are, so k_trace reads it instead of P.eye
+__global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera(PathState G, RenderConst R, const int32_t* tile_ids, const uint32_t* list, uint32_t n,
+                                                                uint32_t sidx, float4* state, uint32_t* mirrors) {
+  guide_camera_body<GUIDE_PINHOLE>(G, R, 0.0f, ShutterConst{}, tile_ids, list, n, sidx, state, mirrors);
+}
+// ... in a render under a thin lens (lens_k = PathState.lens_k of that render): the guides follow the lens (include/jade_bvh.h)
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera_lens(PathState G, RenderConst R, float lens_k, const int32_t* tile_ids, const uint32_t* list,
                                                                      uint32_t n, uint32_t sidx, float4* state, uint32_t* mirrors) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int p = (int)list[i];
-  int x, y;
-  (void)dn_pixel_xy(R, tile_ids, p, &x, &y);
-  uint32_t rng;
-  jvec3 org;
-  const jvec3 dir = camera_ray_lens(R, lens_k, x, y, sidx, &rng, &org);
-  G.orgs[p] = make_float4(org.x, org.y, org.z, __int_as_float(-1));
-  G.slot[p] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
-  state[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-  mirrors[p] = 0u;
+  guide_camera_body<GUIDE_LENS>(G, R, lens_k, ShutterConst{}, tile_ids, list, n, sidx, state, mirrors);
 }
 // ... and in a render under a shutter (H = that render's constants), with a lens or without
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_camera_shutter(PathState G, RenderConst R, float lens_k, const int32_t* tile_ids, const uint32_t* list,
                                                                         uint32_t n, uint32_t sidx, float4* state, uint32_t* mirrors, ShutterConst H) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int p = (int)list[i];
-  int x, y;
-  (void)dn_pixel_xy(R, tile_ids, p, &x, &y);
-  uint32_t rng;
-  jvec3 org;
-  const jvec3 dir = camera_ray_shutter(R, H, lens_k, x, y, sidx, &rng, &org);
-  G.orgs[p] = make_float4(org.x, org.y, org.z, __int_as_float(-1));
-  G.slot[p] = make_float4(dir.x, dir.y, dir.z, __int_as_float(-1));
-  state[p] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-  mirrors[p] = 0u;
+  guide_camera_body<GUIDE_SHUTTER>(G, R, lens_k, H, tile_ids, list, n, sidx, state, mirrors);
 }
 
 // The hits of the rays queue[0 .. *count): a mirror vertex (reflex_mode == JADE_MIRROR, not emissive by bounce_mirror's test, fewer than
 // JADE_MAX_FULL_REFLEX_TIME passed) goes on with bounce_mirror's reflected ray, appended to next_queue; anything else ends the sample
 // and adds {a, z} to acc_az[p] and {n, 0} to acc_n[p].  last: this is the last guide sample, the sums are scaled by inv_g.
+// One text for the four forms, by what the render's kernels take as their table (ST):
+//   NoTables         the parity form: the flat normal, the material's brdf
+//   const float4*    a smooth render (SM_SMOOTH; include/jade_bvh.h, "The shading normal, stated"): the shading normal of the hit - normal(triangle,
+//                    hit point, -d) - in the mirror's reflection, formed again with the flat normal where it does not leave on the viewer's side of
+//                    it, and in the normal guide
+//   TexTables        a textured render (SM_TEX; "The surface colour, stated"): brdf_eff - the brdf times the surface colour at the hit - in the
+//                    throughput and in the albedo guide as well, at every vertex of the mirror chain; the table carries the vertex normals the
+//                    render began with, or the all-flat table
+//   MapTables        a mapped render (SM_NMAP; "The mapped normal, stated"): the mapped normal in the shading normal's place
+struct NoTables {};
+template <class ST>
+static __device__ __forceinline__ void guide_hits_body(const DevScene& S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
+                                                       uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g, uint32_t* next_queue,
+                                                       uint32_t* next_count, const ST& table) {
+  constexpr bool flat_only = std::is_same<ST, NoTables>::value;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= *count) return;
+  const int p = (int)queue[i];
+  const float4 sl = G.slot[p];
+  const jvec3 d = jv(sl.x, sl.y, sl.z);
+  const int h = __float_as_int(sl.w);
+  float4 st = state[p];
+  jvec3 t = jv(st.x, st.y, st.z);
+  float z = st.w;
+  jvec3 a, n;
+  if (h < 0) {
+    a = t;
+    n = jv(0.0f, 0.0f, 0.0f);
+    z = 0.0f;
+  } else {
+    const float4 hp = G.hitp[p];
+    const float4 tn = S.tnorm[h];
+    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
+    const jvec3 flat = jv(tn.x, tn.y, tn.z);
+    const jvec3 o = jv_neg(d);
+    jvec3 norm = flat;
+    if constexpr (!flat_only) norm = shading_normal(table, h, flat, jv(hp.x, hp.y, hp.z), o);
+    const jvec3 brdf = textured(table, h, jv(hp.x, hp.y, hp.z), V3(m->brdf));
+    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
+    const uint32_t k = mirrors[p];
+    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
+      t = jv_mul(t, brdf);
+      z = z + hp.w;
+      jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);  // bounce_mirror's statement
+      if constexpr (!flat_only)
+        if (!same_side(refl, o, flat)) refl = jv_sub(jv_scale(flat, 2 * jv_dot(o, flat)), o);
+      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
+      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
+      state[p] = make_float4(t.x, t.y, t.z, z);
+      mirrors[p] = k + 1u;
+      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
+      return;
+    }
+    z = z + hp.w;
+    a = jv_mul(t, brdf);
+    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
+  }
+  float4 s0 = acc_az[p], s1 = acc_n[p];
+  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
+  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
+  if (last) {
+    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
+    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
+  }
+  acc_az[p] = s0;
+  acc_n[p] = s1;
+}
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
                                                               uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
                                                               uint32_t* next_queue, uint32_t* next_count) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= *count) return;
-  const int p = (int)queue[i];
-  const float4 sl = G.slot[p];
-  const jvec3 d = jv(sl.x, sl.y, sl.z);
-  const int h = __float_as_int(sl.w);
-  float4 st = state[p];
-  jvec3 t = jv(st.x, st.y, st.z);
-  float z = st.w;
-  jvec3 a, n;
-  if (h < 0) {
-    a = t;
-    n = jv(0.0f, 0.0f, 0.0f);
-    z = 0.0f;
-  } else {
-    const float4 hp = G.hitp[p];
-    const float4 tn = S.tnorm[h];
-    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
-    const jvec3 norm = jv(tn.x, tn.y, tn.z);
-    const jvec3 brdf = V3(m->brdf);
-    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
-    const uint32_t k = mirrors[p];
-    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
-      t = jv_mul(t, brdf);
-      z = z + hp.w;
-      const jvec3 o = jv_neg(d);
-      const jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);  // bounce_mirror's statement
-      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
-      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
-      state[p] = make_float4(t.x, t.y, t.z, z);
-      mirrors[p] = k + 1u;
-      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
-      return;
-    }
-    z = z + hp.w;
-    a = jv_mul(t, brdf);
-    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
-  }
-  float4 s0 = acc_az[p], s1 = acc_n[p];
-  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
-  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
-  if (last) {
-    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
-    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
-  }
-  acc_az[p] = s0;
-  acc_n[p] = s1;
+  guide_hits_body(S, G, queue, count, state, mirrors, acc_az, acc_n, last, inv_g, next_queue, next_count, NoTables{});
 }
-// ... in a smooth render (SM_SMOOTH; include/jade_bvh.h, "The shading normal, stated"): the same statements with the shading normal of the hit -
-// normal(triangle, hit point, -d) from the render's table - in the mirror's reflection, formed again with the flat normal where it does not
-// leave on the viewer's side of it, and in the normal guide.  A text of its own: k_guide_hits keeps its instructions.
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_smooth(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
                                                                      uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
                                                                      uint32_t* next_queue, uint32_t* next_count, const float4* table) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= *count) return;
-  const int p = (int)queue[i];
-  const float4 sl = G.slot[p];
-  const jvec3 d = jv(sl.x, sl.y, sl.z);
-  const int h = __float_as_int(sl.w);
-  float4 st = state[p];
-  jvec3 t = jv(st.x, st.y, st.z);
-  float z = st.w;
-  jvec3 a, n;
-  if (h < 0) {
-    a = t;
-    n = jv(0.0f, 0.0f, 0.0f);
-    z = 0.0f;
-  } else {
-    const float4 hp = G.hitp[p];
-    const float4 tn = S.tnorm[h];
-    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
-    const jvec3 flat = jv(tn.x, tn.y, tn.z);
-    const jvec3 o = jv_neg(d);
-    const jvec3 norm = shading_normal(table, h, flat, jv(hp.x, hp.y, hp.z), o);
-    const jvec3 brdf = V3(m->brdf);
-    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
-    const uint32_t k = mirrors[p];
-    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
-      t = jv_mul(t, brdf);
-      z = z + hp.w;
-      jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);
-      if (!same_side(refl, o, flat)) refl = jv_sub(jv_scale(flat, 2 * jv_dot(o, flat)), o);
-      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
-      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
-      state[p] = make_float4(t.x, t.y, t.z, z);
-      mirrors[p] = k + 1u;
-      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
-      return;
-    }
-    z = z + hp.w;
-    a = jv_mul(t, brdf);
-    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
-  }
-  float4 s0 = acc_az[p], s1 = acc_n[p];
-  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
-  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
-  if (last) {
-    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
-    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
-  }
-  acc_az[p] = s0;
-  acc_n[p] = s1;
+  guide_hits_body(S, G, queue, count, state, mirrors, acc_az, acc_n, last, inv_g, next_queue, next_count, table);
 }
-// ... in a textured render (SM_TEX; include/jade_bvh.h, "The surface colour, stated"): k_guide_hits_smooth with brdf_eff - the brdf times the surface
-// colour at the hit - in the throughput and in the albedo guide, at every vertex of the mirror chain; `table` carries the vertex normals the render
-// began with, or the all-flat table.  A third text: through a shared body k_guide_hits_smooth came out in other instructions.
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_textured(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
                                                                        uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
                                                                        uint32_t* next_queue, uint32_t* next_count, TexTables table) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= *count) return;
-  const int p = (int)queue[i];
-  const float4 sl = G.slot[p];
-  const jvec3 d = jv(sl.x, sl.y, sl.z);
-  const int h = __float_as_int(sl.w);
-  float4 st = state[p];
-  jvec3 t = jv(st.x, st.y, st.z);
-  float z = st.w;
-  jvec3 a, n;
-  if (h < 0) {
-    a = t;
-    n = jv(0.0f, 0.0f, 0.0f);
-    z = 0.0f;
-  } else {
-    const float4 hp = G.hitp[p];
-    const float4 tn = S.tnorm[h];
-    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
-    const jvec3 flat = jv(tn.x, tn.y, tn.z);
-    const jvec3 o = jv_neg(d);
-    const jvec3 norm = shading_normal(table, h, flat, jv(hp.x, hp.y, hp.z), o);
-    const jvec3 brdf = jv_mul(V3(m->brdf), surface_colour(table, h, jv(hp.x, hp.y, hp.z)));
-    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
-    const uint32_t k = mirrors[p];
-    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
-      t = jv_mul(t, brdf);
-      z = z + hp.w;
-      jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);
-      if (!same_side(refl, o, flat)) refl = jv_sub(jv_scale(flat, 2 * jv_dot(o, flat)), o);
-      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
-      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
-      state[p] = make_float4(t.x, t.y, t.z, z);
-      mirrors[p] = k + 1u;
-      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
-      return;
-    }
-    z = z + hp.w;
-    a = jv_mul(t, brdf);
-    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
-  }
-  float4 s0 = acc_az[p], s1 = acc_n[p];
-  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
-  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
-  if (last) {
-    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
-    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
-  }
-  acc_az[p] = s0;
-  acc_n[p] = s1;
+  guide_hits_body(S, G, queue, count, state, mirrors, acc_az, acc_n, last, inv_g, next_queue, next_count, table);
 }
-
-// ... in a mapped render (SM_NMAP; include/jade_bvh.h, "The mapped normal, stated"): k_guide_hits_textured with the mapped normal of the hit - in the
-// mirror chain and in the normal guide; `table` carries the map's tables beside the textured render's.  A fourth text, for the same reason.
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_mapped(DevScene S, PathState G, const uint32_t* queue, const uint32_t* count, float4* state,
                                                                      uint32_t* mirrors, float4* acc_az, float4* acc_n, int last, float inv_g,
                                                                      uint32_t* next_queue, uint32_t* next_count, MapTables table) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= *count) return;
-  const int p = (int)queue[i];
-  const float4 sl = G.slot[p];
-  const jvec3 d = jv(sl.x, sl.y, sl.z);
-  const int h = __float_as_int(sl.w);
-  float4 st = state[p];
-  jvec3 t = jv(st.x, st.y, st.z);
-  float z = st.w;
-  jvec3 a, n;
-  if (h < 0) {
-    a = t;
-    n = jv(0.0f, 0.0f, 0.0f);
-    z = 0.0f;
-  } else {
-    const float4 hp = G.hitp[p];
-    const float4 tn = S.tnorm[h];
-    const DevMaterial* m = S.mats + __float_as_uint(tn.w);
-    const jvec3 flat = jv(tn.x, tn.y, tn.z);
-    const jvec3 o = jv_neg(d);
-    const jvec3 norm = shading_normal(table, h, flat, jv(hp.x, hp.y, hp.z), o);
-    const jvec3 brdf = jv_mul(V3(m->brdf), surface_colour(table, h, jv(hp.x, hp.y, hp.z)));
-    const bool emissive = m->emissive[0] > 1.5e-4f || m->emissive[1] > 1.5e-4f || m->emissive[0] > 1.5e-4f;  // (bounce_mirror's test, as written)
-    const uint32_t k = mirrors[p];
-    if (m->reflex_mode == JADE_MIRROR && !emissive && k < (uint32_t)JADE_MAX_FULL_REFLEX_TIME) {
-      t = jv_mul(t, brdf);
-      z = z + hp.w;
-      jvec3 refl = jv_sub(jv_scale(norm, 2 * jv_dot(o, norm)), o);
-      if (!same_side(refl, o, flat)) refl = jv_sub(jv_scale(flat, 2 * jv_dot(o, flat)), o);
-      G.orgs[p] = make_float4(hp.x, hp.y, hp.z, __int_as_float(h));
-      G.slot[p] = make_float4(refl.x, refl.y, refl.z, __int_as_float(-1));
-      state[p] = make_float4(t.x, t.y, t.z, z);
-      mirrors[p] = k + 1u;
-      next_queue[atomicAdd(next_count, 1u)] = (uint32_t)p;
-      return;
-    }
-    z = z + hp.w;
-    a = jv_mul(t, brdf);
-    n = jv_dot(norm, d) > 0.0f ? jv_neg(norm) : norm;
-  }
-  float4 s0 = acc_az[p], s1 = acc_n[p];
-  s0 = make_float4(s0.x + a.x, s0.y + a.y, s0.z + a.z, s0.w + z);
-  s1 = make_float4(s1.x + n.x, s1.y + n.y, s1.z + n.z, 0.0f);
-  if (last) {
-    s0 = make_float4(s0.x * inv_g, s0.y * inv_g, s0.z * inv_g, s0.w * inv_g);
-    s1 = make_float4(s1.x * inv_g, s1.y * inv_g, s1.z * inv_g, 0.0f);
-  }
-  acc_az[p] = s0;
-  acc_n[p] = s1;
+  guide_hits_body(S, G, queue, count, state, mirrors, acc_az, acc_n, last, inv_g, next_queue, next_count, table);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ filter --
@@ -605,7 +467,7 @@ static int dn_guides(jade_scene* s, int G) {
                            texture_tables(s));
       else if (smooth_on(s))
         hipLaunchKernelGGL(k_guide_hits_smooth, dim3(dn_grid(count)), dim3(JADE_DN_BLOCK), 0, s->stream, s->dev, g, queue, &qc[cur].count, state, mirrors,
-                           s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count, s->b_smooth.as<float4>());
+                           s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count, smooth_table(s));
       else
       hipLaunchKernelGGL(k_guide_hits, dim3(dn_grid(count)), dim3(JADE_DN_BLOCK), 0, s->stream, s->dev, g, queue, &qc[cur].count, state, mirrors,
                          s->b_dn_az.as<float4>(), s->b_dn_n.as<float4>(), smp == G - 1 ? 1 : 0, inv_g, next_queue, &qc[cur ^ 1].count);

@@ -1410,289 +1410,6 @@ void jade_scene_destroy(jade_scene* s) {
   delete s;
 }
 
-// The thin lens of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_lens(jade_scene* s, const jade_lens_params* lens) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (!lens) {
-    s->lens = jade_lens_params{};
-    return JADE_OK;
-  }
-  if (!std::isfinite(lens->aperture_radius) || !(lens->aperture_radius >= 0.0f)) return jade_fail(JADE_ERR_INVALID, "aperture_radius must be finite and >= 0");
-  if (lens->aperture_radius > 0.0f && (!std::isfinite(lens->focus_distance) || !(lens->focus_distance > 0.0f)))
-    return jade_fail(JADE_ERR_INVALID, "focus_distance must be finite and > 0 with an open aperture");
-  s->lens = *lens;
-  return JADE_OK;
-}
-int jade_scene_get_lens(jade_scene* s, jade_lens_params* out) {
-  if (!s || !out) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *out = s->lens;
-  return JADE_OK;
-}
-
-// The shutter of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_shutter(jade_scene* s, const jade_shutter_params* sh) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (!sh) {
-    s->shutter = jade_shutter_params{};
-    s->shutter_set = false;
-    return JADE_OK;
-  }
-  for (int i = 0; i < 3; ++i)
-    if (!std::isfinite(sh->eye_close[i])) return jade_fail(JADE_ERR_INVALID, "eye_close must be finite");
-  for (int j = 0; j < 16; ++j)
-    if (!std::isfinite(sh->camera_close[j])) return jade_fail(JADE_ERR_INVALID, "camera_close must be finite");
-  if (!std::isfinite(sh->t_open) || !std::isfinite(sh->t_close) || !(0.0f <= sh->t_open && sh->t_open <= sh->t_close && sh->t_close <= 1.0f))
-    return jade_fail(JADE_ERR_INVALID, "the shutter interval must satisfy 0 <= t_open <= t_close <= 1");
-  s->shutter = *sh;
-  s->shutter_set = true;
-  return JADE_OK;
-}
-int jade_scene_get_shutter(jade_scene* s, jade_shutter_params* out, int* is_set) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (out) *out = s->shutter_set ? s->shutter : jade_shutter_params{};
-  if (is_set) *is_set = s->shutter_set ? 1 : 0;
-  return JADE_OK;
-}
-
-// The light sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_light_sampling(jade_scene* s, int mode) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (mode != JADE_LIGHTS_ALL && mode != JADE_LIGHTS_ONE) return jade_fail(JADE_ERR_INVALID, "unknown light sampling (JADE_LIGHTS_*)");
-  s->light_sampling = mode;
-  return JADE_OK;
-}
-int jade_scene_get_light_sampling(jade_scene* s, int* mode) {
-  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *mode = s->light_sampling;
-  return JADE_OK;
-}
-
-// The bounce sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_bounce_sampling(jade_scene* s, int mode) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (mode != JADE_BOUNCE_UNIFORM && mode != JADE_BOUNCE_COSINE) return jade_fail(JADE_ERR_INVALID, "unknown bounce sampling (JADE_BOUNCE_*)");
-  s->bounce_sampling = mode;
-  return JADE_OK;
-}
-int jade_scene_get_bounce_sampling(jade_scene* s, int* mode) {
-  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *mode = s->bounce_sampling;
-  return JADE_OK;
-}
-
-// The direct sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_direct_sampling(jade_scene* s, int mode) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (mode != JADE_DIRECT_RAYS && mode != JADE_DIRECT_MIS) return jade_fail(JADE_ERR_INVALID, "unknown direct sampling (JADE_DIRECT_*)");
-  s->direct_sampling = mode;
-  return JADE_OK;
-}
-int jade_scene_get_direct_sampling(jade_scene* s, int* mode) {
-  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *mode = s->direct_sampling;
-  return JADE_OK;
-}
-
-// The passes of the scene handle (include/jade_bvh.h): read by the next jade_render_begin.
-int jade_scene_set_passes(jade_scene* s, int on) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  s->passes = on != 0;
-  return JADE_OK;
-}
-int jade_scene_get_passes(jade_scene* s, int* on) {
-  if (!s || !on) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *on = s->passes ? 1 : 0;
-  return JADE_OK;
-}
-
-// The branch sampling of the scene handle (include/jade_bvh.h): checked here, read by the next jade_render_begin.
-int jade_scene_set_branch_sampling(jade_scene* s, int mode) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (mode != JADE_BRANCH_RANDOM && mode != JADE_BRANCH_STRATIFIED) return jade_fail(JADE_ERR_INVALID, "unknown branch sampling (JADE_BRANCH_*)");
-  s->branch_sampling = mode;
-  return JADE_OK;
-}
-int jade_scene_get_branch_sampling(jade_scene* s, int* mode) {
-  if (!s || !mode) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *mode = s->branch_sampling;
-  return JADE_OK;
-}
-
-// The vertex normals of the scene handle (include/jade_bvh.h, "The shading normal, stated"): the table's records (jade_smooth.h) are made here,
-// from the triangles as the handle holds them, and uploaded by the next jade_render_begin - a render in progress keeps the table it began with.
-int jade_scene_set_vertex_normals(jade_scene* s, const float* normals, int32_t n_triangles) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (!normals) {
-    s->smooth_rec.clear();
-    s->smooth_rec.shrink_to_fit();
-    s->smooth_any = false;
-    s->smooth_uploaded = false;
-    s->nmap_uploaded = false;  // (a normal map's records carry the vertex normals: jade_normal_map.h)
-    return JADE_OK;
-  }
-  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "vertex normals: the triangle count is not the scene's");
-  HIP_TRY(hipSetDevice(s->device));
-  std::vector<jade_triangle> tris((size_t)n_triangles);
-  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  std::vector<float4> rec(tris.size() * JADE_SMOOTH_REC);
-  bool any = false;
-  for (size_t i = 0; i < tris.size(); ++i) {
-    const jade_triangle& t = tris[i];
-    smooth_record(t.p1, t.p2, t.p3, normals + 9 * i, t.norm, &rec[i * JADE_SMOOTH_REC]);
-    uint32_t flag;
-    memcpy(&flag, &rec[i * JADE_SMOOTH_REC].w, 4);
-    any = any || flag != SMOOTH_FLAT;
-  }
-  s->smooth_rec.swap(rec);
-  s->smooth_any = any;
-  s->smooth_uploaded = false;
-  s->nmap_uploaded = false;
-  return JADE_OK;
-}
-int jade_scene_get_vertex_normals(jade_scene* s, int* set) {
-  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *set = s->smooth_rec.empty() ? 0 : 1;
-  return JADE_OK;
-}
-
-// The textures of the scene handle (include/jade_bvh.h, "The surface colour, stated"): the records and the texel buffer (jade_texture.h) are made
-// here, from the triangles as the handle holds them, and uploaded by the next jade_render_begin - a render in progress keeps the table it began
-// with.  Everything is checked before anything of the handle changes: a refused call leaves the table that was there.
-int jade_scene_set_textures(jade_scene* s, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of, int32_t n_triangles) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (n_images == 0 || !images || !uv || !image_of) {
-    for (auto* v : {&s->tex_rec, &s->tex_texels}) {
-      v->clear();
-      v->shrink_to_fit();
-    }
-    s->tex_images.clear();
-    s->tex_any = false;
-    s->tex_uploaded = false;
-    return JADE_OK;
-  }
-  if (n_images < 0 || n_images > JADE_TEX_MAX_IMAGES)
-    return jade_fail(JADE_ERR_INVALID, "textures: " + std::to_string(n_images) + " images (at most " + std::to_string(JADE_TEX_MAX_IMAGES) + ")");
-  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "textures: the triangle count " + std::to_string(n_triangles) + " is not the scene's");
-  std::vector<uint4> heads((size_t)n_images);
-  size_t total = 0;
-  for (int32_t k = 0; k < n_images; ++k) {
-    const jade_texture_image& im = images[k];
-    if (im.width < 1 || im.width > JADE_TEX_MAX_SIZE || im.height < 1 || im.height > JADE_TEX_MAX_SIZE)
-      return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " is " + std::to_string(im.width) + " x " + std::to_string(im.height) +
-                                             " (a width and a height of 1 .. " + std::to_string(JADE_TEX_MAX_SIZE) + ")");
-    if (!im.rgb) return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " has no texels");
-    heads[k] = make_uint4((uint32_t)(total & 0xffffffffu), (uint32_t)(total >> 32), (uint32_t)im.width, (uint32_t)im.height);
-    total += (size_t)im.width * (size_t)im.height;
-  }
-  bool any = false;
-  for (int32_t t = 0; t < n_triangles; ++t) {
-    if (image_of[t] < -1 || image_of[t] >= n_images)
-      return jade_fail(JADE_ERR_INVALID, "textures: image_of[" + std::to_string(t) + "] = " + std::to_string(image_of[t]) + " is outside -1 .. " + std::to_string(n_images - 1));
-    any = any || image_of[t] >= 0;
-  }
-  std::vector<float4> texels(total);
-  for (int32_t k = 0; k < n_images; ++k) {
-    const size_t first = ((size_t)heads[k].y << 32) | heads[k].x, n = (size_t)heads[k].z * heads[k].w;
-    const float* rgb = images[k].rgb;
-    for (size_t i = 0; i < n; ++i) {
-      if (!std::isfinite(rgb[3 * i]) || !std::isfinite(rgb[3 * i + 1]) || !std::isfinite(rgb[3 * i + 2]))
-        return jade_fail(JADE_ERR_INVALID, "textures: image " + std::to_string(k) + " has a texel that is not finite at (" + std::to_string(i % heads[k].z) + ", " +
-                                               std::to_string(i / heads[k].z) + ")");
-      texels[first + i] = make_float4(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2], 0.0f);
-    }
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  std::vector<jade_triangle> tris((size_t)n_triangles);
-  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  std::vector<float4> rec(tris.size() * JADE_TEX_REC);
-  for (size_t i = 0; i < tris.size(); ++i) texture_record(tris[i].p1, tris[i].p2, tris[i].p3, uv + 6 * i, image_of[i], &rec[i * JADE_TEX_REC]);
-  s->tex_rec.swap(rec);
-  s->tex_texels.swap(texels);
-  s->tex_images.swap(heads);
-  s->tex_any = any;
-  s->tex_uploaded = false;
-  return JADE_OK;
-}
-int jade_scene_get_textures(jade_scene* s, int* set) {
-  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *set = s->tex_rec.empty() ? 0 : 1;
-  return JADE_OK;
-}
-
-// The normal maps of the scene handle (include/jade_bvh.h, "The mapped normal, stated"): the records and the texel buffer (jade_normal_map.h) are
-// made here as the textures' are, checked in the same order and refused in the same way; the vertex normals a mapped vertex bends are joined to the
-// records by the next jade_render_begin, which uploads them.
-int jade_scene_set_normal_maps(jade_scene* s, int32_t n_images, const jade_texture_image* images, const float* uv, const int32_t* image_of, int32_t n_triangles,
-                               float strength) {
-  if (!s) return jade_fail(JADE_ERR_INVALID, "null argument");
-  if (n_images == 0 || !images || !uv || !image_of) {
-    for (auto* v : {&s->nmap_rec, &s->nmap_texels}) {
-      v->clear();
-      v->shrink_to_fit();
-    }
-    s->nmap_images.clear();
-    s->nmap_any = false;
-    s->nmap_uploaded = false;
-    return JADE_OK;
-  }
-  if (!(strength >= 0.0f && strength < INFINITY))
-    return jade_fail(JADE_ERR_INVALID, "normal maps: the strength " + std::to_string(strength) + " is not finite and >= 0");
-  if (n_images < 0 || n_images > JADE_TEX_MAX_IMAGES)
-    return jade_fail(JADE_ERR_INVALID, "normal maps: " + std::to_string(n_images) + " images (at most " + std::to_string(JADE_TEX_MAX_IMAGES) + ")");
-  if (n_triangles != s->dev.n_tris) return jade_fail(JADE_ERR_INVALID, "normal maps: the triangle count " + std::to_string(n_triangles) + " is not the scene's");
-  std::vector<uint4> heads((size_t)n_images);
-  size_t total = 0;
-  for (int32_t k = 0; k < n_images; ++k) {
-    const jade_texture_image& im = images[k];
-    if (im.width < 1 || im.width > JADE_TEX_MAX_SIZE || im.height < 1 || im.height > JADE_TEX_MAX_SIZE)
-      return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " is " + std::to_string(im.width) + " x " + std::to_string(im.height) +
-                                             " (a width and a height of 1 .. " + std::to_string(JADE_TEX_MAX_SIZE) + ")");
-    if (!im.rgb) return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " has no texels");
-    heads[k] = make_uint4((uint32_t)(total & 0xffffffffu), (uint32_t)(total >> 32), (uint32_t)im.width, (uint32_t)im.height);
-    total += (size_t)im.width * (size_t)im.height;
-  }
-  for (int32_t t = 0; t < n_triangles; ++t)
-    if (image_of[t] < -1 || image_of[t] >= n_images)
-      return jade_fail(JADE_ERR_INVALID, "normal maps: image_of[" + std::to_string(t) + "] = " + std::to_string(image_of[t]) + " is outside -1 .. " + std::to_string(n_images - 1));
-  std::vector<float4> texels(total);
-  for (int32_t k = 0; k < n_images; ++k) {
-    const size_t first = ((size_t)heads[k].y << 32) | heads[k].x, n = (size_t)heads[k].z * heads[k].w;
-    const float* xyz = images[k].rgb;
-    for (size_t i = 0; i < n; ++i) {
-      if (!std::isfinite(xyz[3 * i]) || !std::isfinite(xyz[3 * i + 1]) || !std::isfinite(xyz[3 * i + 2]))
-        return jade_fail(JADE_ERR_INVALID, "normal maps: image " + std::to_string(k) + " has a texel that is not finite at (" + std::to_string(i % heads[k].z) + ", " +
-                                               std::to_string(i / heads[k].z) + ")");
-      texels[first + i] = make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.0f);
-    }
-  }
-  HIP_TRY(hipSetDevice(s->device));
-  std::vector<jade_triangle> tris((size_t)n_triangles);
-  HIP_TRY(hipMemcpyAsync(tris.data(), s->b_tris.p, sizeof(jade_triangle) * tris.size(), hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(hipStreamSynchronize(s->stream));
-  std::vector<float4> rec(tris.size() * JADE_NMAP_REC);
-  bool any = false;
-  for (size_t i = 0; i < tris.size(); ++i) {
-    normal_map_record(tris[i].p1, tris[i].p2, tris[i].p3, uv + 6 * i, image_of[i], &rec[i * JADE_NMAP_REC]);
-    int32_t stored;
-    memcpy(&stored, &rec[i * JADE_NMAP_REC].w, 4);
-    any = any || stored >= 0;  // (a triangle whose frame cannot be formed is stored unmapped)
-  }
-  s->nmap_rec.swap(rec);
-  s->nmap_texels.swap(texels);
-  s->nmap_images.swap(heads);
-  s->nmap_strength = strength;
-  s->nmap_any = any;
-  s->nmap_uploaded = false;
-  return JADE_OK;
-}
-int jade_scene_get_normal_maps(jade_scene* s, int* set) {
-  if (!s || !set) return jade_fail(JADE_ERR_INVALID, "null argument");
-  *set = s->nmap_rec.empty() ? 0 : 1;
-  return JADE_OK;
-}
-
 static int setup_state(jade_scene* s, int npx, int rpp, int nslots, int sum_lanes) {
   const int npix = npx * rpp;
   // carve every per-pixel array out of one allocation
@@ -1786,49 +1503,13 @@ int jade_render_begin(jade_scene* s, const jade_render_params* rp) {
   uint32_t mode = 0;
   std::string why;
   if (const int rc = shade_mode_for(rp->env_sampling, s->lens.aperture_radius > 0.0f, s->shutter_set, s->light_sampling, s->bounce_sampling,
-                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->smooth_any, s->tex_any,
-                                    s->nmap_any))
+                                    s->direct_sampling, &mode, &why, s->passes, s->branch_sampling == JADE_BRANCH_STRATIFIED, s->surf.set.normals_any,
+                                    s->surf.set.textures.any, s->surf.set.maps.any))
     return jade_fail(rc, why);
   if ((mode & SM_PASSES) && s->tun.pixel_rotate)
     return jade_fail(JADE_ERR_UNSUPPORTED, "passes (jade_scene_set_passes) with JADE_PIXEL_ROTATE (a record's samples move between pixels)");
   HIP_TRY(hipSetDevice(s->device));
-  if ((mode & SM_TEX) && s->tex_any && !s->tex_uploaded) {  // the same rule for the textures
-    s->have_rp = false;
-    HIP_TRY(upload(s->b_tex_rec, s->tex_rec.data(), s->tex_rec.size(), s->stream));
-    HIP_TRY(upload(s->b_tex_texels, s->tex_texels.data(), s->tex_texels.size(), s->stream));
-    HIP_TRY(upload(s->b_tex_images, s->tex_images.data(), s->tex_images.size(), s->stream));
-    s->tex_uploaded = true;
-  }
-  if ((mode & SM_TEX) && !s->b_tex_flat.p) {
-    const size_t bytes = sizeof(float4) * JADE_SMOOTH_REC * (size_t)s->dev.n_tris;
-    HIP_TRY(s->b_tex_flat.alloc(bytes));
-    HIP_TRY(hipMemsetAsync(s->b_tex_flat.p, 0, bytes, s->stream));
-  }
-  if (mode & SM_TEX) s->tex_none = !s->tex_any;
-  if ((mode & SM_NMAP) && s->tex_none && !s->b_tex_none.p) {  // a mapped render of a handle that names no image: texture records that say so (image -1, the 16 bytes such a vertex reads)
-    const int32_t no_image = -1;
-    float w;
-    memcpy(&w, &no_image, 4);
-    const std::vector<float4> none((size_t)s->dev.n_tris * JADE_TEX_REC, make_float4(0.0f, 0.0f, 0.0f, w));
-    HIP_TRY(upload(s->b_tex_none, none.data(), none.size(), s->stream));
-  }
-  if ((mode & SM_NMAP) && !s->nmap_uploaded) {  // ... and for the normal maps, whose records carry the vertex normals the handle has now (normal_map_join)
-    s->have_rp = false;
-    std::vector<float4> rec(s->nmap_rec);
-    const size_t n = rec.size() / JADE_NMAP_REC;
-    for (size_t i = 0; i < n; ++i) normal_map_join(&rec[i * JADE_NMAP_REC], s->smooth_any ? &s->smooth_rec[i * JADE_SMOOTH_REC] : nullptr);
-    HIP_TRY(upload(s->b_nmap_rec, rec.data(), rec.size(), s->stream));
-    HIP_TRY(upload(s->b_nmap_texels, s->nmap_texels.data(), s->nmap_texels.size(), s->stream));
-    HIP_TRY(upload(s->b_nmap_images, s->nmap_images.data(), s->nmap_images.size(), s->stream));
-    s->nmap_uploaded = true;
-  }
-  if (mode & SM_NMAP) s->nmap_strength_on = s->nmap_strength;
-  if ((mode & SM_SMOOTH) && s->smooth_any && !s->smooth_uploaded) {  // the handle's table as it is now: the render keeps it whatever the setter is told before the next begin
-    s->have_rp = false;  // (the earlier render's kernels would read the buffer that is given back here)
-    HIP_TRY(upload(s->b_smooth, s->smooth_rec.data(), s->smooth_rec.size(), s->stream));
-    s->smooth_uploaded = true;
-  }
-  if (mode & SM_TEX) s->tex_normals = (s->smooth_any ? s->b_smooth : s->b_tex_flat).as<float4>();  // the handle's vertex normals, or the all-flat table where it carries none
+  if (const int rc = surface_begin(s, mode)) return rc;  // the surface tables the render reads (jade_surface.hip)
   const int tx = (rp->width + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE, ty = (rp->height + JADE_TILE_SIZE - 1) / JADE_TILE_SIZE;
   s->tile_ids.clear();
   for (int y = 0; y < ty; ++y)
@@ -1970,7 +1651,7 @@ static ShadeArgs<K> mode_args(const jade_scene* s) {
     a.map_tables = map_tables(s);
   else if constexpr (sm(K, SM_TEX))
     a.tex_tables = texture_tables(s);
-  else if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = s->b_smooth.as<float4>();
+  else if constexpr (sm(K, SM_SMOOTH)) a.smooth_table = smooth_table(s);
   return a;
 }
 template <uint32_t M>

@@ -140,18 +140,14 @@ int jade_render_multi(jade_scene* const* scenes, int ndev, const jade_render_par
     for (int i = 1; i < ndev; ++i)
       if (scenes[i]->*k.mode != scenes[0]->*k.mode)
         return jade_fail(JADE_ERR_INVALID, std::string("the scenes carry different ") + k.noun + " sampling modes (" + k.setter + "): scene " + std::to_string(i) + " against scene 0");
-  // ... and either every scene shades smooth (jade_scene_set_vertex_normals, a table that is not flat everywhere) or none does
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->smooth_any != scenes[0]->smooth_any)
-      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry vertex normals (jade_scene_set_vertex_normals): scene " + std::to_string(i) + " against scene 0");
-  // ... and the same for textures (jade_scene_set_textures, a table in which a triangle names an image)
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->tex_any != scenes[0]->tex_any)
-      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry textures (jade_scene_set_textures): scene " + std::to_string(i) + " against scene 0");
-  // ... and for normal maps (jade_scene_set_normal_maps, a table in which a triangle is mapped)
-  for (int i = 1; i < ndev; ++i)
-    if (scenes[i]->nmap_any != scenes[0]->nmap_any)
-      return jade_fail(JADE_ERR_INVALID, "the scenes do not all carry normal maps (jade_scene_set_normal_maps): scene " + std::to_string(i) + " against scene 0");
+  // ... and either every scene carries a surface table that acts or none does: vertex normals that are not flat everywhere, textures in which a
+  // triangle names an image, normal maps in which a triangle is mapped
+  const auto table_any = [](const jade_scene* s, int k) { return k == 0 ? s->surf.set.normals_any : k == 1 ? s->surf.set.textures.any : s->surf.set.maps.any; };
+  static const char* const kTables[] = {"vertex normals (jade_scene_set_vertex_normals)", "textures (jade_scene_set_textures)", "normal maps (jade_scene_set_normal_maps)"};
+  for (int k = 0; k < 3; ++k)
+    for (int i = 1; i < ndev; ++i)
+      if (table_any(scenes[i], k) != table_any(scenes[0], k))
+        return jade_fail(JADE_ERR_INVALID, std::string("the scenes do not all carry ") + kTables[k] + ": scene " + std::to_string(i) + " against scene 0");
   // ... and none keeps passes: only the frame is gathered here (each rank renders its share and calls jade_render_passes)
   for (int i = 0; i < ndev; ++i)
     if (scenes[i]->passes)

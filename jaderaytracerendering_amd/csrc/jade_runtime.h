@@ -318,6 +318,33 @@ static inline int shade_mode_for(int env_sampling, bool lens, bool shutter, int 
   return JADE_ERR_UNSUPPORTED;
 }
 
+// The surface tables of a scene handle - vertex normals (jade_smooth.h), textures (jade_texture.h), normal maps (jade_normal_map.h) - kept by
+// jade_surface.hip in two parts: what the setters left, which the next jade_render_begin takes, and what the render in progress took, which
+// no setter touches.  Adding a per-triangle table: DESIGN.md 3.22.
+struct SurfaceImages {  // an image set as jade_texture.h lays it out: the triangles' records, the texels of all images, a head per image
+  std::vector<float4> rec, texels;
+  std::vector<uint4> images;
+  bool any = false;  // a triangle names an image (empty records: no table set)
+};
+struct SurfaceTables {
+  struct {
+    std::vector<float4> normals;  // the vertex normals' records (empty: none set) ...
+    bool normals_any = false;     // ... and whether any triangle of them is not flat
+    SurfaceImages textures;
+    SurfaceImages maps;           // (the records without their smooth part: surface_join_maps adds it)
+    float strength = 1.0f;        // the maps'
+  } set;
+  struct {
+    DevBuf normals, tex_rec, tex_texels, tex_images, map_rec, map_texels, map_images;
+    bool normals_current = false, textures_current = false, maps_current = false;  // the buffers hold what the setters left (surface_begin uploads once)
+    DevBuf flat;      // the all-flat vertex normals a textured render reads where the handle carries none (zeros: SMOOTH_FLAT), made on first need
+    DevBuf no_image;  // the texture records of a mapped render whose handle names no image (every triangle -1), made on first need
+    const float4* tex_normals = nullptr;  // the vertex normals the textured render in progress began with: normals or flat
+    bool tex_none = false;                // ... it reads no_image in place of tex_rec
+    float strength = 1.0f;                // ... and the maps' strength it began with
+  } dev;
+};
+
 struct jade_scene {
   int device = 0;
   Tunables tun;
@@ -337,27 +364,7 @@ struct jade_scene {
   int direct_sampling = JADE_DIRECT_RAYS;     // jade_scene_set_direct_sampling
   bool passes = false;                        // jade_scene_set_passes
   int branch_sampling = JADE_BRANCH_RANDOM;   // jade_scene_set_branch_sampling
-  // jade_scene_set_vertex_normals: the table as jade_smooth.h lays it out (empty: none set), whether any triangle of it is not flat, and
-  // whether b_smooth holds it already (the next jade_render_begin uploads it once)
-  std::vector<float4> smooth_rec;
-  bool smooth_any = false, smooth_uploaded = false;
-  DevBuf b_smooth;
-  // jade_scene_set_textures: the records and the images as jade_texture.h lays them out (empty: none set), whether any triangle names an image, and
-  // whether the device buffers hold them already (the next jade_render_begin uploads them once).  b_tex_flat: the all-flat vertex-normal table a
-  // textured render reads where the handle carries none (zeros: SMOOTH_FLAT)
-  std::vector<float4> tex_rec, tex_texels;
-  std::vector<uint4> tex_images;
-  bool tex_any = false, tex_uploaded = false;
-  DevBuf b_tex_rec, b_tex_texels, b_tex_images, b_tex_flat;
-  const float4* tex_normals = nullptr;  // ... and the vertex-normal table the textured render in progress began with: b_smooth or b_tex_flat
-  // jade_scene_set_normal_maps: the records (without their smooth part) and the images as jade_normal_map.h lays them out (empty: none set), the
-  // strength, whether any triangle is mapped, and whether b_nmap_rec holds the records joined with the vertex normals the handle has now.
-  // b_tex_none: the texture records of a mapped render whose handle names no image (every triangle -1); tex_none: the render in progress reads it
-  std::vector<float4> nmap_rec, nmap_texels;
-  std::vector<uint4> nmap_images;
-  float nmap_strength = 1.0f, nmap_strength_on = 1.0f;  // (the setter's; the render in progress's)
-  bool nmap_any = false, nmap_uploaded = false, tex_none = false;
-  DevBuf b_nmap_rec, b_nmap_texels, b_nmap_images, b_tex_none;
+  SurfaceTables surf;                         // jade_scene_set_vertex_normals / _textures / _normal_maps, and what the render in progress took of them
   // ... and what the render in progress took, whatever the setters are told before the next begin: its mode (ShadeMode bits; read through
   // the predicates below), with rc.lens_radius + ps.lens_k under SM_LENS and the shutter kernels' argument under SM_SHUTTER
   uint32_t mode = 0;
@@ -438,13 +445,17 @@ static inline bool smooth_on(const jade_scene* s) { return (s->mode & SM_SMOOTH)
 static inline bool textures_on(const jade_scene* s) { return (s->mode & SM_TEX) != 0; }
 // ... and what its kernels take (jade_texture.h): the tables as jade_render_begin left them
 static inline TexTables texture_tables(const jade_scene* s) {
-  return TexTables{s->tex_normals, (s->tex_none ? s->b_tex_none : s->b_tex_rec).as<float4>(), s->b_tex_texels.as<float4>(), s->b_tex_images.as<uint4>()};
+  const auto& d = s->surf.dev;
+  return TexTables{d.tex_normals, (d.tex_none ? d.no_image : d.tex_rec).as<float4>(), d.tex_texels.as<float4>(), d.tex_images.as<uint4>()};
 }
 // ... the normal maps are read: a textured render (textures_on is true as well) whose kernels take the map's tables beside the others
 static inline bool normal_maps_on(const jade_scene* s) { return (s->mode & SM_NMAP) != 0; }
 static inline MapTables map_tables(const jade_scene* s) {
-  return MapTables{texture_tables(s), s->b_nmap_rec.as<float4>(), s->b_nmap_texels.as<float4>(), s->b_nmap_images.as<uint4>(), s->nmap_strength_on};
+  const auto& d = s->surf.dev;
+  return MapTables{texture_tables(s), d.map_rec.as<float4>(), d.map_texels.as<float4>(), d.map_images.as<uint4>(), d.strength};
 }
+// ... and the vertex normals a smooth render without textures takes
+static inline const float4* smooth_table(const jade_scene* s) { return s->surf.dev.normals.as<float4>(); }
 
 // What jade_scene_create uploads, prepared on the host without a HIP call (jade_scene_prep.hip), and the facts derived from it.
 struct ScenePrep {
@@ -493,6 +504,16 @@ JADE_HIDDEN int resolve_to(jade_scene* s, int tonemap, float limit, float* dev_r
 JADE_HIDDEN int passes_setup(jade_scene* s, size_t npix);
 // ... and given back by the jade_render_begin of a render that keeps none, with the resolved images
 JADE_HIDDEN void passes_release(jade_scene* s);
+
+// The surface tables (jade_surface.hip).  surface_begin: what jade_render_begin does about them once `mode` is accepted - the uploads that are
+// due, the stand-in tables on first need, and what the render keeps; it ends the earlier render (have_rp) where a buffer that render reads is
+// replaced.  surface_join_maps: the normal maps' records as the setter left them, joined with the vertex normals the handle has now.
+// surface_check_images: the check of an image set (textures and normal maps, `who` is the message's prefix) - plain C++, no HIP call, nothing of
+// a handle read or written: the heads, the packed texels and whether a triangle names an image, or the refusal
+JADE_HIDDEN int surface_begin(jade_scene* s, uint32_t mode);
+JADE_HIDDEN std::vector<float4> surface_join_maps(const SurfaceTables& t);
+JADE_HIDDEN int surface_check_images(const char* who, int32_t n_images, const jade_texture_image* images, const int32_t* image_of, int32_t n_triangles,
+                                     int32_t n_scene, std::vector<uint4>* heads, std::vector<float4>* texels, bool* any);
 
 // What the glare (jade_glare.hip) takes from exposure (jade_expose.hip) rather than copying it: the check of display parameters, the
 // grow-only allocation, flush + k_resolve into b_out_rgb (compact tiles), the meter of n pixels at dev_rgb (tile_ids: compact tiles of

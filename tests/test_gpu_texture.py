@@ -25,6 +25,7 @@ import texture_spec as spec
 from conftest import B
 from jaderaytracerendering_amd import _abi, host as H
 from render_helpers import same_bits
+from texture_cases import FLOOR_S, FLOOR_Y, WALL_S, WALL_Y, corner_ray, mirror_and_wall
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -183,17 +184,7 @@ def test_render_is_the_float64_statement_sample_for_sample(hip, name):
     assert n + skipped == TC.SIZE * TC.SIZE * len(TC.FRAMES)
 
 
-def corner_ray(p, x, y, rx, ry):
-    """jade_spec.sample's camera ray with the two jitter draws given: (rx, ry) in {0, 1}^2 are the corners of pixel (x, y)."""
-    lx = (-1 + 2.0 / p.width * (x + rx - 0.5)) * (p.width / p.height)
-    ly = -1 + 2.0 / p.height * (y + ry - 0.5)
-    M = np.asarray(list(p.camera), np.float64).reshape(4, 4)
-    v = np.array([lx, ly, -1.5, 0.0])
-    d = np.array([sum(M[c][r] * v[c] for c in range(4)) for r in range(3)])
-    return np.asarray(list(p.eye), np.float64), d / math.sqrt(d @ d)
-
-
-FLOOR_Y, FLOOR_S, RAMP_W = -0.9, 12.0, 16
+RAMP_W = 16
 U_CENTRE, DU_DX = 1.0, 1.0 / 9.0
 
 
@@ -286,26 +277,7 @@ def test_the_closed_form_on_a_ramp_textured_floor(hip):
 
 
 # --------------------------------------------------------------------------------------------------------------------- the guide --
-WALL_Y, WALL_S = 5.0, 40.0
 FLOOR_TINT = np.array([0.5, 0.75, 0.875], F32)
-
-
-def mirror_and_wall(wall_image, floor_image):
-    """A mirror floor (brdf 0.9 0.8 0.7) and a diffuse wall (brdf 0.8 0.7 0.6) lying overhead at y = 5, facing down, u = 0.5 + x / 96: the
-    camera looks down at the floor - no camera ray meets the wall - and sees the wall in it."""
-    b = J.SceneBuilder()
-    try:
-        b.add_mesh(SP.quad(FLOOR_Y, FLOOR_S), SP.QUAD_I, H.material(brdf=(0.9, 0.8, 0.7), reflex_mode=_abi.MIRROR))
-        b.add_mesh(SP.quad(WALL_Y, WALL_S, flip=True), SP.QUAD_I, H.material(brdf=(0.8, 0.7, 0.6)))
-        b.set_env_constant(0.5, 0.6, 0.8)
-        hs = b.build()
-    finally:
-        b.close()
-    v = hs.vertices().astype(np.float64)
-    uv = (0.5 + v[:, :, [0, 2]] / (2.4 * WALL_S)).astype(F32)
-    is_wall = np.abs(hs.vertices()[:, :, 1] - WALL_Y).max(1) < 1e-6
-    assert is_wall.sum() == 2
-    return TC.textured(hs, [wall_image, floor_image], image_of=np.where(is_wall, 0, 1), uv=uv), is_wall
 
 
 def test_the_albedo_guide_is_the_product_of_the_chains_effective_brdfs(hip):

@@ -1,6 +1,7 @@
 """What the texture tests share (include/jade_bvh.h, "The surface colour, stated"): putting a table on a host scene, the scene with a
 colour per triangle baked into its materials, and the six scenes of the sample-for-sample comparison with their `need` tables (compared
 in tests/test_gpu_texture.py, counted by count() below on the CPU).  Nothing here opens a device."""
+import math
 import types
 
 import numpy as np
@@ -50,6 +51,39 @@ def baked(hs, c):
     t[:, 16:19] = t[:, 16:19] * c
     t[:, 24:27] = t[:, 24:27] * c
     return out
+
+
+# ---- the floor and the mirror-and-wall scene of the closed forms and the guide tests ----
+FLOOR_Y, FLOOR_S = -0.9, 12.0
+WALL_Y, WALL_S = 5.0, 40.0
+
+
+def corner_ray(p, x, y, rx, ry):
+    """jade_spec.sample's camera ray with the two jitter draws given: (rx, ry) in {0, 1}^2 are the corners of pixel (x, y)."""
+    lx = (-1 + 2.0 / p.width * (x + rx - 0.5)) * (p.width / p.height)
+    ly = -1 + 2.0 / p.height * (y + ry - 0.5)
+    M = np.asarray(list(p.camera), np.float64).reshape(4, 4)
+    v = np.array([lx, ly, -1.5, 0.0])
+    d = np.array([sum(M[c][r] * v[c] for c in range(4)) for r in range(3)])
+    return np.asarray(list(p.eye), np.float64), d / math.sqrt(d @ d)
+
+
+def mirror_and_wall(wall_image, floor_image):
+    """A mirror floor (brdf 0.9 0.8 0.7) and a diffuse wall (brdf 0.8 0.7 0.6) lying overhead at y = 5, facing down, u = 0.5 + x / 96: the
+    camera looks down at the floor - no camera ray meets the wall - and sees the wall in it."""
+    b = J.SceneBuilder()
+    try:
+        b.add_mesh(SP.quad(FLOOR_Y, FLOOR_S), SP.QUAD_I, H.material(brdf=(0.9, 0.8, 0.7), reflex_mode=_abi.MIRROR))
+        b.add_mesh(SP.quad(WALL_Y, WALL_S, flip=True), SP.QUAD_I, H.material(brdf=(0.8, 0.7, 0.6)))
+        b.set_env_constant(0.5, 0.6, 0.8)
+        hs = b.build()
+    finally:
+        b.close()
+    v = hs.vertices().astype(np.float64)
+    uv = (0.5 + v[:, :, [0, 2]] / (2.4 * WALL_S)).astype(F32)
+    is_wall = np.abs(hs.vertices()[:, :, 1] - WALL_Y).max(1) < 1e-6
+    assert is_wall.sum() == 2
+    return textured(hs, [wall_image, floor_image], image_of=np.where(is_wall, 0, 1), uv=uv), is_wall
 
 
 # ---- the six scenes, each with a random 16 x 16 image on every triangle through planar_uv ----
