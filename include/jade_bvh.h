@@ -27,7 +27,7 @@
  * The header also holds the HIP module's other entry points that the CPU
  * oracle does not implement: adaptive sampling and its noise map, the
  * edge-aware denoiser, exposure with its luminance meter, glare, the
- * thin-lens camera and the camera shutter (below).
+ * despeckle pass, the thin-lens camera and the camera shutter (below).
  * Exported by libjade_hip.so only; the oracle has none of them.
  */
 #ifndef JADE_BVH_H
@@ -342,6 +342,82 @@ int jade_glare_image(int device_id, int32_t width, int32_t height, const float* 
  * not changed. */
 int jade_render_glare(jade_scene* scene, const jade_glare_params* params, const jade_display_params* display,
                       float* out_rgb, uint8_t* out_bgr8, float* exposure_used);
+
+/* ---- Despeckle, stated: clamp the firefly pixels that the variance does not back ----
+ *
+ * Non-parity: the reference has no such pass.  Image-space, on the resolved linear frame, ahead of the denoiser; the render is not
+ * changed.  A pixel whose luminance stands above g times the K-th brightest of its neighbours is scaled down to that bound, unless the
+ * variance of its mean says that the excess is real: an excess carried by k of a pixel's samples stands about sqrt(k) standard errors
+ * above the neighbourhood, so "established at z sigmas" reads "at least about z^2 samples back it".  A lamp seen directly is kept, a
+ * highlight that a quarter of the samples hit is kept, one huge sample among 64 is kept by nothing.
+ *
+ * Everything is float32; every operation written below is ONE float operation, nothing is contracted, and the division is the
+ * correctly rounded one.
+ *
+ * Inputs: a frame c of W x H pixels in out_rgb's layout (pixel (x, y) at y*W + x); optionally v, W x H floats, the variance of each
+ * pixel's mean luminance as jade_render_guides gives it; the parameters iterations (0..4), radius R (1..3), rank K (1..4), gain g
+ * (finite, >= 1), floor f (finite, >= 0) and sigmas z (finite, >= 0).  zz = z * z, one float multiplication on the host.
+ *
+ * One pass.  Every decision is taken from the pass's INPUT, never from pixels already written:
+ *   Y(p) = (0.3f * r + 0.6f * g) + 0.1f * b          the denoiser's luminance, whose weights are the weights of v
+ *   p is usable if its three channels and Y(p) are finite.  An unusable pixel keeps its c and v bit for bit and is nobody's neighbour.
+ *   N(p) = the usable pixels q != p with |dx| <= R and |dy| <= R inside the image; nothing is replicated at the border.
+ *          If N(p) has fewer than K pixels, p is unchanged.
+ *   B = the K-th largest Y over N(p); ties count as separate entries
+ *   C = g * max(B, 0.0f) + f                          max(B, 0.0f) is B where B > 0 and +0.0f otherwise
+ *   if not Y(p) > C, p is unchanged.  Otherwise p is ABOVE.
+ *   p is ESTABLISHED if v is given, v(p) is finite and >= 0, and with d = Y(p) - C the test d * d > zz * v(p) holds - taken as
+ *   written, whatever under- or overflow it has.  An established pixel is unchanged.
+ *   Otherwise p is CLAMPED:  k = C / Y(p);  c'(p) = (k r, k g, k b);  v'(p) = (k * k) * v(p) where v is given;
+ *                            scale(p) = scale(p) * k, and scale starts at 1.0f.
+ * `iterations` passes run one after another, each on the previous pass's c and v.  iterations = 0 returns c (and v) bit for bit - -0.0
+ * and NaN payloads included - and runs no kernel, as strength = 0 does in the glare.
+ * 0 <= k < 1, so a clamped pixel never gains light and a finite frame stays finite.
+ *
+ * The report is all integers, so it does not depend on the order in which pixels are counted, and the reports of several frames add:
+ * n_usable is taken from the input frame; n_above, n_established and n_clamped are each summed over the passes; always
+ * n_above == n_established + n_clamped.  No floating-point atomic anywhere: every output word has one writer.
+ *
+ * The defaults come from the measurement in DESIGN.md 3.23. */
+typedef struct jade_despeckle_params {
+  int32_t iterations; /* passes, 0..4; 0 = identity */
+  int32_t radius;     /* R, 1..3: the neighbourhood is (2R + 1)^2 - 1 pixels */
+  int32_t rank;       /* K, 1..4: the K-th brightest neighbour sets the bound (K - 1 neighbouring speckles are seen through) */
+  float gain;         /* g, finite, >= 1 */
+  float floor;        /* f, finite, >= 0 */
+  float sigmas;       /* z, finite, >= 0: the standard errors by which an excess must stand above the bound to be kept */
+} jade_despeckle_params; /* 24 B */
+
+typedef struct jade_despeckle_report {
+  uint64_t n_usable, n_above, n_established, n_clamped;
+} jade_despeckle_report;
+
+/* 1 iteration, radius 1, rank 2, gain 2, floor 0, sigmas 2. */
+void jade_despeckle_defaults(jade_despeckle_params* p);
+
+/* The passes on a caller's host frame on device `device_id`.  variance (nullable): without it nothing is established.  out_variance
+ * (nullable) needs variance.  out_scale (nullable): W x H floats, the product of every k a pixel was clamped by, 1.0f elsewhere.
+ * out_rgb == rgb and out_variance == variance are allowed.  A null rgb, out_rgb or params, a bad size (as jade_denoise_image; also a
+ * height above 524280 = 8 * 65535 rows, which the kernel's grid does not hold), out_variance without variance, or a parameter outside
+ * its range or non-finite returns JADE_ERR_INVALID before any HIP call; device_id is checked as jade_denoise_image checks it.  This is
+ * what despeckles the gathered frame of several ranks: gather rgb (resolve) and jade_render_guides' variance, then this, then
+ * jade_denoise_image; the ranks' reports add. */
+int jade_despeckle_image(int device_id, int32_t width, int32_t height, const float* rgb, const float* variance,
+                         const jade_despeckle_params* params, float* out_rgb, float* out_variance, float* out_scale,
+                         jade_despeckle_report* report);
+
+/* Despeckle the render in progress on its device, one copy back: flush (as resolve), resolve (after jade_render_adaptive with each
+ * tile's own count), the variance, the passes; with denoise parameters the guides and the a-trous filter on the despeckled colour and
+ * variance; the tone pack (tonemap / limit as jade_render_resolve_ex).  out_rgb, out_bgr8, out_scale and report are nullable.
+ * denoise == null: out_rgb is bit for bit jade_despeckle_image on jade_render_resolve_ex's out_rgb and jade_render_guides' variance.
+ *   A sample count that gives no variance (NaN: n < 2, or n > 1024 and not a multiple of 1024) is no refusal here: it simply
+ *   establishes nothing, and every pixel above is clamped.
+ * denoise != null: out_rgb is bit for bit jade_denoise_image on that result's rgb and variance and jade_render_guides' other outputs,
+ *   and the call refuses what jade_render_denoise refuses (such a sample count included).
+ * Full frame only: tile_nranks > 1 gives JADE_ERR_UNSUPPORTED (gather, then jade_despeckle_image).  Fails as jade_render_resolve_ex
+ * does before begin or with no sample rendered.  The render's sums, counters and next step are not changed. */
+int jade_render_despeckle(jade_scene* scene, const jade_despeckle_params* params, const jade_denoise_params* denoise, int tonemap,
+                          float limit, float* out_rgb, uint8_t* out_bgr8, float* out_scale, jade_despeckle_report* report);
 
 /* ---- Thin lens: depth of field ----
  *

@@ -128,6 +128,15 @@ class GlareParams(C.Structure):  # == jade_glare_params, include/jade_bvh.h
     _fields_ = [("levels", C.c_int32), ("strength", C.c_float), ("falloff", C.c_float)]
 
 
+class DespeckleParams(C.Structure):  # == jade_despeckle_params, include/jade_bvh.h
+    _fields_ = [("iterations", C.c_int32), ("radius", C.c_int32), ("rank", C.c_int32),
+                ("gain", C.c_float), ("floor", C.c_float), ("sigmas", C.c_float)]
+
+
+class DespeckleReport(C.Structure):  # == jade_despeckle_report, include/jade_bvh.h
+    _fields_ = [("n_usable", C.c_uint64), ("n_above", C.c_uint64), ("n_established", C.c_uint64), ("n_clamped", C.c_uint64)]
+
+
 class LensParams(C.Structure):  # == jade_lens_params, include/jade_bvh.h
     _fields_ = [("aperture_radius", C.c_float), ("focus_distance", C.c_float)]
 
@@ -208,6 +217,14 @@ BVH_SYMBOLS = {
     "jade_glare_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(GlareParams), C.c_void_p]),
     "jade_render_glare": (C.c_int, [C.c_void_p, C.POINTER(GlareParams), C.POINTER(DisplayParams), C.c_void_p, C.c_void_p,
                                     C.POINTER(C.c_float)]),
+    # despeckle: defaults, caller images (device, width, height, rgb, variance or null, params, out rgb, out variance or null, out
+    # scale or null, report or null) and the render's frame (scene, params, denoise params or null, tonemap, limit, rgb, bgr8, scale,
+    # report)
+    "jade_despeckle_defaults": (None, [C.POINTER(DespeckleParams)]),
+    "jade_despeckle_image": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(DespeckleParams), C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.POINTER(DespeckleReport)]),
+    "jade_render_despeckle": (C.c_int, [C.c_void_p, C.POINTER(DespeckleParams), C.POINTER(DenoiseParams), C.c_int, C.c_float,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DespeckleReport)]),
     # the thin lens of a scene handle (scene, lens or null) / (scene, out)
     "jade_scene_set_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),
     "jade_scene_get_lens": (C.c_int, [C.c_void_p, C.POINTER(LensParams)]),

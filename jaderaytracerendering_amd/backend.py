@@ -218,6 +218,41 @@ class Backend:
         self.check(fn(int(device_id), int(w), int(h), rgb.ctypes.data, C.byref(params), out.ctypes.data))
         return out
 
+    def despeckle_defaults(self):
+        """jade_despeckle_defaults: 1 iteration, radius 1, rank 2, gain 2, floor 0, sigmas 2."""
+        p = _abi.DespeckleParams()
+        self.hip_only("jade_despeckle_defaults")(C.byref(p))
+        return p
+
+    def despeckle_image(self, rgb, variance=None, params=None, device_id=0):
+        """jade_despeckle_image: the despeckle passes (include/jade_bvh.h, "Despeckle, stated") on a caller's linear frame rgb [H, W, 3]
+        and, optionally, the variance [H, W] of each pixel's mean luminance (Scene.guides) on device `device_id`.  params None: the
+        defaults.  Returns (rgb float32 [H, W, 3], variance float32 [H, W] | None, scale float32 [H, W], the report as a dict of its
+        four counts)."""
+        fn = self.hip_only("jade_despeckle_image")
+        if params is None:
+            params = self.despeckle_defaults()
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError(f"rgb of shape {rgb.shape}, expected [H, W, 3]")
+        h, w = rgb.shape[:2]
+        if variance is not None:
+            variance = np.ascontiguousarray(variance, np.float32)
+            if variance.shape != (h, w):
+                raise ValueError(f"variance of shape {variance.shape}, expected {(h, w)}")
+        out = np.zeros((h, w, 3), np.float32)
+        out_v = np.zeros((h, w), np.float32) if variance is not None else None
+        scale = np.zeros((h, w), np.float32)
+        rep = _abi.DespeckleReport()
+        self.check(fn(int(device_id), int(w), int(h), rgb.ctypes.data, variance.ctypes.data if variance is not None else None,
+                      C.byref(params), out.ctypes.data, out_v.ctypes.data if out_v is not None else None, scale.ctypes.data, C.byref(rep)))
+        return out, out_v, scale, despeckle_report(rep)
+
+
+def despeckle_report(rep):
+    """jade_despeckle_report as a dict; reports add field by field"""
+    return {k: int(getattr(rep, k)) for k in ("n_usable", "n_above", "n_established", "n_clamped")}
+
 
 class Scene:
     """A scene resident on the backend (PathTrace.cu:1618-1698 on the reference side)."""
@@ -387,6 +422,26 @@ class Scene:
         self.backend.check(fn(self._h, C.byref(params), C.byref(display) if display is not None else None,
                               rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None, C.byref(e)))
         return rgb, bgr, e.value
+
+    def despeckle(self, params=None, denoise=None, tonemap=None, limit=1.5, want_rgb=True, want_bgr8=True):
+        """jade_render_despeckle: the render in progress, despeckled on its device (full frame only) and tone-packed.  params None: the
+        despeckle defaults.  denoise: DenoiseParams to run the guides and the a-trous filter on the despeckled colour and variance,
+        None for the despeckled frame itself.  Returns (rgb float32 [H, W, 3] | None, bgr8 uint8 [H, W, 3] | None, scale float32
+        [H, W], the report as a dict of its four counts)."""
+        fn = self._hip_only("jade_render_despeckle")
+        if self._params is None:
+            raise JadeError(_abi.JADE_ERR_INVALID, "jade_render_begin not called")
+        if params is None:
+            params = self.backend.despeckle_defaults()
+        h, w = self._params.height, self._params.width
+        rgb = np.zeros((h, w, 3), np.float32) if want_rgb else None
+        bgr = np.zeros((h, w, 3), np.uint8) if want_bgr8 else None
+        scale = np.zeros((h, w), np.float32)
+        rep = _abi.DespeckleReport()
+        self.backend.check(fn(self._h, C.byref(params), C.byref(denoise) if denoise is not None else None,
+                              _abi.TONEMAP_ACES if tonemap is None else int(tonemap), float(limit),
+                              rgb.ctypes.data if want_rgb else None, bgr.ctypes.data if want_bgr8 else None, scale.ctypes.data, C.byref(rep)))
+        return rgb, bgr, scale, despeckle_report(rep)
 
     def set_lens(self, aperture_radius, focus_distance=0.0):
         """jade_scene_set_lens: a thin lens of radius `aperture_radius` (scene units) focused at depth `focus_distance` along the

@@ -29,13 +29,7 @@
 
 #define JADE_DN_BLOCK 256
 
-// owned pixel p (tile t = p >> 8) -> image (x, y); false outside the image (edge tiles)
-static __device__ __forceinline__ bool dn_pixel_xy(const RenderConst& R, const int32_t* tile_ids, int p, int* x, int* y) {
-  const int tid = tile_ids[p >> 8], l = p & 255;
-  *x = (tid % R.tiles_x) * JADE_TILE_SIZE + (l & 15);
-  *y = (tid / R.tiles_x) * JADE_TILE_SIZE + (l >> 4);
-  return *x < R.width && *y < R.height;
-}
+// (dn_pixel_xy and dn_pack, which the despeckle pass's pack kernels call as well: jade_runtime.h)
 
 // ---------------------------------------------------------------------------------------------------------------- variance --
 
@@ -197,35 +191,6 @@ __global__ __launch_bounds__(JADE_DN_BLOCK) void k_guide_hits_mapped(DevScene S,
 
 // ------------------------------------------------------------------------------------------------------------------ filter --
 
-// One pixel's filter record from its inputs; the two pack kernels call it, so the render's path and jade_denoise_image's are the
-// same bits.  nhat = n / |n|, or 0 for the zero normal (a miss in every guide sample).  Where the float sum of squares is 0,
-// subnormal or infinite, n is first scaled by the power of two that brings its largest component into [1, 2) (exact; every other
-// normal takes the plain statements).  L.w = 1 marks an unusable pixel (jade_bvh.h: a non-finite input, a negative variance):
-// k_atrous copies it and never taps it.
-static __device__ __forceinline__ void dn_pack(float r, float g, float b, float v, float ax, float ay, float az, float nx, float ny, float nz,
-                                               float z, float4* A, float4* N, float4* L, size_t o) {
-  const bool usable = isfinite(r) && isfinite(g) && isfinite(b) && isfinite(ax) && isfinite(ay) && isfinite(az) && isfinite(nx) && isfinite(ny) &&
-                      isfinite(nz) && isfinite(z) && isfinite(v) && v >= 0.0f;
-  float hx = 0.0f, hy = 0.0f, hz = 0.0f;
-  if (usable && (nx != 0.0f || ny != 0.0f || nz != 0.0f)) {
-    float ss = nx * nx + ny * ny + nz * nz;
-    if (!(ss >= 1.17549435e-38f && ss <= 3.40282347e+38f)) {
-      const int e = -ilogbf(fmaxf(fabsf(nx), fmaxf(fabsf(ny), fabsf(nz))));
-      nx = ldexpf(nx, e);
-      ny = ldexpf(ny, e);
-      nz = ldexpf(nz, e);
-      ss = nx * nx + ny * ny + nz * nz;
-    }
-    const float len = sqrtf(ss);
-    hx = nx / len;
-    hy = ny / len;
-    hz = nz / len;
-  }
-  A[o] = make_float4(r, g, b, v);
-  N[o] = make_float4(hx, hy, hz, z);
-  L[o] = make_float4(ax, ay, az, usable ? 0.0f : 1.0f);
-}
-
 // The render's owned tiles (compact layout: rgb as k_resolve writes it, variance, guide sums) -> image layout
 __global__ __launch_bounds__(JADE_DN_BLOCK) void k_dn_pack_tiles(RenderConst R, const int32_t* tile_ids, int npx, const float* rgb, const float* var,
                                                                  const float4* acc_az, const float4* acc_n, float4* A, float4* N, float4* L) {
@@ -344,7 +309,7 @@ void jade_denoise_defaults(jade_denoise_params* p) {
   p->sigma_albedo = 0.1f;
 }
 
-static int dn_check_params(const jade_denoise_params* dp) {
+JADE_HIDDEN int dn_check_params(const jade_denoise_params* dp) {
   if (!dp) return jade_fail(JADE_ERR_INVALID, "null denoise parameters");
   if (dp->iterations < 0 || dp->iterations > 8) return jade_fail(JADE_ERR_INVALID, "iterations must be 0..8");
   if (dp->guide_spp < 1 || dp->guide_spp > 64) return jade_fail(JADE_ERR_INVALID, "guide_spp must be 1..64");
@@ -368,13 +333,13 @@ static int dn_flush(jade_scene* s) {
 }
 
 // each owned tile's sample count: its own after jade_render_adaptive, otherwise spp_done
-static std::vector<int32_t> dn_tile_counts(const jade_scene* s) {
+JADE_HIDDEN std::vector<int32_t> dn_tile_counts(const jade_scene* s) {
   if (!s->tile_n.empty()) return s->tile_n;
   return std::vector<int32_t>(s->tile_ids.size(), (int32_t)std::min<int64_t>(s->spp_done, INT32_MAX));
 }
 
 // the variance of every owned pixel into b_dn_var (compact layout)
-static int dn_variance(jade_scene* s) {
+JADE_HIDDEN int dn_variance(jade_scene* s) {
   const size_t nt = s->tile_ids.size();
   HIP_TRY(dn_alloc(s->b_dn_var, (size_t)s->ps.npx * 4));
   DevBuf b_n;
@@ -393,7 +358,7 @@ static int dn_variance(jade_scene* s) {
 // b_dn_n = {normal, 0} (compact layout).  k_trace itself walks the rays (reference walk, nearest hit) on a throw-away PathState, with
 // queue words and work counters of its own: neither the render's state nor its statistics see these rays.  The host waits once per
 // k_trace launch, for the number of mirror continuations (a sample ends after at most JADE_MAX_FULL_REFLEX_TIME + 1 launches).
-static int dn_guides(jade_scene* s, int G) {
+JADE_HIDDEN int dn_guides(jade_scene* s, int G) {
   const size_t n = (size_t)s->ps.npx;
   HIP_TRY(dn_alloc(s->b_dn_orgs, n * 16));
   HIP_TRY(dn_alloc(s->b_dn_slot, n * 16));
@@ -529,7 +494,7 @@ int jade_render_guides(jade_scene* s, int32_t guide_spp, float* out_albedo, floa
 
 // The filter on records already packed in b_dn_rec[0] (colour, variance), [2] (normal, depth), [3] (albedo): the passes, then one
 // output kernel into b_dn_rgb / b_dn_bgr (image layout).
-static int dn_filter_out(hipStream_t stream, int W, int H, const jade_denoise_params* dp, int tonemap, float limit, float* dev_rgb,
+JADE_HIDDEN int dn_filter_out(hipStream_t stream, int W, int H, const jade_denoise_params* dp, int tonemap, float limit, float* dev_rgb,
                          uint8_t* dev_bgr, float4* const* rec) {
   int cur = 0;  // the passes, ping-pong between rec[0] and rec[1]
   const DnSigma sg{dp->sigma_luminance, dp->sigma_normal, dp->sigma_depth, dp->sigma_albedo};

@@ -419,6 +419,9 @@ struct jade_scene {
   // glare (jade_glare.hip), allocated on first use and kept: the frame in image layout (glared in place), its bytes, and every level
   // of the pyramid in one allocation
   DevBuf b_gl_rgb, b_gl_bgr, b_gl_pyr;
+  // despeckle (jade_despeckle.hip), allocated on first use and kept: each pixel's scale and the report's four words (its passes run on
+  // the denoiser's records, b_dn_rec[0] and [1])
+  DevBuf b_ds_scale, b_ds_report;
   // passes (jade_shade.h PassPlanes, jade_passes.hip): the planes of a render with SM_PASSES - cleared by its jade_render_begin - and the
   // 15 resolved images in the compact tile layout, allocated on first use and kept
   DevBuf b_pass_cur, b_pass_tot, b_pass_mask, b_pass_out;
@@ -525,6 +528,53 @@ JADE_HIDDEN int ex_meter(DevBuf& b_rows, DevBuf& b_words, const float* dev_rgb, 
                          jade_meter* out);
 JADE_HIDDEN void ex_launch_pack(const float* dev_rgb, int n, const RenderConst& R, const int32_t* tile_ids, float e, const jade_display_params* p,
                                 uint8_t* dev_bgr, hipStream_t stream);
+
+// What the despeckle pass (jade_despeckle.hip) takes from the denoiser (jade_denoise.hip) rather than copying it.  On the host: the check of
+// denoise parameters, each owned tile's sample count, the variance of every owned pixel into b_dn_var and the guide sums into b_dn_az /
+// b_dn_n (compact layout), and the a-trous passes + output kernel on packed records (rec[0] colour + variance, rec[1] its ping-pong
+// partner, rec[2] normal + depth, rec[3] albedo; with iterations = 0 the output kernel alone, which reads rec[0] only).
+JADE_HIDDEN int dn_check_params(const jade_denoise_params* dp);
+JADE_HIDDEN std::vector<int32_t> dn_tile_counts(const jade_scene* s);
+JADE_HIDDEN int dn_variance(jade_scene* s);
+JADE_HIDDEN int dn_guides(jade_scene* s, int G);
+JADE_HIDDEN int dn_filter_out(hipStream_t stream, int W, int H, const jade_denoise_params* dp, int tonemap, float limit, float* dev_rgb, uint8_t* dev_bgr,
+                              float4* const* rec);
+// ... and on the device, for the pack kernels of both files:
+// owned pixel p (tile t = p >> 8) -> image (x, y); false outside the image (edge tiles)
+static __device__ __forceinline__ bool dn_pixel_xy(const RenderConst& R, const int32_t* tile_ids, int p, int* x, int* y) {
+  const int tid = tile_ids[p >> 8], l = p & 255;
+  *x = (tid % R.tiles_x) * JADE_TILE_SIZE + (l & 15);
+  *y = (tid / R.tiles_x) * JADE_TILE_SIZE + (l >> 4);
+  return *x < R.width && *y < R.height;
+}
+// One pixel's filter record from its inputs; every pack kernel calls it, so the render's paths and jade_denoise_image's are the
+// same bits.  nhat = n / |n|, or 0 for the zero normal (a miss in every guide sample).  Where the float sum of squares is 0,
+// subnormal or infinite, n is first scaled by the power of two that brings its largest component into [1, 2) (exact; every other
+// normal takes the plain statements).  L.w = 1 marks an unusable pixel (jade_bvh.h: a non-finite input, a negative variance):
+// k_atrous copies it and never taps it.
+static __device__ __forceinline__ void dn_pack(float r, float g, float b, float v, float ax, float ay, float az, float nx, float ny, float nz,
+                                               float z, float4* A, float4* N, float4* L, size_t o) {
+  const bool usable = isfinite(r) && isfinite(g) && isfinite(b) && isfinite(ax) && isfinite(ay) && isfinite(az) && isfinite(nx) && isfinite(ny) &&
+                      isfinite(nz) && isfinite(z) && isfinite(v) && v >= 0.0f;
+  float hx = 0.0f, hy = 0.0f, hz = 0.0f;
+  if (usable && (nx != 0.0f || ny != 0.0f || nz != 0.0f)) {
+    float ss = nx * nx + ny * ny + nz * nz;
+    if (!(ss >= 1.17549435e-38f && ss <= 3.40282347e+38f)) {
+      const int e = -ilogbf(fmaxf(fabsf(nx), fmaxf(fabsf(ny), fabsf(nz))));
+      nx = ldexpf(nx, e);
+      ny = ldexpf(ny, e);
+      nz = ldexpf(nz, e);
+      ss = nx * nx + ny * ny + nz * nz;
+    }
+    const float len = sqrtf(ss);
+    hx = nx / len;
+    hy = ny / len;
+    hz = nz / len;
+  }
+  A[o] = make_float4(r, g, b, v);
+  N[o] = make_float4(hx, hy, hz, z);
+  L[o] = make_float4(ax, ay, az, usable ? 0.0f : 1.0f);
+}
 
 // Visits the owned tiles of a W x H image in owned order: f(t, x0, y0, ww, hh) - owned tile t (its pixels are t*256 + ly*16 + lx in
 // the compact layout) covers ww x hh image pixels from (x0, y0).

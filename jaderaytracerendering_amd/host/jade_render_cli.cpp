@@ -40,6 +40,10 @@ struct Api {
   void (*display_defaults)(jade_display_params*) = nullptr;
   int (*render_resolve_exposed)(jade_scene*, const jade_display_params*, float*, uint8_t*, float*, jade_meter*) = nullptr;
   int (*expose_image)(int, int32_t, int32_t, const float*, const jade_display_params*, uint8_t*, float*, jade_meter*) = nullptr;
+  // ... and only for --despeckle
+  void (*despeckle_defaults)(jade_despeckle_params*) = nullptr;
+  int (*render_despeckle)(jade_scene*, const jade_despeckle_params*, const jade_denoise_params*, int, float, float*, uint8_t*, float*,
+                          jade_despeckle_report*) = nullptr;
   // ... and only for --glare
   void (*glare_defaults)(jade_glare_params*) = nullptr;
   int (*glare_image)(int, int32_t, int32_t, const float*, const jade_glare_params*, float*) = nullptr;
@@ -114,6 +118,8 @@ static void usage() {
           "                   [--normal-map K=FILE|bumps[:SIZE[:N]][@PROJECTION][:STRENGTH]]...\n"
           "                   [--adaptive REL [--min-spp N] [--error-floor F]] [--denoise] [--guides PREFIX]\n"
           "                   [--glare STRENGTH [--glare-levels N] [--glare-falloff F]]\n"
+          "                   [--despeckle [--despeckle-sigmas Z] [--despeckle-gain G] [--despeckle-rank K] [--despeckle-radius R]\n"
+          "                    [--despeckle-iterations N] [--despeckle-map FILE.pfm]]\n"
           "                   [--exposure EV|auto [--key K] [--exposure-window LO,HI]] [--histogram FILE]\n"
           "                   [--aperture A (--focus D | --focus-at PX,PY)]\n"
           "  --aperture A: a thin lens of radius A >= 0 (scene units) instead of the pinhole: depth of field (HIP backend only; NOT the\n"
@@ -152,6 +158,11 @@ static void usage() {
           "  --glare STRENGTH: a share STRENGTH in [0, 1] of every pixel's light is scattered over a pyramid of N blurs (1..12, default 6),\n"
           "                    level k weighing F^(k-1) (default 0.5), and added back (HIP backend only; include/jade_bvh.h).  The order is\n"
           "                    resolve, --denoise, glare, --exposure / tone; the .pfm output is the glared linear frame\n"
+          "  --despeckle: a pixel whose luminance stands above G times (default 2) the K-th brightest (1..4, default 2) of its neighbours within\n"
+          "               R pixels (1..3, default 1) is scaled down to that bound, unless the variance of its mean puts the excess Z standard\n"
+          "               errors (default 2) above it; N passes (0..4, default 1) (HIP backend only; include/jade_bvh.h).  The order is resolve,\n"
+          "               despeckle, --denoise, --glare, --exposure / tone.  --despeckle-map FILE.pfm: each pixel's scale (1 = untouched).\n"
+          "               The counts of the report go to stderr\n"
           "  --exposure EV: the frame is multiplied by 2^EV before the tone curve (HIP backend only; the .pfm output is never scaled)\n"
           "  --exposure auto: the multiplier comes from the frame's luminance histogram (include/jade_bvh.h): the log-average luminance of\n"
           "                   the pixels between the LO and HI quantiles (default 0.05,0.95) goes to K (default 0.18)\n"
@@ -191,6 +202,9 @@ int main(int argc, char** argv) {
   std::string histogram;
   bool use_glare = false, have_glare_levels = false, have_glare_falloff = false;
   double glare_strength = 0.0, glare_levels = 6, glare_falloff = 0.5;
+  bool use_despeckle = false, have_despeckle_option = false;
+  double ds_sigmas = 2.0, ds_gain = 2.0, ds_rank = 2, ds_radius = 1, ds_iterations = 1;
+  std::string despeckle_map;
   bool use_aperture = false, have_focus = false, have_focus_at = false;
   double aperture = 0.0, focus = 0.0, focus_px = 0, focus_py = 0;
   bool one_light = false;
@@ -366,6 +380,13 @@ int main(int argc, char** argv) {
       have_window = true;
     }
     else if (a == "--histogram") histogram = need("--histogram");
+    else if (a == "--despeckle") use_despeckle = true;
+    else if (a == "--despeckle-sigmas") { ds_sigmas = number("--despeckle-sigmas", need("--despeckle-sigmas")); have_despeckle_option = true; }
+    else if (a == "--despeckle-gain") { ds_gain = number("--despeckle-gain", need("--despeckle-gain")); have_despeckle_option = true; }
+    else if (a == "--despeckle-rank") { ds_rank = number("--despeckle-rank", need("--despeckle-rank")); have_despeckle_option = true; }
+    else if (a == "--despeckle-radius") { ds_radius = number("--despeckle-radius", need("--despeckle-radius")); have_despeckle_option = true; }
+    else if (a == "--despeckle-iterations") { ds_iterations = number("--despeckle-iterations", need("--despeckle-iterations")); have_despeckle_option = true; }
+    else if (a == "--despeckle-map") { despeckle_map = need("--despeckle-map"); have_despeckle_option = true; }
     else if (a == "--glare") { glare_strength = number("--glare", need("--glare")); use_glare = true; }
     else if (a == "--glare-levels") { glare_levels = number("--glare-levels", need("--glare-levels")); have_glare_levels = true; }
     else if (a == "--glare-falloff") { glare_falloff = number("--glare-falloff", need("--glare-falloff")); have_glare_falloff = true; }
@@ -395,6 +416,12 @@ int main(int argc, char** argv) {
   if (!(key > 0.0) || !std::isfinite((float)key) || !((float)key > 0.0f)) { fprintf(stderr, "--key must be > 0\n"); return 2; }
   if (!(win_lo >= 0.0 && (float)win_lo < (float)win_hi && win_hi <= 1.0)) { fprintf(stderr, "--exposure-window needs 0 <= LO < HI <= 1\n"); return 2; }
   if ((have_glare_levels || have_glare_falloff) && !use_glare) { fprintf(stderr, "--glare-levels and --glare-falloff belong to --glare\n"); return 2; }
+  if (have_despeckle_option && !use_despeckle) { fprintf(stderr, "--despeckle-sigmas, -gain, -rank, -radius, -iterations and -map belong to --despeckle\n"); return 2; }
+  if (!((float)ds_sigmas >= 0.0f) || !std::isfinite((float)ds_sigmas)) { fprintf(stderr, "--despeckle-sigmas must be >= 0\n"); return 2; }
+  if (!((float)ds_gain >= 1.0f) || !std::isfinite((float)ds_gain)) { fprintf(stderr, "--despeckle-gain must be >= 1\n"); return 2; }
+  if (!(ds_rank >= 1 && ds_rank <= 4 && ds_rank == (int)ds_rank)) { fprintf(stderr, "--despeckle-rank must be a whole number 1 .. 4\n"); return 2; }
+  if (!(ds_radius >= 1 && ds_radius <= 3 && ds_radius == (int)ds_radius)) { fprintf(stderr, "--despeckle-radius must be a whole number 1 .. 3\n"); return 2; }
+  if (!(ds_iterations >= 0 && ds_iterations <= 4 && ds_iterations == (int)ds_iterations)) { fprintf(stderr, "--despeckle-iterations must be a whole number 0 .. 4\n"); return 2; }
   if (!(glare_strength >= 0.0 && glare_strength <= 1.0)) { fprintf(stderr, "--glare must be within 0 .. 1\n"); return 2; }
   if (!(glare_levels >= 1 && glare_levels <= 12 && glare_levels == (int)glare_levels)) { fprintf(stderr, "--glare-levels must be a whole number 1 .. 12\n"); return 2; }
   if (!((float)glare_falloff > 0.0f) || !std::isfinite((float)glare_falloff)) { fprintf(stderr, "--glare-falloff must be > 0\n"); return 2; }
@@ -528,6 +555,14 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (use_despeckle) {
+    *(void**)(&api.despeckle_defaults) = dlsym(api.h, "jade_despeckle_defaults");
+    *(void**)(&api.render_despeckle) = dlsym(api.h, "jade_render_despeckle");
+    if (!api.despeckle_defaults || !api.render_despeckle) {
+      fprintf(stderr, "--despeckle needs the HIP backend: %s has no jade_render_despeckle\n", backend.c_str());
+      return 2;
+    }
+  }
   if (use_glare) {
     *(void**)(&api.glare_defaults) = dlsym(api.h, "jade_glare_defaults");
     *(void**)(&api.glare_image) = dlsym(api.h, "jade_glare_image");
@@ -614,15 +649,16 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
-  // (a denoised and glared frame gets its bytes from jade_expose_image even without --exposure)
-  const bool need_display = use_exposure || !histogram.empty() || (use_glare && use_denoise);
+  // (a denoised or despeckled frame is on the host when the glare comes: it gets its bytes from jade_expose_image even without --exposure)
+  const bool host_frame = use_denoise || use_despeckle;
+  const bool need_display = use_exposure || !histogram.empty() || (use_glare && host_frame);
   if (need_display) {
     *(void**)(&api.display_defaults) = dlsym(api.h, "jade_display_defaults");
     *(void**)(&api.render_resolve_exposed) = dlsym(api.h, "jade_render_resolve_exposed");
     *(void**)(&api.expose_image) = dlsym(api.h, "jade_expose_image");
     if (!api.display_defaults || !api.render_resolve_exposed || !api.expose_image) {
       fprintf(stderr, "%s needs the HIP backend: %s has no jade_render_resolve_exposed / jade_expose_image\n",
-              use_exposure ? "--exposure" : !histogram.empty() ? "--histogram" : "--glare with --denoise", backend.c_str());
+              use_exposure ? "--exposure" : !histogram.empty() ? "--histogram" : "--glare with --denoise / --despeckle", backend.c_str());
       return 2;
     }
   }
@@ -733,7 +769,31 @@ int main(int argc, char** argv) {
       printf("wrote %s\n", path.c_str());
     }
   }
-  if (use_denoise) {
+  if (use_despeckle) {
+    // resolve, the passes and - with --denoise - the filter on the despeckled colour and variance, all on the render's device
+    jade_despeckle_params ds;
+    api.despeckle_defaults(&ds);
+    ds.sigmas = (float)ds_sigmas;
+    ds.gain = (float)ds_gain;
+    ds.rank = (int32_t)ds_rank;
+    ds.radius = (int32_t)ds_radius;
+    ds.iterations = (int32_t)ds_iterations;
+    jade_denoise_params dn;
+    if (use_denoise) api.denoise_defaults(&dn);
+    jade_despeckle_report rep;
+    memset(&rep, 0, sizeof rep);
+    std::vector<float> scale(despeckle_map.empty() ? 0 : (size_t)rp.width * rp.height);
+    if (api.render_despeckle(dev, &ds, use_denoise ? &dn : nullptr, JADE_TONEMAP_ACES, 0.0f, rgb.data(), bgr.data(),
+                             scale.empty() ? nullptr : scale.data(), &rep) != JADE_OK) { fprintf(stderr, "despeckle: %s\n", api.last_error()); return 1; }
+    fprintf(stderr, "despeckle: %llu usable pixels, %llu above, %llu established, %llu clamped\n", (unsigned long long)rep.n_usable,
+            (unsigned long long)rep.n_above, (unsigned long long)rep.n_established, (unsigned long long)rep.n_clamped);
+    printf("despeckled: %d passes, radius %d, rank %d, gain %.9g, sigmas %.9g\n", ds.iterations, ds.radius, ds.rank, ds.gain, ds.sigmas);
+    if (use_denoise) printf("denoised: %d a-trous passes, %d guide samples\n", dn.iterations, dn.guide_spp);
+    if (!despeckle_map.empty()) {
+      if (!write_pfm1(despeckle_map, scale.data(), rp.width, rp.height)) { fprintf(stderr, "cannot write %s\n", despeckle_map.c_str()); return 1; }
+      printf("wrote %s\n", despeckle_map.c_str());
+    }
+  } else if (use_denoise) {
     jade_denoise_params dp;
     api.denoise_defaults(&dp);
     if (api.render_denoise(dev, &dp, JADE_TONEMAP_ACES, 0.0f, rgb.data(), bgr.data()) != JADE_OK) { fprintf(stderr, "denoise: %s\n", api.last_error()); return 1; }
@@ -761,8 +821,8 @@ int main(int argc, char** argv) {
     gp.falloff = (float)glare_falloff;
     int rc;
     float e = 1.0f;
-    if (use_denoise) {
-      // a denoised frame is on the host by now; its bytes come from jade_expose_image below
+    if (host_frame) {
+      // a denoised or despeckled frame is on the host by now; its bytes come from jade_expose_image below
       rc = api.glare_image(device, rp.width, rp.height, rgb.data(), &gp, rgb.data());
     } else if (!histogram.empty()) {
       // the histogram wants the meter, which only jade_expose_image hands back: the glared frame alone here, bytes and meter below
@@ -780,7 +840,7 @@ int main(int argc, char** argv) {
     // the bytes again, from exposure x frame; the linear frame (a .pfm output) stays as it is
     float e = 0.0f;
     jade_meter m;
-    const int rc = use_denoise || use_glare ? api.expose_image(device, rp.width, rp.height, rgb.data(), &dp, bgr.data(), &e, &m)
+    const int rc = host_frame || use_glare ? api.expose_image(device, rp.width, rp.height, rgb.data(), &dp, bgr.data(), &e, &m)
                                : api.render_resolve_exposed(dev, &dp, nullptr, bgr.data(), &e, &m);
     if (rc != JADE_OK) { fprintf(stderr, "exposure: %s\n", api.last_error()); return 1; }
     if (use_exposure || !histogram.empty())

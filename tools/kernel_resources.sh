@@ -1,11 +1,11 @@
 #!/bin/bash
 # Per-kernel register / LDS / scratch / occupancy of the HIP module as hipcc reports them (-Rpass-analysis=kernel-resource-usage).
-# usage: tools/kernel_resources.sh [extra -D flags...]
+# usage: tools/kernel_resources.sh [extra -D flags...]      (JADE_RESOURCE_FILES="jade_despeckle ..." lists those files only)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 T=$(mktemp -d)
 trap 'rm -rf "$T"' EXIT
-for f in jade_hip jade_bvh jade_adaptive jade_denoise jade_expose jade_glare jade_passes; do
+for f in ${JADE_RESOURCE_FILES:-jade_hip jade_bvh jade_adaptive jade_denoise jade_expose jade_glare jade_passes jade_despeckle}; do
 /opt/rocm/bin/hipcc "$@" -O3 -fno-slp-vectorize -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -mfma -I"$R/include" -I"$R/jaderaytracerendering_amd/csrc" \
   -c "$R/jaderaytracerendering_amd/csrc/$f.hip" -o "$T/x.o" -Rpass-analysis=kernel-resource-usage 2>&1 |
@@ -24,10 +24,13 @@ for k, v in rows.items():
     m = re.match(r"^_Z\d+(k_[a-z_0-9]+?)(?=\d|P|$)", k)
     t = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILb([01])EE", k)  # a kernel template over one bool: k_name<0> / k_name<1>
     s = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILj(\d+)E", k)  # a kernel template over the ShadeMode mask (jade_runtime.h): k_shade_mode<COSINE|MIS>
-    if not m and not t and not s:
+    n = re.match(r"^_Z\d+(k_[a-z_0-9]+)ILi(\d+)E", k)  # a kernel template over one int: k_despeckle<2>
+    if not m and not t and not s and not n:
         continue
     bits = ("ENVIS", "LENS", "SHUTTER", "LIGHTS", "COSINE", "MIS", "ENVMIX", "PASSES", "BRANCH", "SMOOTH", "TEX", "NMAP")
-    if s:
+    if n:
+        name = "%s<%s>" % (n.group(1), n.group(2))
+    elif s:
         name = "%s<%s>" % (s.group(1), "|".join(b for i, b in enumerate(bits) if int(s.group(2)) >> i & 1) or "0")
     else:
         name = "%s<%s>" % (t.group(1), t.group(2)) if t else m.group(1)
